@@ -12,13 +12,21 @@ Adam step.  Weak scaling: per-GPU batch fixed; `value` = images processed by all
 EXACTLY --steps steps between two barrier + synchronize pairs.
 
 One JSON line on rank 0:
-  * `step_ms`     -- HIP-event duration of every timed step (median / p10 / p90), next to the wall-clock `ms_per_step`;
+  * `step_ms`     -- HIP-event duration of every timed step (median / p10 / p90), next to the wall-clock `ms_per_step`.
+A plain run stops there: set up, warm up, time the steps, print the line.  `--full` adds the legs below (each can still be left
+out with its --no-* option; `sustained` and `roofline` are then null):
   * `sustained`   -- the same step repeated for ~2.5 s after the timed region (not part of `value`): a 20-step region lasts
                      a quarter of a second, too short for a sampling monitor to see the GPU busy or for the clock to settle;
   * `roofline`    -- dominant conv kernel symbol, HIP-event timed on the launch stream in a separate single-stream leg;
   * `cpu_baseline`-- the CPU oracle timed on the host cores (N=1 only);
   * `also`        -- short legs of BASELINE configs 3 and 5 (bf16 storage: adversarial iteration 8+8 x 512^2; r50 at 768^2),
                      each with its own ms_per_step and dominant-kernel roofline (N=1 only; informational).
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step handed back, before anything else runs on the device, as
+DIR/<name>.npy (float32; integer results as float64): the step's losses and its logits (the validation step: its confusion
+matrix too).  Arrays of more than DUMP_SAMPLE elements are replaced by a fixed, seeded sample (dump_sample).  Inputs and initial
+weights are seeded, and the last timed step starts from that seeded state (timed_region's restart_last), so two runs with the
+same arguments compute the same outputs and two builds can be compared array for array.
 """
 import argparse
 import json
@@ -248,6 +256,7 @@ def build_leg(workload, encoder, dtype, batch, size, classes, dev, rank, world, 
                 trainer.d_grad_reducer = GradAllReducer          # its allreduce_now(): one collective over D's gradient arena
     opt = FusedAdam(model.parameters(), lr=1e-4)
     x, y = synthetic(batch, size, size, classes, seed=100 * rank, device=dev)
+    last = {}                      # the tensors the latest step handed back, detached (--dump-outputs)
     if workload == "inference":
         # validate()'s inner loop (train.py:398-408): eval forward + CE + metrics, BatchNorm folded into the convs
         model.eval()
@@ -257,18 +266,76 @@ def build_leg(workload, encoder, dtype, batch, size, classes, dev, rank, world, 
             with torch.no_grad():
                 out = model(x)
                 loss = trainer.criterion(out, y)
-                confusion_matrix(out, y, classes)
+                cm = confusion_matrix(out, y, classes)
+            last["loss"], last["logits"], last["confusion_matrix"] = loss, out, cm
             return loss
     elif workload == "adversarial":
         xt, _ = synthetic(batch, size, size, classes, seed=100 * rank + 2, device=dev)
         trainer.discriminator_optimizer = FusedAdam(trainer.discriminator.parameters(), lr=1e-4)
 
         def step():
-            return trainer.adversarial_step(x, y, xt, opt, update_metrics=False)[3]
+            r = trainer.adversarial_step(x, y, xt, opt, update_metrics=False)
+            last["seg_loss"], last["d_loss"], last["adv_loss"], last["loss"] = (t.detach() for t in r)
+            return r[3]
     else:
         def step():
-            return trainer.train_step(x, y, opt)[0]
+            loss, out = trainer.train_step(x, y, opt)
+            last["loss"], last["logits"] = loss.detach(), out.detach()
+            return loss
+    # the seeded state every training step reads and changes: weights, BatchNorm running statistics and counters of each network,
+    # and the optimizers' moments and step counts (zero: FusedAdam binds its flat buffers at its first step)
+    nets = [model] + ([trainer.discriminator] if workload == "adversarial" else [])
+    opts = [opt] + ([trainer.discriminator_optimizer] if workload == "adversarial" else [])
+    for n in nets:
+        n.ensure_arena()                     # the discriminator's is built at its first forward otherwise (after .to(device))
+    held = lambda: [t for n in nets for t in (n._arena, n._buf_arena, n._nbt)]
+    start = [(t, t.clone()) for t in held()]
+
+    def restart():
+        """Back to the seeded starting state, in place on the current stream (the step's own stream)."""
+        if any(t is not cur for (t, _), cur in zip(start, held())):
+            raise RuntimeError("bench.py: a network rebuilt its arenas after build_leg; the starting state no longer applies")
+        for t, t0 in start:
+            t.copy_(t0)
+        for o in opts:
+            for fl in o._flat.values():      # every parameter's exp_avg / exp_avg_sq / step is a view of these
+                fl["m"].zero_()
+                fl["v"].zero_()
+                fl["step"].zero_()
+    step.outputs = last
+    step.restart = restart
     return step, model, trainer
+
+
+DUMP_SAMPLE = 1 << 22              # elements kept of a larger array (16 MB of float32)
+DUMP_SEED = 1234
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_sample(t):
+    """Flat float32 (integers: float64) copy of `t` on the host; more than DUMP_SAMPLE elements -> the elements at DUMP_SAMPLE
+    flat indices drawn with DUMP_SEED and sorted (the same indices for the same element count, on every run and build)."""
+    flat = t.detach().reshape(-1)
+    flat = flat.float() if flat.is_floating_point() else flat.double()
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def dump_outputs(dirname, step):
+    """DIR/<name>.npy for every tensor the last step handed back.  Returns {name: shape written}."""
+    import numpy as np
+    arrays = dict(step.outputs)
+    out = {name: (dump_sample(t) if t.dim() else t.detach().float().cpu().numpy()) for name, t in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 # every convolution kernel symbol of the library, classed EXPLICITLY by the matrix pipe it runs on (ADVICE r04: a heuristic on the
@@ -305,9 +372,13 @@ def percentile(v, q):
     return v[min(len(v) - 1, max(0, int(round(q * (len(v) - 1)))))]
 
 
-def timed_region(step, steps, warmup, world, dev, rehearse):
+def timed_region(step, steps, warmup, world, dev, rehearse, restart_last=False):
     """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize pairs.  Returns (max-over-ranks wall
-    seconds, per-step HIP-event milliseconds, last loss)."""
+    seconds, per-step HIP-event milliseconds, last loss).
+    restart_last: the last timed step starts from the seeded starting state (step.restart: a few in-place copies and fills on the
+    stream, between the last two steps' event pairs), so that what it computes is the same on every run.  The weight gradients
+    accumulate with atomics: two runs' weights differ in their last bits after one step, and Adam's normalised updates widen
+    that with every further step, far beyond rounding in the logits after a dozen steps."""
     for _ in range(warmup):
         step()
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
@@ -316,7 +387,9 @@ def timed_region(step, steps, warmup, world, dev, rehearse):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for a, b in evs:
+    for i, (a, b) in enumerate(evs):
+        if restart_last and i == steps - 1:
+            step.restart()
         a.record()
         loss = step()
         b.record()
@@ -501,11 +574,15 @@ def also_leg(name, workload, encoder, dtype, batch, size, classes, dev, steps=10
     return out
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the sustained, roofline, cpu_baseline and also legs (each can be left out "
+                         "with its --no-* option); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--encoder", default="resnet18")
     ap.add_argument("--batch", type=int, default=8, help="per-GPU batch")
     ap.add_argument("--size", type=int, default=512)
@@ -514,14 +591,18 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the short cfg 3 / cfg 5 legs")
     ap.add_argument("--no-sustain", action="store_true", help="skip the ~2.5 s sustained leg after the timed region")
-    ap.add_argument("--layer-table", action="store_true", help="print TFLOP/s per conv shape (stderr)")
+    ap.add_argument("--layer-table", action="store_true", help="print TFLOP/s per conv shape (stderr; roofline leg of --full)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="fp32 = BASELINE configs[1] (headline); bf16 = bf16 storage / MFMA with fp32 master (configs 3, 5), "
                          "informational")
     ap.add_argument("--workload", default="segmentation", choices=["segmentation", "adversarial", "inference"],
                     help="segmentation = BASELINE configs[1] (headline); adversarial = configs[2]'s iteration "
                          "(adversarial_trainer.py:85-114) in fp32, reported for information")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -561,11 +642,14 @@ def main():
                 and args.batch == 8)
     step, model, trainer = build_leg(args.workload, args.encoder, args.dtype, args.batch, args.size, args.classes, dev, rank,
                                      world, rehearse)
-    dt, ev_ms, loss = timed_region(step, args.steps, args.warmup, world, dev, rehearse)
+    dt, ev_ms, loss = timed_region(step, args.steps, args.warmup, world, dev, rehearse, restart_last=True)
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step)     # before any later step overwrites the buffers
+        print(f"bench.py: wrote {dumped} to {args.dump_outputs}", file=sys.stderr)
 
     sustained = None
-    if not args.no_sustain and world == 1:
+    if args.full and not args.no_sustain and world == 1:
         # the timed region is a fraction of a second: keep stepping (outside `value`) so that a sampling monitor sees the GPU
         # busy and the rate is also known with the clock settled
         per = dt / args.steps
@@ -581,7 +665,8 @@ def main():
 
     roofline = None
     store = dist.distributed_c10d._get_default_store() if (world > 1 and dist.is_initialized()) else None
-    if not args.no_roofline and rank == 0:
+    run_roofline = args.full and not args.no_roofline
+    if run_roofline and rank == 0:
         # only rank 0 runs this leg.  The other ranks wait on the HOST (a key of the rendezvous store), not inside a collective: an
         # NCCL barrier would park a spinning kernel on seven GPUs for the seconds this takes
         tag = "cfg3" if args.workload == "adversarial" else ("cfg5" if args.encoder == "resnet50" else "fp32")
@@ -590,7 +675,7 @@ def main():
         finally:
             if store is not None:
                 store.set("udaseg_bench_roofline_done", "1")
-    elif store is not None and not args.no_roofline:
+    elif store is not None and run_roofline:
         import datetime
         store.wait(["udaseg_bench_roofline_done"], datetime.timedelta(seconds=600))
     if world > 1:
@@ -630,9 +715,9 @@ def main():
             "sustained": sustained,
             "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.encoder, args.classes, args.size)
-        if world == 1 and headline and not args.no_also and not rehearse:
+        if args.full and world == 1 and headline and not args.no_also and not rehearse:
             del step, model, trainer
             torch.cuda.empty_cache()
             also = [

@@ -64,7 +64,7 @@ def test_bench_n_gt_1_control_flow_four_ranks_one_gpu():
     _lib.require_gpu()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", UDASEG_BENCH_SHARE_GPU="1", UDASEG_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1"]
+           "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

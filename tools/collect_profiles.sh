@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-also --no-sustain"
-python3 $ROOT/bench.py --steps 30 --warmup 10 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err || exit 1
+python3 $ROOT/bench.py --full --steps 30 --warmup 10 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err || exit 1
 echo "bench done"
 UDASEG_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_serial -- $BENCH > $OUT/${TAG}_prof_serial.log 2>&1 || exit 1
 cp $(find $OUT/${TAG}_prof_serial -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_kernel_stats_serial.csv

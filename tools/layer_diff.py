@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Compare two `bench.py --layer-table` stderr dumps layer by layer:  tools/layer_diff.py OLD.err NEW.err [min_ms]"""
+"""Compare two `bench.py --full --layer-table` stderr dumps layer by layer:  tools/layer_diff.py OLD.err NEW.err [min_ms]"""
 import re
 import sys
 

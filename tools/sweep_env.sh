@@ -7,10 +7,10 @@ for v in $vals; do for leg in $legs; do
     3) a="--dtype bf16 --encoder resnet18 --size 512 --workload adversarial";;
     5) a="--dtype bf16 --encoder resnet50 --size 768";;
   esac
-  env $var=$v timeout -k 10 240 python bench.py $a --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-sustain > gpurun_out/sweep_tmp.json 2> gpurun_out/sweep_err.log || exit 1
-  python - "$var=$v" "$leg" >> $out <<'PY'
+  env $var=$v timeout -k 10 240 python bench.py --full $a --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-sustain > $out.tmp.json 2> $out.err.log || exit 1
+  python - "$var=$v" "$leg" "$out.tmp.json" >> $out <<'PY'
 import json, sys
-d = json.loads(open("gpurun_out/sweep_tmp.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])
 ts = d["roofline"].get("time_split", {})
 bn = ts.get("batchnorm_passes", {})
 ck = d["roofline"]["all_conv_kernels"]["by_kernel"]
