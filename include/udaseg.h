@@ -594,6 +594,30 @@ int udaseg_add_i64(int64_t* p, int64_t count, int64_t value, void* stream);
 int udaseg_scale_f32(const float* x, float* y, int64_t count, float alpha, void* stream); /* y = alpha*x: gradient reversal,
                                                                                          * src/models/uda.py:99-111 */
 
+/* ---- prediction: src/models/predict.py -- predict_batch (:113-130, argmax of the logits), predict_mask (:70-111,
+ *      (sigmoid(logits) > 0.5).float()), and predict_large: one frame of any size through the model as a grid of tiles,
+ *      blended back with a window (no reference counterpart; the reference resizes the frame to the model size).
+ *      Tile grid of a frame axis of length L, tile t, stride s: n = 1 if L <= t else ceil((L - t) / s) + 1 tiles with
+ *      origins max(0, min(i*s, L - t)); tiles numbered raster, row-major (k = i*cols + j).  A call covers the tiles
+ *      [first, first + tiles).  views: bitmask of the D4 codes (prepare_batch's convention) taken per tile, in ascending code
+ *      order; odd codes (transposes) need th == tw.  Tile sides are multiples of 32; classes 1..32; ldc, ldp multiples of 4. */
+/* image uint8 [h][w][3] -> out [tiles*V][th][tw][cpad] (fp32, or bf16 when out_bf16; padding lanes 0): crop, numpy "reflect"
+ * padding outside the frame, D4 view, A.Normalize with the arithmetic of udaseg_prepare_batch_u8 (host mean255 / inv_std255). */
+int udaseg_predict_gather_u8(const uint8_t* image, int h, int w, int th, int tw, int rows, int cols, int sy, int sx, int first,
+                             int tiles, int views, const float* mean255, const float* inv_std255, void* out, int cpad,
+                             int out_bf16, void* stream);
+/* logits fp32 [tiles*V][th][tw][ldc] (that gather's order) -> for every frame pixel covered by the call's tiles, in tile
+ * order: acc[p][0..classes) += win_y[ty] * win_x[tx] * sum over views of softmax(logits of the view's pixel that holds it),
+ * wsum[p] += win_y[ty] * win_x[tx] * V.  acc [h*w][ldp], wsum [h*w]; no atomics, bit-identical for any split into calls. */
+int udaseg_predict_blend(const float* logits, int ldc, int h, int w, int th, int tw, int rows, int cols, int sy, int sx, int first,
+                         int tiles, int views, int classes, const float* win_y, const float* win_x, float* acc, int ldp,
+                         float* wsum, void* stream);
+/* labels[p] = argmax over classes of probs[p] (first maximum on ties).  With wsum (may be NULL): first probs[p] /= wsum[p]
+ * in place and the padding lanes [classes, ldc) are set to 0. */
+int udaseg_predict_finish(float* probs, const float* wsum, int64_t pixels, int classes, int ldc, int64_t* labels, void* stream);
+/* logits fp32 padded NHWC [n][hw][ldc] -> out fp32 NCHW [n][classes][hw] = (sigmoid(logit) > 0.5) ? 1 : 0 */
+int udaseg_predict_threshold(const float* logits, int n, int hw, int classes, int ldc, float* out, void* stream);
+
 /* ---- live kernel timing for bench.py's roofline leg: HIP events bracket every launch of the conv
  *      kernel families on the launch stream while enabled. ---- */
 int udaseg_prof_enable(int on);

@@ -1,0 +1,297 @@
+"""Prediction on the device (predict.py / csrc/predict.hip) against numpy oracles: the tile gather bit-exact (crop, reflect
+padding, D4 view, A.Normalize), the blend + finish against a float64 oracle on synthetic logits, a D4 round trip through the
+real gather, determinism across batch sizes, the one-tile identity, an end-to-end run against the CPU model oracle, the
+metrics hand-over, and predict_batch / predict_mask against the model's own logits."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def P():
+    from uda_aerial_semantic_segmentation_research_amd import _lib, predict
+    _lib.require_gpu()
+    return predict
+
+
+def _frame(h, w, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def _tile_oracle(P, img, g, k, code):
+    """numpy: tile k of grid g under D4 view ``code``, normalised (oracle.data_ref) -> fp32 [th, tw, 3]."""
+    from oracle.data_ref import normalize
+    h, w = img.shape[:2]
+    oy, ox = g.oy[k // g.cols], g.ox[k % g.cols]
+    pad = np.pad(img, ((0, max(0, oy + g.th - h)), (0, max(0, ox + g.tw - w)), (0, 0)), mode="reflect")
+    tile = pad[oy:oy + g.th, ox:ox + g.tw]
+    yy, xx = np.meshgrid(np.arange(g.th), np.arange(g.tw), indexing="ij")
+    ty, tx = P.apply_view(code, yy, xx, g.th, g.tw)
+    return normalize(np.ascontiguousarray(tile[ty, tx]))
+
+
+def _gather(P, img_dev, g, first, tiles, codes, dtype=torch.float32, cpad=None):
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    from uda_aerial_semantic_segmentation_research_amd.data import normalize_constants
+    cpad = cpad or (8 if dtype == torch.bfloat16 else 4)
+    out = torch.full((tiles * len(codes), g.th, g.tw, cpad), 7.0, dtype=dtype, device="cuda")     # padding lanes must be written
+    m, r = normalize_constants()
+    K.predict_gather_u8(img_dev, P._grid_args(g), first, tiles, P.view_mask(codes), m, r, out)
+    return out
+
+
+@pytest.mark.parametrize("h,w,tile,codes", [
+    (300, 452, 128, tuple(range(8))),            # inner and flush edge crops, every code on square tiles
+    (300, 452, (96, 160), (0, 2, 4, 6)),         # non-square tiles: the non-transposing codes
+    (40, 70, 128, (0, 2, 4, 6)),                 # L < t on both axes: tile clamped to 64 x 96, reflect padding
+    (50, 50, 128, tuple(range(8))),              # clamped square tile with reflection past one period (50 -> 64)
+    (1, 1, 32, tuple(range(8))),                 # L == 1: the edge value everywhere
+])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_gather_bit_exact(P, h, w, tile, codes, dtype):
+    img = _frame(h, w, 1)
+    g = P.plan_grid(h, w, tile, 0.25)
+    n = g.rows * g.cols
+    out = _gather(P, torch.from_numpy(img).cuda(), g, 0, n, codes, dtype).cpu()
+    assert (out[..., 3:] == 0).all()
+    for k in range(n):
+        for v, c in enumerate(codes):
+            want = torch.from_numpy(_tile_oracle(P, img, g, k, c))
+            got = out[k * len(codes) + v, ..., :3]
+            want = want.to(dtype)
+            assert torch.equal(got, want), (k, c)
+
+
+def test_gather_code0_equals_prepare_batch(P):
+    from uda_aerial_semantic_segmentation_research_amd.data import prepare_batch
+    img = _frame(300, 452, 2)
+    g = P.plan_grid(300, 452, 128, 0.25)
+    dev = torch.from_numpy(img).cuda()
+    for dtype in (torch.float32, torch.bfloat16):
+        out = _gather(P, dev, g, 5, 4, (0,), dtype)                    # tiles 5..8: second row, inner and edge
+        for i, k in enumerate(range(5, 9)):
+            oy, ox = g.oy[k // g.cols], g.ox[k % g.cols]
+            x, _ = prepare_batch(dev[None, oy:oy + 128, ox:ox + 128].contiguous(), dtype=dtype)
+            c = out.shape[-1]
+            full = x.as_strided((128, 128, c), (128 * c, c, 1), x.storage_offset())    # prepare_batch's padded buffer
+            assert torch.equal(out[i], full), (dtype, k)
+
+
+def _blend_oracle(P, g, logits, codes, classes, wy, wx):
+    """float64: probs [h,w,C] from synthetic per-view logits [tiles*V, th, tw, ldc] (padding lanes ignored)."""
+    h, w, V = g.h, g.w, len(codes)
+    acc = np.zeros((h, w, classes))
+    ws = np.zeros((h, w))
+    yy, xx = np.meshgrid(np.arange(g.th), np.arange(g.tw), indexing="ij")
+    wt = wy.astype(np.float64)[:, None] * wx.astype(np.float64)[None, :]
+    for k in range(g.rows * g.cols):
+        s = np.zeros((g.th, g.tw, classes))
+        for v, c in enumerate(codes):
+            lv = logits[k * V + v, ..., :classes].astype(np.float64)
+            e = np.exp(lv - lv.max(-1, keepdims=True))
+            p = e / e.sum(-1, keepdims=True)
+            iy, ix = P.inverse_view(c, yy, xx, g.th, g.tw)
+            s += p[iy, ix]
+        oy, ox = g.oy[k // g.cols], g.ox[k % g.cols]
+        hh, ww = min(g.th, h - oy), min(g.tw, w - ox)
+        acc[oy:oy + hh, ox:ox + ww] += (wt[..., None] * s)[:hh, :ww]
+        ws[oy:oy + hh, ox:ox + ww] += (wt * V)[:hh, :ww]
+    return acc / ws[..., None]
+
+
+def _margin_ok(probs64, thresh):
+    top2 = np.sort(probs64, axis=-1)[..., -2:]
+    return (top2[..., 1] - top2[..., 0]) > thresh
+
+
+def _blend_finish(P, g, logits_dev, ldc, codes, classes, wy, wx, per_call):
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    from uda_aerial_semantic_segmentation_research_amd.engine import ceil4
+    ldp = ceil4(classes)
+    acc = torch.zeros(g.h * g.w * ldp, device="cuda")
+    wsum = torch.zeros(g.h * g.w, device="cuda")
+    V = len(codes)
+    n = g.rows * g.cols
+    for first in range(0, n, per_call):
+        tiles = min(per_call, n - first)
+        chunk = logits_dev[first * V:(first + tiles) * V].contiguous()
+        K.predict_blend(chunk, ldc, P._grid_args(g), first, tiles, P.view_mask(codes), classes, torch.from_numpy(wy).cuda(),
+                        torch.from_numpy(wx).cuda(), acc, ldp, wsum)
+    labels = torch.empty(g.h * g.w, dtype=torch.int64, device="cuda")
+    K.predict_finish(acc, wsum, g.h * g.w, classes, ldp, labels)
+    return acc.view(g.h, g.w, ldp), labels.view(g.h, g.w)
+
+
+@pytest.mark.parametrize("overlap,views,window", [(0.25, 1, "gaussian"), (0.5, 1, "uniform"), (0.25, 4, "uniform"),
+                                                  (0.5, 4, "gaussian"), (0.25, 8, "gaussian"), (0.5, 8, "uniform")])
+def test_blend_finish_against_float64_oracle(P, overlap, views, window):
+    classes, ldc = 23, 24
+    g = P.plan_grid(300, 452, 128, overlap)
+    codes = {1: (0,), 4: (0, 2, 4, 6), 8: tuple(range(8))}[views]
+    rng = np.random.default_rng(3)
+    logits = (rng.standard_normal((g.rows * g.cols * views, g.th, g.tw, ldc)) * 3).astype(np.float32)
+    logits[..., classes:] = 1e4                                           # garbage in the padding lane
+    wy, wx = P.window_vector(g.th, window), P.window_vector(g.tw, window)
+    probs, labels = _blend_finish(P, g, torch.from_numpy(logits).cuda(), ldc, codes, classes, wy, wx, per_call=3)
+    want = _blend_oracle(P, g, logits, codes, classes, wy, wx)
+    probs = probs.cpu().numpy()
+    assert (probs[..., classes:] == 0).all()
+    assert np.abs(probs[..., :classes] - want).max() < 2e-6
+    ok = _margin_ok(want, 1e-5)
+    assert ok.mean() > 0.99
+    assert np.array_equal(labels.cpu().numpy()[ok], want.argmax(-1)[ok])
+
+
+@pytest.mark.parametrize("h,w,tile", [(150, 200, 64), (40, 50, 128)])
+def test_d4_round_trip_through_the_gather(P, h, w, tile):
+    """Gathered fp32 tiles (cpad 4, lane 3 zero) are a valid classes=3, ldc=4 logits buffer: blending all 8 views back must give
+    the softmax of the un-augmented normalised frame -- any error of the inverse map shows."""
+    from oracle.data_ref import normalize
+    img = _frame(h, w, 4)
+    g = P.plan_grid(h, w, tile, 0.25)
+    codes = tuple(range(8))
+    n = g.rows * g.cols
+    x = _gather(P, torch.from_numpy(img).cuda(), g, 0, n, codes)
+    wy, wx = P.window_vector(g.th), P.window_vector(g.tw)
+    probs, _ = _blend_finish(P, g, x, 4, codes, 3, wy, wx, per_call=2)
+    z = normalize(img).astype(np.float64)
+    e = np.exp(z - z.max(-1, keepdims=True))
+    want = e / e.sum(-1, keepdims=True)
+    assert np.abs(probs.cpu().numpy()[..., :3] - want).max() < 1e-6
+
+
+@pytest.fixture(scope="module")
+def r18():
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(0)
+    return Unet("resnet18", encoder_weights=None, in_channels=3, classes=23).to("cuda").eval()
+
+
+def test_determinism_across_batch_sizes(P, r18):
+    img = _frame(200, 300, 5)
+    runs = []
+    for bs, tta in ((1, None), (3, None), (8, None), (8, None)):
+        runs.append(P.predict_large(r18, img, tile=128, overlap=0.25, batch_size=bs, tta=tta, return_probs=True))
+    for lab, pr in runs[1:]:
+        assert torch.equal(pr, runs[0][1]) and torch.equal(lab, runs[0][0])
+    f4 = P.predict_large(r18, img, tile=128, overlap=0.25, batch_size=4, tta="flips", return_probs=True)
+    f8 = P.predict_large(r18, img, tile=128, overlap=0.25, batch_size=8, tta="flips", return_probs=True)
+    assert torch.equal(f4[1], f8[1]) and torch.equal(f4[0], f8[0])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_one_tile_identity(P, dtype):
+    from uda_aerial_semantic_segmentation_research_amd.data import prepare_batch
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(1)
+    model = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23, compute_dtype=dtype).to("cuda").eval()
+    img = _frame(128, 192, 6)
+    labels, probs = P.predict_large(model, img, tile=(128, 192), window="uniform", return_probs=True)
+    assert model.training is False
+    x, _ = prepare_batch(torch.from_numpy(img)[None], dtype=dtype)
+    with torch.no_grad():
+        logits = model(x)
+    assert torch.equal(labels, logits.argmax(1)[0])
+    assert (probs - torch.softmax(logits.double(), 1).float()).abs().max().item() < 1e-6
+
+
+def test_end_to_end_against_cpu_oracle(P):
+    from oracle.unet_ref import UnetRef
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(2)
+    ref = UnetRef("resnet18", classes=23).train()
+    with torch.no_grad():
+        ref(torch.randn(2, 3, 64, 64) * 2 + 0.5)                        # non-trivial BatchNorm running statistics
+    ref.eval()
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23)
+    net.load_state_dict(ref.state_dict())
+    net = net.to("cuda").eval()
+    img = _frame(100, 330, 7)
+    labels, probs = P.predict_large(net, img, tile=128, overlap=0.25, tta="d4", window="gaussian", return_probs=True)
+    g = P.plan_grid(100, 330, 128, 0.25)
+    codes = tuple(range(8))
+    tiles = np.stack([_tile_oracle(P, img, g, k, c) for k in range(g.rows * g.cols) for c in codes])
+    with torch.no_grad():
+        lg = ref(torch.from_numpy(tiles).permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).numpy()
+    want = _blend_oracle(P, g, lg, codes, 23, P.window_vector(g.th), P.window_vector(g.tw))
+    got = probs[0].permute(1, 2, 0).cpu().numpy()
+    assert np.abs(got - want).max() < 1e-4
+    ok = _margin_ok(want, 1e-3)
+    assert ok.mean() > 0.5                                                # a random-init model: many near-ties (68 % measured)
+    assert np.array_equal(labels.cpu().numpy()[ok], want.argmax(-1)[ok])
+
+
+def test_probs_feed_segmentation_metrics(P, r18):
+    from uda_aerial_semantic_segmentation_research_amd.metrics import segmentation_metrics
+    img = _frame(130, 170, 8)
+    mask = torch.from_numpy(np.random.default_rng(9).integers(0, 23, (130, 170))).cuda()
+    labels, probs = P.predict_large(r18, img, tile=64, overlap=0.5, tta="flips", return_probs=True)
+    got = segmentation_metrics(probs, mask[None], 23)
+    t, p = mask.cpu().numpy().ravel(), labels.cpu().numpy().ravel()
+    cm = np.bincount(23 * t + p, minlength=23 * 23).reshape(23, 23).astype(np.float64)
+    tp = np.diag(cm)
+    denom = cm.sum(0) + cm.sum(1) - tp
+    iou = np.where(denom > 0, tp / np.maximum(denom, 1), 0)
+    present = (cm.sum(0) + cm.sum(1)) > 0
+    assert got["accuracy"] == pytest.approx(tp.sum() / cm.sum(), abs=1e-12)
+    assert got["iou"] == pytest.approx((iou * present).sum() / present.sum(), abs=1e-12)
+    for c in range(23):
+        assert got[f"iou_class_{c}"] == pytest.approx(iou[c], abs=1e-12)
+
+
+def test_predict_batch_and_mask(P, r18):
+    from uda_aerial_semantic_segmentation_research_amd.data import prepare_batch
+    torch.manual_seed(3)
+    x = torch.randn(2, 3, 64, 96, device="cuda")
+    r18.train()
+    got = P.predict_batch(r18, x)
+    assert r18.training is False
+    with torch.no_grad():
+        want = r18(x).argmax(1).cpu().numpy()
+    assert got.dtype == np.int64 and got.shape == (2, 64, 96) and np.array_equal(got, want)
+    imgs = torch.from_numpy(np.stack([_frame(64, 64, 10), _frame(64, 64, 11)]))
+    xv, _ = prepare_batch(imgs)
+    with torch.no_grad():
+        want = r18(xv).argmax(1).cpu().numpy()
+    assert np.array_equal(P.predict_batch(r18, xv), want)
+
+    # prediction_suite: a normalised [3,256,256] dataset sample
+    from oracle.data_ref import normalize
+    img = _frame(256, 256, 12)
+    sample = torch.from_numpy(normalize(img)).permute(2, 0, 1).contiguous()
+    m = P.predict_mask(r18, sample)
+    with torch.no_grad():
+        logits = r18(sample[None].cuda())[0].cpu()
+    assert m.dtype == np.float32 and m.shape == (23, 256, 256)
+    keep = logits.abs() >= 1e-6
+    assert np.array_equal(m[keep.numpy()], (torch.sigmoid(logits) > 0.5).float()[keep].numpy())
+    m2 = P.predict_mask(r18, img)                                      # numpy uint8 path: prepare_batch's normalisation
+    xb, _ = prepare_batch(torch.from_numpy(img)[None])
+    with torch.no_grad():
+        logits = r18(xb)[0].cpu()
+    keep = logits.abs() >= 1e-6
+    assert np.array_equal(m2[keep.numpy()], (torch.sigmoid(logits) > 0.5).float()[keep].numpy())
+    with pytest.raises(ValueError, match="predict_large"):
+        P.predict_mask(r18, _frame(128, 256, 13))
+
+
+def test_clear_errors(P):
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    cpu = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23)
+    if next(cpu.parameters()).device.type == "cpu":
+        for call in (lambda: P.predict_large(cpu, _frame(64, 64, 0)), lambda: P.predict_batch(cpu, torch.zeros(1, 3, 64, 64)),
+                     lambda: P.predict_mask(cpu, torch.zeros(3, 256, 256))):
+            with pytest.raises(RuntimeError, match="GPU"):
+                call()
+    gpu = cpu.to("cuda").eval()
+    with pytest.raises(RuntimeError, match="GPU"):
+        P.predict_batch(gpu, torch.zeros(1, 3, 64, 64), device="cpu")
+    with pytest.raises(ValueError, match="uint8"):
+        P.predict_large(gpu, _frame(64, 64, 0).astype(np.float32))
+    with pytest.raises(ValueError, match="uint8"):
+        P.predict_large(gpu, torch.zeros(64, 64, 3, device="cuda"))
+    wide = Unet("resnet18", encoder_weights=None, in_channels=3, classes=33).to("cuda").eval()
+    with pytest.raises(ValueError, match="classes"):
+        P.predict_large(wide, _frame(64, 64, 0))

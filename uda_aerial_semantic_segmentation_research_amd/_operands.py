@@ -15,7 +15,7 @@ ctypes signature, and for each tensor role a wrong dtype and a short buffer must
 
 Names usable in count / dtype expressions: the scalar arguments of the call, the descriptor fields n hi wi ci ho wo co kh kw
 stride pad, X = n*hi*wi*ci, Y = n*ho*wo*co, W = co*kh*kw*ci, R (udaseg_bn_replicas), frag(n_out, k_in, ks), gap_splits(hw),
-ce_partials(), seg_partials(), and the dtypes f32 bf16 f64 i64 i32 u8.  dtype "raw32": any dtype, count in 4-byte units (pure
+ce_partials(), seg_partials(), popcount(v) (set bits of a mask), and the dtypes f32 bf16 f64 i64 i32 u8.  dtype "raw32": any dtype, count in 4-byte units (pure
 data movement in 16-byte vectors: udaseg_upsample2x_concat_fwd moves bf16 tensors as half as many fp32 "channels").
 """
 import ctypes as C
@@ -178,6 +178,19 @@ OPERANDS = {
     "udaseg_prepare_batch_u8": [T("images", u8, "n*h*w*3"), T("masks", u8, "n*h*w", True), T("d4", i32, "n", True), I("n"), I("h"),
                                 I("w"), H("mean255"), H("inv_std255"), T("out_images", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"),
                                 I("cpad"), I("out_bf16"), T("out_masks", i64, "n*h*w", True), I("square_checked"), S],
+    # ---- prediction (popcount(views) = V, the views per tile)
+    "udaseg_predict_gather_u8": [T("image", u8, "h*w*3"), I("h"), I("w"), I("th"), I("tw"), I("rows"), I("cols"), I("sy"), I("sx"),
+                                 I("first"), I("tiles"), I("views"), H("mean255"), H("inv_std255"),
+                                 T("out", "(bf16 if out_bf16 else f32)", "tiles*popcount(views)*th*tw*cpad"), I("cpad"),
+                                 I("out_bf16"), S],
+    "udaseg_predict_blend": [T("logits", f32, "tiles*popcount(views)*th*tw*ldc"), I("ldc"), I("h"), I("w"), I("th"), I("tw"),
+                             I("rows"), I("cols"), I("sy"), I("sx"), I("first"), I("tiles"), I("views"), I("classes"),
+                             T("win_y", f32, "th"), T("win_x", f32, "tw"), T("acc", f32, "h*w*ldp"), I("ldp"),
+                             T("wsum", f32, "h*w"), S],
+    "udaseg_predict_finish": [T("probs", f32, "pixels*ldc"), T("wsum", f32, "pixels", True), I("pixels"), I("classes"), I("ldc"),
+                              T("labels", i64, "pixels"), S],
+    "udaseg_predict_threshold": [T("logits", f32, "n*hw*ldc"), I("n"), I("hw"), I("classes"), I("ldc"),
+                                 T("out", f32, "n*classes*hw"), S],
     # ---- BatchNorm / activation passes
     "udaseg_bn_stats": [T("y", f32, "pixels*c"), I("pixels"), I("c"), T("sums", f64, "2*c*R"), S],
     "udaseg_bn_stats_bf16": [T("y", bf16, "pixels*c"), I("pixels"), I("c"), T("sums", f64, "2*c*R"), S],
@@ -351,6 +364,10 @@ def _seg_partials():
     return _memo("seg", _lib.load().udaseg_seg_partials)
 
 
+def _popcount(v):
+    return bin(v).count("1")
+
+
 def _current_stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -449,7 +466,7 @@ class _Ops:
         self._src = {}
         g = {"_R": _R, "_bad": _bad, "_FN": _FN, "_resolve": _resolve, "_byref": C.byref, "_current_stream": _current_stream,
              "_is_tensor": torch.is_tensor, "frag": _frag, "gap_splits": _gap_splits, "ce_partials": _ce_partials,
-             "seg_partials": _seg_partials, **_DT}
+             "seg_partials": _seg_partials, "popcount": _popcount, **_DT}
         self._globals = g
         for entry, roles in OPERANDS.items():
             src = _compile(entry, roles)
@@ -470,7 +487,8 @@ def requirements(entry, *args):
     roles = OPERANDS[entry]
     if len(args) != len(roles):
         raise TypeError(f"{entry}: {len(roles)} arguments expected, got {len(args)}")
-    env = {"frag": _frag, "gap_splits": _gap_splits, "ce_partials": _ce_partials, "seg_partials": _seg_partials, **_DT}
+    env = {"frag": _frag, "gap_splits": _gap_splits, "ce_partials": _ce_partials, "seg_partials": _seg_partials,
+           "popcount": _popcount, **_DT}
     for r, a in zip(roles, args):
         if r[0] == "desc":
             for f in _DESC_FIELDS:

@@ -78,6 +78,15 @@ def random_d4_codes(n, generator=None, p_rot90=0.5, p_flip=0.5, p_transpose=0.5)
     return torch.tensor(codes, dtype=torch.int32)
 
 
+def normalize_constants(mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=255.0):
+    """A.Normalize's two fp32 vectors as host arrays for the kernels: mean*max_pixel_value and reciprocal(std*max_pixel_value),
+    both rounded to fp32 first."""
+    f3 = ctypes.c_float * 3
+    m255 = f3(*[float(torch.tensor(m, dtype=torch.float32) * max_pixel_value) for m in mean])
+    r255 = f3(*[float(1.0 / (torch.tensor(s, dtype=torch.float32) * max_pixel_value)) for s in std])
+    return m255, r255
+
+
 def prepare_batch(images_u8, masks_u8=None, d4_codes=None, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD,
                   max_pixel_value=255.0):
     """images_u8 ``[N,H,W,3]`` uint8 (RGB, as decoded), masks_u8 ``[N,H,W]`` uint8 or None, d4_codes ``[N]`` int32 or None
@@ -108,10 +117,7 @@ def prepare_batch(images_u8, masks_u8=None, d4_codes=None, dtype=torch.float32, 
     cpad = 8 if dtype == torch.bfloat16 else 4
     out = torch.empty((n, h, w, cpad), device=dev, dtype=dtype)
     out_m = None if msk is None else torch.empty((n, h, w), device=dev, dtype=torch.int64)
-    f3 = ctypes.c_float * 3
-    # A.Normalize: mean*max_pixel_value and reciprocal(std*max_pixel_value), both rounded to fp32 first
-    m255 = f3(*[float(torch.tensor(m, dtype=torch.float32) * max_pixel_value) for m in mean])
-    r255 = f3(*[float(1.0 / (torch.tensor(s, dtype=torch.float32) * max_pixel_value)) for s in std])
+    m255, r255 = normalize_constants(mean, std, max_pixel_value)
     check(ops.udaseg_prepare_batch_u8(img, msk, codes, n, h, w, m255, r255, out, cpad, int(dtype == torch.bfloat16), out_m, square_ok,
                                       None), "prepare_batch_u8")
     mark_padded_input(out)

@@ -807,3 +807,23 @@ def prof_kernels():
         check(lib.udaseg_prof_kernel_read(kid, _byref(ms), _byref(fl), _byref(n)), "prof_kernel_read")
         out.append((lib.udaseg_prof_kernel_name(kid).decode(), ms.value, fl.value, n.value))
     return out
+
+
+# ---- prediction (predict.py; csrc/predict.hip).  grid = (h, w, th, tw, rows, cols, sy, sx) of predict.plan_grid
+def predict_gather_u8(image, grid, first, tiles, views, mean255, inv_std255, out, st=None):
+    """uint8 [h,w,3] frame -> out [tiles*V, th, tw, cpad] model input (fp32 or bf16 by out's dtype)."""
+    check(ops.udaseg_predict_gather_u8(image, *grid, first, tiles, views, mean255, inv_std255, out, out.shape[-1],
+                                       int(out.dtype == torch.bfloat16), st), "predict_gather_u8")
+
+
+def predict_blend(logits, ldc, grid, first, tiles, views, classes, win_y, win_x, acc, ldp, wsum, st=None):
+    check(ops.udaseg_predict_blend(logits, ldc, *grid, first, tiles, views, classes, win_y, win_x, acc, ldp, wsum, st),
+          "predict_blend")
+
+
+def predict_finish(probs, wsum, pixels, classes, ldc, labels, st=None):
+    check(ops.udaseg_predict_finish(probs, wsum, pixels, classes, ldc, labels, st), "predict_finish")
+
+
+def predict_threshold(logits, n, hw, classes, ldc, out, st=None):
+    check(ops.udaseg_predict_threshold(logits, n, hw, classes, ldc, out, st), "predict_threshold")
