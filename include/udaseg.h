@@ -333,6 +333,39 @@ int udaseg_bce_logits_target_bwd(const float* x, const float* target, int n, flo
 int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1, float beta2,
                      float eps, float bc1, float bc2, void* stream);
 
+/* ---- global-norm gradient clipping: torch.nn.utils.clip_grad_norm_(params, max_norm) at src/models/unsupervised_trainer.py:144,
+ *      without a host round trip.  sumsq: *out (= or +=, by `accumulate`) the fp64 sum of g[i]^2; per-block partials are combined
+ *      in a fixed order (no floating-point atomics: the same data give the same bits).  partials: UDASEG_SUMSQ_PARTIALS + 1
+ *      doubles owned by the caller and zeroed ONCE when allocated (the last word is the kernel's arrival counter, which it
+ *      clears itself); calls that share it must be ordered on one stream.
+ *      scale_by_clip: g[i] *= min(1, max_norm / (sqrt(*sumsq) + eps)), the coefficient formed in fp64 on the device and the
+ *      product rounded once; a coefficient >= 1 writes nothing, a NaN norm makes every g[i] NaN (as torch does with
+ *      error_if_nonfinite=False). ---- */
+#define UDASEG_SUMSQ_PARTIALS 256
+int udaseg_sumsq_f32(const float* g, int64_t count, double* partials, double* out, int accumulate, void* stream);
+int udaseg_scale_by_clip_f32(float* g, int64_t count, const double* sumsq, float max_norm, float eps, void* stream);
+
+/* ---- strong augmentation of the phase-3 step (src/models/augmentation.py:40-88, applied per image on the host at
+ *      src/models/unsupervised_trainer.py:100-114): uint8 RGB frames [n][h][w][3] + one parameter record per (view, sample)
+ *      -> `views` (1 or 2) normalised, channel-padded NHWC model inputs [views][n][h][w][cpad].  The pipeline (D4, Gaussian
+ *      noise, blur, shift-scale-rotate, one of sharpen / emboss / brightness-contrast, HSV shift, A.Normalize) is defined in
+ *      INTEGRATION.md, "Phase 3"; all randomness except the per-pixel noise is in the records, the noise is Philox4x32-10 keyed
+ *      by the record.  table: int32 [views][n][UDASEG_STRONG_AUG_WORDS], floats stored as their bit patterns:
+ *        0 flags (1 noise, 2 blur, 4 affine, 8 stage 5, 16 HSV)   1 D4 code (udaseg_prepare_batch_u8's)   2 blur kind (0 box,
+ *        1 median, 2 motion)   3 blur size (3 or 5)   4 motion direction (0 horizontal, 1 vertical, 2 main diagonal, 3 anti-
+ *        diagonal)   5 stage-5 kind (0 sharpen, 1 emboss, 2 brightness-contrast)   6,7 Philox key   8 sigma   9..14 inverse
+ *        affine map (row-major 2 x 3, output pixel -> source position)   15,16 stage-5 parameters (alpha, lightness | alpha,
+ *        strength | brightness, contrast)   17,18,19 hue / saturation / value shifts   20.. not read by the kernels
+ *      mid: fp32 scratch [views][n][h][w][4], needed when source_pass != 0; pass source_pass = 0 when no record has noise or
+ *      blur (one launch instead of two).  A record with flags == 0 gives udaseg_prepare_batch_u8's output bit for bit.
+ *      Transposing D4 codes need h == w (the bit is ignored otherwise).  mean255 / inv_std255: HOST arrays of 3 floats. ---- */
+#define UDASEG_STRONG_AUG_WORDS 32
+int udaseg_strong_aug_u8(const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
+                         const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
+                         int source_pass, void* stream);
+/* the generator's raw words, for tests: out[4i..4i+3] = Philox4x32-10(counter = counters[4i..4i+3], key = keys[2i..2i+1]) */
+int udaseg_philox4x32_debug(const int32_t* counters, const int32_t* keys, int32_t* out, int count, void* stream);
+
 /* ---- device-side input pipeline: uint8 RGB HWC images [n][h][w][3] (+ uint8 masks [n][h][w], may be NULL) ->
  *      normalised, D4-augmented, channel-padded NHWC model input (fp32, or bf16 when out_bf16) and int64 masks.
  *      Replaces the per-sample host work of src/data/dataset.py:116-138 with the geometric part of

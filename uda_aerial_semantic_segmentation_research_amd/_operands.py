@@ -178,6 +178,11 @@ OPERANDS = {
     "udaseg_prepare_batch_u8": [T("images", u8, "n*h*w*3"), T("masks", u8, "n*h*w", True), T("d4", i32, "n", True), I("n"), I("h"),
                                 I("w"), H("mean255"), H("inv_std255"), T("out_images", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"),
                                 I("cpad"), I("out_bf16"), T("out_masks", i64, "n*h*w", True), I("square_checked"), S],
+    "udaseg_strong_aug_u8": [T("images", u8, "n*h*w*3"), T("table", i32, "views*n*32"), I("views"), I("n"), I("h"), I("w"),
+                             T("mid", f32, "views*n*h*w*4", True), H("mean255"), H("inv_std255"),
+                             T("out_images", "(bf16 if out_bf16 else f32)", "views*n*h*w*cpad"), I("cpad"), I("out_bf16"),
+                             I("source_pass"), S],
+    "udaseg_philox4x32_debug": [T("counters", i32, "4*count"), T("keys", i32, "2*count"), T("out", i32, "4*count"), I("count"), S],
     # ---- prediction (popcount(views) = V, the views per tile)
     "udaseg_predict_gather_u8": [T("image", u8, "h*w*3"), I("h"), I("w"), I("th"), I("tw"), I("rows"), I("cols"), I("sy"), I("sx"),
                                  I("first"), I("tiles"), I("views"), H("mean255"), H("inv_std255"),
@@ -317,6 +322,8 @@ OPERANDS = {
     # ---- flat fp32 passes
     "udaseg_adam_flat": [T("p", f32, "count"), T("g", f32, "count"), T("m", f32, "count"), T("v", f32, "count"), I("count"), F("lr"),
                          F("beta1"), F("beta2"), F("eps"), F("bc1"), F("bc2"), S],
+    "udaseg_sumsq_f32": [T("g", f32, "count"), I("count"), T("partials", f64, 257), T("out", f64, 1), I("accumulate"), S],
+    "udaseg_scale_by_clip_f32": [T("g", f32, "count"), I("count"), T("sumsq", f64, 1), F("max_norm"), F("eps"), S],
     "udaseg_fill_f32": [T("p", f32, "count"), I("count"), F("value"), S],
     "udaseg_axpy_f32": [T("y", f32, "count"), T("x", f32, "count"), I("count"), F("alpha"), S],
     "udaseg_add_i64": [T("p", i64, "count"), I("count"), I("value"), S],

@@ -5,8 +5,13 @@ Upstream does this per sample on the host: ``cv2`` decode -> albumentations pipe
 move to one HIP kernel (csrc/data_prep.hip): the D4 geometric augmentations (``RandomRotate90``, ``Flip``, ``Transpose``;
 image and mask together), ``A.Normalize()`` and the layout change -- the output is already the channel-padded NHWC tensor
 the stem convolution reads, handed to ``Unet`` as an ``[N,3,H,W]``-shaped view (no further copy).
-The photometric / elastic augmentations of that pipeline (noise, blur, CLAHE, HSV, distortions) are albumentations
-internals with no reference-side definition to match and stay on the host side of the boundary.
+The photometric / elastic augmentations of that basic pipeline (noise, blur, CLAHE, HSV, distortions) are albumentations
+internals with no reference-side definition to match and stay on the host side of the boundary for ``prepare_batch``.
+
+Phase 3 (``src/models/unsupervised_trainer.py:100-114``) needs two STRONGLY augmented views of every unlabelled batch
+(``augmentation.py:40-88``); ``strong_views`` makes both on the device from a pipeline this build defines itself (INTEGRATION.md,
+"Phase 3": D4, Gaussian noise, blur, shift-scale-rotate, sharpen / emboss / brightness-contrast, HSV shift, Normalize;
+csrc/strong_aug.hip), with all randomness except the per-pixel noise drawn on the host by ``draw_strong_params``.
 """
 import ctypes
 
@@ -130,3 +135,204 @@ def synthetic_u8_batch(n, h, w, classes=23, seed=0, device="cuda"):
     images = torch.randint(0, 256, (n, h, w, 3), generator=g, device=device, dtype=torch.uint8)
     masks = torch.randint(0, classes, (n, h, w), generator=g, device=device, dtype=torch.uint8)
     return images, masks
+
+
+# ----------------------------------------------------------------------------------------------- strong augmentation (phase 3)
+# Flag bits and record words of udaseg_strong_aug_u8 (include/udaseg.h); the pipeline is defined in INTEGRATION.md, "Phase 3".
+SA_WORDS = 32
+SA_NOISE, SA_BLUR, SA_AFFINE, SA_STAGE5, SA_HSV = 1, 2, 4, 8, 16
+BLUR_BOX, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2
+STAGE5_SHARPEN, STAGE5_EMBOSS, STAGE5_BRIGHTNESS_CONTRAST = 0, 1, 2
+(_W_FLAGS, _W_D4, _W_BLUR_KIND, _W_BLUR_K, _W_MOTION_DIR, _W_S5_KIND, _W_KEY, _W_SIGMA, _W_AFFINE, _W_S5_PARAMS, _W_HSV,
+ _W_NOOP_DISTORT, _W_NOOP_CLAHE) = 0, 1, 2, 3, 4, 5, 6, 8, 9, 15, 17, 20, 21
+
+
+def inverse_affine(h, w, shift_x=0.0, shift_y=0.0, scale=1.0, angle_deg=0.0):
+    """The 2 x 3 map from an output pixel to its source position for: rotate by ``angle_deg`` and scale by ``scale`` about the
+    frame centre ``((w-1)/2, (h-1)/2)``, then shift by (``shift_x``, ``shift_y``) pixels.  Composed in float64; six numbers,
+    row-major."""
+    import math
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    a = math.radians(angle_deg)
+    c, s = math.cos(a) / scale, math.sin(a) / scale
+    # forward: p' = C + scale * R (p - C) + t  =>  p = C + R^T (p' - C - t) / scale
+    m = [c, s, 0.0, -s, c, 0.0]
+    m[2] = cx - (m[0] * (cx + shift_x) + m[1] * (cy + shift_y))
+    m[5] = cy - (m[3] * (cx + shift_x) + m[4] * (cy + shift_y))
+    return m
+
+
+class StrongAugParams:
+    """One parameter record per sample for ``strong_views``: an int32 ``[n, 32]`` host table (floats stored as their bit patterns,
+    layout in include/udaseg.h).  A fresh object has every stage off and the identity D4 code; the ``set_*`` methods switch
+    one stage of one sample on, ``draw_strong_params`` fills a table with the reference pipeline's branch probabilities."""
+
+    def __init__(self, n, h, w, d4_codes=None):
+        import numpy as np
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        self._i = np.zeros((self.n, SA_WORDS), dtype=np.int32)
+        self._f = self._i.view(np.float32)
+        self._f[:, _W_AFFINE + 0] = 1.0
+        self._f[:, _W_AFFINE + 4] = 1.0
+        if d4_codes is not None:
+            self._i[:, _W_D4] = np.asarray(d4_codes, dtype=np.int32).reshape(self.n)
+
+    # ---- one stage of one sample
+    def set_d4(self, i, code):
+        self._i[i, _W_D4] = int(code)
+
+    def set_noise(self, i, sigma, key):
+        """``key``: the two 32-bit Philox key words."""
+        self._i[i, _W_FLAGS] |= SA_NOISE
+        self._f[i, _W_SIGMA] = sigma
+        self._i.view("uint32")[i, _W_KEY:_W_KEY + 2] = [int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF]
+
+    def set_blur(self, i, kind, k, direction=0):
+        if kind not in (BLUR_BOX, BLUR_MEDIAN, BLUR_MOTION) or k not in (3, 5) or direction not in (0, 1, 2, 3):
+            raise ValueError("set_blur: kind in {0 box, 1 median, 2 motion}, k in {3, 5}, direction in 0..3")
+        self._i[i, _W_FLAGS] |= SA_BLUR
+        self._i[i, _W_BLUR_KIND], self._i[i, _W_BLUR_K], self._i[i, _W_MOTION_DIR] = kind, k, direction
+
+    def set_affine(self, i, shift_x=0.0, shift_y=0.0, scale=1.0, angle_deg=0.0):
+        self.set_affine_matrix(i, inverse_affine(self.h, self.w, shift_x, shift_y, scale, angle_deg))
+
+    def set_affine_matrix(self, i, m):
+        """``m``: six numbers, the row-major 2 x 3 map from an output pixel (x, y, 1) to its source position."""
+        self._i[i, _W_FLAGS] |= SA_AFFINE
+        self._f[i, _W_AFFINE:_W_AFFINE + 6] = m
+
+    def set_stage5(self, i, kind, p0, p1):
+        """sharpen (alpha, lightness) | emboss (alpha, strength) | brightness-contrast (brightness, contrast)."""
+        if kind not in (STAGE5_SHARPEN, STAGE5_EMBOSS, STAGE5_BRIGHTNESS_CONTRAST):
+            raise ValueError("set_stage5: kind in {0 sharpen, 1 emboss, 2 brightness-contrast}")
+        self._i[i, _W_FLAGS] |= SA_STAGE5
+        self._i[i, _W_S5_KIND] = kind
+        self._f[i, _W_S5_PARAMS:_W_S5_PARAMS + 2] = (p0, p1)
+
+    def set_hsv(self, i, dh, ds, dv):
+        self._i[i, _W_FLAGS] |= SA_HSV
+        self._f[i, _W_HSV:_W_HSV + 3] = (dh, ds, dv)
+
+    # ---- views of the table
+    @property
+    def table(self):
+        """int32 ``[n, 32]`` CPU tensor sharing the object's memory."""
+        return torch.from_numpy(self._i)
+
+    @property
+    def ints(self):
+        return self._i
+
+    @property
+    def floats(self):
+        return self._f
+
+    @property
+    def flags(self):
+        return self._i[:, _W_FLAGS]
+
+    @property
+    def d4(self):
+        return self._i[:, _W_D4]
+
+    def check(self, n, h, w):
+        if (self.n, self.h, self.w) != (n, h, w):
+            raise ValueError(f"strong_views: records drawn for {self.n} x {self.h} x {self.w} frames, batch is {n} x {h} x {w}")
+        i = self._i
+        if h != w and bool((i[:, _W_D4] & TRANSPOSE).any()):
+            raise ValueError("strong_views: transposing D4 codes need square images")
+        if bool(((i[:, _W_D4] < 0) | (i[:, _W_D4] > 7)).any()):
+            raise ValueError("strong_views: D4 codes are 0..7")
+        blur = (i[:, _W_FLAGS] & SA_BLUR) != 0
+        if bool((blur & ((i[:, _W_BLUR_K] != 3) & (i[:, _W_BLUR_K] != 5))).any()):
+            raise ValueError("strong_views: blur sizes are 3 or 5")
+
+
+def draw_strong_params(n, h, w, generator=None):
+    """One record per sample with the branch probabilities of the reference's strong pipeline (``augmentation.py:42-88``);
+    ``OneOf(p=P)``: apply with probability P, pick a child with probability proportional to the child's own ``p``.  Drawn on the
+    host from ``generator`` (a CPU ``torch.Generator``).  The stages this build leaves out (optical / grid / elastic distortion,
+    CLAHE) are drawn too and recorded as no-ops (words 20, 21), so every other rate is the reference's.  On non-square frames
+    the transpose bit of the D4 code is dropped."""
+    import math
+    g = generator
+    codes = random_d4_codes(n, g, 0.7, 0.7, 0.7).numpy()
+    if h != w:
+        codes = codes & ~TRANSPOSE
+    u = torch.rand(n, 24, generator=g, dtype=torch.float64).numpy()
+    keys = torch.randint(0, 1 << 32, (n, 2), generator=g, dtype=torch.int64).numpy()
+    P = StrongAugParams(n, h, w, codes)
+    for i in range(n):
+        r = u[i]
+        if r[0] < 0.4:                                       # OneOf(GaussNoise(30..80), GaussNoise(20..60)), p = 0.4
+            lo, hi = (30.0, 80.0) if r[1] < 0.5 else (20.0, 60.0)
+            P.set_noise(i, math.sqrt(lo + r[2] * (hi - lo)), keys[i])
+        if r[3] < 0.4:                                       # OneOf(MotionBlur 0.4, MedianBlur 0.3, Blur 0.3), p = 0.4
+            kind = BLUR_MOTION if r[4] < 0.4 else (BLUR_MEDIAN if r[4] < 0.7 else BLUR_BOX)
+            P.set_blur(i, kind, 3 if r[5] < 0.5 else 5, min(int(r[6] * 4), 3))
+        if r[7] < 0.5:                                       # ShiftScaleRotate(0.1, 0.3, 60), p = 0.5
+            P.set_affine(i, (2 * r[8] - 1) * 0.1 * w, (2 * r[9] - 1) * 0.1 * h, 1.0 + (2 * r[10] - 1) * 0.3, (2 * r[11] - 1) * 60.0)
+        if r[12] < 0.4:                                      # OneOf(Optical, Grid, Elastic), p = 0.4: left out, a no-op
+            P.ints[i, _W_NOOP_DISTORT] = 1
+        if r[13] < 0.5:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast) at 0.4 each, p = 0.5
+            child = min(int(r[14] * 4), 3)
+            if child == 0:
+                P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
+            elif child == 1:
+                P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[15], 0.5 + 0.5 * r[16])
+            elif child == 2:
+                P.set_stage5(i, STAGE5_EMBOSS, 0.2 + 0.3 * r[15], 0.2 + 0.5 * r[16])
+            else:
+                P.set_stage5(i, STAGE5_BRIGHTNESS_CONTRAST, (2 * r[15] - 1) * 0.3, (2 * r[16] - 1) * 0.3)
+        if r[17] < 0.4:                                      # HueSaturationValue(20, 30, 20), p = 0.4
+            P.set_hsv(i, (2 * r[18] - 1) * 20.0, (2 * r[19] - 1) * 30.0, (2 * r[20] - 1) * 20.0)
+    return P
+
+
+def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                 max_pixel_value=255.0):
+    """images_u8 ``[N,H,W,3]`` uint8 (host or device) + one ``StrongAugParams`` per view -> one or two strongly augmented model
+    inputs (``[N,3,H,W]``-shaped views of channel-padded NHWC buffers in ``dtype``, as ``prepare_batch`` hands them out).  Both
+    views come from one upload of the frames and one of the records, in at most two kernel launches and without a host
+    synchronisation."""
+    _lib.require_gpu()
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"strong_views: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("strong_views: dtype must be torch.float32 or torch.bfloat16")
+    n, h, w, _ = images_u8.shape
+    params = [params_a] if params_b is None else [params_a, params_b]
+    for p in params:
+        if not isinstance(p, StrongAugParams):
+            raise ValueError("strong_views: parameters must be StrongAugParams (see draw_strong_params)")
+        p.check(n, h, w)
+    views = len(params)
+    host = params[0].table if views == 1 else torch.cat([p.table for p in params])
+    source_pass = int(bool((host[:, _W_FLAGS] & (SA_NOISE | SA_BLUR)).any()))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    img = images_u8.to(dev, non_blocking=True).contiguous()
+    table = host.to(dev, non_blocking=True)
+    cpad = 8 if dtype == torch.bfloat16 else 4
+    per = n * h * w * cpad
+    buf = torch.empty(views * per, device=dev, dtype=dtype)
+    mid = torch.empty(views * n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
+    m255, r255 = normalize_constants(mean, std, max_pixel_value)
+    check(ops.udaseg_strong_aug_u8(img, table, views, n, h, w, mid, m255, r255, buf, cpad, int(dtype == torch.bfloat16),
+                                   source_pass, None), "strong_aug_u8")
+    outs = []
+    for v in range(views):
+        # a tensor of its own over the view's part of the storage (not a view of ``buf``): it is what the model recognises
+        o = torch.empty(0, device=dev, dtype=dtype).set_(buf.untyped_storage(), v * per, (n, h, w, cpad), (h * w * cpad, w * cpad, cpad, 1))
+        mark_padded_input(o)
+        outs.append(o.permute(0, 3, 1, 2)[:, :3])
+    return outs[0] if views == 1 else tuple(outs)
+
+
+def philox4x32(counters, keys):
+    """Raw Philox4x32-10 words of the noise stage's generator: counters int32 ``[count,4]``, keys int32 ``[count,2]`` (bit
+    patterns) on the GPU -> int32 ``[count,4]``.  For tests."""
+    _lib.require_gpu()
+    count = counters.shape[0]
+    out = torch.empty((count, 4), device=counters.device, dtype=torch.int32)
+    check(ops.udaseg_philox4x32_debug(counters.contiguous(), keys.contiguous(), out, count, None), "philox4x32_debug")
+    return out

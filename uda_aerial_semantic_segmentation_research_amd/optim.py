@@ -162,3 +162,70 @@ class FusedAdam(torch.optim.Optimizer):
                     p.addcdiv_(m, denom, value=-lr / (1 - b1 ** t))
         self._rebind = rebind_next
         return loss
+
+
+# --------------------------------------------------------------------------------------------- global-norm gradient clipping
+_SUMSQ_PARTIALS = {}     # device -> the fp64 partials + arrival counter of udaseg_sumsq_f32 (zeroed once, see include/udaseg.h)
+
+
+def _sumsq_scratch(dev):
+    buf = _SUMSQ_PARTIALS.get(dev)
+    if buf is None:
+        buf = _SUMSQ_PARTIALS[dev] = torch.zeros(257, device=dev, dtype=torch.float64)
+    return buf
+
+
+def _dense_f32(g):
+    return g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() > 0
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, eps=1e-6):
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (L2 norm, ``error_if_nonfinite=False``; reference
+    ``src/models/unsupervised_trainer.py:144``) without a host round trip: the squared norm is summed in fp64 on the device
+    (csrc/optim.hip, fixed summation order), the coefficient ``min(1, max_norm / (total_norm + eps))`` is formed on the device
+    from that scalar and never visits the host.  Parameters that form a whole gradient arena (``FusedAdam._flat_view``'s test)
+    cost one launch of each kernel per network; other dense gradients go through the same kernels per tensor, strided ones
+    through torch ops.  Returns ``total_norm`` as a 0-dim fp32 device tensor."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be a non-negative number, got {max_norm}")
+    ps = [p for p in parameters if p.grad is not None]
+    if not ps:
+        return torch.tensor(0.0)
+    if not all(p.grad.is_cuda for p in ps):
+        raise RuntimeError("clip_grad_norm_: gradients must live on the GPU (no CPU path; use torch.nn.utils.clip_grad_norm_)")
+    dev = ps[0].grad.device
+    if any(p.grad.device != dev for p in ps):
+        raise RuntimeError("clip_grad_norm_: gradients on several devices are not supported")
+    parts = {}
+    for p in ps:
+        parts.setdefault(p.untyped_storage().data_ptr(), []).append(p)
+    flat, dense, strided = [], [], []
+    for part in parts.values():
+        fv = FusedAdam._flat_view(part)
+        if fv is not None:
+            flat.append(fv[1])
+            continue
+        for p in part:
+            (dense if _dense_f32(p.grad) else strided).append(p.grad)
+    scratch = _sumsq_scratch(dev)
+    sumsq = torch.empty((), device=dev, dtype=torch.float64)
+    first = True
+    for g in flat + dense:
+        K.check(K.ops.udaseg_sumsq_f32(g, g.numel(), scratch, sumsq, int(not first), None), "sumsq_f32")
+        first = False
+    for g in strided:
+        s = g.double().square().sum()
+        sumsq = s if first else sumsq.add_(s)
+        first = False
+    for g in flat + dense:
+        K.check(K.ops.udaseg_scale_by_clip_f32(g, g.numel(), sumsq, max_norm, float(eps), None), "scale_by_clip_f32")
+    total = sumsq.sqrt()
+    if strided:
+        coef = torch.clamp(max_norm / (total + eps), max=1.0)
+        for g in strided:
+            g.mul_(coef.to(g.dtype))
+    return total.to(torch.float32)
