@@ -303,6 +303,21 @@ int udaseg_consistency_bwd(const float* z1, const float* z2, float temperature, 
 int udaseg_argmax_confusion(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc,
                             int64_t* confusion, int64_t* pred, void* stream);
 
+/* ---- per-class ROC / PR curves (SegmentationTrainer._log_roc_curves / _log_pr_curves, train.py:245-328, which sort
+ * softmax(outputs)[:, c] on the host with sklearn).  Score of class c: the log-odds of the softmax probability,
+ * s_c = z_c - log(sum_{j != c} exp(z_j)); grid: bin = clamp(floor((s_c + score_range) * bins / (2 * score_range)), 0, bins - 1)
+ * (a NaN score is counted in bin 0).  pos[c*bins + b] += pixels of target c, neg[c*bins + b] += pixels of every other target in
+ * [0, classes), with s_c in bin b (int64 counters that ACCUMULATE across calls; the caller zeroes them once).
+ * pixels < 2^31, classes <= 32, ldc <= 32, bins in {256, 512, 1024, 2048, 4096}, score_range > 0. */
+int udaseg_score_hist(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, int bins,
+                      float score_range, int64_t* pos, int64_t* neg, void* stream);
+/* from the two tables, per class, bins walked from the top (tp, fp = running sums; P, N = totals): auc = trapezoid over
+ * (fp/N, tp/P) from (0, 0) (sklearn.metrics.roc_auc_score of the bin index), ap = sum (recall_k - recall_{k-1}) * precision_k
+ * (average_precision_score of the bin index), auc_slack = 0.5 * sum_b pos_b * neg_b / (P * N) >= |auc - auc of the exact score|,
+ * support[c] = {P, N}.  auc and auc_slack are NaN when P == 0 or N == 0, ap when P == 0.  Deterministic (fixed summation order). */
+int udaseg_curve_finish(const int64_t* pos, const int64_t* neg, int classes, int bins, double* auc, double* ap,
+                        double* auc_slack, int64_t* support, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

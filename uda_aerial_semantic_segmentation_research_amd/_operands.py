@@ -279,6 +279,11 @@ OPERANDS = {
     "udaseg_scale_unless_one": [T("x", f32, "count"), I("count"), T("x2", f32, "count2", True), I("count2"), T("g", f32, 1), S],
     "udaseg_argmax_confusion": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
                                 T("confusion", i64, "classes*classes"), T("pred", i64, "pixels", True), S],
+    "udaseg_score_hist": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"), I("bins"),
+                          F("score_range"), T("pos", i64, "classes*bins"), T("neg", i64, "classes*bins"), S],
+    "udaseg_curve_finish": [T("pos", i64, "classes*bins"), T("neg", i64, "classes*bins"), I("classes"), I("bins"),
+                            T("auc", f64, "classes"), T("ap", f64, "classes"), T("auc_slack", f64, "classes"),
+                            T("support", i64, "2*classes"), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

@@ -93,6 +93,15 @@ def argmax_confusion(logits_base, target, pixels, classes, ldc, confusion, pred=
           "argmax_confusion")
 
 
+def score_hist(logits_base, target, pixels, classes, ldc, bins, score_range, pos, neg, st=None):
+    """pos / neg [classes * bins] int64 += per-class histograms of the log-odds score (they accumulate)."""
+    check(ops.udaseg_score_hist(logits_base, target, pixels, classes, ldc, bins, score_range, pos, neg, st), "score_hist")
+
+
+def curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st=None):
+    check(ops.udaseg_curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st), "curve_finish")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,

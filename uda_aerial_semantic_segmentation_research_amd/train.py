@@ -3,8 +3,10 @@
 return shapes, same step order (``:336-346``: zero_grad -> forward -> CrossEntropy -> backward -> Adam step), with the
 model, loss and optimizer running on the HIP kernels.  ``EarlyStopping`` restates ``:79-195``.
 
-Left out on purpose (OUT OF SCOPE): the sklearn confusion-matrix / ROC / PR figure logging
-(``:245-328,365-387``) and the torchmetrics objects; TensorBoard logging degrades to a no-op when the package is absent.
+The reference's confusion-matrix / ROC / PR logging (``:245-328``, called at ``:374-379`` and ``:413-417``) is opt-in here
+(``trainer.log_curves = True``): instead of sorting ``softmax(outputs)`` on the host class by class with sklearn it reads ONE
+pair of per-class score histograms made on the device (``curves.py``).  Left out on purpose (OUT OF SCOPE): the
+torchmetrics objects; TensorBoard logging degrades to a no-op when the package is absent.
 """
 import os
 from pathlib import Path
@@ -105,10 +107,69 @@ class SegmentationTrainer:
         self.log_metrics = True           # the reference computes metrics every batch; switch off for pure throughput
         self.grad_reducer = None          # ddp.GradAllReducer when data-parallel
         self.current_epoch = 0
+        self.log_curves = False           # per-class ROC / PR curves, AUC and AP every Config.LOG_INTERVAL batches (reference :374-379)
+        self.last_curves = {}             # prefix ('train' / 'val') -> the curves.curves_from_hist dict of the last logging call
 
     def calculate_metrics(self, outputs, masks):
         """Per-batch IoU / accuracy / per-class IoU (same keys as the reference)."""
         return segmentation_metrics(outputs, masks, self.num_classes)
+
+    def _log_curves(self, outputs, masks, step, prefix):
+        """What reference :374-379 / :413-417 log, from one device->host read: scalars ``{prefix}/auc_class_{c}``,
+        ``{prefix}/ap_class_{c}`` for the classes with a finite value, ``{prefix}/mean_auc``, ``{prefix}/mean_ap``; the curve arrays
+        stay on ``self.last_curves[prefix]``.  A logger other than the NullLogger that has ``log_figure`` also gets the reference's
+        figures ``{prefix}/roc_curves``, ``{prefix}/pr_curves``, ``{prefix}/confusion_matrix`` when matplotlib imports."""
+        from .curves import ScoreHistogram, curves_from_hist
+        from .metrics import confusion_matrix
+        k = self.num_classes
+        hist = ScoreHistogram(k, device=outputs.device).update(outputs, masks)
+        figures = hasattr(self.logger, "log_figure") and not isinstance(self.logger, NullLogger)
+        if figures:
+            try:
+                from matplotlib.figure import Figure
+            except ImportError:
+                figures = False
+        parts = [hist.tables.reshape(-1)]
+        if figures:
+            parts.append(confusion_matrix(outputs, masks, k).reshape(-1))
+        packed = torch.cat(parts).cpu().numpy()                         # the ONE host read of this logging call
+        tab = packed[:2 * k * hist.bins].reshape(2, k, hist.bins)
+        cur = curves_from_hist(tab[0], tab[1], hist.score_range)
+        self.last_curves[prefix] = cur
+        for name in ("auc", "ap"):
+            vals = cur[name]
+            finite = np.isfinite(vals)
+            for c in np.nonzero(finite)[0]:
+                self.logger.log_scalar(f"{prefix}/{name}_class_{c}", vals[c], step)
+            if finite.any():
+                self.logger.log_scalar(f"{prefix}/mean_{name}", float(vals[finite].mean()), step)
+        if not figures:
+            return
+        for tag, xs, ys, val, xl, yl in (("roc_curves", "fpr", "tpr", "auc", "False Positive Rate", "True Positive Rate"),
+                                         ("pr_curves", "recall", "precision", "ap", "Recall", "Precision")):
+            fig = Figure(figsize=(10, 8))
+            ax = fig.subplots()
+            for c in range(k):
+                if np.isfinite(cur[val][c]):
+                    ax.plot(cur[xs][c], cur[ys][c], label=f"Class {c} ({val.upper()} = {cur[val][c]:.2f})")
+            if tag == "roc_curves":
+                ax.plot([0, 1], [0, 1], "k--")
+            ax.set_xlabel(xl)
+            ax.set_ylabel(yl)
+            ax.set_title(f"{prefix.capitalize()} {'ROC' if tag == 'roc_curves' else 'Precision-Recall'} Curves")
+            ax.legend(fontsize="small")
+            self.logger.log_figure(f"{prefix}/{tag}", fig, step)
+        cm = packed[2 * k * hist.bins:].reshape(k, k)
+        fig = Figure(figsize=(10, 8))
+        ax = fig.subplots()
+        ax.imshow(cm, cmap="Blues")
+        for i in range(k):
+            for j in range(k):
+                ax.text(j, i, str(int(cm[i, j])), ha="center", va="center", fontsize=6)
+        ax.set_xlabel("Predicted")
+        ax.set_ylabel("True")
+        ax.set_title(f"{prefix.capitalize()} Confusion Matrix")
+        self.logger.log_figure(f"{prefix}/confusion_matrix", fig, step)
 
     def train_step(self, images, masks, optimizer):
         """The timed hot path: reference train.py:340-344.  Returns (loss tensor, logits), no host sync."""
@@ -138,6 +199,9 @@ class SegmentationTrainer:
                 self.logger.log_scalar("train/iou", metrics["iou"], step)
                 self.logger.log_scalar("train/accuracy", metrics["accuracy"], step)
                 self.logger.log_scalar("train/learning_rate", optimizer.param_groups[0]["lr"], step)
+            if self.log_curves and batch_idx % Config.LOG_INTERVAL == 0:
+                with torch.no_grad():
+                    self._log_curves(outputs.detach(), masks, (epoch - 1) * len(dataloader) + batch_idx, "train")
         return total_loss / len(dataloader)
 
     def validate(self, dataloader):
@@ -157,6 +221,8 @@ class SegmentationTrainer:
                 if batch_idx % Config.LOG_INTERVAL == 0:
                     for c in range(self.num_classes):
                         self.logger.log_scalar(f"val/iou_class_{c}", metrics[f"iou_class_{c}"], self.current_epoch)
+                    if self.log_curves:
+                        self._log_curves(outputs, masks, self.current_epoch, "val")
         avg = {"loss": total_loss / len(dataloader),
                "iou": float(np.mean([m["iou"] for m in all_metrics])),
                "accuracy": float(np.mean([m["accuracy"] for m in all_metrics]))}
