@@ -250,7 +250,7 @@ def test_fused_decoder_input_equals_materialised(pkg, name, dtype, phase, monkey
         e = ((out[True][1] - out[False][1]).abs().max() / out[False][1].abs().max()).item()
         assert e <= 1e-5, f"gradient arenas differ by {e:.3e}"
         return
-    assert getattr(net, "_up_off", None), "the phase packings were not built"
+    assert any("up_fwd" in ent for ent in net._pack.values()), "the phase packings were not built"
     el = ((out[True][0] - out[False][0]).abs().max() / out[False][0].abs().max()).item()
     ga, gb = out[True][1].double(), out[False][1].double()
     cos = (ga @ gb / (ga.norm() * gb.norm())).item()
@@ -258,6 +258,43 @@ def test_fused_decoder_input_equals_materialised(pkg, name, dtype, phase, monkey
     eh = ((ga[o:o + nel] - gb[o:o + nel]).norm() / gb[o:o + nel].norm()).item()
     print(f"phase form vs materialised: logits {el:.3e} head gradient {eh:.3e} 1 - cos(all gradients) {1 - cos:.3e}")
     assert el <= 1e-5 and eh <= 1e-5 and cos >= 0.9995
+
+
+def test_forward_routes_of_r18_fp32_at_8x512(pkg):
+    """The forward route of every conv+BN+activation layer of one r18 fp32 training step at 8 x 3 x 512 x 512 (BASELINE cfg 2), read
+    from the records on the tape.  The table was read off the launch trace of the engine BEFORE routes were values (the forward
+    entry point each layer called): a kernel change that moves a layer to another route changes this table on purpose."""
+    from uda_aerial_semantic_segmentation_research_amd.engine import ConvRecord
+    from uda_aerial_semantic_segmentation_research_amd.losses import CrossEntropyLoss
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    expected = {
+        "encoder.conv1": "stem",
+        "encoder.layer1.0.conv1": "frag", "encoder.layer1.0.conv2": "frag",
+        "encoder.layer1.1.conv1": "frag", "encoder.layer1.1.conv2": "frag",
+        # the stride-2 3x3 and the 1x1 projection that open layers 2-4 stay on the shared implicit GEMM
+        "encoder.layer2.0.conv1": "igemm", "encoder.layer2.0.conv2": "frag", "encoder.layer2.0.downsample.0": "igemm",
+        "encoder.layer2.1.conv1": "frag", "encoder.layer2.1.conv2": "frag",
+        "encoder.layer3.0.conv1": "igemm", "encoder.layer3.0.conv2": "frag", "encoder.layer3.0.downsample.0": "igemm",
+        "encoder.layer3.1.conv1": "frag", "encoder.layer3.1.conv2": "frag",
+        "encoder.layer4.0.conv1": "igemm", "encoder.layer4.0.conv2": "frag", "encoder.layer4.0.downsample.0": "igemm",
+        "encoder.layer4.1.conv1": "frag", "encoder.layer4.1.conv2": "frag",
+        "decoder.blocks.0.conv1.0": "phase", "decoder.blocks.0.conv2.0": "frag",
+        "decoder.blocks.1.conv1.0": "phase", "decoder.blocks.1.conv2.0": "frag",
+        "decoder.blocks.2.conv1.0": "phase", "decoder.blocks.2.conv2.0": "frag",
+        "decoder.blocks.3.conv1.0": "phase", "decoder.blocks.3.conv2.0": "frag_bnin",    # conv1's BatchNorm + ReLU is never written
+        "decoder.blocks.4.conv1.0": "phase", "decoder.blocks.4.conv2.0": "n16",          # 16 produced channels
+    }
+    torch.manual_seed(0)
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23).cuda().train()
+    net.debug_keep_tape = True
+    x = torch.randn(8, 3, 512, 512, device="cuda")
+    y = torch.randint(0, 23, (8, 512, 512), device="cuda")
+    CrossEntropyLoss()(net(x), y).backward()
+    names = {id(m): n for n, m in net.named_modules()}
+    _, tape, stem, _, _ = net._last_tape
+    recs = [stem[0]] + [r for _, blk_tape, _ in tape for r in blk_tape if isinstance(r, ConvRecord)]
+    got = {names[id(r.conv)]: r.route for r in recs}
+    assert got == expected, {k: (got.get(k), expected.get(k)) for k in set(got) | set(expected) if got.get(k) != expected.get(k)}
 
 
 def test_unet_bilinear_decoder_vs_oracle(pkg):

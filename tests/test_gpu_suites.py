@@ -168,7 +168,7 @@ def test_full_size_step_properties(pkg):
     net.debug_keep_tape = True
     net(xd)
     _, _, (r_stem, f1, _, _), _, _ = net._last_tape
-    y_stem, (mean, rstd) = r_stem[4], r_stem[6]
+    y_stem, mean, rstd = r_stem.y, r_stem.mean, r_stem.rstd
     pre = (y_stem - mean) * rstd
     assert pre.mean(dim=(0, 1, 2)).abs().max().item() < 1e-4
     assert (pre.var(dim=(0, 1, 2), unbiased=False) - 1).abs().max().item() < 1e-3

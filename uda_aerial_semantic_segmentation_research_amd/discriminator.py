@@ -107,7 +107,7 @@ class DomainDiscriminator(ArenaModule):
         K.gap_linear_sigmoid_bwd(dp.detach().float().contiguous(), p, pooled, P.pvec(lin, "weight"), dz,
                                  P.gvec(lin, "weight"), P.gvec(lin, "bias"), False, P.st)
         for rec in reversed(recs):
-            x_in = rec[3]
+            x_in = rec.x
             dx = torch.empty_like(x_in)
             P.conv_bn_act_bwd(rec, dz, dx=dx)
             dz = dx

@@ -49,12 +49,6 @@ USE_F32_SPLIT = os.environ.get("UDASEG_F32_SPLIT", "1") != "0"
 # half is a plain 3x3 convolution of its own).  UDASEG_UP_PHASE=0: the nine-tap gather over the virtual concatenation (A/B; tests
 # flip the module attribute to cross-check)
 USE_UP_PHASE = os.environ.get("UDASEG_UP_PHASE", "1") != "0"
-# ... and the weight gradient (conv_wgrad_up_kernel: 16 phase-tap correlations at the half resolution).  Built, graded against f64
-# (tests/test_gpu_up.py) and OFF by default: inside the overlapped step it is neutral (same box, images/s: off 983.7 / 996.7, on
-# 984.8 - 995.2 over two tile shapes and three block counts, profiles/r05_up_phase.txt) -- it does 4/9 of the nine-tap kernel's matrix
-# work but stages the same bytes per pixel for it, and the weight gradients share the chip with the main stream's chain, so what
-# counts is CU-time, not FLOPs.  UDASEG_UP_PHASE_WGRAD=1 switches it on.
-USE_UP_PHASE_WGRAD = os.environ.get("UDASEG_UP_PHASE_WGRAD", "0") == "1"
 # fp32 storage (round 5): 3x3 layers that produce exactly 16 channels (decoder block 4 conv2 forward / data gradient, the head's data
 # gradient) on the sixteen-wide matrix tile (csrc/conv_n16_f32x3.hip).  UDASEG_N16=0: the 32-row tile (A/B, cross-check)
 USE_N16 = os.environ.get("UDASEG_N16", "1") != "0"
@@ -90,11 +84,6 @@ FUSE_BN_APPLY_F32_SMALL_ONLY = os.environ.get("UDASEG_FUSE_BN_APPLY_F32", "1") !
 # ... and through the next decoder block's up-sampling (block output -> conv1 of a block without a skip input): built and tested,
 # off by default -- the 67 MB pass it saves is paid back in the consumer's staging (964.4 with, 966.3 without, 952.9 all off)
 FUSE_BN_APPLY_F32_UP = os.environ.get("UDASEG_FUSE_BN_APPLY_F32_UP", "0") == "1"
-# >= 64-channel layers: the consumer's forward (wave-specialised kernel) can write the activation out while it stages it, so that
-# its weight gradient reads a plain tensor (UDASEG_FUSE_BN_APPLY_F32_WRITE=1).  Built, bit-exact (tests), and OFF: 950.8 against 958.0
-# images/s without it (same box, three alternations) -- the transform + stores in the loader waves cost more than the eleven
-# launch-floor-bound bn_apply passes they replace.
-FUSE_BN_APPLY_F32_WRITE = os.environ.get("UDASEG_FUSE_BN_APPLY_F32_WRITE", "0") == "1"
 
 
 # bf16 storage: weight gradients of the stride-1 3x3 layers with channel counts that are multiples of 64 on the halo-resident
@@ -102,8 +91,13 @@ FUSE_BN_APPLY_F32_WRITE = os.environ.get("UDASEG_FUSE_BN_APPLY_F32_WRITE", "0") 
 USE_WGRAD_HALO = os.environ.get("UDASEG_WGRAD_HALO", "1") != "0"
 
 
-# HIP priority of that stream (0 = default, -1 = high): UDASEG_SIDE_PRIORITY (measured on the fp32 step: 857 / 854 images/s, no effect)
-SIDE_STREAM_PRIORITY = int(os.environ.get("UDASEG_SIDE_PRIORITY", "0"))
+# The closed set of routes a convolution can take (Plan.fwd_route / wgrad_route / dgrad_route; the forward's is kept on the record)
+PHASE, N16, STEM, FRAG_BNIN, FRAG_UP_BNIN, FRAG, UPCAT, IGEMM = "phase", "n16", "stem", "frag_bnin", "frag_up_bnin", "frag", "upcat", "igemm"
+FWD_ROUTES = (PHASE, N16, STEM, FRAG_BNIN, FRAG_UP_BNIN, FRAG, UPCAT, IGEMM)
+BNIN, HALO, PART, GENERIC = "bnin", "halo", "part", "generic"       # weight gradient
+SPLIT, BNREDUCE = "split", "bnreduce"                              # data gradient, beside PHASE / N16 / FRAG / IGEMM
+_MISS = object()
+
 _SIDE_STREAMS = {}   # device -> the one side HIP stream the weight gradients of every network on that device run on
 _ARENA_OWNERS = {}   # parameter-arena storage pointer -> weakref of the ArenaModule that owns it
 
@@ -166,27 +160,45 @@ class LazyAct:
     """act(batchnorm(y)) that is never written: ``y`` is the producer's raw convolution output, ``scale`` / ``shift`` the finalised
     per-channel coefficients (udaseg_bn_finalize).  Its single consumer applies act(fma(y, scale, shift)) rounded to bf16 while
     staging (forward convolution, weight gradient); the producer's BatchNorm backward re-evaluates the mask the same way."""
-    __slots__ = ("y", "scale", "shift", "act", "slope", "z", "z_valid")
+    __slots__ = ("y", "scale", "shift", "act", "slope")
 
-    def __init__(self, y, scale, shift, act, slope, z=None):
+    def __init__(self, y, scale, shift, act, slope):
         self.y, self.scale, self.shift, self.act, self.slope = y, scale, shift, act, slope
-        # fp32 write-through (round 4): a buffer the consumer's FORWARD fills with the activation while it stages y (z_valid then);
-        # the consumer's weight gradient reads it like any tensor
-        self.z, self.z_valid = z, False
 
     shape = property(lambda self: self.y.shape)
     dtype = property(lambda self: self.y.dtype)
     device = property(lambda self: self.y.device)
 
+    def in_args(self):
+        """What a consumer's launch takes to apply the transform while it stages ``y``."""
+        return {"in_scale": self.scale, "in_shift": self.shift, "in_act": self.act, "in_slope": self.slope}
+
     def materialize(self):
         """The activation as a tensor (tests / debugging only): one rounding of y * scale + shift like the kernels' fused
         multiply-add (evaluated in f64, rounded once to fp32), activation, round to the storage type."""
-        if self.z_valid:
-            return self.z
         t = torch.addcmul(self.shift.double(), self.y.double(), self.scale.double()).float()
         if self.act != ACT_NONE:
             t = torch.where(t > 0, t, self.slope * t)
         return t.to(self.y.dtype)
+
+
+class ConvRecord:
+    """What one conv+BN+activation layer leaves for the backward pass.  ``has_res`` tells the backward whether the activation's
+    argument can be re-evaluated from y alone; ``route`` is the forward route the layer took (one of FWD_ROUTES)."""
+    __slots__ = ("conv", "bn", "d", "x", "y", "z", "mean", "rstd", "act", "slope", "has_res", "route")
+
+    def __init__(self, conv, bn, d, x, y, z, mean, rstd, act, slope, has_res, route):
+        self.conv, self.bn, self.d, self.x, self.y, self.z, self.mean, self.rstd = conv, bn, d, x, y, z, mean, rstd
+        self.act, self.slope, self.has_res, self.route = act, slope, has_res, route
+
+    def dgrad_may_reduce(self, grad_shape, accumulate):
+        """May the data gradient of this layer's ONLY consumer make the two reductions of this layer's BatchNorm backward in its
+        epilogue?  (It writes this activation's complete gradient then; each call site adds its own terms.)"""
+        return FUSE_BN_REDUCE and not accumulate and not self.has_res and self.act != ACT_NONE and self.y.shape == grad_shape
+
+    def bn_reduce_args(self, plan, bsums):
+        """The ``bn=`` operand of the data-gradient kernels (kernels.NO_BN names its fields)."""
+        return (self.y, self.mean, self.rstd, plan.pvec(self.bn, "weight"), plan.pvec(self.bn, "bias"), self.act, self.slope, bsums)
 
 
 class ConvP(nn.Module):
@@ -241,6 +253,15 @@ class ArenaModule(nn.Module):
         self._param_list = []
         self._wt_arena = None       # dgrad-packed weights (scratch, refreshed every backward)
         self._wt_off = {}
+        self._wt_table = None
+        # MFMA-fragment packings of the weights (ArenaModule._lay_packings): one bf16 arena, refreshed once per step by one batched
+        # launch per table; _pack: id(conv) -> {"fwd" | "bwd" | "up_fwd" | "up_bwd" | "skip_fwd" | "skip_bwd" | "n16_fwd" | "n16_bwd" |
+        # "stem": (offset, elements)}
+        self._frag_arena = None
+        self._frag_fwd_table = self._frag_bwd_table = self._up_fwd_table = self._up_bwd_table = None
+        self._pack = {}
+        self._route_cache = {}      # Plan._cached: routing answers of the library per (kind, option epoch, geometry ...)
+        self._view_recipes = None   # grad_views
         self._nbt = None            # int64 arena of the BN num_batches_tracked counters
         self._idx = {}
         self._nbn = 0
@@ -334,95 +355,81 @@ class ArenaModule(nn.Module):
             if isinstance(m, ConvP) and m.needs_dgrad:
                 rows.append([self._idx[(id(m), "weight")][0], self._wt_off[id(m)], m.cout_p, m.k * m.k, m.cin_p])
         self._wt_table = torch.tensor(rows or [[0, 0, 0, 1, 0]], dtype=torch.int32, device=device)
-        # bf16 storage: MFMA-fragment packings of the stride-1 3x3 / 1x1 convolutions for the bf16-first kernels
-        # (csrc/conv_halo_bf16.hip), refreshed once per step by one batched launch per direction
-        self._frag_off, self._frag_fwd_table, self._frag_bwd_table, self._frag_arena = {}, None, None, None
-        f32 = self.compute_dtype == torch.float32
-        planes = 3 if f32 else 1          # fp32: the three split planes of every packing
-        if (USE_FRAG_KERNELS and self.compute_dtype == torch.bfloat16) or (USE_F32_SPLIT and f32):
-            foff, frows, brows = 0, [], []
-            for m in self.modules():
-                if isinstance(m, ConvP) and m.stride == 1 and ((m.k == 3 and m.pad == 1) or (m.k == 1 and m.pad == 0 and not f32)):
-                    nf = planes * K.frag_elems(m.cout_p, m.cin_p, m.k)
-                    frows.append([0, self._idx[(id(m), "weight")][0], foff, m.cout_p, m.cin_p, m.k])
-                    ent = [foff, nf, None, 0]
-                    foff += nf
-                    if m.needs_dgrad:
-                        nd = planes * K.frag_elems(m.cin_p, m.cout_p, m.k)
-                        brows.append([1, self._wt_off[id(m)], foff, m.cin_p, m.cout_p, m.k])
-                        ent[2], ent[3] = foff, nd
-                        foff += nd
-                    self._frag_off[id(m)] = tuple(ent)
-                elif (isinstance(m, ConvP) and not f32 and m.k == 4 and m.stride == 2 and m.pad == 1
-                      and m.cin_p & (m.cin_p - 1) == 0):
-                    # the discriminator's 4x4 / stride 2 convolutions as 2x2 windows: the forward over 4 cin phase-major "virtual"
-                    # channels (pack mode 2), the data gradient as four parity classes (modes 3..6), see csrc/conv_halo_bf16.hip
-                    nf = K.frag_elems(m.cout_p, 4 * m.cin_p, 2)
-                    frows.append([2, self._idx[(id(m), "weight")][0], foff, m.cout_p, m.cin_p, 4])
-                    ent = [foff, nf, None, 0]
-                    foff += nf
-                    if m.needs_dgrad:
-                        fe = K.frag_elems(m.cin_p, m.cout_p, 2)
-                        for e in range(4):
-                            brows.append([3 + e, self._wt_off[id(m)], foff + e * fe, m.cin_p, m.cout_p, 4])
-                        ent[2], ent[3] = foff, 4 * fe
-                        foff += 4 * fe
-                    self._frag_off[id(m)] = tuple(ent)
-            # fp32: phase packings of the decoder conv1 layers (csrc/conv_up_f32x3.hip; table rows of 8: mode, src, dst, N, K, ldk)
-            self._up_off, urows_f, urows_b = {}, [], []
-            if f32 and USE_UP_PHASE:
-                for m in self.modules():
-                    cs = m.cin_p - m.up_ca if isinstance(m, ConvP) else 0
-                    if not (isinstance(m, ConvP) and m.up_ca > 0 and m.k == 3 and m.stride == 1 and m.pad == 1 and m.needs_dgrad
-                            and m.bias is None and m.up_ca % 16 == 0 and cs % 8 == 0 and m.cout_p % 8 == 0):
-                        continue
-                    wo, wto, ent = self._idx[(id(m), "weight")][0], self._wt_off[id(m)], {}
-                    for key, mode, src, nn_, kk, ldk in (("up_fwd", 2, wo, m.cout_p, m.up_ca, m.cin_p),
-                                                        ("up_bwd", 3, wto, m.up_ca, m.cout_p, m.cout_p),
-                                                        ("skip_fwd", 0, wo + m.up_ca, m.cout_p, cs, m.cin_p),
-                                                        ("skip_bwd", 1, wto + m.up_ca * 9 * m.cout_p, cs, m.cout_p, m.cout_p)):
-                        if key.startswith("skip") and cs == 0:
-                            continue
-                        ne = 3 * K.frag_elems(nn_, kk, 4 if key.startswith("up") else 3)
-                        (urows_f if key.endswith("fwd") else urows_b).append([mode, src, foff, nn_, kk, ldk, 0, 0])
-                        ent[key] = (foff, ne)
-                        foff += ne
-                    self._up_off[id(m)] = ent
-            # fp32: sixteen-wide-tile packings (csrc/conv_n16_f32x3.hip) of the 3x3 layers that produce (forward) or return gradients
-            # for (data gradient) exactly 16 channels: decoder block 4 conv2, the head's data gradient
-            self._n16_off = {}
-            if f32 and USE_N16:
-                for m in self.modules():
-                    if not (isinstance(m, ConvP) and m.k == 3 and m.stride == 1 and m.pad == 1 and m.up_ca == 0):
-                        continue
-                    ent = {}
-                    if m.cout_p == 16 and m.cin_p % 8 == 0 and m.cin_p <= 32 and m.bias is None:
-                        ne = K.n16_frag_elems(m.cin_p)
-                        urows_f.append([4, self._idx[(id(m), "weight")][0], foff, 16, m.cin_p, m.cin_p, 0, 0])
-                        ent["fwd"] = (foff, ne)
-                        foff += ne
-                    if m.cin_p == 16 and m.needs_dgrad and m.cout_p % 8 == 0 and m.cout_p <= 32:
-                        ne = K.n16_frag_elems(m.cout_p)
-                        urows_b.append([5, self._wt_off[id(m)], foff, 16, m.cout_p, m.cout_p, 0, 0])
-                        ent["bwd"] = (foff, ne)
-                        foff += ne
-                    if ent:
-                        self._n16_off[id(m)] = ent
-            self._stem_off = {}
-            if f32 and USE_STEM:
-                for m in self.modules():
-                    if (isinstance(m, ConvP) and m.k == 7 and m.stride == 2 and m.pad == 3 and m.cin_p == 4 and m.cout_p == 64
-                            and m.bias is None):
-                        urows_f.append([8, self._idx[(id(m), "weight")][0], foff, 64, 4, 4, 0, 0])
-                        self._stem_off[id(m)] = (foff, K.STEM_FRAG_ELEMS)
-                        foff += K.STEM_FRAG_ELEMS
-            self._up_fwd_table = torch.tensor(urows_f, dtype=torch.int32, device=device) if urows_f else None
-            self._up_bwd_table = torch.tensor(urows_b, dtype=torch.int32, device=device) if urows_b else None
-            if frows:
-                self._frag_arena = torch.empty(foff, device=device, dtype=torch.bfloat16)
-                self._frag_fwd_table = torch.tensor(frows, dtype=torch.int32, device=device)
-                self._frag_bwd_table = torch.tensor(brows, dtype=torch.int32, device=device) if brows else None
+        self._route_cache = {}            # offsets and views of the old arenas die here
+        self._lay_packings(device)
         return self
+
+    # The four families of fragment packings, in the order they take their places in the fragment arena.  Each maps a convolution
+    # to [(name, table, rows, elements)]: ``rows`` go to that batched-packing table (frag_*: mode, src, dst, N, K, k; up_*: mode,
+    # src, dst, N, K, ldk, 0, 0) with dst relative to the packing's own offset.
+    def _frag_family(self, m, f32):
+        """Stride-1 3x3 / 1x1 convolutions on the bf16-first kernels (csrc/conv_halo_bf16.hip; fp32: the three split planes of
+        every packing, csrc/conv_halo_f32x3.hip), and bf16 only: the discriminator's 4x4 / stride 2 convolutions as 2x2 windows --
+        the forward over 4 cin phase-major "virtual" channels (pack mode 2), the data gradient as four parity classes (modes 3..6)."""
+        wo, wto, out = self._idx[(id(m), "weight")][0], self._wt_off.get(id(m)), []
+        if m.stride == 1 and ((m.k == 3 and m.pad == 1) or (m.k == 1 and m.pad == 0 and not f32)):
+            planes = 3 if f32 else 1
+            out.append(("fwd", "frag_fwd", [[0, wo, 0, m.cout_p, m.cin_p, m.k]], planes * K.frag_elems(m.cout_p, m.cin_p, m.k)))
+            if m.needs_dgrad:
+                out.append(("bwd", "frag_bwd", [[1, wto, 0, m.cin_p, m.cout_p, m.k]], planes * K.frag_elems(m.cin_p, m.cout_p, m.k)))
+        elif not f32 and m.k == 4 and m.stride == 2 and m.pad == 1 and m.cin_p & (m.cin_p - 1) == 0:
+            out.append(("fwd", "frag_fwd", [[2, wo, 0, m.cout_p, m.cin_p, 4]], K.frag_elems(m.cout_p, 4 * m.cin_p, 2)))
+            if m.needs_dgrad:
+                fe = K.frag_elems(m.cin_p, m.cout_p, 2)
+                out.append(("bwd", "frag_bwd", [[3 + e, wto, e * fe, m.cin_p, m.cout_p, 4] for e in range(4)], 4 * fe))
+        return out
+
+    def _up_family(self, m, f32):
+        """fp32: phase packings of the decoder conv1 layers (csrc/conv_up_f32x3.hip)."""
+        cs = m.cin_p - m.up_ca
+        if not (f32 and USE_UP_PHASE and m.up_ca > 0 and m.k == 3 and m.stride == 1 and m.pad == 1 and m.needs_dgrad
+                and m.bias is None and m.up_ca % 16 == 0 and cs % 8 == 0 and m.cout_p % 8 == 0):
+            return []
+        wo, wto = self._idx[(id(m), "weight")][0], self._wt_off[id(m)]
+        out = [("up_fwd", "up_fwd", [[2, wo, 0, m.cout_p, m.up_ca, m.cin_p, 0, 0]], 3 * K.frag_elems(m.cout_p, m.up_ca, 4)),
+               ("up_bwd", "up_bwd", [[3, wto, 0, m.up_ca, m.cout_p, m.cout_p, 0, 0]], 3 * K.frag_elems(m.up_ca, m.cout_p, 4))]
+        if cs:
+            out += [("skip_fwd", "up_fwd", [[0, wo + m.up_ca, 0, m.cout_p, cs, m.cin_p, 0, 0]], 3 * K.frag_elems(m.cout_p, cs, 3)),
+                    ("skip_bwd", "up_bwd", [[1, wto + m.up_ca * 9 * m.cout_p, 0, cs, m.cout_p, m.cout_p, 0, 0]],
+                     3 * K.frag_elems(cs, m.cout_p, 3))]
+        return out
+
+    def _n16_family(self, m, f32):
+        """fp32: sixteen-wide-tile packings (csrc/conv_n16_f32x3.hip) of the 3x3 layers that produce (forward) or return gradients
+        for (data gradient) exactly 16 channels: decoder block 4 conv2, the head's data gradient."""
+        out = []
+        if not (f32 and USE_N16 and m.k == 3 and m.stride == 1 and m.pad == 1 and m.up_ca == 0):
+            return out
+        if m.cout_p == 16 and m.cin_p % 8 == 0 and m.cin_p <= 32 and m.bias is None:
+            out.append(("n16_fwd", "up_fwd", [[4, self._idx[(id(m), "weight")][0], 0, 16, m.cin_p, m.cin_p, 0, 0]], K.n16_frag_elems(m.cin_p)))
+        if m.cin_p == 16 and m.needs_dgrad and m.cout_p % 8 == 0 and m.cout_p <= 32:
+            out.append(("n16_bwd", "up_bwd", [[5, self._wt_off[id(m)], 0, 16, m.cout_p, m.cout_p, 0, 0]], K.n16_frag_elems(m.cout_p)))
+        return out
+
+    def _stem_family(self, m, f32):
+        """fp32: the 7x7 / stride 2 stem (csrc/conv_stem_f32x3.hip)."""
+        if f32 and USE_STEM and m.k == 7 and m.stride == 2 and m.pad == 3 and m.cin_p == 4 and m.cout_p == 64 and m.bias is None:
+            return [("stem", "up_fwd", [[8, self._idx[(id(m), "weight")][0], 0, 64, 4, 4, 0, 0]], K.STEM_FRAG_ELEMS)]
+        return []
+
+    def _lay_packings(self, device):
+        """Lay every fragment packing out in one bf16 arena: self._pack (offsets), the four tables the batched packing launches
+        read, self._frag_arena (None when no convolution takes the bf16-first / fp32 split kernels)."""
+        f32 = self.compute_dtype == torch.float32
+        self._pack, self._frag_arena, foff = {}, None, 0
+        tables = {"frag_fwd": [], "frag_bwd": [], "up_fwd": [], "up_bwd": []}
+        if (USE_FRAG_KERNELS and not f32) or (USE_F32_SPLIT and f32):
+            convs = [m for m in self.modules() if isinstance(m, ConvP)]
+            for family in (self._frag_family, self._up_family, self._n16_family, self._stem_family):
+                for m in convs:
+                    for name, table, rows, elems in family(m, f32):
+                        tables[table] += [r[:2] + [r[2] + foff] + r[3:] for r in rows]
+                        self._pack.setdefault(id(m), {})[name] = (foff, elems)
+                        foff += elems
+        self._frag_fwd_table, self._frag_bwd_table, self._up_fwd_table, self._up_bwd_table = (
+            torch.tensor(rows, dtype=torch.int32, device=device) if rows else None for rows in tables.values())
+        if tables["frag_fwd"]:
+            self._frag_arena = torch.empty(foff, device=device, dtype=torch.bfloat16)
 
     def _arena_ok(self, full=True):
         if self._arena is None:
@@ -447,7 +454,7 @@ class ArenaModule(nn.Module):
         dev = self._arena.device
         st = _SIDE_STREAMS.get(dev)
         if st is None:
-            st = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
+            st = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
         return st
 
     def tick_batchnorm_counters(self):
@@ -510,7 +517,7 @@ class ArenaModule(nn.Module):
         """Logical-shape gradient views (one per parameter, in ``self._param_list`` order) over a grad arena: ONE as_strided per
         parameter from a cached (size, stride, offset) recipe -- the slice / view / slice / permute chain they replace cost 0.35 ms
         of host time per backward pass (92 parameters), and BASELINE cfg 3 is close to host-bound (profiles/r04_host_bound.txt)."""
-        rec = getattr(self, "_view_recipes", None)
+        rec = self._view_recipes
         if rec is None or rec[0] is not self._entries:
             rs = []
             for p, o, n, shp, mod, name in self._entries:
@@ -537,10 +544,10 @@ class Plan:
         self.bf16 = self.adt == torch.bfloat16
         # bf16 storage: one cast of the whole fp32 master arena per forward (same offsets / physical shapes)
         self.w16 = K.cast_to_bf16(net._arena, st=self.st) if self.bf16 else None
-        self.frag = training and getattr(net, "_frag_arena", None) is not None      # bf16 kernels / fp32 three-term split
+        self.frag = training and net._frag_arena is not None      # bf16 kernels / fp32 three-term split
         if self.frag:
             K.pack_frag_batched(self.w16 if self.bf16 else net._arena, None, net._frag_arena, net._frag_fwd_table, self.st)
-            if getattr(net, "_up_fwd_table", None) is not None:
+            if net._up_fwd_table is not None:
                 K.pack_up_batched(net._arena, None, net._frag_arena, net._up_fwd_table, self.st)
         nbn = net._nbn
         self.dev = dev
@@ -583,7 +590,7 @@ class Plan:
             # ... and the two fragment packings made from it (fp32 split / bf16 kernels): everything the backward pass needs of the weights
             if self.frag and net._frag_bwd_table is not None:
                 K.pack_frag_batched(None, net._wt_arena, net._frag_arena, net._frag_bwd_table, side.cuda_stream)
-            if self.frag and getattr(net, "_up_bwd_table", None) is not None:
+            if self.frag and net._up_bwd_table is not None:
                 K.pack_up_batched(None, net._wt_arena, net._frag_arena, net._up_bwd_table, side.cuda_stream)
             self._packed_all = True
             # ... and the zeroed gradient arena / BatchNorm-backward sums of this step (two fills that sat in front of the backward)
@@ -607,7 +614,7 @@ class Plan:
     def pvec(self, mod, name):
         # parameter vectors are views of the network's arena, which lives as long as the network does: cached there (a slice costs
         # ~1.3 us of host time, a step asks for ~140 of them)
-        cache = self.net.__dict__.setdefault("_pvec_cache", {})
+        cache = self.net._pvec_cache
         key = (id(mod), name)
         v = cache.get(key)
         if v is None or v._base is not self.net._arena:
@@ -626,28 +633,28 @@ class Plan:
     def offset_of(self, mod, name="weight"):
         return self.idx[(id(mod), name)][0]
 
+    def _cached(self, kind, key, compute):
+        """The one cache of routing answers (net._route_cache, emptied by build_arena): the library's answer is a function of the
+        geometry and its switchboard alone -- asked once per (kind, option epoch, key), the fragment views cached with it (two
+        ctypes calls and a slice per convolution and direction otherwise: host time, and cfg 3 runs close to the host's launch
+        rate).  A Python switch the answer depends on is in ``key`` or was tested before this call."""
+        cache, key = self.net._route_cache, (kind, self.epoch, key)
+        v = cache.get(key, _MISS)
+        if v is _MISS:
+            v = cache[key] = compute()
+        return v
+
+    def _view(self, ent):
+        return self.net._frag_arena[ent[0]:ent[0] + ent[1]]
+
     def wfrag(self, conv, d, dgrad=False, up_ca=0):
         """The conv's fragment-packed weights (forward or data gradient) when this launch can take the bf16-first kernels."""
-        if not self.frag:
+        ent = self.net._pack.get(id(conv), {}).get("bwd" if dgrad else "fwd") if self.frag else None
+        if ent is None:
             return None
-        ent = self.net._frag_off.get(id(conv))
-        if ent is None or (dgrad and ent[2] is None):
-            return None
-        # the library's answer is a function of the geometry alone: asked once per (convolution, geometry, policy), the fragment
-        # view cached with it (two ctypes calls and a slice per convolution and direction otherwise: host time, and cfg 3 runs close
-        # to the host's launch rate)
-        cache = self.net.__dict__.setdefault("_wfrag_cache", {})
-        key = (id(conv), d.n, d.hi, d.wi, d.ci, d.co, bool(dgrad), up_ca, FRAG_POLICY, self.bf16, self.epoch)
-        hit = cache.get(key)
-        if hit is not None and hit[0] is self.net._frag_arena:
-            return hit[1]
         ok = K.conv_frag_ok if FRAG_POLICY == "always" else K.conv_frag_preferred
-        view = None
-        if ok(d, dgrad, up_ca, f32=not self.bf16):
-            o, n = (ent[2], ent[3]) if dgrad else (ent[0], ent[1])
-            view = self.net._frag_arena[o:o + n]
-        cache[key] = (self.net._frag_arena, view)
-        return view
+        return self._cached("wfrag", (id(conv), d.n, d.hi, d.wi, d.ci, d.co, bool(dgrad), up_ca, FRAG_POLICY),
+                            lambda: self._view(ent) if ok(d, dgrad, up_ca, f32=not self.bf16) else None)
 
     def prelaunch_skip(self, conv, skip, up_ca):
         """Start the skip half of decoder conv1 ``conv`` (phase form) on the side stream now: y = conv3x3(skip, W[:, up_ca:]).  Called
@@ -672,71 +679,75 @@ class Plan:
         this launch can run its up-sampled half as four 2x2 phase convolutions (csrc/conv_up_f32x3.hip), else None."""
         if not (self.frag and USE_UP_PHASE and not self.bf16):
             return None
-        ent = getattr(self.net, "_up_off", {}).get(id(conv))
-        if ent is None or up_ca != conv.up_ca:
+        ent = self.net._pack.get(id(conv), {})
+        if "up_fwd" not in ent or up_ca != conv.up_ca:
             return None
-        cache = self.net.__dict__.setdefault("_upfrag_cache", {})
-        key = (id(conv), d.n, d.hi, d.wi, d.ci, d.co, self.epoch)
-        hit = cache.get(key)
-        if hit is not None and hit[0] is self.net._frag_arena:
-            return hit[1]
-        views = None
-        if K.conv_up_ok(d, up_ca):
-            views = {k: self.net._frag_arena[o:o + n] for k, (o, n) in ent.items()}
-        cache[key] = (self.net._frag_arena, views)
-        return views
+        return self._cached("up", (id(conv), d.n, d.hi, d.wi, d.ci, d.co), lambda: {
+            k: self._view(ent[k]) for k in ("up_fwd", "up_bwd", "skip_fwd", "skip_bwd") if k in ent} if K.conv_up_ok(d, up_ca) else None)
 
     def stem_frag(self, conv, d):
         """The stem's fragment packing when this launch can take csrc/conv_stem_f32x3.hip."""
         if not (self.frag and USE_STEM and USE_F32_SPLIT and not self.bf16):
             return None
-        ent = getattr(self.net, "_stem_off", {}).get(id(conv))
+        ent = self.net._pack.get(id(conv), {}).get("stem")
         if ent is None:
             return None
-        cache = self.net.__dict__.setdefault("_stem_cache", {})
-        key = (id(conv), d.n, d.hi, d.wi, self.epoch)
-        hit = cache.get(key)
-        if hit is not None and hit[0] is self.net._frag_arena:
-            return hit[1]
-        view = self.net._frag_arena[ent[0]:ent[0] + ent[1]] if K.conv_stem_ok(d) else None
-        cache[key] = (self.net._frag_arena, view)
-        return view
+        return self._cached("stem", (id(conv), d.n, d.hi, d.wi), lambda: self._view(ent) if K.conv_stem_ok(d) else None)
 
     def n16_frag(self, conv, d, dgrad):
         """The conv's sixteen-wide-tile packing (forward or data gradient) when this launch can take csrc/conv_n16_f32x3.hip."""
         if not (self.frag and USE_N16 and USE_F32_SPLIT and not self.bf16):
             return None
-        ent = getattr(self.net, "_n16_off", {}).get(id(conv))
-        key2 = "bwd" if dgrad else "fwd"
-        if ent is None or key2 not in ent:
+        ent = self.net._pack.get(id(conv), {}).get("n16_bwd" if dgrad else "n16_fwd")
+        if ent is None:
             return None
-        cache = self.net.__dict__.setdefault("_n16_cache", {})
-        key = (id(conv), d.n, d.hi, d.wi, d.ci, d.co, bool(dgrad), self.epoch)
-        hit = cache.get(key)
-        if hit is not None and hit[0] is self.net._frag_arena:
-            return hit[1]
-        view = None
-        if K.conv_n16_ok(d, dgrad):
-            o, n = ent[key2]
-            view = self.net._frag_arena[o:o + n]
-        cache[key] = (self.net._frag_arena, view)
-        return view
+        return self._cached("n16", (id(conv), d.n, d.hi, d.wi, d.ci, d.co, bool(dgrad)),
+                            lambda: self._view(ent) if K.conv_n16_ok(d, dgrad) else None)
 
     # -- forward pieces
+    def fwd_route(self, conv, d, x, allowed=FWD_ROUTES):
+        """Which kernel this convolution's training forward takes: (one of ``allowed``, its packed operand or None).  A route
+        outside ``allowed`` is never looked at (Plan.conv has three launches, not eight)."""
+        up = isinstance(x, UpCat)
+        lazy = isinstance(x.a if up else x, LazyAct)          # the (up-sampled) source is an unwritten activation
+        if PHASE in allowed and up and not lazy:
+            upw = self.up_frag(conv, d, x.a.shape[3])
+            if upw is not None:
+                return PHASE, upw
+        if N16 in allowed and not up and conv.bias is None:     # 16 produced channels: the sixteen-wide tile
+            n16 = self.n16_frag(conv, d, False)
+            if n16 is not None:
+                return N16, n16
+        if STEM in allowed and not up and not lazy and conv.bias is None and conv.k == 7:      # the 7x7 / stride 2 stem
+            stem = self.stem_frag(conv, d)
+            if stem is not None:
+                return STEM, stem
+        wf = self.wfrag(conv, d, up_ca=x.a.shape[3] if up else 0)
+        if lazy and not up:
+            assert wf is not None, "a LazyAct input needs the fragment kernels (decided by the producer)"
+            route = FRAG_BNIN
+        elif wf is not None:
+            route = FRAG_UP_BNIN if lazy else FRAG
+            assert not lazy or x.skip is None
+        else:
+            route = UPCAT if up else IGEMM
+        assert route in allowed, (route, allowed)
+        return route, wf
+
     def conv(self, conv, x, act=ACT_NONE, slope=0.0, out_dtype=None):
+        """y = act(conv(x) + bias): the layers without BatchNorm (the head, the discriminator's first)."""
         n, h, w, ci = x.shape
         assert ci == conv.cin_p, (ci, conv.cin_p)
         d = K.conv_desc(n, h, w, ci, conv.cout_p, conv.k, conv.stride, conv.pad)
         y = torch.empty((n, d.ho, d.wo, conv.cout_p), device=x.device, dtype=out_dtype or self.adt)
-        wf = self.wfrag(conv, d)
-        if isinstance(x, LazyAct):
-            assert wf is not None, "a LazyAct input needs the fragment kernels (decided by the producer)"
-            K.conv2d_fwd_frag(d, x.y, None, wf, self.b(conv) if conv.bias is not None else None, y, act, slope,
-                              in_scale=x.scale, in_shift=x.shift, in_act=x.act, in_slope=x.slope, st=self.st)
-        elif wf is not None:
-            K.conv2d_fwd_frag(d, x, None, wf, self.b(conv) if conv.bias is not None else None, y, act, slope, st=self.st)
+        bias = self.b(conv) if conv.bias is not None else None
+        route, wf = self.fwd_route(conv, d, x, (FRAG_BNIN, FRAG, IGEMM))
+        if route == FRAG_BNIN:
+            K.conv2d_fwd_frag(d, x.y, None, wf, bias, y, act, slope, st=self.st, **x.in_args())
+        elif route == FRAG:
+            K.conv2d_fwd_frag(d, x, None, wf, bias, y, act, slope, st=self.st)
         else:
-            K.conv2d_fwd(d, x, self.w(conv), self.b(conv) if conv.bias is not None else None, y, act, slope, False, self.st)
+            K.conv2d_fwd(d, x, self.w(conv), bias, y, act, slope, False, self.st)
         return y, d
 
     def bn(self, bn, y, act, slope, residual=None, sums=None):
@@ -770,14 +781,9 @@ class Plan:
         """Cached per (consumer, geometry, switches): see _lazy_ok_uncached."""
         if consumer is None:
             return False
-        cache = self.net.__dict__.setdefault("_lazy_cache", {})
         key = (id(consumer), c, n, ho, wo, act, residual is None, up, self.bf16, FUSE_BN_APPLY, FUSE_BN_APPLY_1X1_ONLY, FUSE_BN_REDUCE,
-               FUSE_BN_APPLY_F32, FUSE_BN_APPLY_F32_SMALL_ONLY, FUSE_BN_APPLY_F32_UP, FUSE_BN_APPLY_F32_WRITE, USE_F32_SPLIT, FRAG_POLICY,
-               self.frag, self.epoch)
-        v = cache.get(key)
-        if v is None:
-            v = cache[key] = self._lazy_ok_uncached(c, n, ho, wo, consumer, act, residual, up)
-        return v
+               FUSE_BN_APPLY_F32, FUSE_BN_APPLY_F32_SMALL_ONLY, FUSE_BN_APPLY_F32_UP, USE_F32_SPLIT, FRAG_POLICY, self.frag)
+        return self._cached("lazy", key, lambda: self._lazy_ok_uncached(c, n, ho, wo, consumer, act, residual, up))
 
     def _lazy_ok_uncached(self, c, n, ho, wo, consumer, act, residual, up=False):
         """May BatchNorm + activation of this [n, ho, wo, c] output stay unwritten?  Only when its single consumer runs on the
@@ -791,16 +797,13 @@ class Plan:
             if consumer.k != 3 or consumer.stride != 1 or consumer.pad != 1 or consumer.cin_p != c or c % 8 != 0:
                 return False
             if c > 32 or consumer.cout_p > 32:
-                # wide layers: the consumer's forward writes the activation out as it stages it (its loader waves have the slack) and
-                # its weight gradient reads that buffer -- the transform inside the weight gradient's staging costs more than the
-                # pass saves ("2": that form everywhere, for A/B)
+                # wide layers: the transform inside the weight gradient's staging costs more than the pass saves ("2": that form
+                # everywhere, for A/B)
                 if up:
                     return False
                 d2 = K.conv_desc(n, ho, wo, c, consumer.cout_p, 3, 1, 1)
                 if self.wfrag(consumer, d2) is None:
                     return False
-                if FUSE_BN_APPLY_F32_WRITE and K.conv_bnin_writes(d2):
-                    return "write"
                 return (not FUSE_BN_APPLY_F32_SMALL_ONLY) and K.conv_bnin_ok(d2)
             if up and not FUSE_BN_APPLY_F32_UP:
                 return False
@@ -826,7 +829,6 @@ class Plan:
         ``x`` may be an ``UpCat(a, skip)``: the convolution then runs on cat([nearest_x2(a), skip], channels) without that
         tensor ever being written (fused gather; smp's decoder block input)."""
         up = isinstance(x, UpCat)
-        lazy_in = isinstance(x, LazyAct)
         if up:
             n, h, w = x.a.shape[0], 2 * x.a.shape[1], 2 * x.a.shape[2]
             ci, dev = x.a.shape[3] + (0 if x.skip is None else x.skip.shape[3]), x.a.device
@@ -834,82 +836,68 @@ class Plan:
         else:
             (n, h, w, ci), dev = x.shape, x.device
         bias = self.b(conv) if conv.bias is not None else None
-        if self.training:
-            d = K.conv_desc(n, h, w, ci, conv.cout_p, conv.k, conv.stride, conv.pad)
-            pre = self._pre.pop(id(conv), None) if up else None
-            y = pre[0] if pre is not None else torch.empty((n, d.ho, d.wo, conv.cout_p), device=dev, dtype=self.adt)
-            sums = self._next_stats(ceil4(bn.c))
-            wf = self.wfrag(conv, d, up_ca=x.a.shape[3] if up else 0)
-            upw = self.up_frag(conv, d, x.a.shape[3]) if (up and not isinstance(x.a, LazyAct)) else None
-            if pre is not None:
-                assert upw is not None and x.skip is not None and tuple(y.shape) == (n, d.ho, d.wo, conv.cout_p)
-                K.stream_wait(self.st, pre[1])                 # the skip half, started on the side stream when its feature appeared
-            if upw is not None:
-                # phase form: the skip half as a plain 3x3 convolution of its own, the up-sampled half (4 taps per phase) on top,
-                # BatchNorm statistics of the sum in the second launch's epilogue
-                assert bias is None
-                if x.skip is not None and pre is None:
-                    ds = K.conv_desc(n, h, w, x.skip.shape[3], conv.cout_p, 3, 1, 1)
-                    K.conv2d_fwd_frag(ds, x.skip, None, upw["skip_fwd"], None, y, st=self.st)
-                K.conv2d_fwd_up(d, x.a, upw["up_fwd"], y, accumulate=x.skip is not None, stats=sums[0], st=self.st)
-            elif (not up and bias is None and not (lazy_in and x.z is not None)
-                  and self.n16_frag(conv, d, False) is not None):          # 16 produced channels: the sixteen-wide tile
-                n16 = self.n16_frag(conv, d, False)
-                if lazy_in:
-                    K.conv2d_fwd_n16(d, x.y, n16, y, stats=sums[0], in_scale=x.scale, in_shift=x.shift, in_act=x.act, in_slope=x.slope,
-                                     st=self.st)
-                else:
-                    K.conv2d_fwd_n16(d, x, n16, y, stats=sums[0], st=self.st)
-            elif not up and not lazy_in and bias is None and conv.k == 7 and self.stem_frag(conv, d) is not None:
-                K.conv2d_fwd_stem(d, x, self.stem_frag(conv, d), y, stats=sums[0], st=self.st)      # the 7x7 / stride 2 stem
-            elif lazy_in:
-                assert wf is not None, "a LazyAct input needs the bf16-first kernels (decided by the producer)"
-                K.conv2d_fwd_frag(d, x.y, None, wf, bias, y, stats=sums[0], in_scale=x.scale, in_shift=x.shift, in_act=x.act,
-                                  in_slope=x.slope, st=self.st, z_out=x.z)
-                x.z_valid = x.z is not None
-            elif wf is not None and up and isinstance(x.a, LazyAct):       # the up-sampled source is an unwritten activation (fp32)
-                assert x.skip is None
-                K.conv2d_fwd_frag(d, x.a.y, None, wf, bias, y, stats=sums[0], in_scale=x.a.scale, in_shift=x.a.shift, in_act=x.a.act,
-                                  in_slope=x.a.slope, up=True, st=self.st)
-            elif wf is not None:
-                K.conv2d_fwd_frag(d, x.a if up else x, x.skip if up else None, wf, bias, y, stats=sums[0], up=up, st=self.st)
-            elif up:
-                K.conv2d_fwd_upcat(d, x.a, x.skip, self.w(conv), bias, y, ACT_NONE, 0.0, sums[0], self.st)
-            else:
-                K.conv2d_fwd_bnstats(d, x, self.w(conv), bias, y, sums[0], self.st)
-            c = ceil4(bn.c)
-            lazy = y.shape[-1] == c and self._lazy_ok(c, n, d.ho, d.wo, lazy_for, act, residual, lazy_up)
-            if lazy:
-                so, o = sums
-                mean, rstd = self.saved_stats[o:o + c], self.saved_stats[o + c:o + 2 * c]
-                scale, shift = self.coefs[o:o + c], self.coefs[o + c:o + 2 * c]
-                K.bn_finalize(so, self.pvec(bn, "weight"), self.pvec(bn, "bias"), n * d.ho * d.wo, bn.eps, bn.momentum,
-                              bn.running_mean, bn.running_var, mean, rstd, scale, shift, self.st)
-                z, ms = LazyAct(y, scale, shift, act, slope, torch.empty_like(y) if lazy == "write" else None), (mean, rstd)
-            else:
-                z, ms = self.bn(bn, y, act, slope, residual, sums)
+        d = K.conv_desc(n, h, w, ci, conv.cout_p, conv.k, conv.stride, conv.pad)
+        if not self.training:
+            return self._conv_bn_act_eval(conv, bn, d, x, bias, act, slope, residual), None
+        pre = self._pre.pop(id(conv), None) if up else None
+        y = pre[0] if pre is not None else torch.empty((n, d.ho, d.wo, conv.cout_p), device=dev, dtype=self.adt)
+        sums = self._next_stats(ceil4(bn.c))
+        route, wp = self.fwd_route(conv, d, x)
+        src = x.a if up else x             # an unwritten source: the launch reads its y and applies the transform while staging
+        xin, bnin = (src.y, src.in_args()) if isinstance(src, LazyAct) else (src, {})
+        if pre is not None:
+            assert route == PHASE and x.skip is not None and tuple(y.shape) == (n, d.ho, d.wo, conv.cout_p)
+            K.stream_wait(self.st, pre[1])                 # the skip half, started on the side stream when its feature appeared
+        if route == PHASE:
+            # the skip half as a plain 3x3 convolution of its own, the up-sampled half (4 taps per phase) on top, BatchNorm
+            # statistics of the sum in the second launch's epilogue
+            assert bias is None
+            if x.skip is not None and pre is None:
+                ds = K.conv_desc(n, h, w, x.skip.shape[3], conv.cout_p, 3, 1, 1)
+                K.conv2d_fwd_frag(ds, x.skip, None, wp["skip_fwd"], None, y, st=self.st)
+            K.conv2d_fwd_up(d, x.a, wp["up_fwd"], y, accumulate=x.skip is not None, stats=sums[0], st=self.st)
+        elif route == N16:
+            K.conv2d_fwd_n16(d, xin, wp, y, stats=sums[0], st=self.st, **bnin)
+        elif route == STEM:
+            K.conv2d_fwd_stem(d, x, wp, y, stats=sums[0], st=self.st)
+        elif route in (FRAG_BNIN, FRAG_UP_BNIN, FRAG):
+            K.conv2d_fwd_frag(d, xin, x.skip if up else None, wp, bias, y, stats=sums[0], up=up, st=self.st, **bnin)
+        elif route == UPCAT:
+            K.conv2d_fwd_upcat(d, x.a, x.skip, self.w(conv), bias, y, ACT_NONE, 0.0, sums[0], self.st)
         else:
-            # eval mode: ONE kernel per conv+BN(+add)+activation block
-            d = K.conv_desc(n, h, w, ci, conv.cout_p, conv.k, conv.stride, conv.pad)
-            o, nel, shp = self.idx[(id(conv), "weight")]
-            wf = self.fold_w[o:o + nel].view(shp)
-            c = ceil4(bn.c)
-            bf = self.fold_b[self._fold_off:self._fold_off + c]
-            self._fold_off += c
-            w32 = self.net._arena[o:o + nel].view(shp)
-            K.bn_fold(w32, bias, self.pvec(bn, "weight"),
-                      self.pvec(bn, "bias"), bn.running_mean, bn.running_var, bn.eps, wf, bf, self.st)
-            if self.bf16:
-                wf = K.cast_to_bf16(wf, st=self.st)
-            z = torch.empty((n, d.ho, d.wo, conv.cout_p), device=dev, dtype=self.adt)
-            if up:
-                K.conv2d_fwd_upcat(d, x.a, x.skip, wf, bf, z, act, slope, None, self.st)
-            else:
-                K.conv2d_fwd_fused(d, x, wf, bf, residual, z, act, slope, self.st)
-            return z, None
-        # has_res tells the backward whether the activation's argument can be re-evaluated from y alone
-        rec = (conv, bn, d, x, y, z, ms, act, slope, residual is not None) if self.save else None
+            K.conv2d_fwd_bnstats(d, x, self.w(conv), bias, y, sums[0], self.st)
+        c = ceil4(bn.c)
+        lazy = y.shape[-1] == c and self._lazy_ok(c, n, d.ho, d.wo, lazy_for, act, residual, lazy_up)
+        if lazy:
+            so, o = sums
+            mean, rstd = self.saved_stats[o:o + c], self.saved_stats[o + c:o + 2 * c]
+            scale, shift = self.coefs[o:o + c], self.coefs[o + c:o + 2 * c]
+            K.bn_finalize(so, self.pvec(bn, "weight"), self.pvec(bn, "bias"), n * d.ho * d.wo, bn.eps, bn.momentum,
+                          bn.running_mean, bn.running_var, mean, rstd, scale, shift, self.st)
+            z, ms = LazyAct(y, scale, shift, act, slope), (mean, rstd)
+        else:
+            z, ms = self.bn(bn, y, act, slope, residual, sums)
+        rec = ConvRecord(conv, bn, d, x, y, z, ms[0], ms[1], act, slope, residual is not None, route) if self.save else None
         return z, rec
+
+    def _conv_bn_act_eval(self, conv, bn, d, x, bias, act, slope, residual):
+        """Eval mode: BatchNorm folded into the weights, ONE kernel per conv+BN(+add)+activation block."""
+        o, nel, shp = self.idx[(id(conv), "weight")]
+        wf = self.fold_w[o:o + nel].view(shp)
+        c = ceil4(bn.c)
+        bf = self.fold_b[self._fold_off:self._fold_off + c]
+        self._fold_off += c
+        w32 = self.net._arena[o:o + nel].view(shp)
+        K.bn_fold(w32, bias, self.pvec(bn, "weight"),
+                  self.pvec(bn, "bias"), bn.running_mean, bn.running_var, bn.eps, wf, bf, self.st)
+        if self.bf16:
+            wf = K.cast_to_bf16(wf, st=self.st)
+        z = torch.empty((d.n, d.ho, d.wo, conv.cout_p), device=self.dev, dtype=self.adt)
+        if isinstance(x, UpCat):
+            K.conv2d_fwd_upcat(d, x.a, x.skip, wf, bf, z, act, slope, None, self.st)
+        else:
+            K.conv2d_fwd_fused(d, x, wf, bf, residual, z, act, slope, self.st)
+        return z
 
     # -- backward pieces
     def begin_backward(self):
@@ -936,24 +924,10 @@ class Plan:
             K.pack_dgrad_batched(net._arena, net._wt_arena, net._wt_table, self.st)
         if self.frag and net._frag_bwd_table is not None and not self._packed_all:
             K.pack_frag_batched(None, net._wt_arena, net._frag_arena, net._frag_bwd_table, self.st)
-        if self.frag and getattr(net, "_up_bwd_table", None) is not None and not self._packed_all:
+        if self.frag and net._up_bwd_table is not None and not self._packed_all:
             K.pack_up_batched(None, net._wt_arena, net._frag_arena, net._up_bwd_table, self.st)
         if self.side_stream is not None:
             self.side_stream.wait_stream(self.main_stream)      # zeroed gradient arena is visible to the side stream
-
-    def _wgrad_up_ok(self, conv, d, x):
-        """May this fused decoder input's weight gradient run in the phase form?  (fp32 split kernels on, both halves served.)"""
-        if self.bf16 or not (USE_UP_PHASE and USE_UP_PHASE_WGRAD and self._wgrad_halo and USE_F32_SPLIT) or isinstance(x.a, LazyAct):
-            return False
-        cache = self.net.__dict__.setdefault("_wgup_cache", {})
-        key = (id(conv), d.n, d.hi, d.wi, d.ci, d.co, x.a.shape[-1], self.epoch)
-        v = cache.get(key)
-        if v is None:
-            v = K.conv2d_wgrad_up_ok(d, x.a.shape[-1])
-            if v and x.skip is not None:
-                v = K.conv2d_wgrad_halo_ok(K.conv_desc(d.n, d.hi, d.wi, x.skip.shape[-1], d.co, 3, 1, 1), f32=True)
-            cache[key] = v
-        return v
 
     def packed_wt(self, conv):
         o = self.net._wt_off[id(conv)]
@@ -965,15 +939,47 @@ class Plan:
         self._bstat_off += 2 * c
         return self.bstats[o * self.R:(o + 2 * c) * self.R]
 
+    def wgrad_route(self, d, x):
+        """Which weight-gradient kernel: BNIN / HALO / PART for a fused decoder input, BNIN / HALO / GENERIC for a plain one."""
+        up = isinstance(x, UpCat)
+        if isinstance(x.a if up else x, LazyAct):
+            return BNIN
+        if up:
+            both = self._wgrad_halo and x.skip is not None and K.conv2d_wgrad_halo_ok(d, x.a.shape[-1], f32=not self.bf16)
+            return HALO if both else PART
+        return HALO if self._wgrad_halo and K.conv2d_wgrad_halo_ok(d, f32=not self.bf16) else GENERIC
+
+    def dgrad_route(self, conv, d, x, dx, dx_acc):
+        """Which data-gradient kernel and its packed operand: PHASE / FRAG / SPLIT / IGEMM for a fused decoder input, N16 / FRAG /
+        IGEMM for a plain one (conv_bwd turns IGEMM into BNREDUCE when the producer's BatchNorm-backward sums ride along)."""
+        if isinstance(dx, UpGrad):
+            return PHASE, self.up_frag(conv, d, x.a.shape[-1])
+        n16 = self.n16_frag(conv, d, True) if not (dx_acc or isinstance(x, UpCat)) else None      # 16 gradient channels
+        if n16 is not None:
+            return N16, n16
+        wfd = self.wfrag(conv, d, dgrad=True)
+        if isinstance(x, UpCat):
+            if wfd is not None and (x.skip is None or x.a.shape[-1] % 32 == 0):
+                return FRAG, wfd
+            return (IGEMM if x.skip is None else SPLIT), None
+        return (FRAG, wfd) if wfd is not None else (IGEMM, None)
+
+    def _bn_reduce_by(self, prev):
+        """This data gradient's epilogue makes the two reductions of ``prev``'s BatchNorm backward: their accumulators (``bn_bwd``
+        finds them in ``self._bnb`` and skips its reduce pass) inside the kernels' ``bn=`` operand."""
+        bs = self._bnb[id(prev.y)] = self._next_bstats(prev.y.shape[-1] if self.bf16 else ceil4(prev.bn.c))
+        return prev.bn_reduce_args(self, bs)
+
     def conv_bwd(self, conv, d, x, dy, dx=None, dx_acc=False, dbias=None, prev=None):
         """dW (+ dbias) into the grad arena; dx (+)= dgrad when dx is given.  dbias: already-computed channel sums of dy.
 
         ``x`` an ``UpCat(a, skip)`` (fused decoder input): the weight gradient is one launch per source, ``dx`` is the pair
-        (gradient of the UP-SAMPLED a [n,2h,2w,ca], gradient of skip) and both are overwritten.
+        (gradient of the UP-SAMPLED a [n,2h,2w,ca], gradient of skip) and both are overwritten -- or, in the phase form, an
+        ``UpGrad``: the gradient of the half-resolution source at its own resolution.
 
-        ``prev``: the conv+BN+activation record that PRODUCED x, when this convolution is x's only consumer: dx is then that
+        ``prev``: the ConvRecord that PRODUCED x (phase form: x.a), when this convolution is its only consumer: dx is then that
         activation's complete gradient and the data-gradient kernel's epilogue also makes the two reductions of its BatchNorm
-        backward (``bn_bwd`` finds them in ``self._bnb`` and skips its reduce pass)."""
+        backward."""
         side = self.side_stream
         if side is not None:
             wst = self._side_h
@@ -981,87 +987,59 @@ class Plan:
             dy.record_stream(side)                              # the caching allocator must not recycle dy under the side stream
         else:
             wst = self.st
-        if isinstance(x, UpCat):
-            gw = self.gw(conv)
-            if isinstance(x.a, LazyAct):
-                assert x.skip is None
-                K.conv2d_wgrad_bnin(d, x.a.y, x.a.scale, x.a.shift, x.a.act, x.a.slope, dy, gw, True, wst, up=True)
-            elif self._wgrad_up_ok(conv, d, x):
-                # phase form: 16 phase-tap correlations at a's resolution for the up-sampled half, the skip half as a slice
-                K.conv2d_wgrad_up(d, x.a, dy, gw, st=wst)
-                if x.skip is not None:
-                    ds = K.conv_desc(d.n, d.hi, d.wi, x.skip.shape[-1], d.co, 3, 1, 1)
-                    K.conv2d_wgrad_halo_slice(ds, x.skip, dy, gw, x.a.shape[-1], st=wst)
-            elif self._wgrad_halo and x.skip is not None and K.conv2d_wgrad_halo_ok(d, x.a.shape[-1], f32=not self.bf16):
-                K.conv2d_wgrad_halo(d, x.a, x.skip, dy, gw, up=True, st=wst)      # both sources in one launch
-            else:
-                K.conv2d_wgrad_part(d, x.a, 0, True, dy, gw, True, wst)
-                if x.skip is not None:
-                    K.conv2d_wgrad_part(d, x.skip, x.a.shape[-1], False, dy, gw, True, wst)
-            assert not dx_acc and conv.bias is None
-            if isinstance(dx, UpGrad):          # phase form: the gradient of the half-resolution source at its own resolution
-                upw = self.up_frag(conv, d, x.a.shape[-1])
-                # prev: the record of the layer that produced x.a, whose only consumer this convolution is -- da is then that
-                # activation's complete gradient (no 2x2 sum-pool pass follows any more) and the epilogue makes its BatchNorm-backward sums
-                bn = None
-                if (prev is not None and FUSE_BN_REDUCE and not dx.acc and not prev[9] and prev[7] != ACT_NONE
-                        and not isinstance(prev[5], LazyAct) and prev[4].shape == dx.da.shape):
-                    p_bn, p_y, (p_mean, p_rstd) = prev[1], prev[4], prev[6]
-                    bs = self._next_bstats(ceil4(p_bn.c))
-                    bn = (p_y, p_mean, p_rstd, self.pvec(p_bn, "weight"), self.pvec(p_bn, "bias"), prev[7], prev[8], bs)
-                    self._bnb[id(p_y)] = bs
-                K.conv2d_dgrad_up(d, dy, x.a.shape[-1], upw["up_bwd"], dx.da, accumulate=dx.acc, bn=bn, st=self.st)
-                if x.skip is not None:
-                    ds = K.conv_desc(d.n, d.hi, d.wi, x.skip.shape[-1], d.co, 3, 1, 1)
-                    K.conv2d_dgrad_frag(ds, dy, upw["skip_bwd"], dx.d_skip, st=self.st)
-                return
-            d_up, d_skip = dx
-            wfd = self.wfrag(conv, d, dgrad=True)
-            if wfd is not None and (x.skip is None or x.a.shape[-1] % 32 == 0):
-                K.conv2d_dgrad_frag(d, dy, wfd, d_up, d_skip if x.skip is not None else None, st=self.st)
-            elif x.skip is None:
-                K.conv2d_dgrad(d, dy, self.packed_wt(conv), d_up, False, self.st)
-            else:
-                K.conv2d_dgrad_split(d, dy, self.packed_wt(conv), d_up, d_skip, self.st)
-            return
-        if isinstance(x, LazyAct) and x.z_valid:
-            x = x.z                                            # written out by this convolution's own forward
-        if isinstance(x, LazyAct):
-            K.conv2d_wgrad_bnin(d, x.y, x.scale, x.shift, x.act, x.slope, dy, self.gw(conv), True, wst)
-        elif self._wgrad_halo and K.conv2d_wgrad_halo_ok(d, f32=not self.bf16):
-            K.conv2d_wgrad_halo(d, x, None, dy, self.gw(conv), st=wst)
+        up = isinstance(x, UpCat)
+        src, gw, wroute = x.a if up else x, self.gw(conv), self.wgrad_route(d, x)
+        if wroute == BNIN:
+            assert not up or x.skip is None
+            K.conv2d_wgrad_bnin(d, src.y, src.scale, src.shift, src.act, src.slope, dy, gw, True, wst, up=up)
+        elif wroute == HALO:
+            K.conv2d_wgrad_halo(d, src, x.skip if up else None, dy, gw, up=up, st=wst)      # fused input: both sources in one launch
+        elif wroute == PART:
+            K.conv2d_wgrad_part(d, x.a, 0, True, dy, gw, True, wst)
+            if x.skip is not None:
+                K.conv2d_wgrad_part(d, x.skip, x.a.shape[-1], False, dy, gw, True, wst)
         else:
-            K.conv2d_wgrad(d, x, dy, self.gw(conv), True, wst)
+            K.conv2d_wgrad(d, x, dy, gw, True, wst)
+        assert not up or (not dx_acc and conv.bias is None)
         if conv.bias is not None:
             if dbias is not None:
                 K.axpy(self.gvec(conv, "bias"), dbias, 1.0, wst)
             else:
                 K.channel_sum(dy, self.gvec(conv, "bias"), True, wst)
-        if dx is not None:
-            wfd = self.wfrag(conv, d, dgrad=True)
-            n16 = self.n16_frag(conv, d, True) if not dx_acc else None      # 16 gradient channels: the sixteen-wide tile
-            fuse = (prev is not None and FUSE_BN_REDUCE and not dx_acc and not prev[9] and prev[7] != ACT_NONE
-                    and prev[4].shape == dx.shape and (wfd is not None or n16 is not None or K.conv2d_dgrad_bnreduce_ok(d, dy.dtype)))
-            if prev is not None and isinstance(prev[5], LazyAct) and not fuse and self.bf16:
+        if dx is None:
+            return
+        route, wp = self.dgrad_route(conv, d, x, dx, dx_acc)
+        if route == PHASE:
+            # no 2x2 sum-pool pass follows: da is the producer's complete gradient unless another consumer already wrote into it
+            fuse = prev is not None and prev.dgrad_may_reduce(dx.da.shape, dx.acc) and not isinstance(prev.z, LazyAct)
+            K.conv2d_dgrad_up(d, dy, x.a.shape[-1], wp["up_bwd"], dx.da, accumulate=dx.acc, bn=self._bn_reduce_by(prev) if fuse else None,
+                              st=self.st)
+            if x.skip is not None:
+                ds = K.conv_desc(d.n, d.hi, d.wi, x.skip.shape[-1], d.co, 3, 1, 1)
+                K.conv2d_dgrad_frag(ds, dy, wp["skip_bwd"], dx.d_skip, st=self.st)
+        elif up:
+            d_up, d_skip = dx
+            if route == FRAG:
+                K.conv2d_dgrad_frag(d, dy, wp, d_up, d_skip if x.skip is not None else None, st=self.st)
+            elif route == SPLIT:
+                K.conv2d_dgrad_split(d, dy, self.packed_wt(conv), d_up, d_skip, self.st)
+            else:
+                K.conv2d_dgrad(d, dy, self.packed_wt(conv), d_up, False, self.st)
+        else:
+            fuse = (prev is not None and prev.dgrad_may_reduce(dx.shape, dx_acc)
+                    and (route != IGEMM or K.conv2d_dgrad_bnreduce_ok(d, dy.dtype)))
+            if prev is not None and isinstance(prev.z, LazyAct) and not fuse and self.bf16:
                 raise RuntimeError("internal: the producer's activation was not written, its consumer's data gradient must make "
                                    "the BatchNorm-backward sums")
-            if fuse:
-                p_bn, p_y, (p_mean, p_rstd) = prev[1], prev[4], prev[6]
-                bs = self._next_bstats(p_y.shape[-1] if self.bf16 else ceil4(p_bn.c))
-                if n16 is not None:
-                    K.conv2d_dgrad_n16(d, dy, n16, dx, bn=(p_y, p_mean, p_rstd, self.pvec(p_bn, "weight"), self.pvec(p_bn, "bias"),
-                                                           prev[7], prev[8], bs), st=self.st)
-                elif wfd is not None:
-                    K.conv2d_dgrad_frag(d, dy, wfd, dx, bn=(p_y, p_mean, p_rstd, self.pvec(p_bn, "weight"), self.pvec(p_bn, "bias"),
-                                                            prev[7], prev[8], bs), st=self.st)
-                else:
-                    K.conv2d_dgrad_bnreduce(d, dy, self.packed_wt(conv), dx, p_y, p_mean, p_rstd, self.pvec(p_bn, "weight"),
-                                            self.pvec(p_bn, "bias"), prev[7], prev[8], bs, self.st)
-                self._bnb[id(p_y)] = bs
-            elif n16 is not None:
-                K.conv2d_dgrad_n16(d, dy, n16, dx, st=self.st)
-            elif wfd is not None:
-                K.conv2d_dgrad_frag(d, dy, wfd, dx, accumulate=dx_acc, st=self.st)
+            bn = self._bn_reduce_by(prev) if fuse else None
+            if fuse and route == IGEMM:
+                route = BNREDUCE                                # the implicit-GEMM data gradient with the reductions
+            if route == N16:
+                K.conv2d_dgrad_n16(d, dy, wp, dx, bn=bn, st=self.st)
+            elif route == FRAG:
+                K.conv2d_dgrad_frag(d, dy, wp, dx, bn=bn, accumulate=dx_acc, st=self.st)
+            elif route == BNREDUCE:
+                K.conv2d_dgrad_bnreduce(d, dy, self.packed_wt(conv), dx, *bn, self.st)
             else:
                 K.conv2d_dgrad(d, dy, self.packed_wt(conv), dx, dx_acc, self.st)
 
@@ -1090,10 +1068,8 @@ class Plan:
         return dz
 
     def conv_bn_act_bwd(self, rec, dz, dx=None, dx_acc=False, dres=None, dres_acc=False, prev=None):
-        conv, bn, d, x, y, z, ms, act, slope, has_res = rec
-        dy = self.bn_bwd(bn, y, z, ms, dz, act, slope, dres, dres_acc, has_res)
-        self.conv_bwd(conv, d, x, dy, dx, dx_acc, prev=prev)
-
+        dy = self.bn_bwd(rec.bn, rec.y, rec.z, (rec.mean, rec.rstd), dz, rec.act, rec.slope, dres, dres_acc, rec.has_res)
+        self.conv_bwd(rec.conv, rec.d, rec.x, dy, dx, dx_acc, prev=prev)
 
     def ready_events(self):
         """Events after which every gradient issued so far is final (one per stream in use); for the all-reduce stream."""

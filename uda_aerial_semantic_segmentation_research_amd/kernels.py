@@ -269,10 +269,15 @@ def conv2d_fwd_up(d, a, wfrag_up, y, accumulate=False, stats=None, st=None):
     check(ops.udaseg_conv2d_fwd_up_f32x3(d, a, a.shape[-1], wfrag_up, y, int(accumulate), stats, st), "conv2d_fwd_up_f32x3")
 
 
+# the ``bn=`` operand of the data-gradient launches when no BatchNorm-backward reduction rides in the epilogue:
+# (prev_y, save_mean, save_rstd, gamma, beta, act, slope, bsums), built by engine.ConvRecord.bn_reduce_args
+NO_BN = (None, None, None, None, None, ACT_NONE, 0.0, None)
+
+
 def conv2d_dgrad_up(d, dy, up_ca, wfrag_up_t, da, accumulate=False, bn=None, st=None):
     """da (+)= gradient of a through conv3x3(nearest_x2(a)), at a's resolution.
     bn = (prev_y, save_mean, save_rstd, gamma, beta, act, slope, bsums): BatchNorm-backward reductions of the layer that produced a."""
-    py, mu, rs, ga, be, act, slope, bs = bn if bn is not None else (None, None, None, None, None, ACT_NONE, 0.0, None)
+    py, mu, rs, ga, be, act, slope, bs = bn or NO_BN
     check(ops.udaseg_conv2d_dgrad_up_f32x3(d, dy, up_ca, wfrag_up_t, da, py, mu, rs, ga, be, act, slope, bs, int(accumulate), st),
           "conv2d_dgrad_up_f32x3")
 
@@ -320,7 +325,7 @@ def conv2d_fwd_n16(d, x, wfrag, y, stats=None, in_scale=None, in_shift=None, in_
 
 def conv2d_dgrad_n16(d, dy, wfrag_t, dx, bn=None, st=None):
     """Data gradient of a 3x3 convolution with 16 input channels on the sixteen-wide tile; bn as conv2d_dgrad_frag."""
-    py, mu, rs, ga, be, act, slope, bs = bn if bn is not None else (None, None, None, None, None, ACT_NONE, 0.0, None)
+    py, mu, rs, ga, be, act, slope, bs = bn or NO_BN
     check(ops.udaseg_conv2d_dgrad_n16_f32x3(d, dy, wfrag_t, dx, py, mu, rs, ga, be, act, slope, bs, st), "conv2d_dgrad_n16_f32x3")
 
 
@@ -363,7 +368,7 @@ def conv2d_dgrad_frag(d, dy, wfrag_t, dx, dx2=None, bn=None, accumulate=False, s
     """Halo-resident data gradient (bf16 tensors, or fp32 tensors with the three-term split).  dx2: second destination of a
     split gradient (channels [dx.shape[-1], ci)).
     bn = (prev_y, save_mean, save_rstd, gamma, beta, act, slope, bsums): BatchNorm-backward reductions of the layer behind."""
-    py, mu, rs, ga, be, act, slope, bs = bn if bn is not None else (None, None, None, None, None, ACT_NONE, 0.0, None)
+    py, mu, rs, ga, be, act, slope, bs = bn or NO_BN
     fn, name = ((ops.udaseg_conv2d_dgrad_f32x3, "conv2d_dgrad_f32x3") if dy.dtype == torch.float32
                 else (ops.udaseg_conv2d_dgrad_frag_bf16, "conv2d_dgrad_frag_bf16"))
     check(fn(d, dy, wfrag_t, dx, dx2, dx.shape[-1] if dx2 is not None else 0,

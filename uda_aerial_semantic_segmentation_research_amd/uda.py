@@ -111,7 +111,7 @@ class DomainDiscriminator(ArenaModule):
         K.gap_linear_bwd(d_out.detach().float().contiguous().view(-1), pooled, w_row, dz, gw_row, P.gvec(last, "bias"), False, P.st)
         d_feat = None
         for i, rec in enumerate(reversed(recs)):
-            x_in = rec[3]
+            x_in = rec.x
             first = i == len(recs) - 1
             dx = torch.empty_like(x_in) if (need_input_grad or not first) else None
             P.conv_bn_act_bwd(rec, dz, dx=dx)

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import kernels as K
 from ._lib import ACT_LEAKY, ACT_NONE, require_gpu
-from .engine import LazyAct, ArenaModule, BNP, ConvP, GradSlots, Plan, UpCat, UpGrad, ceil4, is_padded_input
+from .engine import PHASE, LazyAct, ArenaModule, BNP, ConvP, GradSlots, Plan, UpCat, UpGrad, ceil4, is_padded_input
 
 ENCODERS = {
     "resnet18": ("basic", (2, 2, 2, 2), (64, 64, 128, 256, 512)),
@@ -177,7 +177,7 @@ class DecoderBlock(nn.Module):
             ds, ds_acc = G.slot(skip)
         else:
             ds, ds_acc = None, False
-        if isinstance(cat, UpCat) and not isinstance(x, LazyAct) and P.up_frag(self.conv1[0], r1[2], x.shape[-1]) is not None:
+        if r1.route == PHASE:
             # phase form (csrc/conv_up_f32x3.hip): conv1's data gradient lands in dx at x's own resolution -- no gradient of the
             # up-sampled tensor, no 2x2 sum-pool pass
             d_skip = (torch.empty_like(skip) if ds_acc else ds) if skip is not None else None
