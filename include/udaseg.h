@@ -381,6 +381,33 @@ int udaseg_strong_aug_u8(const uint8_t* images, const int32_t* table, int views,
 /* the generator's raw words, for tests: out[4i..4i+3] = Philox4x32-10(counter = counters[4i..4i+3], key = keys[2i..2i+1]) */
 int udaseg_philox4x32_debug(const int32_t* counters, const int32_t* keys, int32_t* out, int count, void* stream);
 
+/* ---- labelled training augmentation (src/models/augmentation.py:8-38, applied per sample on the host there): uint8 RGB
+ *      frames [n][h][w][3] + uint8 masks [n][h][w] (may be NULL, with out_masks) + one parameter record per sample -> the
+ *      normalised, channel-padded NHWC model input [n][h][w][cpad] and int64 masks [n][h][w], image and mask carried through
+ *      the same geometry.  The pipeline is defined in INTEGRATION.md, "Training augmentation": the strong pipeline's stages
+ *      plus one of optical / grid / elastic distortion, composed with the affine map into one gather (image bilinear, mask
+ *      nearest; the label value passes through unchanged).  table: int32 [n][UDASEG_TRAIN_AUG_WORDS]:
+ *        0..31 the record of udaseg_strong_aug_u8, flag bit 32 of word 0 = distortion   32 distortion kind (1 optical, 2 grid,
+ *        3 elastic)   33,34,35 optical k, dx, dy   36..41 grid x steps   42..47 grid y steps   48 elastic alpha
+ *        50,51 Philox key of the elastic field   the rest reserved, not read
+ *      mid: fp32 scratch [n][h][w][4], needed when source_pass != 0 (a record with noise or blur).  field: float2 [n][h][w],
+ *      read for the samples on elastic; field_pass != 0 fills it first (udaseg_elastic_field_f32's kernel) and then needs
+ *      gauss_weights: a HOST array of 2 radius + 1 fp32 taps, radius <= UDASEG_ELASTIC_MAX_RADIUS.  A sample on elastic
+ *      without a field buffer is refused by the Python binding; the kernels then leave its distortion out.  At most three
+ *      launches, no synchronisation.  A record with flags == 0 gives udaseg_prepare_batch_u8's output bit for bit, image and
+ *      mask.  mean255 / inv_std255: HOST arrays of 3 floats.  Transposing D4 codes need h == w (the bit is ignored otherwise).
+ *      udaseg_elastic_field_f32: the field pass alone (samples not on elastic are left untouched): field[n][y][x] = the
+ *      separable Gaussian (reflect-101 at any distance) of (2 u0 - 1, 2 u1 - 1), u = the first two uniforms of Philox4x32-10
+ *      at counter (y w + x, 1, 0, 0) under the record's key. ---- */
+#define UDASEG_TRAIN_AUG_WORDS 64
+#define UDASEG_ELASTIC_MAX_RADIUS 18
+int udaseg_train_aug_u8(const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w, float* mid,
+                        float* field, const float* gauss_weights, int radius, const float* mean255, const float* inv_std255,
+                        void* out_images, int cpad, int out_bf16, int64_t* out_masks, int source_pass, int field_pass,
+                        void* stream);
+int udaseg_elastic_field_f32(const int32_t* table, int n, int h, int w, const float* gauss_weights, int radius, float* field,
+                             void* stream);
+
 /* ---- device-side input pipeline: uint8 RGB HWC images [n][h][w][3] (+ uint8 masks [n][h][w], may be NULL) ->
  *      normalised, D4-augmented, channel-padded NHWC model input (fp32, or bf16 when out_bf16) and int64 masks.
  *      Replaces the per-sample host work of src/data/dataset.py:116-138 with the geometric part of

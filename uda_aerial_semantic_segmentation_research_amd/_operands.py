@@ -183,6 +183,12 @@ OPERANDS = {
                              T("out_images", "(bf16 if out_bf16 else f32)", "views*n*h*w*cpad"), I("cpad"), I("out_bf16"),
                              I("source_pass"), S],
     "udaseg_philox4x32_debug": [T("counters", i32, "4*count"), T("keys", i32, "2*count"), T("out", i32, "4*count"), I("count"), S],
+    "udaseg_train_aug_u8": [T("images", u8, "n*h*w*3"), T("masks", u8, "n*h*w", True), T("table", i32, "n*64"), I("n"), I("h"), I("w"),
+                            T("mid", f32, "n*h*w*4", True), T("field", f32, "n*h*w*2", True), H("gauss_weights"), I("radius"),
+                            H("mean255"), H("inv_std255"), T("out_images", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"), I("cpad"),
+                            I("out_bf16"), T("out_masks", i64, "n*h*w", True), I("source_pass"), I("field_pass"), S],
+    "udaseg_elastic_field_f32": [T("table", i32, "n*64"), I("n"), I("h"), I("w"), H("gauss_weights"), I("radius"),
+                                 T("field", f32, "n*h*w*2"), S],
     # ---- prediction (popcount(views) = V, the views per tile)
     "udaseg_predict_gather_u8": [T("image", u8, "h*w*3"), I("h"), I("w"), I("th"), I("tw"), I("rows"), I("cols"), I("sy"), I("sx"),
                                  I("first"), I("tiles"), I("views"), H("mean255"), H("inv_std255"),

@@ -5,8 +5,12 @@ Upstream does this per sample on the host: ``cv2`` decode -> albumentations pipe
 move to one HIP kernel (csrc/data_prep.hip): the D4 geometric augmentations (``RandomRotate90``, ``Flip``, ``Transpose``;
 image and mask together), ``A.Normalize()`` and the layout change -- the output is already the channel-padded NHWC tensor
 the stem convolution reads, handed to ``Unet`` as an ``[N,3,H,W]``-shaped view (no further copy).
-The photometric / elastic augmentations of that basic pipeline (noise, blur, CLAHE, HSV, distortions) are albumentations
-internals with no reference-side definition to match and stay on the host side of the boundary for ``prepare_batch``.
+``prepare_batch`` stops there.  The rest of that basic pipeline (noise, blur, shift-scale-rotate, optical / grid / elastic
+distortion, sharpen / emboss / brightness-contrast, HSV) runs on the device too, through ``train_batch``
+(csrc/train_aug.hip): uint8 frames and uint8 masks in, augmented model input and int64 masks out, image and mask carried
+through the same geometry, from a pipeline this build defines itself ("Training augmentation") with all
+randomness except the per-pixel Philox streams drawn on the host by ``draw_training_params``.  ``DeviceAugmentedLoader`` wraps
+a loader of uint8 batches so that ``SegmentationTrainer`` / ``AdversarialTrainer`` consume it as they are.
 
 Phase 3 (``src/models/unsupervised_trainer.py:100-114``) needs two STRONGLY augmented views of every unlabelled batch
 (``augmentation.py:40-88``); ``strong_views`` makes both on the device from a pipeline this build defines itself (INTEGRATION.md,
@@ -167,10 +171,12 @@ class StrongAugParams:
     layout in include/udaseg.h).  A fresh object has every stage off and the identity D4 code; the ``set_*`` methods switch
     one stage of one sample on, ``draw_strong_params`` fills a table with the reference pipeline's branch probabilities."""
 
+    WORDS = SA_WORDS
+
     def __init__(self, n, h, w, d4_codes=None):
         import numpy as np
         self.n, self.h, self.w = int(n), int(h), int(w)
-        self._i = np.zeros((self.n, SA_WORDS), dtype=np.int32)
+        self._i = np.zeros((self.n, self.WORDS), dtype=np.int32)
         self._f = self._i.view(np.float32)
         self._f[:, _W_AFFINE + 0] = 1.0
         self._f[:, _W_AFFINE + 4] = 1.0
@@ -303,7 +309,7 @@ def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=I
     n, h, w, _ = images_u8.shape
     params = [params_a] if params_b is None else [params_a, params_b]
     for p in params:
-        if not isinstance(p, StrongAugParams):
+        if not isinstance(p, StrongAugParams) or p.WORDS != SA_WORDS:
             raise ValueError("strong_views: parameters must be StrongAugParams (see draw_strong_params)")
         p.check(n, h, w)
     views = len(params)
@@ -336,3 +342,211 @@ def philox4x32(counters, keys):
     out = torch.empty((count, 4), device=counters.device, dtype=torch.int32)
     check(ops.udaseg_philox4x32_debug(counters.contiguous(), keys.contiguous(), out, count, None), "philox4x32_debug")
     return out
+
+
+# ------------------------------------------------------------------------------------- labelled training augmentation
+# Record of udaseg_train_aug_u8 (include/udaseg.h): words 0..31 are the strong record, the rest the distortion stage; the
+# pipeline is defined in INTEGRATION.md, "Training augmentation".
+TA_WORDS = 64
+TA_DISTORT = 32
+DISTORT_OPTICAL, DISTORT_GRID, DISTORT_ELASTIC = 1, 2, 3
+ELASTIC_MAX_RADIUS = 18
+_W_DISTORT_KIND, _W_OPTICAL, _W_GRID_X, _W_GRID_Y, _W_ELASTIC_ALPHA, _W_ELASTIC_KEY = 32, 33, 36, 42, 48, 50
+
+
+def gaussian_weights(sigma):
+    """The elastic field's filter: radius ``R = ceil(3 sigma)``, ``exp(-i^2 / (2 sigma^2))`` for i = -R..R normalised to sum 1 in
+    float64, then rounded once to fp32.  -> (fp32 numpy array of 2R + 1 taps, R)."""
+    import math
+    import numpy as np
+    if not sigma > 0:
+        raise ValueError("gaussian_weights: sigma must be positive")
+    radius = int(math.ceil(3.0 * sigma))
+    if radius > ELASTIC_MAX_RADIUS:
+        raise ValueError(f"gaussian_weights: radius ceil(3 sigma) = {radius} is above {ELASTIC_MAX_RADIUS}")
+    i = np.arange(-radius, radius + 1, dtype=np.float64)
+    wts = np.exp(-i * i / (2.0 * float(sigma) ** 2))
+    return (wts / wts.sum()).astype(np.float32), radius
+
+
+class TrainAugParams(StrongAugParams):
+    """One parameter record per sample for ``train_batch``: an int32 ``[n, 64]`` host table whose words 0..31 are exactly the
+    ``StrongAugParams`` record (same setters) and whose words 32.. hold the distortion stage: at most one of
+    ``set_optical`` / ``set_grid`` / ``set_elastic`` per sample."""
+    WORDS = TA_WORDS
+
+    def __init__(self, n, h, w, d4_codes=None):
+        import numpy as np
+        super().__init__(n, h, w, d4_codes)
+        self._kinds = np.zeros(self.n, dtype=np.int32)        # bit k: set_<kind k> was called for the sample
+
+    def _distort(self, i, kind):
+        self._i[i, _W_FLAGS] |= TA_DISTORT
+        self._i[i, _W_DISTORT_KIND] = kind
+        self._kinds[i] |= 1 << kind
+
+    def set_optical(self, i, k, dx=0.0, dy=0.0):
+        """Radial distortion ``1 + k r^2 + k r^4`` about the frame centre moved by (``dx``, ``dy``) pixels."""
+        self._distort(i, DISTORT_OPTICAL)
+        self._f[i, _W_OPTICAL:_W_OPTICAL + 3] = (k, dx, dy)
+
+    def set_grid(self, i, steps_x, steps_y):
+        """Six step factors per axis: cell ``i`` (of width ``side // 5``) is read ``steps[i]`` times as fast as it is written."""
+        if len(steps_x) != 6 or len(steps_y) != 6:
+            raise ValueError("set_grid: six step factors per axis")
+        self._distort(i, DISTORT_GRID)
+        self._f[i, _W_GRID_X:_W_GRID_X + 6] = steps_x
+        self._f[i, _W_GRID_Y:_W_GRID_Y + 6] = steps_y
+
+    def set_elastic(self, i, alpha, key):
+        """Displacement ``alpha`` x the smoothed Philox field under ``key`` (two 32-bit words)."""
+        self._distort(i, DISTORT_ELASTIC)
+        self._f[i, _W_ELASTIC_ALPHA] = alpha
+        self._i.view("uint32")[i, _W_ELASTIC_KEY:_W_ELASTIC_KEY + 2] = [int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF]
+
+    @property
+    def distortion(self):
+        """Per sample: 0 none, 1 optical, 2 grid, 3 elastic."""
+        import numpy as np
+        return np.where((self._i[:, _W_FLAGS] & TA_DISTORT) != 0, self._i[:, _W_DISTORT_KIND], 0)
+
+    def check(self, n, h, w):
+        super().check(n, h, w)
+        kind = self.distortion
+        if bool(((self._kinds & (self._kinds - 1)) != 0).any()):
+            raise ValueError("train_batch: at most one distortion kind per sample")
+        on = (self._i[:, _W_FLAGS] & TA_DISTORT) != 0
+        if bool((on & ((kind < DISTORT_OPTICAL) | (kind > DISTORT_ELASTIC))).any()):
+            raise ValueError("train_batch: distortion kinds are 1 optical, 2 grid, 3 elastic")
+        if min(h, w) < 5 and bool((kind == DISTORT_GRID).any()):
+            raise ValueError("train_batch: grid distortion needs frames of at least 5 x 5")
+
+
+def draw_training_params(n, h, w, generator=None):
+    """One record per sample with the rates and ranges of the reference's basic training pipeline (``augmentation.py:10-35``;
+    ``OneOf(p=P)`` as in ``draw_strong_params``).  Drawn on the host from ``generator`` (a CPU ``torch.Generator``).  CLAHE is
+    drawn too and recorded as a no-op (word 21), so every other rate is the reference's.  On non-square frames the transpose bit
+    of the D4 code is dropped; frames with a side below 5 are refused (the grid child needs five cells per axis)."""
+    import math
+    if min(h, w) < 5:
+        raise ValueError("draw_training_params: frames of at least 5 x 5 (grid distortion)")
+    g = generator
+    codes = random_d4_codes(n, g).numpy()
+    if h != w:
+        codes = codes & ~TRANSPOSE
+    u = torch.rand(n, 40, generator=g, dtype=torch.float64).numpy()
+    keys = torch.randint(0, 1 << 32, (n, 4), generator=g, dtype=torch.int64).numpy()
+    P = TrainAugParams(n, h, w, codes)
+    for i in range(n):
+        r = u[i]
+        if r[0] < 0.2:                                       # OneOf(GaussNoise(10..50), GaussNoise()), p = 0.2: variance in (10, 50)
+            P.set_noise(i, math.sqrt(10.0 + 40.0 * r[1]), keys[i, :2])
+        if r[2] < 0.2:                                       # OneOf(MotionBlur 0.2, MedianBlur(3) 0.1, Blur(3) 0.1), p = 0.2
+            if r[3] < 0.5:
+                P.set_blur(i, BLUR_MOTION, 3 if r[4] < 0.5 else 5, min(int(r[5] * 4), 3))
+            else:
+                P.set_blur(i, BLUR_MEDIAN if r[3] < 0.75 else BLUR_BOX, 3)
+        if r[6] < 0.2:                                       # ShiftScaleRotate(0.0625, 0.2, 45), p = 0.2
+            P.set_affine(i, (2 * r[7] - 1) * 0.0625 * w, (2 * r[8] - 1) * 0.0625 * h, 1.0 + (2 * r[9] - 1) * 0.2, (2 * r[10] - 1) * 45.0)
+        if r[11] < 0.2:                                      # OneOf(Optical 0.3, Grid 0.1, Elastic 0.3), p = 0.2
+            if r[12] < 3.0 / 7.0:
+                P.set_optical(i, (2 * r[13] - 1) * 0.05, (2 * r[14] - 1) * 0.05, (2 * r[15] - 1) * 0.05)
+            elif r[12] < 4.0 / 7.0:
+                P.set_grid(i, 1.0 + (2 * r[16:22] - 1) * 0.3, 1.0 + (2 * r[22:28] - 1) * 0.3)
+            else:
+                P.set_elastic(i, 120.0, keys[i, 2:])
+        if r[28] < 0.3:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast), equal, p = 0.3
+            child = min(int(r[29] * 4), 3)
+            if child == 0:
+                P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
+            elif child == 1:
+                P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[30], 0.5 + 0.5 * r[31])
+            elif child == 2:
+                P.set_stage5(i, STAGE5_EMBOSS, 0.2 + 0.3 * r[30], 0.2 + 0.5 * r[31])
+            else:
+                P.set_stage5(i, STAGE5_BRIGHTNESS_CONTRAST, (2 * r[30] - 1) * 0.2, (2 * r[31] - 1) * 0.2)
+        if r[32] < 0.3:                                      # HueSaturationValue(20, 30, 20), p = 0.3
+            P.set_hsv(i, (2 * r[33] - 1) * 20.0, (2 * r[34] - 1) * 30.0, (2 * r[35] - 1) * 20.0)
+    return P
+
+
+def _weights_array(sigma):
+    wts, radius = gaussian_weights(sigma)
+    return (ctypes.c_float * len(wts))(*[float(v) for v in wts]), radius
+
+
+def elastic_field(params, elastic_sigma=6.0):
+    """The smoothed displacement field of the samples of ``params`` (a ``TrainAugParams``) that are on elastic: fp32
+    ``[n, h, w, 2]`` (x, y) on the GPU; samples on anything else stay zero.  For tests and tools."""
+    _lib.require_gpu()
+    if not isinstance(params, TrainAugParams):
+        raise ValueError("elastic_field: parameters must be TrainAugParams")
+    n, h, w = params.n, params.h, params.w
+    params.check(n, h, w)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    wts, radius = _weights_array(elastic_sigma)
+    field = torch.zeros((n, h, w, 2), device=dev, dtype=torch.float32)
+    check(ops.udaseg_elastic_field_f32(params.table.to(dev), n, h, w, wts, radius, field, None), "elastic_field_f32")
+    return field
+
+
+def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=torch.float32, elastic_sigma=6.0,
+                mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=255.0):
+    """images_u8 ``[N,H,W,3]`` uint8, masks_u8 ``[N,H,W]`` uint8 or None (host or device), params: a ``TrainAugParams`` or None
+    (drawn with ``draw_training_params(N, H, W, generator)``) -> ``(images, masks)`` exactly in ``prepare_batch``'s output form:
+    the ``[N,3,H,W]``-shaped view of the padded NHWC buffer in ``dtype`` and int64 masks (or None), augmented by the training
+    pipeline of INTEGRATION.md with image and mask carried through the same geometry.  At most three kernel launches and no host
+    synchronisation; a record with every stage off equals ``prepare_batch`` bit for bit."""
+    _lib.require_gpu()
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"train_batch: images must be uint8 [N,H,W,3], got {getattr(images_u8, 'dtype', type(images_u8))} "
+                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("train_batch: dtype must be torch.float32 or torch.bfloat16")
+    n, h, w, _ = images_u8.shape
+    if masks_u8 is not None and (not torch.is_tensor(masks_u8) or masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != (n, h, w)):
+        raise ValueError(f"train_batch: masks must be uint8 [{n},{h},{w}], got {getattr(masks_u8, 'dtype', type(masks_u8))} "
+                         f"{tuple(getattr(masks_u8, 'shape', ()))}")
+    if params is None:
+        params = draw_training_params(n, h, w, generator)
+    if not isinstance(params, TrainAugParams):
+        raise ValueError("train_batch: parameters must be TrainAugParams (64-word records, see draw_training_params)")
+    params.check(n, h, w)
+    host = params.table
+    source_pass = int(bool((host[:, _W_FLAGS] & (SA_NOISE | SA_BLUR)).any()))
+    field_pass = int(bool((params.distortion == DISTORT_ELASTIC).any()))
+    wts, radius = _weights_array(elastic_sigma) if field_pass else (None, 0)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    img = images_u8.to(dev, non_blocking=True).contiguous()
+    msk = None if masks_u8 is None else masks_u8.to(dev, non_blocking=True).contiguous()
+    table = host.to(dev, non_blocking=True)
+    cpad = 8 if dtype == torch.bfloat16 else 4
+    out = torch.empty((n, h, w, cpad), device=dev, dtype=dtype)
+    out_m = None if msk is None else torch.empty((n, h, w), device=dev, dtype=torch.int64)
+    mid = torch.empty(n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
+    field = torch.empty(n * h * w * 2, device=dev, dtype=torch.float32) if field_pass else None
+    m255, r255 = normalize_constants(mean, std, max_pixel_value)
+    check(ops.udaseg_train_aug_u8(img, msk, table, n, h, w, mid, field, wts, radius, m255, r255, out, cpad,
+                                  int(dtype == torch.bfloat16), out_m, source_pass, field_pass, None), "train_aug_u8")
+    mark_padded_input(out)
+    return out.permute(0, 3, 1, 2)[:, :3], out_m
+
+
+class DeviceAugmentedLoader:
+    """Wraps a loader of uint8 ``(images [N,H,W,3], masks [N,H,W])`` batches -- or of images alone -- and yields ``train_batch``'s
+    output in the same structure: ``(images, masks)`` pairs, or image tensors.  Fresh records are drawn for every batch from
+    ``generator``.  ``SegmentationTrainer.train_epoch`` / ``AdversarialTrainer.train_epoch`` consume it as they are."""
+
+    def __init__(self, loader, dtype=torch.float32, generator=None, elastic_sigma=6.0):
+        self.loader, self.dtype, self.generator, self.elastic_sigma = loader, dtype, generator, elastic_sigma
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if torch.is_tensor(batch):
+                yield train_batch(batch, None, None, self.generator, self.dtype, self.elastic_sigma)[0]
+            else:
+                images, masks = batch
+                yield train_batch(images, masks, None, self.generator, self.dtype, self.elastic_sigma)
