@@ -265,6 +265,34 @@ int udaseg_ce_fwd_bwd(const float* logits, const int64_t* target, int64_t pixels
                       float* dlogits, float* colsum_partials, float* colsum, void* stream);
 int udaseg_scale_unless_one(float* x, int64_t count, float* x2, int count2, const float* g, void* stream);
 
+/* ---- cross entropy with options: torch.nn.functional.cross_entropy(weight, ignore_index, reduction, label_smoothing) ----
+ * valid(p): target[p] != ignore_index (when has_ignore) and 0 <= target[p] < classes.  Departure from torch: an out-of-range
+ * target that is not ignore_index raises no error (a launch that never synchronises cannot); it is void, and counted.
+ *   l_p       = (1-eps)*w[t]*(-logp[t]) + (eps/classes)*(-sum_c w[c]*logp[c])  at a valid pixel, exactly 0 at a void one
+ *   dl_p/dz_k = (1-eps)*w[t]*(P_k - [k==t]) + (eps/classes)*(P_k*sum_c w[c] - w[k]), exactly 0 at a void pixel in all ldc lanes
+ *   'sum' = sum_p l_p; 'mean' (mean != 0) = 'sum' / D, D = sum over valid p of w[t_p] (all void: NaN loss, zero gradient).
+ * weight: `classes` floats or NULL (all 1); 0 <= eps <= 1; ignore_index: any int64; the plain udaseg_ce_* calls are untouched.
+ *
+ * udaseg_ce_target_stats reads ONLY the targets (8 B/pixel): denom[0] = D in f64 and stats[0..2] = {valid, void (== ignore_index),
+ * invalid (out of range)} pixel counts, by fixed-order sums (same bits on every call); partials: 4*udaseg_ce_partials() doubles. */
+int udaseg_ce_target_stats(const int64_t* target, const float* weight, int64_t pixels, int classes, int has_ignore,
+                           int64_t ignore_index, double* partials, double* denom, int64_t* stats, void* stream);
+/* ONE pass over the logits (ldc <= 32), as udaseg_ce_fwd_bwd: loss, dlogits for an upstream gradient of 1 -- already divided by
+ * *denom when mean != 0 (denom may be NULL otherwise) -- and the optional column sums (the head conv's bias gradient). */
+int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes, int ldc,
+                          int has_ignore, int64_t ignore_index, float eps, int mean, const double* denom, double* partials,
+                          float* loss, float* dlogits, float* colsum_partials, float* colsum, void* stream);
+/* Two-pass route (no_grad forwards, ldc > 32, reduction 'none', a second backward): lse[p] saved (0 at void pixels);
+ * loss (1 float, reduced) and / or loss_px[p] = l_p ('none'): at least one of the two. */
+int udaseg_ce_opt_fwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes, int ldc,
+                      int has_ignore, int64_t ignore_index, float eps, int mean, const double* denom, float* lse, double* partials,
+                      float* loss, float* loss_px, void* stream);
+/* dlogits[p] = (*grad_out, NULL = 1) * (grad_px[p], NULL = 1: the per-pixel upstream gradient of 'none') * dl_p/dz (/ *denom when
+ * mean != 0); column sums optional, ldc <= 32 only. */
+int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, const float* weight, const float* lse, const float* grad_out,
+                      const float* grad_px, int64_t pixels, int classes, int ldc, int has_ignore, int64_t ignore_index, float eps,
+                      int mean, const double* denom, float* dlogits, float* colsum_partials, float* colsum, void* stream);
+
 /* ---- the reference's other segmentation losses (src/models/losses.py), same logits layout as udaseg_ce_* (ldc <= 32) ----
  * udaseg_seg_partials(): doubles of scratch the *_fwd calls below need in `partials`. */
 int udaseg_seg_partials(void);
@@ -288,6 +316,21 @@ int udaseg_focal_fwd(const float* logits, const int64_t* target, const float* cl
 int udaseg_focal_bwd(const float* logits, const int64_t* target, const float* class_weights, float alpha, float gamma,
                      const float* grad_out, float weight, int64_t pixels, int classes, int ldc, float* dlogits,
                      int accumulate, void* stream);
+/* The four calls above with void labels: a pixel whose target is ignore_index (any int64) or lies outside [0, classes) is left out
+ * of all three Dice sums, has a focal term of 0 ('mean' still divides by `pixels`; class_weights[t] is not read for it) and a
+ * gradient of exactly 0 in all ldc lanes. */
+int udaseg_dice_fwd_ignore(const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes, int ldc,
+                           float smooth, float eps, int pooled, double* sums, float* coef, float* loss, int64_t ignore_index,
+                           void* stream);
+int udaseg_dice_bwd_ignore(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float weight,
+                           int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits, int accumulate,
+                           int64_t ignore_index, void* stream);
+int udaseg_focal_fwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha, float gamma,
+                            int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss, int accumulate,
+                            int64_t ignore_index, void* stream);
+int udaseg_focal_bwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha, float gamma,
+                            const float* grad_out, float weight, int64_t pixels, int classes, int ldc, float* dlogits,
+                            int accumulate, int64_t ignore_index, void* stream);
 /* ConsistencyLoss (losses.py:53-108): p_i = softmax(z_i / T);
  * loss = (KL(p2||p1) + KL(p1||p2)) / (2 * batch)  (F.kl_div(..., reduction='batchmean') both ways, averaged) */
 int udaseg_consistency_fwd(const float* z1, const float* z2, float temperature, int batch, int64_t pixels, int classes,

@@ -1,0 +1,437 @@
+"""Void labels, class weights and label smoothing in the losses (csrc/losses.hip ce_opt_* kernels, csrc/losses_seg.hip IGN
+instantiations) against torch on the CPU in float64, computed from the same seeded fp32 inputs.
+
+Definition: ``torch.nn.functional.cross_entropy(z, t, weight, ignore_index=..., reduction=..., label_smoothing=...)``.  torch raises
+for an out-of-range label that is not ``ignore_index``; the kernels treat it as void, so the oracle is handed those labels
+remapped to its ``ignore_index``.  Dice and focal have no torch form with void labels: ``dice_restated`` / ``focal_restated`` below
+restate them (void pixels out of all three Dice sums; ``F.cross_entropy(..., ignore_index)`` in the focal line, 'mean' over N*H*W).
+
+Bars (tests/test_gpu_losses.py's): values within 1e-5 relative, gradients within 1e-3 relative in max-norm; a per-pixel loss map
+('none') is a value and is held to 1e-5 of its largest entry.  fp32 rounding (6e-8) of logits of a few units through a log-sum-exp
+and one subtraction leaves about 1e-6 of that largest entry.
+"""
+import itertools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 23, 17, 19),      # 323 pixels: one full 256-chunk plus a tail; ldc 24 with one padding lane
+          (2, 5, 32, 32),       # ldc 8
+          (2, 2, 16, 16),       # ldc 4
+          (1, 32, 16, 24),      # ldc 32, the fused boundary
+          (1, 40, 16, 16),      # two-pass route only
+          (2, 23, 384, 384)]    # 294 912 pixels > 1024 blocks x 256: the grid-stride loop runs twice
+PATTERNS = ("no_void", "random_void", "void_run", "all_void", "invalid")
+IGNORES = (255, -100, 0)
+VALUE_TOL, GRAD_TOL = 1e-5, 1e-3
+WORST = {"value": 0.0, "grad": 0.0}
+
+
+@pytest.fixture(scope="module")
+def L():
+    from uda_aerial_semantic_segmentation_research_amd import _lib, losses
+    _lib.require_gpu()
+    return losses
+
+
+def ceil4(c):
+    return (c + 3) // 4 * 4
+
+
+_INPUTS = {}
+
+
+def inputs(shape, pattern, ign):
+    """Seeded fp32 logits, int64 labels, class weights (rand + 0.1, one class weight 0) and an upstream map; made once per case."""
+    key = (shape, pattern, ign)
+    if key not in _INPUTS:
+        n, c, h, w = shape
+        g = torch.Generator().manual_seed(1000 * SHAPES.index(shape) + 10 * PATTERNS.index(pattern) + IGNORES.index(ign))
+        z = torch.randn(n, c, h, w, generator=g) * 3.0
+        t = torch.randint(0, c, (n, h, w), generator=g)
+        flat = t.view(-1)
+        r = torch.rand(flat.numel(), generator=g)
+        if pattern == "random_void":
+            flat[r < 0.3] = ign
+        elif pattern == "void_run":
+            flat[: min(flat.numel(), 256 + 37)] = ign          # covers the whole aligned chunk [0, 256)
+        elif pattern == "all_void":
+            flat[:] = ign
+        elif pattern == "invalid":
+            flat[r < 0.2] = ign
+            flat[(r >= 0.2) & (r < 0.25)] = c
+            flat[(r >= 0.25) & (r < 0.3)] = c + 1
+        wt = torch.rand(c, generator=g) + 0.1
+        wt[c // 2] = 0.0
+        up = torch.rand(n, h, w, generator=g) + 0.5
+        _INPUTS[key] = (z, t, wt, up)
+    return _INPUTS[key]
+
+
+def void_mask(t, c, ign):
+    return (t == ign) | (t < 0) | (t >= c)
+
+
+def oracle_ce(z, t, wt, ign, reduction, eps, up=None):
+    """float64 torch on the CPU -> (value, gradient)."""
+    c = z.shape[1]
+    ign_ref = -100 if ign is None else ign
+    tr = t.clone()
+    tr[void_mask(t, c, ign_ref)] = ign_ref
+    zd = z.double().requires_grad_(True)
+    out = F.cross_entropy(zd, tr, None if wt is None else wt.double(), ignore_index=ign_ref, reduction=reduction, label_smoothing=eps)
+    (out * up.double()).sum().backward() if reduction == "none" else out.backward()
+    return out.detach(), zd.grad
+
+
+def relerr(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
+
+
+def check_against_oracle(L, shape, pattern, ign, use_w, eps, reduction):
+    z, t, wt, up = inputs(shape, pattern, ign)
+    c = shape[1]
+    vref, gref = oracle_ce(z, t, wt if use_w else None, ign, reduction, eps, up)
+    crit = L.CrossEntropyLoss(weight=wt if use_w else None, ignore_index=ign, reduction=reduction, label_smoothing=eps).cuda()
+    assert crit.route == "options"
+    tg = t.cuda()
+    runs = []
+    for _ in range(2):
+        zg = z.cuda().requires_grad_(True)
+        out = crit(zg, tg)
+        (out * up.cuda()).sum().backward() if reduction == "none" else out.backward()
+        runs.append((out.detach().clone(), zg.grad.clone(), crit.last_target_stats.clone()))
+    (val, grad, stats), (val2, grad2, stats2) = runs
+    tag = (shape, pattern, ign, use_w, eps, reduction)
+    # two calls: the same bits (NaN == NaN for the all-void mean)
+    assert torch.equal(torch.nan_to_num(val, nan=-7.0), torch.nan_to_num(val2, nan=-7.0)), tag
+    assert torch.equal(torch.nan_to_num(grad, nan=-7.0), torch.nan_to_num(grad2, nan=-7.0)), tag
+    assert torch.equal(stats, stats2), tag
+    # counters against numpy
+    tn = t.numpy()
+    n_void = int((tn == ign).sum())
+    n_valid = int(((tn >= 0) & (tn < c) & (tn != ign)).sum())
+    assert stats.cpu().tolist() == [n_valid, n_void, tn.size - n_valid - n_void], (tag, stats.cpu().tolist())
+    void = void_mask(t, c, ign)
+    # exact conditions at void / invalid pixels
+    gv = grad.cpu().permute(0, 2, 3, 1)[void]
+    assert gv.numel() == 0 or float(gv.abs().max()) == 0.0, (tag, "gradient at void pixels")
+    if reduction == "none":
+        assert val.dtype == torch.float32 and tuple(val.shape) == tuple(t.shape)
+        assert void.sum() == 0 or float(val.cpu()[void].abs().max()) == 0.0, (tag, "l_p at void pixels")
+    if n_valid == 0:
+        assert float(grad.abs().max()) == 0.0, (tag, "all void: zero gradient")
+        if reduction == "mean":
+            assert bool(torch.isnan(val)) and bool(torch.isnan(vref)), tag
+        else:
+            assert float(val.abs().max()) == 0.0 and float(vref.abs().max()) == 0.0, tag
+        return
+    if reduction == "mean" and bool(torch.isnan(vref)):
+        # D == 0 although pixels are valid (every one of them of the class whose weight is 0): 0 / 0, NaN in torch and here
+        assert use_w and float(wt[t[~void]].abs().max()) == 0.0 and bool(torch.isnan(val)), tag
+        return
+    ev, eg = relerr(val, vref), relerr(grad, gref)
+    WORST["value"], WORST["grad"] = max(WORST["value"], ev), max(WORST["grad"], eg)
+    assert ev < VALUE_TOL, (tag, "value", ev)
+    assert eg < GRAD_TOL, (tag, "gradient", eg)
+
+
+@pytest.mark.parametrize("ign", IGNORES)
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_optioned_cross_entropy_matches_torch_float64(L, shape, pattern, ign):
+    """Weights on/off x eps {0, 0.1} x the three reductions ('none' backpropagated with a random upstream map)."""
+    for use_w, eps, reduction in itertools.product((True, False), (0.0, 0.1), ("mean", "sum", "none")):
+        check_against_oracle(L, shape, pattern, ign, use_w, eps, reduction)
+    print(f"{shape} {pattern} ignore_index={ign}: worst so far value {WORST['value']:.2e}, gradient {WORST['grad']:.2e}")
+
+
+def test_void_pixels_get_no_gradient_and_leave_the_mean(L):
+    """The defect this closes, stated directly: a pixel labelled 255 must add nothing to the loss, to the 1/D scale or to the
+    gradient.  (The plain loss counts its whole log-sum-exp, a full softmax row of gradient and one more pixel in the mean.)"""
+    shape = SHAPES[0]
+    z, t, _, _ = inputs(shape, "random_void", 255)
+    crit = L.CrossEntropyLoss(ignore_index=255)
+    zg = z.cuda().requires_grad_(True)
+    loss = crit(zg, t.cuda())
+    loss.backward()
+    void = t == 255
+    assert void.any() and float(zg.grad.cpu().permute(0, 2, 3, 1)[void].abs().max()) == 0.0
+    keep = ~void
+    ref = F.cross_entropy(z.double().permute(0, 2, 3, 1)[keep], t[keep])          # the mean over the labelled pixels alone
+    assert abs(loss.item() - ref.item()) < VALUE_TOL * abs(ref.item())
+
+
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_kernels_write_exact_zeros_in_all_ldc_lanes(L, shape, pattern):
+    """The launches themselves, on NaN-filled outputs: void and invalid pixels get 0 in ALL ldc lanes (padding lanes included),
+    valid pixels get 0 in the padding lanes, lse / l_p are 0 at void pixels; fused (ldc <= 32) and two-pass routes."""
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    n, c, h, w = shape
+    ign = 255
+    z, t, wt, up = inputs(shape, pattern, ign)
+    ldc, pixels = ceil4(c), n * h * w
+    buf = torch.zeros(n, h, w, ldc)
+    buf[..., :c] = z.permute(0, 2, 3, 1)
+    buf[..., c:] = float("nan")                                    # the padding lanes of the logits must never be read into a result
+    buf, tg, wg, upg = buf.cuda(), t.cuda(), wt.cuda(), up.cuda().reshape(-1).contiguous()
+    np_ = K.ops.udaseg_ce_partials()
+    f64 = dict(device="cuda", dtype=torch.float64)
+    denom, stats = torch.empty(1, **f64), torch.empty(3, device="cuda", dtype=torch.int64)
+    K.ce_target_stats(tg, wg, pixels, c, ign, torch.empty(4 * np_, **f64), denom, stats)
+    void = void_mask(t, c, ign).reshape(-1)
+    results = []
+    if ldc <= 32:
+        dl = torch.full((pixels, ldc), float("nan"), device="cuda")
+        loss, colsum = torch.empty((), device="cuda"), torch.empty(ldc, device="cuda")
+        K.ce_opt_fwd_bwd(buf, tg, wg, pixels, c, ldc, ign, 0.1, True, denom, torch.empty(np_, **f64), loss, dl,
+                         torch.empty(np_ * ldc, device="cuda"), colsum)
+        results.append(("fused", dl, colsum))
+    lse = torch.full((pixels,), float("nan"), device="cuda")
+    lpx = torch.full((pixels,), float("nan"), device="cuda")
+    K.ce_opt_fwd(buf, tg, wg, pixels, c, ldc, ign, 0.1, False, None, lse, torch.empty(np_, **f64), None, lpx)
+    assert not torch.isnan(lse).any() and not torch.isnan(lpx).any()
+    assert void.sum() == 0 or (float(lse.cpu()[void].abs().max()) == 0.0 and float(lpx.cpu()[void].abs().max()) == 0.0)
+    dl2 = torch.full((pixels, ldc), float("nan"), device="cuda")
+    colsum2 = torch.empty(ldc, device="cuda") if ldc <= 32 else None
+    K.ce_opt_bwd(buf, tg, wg, lse, None, upg, pixels, c, ldc, ign, 0.1, False, None, dl2,
+                 torch.empty(np_ * ldc, device="cuda") if ldc <= 32 else None, colsum2)
+    results.append(("two-pass", dl2, colsum2))
+    for name, d, cs in results:
+        dc = d.cpu()
+        assert not torch.isnan(dc).any(), name
+        assert void.sum() == 0 or float(dc[void].abs().max()) == 0.0, (name, "void rows")
+        assert ldc == c or float(dc[:, c:].abs().max()) == 0.0, (name, "padding lanes")
+        if cs is not None:                                         # the bias gradient: column sums of what was written
+            ref = dc.double().sum(0)
+            assert float((cs.cpu().double() - ref).abs().max()) <= 1e-4 * max(float(ref.abs().max()), 1e-30), name
+
+
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[3], SHAPES[5]], ids=lambda s: "x".join(map(str, s)))
+def test_fused_and_two_pass_routes_agree(L, shape, monkeypatch):
+    z, t, wt, _ = inputs(shape, "random_void", 255)
+    crit = L.CrossEntropyLoss(weight=wt, ignore_index=255, label_smoothing=0.1).cuda()
+    out = {}
+    for fuse in (True, False):
+        monkeypatch.setattr(L, "FUSE_CE_BACKWARD", fuse)
+        zg = z.cuda().requires_grad_(True)
+        loss = crit(zg, t.cuda())
+        loss.backward()
+        out[fuse] = (loss.detach(), zg.grad)
+    ev, eg = relerr(out[True][0], out[False][0]), relerr(out[True][1], out[False][1])
+    print(f"{shape}: fused vs two-pass value {ev:.2e}, gradient {eg:.2e}")
+    assert ev < VALUE_TOL and eg < GRAD_TOL
+    with torch.no_grad():                                          # a no_grad forward takes the two-pass forward
+        monkeypatch.setattr(L, "FUSE_CE_BACKWARD", True)
+        assert relerr(crit(z.cuda(), t.cuda()), out[True][0]) < VALUE_TOL
+
+
+def test_upstream_gradient_and_second_backward(L):
+    """``loss * 3`` (an upstream gradient that is not 1) and a second backward through a retained graph."""
+    shape = SHAPES[0]
+    z, t, wt, _ = inputs(shape, "random_void", 255)
+    _, gref = oracle_ce(z, t, wt, 255, "mean", 0.1)
+    crit = L.CrossEntropyLoss(weight=wt, ignore_index=255, label_smoothing=0.1).cuda()
+    zg = z.cuda().requires_grad_(True)
+    loss = crit(zg, t.cuda())
+    (loss * 3.0).backward(retain_graph=True)
+    assert relerr(zg.grad, 3.0 * gref) < GRAD_TOL
+    zg.grad = None
+    loss.backward()
+    assert relerr(zg.grad, gref) < GRAD_TOL
+
+
+def test_narrow_label_dtypes_are_cast(L):
+    shape = SHAPES[1]
+    z, t, _, _ = inputs(shape, "random_void", 255)
+    crit = L.CrossEntropyLoss(ignore_index=255)
+    a = crit(z.cuda(), t.cuda())
+    assert torch.equal(a, crit(z.cuda(), t.to(torch.uint8).cuda())) and torch.equal(a, crit(z.cuda(), t.to(torch.int32).cuda()))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_default_module_is_the_plain_kernels_bit_for_bit(L, shape):
+    """``CrossEntropyLoss()`` on in-range labels: value and gradient ``torch.equal`` to the plain launches called directly."""
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    n, c, h, w = shape
+    z, t, _, _ = inputs(shape, "no_void", 255)
+    ldc, pixels = ceil4(c), n * h * w
+    crit = L.CrossEntropyLoss()
+    assert crit.route == "plain"
+    zg = z.cuda().requires_grad_(True)
+    loss = crit(zg, t.cuda())
+    loss.backward()
+    assert crit.last_target_stats is None
+    buf = torch.zeros(n, h, w, ldc)
+    buf[..., :c] = z.permute(0, 2, 3, 1)
+    buf, tg = buf.cuda(), t.cuda()
+    np_ = K.ops.udaseg_ce_partials()
+    parts, ref_loss = torch.empty(np_, device="cuda", dtype=torch.float64), torch.empty((), device="cuda")
+    dl = torch.empty(n, h, w, ldc, device="cuda")
+    if ldc <= 32:
+        K.ce_fwd_bwd(buf, tg, pixels, c, ldc, parts, ref_loss, dl, torch.empty(np_ * ldc, device="cuda"), torch.empty(ldc, device="cuda"))
+    else:
+        lse = torch.empty(pixels, device="cuda")
+        K.ce_fwd(buf, tg, pixels, c, ldc, lse, parts, ref_loss)
+        K.ce_bwd(buf, tg, lse, torch.ones((), device="cuda"), pixels, c, ldc, dl)
+    assert torch.equal(loss.detach(), ref_loss)
+    assert torch.equal(zg.grad, dl.permute(0, 3, 1, 2)[:, :c])
+
+
+def test_head_bias_gradient_comes_from_the_optioned_column_sums(L):
+    """r18 Unet, 2x3x64x64, train mode, weights + ignore_index=255 + smoothing, 30 % void: the head conv's bias gradient (handed
+    over through COLSUM_SIDE_TABLE by the optioned pass) equals the pixel sum of torch's float64 gradient of the same logits."""
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(7)
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23).cuda().train()
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 3, 64, 64, generator=g)
+    t = torch.randint(0, 23, (2, 64, 64), generator=g)
+    t[torch.rand(2, 64, 64, generator=g) < 0.3] = 255
+    wt = torch.rand(23, generator=g) + 0.1
+    crit = L.CrossEntropyLoss(weight=wt, ignore_index=255, label_smoothing=0.1).cuda()
+    logits = net(x.cuda())
+    loss = crit(logits, t.cuda())
+    loss.backward()
+    vref, gref = oracle_ce(logits.detach().float().cpu(), t, wt, 255, "mean", 0.1)
+    assert abs(loss.item() - vref.item()) < VALUE_TOL * abs(vref.item())
+    bias_grad = net.segmentation_head[0].bias.grad
+    err = relerr(bias_grad, gref.sum(dim=(0, 2, 3)))
+    print(f"head bias gradient vs float64 pixel sum: {err:.2e}")
+    assert err < 1e-3
+
+
+def test_trainer_runs_on_masks_with_void_labels(L):
+    """SegmentationTrainer(criterion=...) on a two-batch uint8 loader through data.train_batch with 255 in the masks."""
+    from uda_aerial_semantic_segmentation_research_amd import data as D
+    from uda_aerial_semantic_segmentation_research_amd.optim import FusedAdam
+    from uda_aerial_semantic_segmentation_research_amd.train import SegmentationTrainer
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(11)
+    g = torch.Generator().manual_seed(5)
+    batches = []
+    for _ in range(2):
+        img = torch.randint(0, 256, (2, 64, 64, 3), generator=g, dtype=torch.uint8)
+        msk = torch.randint(0, 23, (2, 64, 64), generator=g, dtype=torch.uint8)
+        msk[:, :16] = 255
+        batches.append((img, msk))
+    loader = D.DeviceAugmentedLoader(batches, generator=torch.Generator().manual_seed(9))
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23)
+    crit = L.CrossEntropyLoss(weight=torch.rand(23, generator=g) + 0.1, ignore_index=255, label_smoothing=0.1)
+    tr = SegmentationTrainer(net, torch.device("cuda", 0), criterion=crit)
+    assert tr.criterion is crit
+    train_loss = tr.train_epoch(loader, FusedAdam(net.parameters(), lr=1e-4), 1)
+    n_valid, n_void, n_invalid = crit.last_target_stats.tolist()
+    assert np.isfinite(train_loss) and n_void > 0 and n_invalid == 0 and n_valid + n_void == 2 * 64 * 64
+    val = tr.validate(loader)
+    assert np.isfinite(val["loss"]) and crit.last_target_stats[1].item() > 0
+
+
+# ------------------------------------------------------------------------------------------------- Dice / focal
+def dice_restated(z, t, ign, smooth=1.0):
+    c = z.shape[1]
+    valid = ~void_mask(t, c, ign)
+    p = torch.softmax(z, dim=1) * valid.unsqueeze(1)
+    onehot = F.one_hot(t.clamp(0, c - 1), c).permute(0, 3, 1, 2).to(z.dtype) * valid.unsqueeze(1)
+    inter = (p * onehot).sum(dim=(2, 3))
+    union = p.sum(dim=(2, 3)) + onehot.sum(dim=(2, 3))
+    return 1.0 - ((2.0 * inter + smooth) / (union + smooth)).mean()
+
+
+def focal_restated(z, t, wt, ign, alpha, gamma, reduction):
+    c = z.shape[1]
+    tr = t.clone()
+    tr[void_mask(t, c, ign)] = ign
+    ce = F.cross_entropy(z, tr, weight=wt, reduction="none", ignore_index=ign)
+    focal = alpha * (1 - torch.exp(-ce)) ** gamma * ce
+    return focal.mean() if reduction == "mean" else focal.sum()
+
+
+@pytest.mark.parametrize("pattern", ("random_void", "invalid"))
+@pytest.mark.parametrize("shape", [(2, 23, 17, 19), (2, 5, 32, 32)], ids=lambda s: "x".join(map(str, s)))
+def test_dice_and_focal_with_void_labels(L, shape, pattern):
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(77 + c)
+    z = torch.randn(n, c, h, w, generator=g) * 2.0
+    t = torch.randint(0, c, (n, h, w), generator=g)
+    r = torch.rand(n, h, w, generator=g)
+    t[r < 0.3] = 255
+    if pattern == "invalid":
+        t[(r >= 0.3) & (r < 0.4)] = c + 1
+    wt = torch.rand(c, generator=g) + 0.1
+    tg, wg = t.cuda(), wt.cuda()
+    hip = {"dice": lambda x: L.DiceLoss(ignore_index=255)(x, tg),
+           "focal": lambda x: L.WeightedSegmentationLoss(c, wg, 0.3, 2.0, ignore_index=255).focal_loss(x, tg),
+           "focal_sum": lambda x: L.WeightedSegmentationLoss(c, wg, 0.5, 1.5, "sum", ignore_index=255).focal_loss(x, tg),
+           "wseg": lambda x: L.WeightedSegmentationLoss(c, wg, 0.3, 2.0, ignore_index=255)(x, tg, 0.7)}
+    ora = {"dice": lambda x: dice_restated(x, t, 255),
+           "focal": lambda x: focal_restated(x, t, wt.double(), 255, 0.3, 2.0, "mean"),
+           "focal_sum": lambda x: focal_restated(x, t, wt.double(), 255, 0.5, 1.5, "sum"),
+           "wseg": lambda x: 0.7 * (focal_restated(x, t, wt.double(), 255, 0.3, 2.0, "mean") + dice_restated(x, t, 255))}
+    void = void_mask(t, c, 255)
+    for key in hip:
+        zd = z.double().requires_grad_(True)
+        vo = ora[key](zd)
+        vo.backward()
+        zg = z.cuda().requires_grad_(True)
+        vh = hip[key](zg)
+        vh.backward()
+        ev, eg = relerr(vh, vo), relerr(zg.grad, zd.grad)
+        print(f"{shape} {pattern} {key}: value {ev:.2e}, gradient {eg:.2e}")
+        assert ev < VALUE_TOL, (key, ev)
+        assert eg < GRAD_TOL, (key, eg)
+        assert float(zg.grad.cpu().permute(0, 2, 3, 1)[void].abs().max()) == 0.0, (key, "gradient at void pixels")
+
+
+@pytest.mark.parametrize("shape", [(2, 23, 17, 19), (2, 5, 32, 32)], ids=lambda s: "x".join(map(str, s)))
+def test_dice_and_focal_without_ignore_index_are_unchanged(L, shape):
+    """``ignore_index=None`` is the code as it was: the modules' results ``torch.equal`` to the original entry points called
+    directly with the same operands.  The Dice sums go through floating-point atomics, so the Dice gradient is compared for
+    the coefficients the module's own forward left (read from its graph node): with those, every launch here is order-free."""
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(55 + c)
+    z = torch.randn(n, c, h, w, generator=g) * 2.0
+    t = torch.randint(0, c, (n, h, w), generator=g)
+    wt = torch.rand(c, generator=g) + 0.1
+    ldc = ceil4(c)
+    tg, wg = t.cuda(), wt.cuda()
+    buf = torch.zeros(n, h, w, ldc)
+    buf[..., :c] = z.permute(0, 2, 3, 1)
+    buf = buf.cuda()
+    # forward values straight from the original launches
+    sums = torch.zeros(n * 3 * c, device="cuda", dtype=torch.float64)
+    coef, dloss = torch.empty(n * 2 * c, device="cuda"), torch.empty((), device="cuda")
+    K.dice_fwd(buf, tg, n, h * w, c, ldc, 1.0, sums, coef, dloss)
+    floss = torch.zeros((), device="cuda")
+    K.focal_fwd(buf, tg, wg, 0.25, 2.0, n * h * w, c, ldc, True, torch.empty(K.seg_partials(), device="cuda", dtype=torch.float64), floss)
+    one = torch.ones((), device="cuda")
+    zg = z.cuda().requires_grad_(True)
+    assert L.DiceLoss().ignore_index is None
+    dice = L.DiceLoss(ignore_index=None)(zg, tg)
+    assert torch.equal(dice.detach(), dloss)
+    coef_fwd = dice.grad_fn.saved_tensors[3].clone()
+    dice.backward()
+    dl = torch.empty(n, h, w, ldc, device="cuda")
+    K.dice_bwd(buf, tg, coef_fwd, one, 1.0, n, h * w, c, ldc, dl, False)
+    assert torch.equal(zg.grad, dl.permute(0, 3, 1, 2)[:, :c])
+    m = L.WeightedSegmentationLoss(c, wg, ignore_index=None)
+    zg.grad = None
+    focal = m.focal_loss(zg, tg)
+    assert torch.equal(focal.detach(), floss)
+    focal.backward()
+    K.focal_bwd(buf, tg, wg, 0.25, 2.0, one, 1.0 / (n * h * w), n * h * w, c, ldc, dl, False)
+    assert torch.equal(zg.grad, dl.permute(0, 3, 1, 2)[:, :c])
+    zg.grad = None
+    both = m(zg, tg)
+    assert torch.equal(both.detach(), floss + dloss)
+    coef_fwd = both.grad_fn.next_functions[0][0].saved_tensors[3].clone()
+    both.backward()
+    K.dice_bwd(buf, tg, coef_fwd, one, 1.0, n, h * w, c, ldc, dl, True)
+    assert torch.equal(zg.grad, dl.permute(0, 3, 1, 2)[:, :c])

@@ -81,6 +81,14 @@ SIGNATURES = {
     "udaseg_ce_bwd": (_I, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
     "udaseg_ce_fwd_bwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
     "udaseg_scale_unless_one": (_I, [_P, _L, _P, _I, _P, _P]),
+    "udaseg_ce_target_stats": (_I, [_P, _P, _L, _I, _I, _L, _P, _P, _P, _P]),
+    "udaseg_ce_opt_fwd_bwd": (_I, [_P, _P, _P, _L, _I, _I, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "udaseg_ce_opt_fwd": (_I, [_P, _P, _P, _L, _I, _I, _I, _L, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "udaseg_ce_opt_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _F, _I, _P, _P, _P, _P, _P]),
+    "udaseg_dice_fwd_ignore": (_I, [_P, _P, _I, _L, _I, _I, _F, _F, _I, _P, _P, _P, _L, _P]),
+    "udaseg_dice_bwd_ignore": (_I, [_P, _P, _P, _P, _F, _I, _L, _I, _I, _P, _I, _L, _P]),
+    "udaseg_focal_fwd_ignore": (_I, [_P, _P, _P, _F, _F, _L, _I, _I, _I, _P, _P, _I, _L, _P]),
+    "udaseg_focal_bwd_ignore": (_I, [_P, _P, _P, _F, _F, _P, _F, _L, _I, _I, _P, _I, _L, _P]),
     "udaseg_seg_partials": (_I, []),
     "udaseg_dice_fwd": (_I, [_P, _P, _I, _L, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "udaseg_gap_linear_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -283,6 +283,24 @@ OPERANDS = {
                           T("partials", f64, "ce_partials()"), T("loss", f32, 1), T("dlogits", f32, "pixels*ldc"),
                           T("colsum_partials", f32, "ce_partials()*ldc", True), T("colsum", f32, "ldc", True), S],
     "udaseg_scale_unless_one": [T("x", f32, "count"), I("count"), T("x2", f32, "count2", True), I("count2"), T("g", f32, 1), S],
+    # cross entropy with options: weight = `classes` floats, denom = D (f64), stats = [n_valid, n_void, n_invalid]
+    "udaseg_ce_target_stats": [T("target", i64, "pixels"), T("weight", f32, "classes", True), I("pixels"), I("classes"),
+                               I("has_ignore"), I("ignore_index"), T("partials", f64, "4*ce_partials()"), T("denom", f64, 1),
+                               T("stats", i64, 3), S],
+    "udaseg_ce_opt_fwd_bwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("weight", f32, "classes", True),
+                              I("pixels"), I("classes"), I("ldc"), I("has_ignore"), I("ignore_index"), F("eps"), I("mean"),
+                              T("denom", f64, 1, True), T("partials", f64, "ce_partials()"), T("loss", f32, 1),
+                              T("dlogits", f32, "pixels*ldc"), T("colsum_partials", f32, "ce_partials()*ldc", True),
+                              T("colsum", f32, "ldc", True), S],
+    "udaseg_ce_opt_fwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("weight", f32, "classes", True),
+                          I("pixels"), I("classes"), I("ldc"), I("has_ignore"), I("ignore_index"), F("eps"), I("mean"),
+                          T("denom", f64, 1, True), T("lse", f32, "pixels"), T("partials", f64, "ce_partials()"),
+                          T("loss", f32, 1, True), T("loss_px", f32, "pixels", True), S],
+    "udaseg_ce_opt_bwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("weight", f32, "classes", True),
+                          T("lse", f32, "pixels"), T("grad_out", f32, 1, True), T("grad_px", f32, "pixels", True), I("pixels"),
+                          I("classes"), I("ldc"), I("has_ignore"), I("ignore_index"), F("eps"), I("mean"), T("denom", f64, 1, True),
+                          T("dlogits", f32, "pixels*ldc"), T("colsum_partials", f32, "ce_partials()*ldc", True),
+                          T("colsum", f32, "ldc", True), S],
     "udaseg_argmax_confusion": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
                                 T("confusion", i64, "classes*classes"), T("pred", i64, "pixels", True), S],
     "udaseg_score_hist": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"), I("bins"),
@@ -302,6 +320,20 @@ OPERANDS = {
     "udaseg_focal_bwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("class_weights", f32, "classes", True),
                          F("alpha"), F("gamma"), T("grad_out", f32, 1, True), F("weight"), I("pixels"), I("classes"), I("ldc"),
                          T("dlogits", f32, "pixels*ldc"), I("accumulate"), S],
+    "udaseg_dice_fwd_ignore": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
+                               I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
+                               T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1),
+                               I("ignore_index"), S],
+    "udaseg_dice_bwd_ignore": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"),
+                               T("coef", f32, "batch*2*classes"), T("grad_out", f32, 1, True), F("weight"), I("batch"),
+                               I("pix_per_image"), I("classes"), I("ldc"), T("dlogits", f32, "batch*pix_per_image*ldc"),
+                               I("accumulate"), I("ignore_index"), S],
+    "udaseg_focal_fwd_ignore": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("class_weights", f32, "classes", True),
+                                F("alpha"), F("gamma"), I("pixels"), I("classes"), I("ldc"), I("mean"),
+                                T("partials", f64, "seg_partials()"), T("loss", f32, 1), I("accumulate"), I("ignore_index"), S],
+    "udaseg_focal_bwd_ignore": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("class_weights", f32, "classes", True),
+                                F("alpha"), F("gamma"), T("grad_out", f32, 1, True), F("weight"), I("pixels"), I("classes"), I("ldc"),
+                                T("dlogits", f32, "pixels*ldc"), I("accumulate"), I("ignore_index"), S],
     "udaseg_consistency_fwd": [T("z1", f32, "pixels*ldc"), T("z2", f32, "pixels*ldc"), F("temperature"), I("batch"),
                                I("pixels"), I("classes"), I("ldc"), T("partials", f64, "seg_partials()"), T("loss", f32, 1), S],
     "udaseg_consistency_bwd": [T("z1", f32, "pixels*ldc"), T("z2", f32, "pixels*ldc"), F("temperature"),

@@ -255,6 +255,327 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restr
   }
 }
 
+// ---- cross entropy with options: class weights w, ignore_index, label smoothing eps, reductions none / sum / mean --------------
+// (torch.nn.functional.cross_entropy's definition).  A second set of kernels: the plain ones above stay as they are.
+//   valid(p):  t != ignore_index and 0 <= t < classes   (an out-of-range t that is not ignore_index is void too, and counted)
+//   l_p      = (1-eps) * w[t] * (lse - z_t) + (eps/C) * sum_c w[c] * (lse - z_c)            for a valid pixel, exactly 0 otherwise
+//   dl_p/dz_k = (1-eps) * w[t] * (P_k - [k==t]) + (eps/C) * (P_k * sum_c w[c] - w[k])       exactly 0 at void pixels, all ldc lanes
+//   'mean' divides both by D = sum over valid p of w[t_p], which ce_target_stats_kernel makes from the targets alone (8 B/pixel)
+//   BEFORE the one pass over the logits, so that pass writes the gradient already scaled.
+__device__ __forceinline__ bool ce_valid(int64_t t, int classes, int has_ignore, int64_t ignore_index) {
+  return (uint64_t)t < (uint64_t)classes && !(has_ignore && t == ignore_index);
+}
+
+// partials[k][block], k = 0: sum of w[t] over valid pixels (f64), 1..3: valid / void (== ignore_index) / invalid pixel counts
+// (whole numbers < 2^53: exact in f64).  Fixed pixel-to-thread map and fixed-order reductions: two calls give the same bits.
+__global__ __launch_bounds__(256) void ce_target_stats_kernel(const int64_t* __restrict__ target, const float* __restrict__ weight,
+                                                              int64_t pixels, int classes, int has_ignore, int64_t ignore_index,
+                                                              double* __restrict__ partials) {
+  __shared__ float wsh[CE_MAXC];
+  __shared__ double red[4][4];
+  if ((int)threadIdx.x < classes) wsh[threadIdx.x] = weight ? weight[threadIdx.x] : 1.f;
+  __syncthreads();
+  const int64_t T = (int64_t)gridDim.x * blockDim.x;
+  double d = 0.0;
+  int nvalid = 0, nvoid = 0, ninvalid = 0;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += T) {
+    const int64_t t = target[p];
+    if (has_ignore && t == ignore_index) {
+      ++nvoid;
+    } else if ((uint64_t)t < (uint64_t)classes) {
+      ++nvalid;
+      d += (double)wsh[(int)t];
+    } else {
+      ++ninvalid;
+    }
+  }
+  double v[4] = {d, (double)nvalid, (double)nvoid, (double)ninvalid};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    v[k] = wave_sum_d(v[k]);
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    partials[(size_t)k * gridDim.x + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+  }
+}
+
+// single wave: denom = D, stats = [n_valid, n_void, n_invalid]
+__global__ void ce_target_stats_finish_kernel(const double* __restrict__ partials, int n, double* __restrict__ denom,
+                                              int64_t* __restrict__ stats) {
+  double s[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) a += partials[(size_t)k * n + i];
+    s[k] = wave_sum_d(a);
+  }
+  if (threadIdx.x == 0) {
+    *denom = s[0];
+    stats[0] = (int64_t)s[1];
+    stats[1] = (int64_t)s[2];
+    stats[2] = (int64_t)s[3];
+  }
+}
+
+// The per-pixel terms shared by the optioned kernels.  wsh: the class weights in LDS (1 where no weights were given).
+template <int LDC4>
+__device__ __forceinline__ float ce_row_lse(const f32x4 (&v)[LDC4], int classes, int t, float& xt) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < LDC4; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (k * 4 + e < classes) mx = fmaxf(mx, v[k][e]);
+  float sum = 0.f;
+  xt = 0.f;
+#pragma unroll
+  for (int k = 0; k < LDC4; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (k * 4 + e < classes) {
+        sum += expf(v[k][e] - mx);
+        if (k * 4 + e == t) xt = v[k][e];
+      }
+  return mx + logf(sum);
+}
+
+template <int LDC4, bool SMOOTH>
+__device__ __forceinline__ float ce_opt_pixel_loss(const f32x4 (&v)[LDC4], int classes, float l, float xt, float wt, float om, float es,
+                                                   const float* wsh) {
+  float lp = om * wt * (l - xt);
+  if (SMOOTH) {
+    float S = 0.f;
+#pragma unroll
+    for (int k = 0; k < LDC4; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (k * 4 + e < classes) S += wsh[k * 4 + e] * (l - v[k][e]);
+    lp += es * S;
+  }
+  return lp;
+}
+
+// g_c = s * [ (1-eps) w_t (P_c - [c==t]) + (eps/C) (P_c * wsum - w_c) ]   (s: everything the gradient is scaled by)
+template <bool SMOOTH>
+__device__ __forceinline__ float ce_opt_grad(float z, float l, bool is_t, float a /* s*(1-eps)*w_t */, float pk /* a + s*es*wsum */,
+                                             float ek /* s*es */, float wc) {
+  float g = expf(z - l) * (SMOOTH ? pk : a) - (is_t ? a : 0.f);
+  if (SMOOTH) g -= ek * wc;
+  return g;
+}
+
+// ONE pass over the logits, as ce_fwd_bwd_kernel: loss partials, the gradient (already scaled by 1/D for 'mean') through the LDS tile
+// as whole contiguous lines, and the per-class column sums (the head conv's bias gradient).
+template <int LDC4, bool SMOOTH>
+__global__ __launch_bounds__(256) void ce_opt_fwd_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
+                                                             const float* __restrict__ weight, int64_t pixels, int classes,
+                                                             int has_ignore, int64_t ignore_index, float eps,
+                                                             const double* __restrict__ denom, double* __restrict__ partials,
+                                                             f32x4* __restrict__ dlogits, float* __restrict__ colpart) {
+  constexpr int LDC = LDC4 * 4;
+  constexpr int NG = 256 / LDC;
+  __shared__ __attribute__((aligned(16))) float tile[256 * LDC];
+  __shared__ float colred[NG * LDC];
+  __shared__ double red[4];
+  __shared__ float wsh[32];
+  const int tid = threadIdx.x;
+  if (tid < 32) wsh[tid] = tid < classes ? (weight ? weight[tid] : 1.f) : 0.f;
+  __syncthreads();
+  float wsum = 0.f;
+  if (SMOOTH)
+    for (int c = 0; c < classes; ++c) wsum += wsh[c];
+  const float scale = denom ? (float)(1.0 / *denom) : 1.f;
+  const float om = SMOOTH ? 1.f - eps : 1.f, es = SMOOTH ? eps / (float)classes : 0.f;
+  const int64_t nchunks = (pixels + 255) / 256;
+  const int cc = tid % LDC, rg = tid / LDC;
+  float colacc = 0.f;
+  double local = 0.0;
+  for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int64_t p = chunk * 256 + tid;
+    bool ok = p < pixels;
+    int t = 0;
+    if (ok) {
+      const int64_t t64 = target[p];
+      ok = ce_valid(t64, classes, has_ignore, ignore_index);
+      t = ok ? (int)t64 : 0;
+    }
+    if (ok) {
+      f32x4 v[LDC4];
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) v[k] = logits[p * LDC4 + k];
+      float xt;
+      const float l = ce_row_lse<LDC4>(v, classes, t, xt);
+      const float wt = wsh[t];
+      local += (double)ce_opt_pixel_loss<LDC4, SMOOTH>(v, classes, l, xt, wt, om, es, wsh);
+      const float a = scale * om * wt, pk = a + scale * es * wsum, ek = scale * es;
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) {
+        f32x4 g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = k * 4 + e;
+          g[e] = c < classes ? ce_opt_grad<SMOOTH>(v[k][e], l, c == t, a, pk, ek, wsh[c]) : 0.f;
+        }
+        *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();
+    const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
+#pragma unroll
+    for (int it = 0; it < LDC4; ++it) {
+      const int idx = it * 256 + tid;
+      if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
+    }
+    if (colpart && rg < NG) {
+      for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
+    }
+    __syncthreads();
+  }
+  local = wave_sum_d(local);
+  if ((tid & 63) == 0) red[tid >> 6] = local;
+  if (colpart && rg < NG) colred[rg * LDC + cc] = colacc;
+  __syncthreads();
+  if (tid == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if (colpart && tid < LDC) {
+    float s = 0.f;
+    for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
+    colpart[(size_t)blockIdx.x * LDC + tid] = s;
+  }
+}
+
+// loss = sum of the block partials, divided by D for 'mean'; D == 0 (all void, or only zero-weight classes): NaN, whatever the
+// smoothing term sums to -- torch's 0 / 0 in the weighted mean of its first term
+__global__ void ce_opt_finish_kernel(const double* __restrict__ partials, int n, const double* __restrict__ denom,
+                                     float* __restrict__ loss) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
+  s = wave_sum_d(s);
+  if (threadIdx.x == 0) *loss = denom ? (*denom == 0.0 ? NAN : (float)(s / *denom)) : (float)s;
+}
+
+// Two-pass route, forward: lse[p] kept for the backward, loss_px[p] = l_p ('none'; may be null), block partials of sum l_p.
+template <int LDC4, bool SMOOTH>
+__global__ __launch_bounds__(256) void ce_opt_fwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
+                                                         const float* __restrict__ weight, int64_t pixels, int classes,
+                                                         int has_ignore, int64_t ignore_index, float eps, float* __restrict__ lse,
+                                                         float* __restrict__ loss_px, double* __restrict__ partials) {
+  __shared__ double red[4];
+  __shared__ float wsh[CE_MAXC];
+  if (threadIdx.x < CE_MAXC) wsh[threadIdx.x] = (int)threadIdx.x < classes ? (weight ? weight[threadIdx.x] : 1.f) : 0.f;
+  __syncthreads();
+  const float om = SMOOTH ? 1.f - eps : 1.f, es = SMOOTH ? eps / (float)classes : 0.f;
+  const int64_t T = (int64_t)gridDim.x * blockDim.x;
+  double local = 0.0;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += T) {
+    const int64_t t64 = target[p];
+    float l = 0.f, lp = 0.f;
+    if (ce_valid(t64, classes, has_ignore, ignore_index)) {
+      const int t = (int)t64;
+      f32x4 v[LDC4];
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) v[k] = logits[p * LDC4 + k];
+      float xt;
+      l = ce_row_lse<LDC4>(v, classes, t, xt);
+      lp = ce_opt_pixel_loss<LDC4, SMOOTH>(v, classes, l, xt, wsh[t], om, es, wsh);
+    }
+    lse[p] = l;
+    if (loss_px) loss_px[p] = lp;
+    local += (double)lp;
+  }
+  local = wave_sum_d(local);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Two-pass route, backward.  The upstream gradient is the scalar *grad_out (null = 1) times, for 'none', grad_px[p].
+// TILED (ldc <= 32): through the LDS tile with column sums, as ce_bwd_kernel; otherwise one thread per pixel, strided stores.
+template <int LDC4, bool SMOOTH, bool TILED>
+__global__ __launch_bounds__(256) void ce_opt_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
+                                                         const float* __restrict__ weight, const float* __restrict__ lse,
+                                                         const float* __restrict__ grad_out, const float* __restrict__ grad_px,
+                                                         int64_t pixels, int classes, int has_ignore, int64_t ignore_index, float eps,
+                                                         const double* __restrict__ denom, f32x4* __restrict__ dlogits,
+                                                         float* __restrict__ colpart) {
+  constexpr int LDC = LDC4 * 4;
+  constexpr int NG = TILED ? 256 / LDC : 1;
+  __shared__ __attribute__((aligned(16))) float tile[TILED ? 256 * LDC : 4];
+  __shared__ float colred[NG * LDC];
+  __shared__ float wsh[CE_MAXC];
+  const int tid = threadIdx.x;
+  if (tid < CE_MAXC) wsh[tid] = tid < classes ? (weight ? weight[tid] : 1.f) : 0.f;
+  __syncthreads();
+  float wsum = 0.f;
+  if (SMOOTH)
+    for (int c = 0; c < classes; ++c) wsum += wsh[c];
+  const float scale = (grad_out ? *grad_out : 1.f) * (denom ? (float)(1.0 / *denom) : 1.f);
+  const float om = SMOOTH ? 1.f - eps : 1.f, es = SMOOTH ? eps / (float)classes : 0.f;
+  const int64_t nchunks = (pixels + 255) / 256;
+  const int cc = tid % LDC, rg = tid / LDC;
+  float colacc = 0.f;
+  for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int64_t p = chunk * 256 + tid;
+    bool ok = p < pixels;
+    int t = 0;
+    if (ok) {
+      const int64_t t64 = target[p];
+      ok = ce_valid(t64, classes, has_ignore, ignore_index);
+      t = ok ? (int)t64 : 0;
+    }
+    if (ok) {
+      const float l = lse[p];
+      const float s = grad_px ? scale * grad_px[p] : scale;
+      const float a = s * om * wsh[t], pk = a + s * es * wsum, ek = s * es;
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) {
+        const f32x4 v = logits[p * LDC4 + k];
+        f32x4 g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = k * 4 + e;
+          g[e] = c < classes ? ce_opt_grad<SMOOTH>(v[e], l, c == t, a, pk, ek, wsh[c]) : 0.f;
+        }
+        if (TILED) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+        else dlogits[p * LDC4 + k] = g;
+      }
+    } else if (TILED) {
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else if (p < pixels) {
+#pragma unroll
+      for (int k = 0; k < LDC4; ++k) dlogits[p * LDC4 + k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (TILED) {
+      __syncthreads();
+      const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
+#pragma unroll
+      for (int it = 0; it < LDC4; ++it) {
+        const int idx = it * 256 + tid;
+        if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
+      }
+      if (colpart && rg < NG) {
+        for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
+      }
+      __syncthreads();
+    }
+  }
+  if (TILED && colpart) {
+    if (rg < NG) colred[rg * LDC + cc] = colacc;
+    __syncthreads();
+    if (tid < LDC) {
+      float s = 0.f;
+      for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
+      colpart[(size_t)blockIdx.x * LDC + tid] = s;
+    }
+  }
+}
+
 // ---- validation metrics: per-pixel argmax + confusion matrix (SegmentationTrainer.calculate_metrics, reference
 // src/models/train.py:225-243; confusion-matrix definition src/analysis/metrics.py:17-29: bincount(C*true + pred)).
 // One thread per pixel, row in registers; the block's histogram lives in LDS (classes <= 32 -> 4 KiB of counters), one
@@ -674,5 +995,154 @@ extern "C" int udaseg_bce_logits_target_bwd(const float* x, const float* target,
   hipLaunchKernelGGL(bce_target_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), x, target, n, weight, grad_out,
                      dx, accumulate);
   UDASEG_LAUNCH_CHECK("bce_target_bwd launch");
+  return UDASEG_OK;
+}
+
+// ---- cross entropy with options (class weights / ignore_index / label smoothing / reductions) ---------------------------------
+static int check_ce_opt(const char* who, const void* logits, const void* target, int64_t pixels, int classes, int ldc, int maxldc,
+                        float eps) {
+  UDASEG_CHECK_ARG(logits && target, "%s: NULL pointer", who);
+  UDASEG_CHECK_ARG(pixels > 0 && classes > 0 && classes <= ldc && ldc % 4 == 0 && ldc <= maxldc,
+                   "%s: need 0 < classes <= ldc <= %d, ldc %% 4 == 0 (classes=%d ldc=%d)", who, maxldc, classes, ldc);
+  UDASEG_CHECK_ARG(eps >= 0.f && eps <= 1.f, "%s: label smoothing must lie in [0, 1], got %g", who, (double)eps);
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_ce_target_stats(const int64_t* target, const float* weight, int64_t pixels, int classes, int has_ignore,
+                                      int64_t ignore_index, double* partials, double* denom, int64_t* stats, void* stream) {
+  UDASEG_CHECK_ARG(target && partials && denom && stats, "ce_target_stats: NULL pointer");
+  UDASEG_CHECK_ARG(pixels > 0 && classes > 0 && classes <= CE_MAXC, "ce_target_stats: need 0 < classes <= %d (classes=%d)", CE_MAXC,
+                   classes);
+  hipStream_t st = as_stream(stream);
+  const int64_t nb = (pixels + 255) / 256;
+  const int grid = (int)(nb > CE_BLOCKS ? CE_BLOCKS : nb);
+  hipLaunchKernelGGL(ce_target_stats_kernel, dim3(grid), dim3(256), 0, st, target, weight, pixels, classes, has_ignore, ignore_index,
+                     partials);
+  UDASEG_LAUNCH_CHECK("ce_target_stats launch");
+  hipLaunchKernelGGL(ce_target_stats_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, denom, stats);
+  UDASEG_LAUNCH_CHECK("ce_target_stats_finish launch");
+  return UDASEG_OK;
+}
+
+#define CE_OPT_SWITCH_1_8(CASE) \
+  CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#define CE_OPT_SWITCH_9_16(CASE) \
+  CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
+
+extern "C" int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes,
+                                     int ldc, int has_ignore, int64_t ignore_index, float eps, int mean, const double* denom,
+                                     double* partials, float* loss, float* dlogits, float* colsum_partials, float* colsum,
+                                     void* stream) {
+  int rc = check_ce_opt("ce_opt_fwd_bwd", logits, target, pixels, classes, ldc, 32, eps);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(partials && loss && dlogits, "ce_opt_fwd_bwd: NULL pointer");
+  UDASEG_CHECK_ARG(!mean || denom, "ce_opt_fwd_bwd: the 'mean' reduction needs the denominator of udaseg_ce_target_stats");
+  UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_opt_fwd_bwd: colsum and colsum_partials come together");
+  hipStream_t st = as_stream(stream);
+  const int64_t nchunks = (pixels + 255) / 256;
+  const int grid = (int)(nchunks > CE_BLOCKS ? CE_BLOCKS : nchunks);
+  const double* dn = mean ? denom : nullptr;
+#define CE_OFB_CASE(L)                                                                                                       \
+  case L:                                                                                                                    \
+    if (eps != 0.f)                                                                                                          \
+      hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<L, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, \
+                         pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);     \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<L, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, \
+                         pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);     \
+    break;
+  switch (ldc / 4) {
+    CE_OPT_SWITCH_1_8(CE_OFB_CASE)
+    default:
+      set_error("ce_opt_fwd_bwd: unsupported ldc %d", ldc);
+      return UDASEG_E_UNSUPPORTED;
+  }
+#undef CE_OFB_CASE
+  UDASEG_LAUNCH_CHECK("ce_opt_fwd_bwd launch");
+  hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, dn, loss);
+  UDASEG_LAUNCH_CHECK("ce_opt_finish launch");
+  if (colsum) {
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
+    UDASEG_LAUNCH_CHECK("colsum_finish launch");
+  }
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_ce_opt_fwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes,
+                                 int ldc, int has_ignore, int64_t ignore_index, float eps, int mean, const double* denom, float* lse,
+                                 double* partials, float* loss, float* loss_px, void* stream) {
+  int rc = check_ce_opt("ce_opt_fwd", logits, target, pixels, classes, ldc, CE_MAXC, eps);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(lse && partials && (loss || loss_px), "ce_opt_fwd: NULL pointer");
+  UDASEG_CHECK_ARG(!mean || denom, "ce_opt_fwd: the 'mean' reduction needs the denominator of udaseg_ce_target_stats");
+  hipStream_t st = as_stream(stream);
+  const int grid = (int)((pixels + 255) / 256 > CE_BLOCKS ? CE_BLOCKS : (pixels + 255) / 256);
+#define CE_OF_CASE(L)                                                                                                         \
+  case L:                                                                                                                     \
+    if (eps != 0.f)                                                                                                           \
+      hipLaunchKernelGGL((ce_opt_fwd_kernel<L, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels, \
+                         classes, has_ignore, ignore_index, eps, lse, loss_px, partials);                                     \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((ce_opt_fwd_kernel<L, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels, \
+                         classes, has_ignore, ignore_index, eps, lse, loss_px, partials);                                     \
+    break;
+  switch (ldc / 4) {
+    CE_OPT_SWITCH_1_8(CE_OF_CASE)
+    CE_OPT_SWITCH_9_16(CE_OF_CASE)
+    default:
+      set_error("ce_opt_fwd: unsupported ldc %d", ldc);
+      return UDASEG_E_UNSUPPORTED;
+  }
+#undef CE_OF_CASE
+  UDASEG_LAUNCH_CHECK("ce_opt_fwd launch");
+  if (loss) {
+    hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? denom : (const double*)nullptr, loss);
+    UDASEG_LAUNCH_CHECK("ce_opt_finish launch");
+  }
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, const float* weight, const float* lse,
+                                 const float* grad_out, const float* grad_px, int64_t pixels, int classes, int ldc, int has_ignore,
+                                 int64_t ignore_index, float eps, int mean, const double* denom, float* dlogits,
+                                 float* colsum_partials, float* colsum, void* stream) {
+  int rc = check_ce_opt("ce_opt_bwd", logits, target, pixels, classes, ldc, CE_MAXC, eps);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(lse && dlogits, "ce_opt_bwd: NULL pointer");
+  UDASEG_CHECK_ARG(!mean || denom, "ce_opt_bwd: the 'mean' reduction needs the denominator of udaseg_ce_target_stats");
+  UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_opt_bwd: colsum and colsum_partials come together");
+  UDASEG_CHECK_ARG(colsum == nullptr || ldc <= 32, "ce_opt_bwd: fused column sums need ldc <= 32");
+  hipStream_t st = as_stream(stream);
+  const int64_t nchunks = (pixels + 255) / 256;
+  const double* dn = mean ? denom : nullptr;
+  const int grid = (int)(nchunks > (ldc <= 32 ? CE_BLOCKS : 4096) ? (ldc <= 32 ? CE_BLOCKS : 4096) : nchunks);
+#define CE_OB_LAUNCH(L, S, TI)                                                                                               \
+  hipLaunchKernelGGL((ce_opt_bwd_kernel<L, S, TI>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, lse, \
+                     grad_out, grad_px, pixels, classes, has_ignore, ignore_index, eps, dn, (f32x4*)dlogits, colsum_partials)
+#define CE_OB_CASE_T(L)                      \
+  case L:                                    \
+    if (eps != 0.f) CE_OB_LAUNCH(L, true, true); \
+    else CE_OB_LAUNCH(L, false, true);       \
+    break;
+#define CE_OB_CASE_S(L)                       \
+  case L:                                     \
+    if (eps != 0.f) CE_OB_LAUNCH(L, true, false); \
+    else CE_OB_LAUNCH(L, false, false);       \
+    break;
+  switch (ldc / 4) {
+    CE_OPT_SWITCH_1_8(CE_OB_CASE_T)
+    CE_OPT_SWITCH_9_16(CE_OB_CASE_S)
+    default:
+      set_error("ce_opt_bwd: unsupported ldc %d", ldc);
+      return UDASEG_E_UNSUPPORTED;
+  }
+#undef CE_OB_CASE_T
+#undef CE_OB_CASE_S
+#undef CE_OB_LAUNCH
+  UDASEG_LAUNCH_CHECK("ce_opt_bwd launch");
+  if (colsum) {
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
+    UDASEG_LAUNCH_CHECK("colsum_finish launch");
+  }
   return UDASEG_OK;
 }

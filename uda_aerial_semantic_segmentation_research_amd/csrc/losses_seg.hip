@@ -39,11 +39,24 @@ __device__ __forceinline__ void load_softmax(const f32x4* __restrict__ logits, i
   for (int c = 0; c < LDC4 * 4; ++c) pr[c] = c < classes ? expf(pr[c]) : 0.f;
 }
 
+// opt-in void labels (IGN): a pixel whose target is ignore_index, or lies outside [0, classes), takes no part in the loss: it is
+// left out of every Dice sum, its focal term is 0 (class_w[t] is never read for it), and its gradient is exactly 0 in all lanes.
+// IGN = false is the code as it was.
+__device__ __forceinline__ bool seg_void(int64_t t, int classes, int64_t ignore_index) {
+  return t == ignore_index || (uint64_t)t >= (uint64_t)classes;
+}
+template <int LDC4>
+__device__ __forceinline__ void store_zero_row(f32x4* __restrict__ dlogits, int64_t p) {
+#pragma unroll
+  for (int k = 0; k < LDC4; ++k) dlogits[p * LDC4 + k] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // ---------------------------------------------------------------------------------------------------------- Dice
 // sums[b][0][c] = sum_pix p_c * onehot_c, [b][1][c] = sum_pix p_c, [b][2][c] = sum_pix onehot_c   (f64, caller-zeroed)
-template <int LDC4>
+template <int LDC4, bool IGN = false>
 __global__ __launch_bounds__(256) void dice_stats_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
-                                                         int64_t pix_per_image, int classes, double* __restrict__ sums) {
+                                                         int64_t pix_per_image, int classes, double* __restrict__ sums,
+                                                         int64_t ignore_index) {
   constexpr int LDC = LDC4 * 4;
   __shared__ float sh[3][32];
   const int b = blockIdx.y;
@@ -54,6 +67,7 @@ __global__ __launch_bounds__(256) void dice_stats_kernel(const f32x4* __restrict
   for (int c = 0; c < LDC; ++c) psum[c] = 0.f;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < pix_per_image; q += (int64_t)gridDim.x * 256) {
     const int64_t p = (int64_t)b * pix_per_image + q;
+    if (IGN && seg_void(target[p], classes, ignore_index)) continue;
     float pr[LDC];
     load_softmax<LDC4>(logits, p, classes, 1.f, pr);
     const int t = (int)target[p];
@@ -126,15 +140,19 @@ __global__ void dice_finish_kernel(const double* __restrict__ sums, int batch, i
 }
 
 // dlogits (+)= scale * p_k * (g_k - sum_c p_c g_c),  g_c = coef_a[b][c] * onehot_c + coef_b[b][c]
-template <int LDC4>
+template <int LDC4, bool IGN = false>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                        const float* __restrict__ coef, const float* __restrict__ grad_out,
                                                        float weight, int64_t pix_per_image, int batch, int classes,
-                                                       f32x4* __restrict__ dlogits, int accumulate) {
+                                                       f32x4* __restrict__ dlogits, int accumulate, int64_t ignore_index) {
   constexpr int LDC = LDC4 * 4;
   const float scale = (grad_out ? *grad_out : 1.f) * weight;
   const int64_t pixels = pix_per_image * batch;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
+    if (IGN && seg_void(target[p], classes, ignore_index)) {
+      if (!accumulate) store_zero_row<LDC4>(dlogits, p);
+      continue;
+    }
     const int b = (int)(p / pix_per_image);
     float pr[LDC], g[LDC];
     load_softmax<LDC4>(logits, p, classes, 1.f, pr);
@@ -161,14 +179,16 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const f32x4* __restrict__
 
 // ------------------------------------------------------------------------------------------- focal-weighted cross entropy
 // per pixel: ce = w[t] * (lse - z_t); pt = exp(-ce); f = alpha * (1 - pt)^gamma * ce;  partials[block] = sum f
-template <int LDC4>
+template <int LDC4, bool IGN = false>
 __global__ __launch_bounds__(256) void focal_fwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                         const float* __restrict__ class_w, float alpha, float gamma,
-                                                        int64_t pixels, int classes, double* __restrict__ partials) {
+                                                        int64_t pixels, int classes, double* __restrict__ partials,
+                                                        int64_t ignore_index) {
   constexpr int LDC = LDC4 * 4;
   __shared__ double red[4];
   double local = 0.0;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
+    if (IGN && seg_void(target[p], classes, ignore_index)) continue;
     float lp[LDC];
     load_log_softmax<LDC4>(logits, p, classes, 1.f, lp);
     const int t = (int)target[p];
@@ -197,14 +217,19 @@ __global__ void sum_finish_kernel(const double* __restrict__ partials, int n, do
 }
 
 // df/dce = alpha * [(1-pt)^gamma + ce * gamma * (1-pt)^(gamma-1) * pt];  dce/dz_k = w_t * (p_k - [k == t])
-template <int LDC4>
+template <int LDC4, bool IGN = false>
 __global__ __launch_bounds__(256) void focal_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                         const float* __restrict__ class_w, float alpha, float gamma,
                                                         const float* __restrict__ grad_out, float weight, int64_t pixels,
-                                                        int classes, f32x4* __restrict__ dlogits, int accumulate) {
+                                                        int classes, f32x4* __restrict__ dlogits, int accumulate,
+                                                        int64_t ignore_index) {
   constexpr int LDC = LDC4 * 4;
   const float scale = (grad_out ? *grad_out : 1.f) * weight;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
+    if (IGN && seg_void(target[p], classes, ignore_index)) {
+      if (!accumulate) store_zero_row<LDC4>(dlogits, p);
+      continue;
+    }
     float pr[LDC];
     load_log_softmax<LDC4>(logits, p, classes, 1.f, pr);
     const int t = (int)target[p];
@@ -323,6 +348,18 @@ static int grid_pix(int64_t pixels) {
     default: hipLaunchKernelGGL(KERN<8>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                       \
   }
 
+#define SEG_DISPATCH_IGN(KERN, GRID, ...)                                                                   \
+  switch (ldc / 4) {                                                                                        \
+    case 1: hipLaunchKernelGGL((KERN<1, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 2: hipLaunchKernelGGL((KERN<2, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 3: hipLaunchKernelGGL((KERN<3, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 4: hipLaunchKernelGGL((KERN<4, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 5: hipLaunchKernelGGL((KERN<5, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 6: hipLaunchKernelGGL((KERN<6, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    case 7: hipLaunchKernelGGL((KERN<7, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
+    default: hipLaunchKernelGGL((KERN<8, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+  }
+
 }  // namespace udaseg
 
 using namespace udaseg;
@@ -336,7 +373,7 @@ extern "C" int udaseg_dice_fwd(const float* logits, const int64_t* target, int b
   UDASEG_CHECK_ARG(target && sums && coef && loss && batch > 0, "dice_fwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   const int gx = (int)((pix_per_image + 255) / 256 > 256 ? 256 : (pix_per_image + 255) / 256);
-  SEG_DISPATCH(dice_stats_kernel, dim3(gx, batch), (const f32x4*)logits, target, pix_per_image, classes, sums)
+  SEG_DISPATCH(dice_stats_kernel, dim3(gx, batch), (const f32x4*)logits, target, pix_per_image, classes, sums, (int64_t)0)
   UDASEG_LAUNCH_CHECK("dice_stats launch");
   hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, batch, classes, smooth, eps, pooled, loss, coef);
   UDASEG_LAUNCH_CHECK("dice_finish launch");
@@ -351,7 +388,7 @@ extern "C" int udaseg_dice_bwd(const float* logits, const int64_t* target, const
   UDASEG_CHECK_ARG(target && coef && dlogits && batch > 0, "dice_bwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   SEG_DISPATCH(dice_bwd_kernel, dim3(grid_pix(pix_per_image * batch)), (const f32x4*)logits, target, coef, grad_out, weight,
-               pix_per_image, batch, classes, (f32x4*)dlogits, accumulate)
+               pix_per_image, batch, classes, (f32x4*)dlogits, accumulate, (int64_t)0)
   UDASEG_LAUNCH_CHECK("dice_bwd launch");
   return UDASEG_OK;
 }
@@ -364,7 +401,8 @@ extern "C" int udaseg_focal_fwd(const float* logits, const int64_t* target, cons
   UDASEG_CHECK_ARG(target && partials && loss, "focal_fwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   const int grid = grid_pix(pixels);
-  SEG_DISPATCH(focal_fwd_kernel, dim3(grid), (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials)
+  SEG_DISPATCH(focal_fwd_kernel, dim3(grid), (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials,
+               (int64_t)0)
   UDASEG_LAUNCH_CHECK("focal_fwd launch");
   hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
   UDASEG_LAUNCH_CHECK("focal_finish launch");
@@ -379,7 +417,7 @@ extern "C" int udaseg_focal_bwd(const float* logits, const int64_t* target, cons
   UDASEG_CHECK_ARG(target && dlogits, "focal_bwd: NULL pointer");
   hipStream_t st = as_stream(stream);
   SEG_DISPATCH(focal_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)logits, target, class_weights, alpha, gamma, grad_out, weight,
-               pixels, classes, (f32x4*)dlogits, accumulate)
+               pixels, classes, (f32x4*)dlogits, accumulate, (int64_t)0)
   UDASEG_LAUNCH_CHECK("focal_bwd launch");
   return UDASEG_OK;
 }
@@ -409,5 +447,63 @@ extern "C" int udaseg_consistency_bwd(const float* z1, const float* z2, float te
   SEG_DISPATCH(consistency_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)z1, (const f32x4*)z2, 1.f / temperature, grad_out,
                weight, batch, pixels, classes, (f32x4*)d1, (f32x4*)d2, accumulate)
   UDASEG_LAUNCH_CHECK("consistency_bwd launch");
+  return UDASEG_OK;
+}
+
+// ---- the Dice / focal entry points with void labels: the same launches with ignore_index (any int64) honoured ----------------
+extern "C" int udaseg_dice_fwd_ignore(const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes,
+                                      int ldc, float smooth, float eps, int pooled, double* sums, float* coef, float* loss,
+                                      int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_fwd_ignore");
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && sums && coef && loss && batch > 0, "dice_fwd_ignore: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  const int gx = (int)((pix_per_image + 255) / 256 > 256 ? 256 : (pix_per_image + 255) / 256);
+  SEG_DISPATCH_IGN(dice_stats_kernel, dim3(gx, batch), (const f32x4*)logits, target, pix_per_image, classes, sums, ignore_index)
+  UDASEG_LAUNCH_CHECK("dice_stats launch");
+  hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, batch, classes, smooth, eps, pooled, loss, coef);
+  UDASEG_LAUNCH_CHECK("dice_finish launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_dice_bwd_ignore(const float* logits, const int64_t* target, const float* coef, const float* grad_out,
+                                      float weight, int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits,
+                                      int accumulate, int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_bwd_ignore");
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && coef && dlogits && batch > 0, "dice_bwd_ignore: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  SEG_DISPATCH_IGN(dice_bwd_kernel, dim3(grid_pix(pix_per_image * batch)), (const f32x4*)logits, target, coef, grad_out, weight,
+                   pix_per_image, batch, classes, (f32x4*)dlogits, accumulate, ignore_index)
+  UDASEG_LAUNCH_CHECK("dice_bwd launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_focal_fwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                                       float gamma, int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss,
+                                       int accumulate, int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pixels, classes, ldc, "focal_fwd_ignore");
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && partials && loss, "focal_fwd_ignore: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  const int grid = grid_pix(pixels);
+  SEG_DISPATCH_IGN(focal_fwd_kernel, dim3(grid), (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials,
+                   ignore_index)
+  UDASEG_LAUNCH_CHECK("focal_fwd launch");
+  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
+  UDASEG_LAUNCH_CHECK("focal_finish launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_focal_bwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                                       float gamma, const float* grad_out, float weight, int64_t pixels, int classes, int ldc,
+                                       float* dlogits, int accumulate, int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pixels, classes, ldc, "focal_bwd_ignore");
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && dlogits, "focal_bwd_ignore: NULL pointer");
+  hipStream_t st = as_stream(stream);
+  SEG_DISPATCH_IGN(focal_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)logits, target, class_weights, alpha, gamma, grad_out,
+                   weight, pixels, classes, (f32x4*)dlogits, accumulate, ignore_index)
+  UDASEG_LAUNCH_CHECK("focal_bwd launch");
   return UDASEG_OK;
 }

@@ -606,32 +606,80 @@ def scale_unless_one(x, g, x2=None, st=None):
     check(ops.udaseg_scale_unless_one(x, x.numel(), x2, 0 if x2 is None else x2.numel(), g, st), "scale_unless_one")
 
 
+def _ignore_args(ignore_index):
+    """ignore_index (None or any int64) -> (has_ignore, ignore_index) as the C ABI takes them."""
+    return (0, 0) if ignore_index is None else (1, int(ignore_index))
+
+
+def ce_target_stats(target, weight, pixels, classes, ignore_index, partials, denom, stats, st=None):
+    """From the targets alone: denom = sum of weight[t] over valid pixels (f64), stats = [n_valid, n_void, n_invalid] (int64)."""
+    check(ops.udaseg_ce_target_stats(target, weight, pixels, classes, *_ignore_args(ignore_index), partials, denom, stats, st),
+          "ce_target_stats")
+
+
+def ce_opt_fwd_bwd(logits_base, target, weight, pixels, classes, ldc, ignore_index, eps, mean, denom, partials, loss, dlogits,
+                   colsum_partials=None, colsum=None, st=None):
+    """Cross entropy with options, loss and (already scaled) gradient in ONE pass over the logits (ldc <= 32)."""
+    check(ops.udaseg_ce_opt_fwd_bwd(logits_base, target, weight, pixels, classes, ldc, *_ignore_args(ignore_index), float(eps),
+                                    int(mean), denom, partials, loss, dlogits, colsum_partials, colsum, st), "ce_opt_fwd_bwd")
+
+
+def ce_opt_fwd(logits_base, target, weight, pixels, classes, ldc, ignore_index, eps, mean, denom, lse, partials, loss=None,
+               loss_px=None, st=None):
+    check(ops.udaseg_ce_opt_fwd(logits_base, target, weight, pixels, classes, ldc, *_ignore_args(ignore_index), float(eps), int(mean),
+                                denom, lse, partials, loss, loss_px, st), "ce_opt_fwd")
+
+
+def ce_opt_bwd(logits_base, target, weight, lse, grad_out, grad_px, pixels, classes, ldc, ignore_index, eps, mean, denom, dlogits,
+               colsum_partials=None, colsum=None, st=None):
+    check(ops.udaseg_ce_opt_bwd(logits_base, target, weight, lse, grad_out, grad_px, pixels, classes, ldc,
+                                *_ignore_args(ignore_index), float(eps), int(mean), denom, dlogits, colsum_partials, colsum, st),
+          "ce_opt_bwd")
+
+
 def seg_partials():
     return ops.udaseg_seg_partials()
 
 
-def dice_fwd(logits_base, target, batch, pix_per_image, classes, ldc, smooth, sums, coef, loss, eps=1e-7, pooled=False, st=None):
+def dice_fwd(logits_base, target, batch, pix_per_image, classes, ldc, smooth, sums, coef, loss, eps=1e-7, pooled=False, st=None,
+             ignore_index=None):
+    if ignore_index is not None:
+        check(ops.udaseg_dice_fwd_ignore(logits_base, target, batch, pix_per_image, classes, ldc, float(smooth), float(eps),
+                                         int(pooled), sums, coef, loss, int(ignore_index), st), "dice_fwd_ignore")
+        return
     check(ops.udaseg_dice_fwd(logits_base, target, batch, pix_per_image, classes, ldc,
                                        float(smooth), float(eps), int(pooled), sums, coef,
                                        loss, st), "dice_fwd")
 
 
 def dice_bwd(logits_base, target, coef, grad_out, weight, batch, pix_per_image, classes, ldc, dlogits, accumulate=False,
-             st=None):
+             st=None, ignore_index=None):
+    if ignore_index is not None:
+        check(ops.udaseg_dice_bwd_ignore(logits_base, target, coef, grad_out, float(weight), batch, pix_per_image, classes, ldc,
+                                         dlogits, int(accumulate), int(ignore_index), st), "dice_bwd_ignore")
+        return
     check(ops.udaseg_dice_bwd(logits_base, target, coef, grad_out,
                                        float(weight), batch, pix_per_image, classes, ldc, dlogits,
                                        int(accumulate), st), "dice_bwd")
 
 
 def focal_fwd(logits_base, target, class_weights, alpha, gamma, pixels, classes, ldc, mean, partials, loss, accumulate=False,
-              st=None):
+              st=None, ignore_index=None):
+    if ignore_index is not None:
+        check(ops.udaseg_focal_fwd_ignore(logits_base, target, class_weights, float(alpha), float(gamma), pixels, classes, ldc,
+                                          int(mean), partials, loss, int(accumulate), int(ignore_index), st), "focal_fwd_ignore")
+        return
     check(ops.udaseg_focal_fwd(logits_base, target, class_weights, float(alpha),
                                         float(gamma), pixels, classes, ldc, int(mean), partials, loss,
                                         int(accumulate), st), "focal_fwd")
 
 
 def focal_bwd(logits_base, target, class_weights, alpha, gamma, grad_out, weight, pixels, classes, ldc, dlogits,
-              accumulate=False, st=None):
+              accumulate=False, st=None, ignore_index=None):
+    if ignore_index is not None:
+        check(ops.udaseg_focal_bwd_ignore(logits_base, target, class_weights, float(alpha), float(gamma), grad_out, float(weight),
+                                          pixels, classes, ldc, dlogits, int(accumulate), int(ignore_index), st), "focal_bwd_ignore")
+        return
     check(ops.udaseg_focal_bwd(logits_base, target, class_weights, float(alpha),
                                         float(gamma), grad_out, float(weight), pixels, classes, ldc,
                                         dlogits, int(accumulate), st), "focal_bwd")

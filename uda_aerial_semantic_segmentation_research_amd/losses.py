@@ -1,7 +1,8 @@
 """Loss modules of the hot path, backed by the wavefront-reduced HIP kernels in csrc/losses.hip.
 
 * ``CrossEntropyLoss``  -- ``nn.CrossEntropyLoss()`` exactly as the reference constructs it (no arguments: mean
-  reduction, no class weights, no ignore_index, no label smoothing; reference ``src/models/train.py:208``).
+  reduction, no class weights, no ignore_index, no label smoothing; reference ``src/models/train.py:208``); with
+  ``weight`` / ``ignore_index`` / ``reduction`` / ``label_smoothing`` the optioned kernels (void labels).
 * ``AdversarialLoss``   -- mirror of reference ``src/models/losses.py:7-51`` (same constructor, same two methods).
   As upstream, BCE-*with-logits* is applied to whatever the discriminator returns (its sigmoid output).
 * ``DiceLoss``, ``WeightedSegmentationLoss``, ``ConsistencyLoss``, ``FineTuningLoss``, ``calculate_class_weights`` --
@@ -97,8 +98,131 @@ class _CrossEntropyFunction(torch.autograd.Function):
         return out, None
 
 
+class _CrossEntropyOptFunction(torch.autograd.Function):
+    """Cross entropy with class weights / ignore_index / label smoothing / a reduction (csrc/losses.hip, ce_opt_* kernels).
+
+    One launch over the targets alone makes D (the 'mean' denominator, f64) and the target counters; then a training step reads
+    the logits once and writes the gradient once, already scaled (``ce_opt_fwd_bwd``), with the head's bias gradient (column
+    sums).  The two-pass route (forward keeping the log-sum-exp, then backward) serves no_grad forwards, ldc > 32, reduction
+    'none' (its upstream gradient is a per-pixel map) and a second backward through a retained graph."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, reduction, eps, stats):
+        n, c, h, w = logits.shape
+        buf, ldc = _padded_nhwc(logits.detach())
+        tgt = target.contiguous()
+        pixels = n * h * w
+        dev = logits.device
+        np_ = _load().udaseg_ce_partials()
+        denom = torch.empty(1, device=dev, dtype=torch.float64)
+        K.ce_target_stats(tgt, weight, pixels, c, ignore_index, torch.empty(4 * np_, device=dev, dtype=torch.float64), denom, stats)
+        mean = reduction == 'mean'
+        partials = torch.empty(np_, device=dev, dtype=torch.float64)
+        ctx.meta = (n, c, h, w, ldc, ignore_index, reduction, eps)
+        ctx.fused = None
+        if reduction == 'none':
+            lse = torch.empty(pixels, device=dev, dtype=torch.float32)
+            loss_px = torch.empty((n, h, w), device=dev, dtype=torch.float32)
+            K.ce_opt_fwd(buf, tgt, weight, pixels, c, ldc, ignore_index, eps, False, None, lse, partials, None, loss_px)
+            ctx.save_for_backward(buf, tgt, weight, denom, lse)
+            return loss_px
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        if FUSE_CE_BACKWARD and ldc <= 32 and ctx.needs_input_grad[0]:
+            dl = torch.empty((n, h, w, ldc), device=dev, dtype=torch.float32)
+            parts = torch.empty(np_ * ldc, device=dev, dtype=torch.float32)
+            colsum = torch.empty(ldc, device=dev, dtype=torch.float32)
+            K.ce_opt_fwd_bwd(buf, tgt, weight, pixels, c, ldc, ignore_index, eps, mean, denom, partials, loss, dl, parts, colsum)
+            ctx.fused = [dl, colsum]
+            ctx.save_for_backward(buf, tgt, weight, denom)
+            return loss
+        lse = torch.empty(pixels, device=dev, dtype=torch.float32)
+        K.ce_opt_fwd(buf, tgt, weight, pixels, c, ldc, ignore_index, eps, mean, denom, lse, partials, loss, None)
+        ctx.save_for_backward(buf, tgt, weight, denom, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, c, h, w, ldc, ignore_index, reduction, eps = ctx.meta
+        pixels = n * h * w
+        g = grad_out.detach().to(torch.float32).contiguous()
+        if ctx.fused is not None:
+            dl, colsum = ctx.fused
+            ctx.fused = None                           # consumed (a second backward takes the two-pass route)
+            K.scale_unless_one(dl, g, colsum)
+            COLSUM_SIDE_TABLE.clear()
+            COLSUM_SIDE_TABLE[dl.data_ptr()] = colsum
+            return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 6
+        mean = reduction == 'mean'
+        if len(ctx.saved_tensors) == 4:                # fused forward, second backward: recompute the log-sum-exp
+            buf, tgt, weight, denom = ctx.saved_tensors
+            lse = torch.empty(pixels, device=buf.device, dtype=torch.float32)
+            K.ce_opt_fwd(buf, tgt, weight, pixels, c, ldc, ignore_index, eps, mean, denom, lse,
+                         torch.empty(_load().udaseg_ce_partials(), device=buf.device, dtype=torch.float64),
+                         torch.empty((), device=buf.device, dtype=torch.float32), None)
+        else:
+            buf, tgt, weight, denom, lse = ctx.saved_tensors
+        g_scalar, g_px = (None, g.reshape(-1)) if reduction == 'none' else (g, None)
+        dl = torch.empty((n, h, w, ldc), device=buf.device, dtype=torch.float32)
+        if ldc <= 32:
+            parts = torch.empty(_load().udaseg_ce_partials() * ldc, device=buf.device, dtype=torch.float32)
+            colsum = torch.empty(ldc, device=buf.device, dtype=torch.float32)
+            K.ce_opt_bwd(buf, tgt, weight, lse, g_scalar, g_px, pixels, c, ldc, ignore_index, eps, mean, denom, dl, parts, colsum)
+            COLSUM_SIDE_TABLE.clear()
+            COLSUM_SIDE_TABLE[dl.data_ptr()] = colsum
+        else:
+            K.ce_opt_bwd(buf, tgt, weight, lse, g_scalar, g_px, pixels, c, ldc, ignore_index, eps, mean, denom, dl)
+        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 6
+
+
 class CrossEntropyLoss(nn.Module):
-    """Per-pixel cross entropy over ``[N,C,H,W]`` logits and ``[N,H,W]`` int64 targets -> 0-dim loss with grad_fn."""
+    """Per-pixel cross entropy over ``[N,C,H,W]`` logits and ``[N,H,W]`` integer targets, ``nn.CrossEntropyLoss``'s arguments.
+
+    ``CrossEntropyLoss()`` is the plain loss the reference constructs (mean, no weights, no void handling): the plain kernels,
+    one fused pass in a training step.  Any argument selects the optioned kernels, whose definition is
+    ``torch.nn.functional.cross_entropy(input, target, weight, ignore_index=..., reduction=..., label_smoothing=...)``:
+    a pixel is *valid* when ``target != ignore_index`` and ``0 <= target < C``; every other pixel is void: loss and gradient
+    exactly 0 there, and 'mean' divides by the sum of ``weight[target]`` over the valid pixels only (all void: NaN loss, zero
+    gradient, as torch; 'sum': 0).  ``reduction='none'`` returns fp32 ``[N,H,W]``.
+
+    Two departures from torch:
+
+    * ``ignore_index`` defaults to ``None`` ("no void handling", the plain route), not to ``-100``.  Any explicit value, ``-100``
+      included, selects the optioned route.
+    * An out-of-range target that is not ``ignore_index`` raises no ``IndexError`` (that needs a host read of every mask); it is
+      treated as void and counted.  ``last_target_stats`` is a device int64 tensor ``[n_valid, n_void, n_invalid]`` of the last
+      optioned call (``None`` on the plain route), written by the loss's own launches: read it when convenient.
+
+    Under data parallelism each rank divides by its own D, as torch's DistributedDataParallel does.
+    """
+
+    def __init__(self, weight=None, ignore_index=None, reduction='mean', label_smoothing=0.0):
+        super().__init__()
+        if reduction not in ('none', 'sum', 'mean'):
+            raise ValueError(f"CrossEntropyLoss: reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"CrossEntropyLoss: label_smoothing must lie in [0, 1], got {label_smoothing}")
+        if weight is not None:
+            weight = torch.as_tensor(weight)
+            if weight.dim() != 1 or weight.numel() == 0:
+                raise ValueError(f"CrossEntropyLoss: weight must be a 1-D tensor of C class weights, got shape {tuple(weight.shape)}")
+            if weight.numel() > 64:
+                raise ValueError(f"CrossEntropyLoss: at most 64 classes are supported by the HIP kernels, got {weight.numel()} weights")
+            weight = weight.detach().to(torch.float32).clone()
+        ignore_index = _check_ignore_index("CrossEntropyLoss", ignore_index)
+        self.register_buffer('weight', weight)
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+        self.label_smoothing = float(label_smoothing)
+        self.last_target_stats = None
+
+    @property
+    def route(self):
+        """'plain': the kernels of ``CrossEntropyLoss()`` exactly as before; 'options': the ce_opt_* kernels."""
+        plain = self.weight is None and self.ignore_index is None and self.reduction == 'mean' and self.label_smoothing == 0.0
+        return 'plain' if plain else 'options'
+
+    def extra_repr(self):
+        return f"ignore_index={self.ignore_index}, reduction={self.reduction!r}, label_smoothing={self.label_smoothing}, route={self.route}"
 
     def forward(self, input, target):
         if input.device.type != "cuda":
@@ -107,7 +231,21 @@ class CrossEntropyLoss(nn.Module):
             raise ValueError(f"expected logits [N,C,H,W] and target [N,H,W]; got {tuple(input.shape)} and {tuple(target.shape)}")
         if target.dtype != torch.int64:
             target = target.long()
-        return _CrossEntropyFunction.apply(input, target)
+        if self.route == 'plain':
+            return _CrossEntropyFunction.apply(input, target)
+        c = input.shape[1]
+        if c > 64:
+            raise ValueError(f"CrossEntropyLoss: at most 64 classes are supported by the HIP kernels, got {c}")
+        weight = self.weight
+        if weight is not None:
+            if weight.numel() != c:
+                raise ValueError(f"CrossEntropyLoss: weight has {weight.numel()} entries for {c} classes")
+            weight = weight.to(device=input.device, dtype=torch.float32).contiguous()
+        stats = torch.empty(3, device=input.device, dtype=torch.int64)
+        out = _CrossEntropyOptFunction.apply(input, target.to(input.device), weight, self.ignore_index, self.reduction,
+                                             self.label_smoothing, stats)
+        self.last_target_stats = stats
+        return out
 
 
 class _BCEPairFunction(torch.autograd.Function):
@@ -221,12 +359,20 @@ def _check_seg_pair(who, logits, target):
     return target.long().contiguous()
 
 
+def _check_ignore_index(who, ignore_index):
+    if ignore_index is None:
+        return None
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2 ** 63 <= int(ignore_index) < 2 ** 63:
+        raise ValueError(f"{who}: ignore_index must be None or an int64, got {ignore_index!r}")
+    return int(ignore_index)
+
+
 class _SegLossFunction(torch.autograd.Function):
     """loss = focal_w * focal(logits, target) + dice_w * dice(logits, target); either weight may be 0 (term skipped)."""
 
     @staticmethod
     def forward(ctx, logits, target, class_weights, alpha, gamma, mean, smooth, focal_w, dice_w, dice_eps=1e-7,
-                dice_pooled=False):
+                dice_pooled=False, ignore_index=None):
         n, c, h, w = logits.shape
         buf, ldc = _padded_nhwc(logits.detach())
         dev = logits.device
@@ -234,17 +380,18 @@ class _SegLossFunction(torch.autograd.Function):
         coef = None
         if focal_w != 0.0:
             parts = torch.empty(K.seg_partials(), device=dev, dtype=torch.float64)
-            K.focal_fwd(buf, target, class_weights, alpha, gamma, n * h * w, c, ldc, mean, parts, loss)
+            K.focal_fwd(buf, target, class_weights, alpha, gamma, n * h * w, c, ldc, mean, parts, loss, ignore_index=ignore_index)
             if focal_w != 1.0:
                 loss.mul_(focal_w)
         if dice_w != 0.0:
             sums = torch.zeros(n * 3 * c, device=dev, dtype=torch.float64)
             coef = torch.empty(n * 2 * c, device=dev, dtype=torch.float32)
             dloss = torch.empty((), device=dev, dtype=torch.float32)
-            K.dice_fwd(buf, target, n, h * w, c, ldc, smooth, sums, coef, dloss, dice_eps, dice_pooled)
+            K.dice_fwd(buf, target, n, h * w, c, ldc, smooth, sums, coef, dloss, dice_eps, dice_pooled, ignore_index=ignore_index)
             loss.add_(dloss, alpha=dice_w)
         ctx.save_for_backward(buf, target, class_weights, coef)
         ctx.cfg = (n, c, h, w, ldc, alpha, gamma, mean, focal_w, dice_w)
+        ctx.ignore_index = ignore_index
         return loss
 
     @staticmethod
@@ -256,37 +403,47 @@ class _SegLossFunction(torch.autograd.Function):
         wrote = False
         if focal_w != 0.0:
             K.focal_bwd(buf, target, class_weights, alpha, gamma, g, focal_w / (n * h * w) if mean else focal_w, n * h * w, c,
-                        ldc, dl, False)
+                        ldc, dl, False, ignore_index=ctx.ignore_index)
             wrote = True
         if dice_w != 0.0:
-            K.dice_bwd(buf, target, coef, g, dice_w, n, h * w, c, ldc, dl, wrote)
-        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 10
+            K.dice_bwd(buf, target, coef, g, dice_w, n, h * w, c, ldc, dl, wrote, ignore_index=ctx.ignore_index)
+        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 11
 
 
 class DiceLoss(nn.Module):
-    """1 - mean over (image, class) of the soft Dice coefficient of softmax(predictions) against the labels."""
+    """1 - mean over (image, class) of the soft Dice coefficient of softmax(predictions) against the labels.
 
-    def __init__(self, smooth=1.0):
+    ``ignore_index`` (opt-in, default None = as before): pixels labelled ``ignore_index`` or outside ``[0, C)`` are left out of the
+    intersection, the probability sum and the label count of every image and class, and get a gradient of exactly 0."""
+
+    def __init__(self, smooth=1.0, ignore_index=None):
         super().__init__()
         self.smooth = smooth
+        self.ignore_index = _check_ignore_index("DiceLoss", ignore_index)
 
     def forward(self, predictions, targets):
         targets = _check_seg_pair("DiceLoss", predictions, targets)
-        return _SegLossFunction.apply(predictions, targets, None, 0.0, 0.0, True, float(self.smooth), 0.0, 1.0)
+        return _SegLossFunction.apply(predictions, targets, None, 0.0, 0.0, True, float(self.smooth), 0.0, 1.0, 1e-7, False,
+                                      self.ignore_index)
 
 
 class WeightedSegmentationLoss(nn.Module):
-    """domain_weight * (focal-modulated class-weighted cross entropy + Dice)."""
+    """domain_weight * (focal-modulated class-weighted cross entropy + Dice).
+
+    ``ignore_index`` (opt-in, default None = as before): at pixels labelled ``ignore_index`` or outside ``[0, C)`` the cross
+    entropy, hence the focal term, is 0 (``F.cross_entropy(..., ignore_index=...)`` in the reference's line; 'mean' still divides
+    by N*H*W), the class weight of such a label is never read, and the Dice term leaves them out."""
 
     def __init__(self, num_classes: int, class_weights: Optional[torch.Tensor] = None, alpha: float = 0.25,
-                 gamma: float = 2.0, reduction: str = 'mean'):
+                 gamma: float = 2.0, reduction: str = 'mean', ignore_index: Optional[int] = None):
         super().__init__()
+        self.ignore_index = _check_ignore_index("WeightedSegmentationLoss", ignore_index)
         self.num_classes = num_classes
         self.register_buffer('class_weights', torch.ones(num_classes) if class_weights is None else class_weights)
         self.alpha = alpha
         self.gamma = gamma
         self.reduction = reduction
-        self.dice_loss = DiceLoss()
+        self.dice_loss = DiceLoss(ignore_index=self.ignore_index)
 
     def _weights_on(self, device):
         return self.class_weights.to(device=device, dtype=torch.float32).contiguous()
@@ -294,14 +451,14 @@ class WeightedSegmentationLoss(nn.Module):
     def focal_loss(self, inputs, targets):
         targets = _check_seg_pair("WeightedSegmentationLoss.focal_loss", inputs, targets)
         return _SegLossFunction.apply(inputs, targets, self._weights_on(inputs.device), float(self.alpha), float(self.gamma),
-                                      self.reduction == 'mean', 1.0, 1.0, 0.0)
+                                      self.reduction == 'mean', 1.0, 1.0, 0.0, 1e-7, False, self.ignore_index)
 
     def forward(self, inputs, targets, domain_weight: float = 1.0):
         if inputs.dim() == 4 and inputs.shape[1] != self.num_classes:
             raise ValueError(f"WeightedSegmentationLoss: {inputs.shape[1]} channels for {self.num_classes} classes")
         targets = _check_seg_pair("WeightedSegmentationLoss", inputs, targets)
         both = _SegLossFunction.apply(inputs, targets, self._weights_on(inputs.device), float(self.alpha), float(self.gamma),
-                                      self.reduction == 'mean', float(self.dice_loss.smooth), 1.0, 1.0)
+                                      self.reduction == 'mean', float(self.dice_loss.smooth), 1.0, 1.0, 1e-7, False, self.ignore_index)
         return domain_weight * both
 
 

@@ -97,11 +97,13 @@ class EarlyStopping:
 
 
 class SegmentationTrainer:
-    def __init__(self, model, device):
-        """model: segmentation model; device: device to train on."""
+    def __init__(self, model, device, criterion=None):
+        """model: segmentation model; device: device to train on; criterion: the segmentation loss (None: ``CrossEntropyLoss()``,
+        e.g. ``CrossEntropyLoss(weight=w, ignore_index=255)`` for masks with void labels)."""
         self.model = model.to(device)
         self.device = device
-        self.criterion = CrossEntropyLoss()
+        self.criterion = CrossEntropyLoss() if criterion is None else (criterion.to(device) if isinstance(criterion, torch.nn.Module)
+                                                                          else criterion)
         self.logger = NullLogger(log_dir=Config.LOGS_DIR)
         self.num_classes = getattr(model, "classes", Config.NUM_CLASSES)
         self.log_metrics = True           # the reference computes metrics every batch; switch off for pure throughput
