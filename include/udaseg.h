@@ -411,7 +411,7 @@ int udaseg_scale_by_clip_f32(float* g, int64_t count, const double* sumsq, float
  *      by the record.  table: int32 [views][n][UDASEG_STRONG_AUG_WORDS], floats stored as their bit patterns:
  *        0 flags (1 noise, 2 blur, 4 affine, 8 stage 5, 16 HSV)   1 D4 code (udaseg_prepare_batch_u8's)   2 blur kind (0 box,
  *        1 median, 2 motion)   3 blur size (3 or 5)   4 motion direction (0 horizontal, 1 vertical, 2 main diagonal, 3 anti-
- *        diagonal)   5 stage-5 kind (0 sharpen, 1 emboss, 2 brightness-contrast)   6,7 Philox key   8 sigma   9..14 inverse
+ *        diagonal)   5 stage-5 kind (0 sharpen, 1 emboss, 2 brightness-contrast; 3 CLAHE: the _clahe entry points)   6,7 Philox key   8 sigma   9..14 inverse
  *        affine map (row-major 2 x 3, output pixel -> source position)   15,16 stage-5 parameters (alpha, lightness | alpha,
  *        strength | brightness, contrast)   17,18,19 hue / saturation / value shifts   20.. not read by the kernels
  *      mid: fp32 scratch [views][n][h][w][4], needed when source_pass != 0; pass source_pass = 0 when no record has noise or
@@ -450,6 +450,30 @@ int udaseg_train_aug_u8(const uint8_t* images, const uint8_t* masks, const int32
                         void* stream);
 int udaseg_elastic_field_f32(const int32_t* table, int n, int h, int w, const float* gauss_weights, int radius, float* field,
                              void* stream);
+
+/* ---- CLAHE in both augmentation pipelines (the first child of the last OneOf of src/models/augmentation.py:29-34 and :70-79):
+ *      stage-5 kind 3 of a record, flag 8 (stage 5) set, the clip limit (>= 1) in word 15.  Contrast-limited histogram
+ *      equalisation of the Lab lightness of the image after stage 4 / 4b on a fixed 8 x 8 grid of tiles; the mask is never
+ *      touched.  Defined in INTEGRATION.md, "CLAHE".  Frame sides must be multiples of 8.
+ *      udaseg_clahe_lut_u8: the table pass alone, for `words` = 32 (strong records, views 1 or 2) or 64 (training records,
+ *      views 1): lut[views][n][8][8][256] uint8, written for the samples on CLAHE and left untouched for the others.  mid /
+ *      field: the intermediates of the source / field pass as the full calls hold them, or NULL (a record with noise or blur
+ *      then reads the frame itself, a record on elastic is evaluated without its distortion).
+ *      udaseg_strong_aug_clahe_u8 / udaseg_train_aug_clahe_u8: udaseg_strong_aug_u8 / udaseg_train_aug_u8 with the table
+ *      buffer (views * n * UDASEG_CLAHE_LUT_BYTES bytes): every pass of the call, the table pass after the source pass, one
+ *      launch more than the plain entry point and no synchronisation.  Records on the other kinds give the plain entry
+ *      points' output bit for bit.  The plain entry points do not know kind 3. ---- */
+#define UDASEG_CLAHE_GRID 8
+#define UDASEG_CLAHE_LUT_BYTES (8 * 8 * 256)
+int udaseg_clahe_lut_u8(const uint8_t* images, const int32_t* table, int words, int views, int n, int h, int w, const float* mid,
+                        const float* field, uint8_t* lut, void* stream);
+int udaseg_strong_aug_clahe_u8(const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
+                               const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
+                               int source_pass, uint8_t* lut, void* stream);
+int udaseg_train_aug_clahe_u8(const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w, float* mid,
+                              float* field, const float* gauss_weights, int radius, const float* mean255,
+                              const float* inv_std255, void* out_images, int cpad, int out_bf16, int64_t* out_masks,
+                              int source_pass, int field_pass, uint8_t* lut, void* stream);
 
 /* ---- device-side input pipeline: uint8 RGB HWC images [n][h][w][3] (+ uint8 masks [n][h][w], may be NULL) ->
  *      normalised, D4-augmented, channel-padded NHWC model input (fp32, or bf16 when out_bf16) and int64 masks.

@@ -121,6 +121,9 @@ SIGNATURES = {
     "udaseg_philox4x32_debug": (_I, [_P, _P, _P, _I, _P]),
     "udaseg_train_aug_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P]),
     "udaseg_elastic_field_f32": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
+    "udaseg_clahe_lut_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "udaseg_strong_aug_clahe_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "udaseg_train_aug_clahe_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "udaseg_bn_apply_bf16": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _F, _F, _P, _P, _P, _P, _I, _F, _P]),
     "udaseg_bn_bwd_reduce_bf16": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _I, _F, _P]),
     "udaseg_bn_bwd_apply_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _I, _I, _P]),

@@ -189,6 +189,18 @@ OPERANDS = {
                             I("out_bf16"), T("out_masks", i64, "n*h*w", True), I("source_pass"), I("field_pass"), S],
     "udaseg_elastic_field_f32": [T("table", i32, "n*64"), I("n"), I("h"), I("w"), H("gauss_weights"), I("radius"),
                                  T("field", f32, "n*h*w*2"), S],
+    "udaseg_clahe_lut_u8": [T("images", u8, "n*h*w*3"), T("table", i32, "views*n*words"), I("words"), I("views"), I("n"), I("h"), I("w"),
+                            T("mid", f32, "views*n*h*w*4", True), T("field", f32, "n*h*w*2", True),
+                            T("lut", u8, "views*n*16384"), S],
+    "udaseg_strong_aug_clahe_u8": [T("images", u8, "n*h*w*3"), T("table", i32, "views*n*32"), I("views"), I("n"), I("h"), I("w"),
+                                   T("mid", f32, "views*n*h*w*4", True), H("mean255"), H("inv_std255"),
+                                   T("out_images", "(bf16 if out_bf16 else f32)", "views*n*h*w*cpad"), I("cpad"), I("out_bf16"),
+                                   I("source_pass"), T("lut", u8, "views*n*16384"), S],
+    "udaseg_train_aug_clahe_u8": [T("images", u8, "n*h*w*3"), T("masks", u8, "n*h*w", True), T("table", i32, "n*64"), I("n"), I("h"),
+                                  I("w"), T("mid", f32, "n*h*w*4", True), T("field", f32, "n*h*w*2", True), H("gauss_weights"),
+                                  I("radius"), H("mean255"), H("inv_std255"),
+                                  T("out_images", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"), I("cpad"), I("out_bf16"),
+                                  T("out_masks", i64, "n*h*w", True), I("source_pass"), I("field_pass"), T("lut", u8, "n*16384"), S],
     # ---- prediction (popcount(views) = V, the views per tile)
     "udaseg_predict_gather_u8": [T("image", u8, "h*w*3"), I("h"), I("w"), I("th"), I("tw"), I("rows"), I("cols"), I("sy"), I("sx"),
                                  I("first"), I("tiles"), I("views"), H("mean255"), H("inv_std255"),

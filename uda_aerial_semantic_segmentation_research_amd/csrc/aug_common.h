@@ -1,6 +1,8 @@
-// Device helpers shared by the two augmentation sources (strong_aug.hip: phase-3 views; train_aug.hip: labelled training
-// batches): the record loader, reflect-101, Philox4x32-10, the D4 gather, the k x k median, the stage-3 source pass, the frame /
-// intermediate fetch, stage 4 (the affine gather) and the HSV shift.  One definition each: both pipelines are held to the same arithmetic bit for bit.
+// Device helpers shared by the augmentation sources (strong_aug.hip: phase-3 views; train_aug.hip: labelled training batches;
+// clahe.hip: the CLAHE table pass): the record loader, reflect-101, Philox4x32-10, the D4 gather, the k x k median, the stage-3
+// source pass, the frame / intermediate fetch, stage 4 (the affine gather), the HSV shift, the training record with stages
+// 4 + 4b (the composed gather), and CLAHE's colour round trip and per-pixel table blend.  One definition each: both pipelines
+// are held to the same arithmetic bit for bit.
 #pragma once
 #include "common.h"
 
@@ -225,5 +227,217 @@ __device__ __forceinline__ void sa_hsv_shift(float (&v)[3], float dh, float ds, 
   }
   v[0] = clamp255(ro); v[1] = clamp255(go); v[2] = clamp255(bo);
 }
+
+// ---------------------------------------------------------------------------------- the training record and stages 4 + 4b
+constexpr int TA_WORDS = 64;            // 4-byte words per record (include/udaseg.h: UDASEG_TRAIN_AUG_WORDS); 0..31: the strong record
+constexpr int TA_DISTORT = 32;          // flag bit of word 0
+constexpr int TA_OPTICAL = 1, TA_GRID = 2, TA_ELASTIC = 3;
+constexpr int TA_MAX_RADIUS = 18;       // include/udaseg.h: UDASEG_ELASTIC_MAX_RADIUS
+constexpr int TA_FT = 32;               // the field kernel's tile side
+constexpr int TA_FS = TA_FT + 2 * TA_MAX_RADIUS;
+
+typedef float ta_f2 __attribute__((ext_vector_type(2)));
+
+struct TaWeights { float w[2 * TA_MAX_RADIUS + 1]; };
+
+struct TaRec {
+  SaRec s;
+  int kind;                             // 0: no distortion
+  float ok, odx, ody;                   // optical
+  float alpha;                          // elastic (the grid's step factors go to LDS: ta_grid_table)
+};
+
+__device__ __forceinline__ TaRec ta_load(const int32_t* __restrict__ t) {
+  TaRec r;
+  r.s = sa_load(t);
+  r.kind = (r.s.flags & TA_DISTORT) ? t[32] : 0;
+  r.ok = __int_as_float(t[33]); r.odx = __int_as_float(t[34]); r.ody = __int_as_float(t[35]);
+  r.alpha = __int_as_float(t[48]);
+  return r;
+}
+
+struct TaGeo {                          // what the block needs of the record's geometry, formed once
+  int kind, affine, cw, ch;
+  float cx, cy;                         // optical centre
+  const float* grid;                    // LDS: x starts [6], x steps [6], y starts [6], y steps [6]
+  const ta_f2* field;                   // the sample's field, or nullptr
+};
+
+// grid distortion: cell i of an axis starts at s_i on the source grid, s_0 = 0, s_{i+1} = s_i + cell * step_i (summed in this
+// order); threads 0..11 form one entry each of the block's table
+__device__ __forceinline__ void ta_grid_table(const int32_t* __restrict__ t, int cw, int ch, float* tab) {
+  if (threadIdx.x < 12) {
+    const int axis = threadIdx.x / 6, cell = threadIdx.x - axis * 6;
+    const int32_t* steps = t + 36 + 6 * axis;
+    const float side = (float)(axis ? ch : cw);
+    float s = 0.f;
+    for (int i = 0; i < cell; ++i) s = s + side * __int_as_float(steps[i]);
+    tab[12 * axis + cell] = s;
+    tab[12 * axis + 6 + cell] = __int_as_float(steps[cell]);
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ TaGeo ta_geometry(const TaRec& rec, const ta_f2* field, const float* grid, int h, int w) {
+  TaGeo g;
+  g.kind = rec.kind;
+  g.affine = (rec.s.flags & SA_AFFINE) ? 1 : 0;
+  g.field = field;
+  g.grid = grid;
+  g.cw = w / 5 > 0 ? w / 5 : 1;
+  g.ch = h / 5 > 0 ? h / 5 : 1;
+  g.cx = (float)(w - 1) * 0.5f + rec.odx;
+  g.cy = (float)(h - 1) * 0.5f + rec.ody;
+  if (g.kind == TA_ELASTIC && !field) g.kind = 0;               // the binding refuses such a call; never dereference a missing field
+  return g;
+}
+
+__device__ __forceinline__ float ta_grid_axis(int x, int cw, const float* tab) {
+  int i = x / cw;
+  i = i < 5 ? i : 5;                                            // the last cell takes what remains of the axis
+  return tab[i] + (float)(x - i * cw) * tab[6 + i];
+}
+
+// source position r of output pixel (y, x) (inside the frame): r = M (q(p), 1)
+__device__ __forceinline__ void ta_position(const TaGeo& g, const TaRec& rec, int y, int x, int h, int w, float& rx, float& ry) {
+  const float fx = (float)x, fy = (float)y;
+  if (!g.kind) {                                                // shift-scale-rotate alone: sa_stage4's own expression
+    rx = rec.s.m[0] * fx + rec.s.m[1] * fy + rec.s.m[2];
+    ry = rec.s.m[3] * fx + rec.s.m[4] * fy + rec.s.m[5];
+    return;
+  }
+  float qx = fx, qy = fy;
+  if (g.kind == TA_OPTICAL) {
+    const float ex = fx - g.cx, ey = fy - g.cy;
+    const float u = ex / (float)w, v = ey / (float)h;
+    const float r2 = u * u + v * v;
+    const float f = 1.f + rec.ok * r2 + rec.ok * r2 * r2;
+    qx = g.cx + ex * f;
+    qy = g.cy + ey * f;
+  } else if (g.kind == TA_GRID) {
+    qx = ta_grid_axis(x, g.cw, g.grid);
+    qy = ta_grid_axis(y, g.ch, g.grid + 12);
+  } else if (g.kind == TA_ELASTIC) {
+    const ta_f2 d = g.field[y * w + x];
+    qx = fx + rec.alpha * d.x;
+    qy = fy + rec.alpha * d.y;
+  }
+  if (g.affine) {
+    rx = rec.s.m[0] * qx + rec.s.m[1] * qy + rec.s.m[2];
+    ry = rec.s.m[3] * qx + rec.s.m[4] * qy + rec.s.m[5];
+  } else {
+    rx = qx;
+    ry = qy;
+  }
+}
+
+// the image after stages 4 and 4b at output-grid pixel (y, x) (inside the frame): one bilinear sample at r
+// (the interpolation is written out as in sa_stage4, which stays as it is: its compiled arithmetic is what strong_views is pinned to)
+__device__ __forceinline__ void ta_stage4(const SaSrc& s, const TaGeo& g, const TaRec& rec, int y, int x, float (&v)[3]) {
+  if (!g.kind) {                                                // no distortion: the strong pipeline's stage 4, bit for bit
+    sa_stage4(s, rec.s, y, x, v);
+    return;
+  }
+  float sx, sy;
+  ta_position(g, rec, y, x, s.h, s.w, sx, sy);
+  const float x0f = floorf(sx), y0f = floorf(sy);
+  const float ax = sx - x0f, ay = sy - y0f;
+  const int x0 = reflect101((int)x0f, s.w), x1 = reflect101((int)x0f + 1, s.w);
+  const int y0 = reflect101((int)y0f, s.h), y1 = reflect101((int)y0f + 1, s.h);
+  float a[3], b[3], c[3], d[3];
+  sa_fetch(s, y0, x0, a);
+  sa_fetch(s, y0, x1, b);
+  sa_fetch(s, y1, x0, c);
+  sa_fetch(s, y1, x1, d);
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    v[k] = (1.f - ay) * ((1.f - ax) * a[k] + ax * b[k]) + ay * ((1.f - ax) * c[k] + ax * d[k]);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ CLAHE
+// Stage-5 kind 3 ("CLAHE"): histogram equalisation of the Lab lightness of the stage-4 image on a fixed 8 x 8
+// grid of tiles, clip limit in word 15.  The table pass (clahe.hip) writes uint8 lut[slot][8][8][256]; the output pass blends
+// the four neighbouring tiles' entries of the pixel's own bin.  sRGB transfer function, D65 matrix rows divided by the white
+// point (0.950456, 1, 1.088754); both matrices are formed in float64 and rounded once to fp32:
+constexpr int SA_CLAHE = 3;             // word 5
+constexpr int CL_GRID = 8, CL_BINS = 256, CL_TILES = CL_GRID * CL_GRID;
+//   forward: (0.412453, 0.357580, 0.180423) / 0.950456 | (0.212671, 0.715160, 0.072169) | (0.019334, 0.119193, 0.950227) / 1.088754
+constexpr float CL_M00 = 0.433952749f, CL_M01 = 0.376219422f, CL_M02 = 0.18982783f;
+constexpr float CL_M10 = 0.212670997f, CL_M11 = 0.715160012f, CL_M12 = 0.0721689984f;
+constexpr float CL_M20 = 0.017757915f, CL_M21 = 0.109476522f, CL_M22 = 0.872765541f;
+//   inverse of the forward matrix (float64), rounded once to fp32
+constexpr float CL_I00 = 3.07993484f, CL_I01 = -1.53715158f, CL_I02 = -0.542783439f;
+constexpr float CL_I10 = -0.92123419f, CL_I11 = 1.87599003f, CL_I12 = 0.0452441797f;
+constexpr float CL_I20 = 0.0528896824f, CL_I21 = -0.204041332f, CL_I22 = 1.15115166f;
+
+__device__ __forceinline__ float cl_linear(float v) {           // sRGB level 0..255 -> linear 0..1
+  const float c = v / 255.f;
+  return c <= 0.04045f ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f);
+}
+
+__device__ __forceinline__ float cl_level(float lin) {          // linear -> sRGB level, clamped to 0..255
+  const float c = lin <= 0.0031308f ? 12.92f * lin : 1.055f * powf(lin, 1.f / 2.4f) - 0.055f;
+  return clamp255(c * 255.f);
+}
+
+__device__ __forceinline__ float cl_f(float t) { return t > 0.008856f ? cbrtf(t) : 7.787f * t + 16.f / 116.f; }
+
+__device__ __forceinline__ float cl_f_inv(float f) {
+  const float t3 = f * f * f;
+  return t3 > 0.008856f ? t3 : (f - 16.f / 116.f) / 7.787f;
+}
+
+// lightness on the 8-bit scale (L8 = 2.55 L) and the pixel's own a, b
+__device__ __forceinline__ void cl_rgb_to_lab(const float (&v)[3], float& l8, float& a, float& b) {
+  const float r = cl_linear(v[0]), g = cl_linear(v[1]), bl = cl_linear(v[2]);
+  const float fx = cl_f(CL_M00 * r + CL_M01 * g + CL_M02 * bl);
+  const float fy = cl_f(CL_M10 * r + CL_M11 * g + CL_M12 * bl);
+  const float fz = cl_f(CL_M20 * r + CL_M21 * g + CL_M22 * bl);
+  l8 = 2.55f * (116.f * fy - 16.f);
+  a = 500.f * (fx - fy);
+  b = 200.f * (fy - fz);
+}
+
+__device__ __forceinline__ int cl_bin(float l8) {
+  const int k = (int)floorf(l8 + 0.5f);
+  return k < 0 ? 0 : (k > CL_BINS - 1 ? CL_BINS - 1 : k);
+}
+
+__device__ __forceinline__ void cl_lab_to_rgb(float l8, float a, float b, float (&v)[3]) {
+  const float fy = (l8 / 2.55f + 16.f) / 116.f;
+  const float x = cl_f_inv(fy + a / 500.f), y = cl_f_inv(fy), z = cl_f_inv(fy - b / 200.f);
+  v[0] = cl_level(CL_I00 * x + CL_I01 * y + CL_I02 * z);
+  v[1] = cl_level(CL_I10 * x + CL_I11 * y + CL_I12 * z);
+  v[2] = cl_level(CL_I20 * x + CL_I21 * y + CL_I22 * z);
+}
+
+// position of pixel coordinate x on the axis of tile centres: the two neighbouring tiles and the weight of the second
+__device__ __forceinline__ void cl_neighbours(int x, int tile, int& t0, int& t1, float& a) {
+  const float tf = (float)x / (float)tile - 0.5f;
+  const float fl = floorf(tf);
+  a = tf - fl;
+  const int i = (int)fl;
+  t0 = i > 0 ? i : 0;
+  t1 = i + 1 < CL_GRID - 1 ? i + 1 : CL_GRID - 1;
+}
+
+// the stage itself at output pixel (y, x): v = the stage-4 image there; lut = the slot's [8][8][256] table
+__device__ __forceinline__ void cl_apply(float (&v)[3], const uint8_t* __restrict__ lut, int y, int x, int th, int tw) {
+  float l8, a, b;
+  cl_rgb_to_lab(v, l8, a, b);
+  const int k = cl_bin(l8);
+  int x0, x1, y0, y1;
+  float ax, ay;
+  cl_neighbours(x, tw, x0, x1, ax);
+  cl_neighbours(y, th, y0, y1, ay);
+  const float l00 = (float)lut[(y0 * CL_GRID + x0) * CL_BINS + k], l01 = (float)lut[(y0 * CL_GRID + x1) * CL_BINS + k];
+  const float l10 = (float)lut[(y1 * CL_GRID + x0) * CL_BINS + k], l11 = (float)lut[(y1 * CL_GRID + x1) * CL_BINS + k];
+  const float lo = (1.f - ay) * ((1.f - ax) * l00 + ax * l01) + ay * ((1.f - ax) * l10 + ax * l11);
+  cl_lab_to_rgb(lo, a, b, v);
+}
+
+// the table pass (clahe.hip) for `words`-word records (32: strong, 64: training): one launch, samples not on CLAHE return at once
+void clahe_launch_lut(const uint8_t* images, const int32_t* table, int words, int views, int n, int h, int w, const float* mid,
+                      const float* field, uint8_t* lut, hipStream_t st);
 
 }  // namespace udaseg

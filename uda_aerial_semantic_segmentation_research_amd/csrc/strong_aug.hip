@@ -11,6 +11,8 @@
 //                frame through the D4 code when the sample has neither noise nor blur -- then the point-wise stages and the store.
 // A record with every stage off therefore costs one pass and computes exactly udaseg_prepare_batch_u8's arithmetic.
 // Stage selection is per sample (blockIdx.y) and per view (blockIdx.z): every branch on the record is uniform over the block.
+// udaseg_strong_aug_clahe_u8 is the same call for batches with a record on CLAHE (stage-5 kind 3): the table pass (clahe.hip)
+// runs between the two, and the output pass is the variant with that one more stage-5 branch.
 #include "aug_common.h"
 
 namespace udaseg {
@@ -23,10 +25,13 @@ __global__ __launch_bounds__(256) void strong_source_kernel(const uint8_t* __res
   sa_source_pass(images, rec, ni, (size_t)view * n + ni, h, w, mid);
 }
 
-template <bool BF16>
+// the output pass.  CLAHE = false is the kernel of udaseg_strong_aug_u8 (lut is not read); CLAHE = true adds stage-5 kind 3 (the
+// slot's table from the table pass, clahe.hip) and leaves every other branch as it is written here.
+template <bool BF16, bool CLAHE>
 __global__ __launch_bounds__(256) void strong_output_kernel(const uint8_t* __restrict__ images, const int32_t* __restrict__ table,
                                                             const f32x4* __restrict__ mid, int n, int h, int w, float m0, float m1,
-                                                            float m2, float r0, float r1, float r2, void* __restrict__ out, int cpad) {
+                                                            float m2, float r0, float r1, float r2, void* __restrict__ out, int cpad,
+                                                            const uint8_t* __restrict__ lut) {
   const int ni = blockIdx.y, view = blockIdx.z;
   const SaRec rec = sa_load(table + ((size_t)view * n + ni) * SA_WORDS);
   const int hw = h * w;
@@ -65,6 +70,9 @@ __global__ __launch_bounds__(256) void strong_output_kernel(const uint8_t* __res
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) v[c] = clamp255(acc[c]);
+    } else if (CLAHE && (rec.flags & SA_STAGE5) && rec.s5_kind == SA_CLAHE) {
+      sa_stage4(src, rec, y, x, v);
+      cl_apply(v, lut + ((size_t)view * n + ni) * (CL_TILES * CL_BINS), y, x, h / CL_GRID, w / CL_GRID);
     } else {
       sa_stage4(src, rec, y, x, v);
       if (rec.flags & SA_STAGE5) {                               // brightness-contrast: v (1 + c) + 255 b
@@ -104,30 +112,58 @@ __global__ void philox_debug_kernel(const int32_t* __restrict__ counters, const 
 
 using namespace udaseg;
 
-extern "C" int udaseg_strong_aug_u8(const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
-                                    const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
-                                    int source_pass, void* stream) {
-  UDASEG_CHECK_ARG(images && table && out_images && mean255 && inv_std255 && n > 0 && h > 0 && w > 0, "strong_aug_u8: bad arguments");
-  UDASEG_CHECK_ARG(views == 1 || views == 2, "strong_aug_u8: views must be 1 or 2");
-  UDASEG_CHECK_ARG(cpad >= 4 && cpad % (out_bf16 ? 8 : 4) == 0, "strong_aug_u8: cpad must be a multiple of %d", out_bf16 ? 8 : 4);
-  UDASEG_CHECK_ARG((int64_t)h * w < (1LL << 30) && n <= 65535, "strong_aug_u8: batch too large");
-  UDASEG_CHECK_ARG(!source_pass || mid, "strong_aug_u8: the source pass needs the intermediate buffer");
-  UDASEG_CHECK_ARG(((uintptr_t)mid & 15) == 0 && ((uintptr_t)out_images & 15) == 0, "strong_aug_u8: buffers must be 16-byte aligned");
+// every pass of a call; lut == nullptr: today's launches, else the table pass goes between the source and the output pass
+static int strong_aug_run(const char* who, const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
+                          const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16, int source_pass,
+                          uint8_t* lut, bool clahe, void* stream) {
+  UDASEG_CHECK_ARG(images && table && out_images && mean255 && inv_std255 && n > 0 && h > 0 && w > 0, "%s: bad arguments", who);
+  UDASEG_CHECK_ARG(views == 1 || views == 2, "%s: views must be 1 or 2", who);
+  UDASEG_CHECK_ARG(cpad >= 4 && cpad % (out_bf16 ? 8 : 4) == 0, "%s: cpad must be a multiple of %d", who, out_bf16 ? 8 : 4);
+  UDASEG_CHECK_ARG((int64_t)h * w < (1LL << 30) && n <= 65535, "%s: batch too large", who);
+  UDASEG_CHECK_ARG(!source_pass || mid, "%s: the source pass needs the intermediate buffer", who);
+  UDASEG_CHECK_ARG(((uintptr_t)mid & 15) == 0 && ((uintptr_t)out_images & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  UDASEG_CHECK_ARG(!clahe || lut, "%s: the table pass needs the table buffer", who);
+  UDASEG_CHECK_ARG(!clahe || (h % CL_GRID == 0 && w % CL_GRID == 0), "%s: the frame sides must be multiples of %d", who, CL_GRID);
   hipStream_t st = as_stream(stream);
   if (source_pass) {
     const int tiles = cdiv(h, SA_TILE) * cdiv(w, SA_TILE);
     hipLaunchKernelGGL(strong_source_kernel, dim3(tiles, n, views), dim3(256), 0, st, images, table, n, h, w, (f32x4*)mid);
     UDASEG_LAUNCH_CHECK("strong_aug source pass launch");
   }
+  if (clahe) {
+    clahe_launch_lut(images, table, SA_WORDS, views, n, h, w, source_pass ? mid : nullptr, nullptr, lut, st);
+    UDASEG_LAUNCH_CHECK("strong_aug table pass launch");
+  }
   const int gx = (h * w + 255) / 256 > 1024 ? 1024 : (h * w + 255) / 256;
-  if (out_bf16)
-    hipLaunchKernelGGL(strong_output_kernel<true>, dim3(gx, n, views), dim3(256), 0, st, images, table, (const f32x4*)mid, n, h, w,
-                       mean255[0], mean255[1], mean255[2], inv_std255[0], inv_std255[1], inv_std255[2], out_images, cpad);
-  else
-    hipLaunchKernelGGL(strong_output_kernel<false>, dim3(gx, n, views), dim3(256), 0, st, images, table, (const f32x4*)mid, n, h, w,
-                       mean255[0], mean255[1], mean255[2], inv_std255[0], inv_std255[1], inv_std255[2], out_images, cpad);
+  const float m0 = mean255[0], m1 = mean255[1], m2 = mean255[2], r0 = inv_std255[0], r1 = inv_std255[1], r2 = inv_std255[2];
+  const uint8_t* tab = lut;
+#define UDASEG_SA_OUTPUT(BF16, CLAHE)                                                                                                \
+  hipLaunchKernelGGL((strong_output_kernel<BF16, CLAHE>), dim3(gx, n, views), dim3(256), 0, st, images, table, (const f32x4*)mid, n, \
+                     h, w, m0, m1, m2, r0, r1, r2, out_images, cpad, tab)
+  if (clahe) {
+    if (out_bf16) UDASEG_SA_OUTPUT(true, true);
+    else UDASEG_SA_OUTPUT(false, true);
+  } else {
+    if (out_bf16) UDASEG_SA_OUTPUT(true, false);
+    else UDASEG_SA_OUTPUT(false, false);
+  }
+#undef UDASEG_SA_OUTPUT
   UDASEG_LAUNCH_CHECK("strong_aug output pass launch");
   return UDASEG_OK;
+}
+
+extern "C" int udaseg_strong_aug_u8(const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
+                                    const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
+                                    int source_pass, void* stream) {
+  return strong_aug_run("strong_aug_u8", images, table, views, n, h, w, mid, mean255, inv_std255, out_images, cpad, out_bf16,
+                        source_pass, nullptr, false, stream);
+}
+
+extern "C" int udaseg_strong_aug_clahe_u8(const uint8_t* images, const int32_t* table, int views, int n, int h, int w, float* mid,
+                                          const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
+                                          int source_pass, uint8_t* lut, void* stream) {
+  return strong_aug_run("strong_aug_clahe_u8", images, table, views, n, h, w, mid, mean255, inv_std255, out_images, cpad, out_bf16,
+                        source_pass, lut, true, stream);
 }
 
 extern "C" int udaseg_philox4x32_debug(const int32_t* counters, const int32_t* keys, int32_t* out, int count, void* stream) {

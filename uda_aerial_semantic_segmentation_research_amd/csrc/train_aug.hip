@@ -11,36 +11,12 @@
 //   output pass  the composed gather (x 9 for the 3x3 stage), the point-wise stages, the image store and the mask store
 // A record with every stage off computes exactly udaseg_prepare_batch_u8's arithmetic, image and mask.
 // Stage selection is per sample (blockIdx.y): every branch on the record is uniform over the block.
+// udaseg_train_aug_clahe_u8 is the same call for batches with a record on CLAHE (stage-5 kind 3): the table pass (clahe.hip)
+// runs in front of the output pass, which is the variant with that one more stage-5 branch; the record, the geometry and the
+// composed gather (TaRec, TaGeo, ta_stage4) live in aug_common.h, where the table pass finds them too.
 #include "aug_common.h"
 
 namespace udaseg {
-
-constexpr int TA_WORDS = 64;            // 4-byte words per record (include/udaseg.h: UDASEG_TRAIN_AUG_WORDS); 0..31: the strong record
-constexpr int TA_DISTORT = 32;          // flag bit of word 0
-constexpr int TA_OPTICAL = 1, TA_GRID = 2, TA_ELASTIC = 3;
-constexpr int TA_MAX_RADIUS = 18;       // include/udaseg.h: UDASEG_ELASTIC_MAX_RADIUS
-constexpr int TA_FT = 32;               // the field kernel's tile side
-constexpr int TA_FS = TA_FT + 2 * TA_MAX_RADIUS;
-
-typedef float ta_f2 __attribute__((ext_vector_type(2)));
-
-struct TaWeights { float w[2 * TA_MAX_RADIUS + 1]; };
-
-struct TaRec {
-  SaRec s;
-  int kind;                             // 0: no distortion
-  float ok, odx, ody;                   // optical
-  float alpha;                          // elastic (the grid's step factors go to LDS: ta_grid_table)
-};
-
-__device__ __forceinline__ TaRec ta_load(const int32_t* __restrict__ t) {
-  TaRec r;
-  r.s = sa_load(t);
-  r.kind = (r.s.flags & TA_DISTORT) ? t[32] : 0;
-  r.ok = __int_as_float(t[33]); r.odx = __int_as_float(t[34]); r.ody = __int_as_float(t[35]);
-  r.alpha = __int_as_float(t[48]);
-  return r;
-}
 
 // ------------------------------------------------------------------------------------------------------ the elastic field
 // G = separable Gaussian (radius R, reflect-101 at any distance) of the raw field (2 u0 - 1, 2 u1 - 1), u = the first two
@@ -102,110 +78,14 @@ __global__ __launch_bounds__(256) void train_source_kernel(const uint8_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------ output pass
-struct TaGeo {                          // what the block needs of the record's geometry, formed once
-  int kind, affine, cw, ch;
-  float cx, cy;                         // optical centre
-  const float* grid;                    // LDS: x starts [6], x steps [6], y starts [6], y steps [6]
-  const ta_f2* field;                   // the sample's field, or nullptr
-};
-
-// grid distortion: cell i of an axis starts at s_i on the source grid, s_0 = 0, s_{i+1} = s_i + cell * step_i (summed in this
-// order); threads 0..11 form one entry each of the block's table
-__device__ __forceinline__ void ta_grid_table(const int32_t* __restrict__ t, int cw, int ch, float* tab) {
-  if (threadIdx.x < 12) {
-    const int axis = threadIdx.x / 6, cell = threadIdx.x - axis * 6;
-    const int32_t* steps = t + 36 + 6 * axis;
-    const float side = (float)(axis ? ch : cw);
-    float s = 0.f;
-    for (int i = 0; i < cell; ++i) s = s + side * __int_as_float(steps[i]);
-    tab[12 * axis + cell] = s;
-    tab[12 * axis + 6 + cell] = __int_as_float(steps[cell]);
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ TaGeo ta_geometry(const TaRec& rec, const ta_f2* field, const float* grid, int h, int w) {
-  TaGeo g;
-  g.kind = rec.kind;
-  g.affine = (rec.s.flags & SA_AFFINE) ? 1 : 0;
-  g.field = field;
-  g.grid = grid;
-  g.cw = w / 5 > 0 ? w / 5 : 1;
-  g.ch = h / 5 > 0 ? h / 5 : 1;
-  g.cx = (float)(w - 1) * 0.5f + rec.odx;
-  g.cy = (float)(h - 1) * 0.5f + rec.ody;
-  if (g.kind == TA_ELASTIC && !field) g.kind = 0;               // the binding refuses such a call; never dereference a missing field
-  return g;
-}
-
-__device__ __forceinline__ float ta_grid_axis(int x, int cw, const float* tab) {
-  int i = x / cw;
-  i = i < 5 ? i : 5;                                            // the last cell takes what remains of the axis
-  return tab[i] + (float)(x - i * cw) * tab[6 + i];
-}
-
-// source position r of output pixel (y, x) (inside the frame): r = M (q(p), 1)
-__device__ __forceinline__ void ta_position(const TaGeo& g, const TaRec& rec, int y, int x, int h, int w, float& rx, float& ry) {
-  const float fx = (float)x, fy = (float)y;
-  if (!g.kind) {                                                // shift-scale-rotate alone: sa_stage4's own expression
-    rx = rec.s.m[0] * fx + rec.s.m[1] * fy + rec.s.m[2];
-    ry = rec.s.m[3] * fx + rec.s.m[4] * fy + rec.s.m[5];
-    return;
-  }
-  float qx = fx, qy = fy;
-  if (g.kind == TA_OPTICAL) {
-    const float ex = fx - g.cx, ey = fy - g.cy;
-    const float u = ex / (float)w, v = ey / (float)h;
-    const float r2 = u * u + v * v;
-    const float f = 1.f + rec.ok * r2 + rec.ok * r2 * r2;
-    qx = g.cx + ex * f;
-    qy = g.cy + ey * f;
-  } else if (g.kind == TA_GRID) {
-    qx = ta_grid_axis(x, g.cw, g.grid);
-    qy = ta_grid_axis(y, g.ch, g.grid + 12);
-  } else if (g.kind == TA_ELASTIC) {
-    const ta_f2 d = g.field[y * w + x];
-    qx = fx + rec.alpha * d.x;
-    qy = fy + rec.alpha * d.y;
-  }
-  if (g.affine) {
-    rx = rec.s.m[0] * qx + rec.s.m[1] * qy + rec.s.m[2];
-    ry = rec.s.m[3] * qx + rec.s.m[4] * qy + rec.s.m[5];
-  } else {
-    rx = qx;
-    ry = qy;
-  }
-}
-
-// the image after stages 4 and 4b at output-grid pixel (y, x) (inside the frame): one bilinear sample at r
-// (the interpolation is written out as in sa_stage4, which stays as it is: its compiled arithmetic is what strong_views is pinned to)
-__device__ __forceinline__ void ta_stage4(const SaSrc& s, const TaGeo& g, const TaRec& rec, int y, int x, float (&v)[3]) {
-  if (!g.kind) {                                                // no distortion: the strong pipeline's stage 4, bit for bit
-    sa_stage4(s, rec.s, y, x, v);
-    return;
-  }
-  float sx, sy;
-  ta_position(g, rec, y, x, s.h, s.w, sx, sy);
-  const float x0f = floorf(sx), y0f = floorf(sy);
-  const float ax = sx - x0f, ay = sy - y0f;
-  const int x0 = reflect101((int)x0f, s.w), x1 = reflect101((int)x0f + 1, s.w);
-  const int y0 = reflect101((int)y0f, s.h), y1 = reflect101((int)y0f + 1, s.h);
-  float a[3], b[3], c[3], d[3];
-  sa_fetch(s, y0, x0, a);
-  sa_fetch(s, y0, x1, b);
-  sa_fetch(s, y1, x0, c);
-  sa_fetch(s, y1, x1, d);
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    v[k] = (1.f - ay) * ((1.f - ax) * a[k] + ax * b[k]) + ay * ((1.f - ax) * c[k] + ax * d[k]);
-}
-
-template <bool BF16>
+// the output pass.  CLAHE = false is the kernel of udaseg_train_aug_u8 (lut is not read); CLAHE = true adds stage-5 kind 3 (the
+// sample's table from the table pass, clahe.hip) and leaves every other branch as it is written here.  The mask never sees it.
+template <bool BF16, bool CLAHE>
 __global__ __launch_bounds__(256) void train_output_kernel(const uint8_t* __restrict__ images, const uint8_t* __restrict__ masks,
                                                            const int32_t* __restrict__ table, const f32x4* __restrict__ mid,
                                                            const ta_f2* __restrict__ field, int h, int w, float m0, float m1, float m2,
                                                            float r0, float r1, float r2, void* __restrict__ out, int cpad,
-                                                           int64_t* __restrict__ out_masks) {
+                                                           int64_t* __restrict__ out_masks, const uint8_t* __restrict__ lut) {
   __shared__ float grid_tab[24];
   const int ni = blockIdx.y;
   const TaRec rec = ta_load(table + (size_t)ni * TA_WORDS);
@@ -249,6 +129,9 @@ __global__ __launch_bounds__(256) void train_output_kernel(const uint8_t* __rest
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) v[c] = clamp255(acc[c]);
+    } else if (CLAHE && (rec.s.flags & SA_STAGE5) && rec.s.s5_kind == SA_CLAHE) {
+      ta_stage4(src, geo, rec, y, x, v);
+      cl_apply(v, lut + (size_t)ni * (CL_TILES * CL_BINS), y, x, h / CL_GRID, w / CL_GRID);
     } else {
       ta_stage4(src, geo, rec, y, x, v);
       if (rec.s.flags & SA_STAGE5) {                             // brightness-contrast: v (1 + c) + 255 b
@@ -311,19 +194,22 @@ extern "C" int udaseg_elastic_field_f32(const int32_t* table, int n, int h, int 
   return UDASEG_OK;
 }
 
-extern "C" int udaseg_train_aug_u8(const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w, float* mid,
-                                   float* field, const float* gauss_weights, int radius, const float* mean255,
-                                   const float* inv_std255, void* out_images, int cpad, int out_bf16, int64_t* out_masks,
-                                   int source_pass, int field_pass, void* stream) {
-  UDASEG_CHECK_ARG(images && table && out_images && mean255 && inv_std255 && n > 0 && h > 0 && w > 0, "train_aug_u8: bad arguments");
-  UDASEG_CHECK_ARG(cpad >= 4 && cpad % (out_bf16 ? 8 : 4) == 0, "train_aug_u8: cpad must be a multiple of %d", out_bf16 ? 8 : 4);
-  UDASEG_CHECK_ARG((int64_t)h * w < (1LL << 30) && n <= 65535, "train_aug_u8: batch too large");
-  UDASEG_CHECK_ARG((masks == nullptr) == (out_masks == nullptr), "train_aug_u8: masks and out_masks go together");
-  UDASEG_CHECK_ARG(!source_pass || mid, "train_aug_u8: the source pass needs the intermediate buffer");
-  UDASEG_CHECK_ARG(!field_pass || (field && gauss_weights), "train_aug_u8: the field pass needs the field buffer and the weights");
-  UDASEG_CHECK_ARG(!field_pass || (radius >= 0 && radius <= TA_MAX_RADIUS), "train_aug_u8: radius must be 0..%d", TA_MAX_RADIUS);
-  UDASEG_CHECK_ARG(((uintptr_t)mid & 15) == 0 && ((uintptr_t)out_images & 15) == 0, "train_aug_u8: buffers must be 16-byte aligned");
-  UDASEG_CHECK_ARG(((uintptr_t)field & 7) == 0 && ((uintptr_t)out_masks & 7) == 0, "train_aug_u8: field and out_masks must be 8-byte aligned");
+// every pass of a call; clahe == false: today's launches, else the table pass goes in front of the output pass
+static int train_aug_run(const char* who, const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w,
+                         float* mid, float* field, const float* gauss_weights, int radius, const float* mean255,
+                         const float* inv_std255, void* out_images, int cpad, int out_bf16, int64_t* out_masks, int source_pass,
+                         int field_pass, uint8_t* lut, bool clahe, void* stream) {
+  UDASEG_CHECK_ARG(images && table && out_images && mean255 && inv_std255 && n > 0 && h > 0 && w > 0, "%s: bad arguments", who);
+  UDASEG_CHECK_ARG(cpad >= 4 && cpad % (out_bf16 ? 8 : 4) == 0, "%s: cpad must be a multiple of %d", who, out_bf16 ? 8 : 4);
+  UDASEG_CHECK_ARG((int64_t)h * w < (1LL << 30) && n <= 65535, "%s: batch too large", who);
+  UDASEG_CHECK_ARG((masks == nullptr) == (out_masks == nullptr), "%s: masks and out_masks go together", who);
+  UDASEG_CHECK_ARG(!source_pass || mid, "%s: the source pass needs the intermediate buffer", who);
+  UDASEG_CHECK_ARG(!field_pass || (field && gauss_weights), "%s: the field pass needs the field buffer and the weights", who);
+  UDASEG_CHECK_ARG(!field_pass || (radius >= 0 && radius <= TA_MAX_RADIUS), "%s: radius must be 0..%d", who, TA_MAX_RADIUS);
+  UDASEG_CHECK_ARG(((uintptr_t)mid & 15) == 0 && ((uintptr_t)out_images & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+  UDASEG_CHECK_ARG(((uintptr_t)field & 7) == 0 && ((uintptr_t)out_masks & 7) == 0, "%s: field and out_masks must be 8-byte aligned", who);
+  UDASEG_CHECK_ARG(!clahe || lut, "%s: the table pass needs the table buffer", who);
+  UDASEG_CHECK_ARG(!clahe || (h % CL_GRID == 0 && w % CL_GRID == 0), "%s: the frame sides must be multiples of %d", who, CL_GRID);
   hipStream_t st = as_stream(stream);
   if (field_pass) {
     TaWeights gw;
@@ -336,15 +222,40 @@ extern "C" int udaseg_train_aug_u8(const uint8_t* images, const uint8_t* masks, 
     hipLaunchKernelGGL(train_source_kernel, dim3(tiles, n), dim3(256), 0, st, images, table, h, w, (f32x4*)mid);
     UDASEG_LAUNCH_CHECK("train_aug source pass launch");
   }
+  if (clahe) {
+    clahe_launch_lut(images, table, TA_WORDS, 1, n, h, w, source_pass ? mid : nullptr, field, lut, st);
+    UDASEG_LAUNCH_CHECK("train_aug table pass launch");
+  }
   const int gx = (h * w + 255) / 256 > 1024 ? 1024 : (h * w + 255) / 256;
-  if (out_bf16)
-    hipLaunchKernelGGL(train_output_kernel<true>, dim3(gx, n), dim3(256), 0, st, images, masks, table, (const f32x4*)mid,
-                       (const ta_f2*)field, h, w, mean255[0], mean255[1], mean255[2], inv_std255[0], inv_std255[1], inv_std255[2],
-                       out_images, cpad, out_masks);
-  else
-    hipLaunchKernelGGL(train_output_kernel<false>, dim3(gx, n), dim3(256), 0, st, images, masks, table, (const f32x4*)mid,
-                       (const ta_f2*)field, h, w, mean255[0], mean255[1], mean255[2], inv_std255[0], inv_std255[1], inv_std255[2],
-                       out_images, cpad, out_masks);
+  const float m0 = mean255[0], m1 = mean255[1], m2 = mean255[2], r0 = inv_std255[0], r1 = inv_std255[1], r2 = inv_std255[2];
+  const uint8_t* tab = lut;
+#define UDASEG_TA_OUTPUT(BF16, CLAHE)                                                                                               \
+  hipLaunchKernelGGL((train_output_kernel<BF16, CLAHE>), dim3(gx, n), dim3(256), 0, st, images, masks, table, (const f32x4*)mid,    \
+                     (const ta_f2*)field, h, w, m0, m1, m2, r0, r1, r2, out_images, cpad, out_masks, tab)
+  if (clahe) {
+    if (out_bf16) UDASEG_TA_OUTPUT(true, true);
+    else UDASEG_TA_OUTPUT(false, true);
+  } else {
+    if (out_bf16) UDASEG_TA_OUTPUT(true, false);
+    else UDASEG_TA_OUTPUT(false, false);
+  }
+#undef UDASEG_TA_OUTPUT
   UDASEG_LAUNCH_CHECK("train_aug output pass launch");
   return UDASEG_OK;
+}
+
+extern "C" int udaseg_train_aug_u8(const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w, float* mid,
+                                   float* field, const float* gauss_weights, int radius, const float* mean255,
+                                   const float* inv_std255, void* out_images, int cpad, int out_bf16, int64_t* out_masks,
+                                   int source_pass, int field_pass, void* stream) {
+  return train_aug_run("train_aug_u8", images, masks, table, n, h, w, mid, field, gauss_weights, radius, mean255, inv_std255, out_images,
+                       cpad, out_bf16, out_masks, source_pass, field_pass, nullptr, false, stream);
+}
+
+extern "C" int udaseg_train_aug_clahe_u8(const uint8_t* images, const uint8_t* masks, const int32_t* table, int n, int h, int w,
+                                         float* mid, float* field, const float* gauss_weights, int radius, const float* mean255,
+                                         const float* inv_std255, void* out_images, int cpad, int out_bf16, int64_t* out_masks,
+                                         int source_pass, int field_pass, uint8_t* lut, void* stream) {
+  return train_aug_run("train_aug_clahe_u8", images, masks, table, n, h, w, mid, field, gauss_weights, radius, mean255, inv_std255,
+                       out_images, cpad, out_bf16, out_masks, source_pass, field_pass, lut, true, stream);
 }

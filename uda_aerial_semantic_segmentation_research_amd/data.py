@@ -6,7 +6,7 @@ move to one HIP kernel (csrc/data_prep.hip): the D4 geometric augmentations (``R
 image and mask together), ``A.Normalize()`` and the layout change -- the output is already the channel-padded NHWC tensor
 the stem convolution reads, handed to ``Unet`` as an ``[N,3,H,W]``-shaped view (no further copy).
 ``prepare_batch`` stops there.  The rest of that basic pipeline (noise, blur, shift-scale-rotate, optical / grid / elastic
-distortion, sharpen / emboss / brightness-contrast, HSV) runs on the device too, through ``train_batch``
+distortion, CLAHE / sharpen / emboss / brightness-contrast, HSV) runs on the device too, through ``train_batch``
 (csrc/train_aug.hip): uint8 frames and uint8 masks in, augmented model input and int64 masks out, image and mask carried
 through the same geometry, from a pipeline this build defines itself ("Training augmentation") with all
 randomness except the per-pixel Philox streams drawn on the host by ``draw_training_params``.  ``DeviceAugmentedLoader`` wraps
@@ -14,8 +14,8 @@ a loader of uint8 batches so that ``SegmentationTrainer`` / ``AdversarialTrainer
 
 Phase 3 (``src/models/unsupervised_trainer.py:100-114``) needs two STRONGLY augmented views of every unlabelled batch
 (``augmentation.py:40-88``); ``strong_views`` makes both on the device from a pipeline this build defines itself (INTEGRATION.md,
-"Phase 3": D4, Gaussian noise, blur, shift-scale-rotate, sharpen / emboss / brightness-contrast, HSV shift, Normalize;
-csrc/strong_aug.hip), with all randomness except the per-pixel noise drawn on the host by ``draw_strong_params``.
+"Phase 3": D4, Gaussian noise, blur, shift-scale-rotate, CLAHE / sharpen / emboss / brightness-contrast, HSV shift, Normalize;
+csrc/strong_aug.hip, csrc/clahe.hip), with all randomness except the per-pixel noise drawn on the host by ``draw_strong_params``.
 """
 import ctypes
 
@@ -147,6 +147,8 @@ SA_WORDS = 32
 SA_NOISE, SA_BLUR, SA_AFFINE, SA_STAGE5, SA_HSV = 1, 2, 4, 8, 16
 BLUR_BOX, BLUR_MEDIAN, BLUR_MOTION = 0, 1, 2
 STAGE5_SHARPEN, STAGE5_EMBOSS, STAGE5_BRIGHTNESS_CONTRAST = 0, 1, 2
+STAGE5_CLAHE = 3                           # stage 5's fourth child: its own setter (set_clahe), its own pass and entry points
+CLAHE_GRID, CLAHE_LUT_BYTES = 8, 8 * 8 * 256
 (_W_FLAGS, _W_D4, _W_BLUR_KIND, _W_BLUR_K, _W_MOTION_DIR, _W_S5_KIND, _W_KEY, _W_SIGMA, _W_AFFINE, _W_S5_PARAMS, _W_HSV,
  _W_NOOP_DISTORT, _W_NOOP_CLAHE) = 0, 1, 2, 3, 4, 5, 6, 8, 9, 15, 17, 20, 21
 
@@ -182,6 +184,7 @@ class StrongAugParams:
         self._f[:, _W_AFFINE + 4] = 1.0
         if d4_codes is not None:
             self._i[:, _W_D4] = np.asarray(d4_codes, dtype=np.int32).reshape(self.n)
+        self.any_clahe = False                               # whether a record is on CLAHE, as of the last check()
 
     # ---- one stage of one sample
     def set_d4(self, i, code):
@@ -215,6 +218,15 @@ class StrongAugParams:
         self._i[i, _W_S5_KIND] = kind
         self._f[i, _W_S5_PARAMS:_W_S5_PARAMS + 2] = (p0, p1)
 
+    def set_clahe(self, i, clip_limit):
+        """CLAHE on the Lab lightness (8 x 8 tiles) as the sample's stage 5, in place of sharpen / emboss / brightness-contrast;
+        ``clip_limit >= 1`` as albumentations draws it.  The frame sides must be multiples of 8 (``check``)."""
+        if not clip_limit >= 1.0:
+            raise ValueError("set_clahe: clip_limit must be at least 1")
+        self._i[i, _W_FLAGS] |= SA_STAGE5
+        self._i[i, _W_S5_KIND] = STAGE5_CLAHE
+        self._f[i, _W_S5_PARAMS:_W_S5_PARAMS + 2] = (clip_limit, 0.0)
+
     def set_hsv(self, i, dh, ds, dv):
         self._i[i, _W_FLAGS] |= SA_HSV
         self._f[i, _W_HSV:_W_HSV + 3] = (dh, ds, dv)
@@ -241,6 +253,11 @@ class StrongAugParams:
     def d4(self):
         return self._i[:, _W_D4]
 
+    @property
+    def clahe(self):
+        """Per sample: whether the record is on CLAHE."""
+        return ((self._i[:, _W_FLAGS] & SA_STAGE5) != 0) & (self._i[:, _W_S5_KIND] == STAGE5_CLAHE)
+
     def check(self, n, h, w):
         if (self.n, self.h, self.w) != (n, h, w):
             raise ValueError(f"strong_views: records drawn for {self.n} x {self.h} x {self.w} frames, batch is {n} x {h} x {w}")
@@ -252,15 +269,30 @@ class StrongAugParams:
         blur = (i[:, _W_FLAGS] & SA_BLUR) != 0
         if bool((blur & ((i[:, _W_BLUR_K] != 3) & (i[:, _W_BLUR_K] != 5))).any()):
             raise ValueError("strong_views: blur sizes are 3 or 5")
+        self.any_clahe = bool((i[:, _W_S5_KIND] == STAGE5_CLAHE).any()) and bool(self.clahe.any())   # one comparison when none is
+        if self.any_clahe:
+            on = self.clahe
+            if h % CLAHE_GRID or w % CLAHE_GRID:
+                raise ValueError(f"CLAHE records need frame sides that are multiples of {CLAHE_GRID}, batch is {h} x {w}")
+            if not bool((self._f[on, _W_S5_PARAMS] >= 1.0).all()):
+                raise ValueError("CLAHE records need a clip limit of at least 1")
 
 
-def draw_strong_params(n, h, w, generator=None):
+def _clahe_frames(who, clahe, h, w):
+    if clahe and (h % CLAHE_GRID or w % CLAHE_GRID):
+        raise ValueError(f"{who}: clahe=True needs frame sides that are multiples of {CLAHE_GRID}, got {h} x {w}")
+
+
+def draw_strong_params(n, h, w, generator=None, clahe=False):
     """One record per sample with the branch probabilities of the reference's strong pipeline (``augmentation.py:42-88``);
     ``OneOf(p=P)``: apply with probability P, pick a child with probability proportional to the child's own ``p``.  Drawn on the
-    host from ``generator`` (a CPU ``torch.Generator``).  The stages this build leaves out (optical / grid / elastic distortion,
-    CLAHE) are drawn too and recorded as no-ops (words 20, 21), so every other rate is the reference's.  On non-square frames
-    the transpose bit of the D4 code is dropped."""
+    host from ``generator`` (a CPU ``torch.Generator``).  The distortions, which the strong pipeline leaves out, are drawn too and
+    recorded as a no-op (word 20), so every other rate is the reference's.  CLAHE (``clip_limit=4``: uniform in [1, 4]) is opt-in:
+    by default it is drawn and recorded as a no-op (word 21); with ``clahe=True`` the same draws switch the stage on
+    (``set_clahe``) and word 21 stays 0 -- every other word of every record is the same either way.  On non-square frames the
+    transpose bit of the D4 code is dropped."""
     import math
+    _clahe_frames("draw_strong_params", clahe, h, w)
     g = generator
     codes = random_d4_codes(n, g, 0.7, 0.7, 0.7).numpy()
     if h != w:
@@ -282,7 +314,9 @@ def draw_strong_params(n, h, w, generator=None):
             P.ints[i, _W_NOOP_DISTORT] = 1
         if r[13] < 0.5:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast) at 0.4 each, p = 0.5
             child = min(int(r[14] * 4), 3)
-            if child == 0:
+            if child == 0 and clahe:
+                P.set_clahe(i, 1.0 + r[15] * (4.0 - 1.0))
+            elif child == 0:
                 P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
             elif child == 1:
                 P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[15], 0.5 + 0.5 * r[16])
@@ -295,12 +329,23 @@ def draw_strong_params(n, h, w, generator=None):
     return P
 
 
+def _clahe_buffer(clahe_tables, slots, dev):
+    """The table buffer of a call with a record on CLAHE: the caller's (tests and tools read the tables back) or a fresh one."""
+    if clahe_tables is None:
+        return torch.empty(slots * CLAHE_LUT_BYTES, device=dev, dtype=torch.uint8)
+    if (not torch.is_tensor(clahe_tables) or clahe_tables.dtype != torch.uint8 or clahe_tables.device != dev
+            or clahe_tables.numel() != slots * CLAHE_LUT_BYTES or not clahe_tables.is_contiguous()):
+        raise ValueError(f"clahe_tables must be a contiguous uint8 tensor of {slots} x 8 x 8 x 256 elements on {dev}")
+    return clahe_tables
+
+
 def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                 max_pixel_value=255.0):
+                 max_pixel_value=255.0, clahe_tables=None):
     """images_u8 ``[N,H,W,3]`` uint8 (host or device) + one ``StrongAugParams`` per view -> one or two strongly augmented model
     inputs (``[N,3,H,W]``-shaped views of channel-padded NHWC buffers in ``dtype``, as ``prepare_batch`` hands them out).  Both
-    views come from one upload of the frames and one of the records, in at most two kernel launches and without a host
-    synchronisation."""
+    views come from one upload of the frames and one of the records, in at most two kernel launches -- three when a record is
+    on CLAHE (the table pass) -- and without a host synchronisation.  ``clahe_tables``: an optional uint8 device tensor
+    ``[views*N,8,8,256]`` that receives the CLAHE tables of such a call (rows of samples not on CLAHE are left as they are)."""
     _lib.require_gpu()
     if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
         raise ValueError(f"strong_views: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
@@ -323,8 +368,13 @@ def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=I
     buf = torch.empty(views * per, device=dev, dtype=dtype)
     mid = torch.empty(views * n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
-    check(ops.udaseg_strong_aug_u8(img, table, views, n, h, w, mid, m255, r255, buf, cpad, int(dtype == torch.bfloat16),
-                                   source_pass, None), "strong_aug_u8")
+    if any(p.any_clahe for p in params):                         # set by check()
+        lut = _clahe_buffer(clahe_tables, views * n, dev)
+        check(ops.udaseg_strong_aug_clahe_u8(img, table, views, n, h, w, mid, m255, r255, buf, cpad, int(dtype == torch.bfloat16),
+                                             source_pass, lut, None), "strong_aug_clahe_u8")
+    else:
+        check(ops.udaseg_strong_aug_u8(img, table, views, n, h, w, mid, m255, r255, buf, cpad, int(dtype == torch.bfloat16),
+                                       source_pass, None), "strong_aug_u8")
     outs = []
     for v in range(views):
         # a tensor of its own over the view's part of the storage (not a view of ``buf``): it is what the model recognises
@@ -422,12 +472,14 @@ class TrainAugParams(StrongAugParams):
             raise ValueError("train_batch: grid distortion needs frames of at least 5 x 5")
 
 
-def draw_training_params(n, h, w, generator=None):
+def draw_training_params(n, h, w, generator=None, clahe=False):
     """One record per sample with the rates and ranges of the reference's basic training pipeline (``augmentation.py:10-35``;
-    ``OneOf(p=P)`` as in ``draw_strong_params``).  Drawn on the host from ``generator`` (a CPU ``torch.Generator``).  CLAHE is
-    drawn too and recorded as a no-op (word 21), so every other rate is the reference's.  On non-square frames the transpose bit
-    of the D4 code is dropped; frames with a side below 5 are refused (the grid child needs five cells per axis)."""
+    ``OneOf(p=P)`` as in ``draw_strong_params``).  Drawn on the host from ``generator`` (a CPU ``torch.Generator``).  CLAHE
+    (``clip_limit=2``: uniform in [1, 2]) is opt-in as in ``draw_strong_params``: a recorded no-op (word 21) by default, the
+    stage itself with ``clahe=True``, every other word unchanged.  On non-square frames the transpose bit of the D4 code is
+    dropped; frames with a side below 5 are refused (the grid child needs five cells per axis)."""
     import math
+    _clahe_frames("draw_training_params", clahe, h, w)
     if min(h, w) < 5:
         raise ValueError("draw_training_params: frames of at least 5 x 5 (grid distortion)")
     g = generator
@@ -457,7 +509,9 @@ def draw_training_params(n, h, w, generator=None):
                 P.set_elastic(i, 120.0, keys[i, 2:])
         if r[28] < 0.3:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast), equal, p = 0.3
             child = min(int(r[29] * 4), 3)
-            if child == 0:
+            if child == 0 and clahe:
+                P.set_clahe(i, 1.0 + r[30] * (2.0 - 1.0))
+            elif child == 0:
                 P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
             elif child == 1:
                 P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[30], 0.5 + 0.5 * r[31])
@@ -490,13 +544,41 @@ def elastic_field(params, elastic_sigma=6.0):
     return field
 
 
+def clahe_tables(images_u8, params_a, params_b=None):
+    """The CLAHE table pass alone (udaseg_clahe_lut_u8), for tests and tools: uint8 ``[views*N,8,8,256]`` on the GPU, zero rows
+    for samples not on CLAHE.  Records whose stage-4 image needs the source or the field pass (noise, blur, elastic) are
+    refused: ``strong_views`` / ``train_batch`` hand their tables out through ``clahe_tables=``."""
+    _lib.require_gpu()
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"clahe_tables: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+    n, h, w, _ = images_u8.shape
+    params = [params_a] if params_b is None else [params_a, params_b]
+    words = params_a.WORDS if isinstance(params_a, StrongAugParams) else 0
+    for p in params:
+        if not isinstance(p, StrongAugParams) or p.WORDS != words or (len(params) == 2 and words != SA_WORDS):
+            raise ValueError("clahe_tables: one StrongAugParams per view, or one TrainAugParams")
+        p.check(n, h, w)
+        if bool((p.flags & (SA_NOISE | SA_BLUR)).any()) or (words == TA_WORDS and bool((p.distortion == DISTORT_ELASTIC).any())):
+            raise ValueError("clahe_tables: records with noise, blur or elastic distortion take the full call (clahe_tables=)")
+    if h % CLAHE_GRID or w % CLAHE_GRID:
+        raise ValueError(f"clahe_tables: frame sides must be multiples of {CLAHE_GRID}, got {h} x {w}")
+    views = len(params)
+    host = params[0].table if views == 1 else torch.cat([p.table for p in params])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lut = torch.zeros((views * n, CLAHE_GRID, CLAHE_GRID, 256), device=dev, dtype=torch.uint8)
+    check(ops.udaseg_clahe_lut_u8(images_u8.to(dev, non_blocking=True).contiguous(), host.to(dev, non_blocking=True), words, views, n,
+                                  h, w, None, None, lut, None), "clahe_lut_u8")
+    return lut
+
+
 def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=torch.float32, elastic_sigma=6.0,
-                mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=255.0):
+                mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=255.0, clahe=False, clahe_tables=None):
     """images_u8 ``[N,H,W,3]`` uint8, masks_u8 ``[N,H,W]`` uint8 or None (host or device), params: a ``TrainAugParams`` or None
-    (drawn with ``draw_training_params(N, H, W, generator)``) -> ``(images, masks)`` exactly in ``prepare_batch``'s output form:
-    the ``[N,3,H,W]``-shaped view of the padded NHWC buffer in ``dtype`` and int64 masks (or None), augmented by the training
-    pipeline of INTEGRATION.md with image and mask carried through the same geometry.  At most three kernel launches and no host
-    synchronisation; a record with every stage off equals ``prepare_batch`` bit for bit."""
+    (drawn with ``draw_training_params(N, H, W, generator, clahe)``) -> ``(images, masks)`` exactly in ``prepare_batch``'s output
+    form: the ``[N,3,H,W]``-shaped view of the padded NHWC buffer in ``dtype`` and int64 masks (or None), augmented by the
+    training pipeline of INTEGRATION.md with image and mask carried through the same geometry.  At most three kernel launches --
+    four when a record is on CLAHE (the table pass) -- and no host synchronisation; a record with every stage off equals
+    ``prepare_batch`` bit for bit.  ``clahe_tables``: as in ``strong_views``, ``[N,8,8,256]``."""
     _lib.require_gpu()
     if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
         raise ValueError(f"train_batch: images must be uint8 [N,H,W,3], got {getattr(images_u8, 'dtype', type(images_u8))} "
@@ -508,7 +590,7 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
         raise ValueError(f"train_batch: masks must be uint8 [{n},{h},{w}], got {getattr(masks_u8, 'dtype', type(masks_u8))} "
                          f"{tuple(getattr(masks_u8, 'shape', ()))}")
     if params is None:
-        params = draw_training_params(n, h, w, generator)
+        params = draw_training_params(n, h, w, generator, clahe)
     if not isinstance(params, TrainAugParams):
         raise ValueError("train_batch: parameters must be TrainAugParams (64-word records, see draw_training_params)")
     params.check(n, h, w)
@@ -526,8 +608,14 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
     mid = torch.empty(n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
     field = torch.empty(n * h * w * 2, device=dev, dtype=torch.float32) if field_pass else None
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
-    check(ops.udaseg_train_aug_u8(img, msk, table, n, h, w, mid, field, wts, radius, m255, r255, out, cpad,
-                                  int(dtype == torch.bfloat16), out_m, source_pass, field_pass, None), "train_aug_u8")
+    if params.any_clahe:                                         # set by check()
+        lut = _clahe_buffer(clahe_tables, n, dev)
+        check(ops.udaseg_train_aug_clahe_u8(img, msk, table, n, h, w, mid, field, wts, radius, m255, r255, out, cpad,
+                                            int(dtype == torch.bfloat16), out_m, source_pass, field_pass, lut, None),
+              "train_aug_clahe_u8")
+    else:
+        check(ops.udaseg_train_aug_u8(img, msk, table, n, h, w, mid, field, wts, radius, m255, r255, out, cpad,
+                                      int(dtype == torch.bfloat16), out_m, source_pass, field_pass, None), "train_aug_u8")
     mark_padded_input(out)
     return out.permute(0, 3, 1, 2)[:, :3], out_m
 
@@ -535,10 +623,11 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
 class DeviceAugmentedLoader:
     """Wraps a loader of uint8 ``(images [N,H,W,3], masks [N,H,W])`` batches -- or of images alone -- and yields ``train_batch``'s
     output in the same structure: ``(images, masks)`` pairs, or image tensors.  Fresh records are drawn for every batch from
-    ``generator``.  ``SegmentationTrainer.train_epoch`` / ``AdversarialTrainer.train_epoch`` consume it as they are."""
+    ``generator``, with CLAHE switched on by ``clahe=True`` (``draw_training_params``).  ``SegmentationTrainer.train_epoch`` /
+    ``AdversarialTrainer.train_epoch`` consume it as they are."""
 
-    def __init__(self, loader, dtype=torch.float32, generator=None, elastic_sigma=6.0):
-        self.loader, self.dtype, self.generator, self.elastic_sigma = loader, dtype, generator, elastic_sigma
+    def __init__(self, loader, dtype=torch.float32, generator=None, elastic_sigma=6.0, clahe=False):
+        self.loader, self.dtype, self.generator, self.elastic_sigma, self.clahe = loader, dtype, generator, elastic_sigma, clahe
 
     def __len__(self):
         return len(self.loader)
@@ -546,7 +635,7 @@ class DeviceAugmentedLoader:
     def __iter__(self):
         for batch in self.loader:
             if torch.is_tensor(batch):
-                yield train_batch(batch, None, None, self.generator, self.dtype, self.elastic_sigma)[0]
+                yield train_batch(batch, None, None, self.generator, self.dtype, self.elastic_sigma, clahe=self.clahe)[0]
             else:
                 images, masks = batch
-                yield train_batch(images, masks, None, self.generator, self.dtype, self.elastic_sigma)
+                yield train_batch(images, masks, None, self.generator, self.dtype, self.elastic_sigma, clahe=self.clahe)

@@ -32,10 +32,10 @@ _LOGGED = ("total", "consistency", "domain_confusion", "supervised")
 
 class UnsupervisedTrainer(SegmentationTrainer):
     def __init__(self, model, device, consistency_weight=1.0, domain_weight=0.1, supervised_weight=0.1, rampup_length=40,
-                 log_interval=10, patience=7, augment=None, seed=0):
+                 log_interval=10, patience=7, augment=None, seed=0, clahe=False):
         """``augment``: callable for loaders that yield float ``[N,3,H,W]`` batches (called twice per batch, once per view);
         uint8 ``[N,H,W,3]`` batches take the device pipeline.  ``seed``: of the generator the augmentation records are drawn
-        from."""
+        from.  ``clahe``: draw them with CLAHE switched on (``data.draw_strong_params``)."""
         if not isinstance(model, DomainAdaptationModel):
             dtype = getattr(model, "compute_dtype", torch.float32)
             model = DomainAdaptationModel(model, DomainDiscriminator(compute_dtype=dtype).to(device))
@@ -44,6 +44,7 @@ class UnsupervisedTrainer(SegmentationTrainer):
                                                supervised_weight=supervised_weight, rampup_length=rampup_length)
         self.domain_metrics = DomainAdaptationMetrics()
         self.augment = augment
+        self.clahe = clahe
         self.generator = torch.Generator().manual_seed(seed)
         self.log_interval = log_interval
         self.patience = patience
@@ -69,12 +70,14 @@ class UnsupervisedTrainer(SegmentationTrainer):
                                "data-parallel phase 3 is out of scope")
 
     # ------------------------------------------------------------------------------------------------ one iteration
-    def _views(self, target, params):
+    def _views(self, target, params, clahe=None):
         dtype = getattr(self.model, "compute_dtype", torch.float32)
         if target.dtype == torch.uint8:
             n, h, w, _ = target.shape
             if params is None:
-                params = (data.draw_strong_params(n, h, w, self.generator), data.draw_strong_params(n, h, w, self.generator))
+                clahe = self.clahe if clahe is None else clahe
+                params = (data.draw_strong_params(n, h, w, self.generator, clahe),
+                          data.draw_strong_params(n, h, w, self.generator, clahe))
             frames = target.to(self.device, non_blocking=True)
             view1, view2 = data.strong_views(frames, params[0], params[1], dtype=dtype)
             plain, _ = data.prepare_batch(frames, dtype=dtype)
@@ -85,9 +88,11 @@ class UnsupervisedTrainer(SegmentationTrainer):
         plain = target.to(self.device)
         return self.augment(plain), self.augment(plain), plain
 
-    def finetune_step(self, target_u8, optimizer, epoch, params=None, supervised=None, update_metrics=True, _events=None):
+    def finetune_step(self, target_u8, optimizer, epoch, params=None, supervised=None, update_metrics=True, _events=None,
+                      clahe=None):
         """The hot path.  ``target_u8``: uint8 ``[N,H,W,3]`` frames (or a float batch with ``augment=``); ``params``: a pair of
-        ``data.StrongAugParams`` (drawn from the trainer's generator when None); ``supervised``: ``(images, masks)`` or None.
+        ``data.StrongAugParams`` (drawn from the trainer's generator when None, with ``clahe`` -- the trainer's own setting when
+        None -- passed to the draw); ``supervised``: ``(images, masks)`` or None.
         Returns the loss dict as device tensors, plus ``"skipped"`` (bool).  One host read: the finiteness check of the total,
         which fetches the logged scalars in the same transfer (``self.last_losses``).  ``_events``: a list that receives
         ``(phase, torch.cuda.Event)`` marks (tools/bench_finetune.py)."""
@@ -99,7 +104,7 @@ class UnsupervisedTrainer(SegmentationTrainer):
 
         model = self.model
         mark("augment")
-        view1, view2, plain = self._views(target_u8, params)
+        view1, view2, plain = self._views(target_u8, params, clahe)
         mark("forward")
         pred1 = model(view1)
         pred2 = model(view2)
