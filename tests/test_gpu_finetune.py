@@ -1,4 +1,4 @@
-"""Phase 3 on the device: ``data.strong_views`` (csrc/strong_aug.hip) stage by stage against the float64 numpy restatement of
+"""Phase 3 on the device: ``data.strong_views`` (csrc/augment.hip) stage by stage against the float64 numpy restatement of
 its definition (tests/_strong_aug_ref.py), ``optim.clip_grad_norm_`` against a float64 restatement on the real gradient arenas,
 two live ``Unet`` plans in one autograd graph, and ``UnsupervisedTrainer.finetune_step`` against a torch restatement built
 from the oracle classes.

@@ -1,4 +1,4 @@
-"""The labelled training augmentation on the device: ``data.train_batch`` (csrc/train_aug.hip) against the float64 numpy
+"""The labelled training augmentation on the device: ``data.train_batch`` (csrc/augment.hip, csrc/elastic_field.hip) against the float64 numpy
 restatement of its definition (tests/_train_aug_ref.py; INTEGRATION.md, "Training augmentation").
 
 Image bars as in tests/test_gpu_finetune.py: per sample, |kernel - f64| <= max(4 x |f32 - f64| of the restatement, 2 ulp of fp32

@@ -1,8 +1,9 @@
-// Device helpers shared by the augmentation sources (strong_aug.hip: phase-3 views; train_aug.hip: labelled training batches;
-// clahe.hip: the CLAHE table pass): the record loader, reflect-101, Philox4x32-10, the D4 gather, the k x k median, the stage-3
-// source pass, the frame / intermediate fetch, stage 4 (the affine gather), the HSV shift, the training record with stages
-// 4 + 4b (the composed gather), and CLAHE's colour round trip and per-pixel table blend.  One definition each: both pipelines
-// are held to the same arithmetic bit for bit.
+// Device helpers shared by the augmentation sources (augment.hip: the source and output pass of both pipelines, phase-3 views
+// and labelled training batches; elastic_field.hip: the elastic field pass; clahe.hip: the CLAHE table pass): the record layout
+// and loader, reflect-101, Philox4x32-10, the D4 gather, the k x k median, the stage-3 source pass, the frame / intermediate
+// fetch, stage 4 (the affine gather), the 3 x 3 stage's kernel, the HSV shift, the training record with stages 4 + 4b (the
+// composed gather), the per-block set-up of the passes that evaluate stage 4, and CLAHE's colour round trip and per-pixel
+// table blend.  One definition each: both pipelines are held to the same arithmetic bit for bit.
 #pragma once
 #include "common.h"
 
@@ -10,6 +11,9 @@ namespace udaseg {
 
 constexpr int SA_WORDS = 32;            // 4-byte words per record (include/udaseg.h: UDASEG_STRONG_AUG_WORDS)
 constexpr int SA_NOISE = 1, SA_BLUR = 2, SA_AFFINE = 4, SA_STAGE5 = 8, SA_HSV = 16;
+// word indices of the record (data.py keeps the same list as _W_*)
+constexpr int SA_W_FLAGS = 0, SA_W_D4 = 1, SA_W_BLUR_KIND = 2, SA_W_BLUR_K = 3, SA_W_MOTION_DIR = 4, SA_W_S5_KIND = 5, SA_W_KEY = 6,
+              SA_W_SIGMA = 8, SA_W_AFFINE = 9, SA_W_S5_PARAMS = 15, SA_W_HSV = 17;
 constexpr int SA_TILE = 16, SA_HALO = 2, SA_SIDE = SA_TILE + 2 * SA_HALO, SA_LD = SA_SIDE + 1;
 
 struct SaRec {
@@ -20,13 +24,14 @@ struct SaRec {
 
 __device__ __forceinline__ SaRec sa_load(const int32_t* __restrict__ t) {
   SaRec r;
-  r.flags = t[0]; r.d4 = t[1]; r.blur_kind = t[2]; r.blur_k = t[3]; r.motion_dir = t[4]; r.s5_kind = t[5];
-  r.key0 = (uint32_t)t[6]; r.key1 = (uint32_t)t[7];
-  r.sigma = __int_as_float(t[8]);
+  r.flags = t[SA_W_FLAGS]; r.d4 = t[SA_W_D4]; r.blur_kind = t[SA_W_BLUR_KIND]; r.blur_k = t[SA_W_BLUR_K];
+  r.motion_dir = t[SA_W_MOTION_DIR]; r.s5_kind = t[SA_W_S5_KIND];
+  r.key0 = (uint32_t)t[SA_W_KEY]; r.key1 = (uint32_t)t[SA_W_KEY + 1];
+  r.sigma = __int_as_float(t[SA_W_SIGMA]);
 #pragma unroll
-  for (int i = 0; i < 6; ++i) r.m[i] = __int_as_float(t[9 + i]);
-  r.p5a = __int_as_float(t[15]); r.p5b = __int_as_float(t[16]);
-  r.dh = __int_as_float(t[17]); r.ds = __int_as_float(t[18]); r.dv = __int_as_float(t[19]);
+  for (int i = 0; i < 6; ++i) r.m[i] = __int_as_float(t[SA_W_AFFINE + i]);
+  r.p5a = __int_as_float(t[SA_W_S5_PARAMS]); r.p5b = __int_as_float(t[SA_W_S5_PARAMS + 1]);
+  r.dh = __int_as_float(t[SA_W_HSV]); r.ds = __int_as_float(t[SA_W_HSV + 1]); r.dv = __int_as_float(t[SA_W_HSV + 2]);
   return r;
 }
 
@@ -195,6 +200,20 @@ __device__ __forceinline__ void sa_stage4(const SaSrc& s, const SaRec& rec, int 
     v[k] = (1.f - ay) * ((1.f - ax) * a[k] + ax * b[k]) + ay * ((1.f - ax) * c[k] + ax * d[k]);
 }
 
+// stage 5, kinds 0 and 1: the 3 x 3 stage's kernel (correlation, row-major)
+__device__ __forceinline__ void sa_kernel3(const SaRec& rec, float (&k3)[9]) {
+  const float a = rec.p5a, p = rec.p5b;
+  if (rec.s5_kind == 0) {                                        // sharpen: (1-a) I + a [[-1,-1,-1],[-1,8+l,-1],[-1,-1,-1]]
+#pragma unroll
+    for (int i = 0; i < 9; ++i) k3[i] = -a;
+    k3[4] = (1.f - a) + a * (8.f + p);
+  } else {                                                       // emboss: (1-a) I + a [[-1-s,-s,0],[-s,1,s],[0,s,1+s]]
+    k3[0] = a * (-1.f - p); k3[1] = a * -p; k3[2] = 0.f;
+    k3[3] = a * -p; k3[4] = (1.f - a) + a; k3[5] = a * p;
+    k3[6] = 0.f; k3[7] = a * p; k3[8] = a * (1.f + p);
+  }
+}
+
 __device__ __forceinline__ void sa_hsv_shift(float (&v)[3], float dh, float ds, float dv) {
   const float r = v[0], g = v[1], b = v[2];
   const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
@@ -231,6 +250,7 @@ __device__ __forceinline__ void sa_hsv_shift(float (&v)[3], float dh, float ds, 
 // ---------------------------------------------------------------------------------- the training record and stages 4 + 4b
 constexpr int TA_WORDS = 64;            // 4-byte words per record (include/udaseg.h: UDASEG_TRAIN_AUG_WORDS); 0..31: the strong record
 constexpr int TA_DISTORT = 32;          // flag bit of word 0
+constexpr int TA_W_DISTORT_KIND = 32, TA_W_OPTICAL = 33, TA_W_GRID = 36, TA_W_ELASTIC_ALPHA = 48, TA_W_ELASTIC_KEY = 50;
 constexpr int TA_OPTICAL = 1, TA_GRID = 2, TA_ELASTIC = 3;
 constexpr int TA_MAX_RADIUS = 18;       // include/udaseg.h: UDASEG_ELASTIC_MAX_RADIUS
 constexpr int TA_FT = 32;               // the field kernel's tile side
@@ -250,9 +270,9 @@ struct TaRec {
 __device__ __forceinline__ TaRec ta_load(const int32_t* __restrict__ t) {
   TaRec r;
   r.s = sa_load(t);
-  r.kind = (r.s.flags & TA_DISTORT) ? t[32] : 0;
-  r.ok = __int_as_float(t[33]); r.odx = __int_as_float(t[34]); r.ody = __int_as_float(t[35]);
-  r.alpha = __int_as_float(t[48]);
+  r.kind = (r.s.flags & TA_DISTORT) ? t[TA_W_DISTORT_KIND] : 0;
+  r.ok = __int_as_float(t[TA_W_OPTICAL]); r.odx = __int_as_float(t[TA_W_OPTICAL + 1]); r.ody = __int_as_float(t[TA_W_OPTICAL + 2]);
+  r.alpha = __int_as_float(t[TA_W_ELASTIC_ALPHA]);
   return r;
 }
 
@@ -268,7 +288,7 @@ struct TaGeo {                          // what the block needs of the record's 
 __device__ __forceinline__ void ta_grid_table(const int32_t* __restrict__ t, int cw, int ch, float* tab) {
   if (threadIdx.x < 12) {
     const int axis = threadIdx.x / 6, cell = threadIdx.x - axis * 6;
-    const int32_t* steps = t + 36 + 6 * axis;
+    const int32_t* steps = t + TA_W_GRID + 6 * axis;
     const float side = (float)(axis ? ch : cw);
     float s = 0.f;
     for (int i = 0; i < cell; ++i) s = s + side * __int_as_float(steps[i]);
@@ -352,6 +372,43 @@ __device__ __forceinline__ void ta_stage4(const SaSrc& s, const TaGeo& g, const 
 #pragma unroll
   for (int k = 0; k < 3; ++k)
     v[k] = (1.f - ay) * ((1.f - ax) * a[k] + ax * b[k]) + ay * ((1.f - ax) * c[k] + ax * d[k]);
+}
+
+// What a block of a pass that evaluates stage 4 (the output pass, augment.hip; the table pass, clahe.hip) forms once from its
+// record t: the record, the source and, for the training record, the geometry with the grid table in LDS (grid_tab: 24 floats;
+// not touched with TRAIN == false, where the distortion kind is 0 and geo stays unset).  slot = view * n + ni.
+struct AugBlock {
+  TaRec rec;
+  SaSrc src;
+  TaGeo geo;
+};
+
+template <bool TRAIN>
+__device__ __forceinline__ AugBlock aug_block(const int32_t* __restrict__ t, const uint8_t* __restrict__ images,
+                                              const f32x4* __restrict__ mid, const ta_f2* __restrict__ field, int ni, size_t slot, int h,
+                                              int w, float* grid_tab) {
+  AugBlock b;
+  if (TRAIN) {
+    b.rec = ta_load(t);
+  } else {
+    b.rec.s = sa_load(t);
+    b.rec.kind = 0;
+  }
+  const int hw = h * w;
+  b.src.img = images + (size_t)ni * hw * 3;
+  b.src.mid = ((b.rec.s.flags & (SA_NOISE | SA_BLUR)) && mid) ? mid + slot * hw : nullptr;
+  b.src.d4 = sa_code(b.rec.s.d4, h, w); b.src.h = h; b.src.w = w;
+  if (TRAIN) {
+    b.geo = ta_geometry(b.rec, field ? field + slot * hw : nullptr, grid_tab, h, w);
+    if (b.geo.kind == TA_GRID) ta_grid_table(t, b.geo.cw, b.geo.ch, grid_tab);   // block-uniform
+  }
+  return b;
+}
+
+template <bool TRAIN>
+__device__ __forceinline__ void aug_stage4(const AugBlock& b, int y, int x, float (&v)[3]) {
+  if (TRAIN) ta_stage4(b.src, b.geo, b.rec, y, x, v);
+  else sa_stage4(b.src, b.rec.s, y, x, v);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ CLAHE
@@ -439,5 +496,10 @@ __device__ __forceinline__ void cl_apply(float (&v)[3], const uint8_t* __restric
 // the table pass (clahe.hip) for `words`-word records (32: strong, 64: training): one launch, samples not on CLAHE return at once
 void clahe_launch_lut(const uint8_t* images, const int32_t* table, int words, int views, int n, int h, int w, const float* mid,
                       const float* field, uint8_t* lut, hipStream_t st);
+
+// the field pass (elastic_field.hip) of n training records: float2 field[n][h][w], written for the samples on elastic alone;
+// gauss_weights: 2 radius + 1 taps, radius in 0..TA_MAX_RADIUS (the entry points check both)
+void elastic_launch_field(const int32_t* table, int n, int h, int w, const float* gauss_weights, int radius, float* field,
+                          hipStream_t st);
 
 }  // namespace udaseg

@@ -2,13 +2,14 @@
 // The stage needs a histogram of the Lab lightness of the stage-4 image over each of the 8 x 8 tiles before any output pixel
 // can be written, so it gets a pass of its own between the source pass and the output pass:
 //   one block per (tile, sample, view); samples not on CLAHE return at once (block-uniform)
-//   stage 4 (/ 4b) is evaluated per pixel through sa_stage4 / ta_stage4, as the 3 x 3 stage does: no full-frame intermediate
+//   stage 4 (/ 4b) is evaluated per pixel through aug_stage4 after the output pass's own per-block set-up (aug_block), as the
+//   3 x 3 stage does: no full-frame intermediate
 //   integer histograms in LDS, one private 256-bin histogram per wave (aerial tiles are dominated by a few bins: the four
 //   waves do not queue on one another's atomics), summed afterwards, one bin per thread
 //   clip, redistribution, prefix sum (a wave scan + the four wave totals) and the rounding stay in integers inside the block
 //   output: uint8 lut[slot][8][8][256], slot = view * n + sample
 // Integer LDS atomics are order-independent: two calls give equal bits.  The output pass's CLAHE branch (cl_apply,
-// aug_common.h) lives in the two pipelines' output kernels (strong_aug.hip, train_aug.hip).
+// aug_common.h) lives in the two pipelines' output kernel (augment.hip).
 #include "aug_common.h"
 
 namespace udaseg {
@@ -32,24 +33,8 @@ __global__ __launch_bounds__(256) void clahe_lut_kernel(const uint8_t* __restric
   const int tile = blockIdx.x, ni = blockIdx.y, view = blockIdx.z;
   const size_t slot = (size_t)view * n + ni;
   const int32_t* t = table + slot * WORDS;
-  if (!((t[0] & SA_STAGE5) && t[5] == SA_CLAHE)) return;         // block-uniform
-  TaRec rec;
-  if (TRAIN) {
-    rec = ta_load(t);
-  } else {
-    rec.s = sa_load(t);
-    rec.kind = 0;
-  }
-  const int hw = h * w;
-  SaSrc src;
-  src.img = images + (size_t)ni * hw * 3;
-  src.mid = ((rec.s.flags & (SA_NOISE | SA_BLUR)) && mid) ? mid + slot * hw : nullptr;
-  src.d4 = sa_code(rec.s.d4, h, w); src.h = h; src.w = w;
-  TaGeo geo;
-  if (TRAIN) {
-    geo = ta_geometry(rec, field ? field + slot * hw : nullptr, grid_tab, h, w);
-    if (geo.kind == TA_GRID) ta_grid_table(t, geo.cw, geo.ch, grid_tab);   // block-uniform
-  }
+  if (!((t[SA_W_FLAGS] & SA_STAGE5) && t[SA_W_S5_KIND] == SA_CLAHE)) return;         // block-uniform
+  const AugBlock blk = aug_block<TRAIN>(t, images, mid, field, ni, slot, h, w, grid_tab);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int i = 0; i < CL_WAVES; ++i) hist[i][tid] = 0u;
@@ -59,15 +44,14 @@ __global__ __launch_bounds__(256) void clahe_lut_kernel(const uint8_t* __restric
   for (int i = tid; i < area; i += 256) {
     const int ly = i / tw, lx = i - ly * tw;
     float v[3], l8, a, b;
-    if (TRAIN) ta_stage4(src, geo, rec, ty0 + ly, tx0 + lx, v);
-    else sa_stage4(src, rec.s, ty0 + ly, tx0 + lx, v);
+    aug_stage4<TRAIN>(blk, ty0 + ly, tx0 + lx, v);
     cl_rgb_to_lab(v, l8, a, b);
     atomicAdd(&hist[wave][cl_bin(l8)], 1u);
   }
   __syncthreads();
   // bin `tid` from here on
   unsigned cnt = hist[0][tid] + hist[1][tid] + hist[2][tid] + hist[3][tid];
-  const double lim = (double)rec.s.p5a * (double)area / 256.0;    // exact: a 24-bit factor times an integer below 2^24
+  const double lim = (double)blk.rec.s.p5a * (double)area / 256.0;    // exact: a 24-bit factor times an integer below 2^24
   const unsigned limit = lim >= (double)area ? (unsigned)area : (lim >= 1.0 ? (unsigned)lim : 1u);   // max(1, int(lim)); above the area it clips nothing
   const unsigned over = cnt > limit ? cnt - limit : 0u;
   cnt -= over;

@@ -36,6 +36,29 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// A.Normalize + the channel-padded NHWC store of one pixel (data_prep.hip, augment.hip): (v - 255 mean) * 1 / (255 std) into
+// channels 0..2 of the cpad-wide pixel that starts at element o of out, zeros into the rest
+struct Normalize3 { float m0, m1, m2, r0, r1, r2; };
+static inline Normalize3 normalize3(const float* mean255, const float* inv_std255) {
+  return Normalize3{mean255[0], mean255[1], mean255[2], inv_std255[0], inv_std255[1], inv_std255[2]};
+}
+template <bool BF16>
+__device__ __forceinline__ void store_normalized(void* __restrict__ out, size_t o, int cpad, const Normalize3& nm, float a0, float a1,
+                                                 float a2) {
+  const float v0 = (a0 - nm.m0) * nm.r0, v1 = (a1 - nm.m1) * nm.r1, v2 = (a2 - nm.m2) * nm.r2;
+  if (BF16) {
+    __bf16* dst = reinterpret_cast<__bf16*>(out) + o;
+    dst[0] = (__bf16)v0;
+    dst[1] = (__bf16)v1;
+    dst[2] = (__bf16)v2;
+    for (int k = 3; k < cpad; ++k) dst[k] = (__bf16)0.f;
+  } else {
+    float* dst = reinterpret_cast<float*>(out) + o;
+    *reinterpret_cast<f32x4*>(dst) = f32x4{v0, v1, v2, 0.f};
+    for (int k = 4; k < cpad; ++k) dst[k] = 0.f;
+  }
+}
+
 // q = n / d for 0 <= n < 2^31, d >= 1, with rcp = 1.0f / d: float estimate + exact fix-up.
 __device__ __forceinline__ int fast_div(int n, int d, float rcp) {
   int q = (int)((float)n * rcp);

@@ -14,9 +14,8 @@ namespace udaseg {
 //   out = fliph^b2( flipv^b1( transpose^b0( in ) ) )
 template <bool BF16>
 __global__ __launch_bounds__(256) void prepare_batch_kernel(const uint8_t* __restrict__ images, const uint8_t* __restrict__ masks,
-                                                            const int32_t* __restrict__ d4, int h, int w, float m0, float m1,
-                                                            float m2, float r0, float r1, float r2, void* __restrict__ out,
-                                                            int cpad, int64_t* __restrict__ out_masks) {
+                                                            const int32_t* __restrict__ d4, int h, int w, Normalize3 nm,
+                                                            void* __restrict__ out, int cpad, int64_t* __restrict__ out_masks) {
   const int ni = blockIdx.y;
   const int code = d4 ? d4[ni] : 0;
   const int hw = h * w;
@@ -27,21 +26,8 @@ __global__ __launch_bounds__(256) void prepare_batch_kernel(const uint8_t* __res
     if (code & 2) y = h - 1 - y;
     if (code & 4) x = w - 1 - x;
     const int sp = (code & 1) ? x * w + y : y * w + x;        // transpose needs h == w (checked by the caller)
-    const float v0 = ((float)img[sp * 3 + 0] - m0) * r0;
-    const float v1 = ((float)img[sp * 3 + 1] - m1) * r1;
-    const float v2 = ((float)img[sp * 3 + 2] - m2) * r2;
-    const size_t o = ((size_t)ni * hw + p) * cpad;
-    if (BF16) {
-      __bf16* dst = reinterpret_cast<__bf16*>(out) + o;
-      dst[0] = (__bf16)v0;
-      dst[1] = (__bf16)v1;
-      dst[2] = (__bf16)v2;
-      for (int k = 3; k < cpad; ++k) dst[k] = (__bf16)0.f;
-    } else {
-      float* dst = reinterpret_cast<float*>(out) + o;
-      *reinterpret_cast<f32x4*>(dst) = f32x4{v0, v1, v2, 0.f};
-      for (int k = 4; k < cpad; ++k) dst[k] = 0.f;
-    }
+    store_normalized<BF16>(out, ((size_t)ni * hw + p) * cpad, cpad, nm, (float)img[sp * 3 + 0], (float)img[sp * 3 + 1],
+                           (float)img[sp * 3 + 2]);
     if (msk) out_masks[(size_t)ni * hw + p] = (int64_t)msk[sp];
   }
 }
@@ -62,12 +48,11 @@ extern "C" int udaseg_prepare_batch_u8(const uint8_t* images, const uint8_t* mas
   UDASEG_CHECK_ARG((int64_t)h * w < (1LL << 30), "prepare_batch_u8: image too large");
   const int gx = (h * w + 255) / 256 > 1024 ? 1024 : (h * w + 255) / 256;
   hipStream_t st = as_stream(stream);
+  const Normalize3 nm = normalize3(mean255, inv_std255);
   if (out_bf16)
-    hipLaunchKernelGGL(prepare_batch_kernel<true>, dim3(gx, n), dim3(256), 0, st, images, masks, d4, h, w, mean255[0], mean255[1],
-                       mean255[2], inv_std255[0], inv_std255[1], inv_std255[2], out_images, cpad, out_masks);
+    hipLaunchKernelGGL(prepare_batch_kernel<true>, dim3(gx, n), dim3(256), 0, st, images, masks, d4, h, w, nm, out_images, cpad, out_masks);
   else
-    hipLaunchKernelGGL(prepare_batch_kernel<false>, dim3(gx, n), dim3(256), 0, st, images, masks, d4, h, w, mean255[0], mean255[1],
-                       mean255[2], inv_std255[0], inv_std255[1], inv_std255[2], out_images, cpad, out_masks);
+    hipLaunchKernelGGL(prepare_batch_kernel<false>, dim3(gx, n), dim3(256), 0, st, images, masks, d4, h, w, nm, out_images, cpad, out_masks);
   UDASEG_LAUNCH_CHECK("prepare_batch launch");
   return UDASEG_OK;
 }

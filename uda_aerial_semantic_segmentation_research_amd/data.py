@@ -7,7 +7,7 @@ image and mask together), ``A.Normalize()`` and the layout change -- the output 
 the stem convolution reads, handed to ``Unet`` as an ``[N,3,H,W]``-shaped view (no further copy).
 ``prepare_batch`` stops there.  The rest of that basic pipeline (noise, blur, shift-scale-rotate, optical / grid / elastic
 distortion, CLAHE / sharpen / emboss / brightness-contrast, HSV) runs on the device too, through ``train_batch``
-(csrc/train_aug.hip): uint8 frames and uint8 masks in, augmented model input and int64 masks out, image and mask carried
+(csrc/augment.hip, csrc/elastic_field.hip): uint8 frames and uint8 masks in, augmented model input and int64 masks out, image and mask carried
 through the same geometry, from a pipeline this build defines itself ("Training augmentation") with all
 randomness except the per-pixel Philox streams drawn on the host by ``draw_training_params``.  ``DeviceAugmentedLoader`` wraps
 a loader of uint8 batches so that ``SegmentationTrainer`` / ``AdversarialTrainer`` consume it as they are.
@@ -15,7 +15,7 @@ a loader of uint8 batches so that ``SegmentationTrainer`` / ``AdversarialTrainer
 Phase 3 (``src/models/unsupervised_trainer.py:100-114``) needs two STRONGLY augmented views of every unlabelled batch
 (``augmentation.py:40-88``); ``strong_views`` makes both on the device from a pipeline this build defines itself (INTEGRATION.md,
 "Phase 3": D4, Gaussian noise, blur, shift-scale-rotate, CLAHE / sharpen / emboss / brightness-contrast, HSV shift, Normalize;
-csrc/strong_aug.hip, csrc/clahe.hip), with all randomness except the per-pixel noise drawn on the host by ``draw_strong_params``.
+csrc/augment.hip, csrc/clahe.hip), with all randomness except the per-pixel noise drawn on the host by ``draw_strong_params``.
 """
 import ctypes
 
@@ -96,19 +96,49 @@ def normalize_constants(mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=25
     return m255, r255
 
 
+def _check_frames(who, images_u8, masks_u8=None, dtype=torch.float32):
+    """The checks every entry point makes of (frames, masks, output dtype), arguments that are no tensors included -> n, h, w."""
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"{who}: images must be uint8 [N,H,W,3], got {getattr(images_u8, 'dtype', type(images_u8))} "
+                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: dtype must be torch.float32 or torch.bfloat16")
+    n, h, w, _ = images_u8.shape
+    if masks_u8 is not None and (not torch.is_tensor(masks_u8) or masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != (n, h, w)):
+        raise ValueError(f"{who}: masks must be uint8 [{n},{h},{w}], got {getattr(masks_u8, 'dtype', type(masks_u8))} "
+                         f"{tuple(getattr(masks_u8, 'shape', ()))}")
+    return n, h, w
+
+
+def _device_batch(images_u8, masks_u8, records, n, h, w, dtype, views=1):
+    """The device side of a call: frames, masks and ``records`` (the parameter table or the D4 codes; masks and records may be
+    None) moved with one async copy each -- all copies go out before anything is allocated, so that they run meanwhile -- then
+    the channel padding of ``dtype`` and the unwritten outputs: ``views`` x N padded NHWC images in one buffer and the int64
+    masks (None without masks).  -> (device, frames, masks, records, cpad, images out, masks out)"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    img = images_u8.to(dev, non_blocking=True).contiguous()
+    msk = None if masks_u8 is None else masks_u8.to(dev, non_blocking=True).contiguous()
+    rec = None if records is None else records.to(dev, non_blocking=True).contiguous()
+    cpad = 8 if dtype == torch.bfloat16 else 4
+    out = torch.empty((views * n, h, w, cpad), device=dev, dtype=dtype)
+    out_m = None if msk is None else torch.empty((n, h, w), device=dev, dtype=torch.int64)
+    return dev, img, msk, rec, cpad, out, out_m
+
+
+def _model_input(out):
+    """A padded NHWC buffer ``[N,H,W,cpad]`` as the model takes it: registered for the stem convolution to read in place, handed
+    out as its ``[N,3,H,W]``-shaped view."""
+    mark_padded_input(out)
+    return out.permute(0, 3, 1, 2)[:, :3]
+
+
 def prepare_batch(images_u8, masks_u8=None, d4_codes=None, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD,
                   max_pixel_value=255.0):
     """images_u8 ``[N,H,W,3]`` uint8 (RGB, as decoded), masks_u8 ``[N,H,W]`` uint8 or None, d4_codes ``[N]`` int32 or None
     -> (images ``[N,3,H,W]``-shaped view of the padded NHWC buffer in ``dtype``, masks ``[N,H,W]`` int64 or None).
     Inputs may live on the host (moved with one async copy each) or on the GPU."""
     _lib.require_gpu()
-    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise ValueError(f"prepare_batch: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("prepare_batch: dtype must be torch.float32 or torch.bfloat16")
-    n, h, w, _ = images_u8.shape
-    if masks_u8 is not None and (masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != (n, h, w)):
-        raise ValueError(f"prepare_batch: masks must be uint8 [{n},{h},{w}], got {masks_u8.dtype} {tuple(masks_u8.shape)}")
+    n, h, w = _check_frames("prepare_batch", images_u8, masks_u8, dtype)
     square_ok = 0
     if d4_codes is not None:
         if d4_codes.dtype != torch.int32 or tuple(d4_codes.shape) != (n,):
@@ -119,18 +149,11 @@ def prepare_batch(images_u8, masks_u8=None, d4_codes=None, dtype=torch.float32, 
             if bool((d4_codes & TRANSPOSE).any()):
                 raise ValueError("prepare_batch: transposing D4 codes need square images")
             square_ok = 1
-    dev = torch.device("cuda", torch.cuda.current_device())
-    img = images_u8.to(dev, non_blocking=True).contiguous()
-    msk = None if masks_u8 is None else masks_u8.to(dev, non_blocking=True).contiguous()
-    codes = None if d4_codes is None else d4_codes.to(dev, non_blocking=True).contiguous()
-    cpad = 8 if dtype == torch.bfloat16 else 4
-    out = torch.empty((n, h, w, cpad), device=dev, dtype=dtype)
-    out_m = None if msk is None else torch.empty((n, h, w), device=dev, dtype=torch.int64)
+    _, img, msk, codes, cpad, out, out_m = _device_batch(images_u8, masks_u8, d4_codes, n, h, w, dtype)
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
     check(ops.udaseg_prepare_batch_u8(img, msk, codes, n, h, w, m255, r255, out, cpad, int(dtype == torch.bfloat16), out_m, square_ok,
                                       None), "prepare_batch_u8")
-    mark_padded_input(out)
-    return out.permute(0, 3, 1, 2)[:, :3], out_m
+    return _model_input(out), out_m
 
 
 def synthetic_u8_batch(n, h, w, classes=23, seed=0, device="cuda"):
@@ -283,6 +306,26 @@ def _clahe_frames(who, clahe, h, w):
         raise ValueError(f"{who}: clahe=True needs frame sides that are multiples of {CLAHE_GRID}, got {h} x {w}")
 
 
+def _draw_stage5_hsv(P, i, r, clahe, p5, clip_hi, bc, p_hsv):
+    """Stages 5 and 6 of record ``i`` of either draw from its eight uniforms ``r`` (stage 5: apply, child, two parameters; HSV:
+    apply, three shifts): ``OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast)`` with equal weights at ``p5`` -- the clip limit
+    uniform in [1, ``clip_hi``], brightness and contrast in +-``bc`` -- then ``HueSaturationValue(20, 30, 20)`` at ``p_hsv``."""
+    if r[0] < p5:
+        child = min(int(r[1] * 4), 3)
+        if child == 0 and clahe:
+            P.set_clahe(i, 1.0 + r[2] * (clip_hi - 1.0))
+        elif child == 0:
+            P.ints[i, _W_NOOP_CLAHE] = 1                     # left out, a no-op
+        elif child == 1:
+            P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[2], 0.5 + 0.5 * r[3])
+        elif child == 2:
+            P.set_stage5(i, STAGE5_EMBOSS, 0.2 + 0.3 * r[2], 0.2 + 0.5 * r[3])
+        else:
+            P.set_stage5(i, STAGE5_BRIGHTNESS_CONTRAST, (2 * r[2] - 1) * bc, (2 * r[3] - 1) * bc)
+    if r[4] < p_hsv:
+        P.set_hsv(i, (2 * r[5] - 1) * 20.0, (2 * r[6] - 1) * 30.0, (2 * r[7] - 1) * 20.0)
+
+
 def draw_strong_params(n, h, w, generator=None, clahe=False):
     """One record per sample with the branch probabilities of the reference's strong pipeline (``augmentation.py:42-88``);
     ``OneOf(p=P)``: apply with probability P, pick a child with probability proportional to the child's own ``p``.  Drawn on the
@@ -312,20 +355,8 @@ def draw_strong_params(n, h, w, generator=None, clahe=False):
             P.set_affine(i, (2 * r[8] - 1) * 0.1 * w, (2 * r[9] - 1) * 0.1 * h, 1.0 + (2 * r[10] - 1) * 0.3, (2 * r[11] - 1) * 60.0)
         if r[12] < 0.4:                                      # OneOf(Optical, Grid, Elastic), p = 0.4: left out, a no-op
             P.ints[i, _W_NOOP_DISTORT] = 1
-        if r[13] < 0.5:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast) at 0.4 each, p = 0.5
-            child = min(int(r[14] * 4), 3)
-            if child == 0 and clahe:
-                P.set_clahe(i, 1.0 + r[15] * (4.0 - 1.0))
-            elif child == 0:
-                P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
-            elif child == 1:
-                P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[15], 0.5 + 0.5 * r[16])
-            elif child == 2:
-                P.set_stage5(i, STAGE5_EMBOSS, 0.2 + 0.3 * r[15], 0.2 + 0.5 * r[16])
-            else:
-                P.set_stage5(i, STAGE5_BRIGHTNESS_CONTRAST, (2 * r[15] - 1) * 0.3, (2 * r[16] - 1) * 0.3)
-        if r[17] < 0.4:                                      # HueSaturationValue(20, 30, 20), p = 0.4
-            P.set_hsv(i, (2 * r[18] - 1) * 20.0, (2 * r[19] - 1) * 30.0, (2 * r[20] - 1) * 20.0)
+        # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast) at 0.4 each, p = 0.5; HueSaturationValue(20, 30, 20), p = 0.4
+        _draw_stage5_hsv(P, i, r[13:21], clahe, 0.5, 4.0, 0.3, 0.4)
     return P
 
 
@@ -347,11 +378,7 @@ def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=I
     on CLAHE (the table pass) -- and without a host synchronisation.  ``clahe_tables``: an optional uint8 device tensor
     ``[views*N,8,8,256]`` that receives the CLAHE tables of such a call (rows of samples not on CLAHE are left as they are)."""
     _lib.require_gpu()
-    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise ValueError(f"strong_views: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("strong_views: dtype must be torch.float32 or torch.bfloat16")
-    n, h, w, _ = images_u8.shape
+    n, h, w = _check_frames("strong_views", images_u8, None, dtype)
     params = [params_a] if params_b is None else [params_a, params_b]
     for p in params:
         if not isinstance(p, StrongAugParams) or p.WORDS != SA_WORDS:
@@ -360,12 +387,7 @@ def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=I
     views = len(params)
     host = params[0].table if views == 1 else torch.cat([p.table for p in params])
     source_pass = int(bool((host[:, _W_FLAGS] & (SA_NOISE | SA_BLUR)).any()))
-    dev = torch.device("cuda", torch.cuda.current_device())
-    img = images_u8.to(dev, non_blocking=True).contiguous()
-    table = host.to(dev, non_blocking=True)
-    cpad = 8 if dtype == torch.bfloat16 else 4
-    per = n * h * w * cpad
-    buf = torch.empty(views * per, device=dev, dtype=dtype)
+    dev, img, _, table, cpad, buf, _ = _device_batch(images_u8, None, host, n, h, w, dtype, views)
     mid = torch.empty(views * n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
     if any(p.any_clahe for p in params):                         # set by check()
@@ -378,9 +400,9 @@ def strong_views(images_u8, params_a, params_b=None, dtype=torch.float32, mean=I
     outs = []
     for v in range(views):
         # a tensor of its own over the view's part of the storage (not a view of ``buf``): it is what the model recognises
-        o = torch.empty(0, device=dev, dtype=dtype).set_(buf.untyped_storage(), v * per, (n, h, w, cpad), (h * w * cpad, w * cpad, cpad, 1))
-        mark_padded_input(o)
-        outs.append(o.permute(0, 3, 1, 2)[:, :3])
+        o = torch.empty(0, device=dev, dtype=dtype).set_(buf.untyped_storage(), v * n * h * w * cpad, (n, h, w, cpad),
+                                                         (h * w * cpad, w * cpad, cpad, 1))
+        outs.append(_model_input(o))
     return outs[0] if views == 1 else tuple(outs)
 
 
@@ -507,20 +529,8 @@ def draw_training_params(n, h, w, generator=None, clahe=False):
                 P.set_grid(i, 1.0 + (2 * r[16:22] - 1) * 0.3, 1.0 + (2 * r[22:28] - 1) * 0.3)
             else:
                 P.set_elastic(i, 120.0, keys[i, 2:])
-        if r[28] < 0.3:                                      # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast), equal, p = 0.3
-            child = min(int(r[29] * 4), 3)
-            if child == 0 and clahe:
-                P.set_clahe(i, 1.0 + r[30] * (2.0 - 1.0))
-            elif child == 0:
-                P.ints[i, _W_NOOP_CLAHE] = 1                 # left out, a no-op
-            elif child == 1:
-                P.set_stage5(i, STAGE5_SHARPEN, 0.2 + 0.3 * r[30], 0.5 + 0.5 * r[31])
-            elif child == 2:
-                P.set_stage5(i, STAGE5_EMBOSS, 0.2 + 0.3 * r[30], 0.2 + 0.5 * r[31])
-            else:
-                P.set_stage5(i, STAGE5_BRIGHTNESS_CONTRAST, (2 * r[30] - 1) * 0.2, (2 * r[31] - 1) * 0.2)
-        if r[32] < 0.3:                                      # HueSaturationValue(20, 30, 20), p = 0.3
-            P.set_hsv(i, (2 * r[33] - 1) * 20.0, (2 * r[34] - 1) * 30.0, (2 * r[35] - 1) * 20.0)
+        # OneOf(CLAHE, Sharpen, Emboss, BrightnessContrast), equal, p = 0.3; HueSaturationValue(20, 30, 20), p = 0.3
+        _draw_stage5_hsv(P, i, r[28:36], clahe, 0.3, 2.0, 0.2, 0.3)
     return P
 
 
@@ -549,9 +559,7 @@ def clahe_tables(images_u8, params_a, params_b=None):
     for samples not on CLAHE.  Records whose stage-4 image needs the source or the field pass (noise, blur, elastic) are
     refused: ``strong_views`` / ``train_batch`` hand their tables out through ``clahe_tables=``."""
     _lib.require_gpu()
-    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise ValueError(f"clahe_tables: images must be uint8 [N,H,W,3], got {images_u8.dtype} {tuple(images_u8.shape)}")
-    n, h, w, _ = images_u8.shape
+    n, h, w = _check_frames("clahe_tables", images_u8)
     params = [params_a] if params_b is None else [params_a, params_b]
     words = params_a.WORDS if isinstance(params_a, StrongAugParams) else 0
     for p in params:
@@ -580,15 +588,7 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
     four when a record is on CLAHE (the table pass) -- and no host synchronisation; a record with every stage off equals
     ``prepare_batch`` bit for bit.  ``clahe_tables``: as in ``strong_views``, ``[N,8,8,256]``."""
     _lib.require_gpu()
-    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
-        raise ValueError(f"train_batch: images must be uint8 [N,H,W,3], got {getattr(images_u8, 'dtype', type(images_u8))} "
-                         f"{tuple(getattr(images_u8, 'shape', ()))}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("train_batch: dtype must be torch.float32 or torch.bfloat16")
-    n, h, w, _ = images_u8.shape
-    if masks_u8 is not None and (not torch.is_tensor(masks_u8) or masks_u8.dtype != torch.uint8 or tuple(masks_u8.shape) != (n, h, w)):
-        raise ValueError(f"train_batch: masks must be uint8 [{n},{h},{w}], got {getattr(masks_u8, 'dtype', type(masks_u8))} "
-                         f"{tuple(getattr(masks_u8, 'shape', ()))}")
+    n, h, w = _check_frames("train_batch", images_u8, masks_u8, dtype)
     if params is None:
         params = draw_training_params(n, h, w, generator, clahe)
     if not isinstance(params, TrainAugParams):
@@ -598,13 +598,7 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
     source_pass = int(bool((host[:, _W_FLAGS] & (SA_NOISE | SA_BLUR)).any()))
     field_pass = int(bool((params.distortion == DISTORT_ELASTIC).any()))
     wts, radius = _weights_array(elastic_sigma) if field_pass else (None, 0)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    img = images_u8.to(dev, non_blocking=True).contiguous()
-    msk = None if masks_u8 is None else masks_u8.to(dev, non_blocking=True).contiguous()
-    table = host.to(dev, non_blocking=True)
-    cpad = 8 if dtype == torch.bfloat16 else 4
-    out = torch.empty((n, h, w, cpad), device=dev, dtype=dtype)
-    out_m = None if msk is None else torch.empty((n, h, w), device=dev, dtype=torch.int64)
+    dev, img, msk, table, cpad, out, out_m = _device_batch(images_u8, masks_u8, host, n, h, w, dtype)
     mid = torch.empty(n * h * w * 4, device=dev, dtype=torch.float32) if source_pass else None
     field = torch.empty(n * h * w * 2, device=dev, dtype=torch.float32) if field_pass else None
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
@@ -616,8 +610,7 @@ def train_batch(images_u8, masks_u8=None, params=None, generator=None, dtype=tor
     else:
         check(ops.udaseg_train_aug_u8(img, msk, table, n, h, w, mid, field, wts, radius, m255, r255, out, cpad,
                                       int(dtype == torch.bfloat16), out_m, source_pass, field_pass, None), "train_aug_u8")
-    mark_padded_input(out)
-    return out.permute(0, 3, 1, 2)[:, :3], out_m
+    return _model_input(out), out_m
 
 
 class DeviceAugmentedLoader:
