@@ -486,6 +486,40 @@ int udaseg_prepare_batch_u8(const uint8_t* images, const uint8_t* masks, const i
                             const float* mean255, const float* inv_std255, void* out_images, int cpad, int out_bf16,
                             int64_t* out_masks, int square_checked, void* stream);
 
+/* ---- frame ingest (csrc/resize.hip): decoded uint8 frames and label masks of ANY size -> the uint8 batch at the model's size
+ *      that the entry points above take, and the per-mask class statistics.  The reference does this per sample on the host:
+ *      cv2.resize(INTER_AREA) in src/data/target_dataset.py:46-48, Resize(Config.IMAGE_SIZE) in src/models/predict.py:91-98,
+ *      the mask reads of src/data/dataset.py:48-111.  Sizes are (height, width): H x W source, h x w destination.
+ *      n, h <= 65535, H*h and W*w < 2^31. ---- */
+/* Area resize, exact: src [n][H][W][3] -> dst [n][h][w][3], H >= h >= 1 and W >= w >= 1 (an enlargement on either axis is
+ * refused: use udaseg_resize_aa_u8).  Per channel, in integer units: destination row i covers [i*H, (i+1)*H), source row s
+ * covers [s*h, (s+1)*h), wy(i,s) = the length of their overlap (an integer in [0, h]; the weights of one destination row sum
+ * to H); columns alike with W, w, wx.  total = sum_s sum_t wy(i,s) * wx(j,t) * src[s][t];
+ * dst = floor((2*total + H*W) / (2*H*W)): the area-weighted mean, rounded half up.  total reaches 255*H*W (> 2^32 for a
+ * 4000 x 6000 frame): column sums are u32 (255*H < 2^32: H <= 16843009, checked), the horizontal sum and the division u64.
+ * The result does not depend on the order
+ * of summation.  (OpenCV evaluates the same weights in fp32 and rounds to nearest-even: expected within one grey level.) */
+int udaseg_resize_area_u8(const uint8_t* src, int n, int H, int W, int h, int w, uint8_t* dst, void* stream);
+/* Nearest resize for label masks: src [n][H][W] -> dst [n][h][w], dst[i][j] = src[(i*H)/h][(j*W)/w] in integer arithmetic, any
+ * size ratio; values pass through unchanged (255 included).  cv2 INTER_NEAREST / torch mode="nearest". */
+int udaseg_resize_nearest_u8(const uint8_t* src, int n, int H, int W, int h, int w, uint8_t* dst, void* stream);
+/* Mask histogram: masks [n][pixels] -> hist[k][v] += the number of pixels of mask k equal to v (int64 [n][256] counters that
+ * ACCUMULATE across calls; the caller zeroes them once, as for udaseg_score_hist).  pixels < 2^32. */
+int udaseg_mask_hist_u8(const uint8_t* masks, int n, int64_t pixels, int64_t* hist, void* stream);
+/* Antialiased bilinear resize fused with A.Normalize: src [n][H][W][3] -> out [n][h][w][cpad] (fp32, or bf16 when out_bf16,
+ * rounded once from the fp32 value; padding lanes 0), any size ratio.  Each axis has a DEVICE table built by the caller:
+ * destination index i reads the `taps` source indices start[i] .. start[i] + taps - 1 (those outside the source are skipped)
+ * with the fp32 weights w[i][0..taps).  The tables of torch.nn.functional.interpolate(mode="bilinear", antialias=True,
+ * align_corners=False) for L -> l: scale = L/l, support = max(scale, 1), c = scale*(i + 0.5), lo = max(0, int(c - support + 0.5)),
+ * hi = min(L, int(c + support + 0.5)), weight_j = max(0, 1 - |(j - c + 0.5) / support|) for j in [lo, hi) divided by their sum,
+ * in float64, rounded to fp32 (at equal size the weights are (1, 0); an enlargement is plain bilinear).
+ * v = sum_s y_w[i][s] * sum_t x_w[j][t] * src, accumulated in fp32 on the 0..255 scale (rows first), then
+ * out = (v - mean255[c]) * inv_std255[c] with HOST arrays of 3 floats: the arithmetic of udaseg_prepare_batch_u8.  Normalising
+ * after resampling equals the reference's normalise-then-resize up to rounding, since the weights of a pixel sum to 1. */
+int udaseg_resize_aa_u8(const uint8_t* src, int n, int H, int W, int h, int w, const int32_t* y_start, const float* y_w, int y_taps,
+                        const int32_t* x_start, const float* x_w, int x_taps, const float* mean255, const float* inv_std255,
+                        void* out, int cpad, int out_bf16, void* stream);
+
 /* ---- scratch: one caller-owned device buffer PER DEVICE the library may use for split partial results (currently the
  *      small-channel weight gradient, <= 10 MiB); the call binds it to the device that is current when it is made.
  *      Without it those calls take the generic atomics path. ---- */

@@ -97,6 +97,10 @@ SIGNATURES = {
     "udaseg_bce_logits_target_bwd": (_I, [_P, _P, _I, _F, _P, _P, _I, _P]),
     "udaseg_scale_f32": (_I, [_P, _P, _L, _F, _P]),
     "udaseg_prepare_batch_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _P]),
+    "udaseg_resize_area_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_resize_nearest_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_mask_hist_u8": (_I, [_P, _I, _L, _P, _P]),
+    "udaseg_resize_aa_u8": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
     "udaseg_predict_gather_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     "udaseg_predict_blend": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "udaseg_predict_finish": (_I, [_P, _P, _L, _I, _I, _P, _P]),

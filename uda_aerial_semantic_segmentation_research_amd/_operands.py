@@ -201,6 +201,14 @@ OPERANDS = {
                                   I("radius"), H("mean255"), H("inv_std255"),
                                   T("out_images", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"), I("cpad"), I("out_bf16"),
                                   T("out_masks", i64, "n*h*w", True), I("source_pass"), I("field_pass"), T("lut", u8, "n*16384"), S],
+    # ---- frame ingest (H x W source, h x w destination)
+    "udaseg_resize_area_u8": [T("src", u8, "n*H*W*3"), I("n"), I("H"), I("W"), I("h"), I("w"), T("dst", u8, "n*h*w*3"), S],
+    "udaseg_resize_nearest_u8": [T("src", u8, "n*H*W"), I("n"), I("H"), I("W"), I("h"), I("w"), T("dst", u8, "n*h*w"), S],
+    "udaseg_mask_hist_u8": [T("masks", u8, "n*pixels"), I("n"), I("pixels"), T("hist", i64, "n*256"), S],
+    "udaseg_resize_aa_u8": [T("src", u8, "n*H*W*3"), I("n"), I("H"), I("W"), I("h"), I("w"), T("y_start", i32, "h"),
+                            T("y_w", f32, "h*y_taps"), I("y_taps"), T("x_start", i32, "w"), T("x_w", f32, "w*x_taps"), I("x_taps"),
+                            H("mean255"), H("inv_std255"), T("out", "(bf16 if out_bf16 else f32)", "n*h*w*cpad"), I("cpad"),
+                            I("out_bf16"), S],
     # ---- prediction (popcount(views) = V, the views per tile)
     "udaseg_predict_gather_u8": [T("image", u8, "h*w*3"), I("h"), I("w"), I("th"), I("tw"), I("rows"), I("cols"), I("sy"), I("sx"),
                                  I("first"), I("tiles"), I("views"), H("mean255"), H("inv_std255"),

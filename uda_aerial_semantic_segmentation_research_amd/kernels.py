@@ -889,3 +889,31 @@ def predict_finish(probs, wsum, pixels, classes, ldc, labels, st=None):
 
 def predict_threshold(logits, n, hw, classes, ldc, out, st=None):
     check(ops.udaseg_predict_threshold(logits, n, hw, classes, ldc, out, st), "predict_threshold")
+
+
+# ---- frame ingest (ingest.py; csrc/resize.hip).  Sizes are (height, width)
+def resize_area_u8(src, dst, st=None):
+    """uint8 [n,H,W,3] -> uint8 [n,h,w,3] (dst's size), exact area filter; shrinking only."""
+    n, H, W, _ = src.shape
+    check(ops.udaseg_resize_area_u8(src, n, H, W, dst.shape[1], dst.shape[2], dst, st), "resize_area_u8")
+
+
+def resize_nearest_u8(src, dst, st=None):
+    """uint8 [n,H,W] -> uint8 [n,h,w] (dst's size), dst[i][j] = src[(i*H)//h][(j*W)//w]."""
+    n, H, W = src.shape
+    check(ops.udaseg_resize_nearest_u8(src, n, H, W, dst.shape[1], dst.shape[2], dst, st), "resize_nearest_u8")
+
+
+def mask_hist_u8(masks, hist, st=None):
+    """uint8 [n, ...] masks -> hist int64 [n,256] += per-mask counts of every byte value (accumulates)."""
+    n = masks.shape[0]
+    check(ops.udaseg_mask_hist_u8(masks, n, masks.numel() // n, hist, st), "mask_hist_u8")
+
+
+def resize_aa_u8(src, y_table, x_table, mean255, inv_std255, out, st=None):
+    """uint8 [n,H,W,3] -> out [n,h,w,cpad] (fp32 or bf16 by out's dtype): antialiased bilinear + A.Normalize.  A table is
+    (start int32 [l], weights fp32 [l,taps]) on the device."""
+    n, H, W, _ = src.shape
+    (ys, yw), (xs, xw) = y_table, x_table
+    check(ops.udaseg_resize_aa_u8(src, n, H, W, out.shape[1], out.shape[2], ys, yw, yw.shape[1], xs, xw, xw.shape[1], mean255,
+                                  inv_std255, out, out.shape[-1], int(out.dtype == torch.bfloat16), st), "resize_aa_u8")

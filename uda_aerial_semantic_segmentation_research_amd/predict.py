@@ -137,15 +137,19 @@ def predict_batch(model, images, device="cuda"):
         return labels.cpu().numpy()
 
 
-def predict_mask(model, img, device=None):
+def predict_mask(model, img, device=None, resize=False):
     """Reference ``predict.py:70-111``, quirk included: ``(sigmoid(logits) > 0.5)`` as float 0/1, ``.squeeze()``d, as numpy
     (``[C,H,W]`` for one image) -- multi-class thresholding, not an argmax.
 
-    * A tensor (``[3,H,W]`` or ``[1,3,H,W]``, normalised) is used as is, as the reference's tensor branch does.
+    * A tensor (``[3,H,W]`` or ``[1,3,H,W]``, normalised) is used as is, as the reference's tensor branch does; ``resize``
+      does not apply to it (``ingest.resize_normalized`` makes such a tensor from a uint8 frame).
     * A numpy uint8 ``[H,W,3]`` RGB image (or a PIL image) is normalised by ``data.prepare_batch``: ``A.Normalize``'s fp32
       ``(x - 255*mean) * (1 / (255*std))``, where the reference's ``ToTensor`` + ``Normalize`` computes
       ``(x / 255 - mean) / std`` -- the same up to one fp32 rounding.  The reference then resizes to ``Config.IMAGE_SIZE``;
-      that is the identity only at that size, so any other size raises ``ValueError`` (use ``predict_large``).
+      that is the identity only at that size, so any other size raises ``ValueError`` (use ``predict_large``) -- unless
+      ``resize=True``: then a frame of any size goes through ``ingest.resize_normalized`` (antialiased bilinear + the same
+      ``A.Normalize``, csrc/resize.hip) to ``Config.IMAGE_SIZE`` on the model's device, and the result stays at the model's size,
+      as the reference's does.
     The threshold is one HIP kernel writing the NCHW float output."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if dev.type != "cuda":
@@ -162,12 +166,16 @@ def predict_mask(model, img, device=None):
     if isinstance(img, np.ndarray):
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
             raise ValueError(f"predict_mask: numpy images must be uint8 [H,W,3] RGB, got {img.dtype} {img.shape}")
-        if tuple(img.shape[:2]) != tuple(Config.IMAGE_SIZE):
+        if resize:
+            from .ingest import frame_for_model
+            x = frame_for_model(model, img)
+        elif tuple(img.shape[:2]) != tuple(Config.IMAGE_SIZE):
             raise ValueError(f"predict_mask: image is {img.shape[0]}x{img.shape[1]}, the model size is "
                              f"{Config.IMAGE_SIZE[0]}x{Config.IMAGE_SIZE[1]}; the reference's Resize is not reproduced here -- "
                              f"use predict_large for frames of other sizes")
-        x, _ = prepare_batch(torch.from_numpy(np.ascontiguousarray(img))[None], dtype=getattr(model, "compute_dtype",
-                                                                                              torch.float32))
+        else:
+            x, _ = prepare_batch(torch.from_numpy(np.ascontiguousarray(img))[None], dtype=getattr(model, "compute_dtype",
+                                                                                                  torch.float32))
     elif torch.is_tensor(img):
         x = (img.unsqueeze(0) if img.dim() == 3 else img).to(dev)
     else:
