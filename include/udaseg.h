@@ -181,6 +181,11 @@ double udaseg_conv_flops(const udaseg_conv_desc* d);
 /* x[n][c][h][w] -> y[n][h][w][cpad], channels c..cpad-1 zero-filled */
 int udaseg_nchw_to_nhwc(const float* x, float* y, int n, int c, int h, int w, int cpad, void* stream);
 
+/* most channels the BatchNorm kernels take (they keep per-channel coefficients in LDS, 64 KB at most for the bf16 backward) */
+#define UDASEG_BN_MAX_C 4096                    /* every fp32 entry point; bf16 statistics, apply, reduce, channel_sum */
+#define UDASEG_BN_BWD_APPLY_BF16_MAX_C 3272     /* udaseg_bn_bwd_apply_bf16: 20 bytes of LDS per channel */
+#define UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C 2336 /* udaseg_bn_bwd_apply_recompute_bf16: 28 bytes of LDS per channel */
+
 /* ---- batch norm (training mode) + activation: torch.nn.BatchNorm2d/ReLU/LeakyReLU inside smp.Unet and
  *      discriminator.py:21-33.  sums / bsums = [R][2][c] doubles (R = udaseg_bn_replicas() replicated accumulators of
  *      sum and sum of squares, spread to avoid same-address atomic serialisation), zeroed by the caller. ---- */
@@ -387,8 +392,9 @@ int udaseg_bce_logits_target_bwd(const float* x, const float* target, int n, flo
                                  int accumulate, void* stream);
 
 /* ---- Adam: torch.optim.Adam(...).step() at train.py:344,461; adversarial_trainer.py:56-59,98,114 ----
- * flat fp32 arrays; bc1 = 1-beta1^t, bc2 = 1-beta2^t computed by the caller. */
-int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1, float beta2,
+ * flat fp32 arrays; bc1 = 1-beta1^t, bc2 = 1-beta2^t computed by the caller.  beta1 / beta2 are doubles: the kernel multiplies by
+ * 1-beta1 and 1-beta2, which are formed in double and rounded to fp32 once (formed from fp32 betas they are off by up to 1.3e-5). */
+int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count, float lr, double beta1, double beta2,
                      float eps, float bc1, float bc2, void* stream);
 
 /* ---- global-norm gradient clipping: torch.nn.utils.clip_grad_norm_(params, max_norm) at src/models/unsupervised_trainer.py:144,

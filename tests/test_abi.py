@@ -148,7 +148,7 @@ def test_every_entry_point_checks_its_operands_before_the_library_is_called():
     import torch
     from uda_aerial_semantic_segmentation_research_amd import _lib, _operands as O
     kinds = {"desc": (_lib._D,), "stream": (ctypes.c_void_p,), "tensor": (ctypes.c_void_p,),
-             "int": (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t), "float": (ctypes.c_float,)}
+             "int": (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t), "float": (ctypes.c_float, ctypes.c_double)}
     assert sorted(O.OPERANDS) == sorted(_lib.SIGNATURES)
     other = {torch.float32: torch.bfloat16, torch.bfloat16: torch.float32, torch.float64: torch.float32, torch.int64: torch.int32,
              torch.int32: torch.int64, torch.uint8: torch.int32}

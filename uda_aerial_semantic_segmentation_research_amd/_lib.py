@@ -118,7 +118,7 @@ SIGNATURES = {
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "udaseg_bce_logits_fwd": (_I, [_P, _I, _F, _F, _P, _I, _P]),
     "udaseg_bce_logits_bwd": (_I, [_P, _I, _F, _F, _P, _P, _I, _P]),
-    "udaseg_adam_flat": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),
+    "udaseg_adam_flat": (_I, [_P, _P, _P, _P, _L, _F, C.c_double, C.c_double, _F, _F, _F, _P]),
     "udaseg_sumsq_f32": (_I, [_P, _L, _P, _P, _I, _P]),
     "udaseg_scale_by_clip_f32": (_I, [_P, _L, _P, _F, _F, _P]),
     "udaseg_strong_aug_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),

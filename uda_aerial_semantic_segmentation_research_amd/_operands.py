@@ -35,7 +35,7 @@ def I(name):             # int / int64_t / size_t scalar
     return ("int", name)
 
 
-def F(name):             # float scalar
+def F(name):             # float / double scalar
     return ("float", name)
 
 

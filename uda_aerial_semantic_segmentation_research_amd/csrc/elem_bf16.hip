@@ -57,10 +57,10 @@ __global__ void bn_apply_bf16_kernel(const f32x4* __restrict__ y, const double* 
       if (save_mean) save_mean[c] = (float)m;
       if (save_rstd) save_rstd[c] = rstd;
       if (running_mean) {
-        const float v = (float)var;
-        const float unb = pixels > 1 ? v * ((float)pixels / (float)(pixels - 1)) : v;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * unb;
+        // in f64 and rounded once: the fp32 form rounded six times and could land 2.3 ulp off (tests/test_gpu_norm_grade.py)
+        const double unb = pixels > 1 ? var * ((double)pixels / (double)(pixels - 1)) : var, mo = (double)momentum;
+        running_mean[c] = (float)((1.0 - mo) * (double)running_mean[c] + mo * m);
+        running_var[c] = (float)((1.0 - mo) * (double)running_var[c] + mo * unb);
       }
     }
   }
@@ -284,10 +284,10 @@ __global__ void bn_finalize_kernel(const double* __restrict__ sums, const float*
     if (save_mean) save_mean[c] = (float)m;
     if (save_rstd) save_rstd[c] = rstd;
     if (running_mean) {
-      const float v = (float)var;
-      const float unb = pixels > 1 ? v * ((float)pixels / (float)(pixels - 1)) : v;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * unb;
+      // in f64 and rounded once: the fp32 form rounded six times and could land 2.3 ulp off (tests/test_gpu_norm_grade.py)
+      const double unb = pixels > 1 ? var * ((double)pixels / (double)(pixels - 1)) : var, mo = (double)momentum;
+      running_mean[c] = (float)((1.0 - mo) * (double)running_mean[c] + mo * m);
+      running_var[c] = (float)((1.0 - mo) * (double)running_var[c] + mo * unb);
     }
   }
 }
@@ -547,8 +547,9 @@ static inline int grid_for8(int64_t items, int per_thread = 2) {
 }
 
 static int check_pc8(int64_t pixels, int c, const char* who) {
-  UDASEG_CHECK_ARG(pixels > 0 && c > 0 && c % 8 == 0 && c <= 4096, "%s: need pixels > 0 and channels a positive multiple of 8, <= 4096 (got %lld, %d)",
-                   who, (long long)pixels, c);
+  UDASEG_CHECK_ARG(pixels > 0 && c > 0 && c % 8 == 0, "%s: need pixels > 0 and channels a positive multiple of 8 (got %lld, %d)", who,
+                   (long long)pixels, c);
+  UDASEG_CHECK_ARG(c <= UDASEG_BN_MAX_C, "%s: too many channels (%d, at most %d)", who, c, UDASEG_BN_MAX_C);
   return UDASEG_OK;
 }
 
@@ -611,7 +612,10 @@ extern "C" int udaseg_bn_bwd_apply_bf16(const void* dz, const void* z, const voi
   if (rc) return rc;
   UDASEG_CHECK_ARG(dz && y && save_mean && save_rstd && gamma && bsums && dy && (act == UDASEG_ACT_NONE || z),
                    "bn_bwd_apply_bf16: NULL pointer");
-  UDASEG_CHECK_ARG((size_t)5 * c * sizeof(float) <= 65536, "bn_bwd_apply_bf16: too many channels");
+  static_assert((size_t)5 * UDASEG_BN_BWD_APPLY_BF16_MAX_C * sizeof(float) <= 65536 &&
+                (size_t)5 * (UDASEG_BN_BWD_APPLY_BF16_MAX_C + 8) * sizeof(float) > 65536, "the documented maximum is the 64 KB of coefficients");
+  UDASEG_CHECK_ARG(c <= UDASEG_BN_BWD_APPLY_BF16_MAX_C, "bn_bwd_apply_bf16: too many channels (%d, at most %d)", c,
+                   UDASEG_BN_BWD_APPLY_BF16_MAX_C);
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, 2048, apply_per_thread());
   static std::atomic<int> kid_bwa{-1};
@@ -632,7 +636,10 @@ extern "C" int udaseg_bn_bwd_apply_recompute_bf16(const void* dz, const void* y,
   if (rc) return rc;
   UDASEG_CHECK_ARG(dz && y && fwd_scale && fwd_shift && save_mean && save_rstd && gamma && bsums && dy,
                    "bn_bwd_apply_recompute_bf16: NULL pointer");
-  UDASEG_CHECK_ARG((size_t)7 * c * sizeof(float) <= 65536, "bn_bwd_apply_recompute_bf16: too many channels");
+  static_assert((size_t)7 * UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C * sizeof(float) <= 65536 &&
+                (size_t)7 * (UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C + 8) * sizeof(float) > 65536, "the documented maximum is the 64 KB of coefficients");
+  UDASEG_CHECK_ARG(c <= UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C, "bn_bwd_apply_recompute_bf16: too many channels (%d, at most %d)", c,
+                   UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C);
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, 2048, apply_per_thread());
   static std::atomic<int> kid_bwr{-1};

@@ -42,7 +42,6 @@ __global__ void bn_stats_kernel(const f32x4* __restrict__ y, int64_t n4, int c4,
   block_fold_add(ss, rep + (size_t)c4 * 4, c4, q, red);
 }
 
-constexpr int MAX_C4 = 1024;  // channels <= 4096
 
 // Per-channel-quad coefficients are computed ONCE per block (threads q < c4, strided) into LDS; every thread then picks
 // the quad it streams.  (Summing the 16 replicas in every thread cost more than the streaming itself on small tensors.)
@@ -75,10 +74,10 @@ __global__ void bn_apply_kernel(const f32x4* __restrict__ y, const double* __res
         if (save_mean) save_mean[c] = (float)m;
         if (save_rstd) save_rstd[c] = rstd;
         if (running_mean) {
-          const float v = (float)var;
-          const float unb = pixels > 1 ? v * ((float)pixels / (float)(pixels - 1)) : v;
-          running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-          running_var[c] = (1.f - momentum) * running_var[c] + momentum * unb;
+          // in f64 and rounded once: the fp32 form rounded six times and could land 2.3 ulp off (tests/test_gpu_norm_grade.py)
+          const double unb = pixels > 1 ? var * ((double)pixels / (double)(pixels - 1)) : var, mo = (double)momentum;
+          running_mean[c] = (float)((1.0 - mo) * (double)running_mean[c] + mo * m);
+          running_var[c] = (float)((1.0 - mo) * (double)running_var[c] + mo * unb);
         }
       }
     }
@@ -326,7 +325,7 @@ __global__ void bn_fold_kernel(const float* __restrict__ w, const float* __restr
 static int check_pc(int64_t pixels, int c, const char* who) {
   UDASEG_CHECK_ARG(pixels > 0 && c > 0 && c % 4 == 0, "%s: need pixels > 0 and channels a positive multiple of 4 (got %lld, %d)",
                    who, (long long)pixels, c);
-  UDASEG_CHECK_ARG(c <= 4096, "%s: channels > 4096 unsupported", who);
+  UDASEG_CHECK_ARG(c <= UDASEG_BN_MAX_C, "%s: too many channels (%d, at most %d)", who, c, UDASEG_BN_MAX_C);
   return UDASEG_OK;
 }
 

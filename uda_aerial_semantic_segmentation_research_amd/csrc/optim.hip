@@ -4,21 +4,23 @@
 // src/models/adversarial_trainer.py:56-59,98,114): lr from the caller, betas (0.9, 0.999), eps 1e-8,
 // no weight decay, no amsgrad.  Arithmetic order follows torch's single-tensor Adam:
 //   m = m + (g - m)*(1-b1);  v = v*b2 + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// The betas arrive as doubles and 1-b1, 1-b2 are formed in double and rounded once, as torch forms them: 1.f - 0.999f is
+// 0.00099998713, 1.3e-5 off 0.001, and v carried that error (tests/test_gpu_norm_grade.py).
 #include "common.h"
 
 namespace udaseg {
 
 __global__ void adam_flat_kernel(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m,
                                  f32x4* __restrict__ v, int64_t n4, float* __restrict__ ptail, const float* __restrict__ gtail,
-                                 float* __restrict__ mtail, float* __restrict__ vtail, int tail, float step_size, float beta1,
-                                 float beta2, float eps, float inv_sqrt_bc2) {
+                                 float* __restrict__ mtail, float* __restrict__ vtail, int tail, float step_size, float omb1,
+                                 float beta2, float omb2, float eps, float inv_sqrt_bc2) {
   const int64_t T = (int64_t)gridDim.x * blockDim.x;
   const int64_t g0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int64_t i = g0; i < n4; i += T) {
     const f32x4 gg = g[i];
     f32x4 mm = m[i], vv = v[i], pp = p[i];
-    mm = mm + (gg - mm) * (1.f - beta1);
-    vv = vv * beta2 + gg * gg * (1.f - beta2);
+    mm = mm + (gg - mm) * omb1;
+    vv = vv * beta2 + gg * gg * omb2;
     f32x4 upd;
 #pragma unroll
     for (int e = 0; e < 4; ++e) upd[e] = mm[e] / (sqrtf(vv[e]) * inv_sqrt_bc2 + eps);
@@ -30,8 +32,8 @@ __global__ void adam_flat_kernel(f32x4* __restrict__ p, const f32x4* __restrict_
   if (g0 < tail) {
     const float gg = gtail[g0];
     float mm = mtail[g0], vv = vtail[g0];
-    mm = mm + (gg - mm) * (1.f - beta1);
-    vv = vv * beta2 + gg * gg * (1.f - beta2);
+    mm = mm + (gg - mm) * omb1;
+    vv = vv * beta2 + gg * gg * omb2;
     ptail[g0] -= step_size * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
     mtail[g0] = mm;
     vtail[g0] = vv;
@@ -130,8 +132,8 @@ extern "C" int udaseg_scale_by_clip_f32(float* g, int64_t count, const double* s
   return UDASEG_OK;
 }
 
-extern "C" int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count, float lr, float beta1,
-                                float beta2, float eps, float bc1, float bc2, void* stream) {
+extern "C" int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count, float lr, double beta1,
+                                double beta2, float eps, float bc1, float bc2, void* stream) {
   UDASEG_CHECK_ARG(p && g && m && v && count > 0, "adam_flat: bad arguments");
   UDASEG_CHECK_ARG(bc1 > 0.f && bc2 > 0.f, "adam_flat: bias corrections must be positive");
   UDASEG_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_flat: pointers must be 16-byte aligned");
@@ -141,8 +143,8 @@ extern "C" int udaseg_adam_flat(float* p, const float* g, float* m, float* v, in
   if (want > 2048) want = 2048;
   if (want < 1) want = 1;
   hipLaunchKernelGGL(adam_flat_kernel, dim3((int)want), dim3(256), 0, as_stream(stream), (f32x4*)p, (const f32x4*)g, (f32x4*)m,
-                     (f32x4*)v, n4, p + n4 * 4, g + n4 * 4, m + n4 * 4, v + n4 * 4, tail, lr / bc1, beta1, beta2, eps,
-                     1.0f / sqrtf(bc2));
+                     (f32x4*)v, n4, p + n4 * 4, g + n4 * 4, m + n4 * 4, v + n4 * 4, tail, lr / bc1, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), eps, 1.0f / sqrtf(bc2));
   UDASEG_LAUNCH_CHECK("adam_flat launch");
   return UDASEG_OK;
 }
