@@ -74,7 +74,9 @@ int udaseg_version(void);
 #define UDASEG_OPT_HALO_S2_CK 30            /* UDASEG_HALO_S2_CK: channels per staged chunk of the 4x4 / stride 2 halo form: 32 | 64 */
 #define UDASEG_OPT_UP_CFG 31                /* UDASEG_UP_CFG: conv_up_f32x3.hip: one tile configuration 1..8 for every launch (udaseg_up_f32x3_force_config) */
 #define UDASEG_OPT_WGRAD_UP_BLOCKS 32       /* UDASEG_WGRAD_UP_BLOCKS: blocks of a conv_wgrad_up_kernel launch (0: 96; udaseg_wgrad_up_set_blocks) */
-#define UDASEG_OPT_COUNT 33
+#define UDASEG_OPT_WGRAD_PAIR 33            /* UDASEG_WGRAD_PAIR: fp32 weight gradients of 16-channel inputs on the pair-packed halo kernel: bit 0 the 16 -> 16 layers, bit 1 those of 24 / 32 produced channels, bit 2 the up-sampled 32 -> 16 layer without a skip half; 0: all on conv3x3_small_wgrad_kernel */
+#define UDASEG_OPT_WGRAD_PAIR_BLOCKS 34     /* UDASEG_WGRAD_PAIR_BLOCKS: blocks of a pair-packed halo weight-gradient launch (0: 120) */
+#define UDASEG_OPT_COUNT 35
 int udaseg_set_option(int key, int value);
 int udaseg_get_option(int key);
 int udaseg_option_count(void);
@@ -693,7 +695,10 @@ int udaseg_conv2d_dgrad_f32x3(const udaseg_conv_desc* d, const float* dy, const 
  * blocks: 64 x 64, 32 produced x 64 gathered, 32 x 32 (co % 32 == 0 and ci % 32 == 0); images at least 32 pixels wide, or 16-pixel-
  * wide ones with 64-multiples (8 x 16 tiles).  Reference: loss.backward(), src/models/train.py:343.
  * up_ca > 0: x is the half-resolution tensor of a fused decoder input, skip the other source (up_ca a multiple of the gathered
- * channel block). */
+ * channel block).
+ * Pair-packed forms (UDASEG_OPT_WGRAD_PAIR): ci == 16 with co in {8, 16, 24, 32} and an even width >= 16 (two pixels of a
+ * 16-channel tensor fill the 32 rows of an MFMA operand), and the one geometry with up_ca == ci: 32 up-sampled -> 16 produced
+ * channels without a skip half (skip == NULL). */
 int udaseg_conv2d_wgrad_halo_f32x3_ok(const udaseg_conv_desc* d, int up_ca);
 int udaseg_conv2d_wgrad_halo_f32x3(const udaseg_conv_desc* d, const float* x, const float* skip, int up_ca, const float* dy,
                                    float* dw, void* stream);

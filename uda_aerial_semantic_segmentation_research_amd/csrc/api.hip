@@ -284,7 +284,9 @@ static const OptRow g_opt_rows[UDASEG_OPT_COUNT] = {
     /* 29 HALO_DEEP */ {"UDASEG_HALO_DEEP", K_OFF0, 1},
     /* 30 HALO_S2_CK */ {"UDASEG_HALO_S2_CK", K_INT, 64},
     /* 31 UP_CFG */ {"UDASEG_UP_CFG", K_INT, 0},
-    /* 32 WGRAD_UP_BLOCKS */ {"UDASEG_WGRAD_UP_BLOCKS", K_INT, 0}};
+    /* 32 WGRAD_UP_BLOCKS */ {"UDASEG_WGRAD_UP_BLOCKS", K_INT, 0},
+    /* 33 WGRAD_PAIR */ {"UDASEG_WGRAD_PAIR", K_INT, 4},
+    /* 34 WGRAD_PAIR_BLOCKS */ {"UDASEG_WGRAD_PAIR_BLOCKS", K_INT, 0}};
 int g_opt_val[UDASEG_OPT_COUNT];
 static int g_opt_default[UDASEG_OPT_COUNT];
 std::atomic<bool> g_opt_ready{false};

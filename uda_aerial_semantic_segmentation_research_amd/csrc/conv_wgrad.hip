@@ -1102,7 +1102,9 @@ extern "C" int udaseg_conv2d_wgrad_bnin(const udaseg_conv_desc* d, const float* 
     return UDASEG_E_UNSUPPORTED;
   }
   hipStream_t st = as_stream(stream);
-  const bool small = small_wgrad_applicable(d->kh, d->stride, d->pad, d->ci, d->co, d->n * cdiv(d->hi, 16) * cdiv(d->wi, 16));
+  // 16 gathered channels, plain source: the pair-packed halo kernel where UDASEG_OPT_WGRAD_PAIR gives it the layer
+  const bool pair = !up && d->ci <= 16 && !wgrad_halo_off(true) && wgrad_h2_applicable(d, 0, true);
+  const bool small = !pair && small_wgrad_applicable(d->kh, d->stride, d->pad, d->ci, d->co, d->n * cdiv(d->hi, 16) * cdiv(d->wi, 16));
   if (!small && !accumulate) {          // before prof_begin: an early return must not leave the family's timing record open
     hipError_t e = hipMemsetAsync(dw, 0, (size_t)d->co * 9 * d->ci * sizeof(float), st);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(dw)");
@@ -1146,7 +1148,8 @@ extern "C" int udaseg_conv2d_wgrad_halo_f32x3(const udaseg_conv_desc* d, const f
                                               float* dw, void* stream) {
   UDASEG_CHECK_ARG(d && x && dy && dw, "conv2d_wgrad_halo_f32x3: NULL pointer");
   UDASEG_CHECK_ARG(d->n > 0 && d->hi > 0 && d->wi > 0 && d->ho == d->hi && d->wo == d->wi, "conv2d_wgrad_halo_f32x3: bad extents");
-  UDASEG_CHECK_ARG((up_ca > 0) == (skip != nullptr), "conv2d_wgrad_halo_f32x3: up_ca=%d, skip %s", up_ca, skip ? "given" : "NULL");
+  // (up_ca == ci: every gathered channel is up-sampled -- a decoder block without a skip half)
+  UDASEG_CHECK_ARG((up_ca > 0 && up_ca < d->ci) == (skip != nullptr), "conv2d_wgrad_halo_f32x3: up_ca=%d, skip %s", up_ca, skip ? "given" : "NULL");
   if (!udaseg_conv2d_wgrad_halo_f32x3_ok(d, up_ca)) {
     set_error("conv2d_wgrad_halo_f32x3: geometry not supported (ask udaseg_conv2d_wgrad_halo_f32x3_ok first)");
     return UDASEG_E_UNSUPPORTED;

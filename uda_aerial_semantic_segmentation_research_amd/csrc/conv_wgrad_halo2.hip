@@ -351,15 +351,446 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_h2_kernel(const WgradH2Args
   else wgrad_h2_role<C, 2, 1, true, TL, XF>(a, h2smem, tid, lane, wave);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Pair-packed form for 16-channel tensors (the full-resolution decoder tail: block-5 conv2 16 -> 16, the head 16 -> 24).  A
+// 16-channel NHWC row of W pixels is, byte for byte, a 32-channel row of W / 2 pixel PAIRS, so the 32 x 32 x 16 MFMA of the kernel
+// above runs on it with k = one pair:
+//     A[m][k] = dy[2k + (m >= 16)][m % 16]        B[k][n] = x[2k + s + (n >= 16)][n % 16]         (s: the group's shift in pixels)
+// and the four 16 x 16 blocks of the accumulator are  (m<16, n<16): tap s over the even pixels,  (m>=16, n>=16): tap s over the odd
+// pixels,  (m<16, n>=16): tap s + 1 over the even pixels,  (m>=16, n<16): tap s - 1 over the odd pixels.  Two shift groups give the
+// three kernel columns: s = -1 holds column 0 (both diagonal blocks) and the even half of column 1, s = +1 column 2 and the odd half
+// of column 1; the (m>=16, n<16) block of s = -1 and the (m<16, n>=16) block of s = +1 are the offsets -2 / +2 and are dropped in the
+// epilogue.  36 MFMAs per 32 pixels, 75 % of them useful (plain channel padding to 32 x 32: 25 %).
+// LDS planes are linear pixel arrays of 32 bytes (16 bf16) per pixel: halo pixel hx of a row is image column x0 + hx - 1, so group
+// s = -1 reads its 64-byte pair rows from byte 0 of the row and s = +1 from byte 64 -- every transposed read still covers 256
+// contiguous bytes.  Zero padding comes from the halo's range-checked loads, ragged tiles from dy's: no edge fix-up.
+// Waves: group = wave & 1, the other four split the tile's K (the two 32-pixel halves of a 64-pixel row x two row ranges); all
+// eight stage (register-staged, two LDS buffers, one barrier per tile) and all eight run MFMAs.  Blocks of 16 produced channels:
+// a layer with 24 has two, the second half empty (its dy pieces load as zero, its dW rows are never written).
+template <int TR_, int TWK_>
+struct H2P {
+  static constexpr int PL = 3, TR = TR_, TWK = TWK_;               // TWK: 16-pair (32-pixel) K steps per tile row
+  static constexpr bool UP = false;
+  static constexpr int NT = 512;
+  static constexpr int TW = 32 * TWK, HR = TR + 2, HWD = TW + 2, HP = HR * HWD, TP = TR * TW;
+  static constexpr int KS = 4;                                     // waves per shift group
+  static constexpr int KSH = KS < TWK ? KS : TWK, KSR = KS / KSH;
+  static constexpr int RW = TR / KSR, NHF = TWK / KSH;
+  static constexpr int XPLANE = HP * 32, DPLANE = TP * 32;         // bytes per split plane
+  static constexpr int BUF = PL * (XPLANE + DPLANE);
+  static constexpr int LDS = 2 * BUF;
+  static constexpr int XPC = HP * 2, DPC = TP * 2;                 // 8-channel pieces
+  static constexpr int NX = (XPC + NT - 1) / NT, ND = (DPC + NT - 1) / NT;
+  static_assert(TR % KSR == 0 && TWK % KSH == 0 && KSH * KSR == KS, "K split tiles the tile");
+  static_assert(LDS <= 160 * 1024 && 6 * 24 * 64 * 4 <= LDS, "LDS");
+};
+
+template <typename C, bool XF>
+__device__ __forceinline__ void wgrad_h2p_role(const WgradH2Args& a, char* smem, int tid, int lane, int wave) {
+  constexpr int PL = 3;
+  char* const Xs = smem;
+  char* const Ds = smem + PL * C::XPLANE;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int grp = lane >> 4, cb = 16 * (grp & 1), hk = grp >> 1, tq = (lane & 15) >> 2, tp = lane & 3;
+  const int sg = wave & 1, ks = wave >> 1;                          // shift group (0: s = -1, 1: s = +1), K share
+  const int ksh = ks % C::KSH, r0 = (ks / C::KSH) * C::RW;
+  const int cob = (int)blockIdx.x % a.pairs, split = (int)blockIdx.x / a.pairs;
+  const int H = a.h, W = a.w;
+  __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), 0, (int)a.dy_bytes, 0x00020000);
+  u32x4 sx[C::NX][2], sd[C::ND][2];
+  // in-staging transform of x: a thread's channel octet is the same for every piece it owns (NT is even)
+  unsigned x_in = 0;
+  f32x4 xsc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, xsh[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if constexpr (XF) {
+    const int ch = (tid & 1) * 8;
+    xsc[0] = *reinterpret_cast<const f32x4*>(a.in_scale + ch);
+    xsc[1] = *reinterpret_cast<const f32x4*>(a.in_scale + ch + 4);
+    xsh[0] = *reinterpret_cast<const f32x4*>(a.in_shift + ch);
+    xsh[1] = *reinterpret_cast<const f32x4*>(a.in_shift + ch + 4);
+  }
+  const int dch = cob * 16 + (tid & 1) * 8;                         // this thread's dy channel octet; >= co: the empty half of a block
+  auto load_tile = [&](int tile) {
+    x_in = 0;
+    const int tx = tile % a.ntx;
+    const int t2 = tile / a.ntx;
+    const int ty = t2 % a.nty, img = t2 / a.nty;
+    const int y0 = ty * C::TR, x0 = tx * C::TW;
+#pragma unroll
+    for (int i = 0; i < C::NX; ++i) {
+      const int pc = tid + i * C::NT;
+      const int pix = pc >> 1, oct = pc & 1;
+      const int hy = pix / C::HWD, hx = pix - hy * C::HWD;
+      const int iy = y0 + hy - 1, ix = x0 + hx - 1;
+      const bool ok = pc < C::XPC && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+      const unsigned off = ok ? (unsigned)((((img * H + iy) * W + ix) * 16 + oct * 8) * 4) : 0x80000000u;
+      if constexpr (XF) x_in |= (ok ? 1u : 0u) << i;
+#pragma unroll
+      for (int l = 0; l < 2; ++l) sx[i][l] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)off, 16 * l, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < C::ND; ++i) {
+      const int pc = tid + i * C::NT;
+      const int pix = pc >> 1;
+      const int oy = y0 + pix / C::TW, ox = x0 + pix % C::TW;
+      const bool ok = pc < C::DPC && oy < H && ox < W && dch < a.co;
+      const unsigned off = ok ? (unsigned)((((img * H + oy) * W + ox) * a.co + dch) * 4) : 0x80000000u;
+#pragma unroll
+      for (int l = 0; l < 2; ++l) sd[i][l] = __builtin_amdgcn_raw_buffer_load_b128(rs_d, (int)off, 16 * l, 0);
+    }
+  };
+  auto store_piece = [&](char* dst, int plane_bytes, const u32x4 (&v)[2], unsigned sgn) {
+    u32x4 p0, p1, p2;
+    split3(v[0] ^ sgn, v[1] ^ sgn, p0, p1, p2);
+    *reinterpret_cast<u32x4*>(dst) = p0;
+    *reinterpret_cast<u32x4*>(dst + plane_bytes) = p1;
+    *reinterpret_cast<u32x4*>(dst + 2 * plane_bytes) = p2;
+  };
+  const int nseq = split < a.ntiles ? (a.ntiles - split + a.P - 1) / a.P : 0;
+  const int sq1 = (nseq + 2) / 4, sq3 = nseq - sq1;               // + - - + over the block's tile sequence (see wgrad_h2_role)
+  auto store_tile = [&](int bo, int seq) {
+    const unsigned dsgn = (seq >= sq1 && seq < sq3) ? 0x80000000u : 0u;
+#pragma unroll
+    for (int i = 0; i < C::NX; ++i) {
+      const int pc = tid + i * C::NT;
+      if constexpr (XF) {
+        const bool in = (x_in >> i) & 1u;
+#pragma unroll
+        for (int l = 0; l < 2; ++l) {
+          f32x4 v = __builtin_bit_cast(f32x4, sx[i][l]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float t = act_apply(__builtin_fmaf(v[e], xsc[l][e], xsh[l][e]), a.in_act, a.in_slope);
+            v[e] = in ? t : 0.f;
+          }
+          sx[i][l] = __builtin_bit_cast(u32x4, v);
+        }
+      }
+      if (i < C::NX - 1 || pc < C::XPC) store_piece(Xs + bo + pc * 16, C::XPLANE, sx[i], 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < C::ND; ++i) {
+      const int pc = tid + i * C::NT;
+      if (i < C::ND - 1 || pc < C::DPC) store_piece(Ds + bo + pc * 16, C::DPLANE, sd[i], dsgn);
+    }
+  };
+
+  f32x16 acc[3];        // [kernel row]
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+
+  const int lane_off = (8 * hk + tq) * 64 + (cb + 4 * tp) * 2;
+  const char* const dbase0 = Ds + (r0 * C::TW + 32 * ksh) * 32 + lane_off;
+  const char* const xbase0 = Xs + (r0 * C::HWD + 32 * ksh + 2 * sg) * 32 + lane_off;
+
+  int cur = 0;
+  if (split < a.ntiles) load_tile(split);
+  store_tile(0, 0);
+  if (split + a.P < a.ntiles) load_tile(split + a.P);
+  __syncthreads();
+  int seq = 0;
+  bool negated = false;
+  for (int tile = split; tile < a.ntiles; tile += a.P, ++seq) {
+    if ((seq >= sq1 && seq < sq3) != negated) {
+      negated = !negated;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) acc[t] = -acc[t];
+    }
+    if (tile + a.P < a.ntiles) {
+      store_tile(cur ^ C::BUF, seq + 1);
+      if (tile + 2 * a.P < a.ntiles) load_tile(tile + 2 * a.P);
+    }
+    const char* const dbase = dbase0 + cur;
+    const char* const xbase = xbase0 + cur;
+    cur ^= C::BUF;
+#pragma unroll
+    for (int hfi = 0; hfi < C::NHF; ++hfi) {
+      bf16x8 A[3][PL];
+#pragma unroll
+      for (int rr = 0; rr < C::RW + 2; ++rr) {
+        if (rr < C::RW) {
+#pragma unroll
+          for (int pl = 0; pl < PL; ++pl)
+            A[rr % 3][pl] = h2_tr_fragment(dbase + pl * C::DPLANE + (rr * C::TW + 32 * C::KSH * hfi) * 32);
+        }
+        bf16x8 B[PL];
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) B[pl] = h2_tr_fragment(xbase + pl * C::XPLANE + (rr * C::HWD + 32 * C::KSH * hfi) * 32);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          const int j = rr - ky;               // output row (relative to r0) whose kernel row ky reads halo row rr
+          if (j >= 0 && j < C::RW) {
+#pragma unroll
+            for (int ij = 2; ij >= 0; --ij)
+#pragma unroll
+              for (int i = 0; i <= ij; ++i)
+                acc[ky] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[j % 3][i], B[ij - i], acc[ky], 0, 0, 0);
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (negated) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t) acc[t] = -acc[t];
+  }
+  // accumulator -> taps.  Register v < 8 of lane (lh, lr) is row m = (v & 3) + 8 (v >> 2) + 4 lh < 16, column n = lr; register v + 8
+  // is row m + 16.  One exchange across lr ^ 16 brings the odd-pixel blocks to the lanes that hold their even-pixel partners:
+  //   s = -1: lanes n < 16 add (m + 16, n + 16) -> column 0;  lanes n >= 16 keep (m, n) -> column 1;  (m + 16, n < 16) is dropped
+  //   s = +1: lanes n < 16 add (m + 16, n + 16) -> column 2;  lanes n >= 16 take (m + 16, n - 16) -> column 1;  (m, n >= 16) is dropped
+  // The four K shares of a shift group meet in LDS (free after the last tile) before ONE set of atomics per block and group: the
+  // rounding of the fp32 atomics onto a growing dW is what a long sum's error is made of, a quarter of the partials halves it.
+  const bool lo = lr < 16;
+  float out[24];
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      const float other = __shfl_xor(acc[ky][v + 8], 16);
+      out[ky * 8 + v] = lo ? acc[ky][v] + other : (sg ? other : acc[ky][v]);
+    }
+  float* const red = reinterpret_cast<float*>(smem);                 // [3 shares][2 groups][24][64 lanes]
+  if (ks != 0) {
+#pragma unroll
+    for (int j = 0; j < 24; ++j) red[(((ks - 1) * 2 + sg) * 24 + j) * 64 + lane] = out[j];
+  }
+  __syncthreads();
+  if (ks != 0) return;
+#pragma unroll
+  for (int k2 = 0; k2 < 3; ++k2)
+#pragma unroll
+    for (int j = 0; j < 24; ++j) out[j] += red[((k2 * 2 + sg) * 24 + j) * 64 + lane];
+  const int ci_g = lr & 15;
+  const int kx = lo ? 2 * sg : 1;
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      const int co_g = cob * 16 + (v & 3) + 8 * (v >> 2) + 4 * lh;
+      if (co_g < a.co) atomicAdd(a.dw + ((size_t)co_g * 9 + ky * 3 + kx) * a.ldw + a.dw_coff + ci_g, out[ky * 8 + v]);
+    }
+}
+
+// The same for a decoder conv1 WITHOUT a skip half whose 32 gathered channels are the nearest x2 up-sampling of `a` (block 5:
+// 32 -> 16 at full resolution).  dy is paired as above; x has 32 channels, so B carries one pixel per k:
+//     B[k][n] = x_up[2k + s][n] = a[y >> 1][j + floor(s / 2)][n]
+// -- contiguous pixel rows of the half-resolution source, shifted by e = floor(s / 2) in {-1, 0, +1}.  The shifts s = 0 and s = 1 read
+// the same rows of `a` and therefore ARE the same product: three products e = -1, 0, +1 stand for the four shift groups,
+//     column 0 = P(-1)[m<16] + P(0)[m>=16]      column 1 = P(0)[m<16] + P(0)[m>=16]      column 2 = P(0)[m<16] + P(+1)[m>=16]
+// (m < 16: the even pixels, m >= 16: the odd ones; P(-1)[m>=16] and P(+1)[m<16] are the offsets -2 / +2 and are dropped).  Rows
+// repeat in the same way: the three kernel rows of an output row y read only two rows of `a` -- (y >> 1) + py - 1 + u, u in {0, 1},
+// py = y & 1 -- which stand for the kernel rows {0}, {1, 2} (py = 0) or {0, 1}, {2} (py = 1).  A wave owns one output row of the
+// 4 x 64 pixel tile's parity py = wave & 1 and one 32-pixel half of it: 2 x 3 accumulators, 36 MFMAs per tile like the form above.
+template <int TR_, int TWK_>
+struct H2PU {
+  static constexpr int PL = 3, TR = TR_, TWK = TWK_;
+  static constexpr bool UP = true;
+  static constexpr int NT = 512;
+  static constexpr int TW = 32 * TWK, AR = TR / 2 + 2, AW = TW / 2 + 2, AP = AR * AW, TP = TR * TW;      // halo of `a`: AR rows x AW pixels
+  static constexpr int XPLANE = AP * 64, DPLANE = TP * 32;
+  static constexpr int BUF = PL * (XPLANE + DPLANE);
+  static constexpr int LDS = 2 * BUF;
+  static constexpr int XPC = AP * 4, DPC = TP * 2;
+  static constexpr int NX = (XPC + NT - 1) / NT, ND = (DPC + NT - 1) / NT;
+  static_assert(TR % 2 == 0 && (TR / 2) * TWK == 4, "one (row, half) of each parity per wave");
+  static_assert(LDS <= 160 * 1024 && 6 * 48 * 64 * 4 <= LDS, "LDS");
+};
+
+template <typename C>
+__device__ __forceinline__ void wgrad_h2pu_role(const WgradH2Args& a, char* smem, int tid, int lane, int wave) {
+  constexpr int PL = 3;
+  char* const Xs = smem;
+  char* const Ds = smem + PL * C::XPLANE;
+  const int lr = lane & 31, lh = lane >> 5;
+  const int grp = lane >> 4, cb = 16 * (grp & 1), hk = grp >> 1, tq = (lane & 15) >> 2, tp = lane & 3;
+  const int py = wave & 1, ks = wave >> 1;
+  const int ksh = ks % C::TWK, rsel = ks / C::TWK;                  // this wave's output row of the tile: 2 rsel + py
+  const int split = (int)blockIdx.x;
+  const int H = a.h, W = a.w, HA = a.h >> 1, WA = a.w >> 1;
+  __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), 0, (int)a.dy_bytes, 0x00020000);
+  u32x4 sx[C::NX][2], sd[C::ND][2];
+  auto load_tile = [&](int tile) {
+    const int tx = tile % a.ntx;
+    const int t2 = tile / a.ntx;
+    const int ty = t2 % a.nty, img = t2 / a.nty;
+    const int y0 = ty * C::TR, x0 = tx * C::TW;
+#pragma unroll
+    for (int i = 0; i < C::NX; ++i) {
+      const int pc = tid + i * C::NT;
+      const int pix = pc >> 2, oct = pc & 3;
+      const int hy = pix / C::AW, hx = pix - hy * C::AW;
+      const int iy = (y0 >> 1) + hy - 1, ix = (x0 >> 1) + hx - 1;
+      const bool ok = pc < C::XPC && (unsigned)iy < (unsigned)HA && (unsigned)ix < (unsigned)WA;
+      const unsigned off = ok ? (unsigned)((((img * HA + iy) * WA + ix) * 32 + oct * 8) * 4) : 0x80000000u;
+#pragma unroll
+      for (int l = 0; l < 2; ++l) sx[i][l] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)off, 16 * l, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < C::ND; ++i) {
+      const int pc = tid + i * C::NT;
+      const int pix = pc >> 1, oct = pc & 1;
+      const int oy = y0 + pix / C::TW, ox = x0 + pix % C::TW;
+      const bool ok = pc < C::DPC && oy < H && ox < W;
+      const unsigned off = ok ? (unsigned)((((img * H + oy) * W + ox) * 16 + oct * 8) * 4) : 0x80000000u;
+#pragma unroll
+      for (int l = 0; l < 2; ++l) sd[i][l] = __builtin_amdgcn_raw_buffer_load_b128(rs_d, (int)off, 16 * l, 0);
+    }
+  };
+  auto store_piece = [&](char* dst, int plane_bytes, const u32x4 (&v)[2], unsigned sgn) {
+    u32x4 p0, p1, p2;
+    split3(v[0] ^ sgn, v[1] ^ sgn, p0, p1, p2);
+    *reinterpret_cast<u32x4*>(dst) = p0;
+    *reinterpret_cast<u32x4*>(dst + plane_bytes) = p1;
+    *reinterpret_cast<u32x4*>(dst + 2 * plane_bytes) = p2;
+  };
+  const int nseq = split < a.ntiles ? (a.ntiles - split + a.P - 1) / a.P : 0;
+  const int sq1 = (nseq + 2) / 4, sq3 = nseq - sq1;               // + - - + over the block's tile sequence (see wgrad_h2_role)
+  auto store_tile = [&](int bo, int seq) {
+    const unsigned dsgn = (seq >= sq1 && seq < sq3) ? 0x80000000u : 0u;
+#pragma unroll
+    for (int i = 0; i < C::NX; ++i) {
+      const int pc = tid + i * C::NT;
+      if (i < C::NX - 1 || pc < C::XPC) store_piece(Xs + bo + pc * 16, C::XPLANE, sx[i], 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < C::ND; ++i) {
+      const int pc = tid + i * C::NT;
+      if (i < C::ND - 1 || pc < C::DPC) store_piece(Ds + bo + pc * 16, C::DPLANE, sd[i], dsgn);
+    }
+  };
+
+  f32x16 acc[6];        // [u][e + 1]
+#pragma unroll
+  for (int t = 0; t < 6; ++t)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+
+  const int lane_off = (8 * hk + tq) * 64 + (cb + 4 * tp) * 2;
+  const char* const dbase0 = Ds + ((2 * rsel + py) * C::TW + 32 * ksh) * 32 + lane_off;
+  const char* const xbase0 = Xs + ((rsel + py) * C::AW + 16 * ksh) * 64 + lane_off;      // halo row (y >> 1) + py - 1 + u, pixel j - 1 + (e + 1)
+
+  int cur = 0;
+  if (split < a.ntiles) load_tile(split);
+  store_tile(0, 0);
+  if (split + a.P < a.ntiles) load_tile(split + a.P);
+  __syncthreads();
+  int seq = 0;
+  bool negated = false;
+  for (int tile = split; tile < a.ntiles; tile += a.P, ++seq) {
+    if ((seq >= sq1 && seq < sq3) != negated) {
+      negated = !negated;
+#pragma unroll
+      for (int t = 0; t < 6; ++t) acc[t] = -acc[t];
+    }
+    if (tile + a.P < a.ntiles) {
+      store_tile(cur ^ C::BUF, seq + 1);
+      if (tile + 2 * a.P < a.ntiles) load_tile(tile + 2 * a.P);
+    }
+    const char* const dbase = dbase0 + cur;
+    const char* const xbase = xbase0 + cur;
+    cur ^= C::BUF;
+    bf16x8 A[PL];
+#pragma unroll
+    for (int pl = 0; pl < PL; ++pl) A[pl] = h2_tr_fragment(dbase + pl * C::DPLANE);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        bf16x8 B[PL];
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) B[pl] = h2_tr_fragment(xbase + pl * C::XPLANE + (u * C::AW + e) * 64);
+#pragma unroll
+        for (int ij = 2; ij >= 0; --ij)
+#pragma unroll
+          for (int i = 0; i <= ij; ++i)
+            acc[u * 3 + e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[i], B[ij - i], acc[u * 3 + e], 0, 0, 0);
+      }
+    __syncthreads();
+  }
+  if (negated) {
+#pragma unroll
+    for (int t = 0; t < 6; ++t) acc[t] = -acc[t];
+  }
+  // accumulator -> taps: register v < 8 is the even-pixel row m = (v & 3) + 8 (v >> 2) + 4 lh, register v + 8 its odd-pixel twin, the
+  // lane's column is the gathered channel.  Kernel rows of (py, u): py = 0: {0}, {1, 2};  py = 1: {0, 1}, {2}.
+  // The columns are formed first, then the four K shares of a row parity meet in LDS (free after the last tile): one set of atomics
+  // per block and parity.
+  float out[48];        // [u][kx][v]
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      out[(u * 3 + 0) * 8 + v] = acc[u * 3 + 0][v] + acc[u * 3 + 1][v + 8];
+      out[(u * 3 + 1) * 8 + v] = acc[u * 3 + 1][v] + acc[u * 3 + 1][v + 8];
+      out[(u * 3 + 2) * 8 + v] = acc[u * 3 + 1][v] + acc[u * 3 + 2][v + 8];
+    }
+  float* const red = reinterpret_cast<float*>(smem);                 // [3 shares][2 parities][48][64 lanes]
+  if (ks != 0) {
+#pragma unroll
+    for (int j = 0; j < 48; ++j) red[(((ks - 1) * 2 + py) * 48 + j) * 64 + lane] = out[j];
+  }
+  __syncthreads();
+  if (ks != 0) return;
+#pragma unroll
+  for (int k2 = 0; k2 < 3; ++k2)
+#pragma unroll
+    for (int j = 0; j < 48; ++j) out[j] += red[((k2 * 2 + py) * 48 + j) * 64 + lane];
+  auto emit = [&](int u, int ky) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      const int co_g = (v & 3) + 8 * (v >> 2) + 4 * lh;
+      float* const row = a.dw + ((size_t)co_g * 9 + ky * 3) * a.ldw + a.dw_coff + lr;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) atomicAdd(row + kx * a.ldw, out[(u * 3 + kx) * 8 + v]);
+    }
+  };
+  if (py == 0) {
+    emit(0, 0); emit(1, 1); emit(1, 2);
+  } else {
+    emit(0, 0); emit(0, 1); emit(1, 2);
+  }
+}
+
+// its own template under the same name: the profiling symbol is conv_wgrad_h2_kernel<3, udaseg::H2P<TR, TWK>, XF> (H2PU: the up-sampled form)
+template <int PL, typename C, bool XF>
+__global__ __launch_bounds__(512, 1) void conv_wgrad_h2_kernel(const WgradH2Args a) {
+  static_assert(PL == 3, "the pair-packed form is fp32 split only");
+  extern __shared__ __attribute__((aligned(16))) char h2smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (C::UP) wgrad_h2pu_role<C>(a, h2smem, tid, lane, wave);
+  else wgrad_h2p_role<C, XF>(a, h2smem, tid, lane, wave);
+}
+
+// the pair-packed form serves d (UDASEG_OPT_WGRAD_PAIR: bit 0 the 16 -> 16 layers, bit 1 the layers of two produced-channel blocks,
+// bit 2 the up-sampled 32 -> 16 layer without a skip half -- the one geometry with up_ca == ci)
+static bool h2_pair_up_config(const udaseg_conv_desc* d, int up_ca, bool f32) {
+  if (!f32 || up_ca != 32 || d->ci != 32 || d->co != 16) return false;
+  if (d->hi % 2 != 0 || d->wi % 2 != 0 || d->wi < 16) return false;
+  return (opt_get(UDASEG_OPT_WGRAD_PAIR) & 4) != 0;
+}
+static bool h2_pair_config(const udaseg_conv_desc* d, int up_ca, bool f32) {
+  if (!f32 || up_ca != 0 || d->ci != 16 || d->co < 8 || d->co > 32 || d->co % 8 != 0) return false;
+  if (d->wi % 2 != 0 || d->wi < 16) return false;
+  return (opt_get(UDASEG_OPT_WGRAD_PAIR) & (d->co <= 16 ? 1 : 2)) != 0;
+}
+
 // which configuration serves (d, up_ca): 0 = none
 //   1: 64 x 64 channel blocks, 4 x 32 pixel tiles (f32x3) / 8 x 32 (bf16)      2: 64 x 64, 8 x 16 pixel tiles (16-pixel-wide images)
 //   3: 32 produced x 64 gathered channels, 4 x 32 (f32x3) / 8 x 32 (bf16)      4: 32 x 32 channels
+//   5: 16 gathered channels, pair-packed, 4 x 64 pixel tiles (fp32 only)      6: 32 up-sampled -> 16, no skip half, pair-packed dy
 static int h2_config(const udaseg_conv_desc* d, int up_ca, bool f32) {
   if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1) return 0;
   if (d->n <= 0 || d->hi <= 0 || d->wi <= 0 || d->ho != d->hi || d->wo != d->wi || d->ci <= 0 || d->co <= 0) return 0;
   const long long px = (long long)d->n * d->hi * d->wi;
   const int es = f32 ? 4 : 2;
   if (px * d->ci * es >= (1LL << 31) || px * d->co * es >= (1LL << 31)) return 0;
+  if (h2_pair_config(d, up_ca, f32)) return 5;
+  if (h2_pair_up_config(d, up_ca, f32)) return 6;
   int cfg = 0;
   if (d->ci % 64 == 0 && d->co % 64 == 0) cfg = d->wi < 32 ? 2 : 1;
   else if (d->ci % 64 == 0 && d->co % 32 == 0) cfg = 3;
@@ -463,6 +894,50 @@ static int launch_h2_t(const udaseg_conv_desc* d, const void* x, const void* x2,
   return UDASEG_OK;
 }
 
+template <typename C>
+static int launch_h2p_t(const udaseg_conv_desc* d, const void* x, const void* dy, float* dw, hipStream_t s, int target, const H2In& in) {
+  WgradH2Args a = {};
+  a.x = x; a.dy = dy; a.dw = dw;
+  a.ldw = in.ldw > 0 ? in.ldw : d->ci; a.dw_coff = in.ldw > 0 ? in.dw_coff : 0;
+  a.in_scale = in.scale; a.in_shift = in.shift; a.in_act = in.act; a.in_slope = in.slope;
+  a.n = d->n; a.h = d->hi; a.w = d->wi; a.ci = d->ci; a.co = d->co;
+  a.ntx = cdiv(d->wi, C::TW); a.nty = cdiv(d->hi, C::TR); a.ntiles = d->n * a.ntx * a.nty;
+  a.ncib = 1; a.pairs = cdiv(d->co, 16);
+  int P = target / a.pairs;
+  if (P < 1) P = 1;
+  if (P > a.ntiles) P = a.ntiles;
+  a.P = P;
+  const long long px = (long long)d->n * d->hi * d->wi;
+  a.x_bytes = (unsigned)((C::UP ? px / 4 : px) * d->ci * 4);
+  a.dy_bytes = (unsigned)(px * d->co * 4);
+  if (C::UP && a.in_scale != nullptr) {          // the up-sampled form has no in-staging transform
+    set_error("conv2d_wgrad_halo: the pair-packed up-sampled form takes a written source only");
+    return UDASEG_E_UNSUPPORTED;
+  }
+  const bool xf = a.in_scale != nullptr;
+  auto kern = conv_wgrad_h2_kernel<3, C, false>;
+  if constexpr (!C::UP) {
+    if (xf) kern = conv_wgrad_h2_kernel<3, C, true>;
+  }
+  static std::atomic<bool> attr_done[2] = {};
+  if (!attr_done[xf]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_h2, pair-packed)");
+    attr_done[xf] = true;
+  }
+  static std::atomic<int> kid[2] = {{-1}, {-1}};
+  if (kid[xf] < 0) {
+    char nm[96];
+    snprintf(nm, sizeof(nm), "conv_wgrad_h2_kernel<3, udaseg::H2P%s<%d, %d>, %s>", C::UP ? "U" : "", C::TR, C::TWK, xf ? "true" : "false");
+    kid[xf] = kprof_id(nm);
+  }
+  hipEvent_t ev = kprof_begin(s);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, s, a);
+  kprof_end(kid[xf], ev, s, 2.0 * (double)px * d->co * 9.0 * d->ci);
+  UDASEG_LAUNCH_CHECK("conv_wgrad_h2 (pair-packed) launch");
+  return UDASEG_OK;
+}
+
 int launch_wgrad_h2(const udaseg_conv_desc* d, const void* x, const void* x2, int up_ca, const void* dy, float* dw, bool f32,
                     hipStream_t s, const float* in_scale, const float* in_shift, int in_act, float in_slope, int ldw, int dw_coff) {
   H2In in;
@@ -488,6 +963,14 @@ int launch_wgrad_h2(const udaseg_conv_desc* d, const void* x, const void* x2, in
   if (tbf < 1) tbf = 96;
   const int db = opt_get(UDASEG_OPT_WGRAD_DB);      // 0: the single-buffer 4-row form of the 64 x 64 fp32 configuration (A/B)
   if (f32) {
+    if (cfg == 5) {          // UDASEG_OPT_WGRAD_PAIR_BLOCKS: tuning aid
+      const int tp = opt_get(UDASEG_OPT_WGRAD_PAIR_BLOCKS);
+      return launch_h2p_t<H2P<4, 2>>(d, x, dy, dw, s, tp >= 1 ? tp : 120, in);
+    }
+    if (cfg == 6) {
+      const int tp = opt_get(UDASEG_OPT_WGRAD_PAIR_BLOCKS);
+      return launch_h2p_t<H2PU<4, 2>>(d, x, dy, dw, s, tp >= 1 ? tp : 120, in);
+    }
     if (cfg == 1 && db) return launch_h2_t<3, 2, 2, 2, 2, 4, true>(d, x, x2, up_ca, dy, dw, s, tf3, in);
     if (cfg == 1) return launch_h2_t<3, 2, 2, 4, 2, 4>(d, x, x2, up_ca, dy, dw, s, tf3, in);
     if (cfg == 2) return launch_h2_t<3, 2, 2, 8, 1, 4>(d, x, x2, up_ca, dy, dw, s, tdeep3, in);

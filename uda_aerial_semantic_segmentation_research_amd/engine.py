@@ -945,7 +945,8 @@ class Plan:
         if isinstance(x.a if up else x, LazyAct):
             return BNIN
         if up:
-            both = self._wgrad_halo and x.skip is not None and K.conv2d_wgrad_halo_ok(d, x.a.shape[-1], f32=not self.bf16)
+            # (no skip half: only the pair-packed form of the full-resolution 32 -> 16 layer takes it)
+            both = self._wgrad_halo and K.conv2d_wgrad_halo_ok(d, x.a.shape[-1], f32=not self.bf16)
             return HALO if both else PART
         return HALO if self._wgrad_halo and K.conv2d_wgrad_halo_ok(d, f32=not self.bf16) else GENERIC
 
