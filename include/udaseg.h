@@ -368,6 +368,33 @@ int udaseg_score_hist(const float* logits, const int64_t* target, int64_t pixels
 int udaseg_curve_finish(const int64_t* pos, const int64_t* neg, int classes, int bins, double* auc, double* ap,
                         double* auc_slack, int64_t* support, void* stream);
 
+/* ---- class-balanced pseudo-labels of unlabelled target frames (CBST, Zou et al. 2018; an extension, the reference's phase 3 is
+ * consistency only).  scores: padded NHWC fp32 [pixels][ldc], 16-byte aligned, ldc % 4 == 0, 0 < classes <= 32, classes <= ldc,
+ * 0 < pixels < 2^31; only channels < classes are read.  ONE definition serves both pixel entry points:
+ *   probs == 0 (logits z):        c^ = first maximum of z (udaseg_score_hist's comparison), m = z[c^],
+ *                                 S = sum_{c < classes} expf(z_c - m), confidence p = 1 / S
+ *   probs == 1 (probabilities q): c^ = first maximum of q, p = q[c^]      (udaseg_predict_finish's normalised accumulator)
+ *   bin(p) = min((int)floorf(p * bins), bins - 1), bins in {256, 512, 1024, 2048, 4096}: edges k / bins exact, p == 1 in the top bin
+ *   a pixel whose p is not finite (a NaN logit, a +inf logit, all logits -inf) or, with probs, outside [0, 1] or beside a NaN in
+ *   any channel < classes is NON-FINITE: counted in no histogram cell, always labelled void, counted on its own.
+ * hist[c^ * bins + bin(p)] += 1 for every finite pixel, nonfinite[0] += the others (int64 counters that ACCUMULATE across calls;
+ * the caller zeroes them once, as for udaseg_score_hist). */
+int udaseg_conf_hist(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, int64_t* hist,
+                     int64_t* nonfinite, void* stream);
+/* per class c, in integers and IEEE float64 only: n_c = sum_b hist[c][b], need_c = (int64)ceil(portion[c] * (double)n_c),
+ * k_c = the largest k in [0, bins - 1] with sum_{b >= k} hist[c][b] >= need_c (bins - 1 when n_c == 0; 0 if no k qualifies), then
+ * thr_bins[c] = min(max(k_c, k_floor), k_cap) and support[c] = n_c.  portion: float64 [classes] ON THE DEVICE, each in (0, 1];
+ * 0 <= k_floor <= k_cap <= bins - 1 is checked.  A pixel predicted as c is kept iff bin(p) >= thr_bins[c], i.e. p >= thr_bins[c] /
+ * bins; k_cap is CBST's rule that no class has to be more confident than the cap.  Deterministic (fixed summation order). */
+int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bins, const double* portion, int k_floor, int k_cap,
+                             int32_t* thr_bins, int64_t* support, void* stream);
+/* labels[p] = c^ if the pixel is finite and bin(p) >= thr_bins[c^], else void_label (classes <= void_label <= 255); conf (fp32
+ * [pixels], may be NULL) receives p, or 0 for a non-finite pixel; counts (int64 [classes + 2], ACCUMULATES) += the kept pixels per
+ * class, then the void pixels (the non-finite ones included), then the non-finite ones.  bins must be the value the thresholds
+ * were made with. */
+int udaseg_pseudo_labels(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, const int32_t* thr_bins,
+                         int void_label, uint8_t* labels, float* conf, int64_t* counts, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

@@ -113,6 +113,9 @@ SIGNATURES = {
     "udaseg_argmax_confusion": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "udaseg_score_hist": (_I, [_P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
     "udaseg_curve_finish": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "udaseg_conf_hist": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_pseudo_thresholds": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "udaseg_pseudo_labels": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

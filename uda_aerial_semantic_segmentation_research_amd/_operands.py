@@ -328,6 +328,13 @@ OPERANDS = {
     "udaseg_curve_finish": [T("pos", i64, "classes*bins"), T("neg", i64, "classes*bins"), I("classes"), I("bins"),
                             T("auc", f64, "classes"), T("ap", f64, "classes"), T("auc_slack", f64, "classes"),
                             T("support", i64, "2*classes"), S],
+    "udaseg_conf_hist": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
+                         T("hist", i64, "classes*bins"), T("nonfinite", i64, 1), S],
+    "udaseg_pseudo_thresholds": [T("hist", i64, "classes*bins"), I("classes"), I("bins"), T("portion", f64, "classes"), I("k_floor"),
+                                 I("k_cap"), T("thr_bins", i32, "classes"), T("support", i64, "classes"), S],
+    "udaseg_pseudo_labels": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
+                             T("thr_bins", i32, "classes"), I("void_label"), T("labels", u8, "pixels"), T("conf", f32, "pixels", True),
+                             T("counts", i64, "classes+2"), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

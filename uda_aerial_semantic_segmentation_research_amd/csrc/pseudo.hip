@@ -1,0 +1,358 @@
+// Class-balanced pseudo-labels of unlabelled target frames on the device (CBST, Zou et al. 2018; an extension: the reference's
+// phase 3 is consistency only).  Done with torch this is softmax -> max -> one quantile (a sort) per class -> where, several
+// passes over the scores; here ONE pass makes a per-class histogram of the winning class's confidence (udaseg_conf_hist), a
+// tiny kernel turns the histogram into one threshold BIN per class (udaseg_pseudo_thresholds), and one more pass writes the
+// uint8 masks with everything below its class's threshold marked void (udaseg_pseudo_labels).  No sort, integer counters only.
+//
+// The shared definition (pixel_conf below, used by BOTH pixel kernels, so that histogram and labelling cannot disagree).
+// scores: padded NHWC fp32 [pixels][ldc], ldc % 4 == 0, 0 < classes <= 32, classes <= ldc; only channels < classes count.
+//   probs == 0 (logits z):     c^ = first maximum of z (the comparison rule of score_hist_kernel), m = z[c^],
+//                              S = sum_{c < classes} expf(z_c - m) in fp32 (four partial sums, channel c in sum c % 4,
+//                              folded as (s0 + s1) + (s2 + s3): a third of the rounding of one chain), confidence p = 1 / S
+//   probs == 1 (probabilities q, predict_large's accumulator view):   c^ = first maximum of q, p = q[c^]
+//   bin(p) = min((int)floorf(p * B), B - 1), B in {256, 512, 1024, 2048, 4096}: the edges k / B are exact, p == 1 is in bin B - 1
+//   a pixel whose p is not finite (a NaN logit, a +inf logit, all logits -inf) or, in probs mode, outside [0, 1] or beside a
+//   NaN in any channel < classes is NON-FINITE: in no histogram cell, always void, counted on its own.
+// A pixel predicted as c is kept iff bin(p) >= thr_bins[c], i.e. iff p >= thr_bins[c] / B.
+//
+// Routes of udaseg_conf_hist.  Each pixel touches ONE cell, so the block's whole [classes][bins] table of 32-bit counters sits
+// in dynamic LDS whenever it fits CH_CELLS = 32768 cells (128 KiB of the CU's 160 KiB) and the scores are read once:
+//   bins  256,  512, 1024: every class count (<= 32) in one group      -- 23 classes x 1024 bins = 92 KiB, ONE pass
+//   bins 2048:             classes <= 16 one group, 17..32 two groups over blockIdx.y (each group re-reads the scores)
+//   bins 4096:             classes <=  8 one group, then one more group per 8 classes (up to four)
+// Blocks are few and long (CH_BLOCKS in all, 1024 threads each: a table beyond 80 KiB leaves one block per CU, and sixteen waves
+// keep enough loads in flight for it), for the reason given in curves.hip: a block flushes one 64-bit global atomic per NON-EMPTY
+// cell, so its pixel count has to be large against its cell count.  The LDS atomics are plain: a wave's 64 pixels are 6 KiB of
+// scores, hundreds of clocks of a CU's share of the memory rate, against at most 64 clocks when every lane hits the same top
+// bin; score_hist_kernel issues 23 such atomics per pixel and runs at the memory rate (profiles/curves_bench.txt).
+// tools/bench_pseudo.py reports both pixel kernels against a device copy of the same bytes.
+#include "common.h"
+
+namespace udaseg {
+
+struct PixelConf {
+  int cls;        // c^
+  float p;        // confidence
+  bool finite;
+};
+
+template <int NV>
+__device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, int classes, int probs) {
+  f32x4 v[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);
+  float m = -INFINITY;
+  int am = 0;
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * q + e;
+      if (c < classes && (c == 0 || v[q][e] > m)) { m = v[q][e]; am = c; }
+    }
+  PixelConf r;
+  r.cls = am;
+  if (probs) {
+    bool nan = false;                                      // the comparison above steps over a NaN beyond channel 0
+#pragma unroll
+    for (int q = 0; q < NV; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) nan |= 4 * q + e < classes && v[q][e] != v[q][e];
+    r.p = m;
+    r.finite = !nan && m >= 0.f && m <= 1.f;
+  } else {
+    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};                       // channel c adds into partial sum c % 4: four short chains
+#pragma unroll
+    for (int q = 0; q < NV; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * q + e < classes) s4[e] += expf(v[q][e] - m);   // exactly 1 at the maximum, so S >= 1 whenever it is a number
+    const float S = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    r.p = 1.f / S;
+    r.finite = __builtin_isfinite(r.p);
+  }
+  return r;
+}
+
+__device__ __forceinline__ int conf_bin(float p, int bins) { return min((int)floorf(p * (float)bins), bins - 1); }
+
+__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+constexpr int CH_CELLS = 32768;
+constexpr int CH_THREADS = 1024;
+constexpr int CH_BLOCKS = 256;
+constexpr int CH_LDS_MAX = (CH_CELLS + 4) * 4;
+
+// LDS: [tab] table cells of this block's class group, then one counter of the non-finite pixels (group 0 reports it).
+template <int NV>
+__global__ __launch_bounds__(CH_THREADS) void conf_hist_kernel(const float* __restrict__ scores, int64_t pixels, int classes, int ldc,
+                                                               int probs, int bins, int cg, int tab,
+                                                               unsigned long long* __restrict__ hist,
+                                                               unsigned long long* __restrict__ nonfinite) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int cells[];
+  const int c0 = blockIdx.y * cg;
+  const int nc = min(cg, classes - c0);
+  const int ncell = nc * bins;                             // <= tab
+  for (int i = threadIdx.x; i < ncell; i += CH_THREADS) cells[i] = 0;
+  if (threadIdx.x == 0) cells[tab] = 0;
+  __syncthreads();
+  unsigned int bad = 0;
+  const int64_t T = (int64_t)gridDim.x * CH_THREADS;
+  for (int64_t p = (int64_t)blockIdx.x * CH_THREADS + threadIdx.x; p < pixels; p += T) {
+    const PixelConf r = pixel_conf<NV>(scores + p * ldc, classes, probs);
+    if (!r.finite) {
+      ++bad;
+      continue;
+    }
+    const int c = r.cls - c0;
+    if (c >= 0 && c < nc) atomicAdd(&cells[c * bins + conf_bin(r.p, bins)], 1u);
+  }
+  if (blockIdx.y == 0) {
+    bad = wave_sum_u(bad);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&cells[tab], bad);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < ncell; i += CH_THREADS) {
+    const unsigned int v = cells[i];
+    if (v) atomicAdd(&hist[(size_t)c0 * bins + i], (unsigned long long)v);
+  }
+  if (threadIdx.x == 0 && blockIdx.y == 0 && cells[tab]) atomicAdd(nonfinite, (unsigned long long)cells[tab]);
+}
+
+// One block per class.  Thread j owns the j-th chunk of bins / 256 bins from the top; the chunk sums are combined in thread
+// order, so the result does not depend on timing.  need = (int64)ceil(portion * (double)n); the threshold bin is the largest k
+// with sum_{b >= k} hist[b] >= need (bins - 1 for an empty class, 0 if no k qualifies), then clamped into [k_floor, k_cap].
+constexpr int PT_THREADS = 256;
+
+__global__ __launch_bounds__(PT_THREADS) void pseudo_thresholds_kernel(const unsigned long long* __restrict__ hist, int bins,
+                                                                       const double* __restrict__ portion, int k_floor, int k_cap,
+                                                                       int* __restrict__ thr_bins,
+                                                                       unsigned long long* __restrict__ support) {
+  __shared__ unsigned long long chunk[PT_THREADS];
+  __shared__ int found;
+  const int c = blockIdx.x, j = threadIdx.x;
+  const int per = bins / PT_THREADS;
+  const unsigned long long* row = hist + (size_t)c * bins;
+  const int hi = bins - 1 - j * per;                       // this thread's bins: hi, hi - 1, ..., hi - per + 1
+  unsigned long long s = 0;
+  for (int i = 0; i < per; ++i) s += row[hi - i];
+  chunk[j] = s;
+  __syncthreads();
+  unsigned long long above = 0, n = 0;                     // above: the pixels in the bins above this thread's chunk
+  for (int i = 0; i < PT_THREADS; ++i) {
+    if (i == j) above = n;
+    n += chunk[i];
+  }
+  const long long need = (long long)ceil(portion[c] * (double)n);
+  if (j == 0) found = need <= 0 ? bins - 1 : 0;
+  __syncthreads();
+  if ((long long)above < need) {                           // at most one thread crosses `need` inside its chunk
+    unsigned long long run = above;
+    for (int i = 0; i < per; ++i) {
+      run += row[hi - i];
+      if ((long long)run >= need) {
+        found = hi - i;
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  if (j == 0) {
+    thr_bins[c] = min(max(found, k_floor), k_cap);
+    support[c] = n;
+  }
+}
+
+// A wave takes 256 consecutive pixels at a time, lane l the pixels 64 j + l (j = 0..3): consecutive lanes read consecutive rows.
+// The four labels of a lane are packed into one word and exchanged so that lane l holds the pixels 4 l .. 4 l + 3 and writes them
+// with ONE 32-bit store (256 contiguous bytes per wave); a chunk cut short by the end of the buffer, or labels that are not
+// 4-byte aligned, take the byte stores.  conf is written as it is computed: one float per lane, contiguous over the wave.
+// counts: kept per class through LDS counters, void / non-finite in registers, one global atomic per non-zero counter per block.
+constexpr int PL_THREADS = 256;
+constexpr int PL_MAX_BLOCKS = 2048;
+
+template <int NV>
+__global__ __launch_bounds__(PL_THREADS) void pseudo_labels_kernel(const float* __restrict__ scores, int64_t pixels, int classes,
+                                                                   int ldc, int probs, int bins, const int* __restrict__ thr_bins,
+                                                                   int void_label, uint8_t* __restrict__ labels,
+                                                                   float* __restrict__ conf, unsigned long long* __restrict__ counts,
+                                                                   int vec_ok) {
+  __shared__ unsigned int cnt[34];
+  __shared__ int thr[32];
+  if (threadIdx.x < 34) cnt[threadIdx.x] = 0;
+  if (threadIdx.x < classes) thr[threadIdx.x] = thr_bins[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr int WAVES = PL_THREADS / 64;
+  unsigned int nvoid = 0, nbad = 0;
+  const int64_t chunks = (pixels + 255) >> 8;
+  for (int64_t ch = (int64_t)blockIdx.x * WAVES + wave; ch < chunks; ch += (int64_t)gridDim.x * WAVES) {
+    const int64_t base = ch << 8;
+    unsigned int packed = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t p = base + 64 * j + lane;
+      int lab = void_label;
+      if (p < pixels) {
+        const PixelConf r = pixel_conf<NV>(scores + p * ldc, classes, probs);
+        float cf = 0.f;
+        if (r.finite) {
+          cf = r.p;
+          if (conf_bin(r.p, bins) >= thr[r.cls]) {
+            lab = r.cls;
+            atomicAdd(&cnt[lab], 1u);
+          } else {
+            ++nvoid;
+          }
+        } else {
+          ++nvoid;
+          ++nbad;
+        }
+        if (conf) conf[p] = cf;
+      }
+      packed |= (unsigned int)lab << (8 * j);
+    }
+    if (vec_ok && base + 256 <= pixels) {                  // uniform over the wave
+      unsigned int out = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {                        // pixel 4 l + e: lane (4 l + e) & 63 holds it in byte l >> 4
+        const unsigned int w = (unsigned int)__shfl((int)packed, (4 * lane + e) & 63, 64);
+        out |= ((w >> (8 * (lane >> 4))) & 0xffu) << (8 * e);
+      }
+      reinterpret_cast<unsigned int*>(labels + base)[lane] = out;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t p = base + 64 * j + lane;
+        if (p < pixels) labels[p] = (uint8_t)((packed >> (8 * j)) & 0xffu);
+      }
+    }
+  }
+  nvoid = wave_sum_u(nvoid);
+  nbad = wave_sum_u(nbad);
+  if (lane == 0) {
+    if (nvoid) atomicAdd(&cnt[32], nvoid);
+    if (nbad) atomicAdd(&cnt[33], nbad);
+  }
+  __syncthreads();
+  if (threadIdx.x < classes) {
+    if (cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+  } else if (threadIdx.x < classes + 2) {
+    const unsigned int v = cnt[32 + threadIdx.x - classes];
+    if (v) atomicAdd(&counts[threadIdx.x], (unsigned long long)v);
+  }
+}
+
+static bool pseudo_bins_supported(int bins) { return bins == 256 || bins == 512 || bins == 1024 || bins == 2048 || bins == 4096; }
+
+static bool scores_args_ok(const char* who, const void* scores, int64_t pixels, int classes, int ldc, int probs, int bins) {
+  if (!(pixels > 0 && pixels < ((int64_t)1 << 31) && classes > 0 && classes <= 32 && classes <= ldc && ldc % 4 == 0)) {
+    set_error("%s: need 0 < pixels < 2^31, 0 < classes <= 32, classes <= ldc, ldc %% 4 == 0 (pixels=%lld classes=%d ldc=%d)", who,
+              (long long)pixels, classes, ldc);
+    return false;
+  }
+  if (!pseudo_bins_supported(bins)) {
+    set_error("%s: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", who, bins);
+    return false;
+  }
+  if (probs != 0 && probs != 1) {
+    set_error("%s: probs must be 0 (logits) or 1 (probabilities), got %d", who, probs);
+    return false;
+  }
+  if (reinterpret_cast<uintptr_t>(scores) & 15) {
+    set_error("%s: scores must be 16-byte aligned", who);
+    return false;
+  }
+  return true;
+}
+
+}  // namespace udaseg
+
+using namespace udaseg;
+
+#define PSEUDO_DISPATCH_NV(nv, kernel, grid, block, lds, st, ...)                       \
+  switch (nv) {                                                                         \
+    case 1: hipLaunchKernelGGL(kernel<1>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 2: hipLaunchKernelGGL(kernel<2>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 3: hipLaunchKernelGGL(kernel<3>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 4: hipLaunchKernelGGL(kernel<4>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 5: hipLaunchKernelGGL(kernel<5>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 6: hipLaunchKernelGGL(kernel<6>, grid, block, lds, st, __VA_ARGS__); break;    \
+    case 7: hipLaunchKernelGGL(kernel<7>, grid, block, lds, st, __VA_ARGS__); break;    \
+    default: hipLaunchKernelGGL(kernel<8>, grid, block, lds, st, __VA_ARGS__); break;   \
+  }
+
+template <int NV>
+static hipError_t conf_hist_allow_lds() {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(conf_hist_kernel<NV>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             CH_LDS_MAX);
+}
+
+extern "C" int udaseg_conf_hist(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, int64_t* hist,
+                                int64_t* nonfinite, void* stream) {
+  UDASEG_CHECK_ARG(scores && hist && nonfinite, "conf_hist: NULL pointer");
+  if (!scores_args_ok("conf_hist", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
+  hipStream_t st = as_stream(stream);
+  const int nv = cdiv(classes, 4);
+  const int cg = min(classes, CH_CELLS / bins);            // classes per group
+  const int groups = cdiv(classes, cg);
+  const int tab = cg * bins;
+  const size_t lds = (size_t)(tab + 4) * 4;
+  static std::atomic<bool> attr_done[9];
+  if (lds > 48 * 1024 && !attr_done[nv]) {
+    hipError_t e = hipSuccess;
+    switch (nv) {
+      case 1: e = conf_hist_allow_lds<1>(); break;
+      case 2: e = conf_hist_allow_lds<2>(); break;
+      case 3: e = conf_hist_allow_lds<3>(); break;
+      case 4: e = conf_hist_allow_lds<4>(); break;
+      case 5: e = conf_hist_allow_lds<5>(); break;
+      case 6: e = conf_hist_allow_lds<6>(); break;
+      case 7: e = conf_hist_allow_lds<7>(); break;
+      default: e = conf_hist_allow_lds<8>(); break;
+    }
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conf_hist)");
+    attr_done[nv] = true;
+  }
+  int gx = CH_BLOCKS / groups;
+  const int64_t want = cdiv64(pixels, CH_THREADS);
+  if (gx > want) gx = (int)want;
+  if (gx < 1) gx = 1;
+  PSEUDO_DISPATCH_NV(nv, conf_hist_kernel, dim3(gx, groups), dim3(CH_THREADS), lds, st, scores, pixels, classes, ldc, probs, bins, cg,
+                     tab, (unsigned long long*)hist, (unsigned long long*)nonfinite);
+  UDASEG_LAUNCH_CHECK("conf_hist launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bins, const double* portion, int k_floor, int k_cap,
+                                        int32_t* thr_bins, int64_t* support, void* stream) {
+  UDASEG_CHECK_ARG(hist && portion && thr_bins && support, "pseudo_thresholds: NULL pointer");
+  UDASEG_CHECK_ARG(classes > 0 && classes <= 32, "pseudo_thresholds: need 0 < classes <= 32 (classes=%d)", classes);
+  UDASEG_CHECK_ARG(pseudo_bins_supported(bins), "pseudo_thresholds: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
+  UDASEG_CHECK_ARG(0 <= k_floor && k_floor <= k_cap && k_cap <= bins - 1,
+                   "pseudo_thresholds: need 0 <= k_floor <= k_cap <= bins - 1 (k_floor=%d k_cap=%d bins=%d)", k_floor, k_cap, bins);
+  hipLaunchKernelGGL(pseudo_thresholds_kernel, dim3(classes), dim3(PT_THREADS), 0, as_stream(stream), (const unsigned long long*)hist,
+                     bins, portion, k_floor, k_cap, thr_bins, (unsigned long long*)support);
+  UDASEG_LAUNCH_CHECK("pseudo_thresholds launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_pseudo_labels(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins,
+                                    const int32_t* thr_bins, int void_label, uint8_t* labels, float* conf, int64_t* counts,
+                                    void* stream) {
+  UDASEG_CHECK_ARG(scores && thr_bins && labels && counts, "pseudo_labels: NULL pointer");
+  if (!scores_args_ok("pseudo_labels", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
+  UDASEG_CHECK_ARG(void_label >= classes && void_label <= 255,
+                   "pseudo_labels: need classes <= void_label <= 255 (void_label=%d classes=%d)", void_label, classes);
+  const int64_t want = cdiv64(cdiv64(pixels, 256), PL_THREADS / 64);
+  const int gx = (int)(want > PL_MAX_BLOCKS ? PL_MAX_BLOCKS : want);
+  const int vec_ok = (reinterpret_cast<uintptr_t>(labels) & 3) == 0;
+  PSEUDO_DISPATCH_NV(cdiv(classes, 4), pseudo_labels_kernel, dim3(gx), dim3(PL_THREADS), 0, as_stream(stream), scores, pixels, classes,
+                     ldc, probs, bins, thr_bins, void_label, labels, conf, (unsigned long long*)counts, vec_ok);
+  UDASEG_LAUNCH_CHECK("pseudo_labels launch");
+  return UDASEG_OK;
+}

@@ -102,6 +102,24 @@ def curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st=None):
     check(ops.udaseg_curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st), "curve_finish")
 
 
+def conf_hist(scores_base, pixels, classes, ldc, probs, bins, hist, nonfinite, st=None):
+    """hist [classes * bins] int64 += the histogram of the winning class's confidence, nonfinite [1] += the pixels without one
+    (they accumulate)."""
+    check(ops.udaseg_conf_hist(scores_base, pixels, classes, ldc, int(bool(probs)), bins, hist, nonfinite, st), "conf_hist")
+
+
+def pseudo_thresholds(hist, classes, bins, portion, k_floor, k_cap, thr_bins, support, st=None):
+    """thr_bins [classes] int32, support [classes] int64 from the table; portion: float64 [classes] on the device."""
+    check(ops.udaseg_pseudo_thresholds(hist, classes, bins, portion, k_floor, k_cap, thr_bins, support, st), "pseudo_thresholds")
+
+
+def pseudo_labels(scores_base, pixels, classes, ldc, probs, bins, thr_bins, void_label, labels, conf, counts, st=None):
+    """labels [pixels] uint8 (void_label below the class's threshold bin), conf [pixels] fp32 or None, counts [classes + 2] int64 +=
+    kept per class, void, non-finite."""
+    check(ops.udaseg_pseudo_labels(scores_base, pixels, classes, ldc, int(bool(probs)), bins, thr_bins, void_label, labels, conf,
+                                   counts, st), "pseudo_labels")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,
