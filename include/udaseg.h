@@ -395,6 +395,34 @@ int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bins, const d
 int udaseg_pseudo_labels(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, const int32_t* thr_bins,
                          int void_label, uint8_t* labels, float* conf, int64_t* counts, void* stream);
 
+/* ---- rendering of label maps: colour masks, overlays, error maps, outlines, class counts in one pass (reference predict.py
+ * create_colored_mask / create_overlay / test_model's class distribution, train.py _log_predictions).  Per pixel of image i of
+ * n images [h][w], all tensors contiguous:
+ *   L   = labels[i][y][x]: uint8 (labels_i64 == 0) or int64 (== 1; a value outside [0, 255] is read as 255; 8-byte aligned)
+ *   c   = table[L], table uint8 [256][3] (the palette for L < classes, the void colour elsewhere: made by the caller)
+ *   b   = the base pixel (base_kind, UDASEG_RENDER_BASE_*): NONE (base NULL); U8, a uint8 frame [n][h][w][3]; F32 / BF16, the
+ *         model input, padded NHWC with 16-byte pixels ([n][h][w][4] fp32 / [n][h][w][8] bf16, 16-byte aligned), channel j
+ *         de-normalised as clip(rint(x * denorm[j] + denorm[3 + j]), 0, 255): an fp32 multiply, an fp32 add (not fused), round
+ *         half to even, NaN -> 0.  denorm: HOST float[6], std * 255 then mean * 255.
+ *   k   = 3 if truth is given and void (has_ignore and truth == ignore_index, or truth >= classes after the same int64 rule;
+ *         the comparison with ignore_index uses the raw int64 value), else 2 if truth is given and equals L, else 1 if
+ *         L >= classes, else 0.  truth: NULL or the dtype and shape of labels.
+ *   out = (b * (256 - alpha[k]) + c * alpha[k] + 128) >> 8 per channel in integers, alpha: HOST int32[4], each in [0, 256]
+ *         (0 returns b, 256 returns c); out = c without a base.
+ *   outline >= 0 (r | g << 8 | b << 16; -1: none): a pixel whose label differs from its left, right, upper or lower neighbour
+ *         INSIDE image i gets that colour instead (the frame's edge is no outline).
+ *   counts (NULL or int64 [n][256], ACCUMULATES): counts[i][L] += 1.  agreement (NULL or int64 [n][3], needs truth, ACCUMULATES):
+ *         += the pixels with truth == L / truth valid and != L / truth void.
+ * out: uint8 [n][h][w][3].  No operand needs more than its dtype's alignment beyond the two stated: labels, frame and output
+ * of an image that does not start on a 4-byte boundary are moved in bytes.  0 < n <= 65535, h * w < 2^31 - 4, 1 <= classes <= 256. */
+#define UDASEG_RENDER_BASE_NONE 0
+#define UDASEG_RENDER_BASE_U8 1
+#define UDASEG_RENDER_BASE_F32 2
+#define UDASEG_RENDER_BASE_BF16 3
+int udaseg_render_u8(const void* labels, const void* truth, int labels_i64, const void* base, int base_kind, const uint8_t* table,
+                     int n, int h, int w, int classes, int has_ignore, int ignore_index, const int32_t* alpha, const float* denorm,
+                     int outline, uint8_t* out, int64_t* counts, int64_t* agreement, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

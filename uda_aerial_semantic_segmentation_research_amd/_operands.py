@@ -335,6 +335,12 @@ OPERANDS = {
     "udaseg_pseudo_labels": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
                              T("thr_bins", i32, "classes"), I("void_label"), T("labels", u8, "pixels"), T("conf", f32, "pixels", True),
                              T("counts", i64, "classes+2"), S],
+    "udaseg_render_u8": [T("labels", "(i64 if labels_i64 else u8)", "n*h*w"), T("truth", "(i64 if labels_i64 else u8)", "n*h*w", True),
+                         I("labels_i64"), T("base", "(u8 if base_kind == 1 else (bf16 if base_kind == 3 else f32))",
+                                            "n*h*w*(3 if base_kind == 1 else (8 if base_kind == 3 else 4))", True), I("base_kind"),
+                         T("table", u8, 768), I("n"), I("h"), I("w"), I("classes"), I("has_ignore"), I("ignore_index"), H("alpha"),
+                         H("denorm"), I("outline"), T("out", u8, "n*h*w*3"), T("counts", i64, "n*256", True),
+                         T("agreement", i64, "n*3", True), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

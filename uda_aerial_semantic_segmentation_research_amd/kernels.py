@@ -120,6 +120,30 @@ def pseudo_labels(scores_base, pixels, classes, ldc, probs, bins, thr_bins, void
                                    counts, st), "pseudo_labels")
 
 
+RENDER_BASE_NONE, RENDER_BASE_U8, RENDER_BASE_F32, RENDER_BASE_BF16 = 0, 1, 2, 3
+_RENDER_HOST = {}
+
+
+def render_u8(labels, truth, base, table, n, h, w, classes, ignore_index, alpha, denorm, outline, out, counts, agreement, st=None):
+    """out [n,h,w,3] uint8 = the rendering of labels [n,h,w] (uint8 or int64; truth None or alike) over base (None, a uint8
+    [n,h,w,3] frame or the padded fp32 [n,h,w,4] / bf16 [n,h,w,8] model input: the kind follows its dtype).  table: uint8 [256,3]
+    on the device; alpha: four integers in [0, 256]; denorm: six floats (std * 255, mean * 255) or None; ignore_index: an int or
+    None; outline: r | g << 8 | b << 16 or -1; counts [n,256] / agreement [n,3] int64 or None (they accumulate)."""
+    kind = RENDER_BASE_NONE if base is None else {torch.uint8: RENDER_BASE_U8, torch.float32: RENDER_BASE_F32,
+                                                   torch.bfloat16: RENDER_BASE_BF16}.get(getattr(base, "dtype", None), RENDER_BASE_F32)
+    key = (tuple(alpha), None if denorm is None else tuple(denorm))
+    host = _RENDER_HOST.get(key)
+    if host is None:                         # the two small host arrays of a call are kept: callers render with the same few tables
+        if len(_RENDER_HOST) > 256:
+            _RENDER_HOST.clear()
+        host = _RENDER_HOST[key] = ((_lib.C.c_int32 * 4)(*[int(v) for v in key[0]]),
+                                    None if denorm is None else (_lib.C.c_float * 6)(*[float(v) for v in key[1]]))
+    a4, d6 = host
+    check(ops.udaseg_render_u8(labels, truth, int(getattr(labels, "dtype", None) == torch.int64), base, kind, table, n, h, w, classes,
+                               int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), a4, d6, outline, out,
+                               counts, agreement, st), "render_u8")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,

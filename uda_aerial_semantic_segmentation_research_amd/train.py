@@ -111,6 +111,8 @@ class SegmentationTrainer:
         self.current_epoch = 0
         self.log_curves = False           # per-class ROC / PR curves, AUC and AP every Config.LOG_INTERVAL batches (reference :374-379)
         self.last_curves = {}             # prefix ('train' / 'val') -> the curves.curves_from_hist dict of the last logging call
+        self.log_predictions = False      # image / ground truth / prediction / overlay of the batch's first sample, same schedule (reference _log_predictions)
+        self.last_renders = {}            # 'image' / 'ground_truth' / 'prediction' / 'overlay' -> uint8 [H,W,3] on the device, of the last logging call
 
     def calculate_metrics(self, outputs, masks):
         """Per-batch IoU / accuracy / per-class IoU (same keys as the reference)."""
@@ -173,6 +175,27 @@ class SegmentationTrainer:
         ax.set_title(f"{prefix.capitalize()} Confusion Matrix")
         self.logger.log_figure(f"{prefix}/confusion_matrix", fig, step)
 
+    def _log_predictions(self, images, masks, outputs, step, prefix):
+        """The reference's ``_log_predictions`` with pictures made on the device (render.py): the first sample of the batch as
+        ``{prefix}/image`` (the model input de-normalised), ``/ground_truth`` and ``/prediction`` (colour masks, void labels in the
+        void colour) and ``/overlay`` (the prediction's colours over the image at 0.5), each handed to ``logger.log_image`` as a uint8
+        ``[3,H,W]`` device tensor; the ``[H,W,3]`` pictures stay on ``self.last_renders``."""
+        from . import kernels as K, render
+        from .predict import _logits_nhwc
+        k = self.num_classes
+        logits = outputs[:1]
+        _, c, h, w = logits.shape
+        buf, ldc = _logits_nhwc(logits)
+        pred = torch.empty((1, h, w), dtype=torch.int64, device=buf.device)
+        K.predict_finish(buf, None, h * w, c, ldc, pred)
+        pics = {"image": render.overlay(images[:1], pred, alpha=0.0, classes=k),
+                "ground_truth": render.colorize(masks[:1], classes=k),
+                "prediction": render.colorize(pred, classes=k),
+                "overlay": render.overlay(images[:1], pred, alpha=0.5, classes=k)}
+        self.last_renders = {name: p[0] for name, p in pics.items()}
+        for name, p in self.last_renders.items():
+            self.logger.log_image(f"{prefix}/{name}", p.permute(2, 0, 1), step)
+
     def train_step(self, images, masks, optimizer):
         """The timed hot path: reference train.py:340-344.  Returns (loss tensor, logits), no host sync."""
         optimizer.zero_grad()
@@ -204,6 +227,9 @@ class SegmentationTrainer:
             if self.log_curves and batch_idx % Config.LOG_INTERVAL == 0:
                 with torch.no_grad():
                     self._log_curves(outputs.detach(), masks, (epoch - 1) * len(dataloader) + batch_idx, "train")
+            if self.log_predictions and batch_idx % Config.LOG_INTERVAL == 0:
+                with torch.no_grad():
+                    self._log_predictions(images, masks, outputs.detach(), (epoch - 1) * len(dataloader) + batch_idx, "train")
         return total_loss / len(dataloader)
 
     def validate(self, dataloader):
@@ -225,6 +251,8 @@ class SegmentationTrainer:
                         self.logger.log_scalar(f"val/iou_class_{c}", metrics[f"iou_class_{c}"], self.current_epoch)
                     if self.log_curves:
                         self._log_curves(outputs, masks, self.current_epoch, "val")
+                    if self.log_predictions:
+                        self._log_predictions(images, masks, outputs, self.current_epoch, "val")
         avg = {"loss": total_loss / len(dataloader),
                "iou": float(np.mean([m["iou"] for m in all_metrics])),
                "accuracy": float(np.mean([m["accuracy"] for m in all_metrics]))}
