@@ -1314,13 +1314,16 @@ static int halo_cfg_override() {
 }
 
 // Can this convolution take the halo kernel?  gathered / produced: channel counts of the launch (for a data gradient: co / ci).
-bool halo_applicable(const udaseg_conv_desc* d, int gathered, int produced, int up_ca) {
+bool halo_applicable(const udaseg_conv_desc* d, int gathered, int produced, int up_ca, bool dgrad = false) {
   if (opt_get(UDASEG_OPT_NO_HALO)) return false;   // 1: keep every layer on the shared implicit-GEMM source (A/B, cross-check)
   if (d->kh == 4 && d->kw == 4 && d->stride == 2 && d->pad == 1) {
     // the discriminator's convolutions, as 2 x 2 windows over parity phases (forward) / parity classes (data gradient)
     const int s2off = opt_get(UDASEG_OPT_NO_HALO_S2);   // 1: they stay on the shared implicit-GEMM source (A/B)
     if (s2off || up_ca != 0 || d->hi % 2 != 0 || d->wi % 2 != 0 || d->ho * 2 != d->hi || d->wo * 2 != d->wi) return false;
     if (d->ci % 8 != 0 || d->co % 8 != 0 || (d->ci & (d->ci - 1)) != 0) return false;      // real input channels: a power of two
+    // the 2 x 2-window instances stage whole chunks of 32 channels: the forward gathers 4 ci of them, the data gradient co
+    // (launch_halo refuses anything else; without this line the query said yes to a launch that then failed)
+    if (dgrad && d->co % 32 != 0) return false;
     const long long pin = (long long)d->n * d->hi * d->wi, pout = (long long)d->n * d->ho * d->wo;
     return pin * d->ci * 2 < (1LL << 31) && pout * d->co * 4 < (1LL << 31);
   }
@@ -1462,7 +1465,7 @@ extern "C" int udaseg_pack_frag_batched_bf16(const void* w16, const void* wt16, 
 
 extern "C" int udaseg_conv_frag_ok(const udaseg_conv_desc* d, int dgrad, int up_ca) {
   if (!d) return 0;
-  return halo_applicable(d, dgrad ? d->co : d->ci, dgrad ? d->ci : d->co, up_ca) ? 1 : 0;
+  return halo_applicable(d, dgrad ? d->co : d->ci, dgrad ? d->ci : d->co, up_ca, dgrad != 0) ? 1 : 0;
 }
 
 extern "C" int udaseg_conv_frag_preferred(const udaseg_conv_desc* d, int dgrad, int up_ca) {
@@ -1540,7 +1543,7 @@ extern "C" int udaseg_conv2d_dgrad_frag_bf16(const udaseg_conv_desc* d, const vo
                    "conv2d_dgrad_frag_bf16: the BatchNorm-backward reductions need mean / rstd / gamma / beta / bsums, no split, "
                    "no accumulation");
   UDASEG_CHECK_ARG(!(accumulate && split > 0), "conv2d_dgrad_frag_bf16: accumulation onto a split gradient is not supported");
-  if (!halo_applicable(d, d->co, d->ci, 0)) {
+  if (!halo_applicable(d, d->co, d->ci, 0, true)) {
     set_error("conv2d_dgrad_frag_bf16: geometry not supported (ask udaseg_conv_frag_ok first)");
     return UDASEG_E_UNSUPPORTED;
   }
