@@ -395,6 +395,31 @@ int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bins, const d
 int udaseg_pseudo_labels(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, const int32_t* thr_bins,
                          int void_label, uint8_t* labels, float* conf, int64_t* counts, void* stream);
 
+/* ---- cross-domain class mixing of a source and a target batch (DACS, Tranheden et al. 2021; ClassMix, Olsson et al. 2021; an
+ * extension, the reference has no counterpart).  Integers only: every output is exact.
+ * Selection, per source mask i, from the [n][256] table of udaseg_mask_hist_u8 (1 <= classes <= 32, min_pixels >= 1):
+ *   present = the ascending list of c in [0, classes) with hist[i][c] >= min_pixels, P = its length, k = (P + 1) / 2;
+ *   for j = 0 .. k-1:  r = word 0 of Philox4x32-10 with counter (j, 0, 0, 0) and key (keys[i][0], keys[i][1]) read as uint32,
+ *                      t = j + (int)(((uint64)r * (P - j)) >> 32), swap present[j] and present[t];
+ *   sel[i] = OR of 1 << present[j] for j < k, stored as the bit pattern of an int32 (bit 31 is class 31); P == 0 gives 0.
+ * One launch for all n samples; nothing is read back. */
+int udaseg_classmix_select(const int64_t* hist, int n, int classes, int64_t min_pixels, const int32_t* keys, int32_t* sel,
+                           void* stream);
+/* Mixing: src, tgt, out uint8 [n][h][w][3]; src_masks, tgt_masks (may be NULL), out_masks uint8 [n][h][w]; sel int32 [n]; boxes
+ * (may be NULL) int32 [n][4] = (y0, x0, y1, x1), 0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w, empty allowed; counts (may be NULL) int64
+ * [n][3].  Per sample i and pixel (y, x), with s = src_masks[i][y][x]:
+ *   m = (s < classes and (sel[i] >> s) & 1) or (boxes and y0 <= y < y1 and x0 <= x < x1)
+ *   out[i][y][x] = m ? src[i][y][x] : tgt[i][y][x] (three bytes);  out_masks[i][y][x] = m ? s : (tgt_masks ? tgt_masks[i][y][x]
+ *   : void_label);  counts[i] += {pixels with m, pixels without m whose output label is < classes, pixels without m whose output
+ *   label is >= classes}: int64 counters that ACCUMULATE across calls, the three add up to h * w per call.
+ * Refused (non-zero, nothing launched): classes outside 1..32, void_label outside classes..255, n, h or w <= 0, n*h*w >= 2^31,
+ * a required pointer NULL, an output range that overlaps an input range or another output.  Two forms with identical bytes,
+ * chosen per launch: 16 pixels per lane in 16-byte accesses when h * w % 16 == 0 and every frame and mask pointer is 16-byte
+ * aligned, one pixel per lane otherwise. */
+int udaseg_classmix_u8(const uint8_t* src, const uint8_t* src_masks, const uint8_t* tgt, const uint8_t* tgt_masks,
+                       const int32_t* sel, const int32_t* boxes, int n, int h, int w, int classes, int void_label, uint8_t* out,
+                       uint8_t* out_masks, int64_t* counts, void* stream);
+
 /* ---- rendering of label maps: colour masks, overlays, error maps, outlines, class counts in one pass (reference predict.py
  * create_colored_mask / create_overlay / test_model's class distribution, train.py _log_predictions).  Per pixel of image i of
  * n images [h][w], all tensors contiguous:

@@ -1,0 +1,284 @@
+"""CPU checks of the class-mixing module (mix.py): the host mirror of the selection rule against tests/_mix_ref.py and its
+invariants, the uniformity of the selection, the box draw, the decoding, every argument refusal, and the operand rows of the two
+entry points.  No GPU."""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import _mix_ref as R
+
+
+@pytest.fixture(scope="module")
+def M():
+    from uda_aerial_semantic_segmentation_research_amd import mix
+    return mix
+
+
+def _draw_keys(n, seed):
+    return torch.randint(0, 1 << 32, (n, 2), generator=torch.Generator().manual_seed(seed), dtype=torch.int64).numpy()
+
+
+def _hist_of(present_sets, count=10):
+    hist = np.zeros((len(present_sets), 256), dtype=np.int64)
+    for i, s in enumerate(present_sets):
+        hist[i, list(s)] = count
+    return hist
+
+
+# ------------------------------------------------------------------------------------------------------------- selection
+def test_selection_matches_the_mirror_and_its_invariants(M):
+    g = np.random.default_rng(0)
+    for classes in (1, 5, 23, 32):
+        n = 40
+        hist = g.integers(0, 4, size=(n, 256)).astype(np.int64)             # a third of the classes absent, labels >= classes too
+        hist[0] = 0                                                          # nothing present
+        hist[1, :classes] = 0
+        hist[1, classes - 1] = 7                                             # the top class alone
+        keys = _draw_keys(n, classes)
+        for min_pixels in (1, 3):
+            sel = M.selection_from_hist(hist, classes, keys, min_pixels)
+            assert sel.dtype == np.int32 and sel.shape == (n,)
+            assert np.array_equal(sel, R.select(hist, classes, keys, min_pixels))
+            for i in range(n):
+                present = [c for c in range(classes) if hist[i, c] >= min_pixels]
+                bits = int(sel[i]) & 0xFFFFFFFF
+                chosen = [c for c in range(32) if (bits >> c) & 1]
+                assert len(chosen) == (len(present) + 1) // 2 and set(chosen) <= set(present)
+                assert all(c < classes for c in chosen)
+            assert sel[0] == 0
+        assert M.selection_from_hist(hist, classes, keys)[1] == np.uint32(1 << (classes - 1)).view(np.int32)
+    # tensors and int32 bit patterns of the keys are taken alike
+    keys = _draw_keys(40, 5)
+    a = M.selection_from_hist(torch.from_numpy(hist), 32, torch.from_numpy(keys))
+    b = M.selection_from_hist(hist, 32, keys.astype(np.uint32).view(np.int32))
+    assert np.array_equal(a, b)
+
+
+def test_min_pixels_excludes_a_class_one_below_it(M):
+    hist = np.zeros((1, 256), dtype=np.int64)
+    hist[0, 2], hist[0, 4] = 9, 10
+    for seed in range(8):
+        keys = _draw_keys(1, seed)
+        assert M.decode_selection(M.selection_from_hist(hist, 5, keys, min_pixels=10), 5) == [[4]]
+        assert M.decode_selection(M.selection_from_hist(hist, 5, keys, min_pixels=11), 5) == [[]]
+        assert len(M.decode_selection(M.selection_from_hist(hist, 5, keys, min_pixels=9), 5)[0]) == 1
+
+
+def test_bit_31_is_a_class(M):
+    hist = _hist_of([{31}, set(range(32))])
+    sel = M.selection_from_hist(hist, 32, _draw_keys(2, 0))
+    assert sel[0] == np.iinfo(np.int32).min and M.decode_selection(sel, 32)[0] == [31]
+    assert len(M.decode_selection(sel, 32)[1]) == 16
+    assert any(31 in M.decode_selection(M.selection_from_hist(hist[1:], 32, _draw_keys(1, seed)), 32)[0]
+               for seed in range(16))                                        # the top bit is reachable through the shuffle as well
+    assert M.selection_from_hist(hist[:1], 31, _draw_keys(1, 0))[0] == 0     # and no class at classes = 31
+
+
+@pytest.mark.parametrize("present", [(0, 2, 3, 7, 22), (1, 4), tuple(range(23)), tuple(range(32))], ids=["five", "two", "23", "32"])
+def test_selection_is_uniform_over_the_present_classes(M, present):
+    """4096 keys from seed 0: every present class is selected with frequency within 5 standard deviations of k / P, sd =
+    sqrt(p (1 - p) / 4096).  The rule as specified stays at 1.03, 0.06, 1.66 and 2.91 sd for the four sets."""
+    n = 4096
+    classes = 32 if max(present) >= 23 else 23
+    keys = _draw_keys(n, 0)
+    hist = _hist_of([present] * n)
+    sel = M.selection_from_hist(hist, classes, keys).view(np.uint32)
+    P = len(present)
+    k = (P + 1) // 2
+    p = k / P
+    sd = math.sqrt(p * (1.0 - p) / n)
+    worst = 0.0
+    for c in range(32):
+        freq = float(((sel >> np.uint32(c)) & np.uint32(1)).mean())
+        if c in present:
+            worst = max(worst, abs(freq - p) / sd)
+        else:
+            assert freq == 0.0
+    print(f"present={present[:3]}.. P={P} k={k}: worst deviation {worst:.2f} sd")
+    assert worst <= 5.0
+
+
+# ------------------------------------------------------------------------------------------------------------- boxes
+@pytest.mark.parametrize("h,w", [(1, 1), (7, 7), (512, 512), (1, 512), (7, 512)])
+def test_draw_boxes(M, h, w):
+    n, share = 256, (0.25, 0.5)
+    boxes = M.draw_boxes(n, h, w, torch.Generator().manual_seed(3), share)
+    assert boxes.dtype == torch.int32 and tuple(boxes.shape) == (n, 4) and not boxes.is_cuda
+    assert torch.equal(boxes, M.draw_boxes(n, h, w, torch.Generator().manual_seed(3), share))       # deterministic per seed
+    assert not torch.equal(boxes, M.draw_boxes(n, h, w, torch.Generator().manual_seed(4), share)) or h * w == 1
+    b = boxes.numpy().astype(np.int64)
+    y0, x0, y1, x1 = b.T
+    assert (0 <= y0).all() and (y0 < y1).all() and (y1 <= h).all() and (0 <= x0).all() and (x0 < x1).all() and (x1 <= w).all()
+    # the rounding rule: each side is the rounded ideal side unless the frame or the 1-pixel floor clamps it
+    u = torch.rand(n, 4, generator=torch.Generator().manual_seed(3), dtype=torch.float64).numpy()
+    a = share[0] + u[:, 0] * (share[1] - share[0])
+    r = np.exp((2.0 * u[:, 1] - 1.0) * math.log(2.0))
+    for side, ideal, full in ((y1 - y0, np.sqrt(a * h * w * r), h), (x1 - x0, np.sqrt(a * h * w / r), w)):
+        free = (ideal >= 1.0) & (ideal <= full)
+        assert (np.abs(side - ideal)[free] <= 0.5).all()
+        assert (side[ideal > full] == full).all() and (side[ideal < 1.0] == 1).all()
+    if h == w == 512:                                                        # nothing clamps: the area share follows
+        area = (y1 - y0) * (x1 - x0) / float(h * w)
+        ideal_h, ideal_w = np.sqrt(a * h * w * r), np.sqrt(a * h * w / r)
+        slack = (0.5 * (ideal_h + ideal_w) + 0.25) / float(h * w)
+        assert (np.abs(area - a) <= slack).all() and area.min() >= share[0] - slack.max() and area.max() <= share[1] + slack.max()
+    # the origin rule: floor(u * (free positions))
+    assert np.array_equal(y0, np.floor(u[:, 2] * (h - (y1 - y0) + 1)).astype(np.int64))
+    assert np.array_equal(x0, np.floor(u[:, 3] * (w - (x1 - x0) + 1)).astype(np.int64))
+
+
+def test_decode_selection_round_trip(M):
+    g = np.random.default_rng(1)
+    for classes in (1, 5, 23, 32):
+        lists = [sorted(set(g.integers(0, classes, size=g.integers(0, classes + 1)).tolist())) for _ in range(20)]
+        sel = np.array([sum(1 << c for c in cl) for cl in lists], dtype=np.uint32).view(np.int32)
+        assert M.decode_selection(sel, classes) == lists
+        assert M.decode_selection(torch.from_numpy(sel), classes) == lists
+    assert M.decode_selection(np.array([-1], dtype=np.int32), 5) == [[0, 1, 2, 3, 4]]       # bits above the classes are not classes
+
+
+# ------------------------------------------------------------------------------------------------------------- refusals
+def test_refusals(M):
+    hist, keys = np.zeros((2, 256), dtype=np.int64), np.zeros((2, 2), dtype=np.int64)
+    for bad in (0, 33, -1, 2.5):
+        with pytest.raises(ValueError, match="num_classes"):
+            M.selection_from_hist(hist, bad, keys)
+        with pytest.raises(ValueError, match="num_classes"):
+            M.decode_selection(np.zeros(1, dtype=np.int32), bad)
+        with pytest.raises(ValueError, match="num_classes"):
+            M.MixedLoader([], [], bad)
+    for bad in (0, -3, 1.5):
+        with pytest.raises(ValueError, match="min_pixels"):
+            M.selection_from_hist(hist, 5, keys, min_pixels=bad)
+        with pytest.raises(ValueError, match="min_pixels"):
+            M.MixedLoader([], [], 5, min_pixels=bad)
+        with pytest.raises(ValueError, match="min_pixels"):
+            M.select_classes(torch.zeros(1, 2, 2, dtype=torch.uint8), 5, min_pixels=bad)
+    for bad in (np.zeros((2, 255), dtype=np.int64), np.zeros(256, dtype=np.int64), np.zeros((2, 256), dtype=np.float32)):
+        with pytest.raises(ValueError, match="hist"):
+            M.selection_from_hist(bad, 5, keys)
+    for bad in (np.zeros((3, 2), dtype=np.int64), np.zeros((2, 3), dtype=np.int64), np.zeros((2, 2), dtype=np.float64)):
+        with pytest.raises(ValueError, match="keys"):
+            M.selection_from_hist(hist, 5, bad)
+    with pytest.raises(ValueError, match="sel"):
+        M.decode_selection(np.zeros((2, 2), dtype=np.int32), 5)
+    for bad in ((0.0, 0.5), (0.5, 0.25), (0.25, 1.5), (0.5,), 0.3):
+        with pytest.raises(ValueError, match="share"):
+            M.draw_boxes(2, 8, 8, None, bad)
+        with pytest.raises(ValueError, match="share"):
+            M.MixedLoader([], [], 5, share=bad)
+    for kw in (dict(n=0, h=8, w=8), dict(n=2, h=0, w=8), dict(n=2, h=8, w=-1)):
+        with pytest.raises(ValueError):
+            M.draw_boxes(**kw)
+    for bad in (4, 256, -1):
+        with pytest.raises(ValueError, match="void"):
+            M.MixedLoader([], [], 5, void=bad)
+    with pytest.raises(ValueError, match="mode"):
+        M.MixedLoader([], [], 5, mode="cut")
+    # dtypes and shapes of the device calls: refused before anything touches the GPU
+    with pytest.raises(ValueError, match="uint8"):
+        M.select_classes(torch.zeros(1, 2, 2, dtype=torch.int64), 5)
+    with pytest.raises(ValueError, match="dimensions"):
+        M.select_classes(torch.zeros(2, 2, dtype=torch.uint8), 5)
+    with pytest.raises(ValueError, match="keys"):
+        M.select_classes(torch.zeros(1, 2, 2, dtype=torch.uint8), 5, keys=np.zeros((2, 2), dtype=np.int64))
+    f = torch.zeros(2, 4, 6, 3, dtype=torch.uint8)
+    m = torch.zeros(2, 4, 6, dtype=torch.uint8)
+    sel = torch.zeros(2, dtype=torch.int32)
+    good = dict(src_frames=f, src_masks=m, tgt_frames=f.clone(), tgt_masks=m.clone(), sel=sel, num_classes=5)
+    for bad in (dict(src_frames=f.float()), dict(src_frames=f[..., :2]), dict(src_frames=f[0]), dict(tgt_frames=f[:1]),
+                dict(tgt_frames=f.long()), dict(src_masks=m[:, :3]), dict(src_masks=m.long()), dict(tgt_masks=m[:1]),
+                dict(tgt_masks=m.int()), dict(sel=sel.long()), dict(sel=sel[:1]), dict(sel=[0, 0]),
+                dict(boxes=torch.zeros(2, 4, dtype=torch.int64)), dict(boxes=torch.zeros(2, 3, dtype=torch.int32)),
+                dict(boxes=torch.tensor([[0, 0, 5, 6], [0, 0, 4, 6]], dtype=torch.int32)),          # y1 > h
+                dict(boxes=torch.tensor([[2, 0, 1, 6], [0, 0, 4, 6]], dtype=torch.int32)),          # y0 > y1
+                dict(boxes=torch.tensor([[0, -1, 4, 6], [0, 0, 4, 6]], dtype=torch.int32)),         # x0 < 0
+                dict(num_classes=0), dict(num_classes=33), dict(num_classes=None), dict(void=4), dict(void=256)):
+        with pytest.raises(ValueError):
+            M.class_mix(**{**good, **bad})
+    # loaders: refused at the first batch, before the device is asked for
+    src = [(f, m)]
+    for tgt in ([(torch.zeros(2, 4, 5, 3, dtype=torch.uint8), torch.zeros(2, 4, 5, dtype=torch.uint8))],       # another W
+                [torch.zeros(2, 5, 6, 3, dtype=torch.uint8)],                                                  # another H
+                [(f, torch.zeros(2, 4, 6, dtype=torch.int64))], [f.float()]):
+        with pytest.raises(ValueError):
+            next(iter(_HostOnly(M.MixedLoader(src, tgt, 5))))
+    with pytest.raises(ValueError):
+        next(iter(_HostOnly(M.MixedLoader([f], [f], 5))))                    # source batches carry masks
+    assert len(M.MixedLoader([1, 2, 3], [1, 2], 5)) == 2
+
+
+class _HostOnly:
+    """Iterates a MixedLoader with the device query stubbed out: the argument checks of a batch come before any GPU work."""
+
+    def __init__(self, loader):
+        self.loader = loader
+
+    def __iter__(self):
+        from uda_aerial_semantic_segmentation_research_amd import mix
+        saved = mix._device
+        mix._device = lambda: torch.device("cpu")
+        try:
+            yield from self.loader
+        finally:
+            mix._device = saved
+
+
+# ------------------------------------------------------------------------------------------------------------- operand rows
+def test_operand_rows(M):
+    from uda_aerial_semantic_segmentation_research_amd import _lib, _operands as O, kernels as K
+    assert callable(K.classmix_select) and callable(K.classmix_u8)
+    rows = {e: O.OPERANDS[e] for e in ("udaseg_classmix_select", "udaseg_classmix_u8")}
+    for e, roles in rows.items():
+        assert len(roles) == len(_lib.SIGNATURES[e][1]) and _lib.SIGNATURES[e][0] is ctypes.c_int
+    opt = {e: {r[1]: r[4] for r in roles if r[0] == "tensor"} for e, roles in rows.items()}
+    assert opt["udaseg_classmix_select"] == {"hist": False, "keys": False, "sel": False}
+    assert opt["udaseg_classmix_u8"] == {"src": False, "src_masks": False, "tgt": False, "tgt_masks": True, "sel": False, "boxes": True,
+                                         "out": False, "out_masks": False, "counts": True}
+    n, h, w = 3, 5, 7
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in O.requirements("udaseg_classmix_select", None, n, 23, 1, None, None, 0)}
+    assert req == {"hist": (torch.int64, n * 256), "keys": (torch.int32, n * 2), "sel": (torch.int32, n)}
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in
+           O.requirements("udaseg_classmix_u8", None, None, None, None, None, None, n, h, w, 23, 255, None, None, None, 0)}
+    px = n * h * w
+    assert req == {"src": (torch.uint8, px * 3), "src_masks": (torch.uint8, px), "tgt": (torch.uint8, px * 3),
+                   "tgt_masks": (torch.uint8, px), "sel": (torch.int32, n), "boxes": (torch.int32, n * 4),
+                   "out": (torch.uint8, px * 3), "out_masks": (torch.uint8, px), "counts": (torch.int64, n * 3)}
+
+
+def test_library_refuses_bad_arguments_before_any_launch():
+    """The C entry points return an error code and launch nothing (no GPU here): the ranges of the scalars, NULL pointers, and an
+    output range that overlaps an input range."""
+    from uda_aerial_semantic_segmentation_research_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(1 << 16)
+    a = ctypes.addressof(buf)
+    hist, keys, sel = a, a + 8192, a + 9000
+    assert lib.udaseg_classmix_select(None, 2, 5, 1, keys, sel, None) != 0
+    assert lib.udaseg_classmix_select(hist, 0, 5, 1, keys, sel, None) != 0
+    assert lib.udaseg_classmix_select(hist, 2, 0, 1, keys, sel, None) != 0
+    assert lib.udaseg_classmix_select(hist, 2, 33, 1, keys, sel, None) != 0
+    assert lib.udaseg_classmix_select(hist, 2, 5, 0, keys, sel, None) != 0 and b"min_pixels" in lib.udaseg_last_error()
+    assert lib.udaseg_classmix_select(hist, 2, 5, 1, keys, keys + 4, None) != 0 and b"overlaps" in lib.udaseg_last_error()
+    n, h, w = 2, 4, 4                                                        # 96-byte frames, 32-byte masks
+    src, sm, tgt, tm, out, om, selp, boxes, counts = (a + 1024 * i for i in range(9))
+    good = [src, sm, tgt, tm, selp, boxes, n, h, w, 5, 255, out, om, counts, None]
+
+    def call(**kw):
+        names = ["src", "src_masks", "tgt", "tgt_masks", "sel", "boxes", "n", "h", "w", "classes", "void_label", "out", "out_masks",
+                 "counts", "stream"]
+        args = list(good)
+        for k, v in kw.items():
+            args[names.index(k)] = v
+        return lib.udaseg_classmix_u8(*args)
+
+    for kw in (dict(src=None), dict(src_masks=None), dict(tgt=None), dict(sel=None), dict(out=None), dict(out_masks=None),
+               dict(n=0), dict(h=0), dict(w=-1), dict(n=1 << 11, h=1 << 10, w=1 << 10), dict(classes=0), dict(classes=33),
+               dict(void_label=4), dict(void_label=256),
+               dict(out=src), dict(out=tgt + 95), dict(out_masks=tm + 31), dict(out_masks=sm), dict(out=selp - 90), dict(counts=boxes + 8),
+               dict(out_masks=out + 95), dict(counts=om)):
+        assert call(**kw) != 0, kw
+        assert lib.udaseg_last_error()

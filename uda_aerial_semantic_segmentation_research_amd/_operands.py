@@ -335,6 +335,11 @@ OPERANDS = {
     "udaseg_pseudo_labels": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
                              T("thr_bins", i32, "classes"), I("void_label"), T("labels", u8, "pixels"), T("conf", f32, "pixels", True),
                              T("counts", i64, "classes+2"), S],
+    "udaseg_classmix_select": [T("hist", i64, "n*256"), I("n"), I("classes"), I("min_pixels"), T("keys", i32, "n*2"), T("sel", i32, "n"), S],
+    "udaseg_classmix_u8": [T("src", u8, "n*h*w*3"), T("src_masks", u8, "n*h*w"), T("tgt", u8, "n*h*w*3"),
+                           T("tgt_masks", u8, "n*h*w", True), T("sel", i32, "n"), T("boxes", i32, "n*4", True), I("n"), I("h"), I("w"),
+                           I("classes"), I("void_label"), T("out", u8, "n*h*w*3"), T("out_masks", u8, "n*h*w"),
+                           T("counts", i64, "n*3", True), S],
     "udaseg_render_u8": [T("labels", "(i64 if labels_i64 else u8)", "n*h*w"), T("truth", "(i64 if labels_i64 else u8)", "n*h*w", True),
                          I("labels_i64"), T("base", "(u8 if base_kind == 1 else (bf16 if base_kind == 3 else f32))",
                                             "n*h*w*(3 if base_kind == 1 else (8 if base_kind == 3 else 4))", True), I("base_kind"),

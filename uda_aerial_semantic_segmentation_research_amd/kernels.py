@@ -120,6 +120,19 @@ def pseudo_labels(scores_base, pixels, classes, ldc, probs, bins, thr_bins, void
                                    counts, st), "pseudo_labels")
 
 
+def classmix_select(hist, n, classes, min_pixels, keys, sel, st=None):
+    """sel [n] int32 = the class selection of every source mask from its row of the [n,256] int64 mask histogram and its Philox
+    key (keys [n,2] int32 bit patterns): half of the present classes, rounded up (mix.py's module docstring has the rule)."""
+    check(ops.udaseg_classmix_select(hist, n, classes, min_pixels, keys, sel, st), "classmix_select")
+
+
+def classmix_u8(src, src_masks, tgt, tgt_masks, sel, boxes, n, h, w, classes, void_label, out, out_masks, counts, st=None):
+    """out [n,h,w,3] / out_masks [n,h,w] uint8 = the source where its class is selected (or inside the sample's box), the target
+    (tgt_masks None: void_label) elsewhere; counts [n,3] int64 or None += pasted, kept target labels, void."""
+    check(ops.udaseg_classmix_u8(src, src_masks, tgt, tgt_masks, sel, boxes, n, h, w, classes, void_label, out, out_masks, counts, st),
+          "classmix_u8")
+
+
 RENDER_BASE_NONE, RENDER_BASE_U8, RENDER_BASE_F32, RENDER_BASE_BF16 = 0, 1, 2, 3
 _RENDER_HOST = {}
 
