@@ -491,6 +491,19 @@ int udaseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t count
 int udaseg_sumsq_f32(const float* g, int64_t count, double* partials, double* out, int accumulate, void* stream);
 int udaseg_scale_by_clip_f32(float* g, int64_t count, const double* sumsq, float max_norm, float eps, void* stream);
 
+/* ---- mean teacher (Tarvainen & Valpola 2017): t[i] <- t[i] + (1 - decay) * (s[i] - t[i]) over two flat fp32 arrays in one
+ *      streaming pass of 12 B per element.  Arithmetic contract: w = (float)(1.0 - decay), formed in double and rounded once;
+ *      d = s[i] - t[i] in fp32; t[i] = fmaf(w, d, t[i]) (fused: one rounding of the result).  decay == 0 is a copy, t[i] = s[i]
+ *      bit for bit; decay == 1 leaves t unchanged; where s[i] == t[i] the element keeps its bits; zero padding lanes of both
+ *      arrays therefore stay zero.  0 <= decay <= 1, anything else (a NaN included) is UDASEG_E_BADARG.
+ *      dist2 (may be NULL): *dist2 (= or +=, by `accumulate`) the fp64 sum of ((double)s[i] - (double)t_new[i])^2 of the same
+ *      pass, combined in a fixed order as udaseg_sumsq_f32 combines its sum (same bits on every run); partials: that entry
+ *      point's UDASEG_SUMSQ_PARTIALS + 1 doubles of scratch under the same rules, required only with dist2.
+ *      t, s: 4-byte aligned; 16-byte vector loads and stores when both are 16-byte aligned, the scalar form otherwise;
+ *      overlapping ranges are UDASEG_E_BADARG. ---- */
+int udaseg_ema_flat(float* t, const float* s, int64_t count, double decay, double* partials, double* dist2, int accumulate,
+                    void* stream);
+
 /* ---- strong augmentation of the phase-3 step (src/models/augmentation.py:40-88, applied per image on the host at
  *      src/models/unsupervised_trainer.py:100-114): uint8 RGB frames [n][h][w][3] + one parameter record per (view, sample)
  *      -> `views` (1 or 2) normalised, channel-padded NHWC model inputs [views][n][h][w][cpad].  The pipeline (D4, Gaussian

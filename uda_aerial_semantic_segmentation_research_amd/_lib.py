@@ -127,6 +127,7 @@ SIGNATURES = {
     "udaseg_adam_flat": (_I, [_P, _P, _P, _P, _L, _F, C.c_double, C.c_double, _F, _F, _F, _P]),
     "udaseg_sumsq_f32": (_I, [_P, _L, _P, _P, _I, _P]),
     "udaseg_scale_by_clip_f32": (_I, [_P, _L, _P, _F, _F, _P]),
+    "udaseg_ema_flat": (_I, [_P, _P, _L, C.c_double, _P, _P, _I, _P]),
     "udaseg_strong_aug_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_philox4x32_debug": (_I, [_P, _P, _P, _I, _P]),
     "udaseg_train_aug_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P]),

@@ -405,6 +405,8 @@ OPERANDS = {
                          F("beta1"), F("beta2"), F("eps"), F("bc1"), F("bc2"), S],
     "udaseg_sumsq_f32": [T("g", f32, "count"), I("count"), T("partials", f64, 257), T("out", f64, 1), I("accumulate"), S],
     "udaseg_scale_by_clip_f32": [T("g", f32, "count"), I("count"), T("sumsq", f64, 1), F("max_norm"), F("eps"), S],
+    "udaseg_ema_flat": [T("t", f32, "count"), T("s", f32, "count"), I("count"), F("decay"), T("partials", f64, 257, True),
+                        T("dist2", f64, 1, True), I("accumulate"), S],
     "udaseg_fill_f32": [T("p", f32, "count"), I("count"), F("value"), S],
     "udaseg_axpy_f32": [T("y", f32, "count"), T("x", f32, "count"), I("count"), F("alpha"), S],
     "udaseg_add_i64": [T("p", i64, "count"), I("count"), I("value"), S],

@@ -72,6 +72,8 @@ class AdversarialTrainer(SegmentationTrainer):
         if self.grad_reducer is not None:
             self.grad_reducer.finish()
         optimizer.step()
+        if self.teacher is not None:
+            self.teacher.update()
         return seg_loss, d_loss, adv_loss, total
 
     # ------------------------------------------------------------------------------------------------------ epochs

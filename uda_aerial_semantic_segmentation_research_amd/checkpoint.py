@@ -32,21 +32,24 @@ def save_training_checkpoint(directory, epoch, model, optimizer, metrics, improv
     return path
 
 
-def save_phase_checkpoint(directory, model, metrics, phase, discriminator=None, is_best=False):
+def save_phase_checkpoint(directory, model, metrics, phase, discriminator=None, is_best=False, teacher=None):
+    """``teacher``: a ``teacher.MeanTeacher``; adds the one key ``teacher_state_dict`` (an extension: upstream has no teacher)."""
     if phase not in PHASES:
         raise ValueError(f"phase must be one of {PHASES}, got {phase!r}")
     payload = {"model_state_dict": dense_state_dict(model), "metrics": metrics, "phase": phase,
                "timestamp": datetime.datetime.now().isoformat()}
     if phase in PHASES[1:] and discriminator is not None:
         payload["discriminator_state_dict"] = dense_state_dict(discriminator)
+    if teacher is not None:
+        payload["teacher_state_dict"] = teacher.state_dict()
     path = Path(directory) / ("best_model.pth" if is_best else "latest_model.pth")
     path.parent.mkdir(parents=True, exist_ok=True)
     torch.save(payload, path)
     return path
 
 
-def load_phase_checkpoint(directory, model, load_best=True, discriminator=None, map_location="cpu"):
-    """Returns the checkpoint dict (model -- and discriminator, when given and present -- already loaded), or None when the
+def load_phase_checkpoint(directory, model, load_best=True, discriminator=None, map_location="cpu", teacher=None):
+    """Returns the checkpoint dict (model -- and discriminator / teacher, when given and present -- already loaded), or None when the
     file does not exist, like upstream."""
     path = Path(directory) / ("best_model.pth" if load_best else "latest_model.pth")
     if not path.exists():
@@ -55,4 +58,6 @@ def load_phase_checkpoint(directory, model, load_best=True, discriminator=None, 
     model.load_state_dict(ckpt["model_state_dict"])
     if discriminator is not None and "discriminator_state_dict" in ckpt:
         discriminator.load_state_dict(ckpt["discriminator_state_dict"])
+    if teacher is not None and "teacher_state_dict" in ckpt:
+        teacher.load_state_dict(ckpt["teacher_state_dict"])
     return ckpt

@@ -8,6 +8,7 @@ Design (MI355X-first):
 * a network's forward/backward is an explicit plan of C-ABI kernel launches behind a single ``autograd.Function``
   (no per-op autograd graph, no per-op allocator traffic beyond activations).
 """
+import copy
 import math
 import os
 import weakref
@@ -430,6 +431,16 @@ class ArenaModule(nn.Module):
             torch.tensor(rows, dtype=torch.int32, device=device) if rows else None for rows in tables.values())
         if tables["frag_fwd"]:
             self._frag_arena = torch.empty(foff, device=device, dtype=torch.bfloat16)
+
+    # what a network carries besides its values: scratch of the last step (rebuilt by build_arena or by the next backward) and the
+    # data-parallel hook (a subclass's attribute); a new scratch arena belongs in this list
+    _NOT_CLONED = ("_grad_arena", "_wt_arena", "_frag_arena", "_last_tape", "grad_ready_hook")
+
+    def clone_network(self):
+        """A deep copy of this network's modules and values laid into arenas of its own (registered with ``arena_owner``), without
+        the scratch and the hook of ``_NOT_CLONED``: what teacher.MeanTeacher starts from."""
+        memo = {id(v): None for v in (getattr(self, k, None) for k in self._NOT_CLONED) if v is not None}
+        return copy.deepcopy(self, memo).build_arena()
 
     def _arena_ok(self, full=True):
         if self._arena is None:

@@ -854,6 +854,12 @@ def adam_flat(p, g, m, v, count, lr, beta1, beta2, eps, bc1, bc2, st=None):
                                         bc1, bc2, st), "adam_flat")
 
 
+def ema_flat(t, s, count, decay, partials=None, dist2=None, accumulate=False, st=None):
+    """t <- t + (1 - decay) * (s - t) over ``count`` fp32 elements (include/udaseg.h: decay 0 copies, 1 keeps; fused multiply-add);
+    with ``dist2`` (0-dim fp64, and the 257-double ``partials`` scratch of ``sumsq_f32``) also the squared distance |s - t_new|^2."""
+    check(ops.udaseg_ema_flat(t, s, count, float(decay), partials, dist2, int(accumulate), st), "ema_flat")
+
+
 def fill(t, value, st=None):
     check(ops.udaseg_fill_f32(t, t.numel(), value, st), "fill_f32")
 

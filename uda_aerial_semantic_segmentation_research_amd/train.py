@@ -113,6 +113,7 @@ class SegmentationTrainer:
         self.last_curves = {}             # prefix ('train' / 'val') -> the curves.curves_from_hist dict of the last logging call
         self.log_predictions = False      # image / ground truth / prediction / overlay of the batch's first sample, same schedule (reference _log_predictions)
         self.last_renders = {}            # 'image' / 'ground_truth' / 'prediction' / 'overlay' -> uint8 [H,W,3] on the device, of the last logging call
+        self.teacher = None               # teacher.MeanTeacher: updated right after every optimiser step of the segmenter
 
     def calculate_metrics(self, outputs, masks):
         """Per-batch IoU / accuracy / per-class IoU (same keys as the reference)."""
@@ -196,6 +197,11 @@ class SegmentationTrainer:
         for name, p in self.last_renders.items():
             self.logger.log_image(f"{prefix}/{name}", p.permute(2, 0, 1), step)
 
+    def _log_teacher(self, step):
+        """``train/teacher_decay`` (the decay of the last update) and ``train/teacher_distance`` (|student - teacher| after it)."""
+        self.logger.log_scalar("train/teacher_decay", self.teacher.decay_at(self.teacher.step - 1), step)
+        self.logger.log_scalar("train/teacher_distance", float(self.teacher.distance()), step)
+
     def train_step(self, images, masks, optimizer):
         """The timed hot path: reference train.py:340-344.  Returns (loss tensor, logits), no host sync."""
         optimizer.zero_grad()
@@ -205,6 +211,8 @@ class SegmentationTrainer:
         if self.grad_reducer is not None:
             self.grad_reducer.finish()
         optimizer.step()
+        if self.teacher is not None:
+            self.teacher.update()
         return loss, outputs
 
     def train_epoch(self, dataloader, optimizer, epoch):
@@ -224,6 +232,8 @@ class SegmentationTrainer:
                 self.logger.log_scalar("train/iou", metrics["iou"], step)
                 self.logger.log_scalar("train/accuracy", metrics["accuracy"], step)
                 self.logger.log_scalar("train/learning_rate", optimizer.param_groups[0]["lr"], step)
+                if self.teacher is not None and batch_idx % Config.LOG_INTERVAL == 0:
+                    self._log_teacher(step)
             if self.log_curves and batch_idx % Config.LOG_INTERVAL == 0:
                 with torch.no_grad():
                     self._log_curves(outputs.detach(), masks, (epoch - 1) * len(dataloader) + batch_idx, "train")

@@ -135,6 +135,8 @@ class UnsupervisedTrainer(SegmentationTrainer):
         self.last_grad_norm = clip_grad_norm_(model.parameters(), self.max_grad_norm)
         mark("adam")
         optimizer.step()
+        if self.teacher is not None:
+            self.teacher.update()
         mark("end")
         if update_metrics:
             verdict = torch.sigmoid(domain_pred.detach())
@@ -169,6 +171,8 @@ class UnsupervisedTrainer(SegmentationTrainer):
                     self.logger.log_scalar(f"train/loss_{k}", v, step)
                 for k, v in self.domain_metrics.get_metrics().items():
                     self.logger.log_scalar(f"train/{k}", float(v), step)
+                if self.teacher is not None:
+                    self._log_teacher(step)
         return total_loss / max(num_batches, 1), self.domain_metrics.get_metrics()
 
     def validate(self, dataloader):
