@@ -400,6 +400,11 @@ CE_CASES = [dict(ldc=ldc, classes=cl, pixels=p, **({"size": BIG} if p > 257 else
             for ldc, cl in ((24, 23), (12, 11), (40, 37), (64, 64)) for p in (257, 262_656)]
 
 
+# every width of the ce_fwd / ce_bwd / ce_fwd_bwd launch ladders (ldc 4 ... 64; the tiled backward and the fused pass end at 32):
+# one full 256-pixel chunk plus a ragged tail
+CE_WIDTH_CASES = [dict(ldc=ldc, classes=ldc - 1, pixels=300) for ldc in range(4, 65, 4)]
+
+
 def ce_id(c):
     return f"ldc{c['ldc']}-c{c['classes']}-p{c['pixels']}"
 
@@ -517,6 +522,7 @@ FAMILIES = {                               # name -> (cases, id function, runner
     "consistency_edge": (CONS_EDGE, seg_id, run_consistency_edge),
     "seg_accumulate": (ACC_SHAPES, seg_id, run_seg_accumulate),
     "ce": (CE_CASES, ce_id, run_ce),
+    "ce_width": (CE_WIDTH_CASES, ce_id, run_ce),
     "tail": (TAIL_CASES + [dict(n=3, hw=24, c=512, bf16=True)], tail_id, run_tail),
     "bce": (BCE_CASES, lambda c: f"n{c['n']}", run_bce),
 }

@@ -25,6 +25,7 @@ SHAPES = [(1, 23, 17, 19),      # 323 pixels: one full 256-chunk plus a tail; ld
           (1, 32, 16, 24),      # ldc 32, the fused boundary
           (1, 40, 16, 16),      # two-pass route only
           (2, 23, 384, 384)]    # 294 912 pixels > 1024 blocks x 256: the grid-stride loop runs twice
+WIDTH_SHAPES = [(1, ldc - 1, 15, 20) for ldc in range(4, 65, 4)]   # 300 pixels at every width of the launch ladders
 PATTERNS = ("no_void", "random_void", "void_run", "all_void", "invalid")
 IGNORES = (255, -100, 0)
 VALUE_TOL, GRAD_TOL = 1e-5, 1e-3
@@ -50,7 +51,7 @@ def inputs(shape, pattern, ign):
     key = (shape, pattern, ign)
     if key not in _INPUTS:
         n, c, h, w = shape
-        g = torch.Generator().manual_seed(1000 * SHAPES.index(shape) + 10 * PATTERNS.index(pattern) + IGNORES.index(ign))
+        g = torch.Generator().manual_seed(1000 * (SHAPES + WIDTH_SHAPES).index(shape) + 10 * PATTERNS.index(pattern) + IGNORES.index(ign))
         z = torch.randn(n, c, h, w, generator=g) * 3.0
         t = torch.randint(0, c, (n, h, w), generator=g)
         flat = t.view(-1)
@@ -149,6 +150,14 @@ def test_optioned_cross_entropy_matches_torch_float64(L, shape, pattern, ign):
     for use_w, eps, reduction in itertools.product((True, False), (0.0, 0.1), ("mean", "sum", "none")):
         check_against_oracle(L, shape, pattern, ign, use_w, eps, reduction)
     print(f"{shape} {pattern} ignore_index={ign}: worst so far value {WORST['value']:.2e}, gradient {WORST['grad']:.2e}")
+
+
+@pytest.mark.parametrize("shape", WIDTH_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_optioned_cross_entropy_at_every_launch_width(L, shape):
+    """ldc 4 ... 64, with and without label smoothing (the SMOOTH instantiations): 'mean' takes the fused ce_opt_fwd_bwd where
+    ldc <= 32, 'none' the two passes ce_opt_fwd + ce_opt_bwd (tiled to ldc 32, one thread per pixel beyond) at every ldc."""
+    for eps, reduction in itertools.product((0.0, 0.1), ("mean", "none")):
+        check_against_oracle(L, shape, "random_void", 255, True, eps, reduction)
 
 
 def test_void_pixels_get_no_gradient_and_leave_the_mean(L):

@@ -112,6 +112,29 @@ def test_tables_edge_by_edge(C, name):
     _check_tables(name, kpos, kneg, logits, target)
 
 
+@pytest.mark.parametrize("classes,ldc", [(ldc - 1, ldc) for ldc in range(4, 33, 4)] + [(4, 4), (32, 32)])
+def test_every_row_width(C, classes, ldc):
+    """All eight instantiations of the histogram kernel at kernel level, by the per-edge criterion: junk in the pad lanes, an exact
+    tie of the maximum, and a NaN above channel 0, whose pixel has no number for a score and lands in bin 0 of every class."""
+    import _scores_ref as S
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    rows = S.sweep_rows(classes, seed=200 + ldc)
+    rng = np.random.default_rng(ldc)
+    tgt = rng.integers(0, classes, S.PIXELS)
+    tgt[[3, 290]] = -1, classes + 5
+    tables = torch.zeros(2, classes, R.SCORE_BINS, dtype=torch.int64, device="cuda")
+    K.score_hist(torch.from_numpy(S.padded(rows, ldc)).cuda(), torch.from_numpy(tgt).cuda(), S.PIXELS, classes, ldc, R.SCORE_BINS,
+                 R.SCORE_RANGE, tables[0], tables[1])
+    kpos, kneg = tables.cpu().numpy()
+    assert np.isnan(rows[S.NAN_PIXEL]).sum() == 1
+    for k in range(classes):                                          # the NaN pixel: bin 0 of every class
+        (kpos if k == tgt[S.NAN_PIXEL] else kneg)[k, 0] -= 1
+    assert kpos.min() >= 0 and kneg.min() >= 0
+    keep = np.arange(S.PIXELS) != S.NAN_PIXEL
+    logits = rows[keep].T.reshape(1, classes, 1, -1)
+    _check_tables(f"classes={classes} ldc={ldc}", kpos, kneg, logits, tgt[keep].reshape(1, 1, -1))
+
+
 def test_other_grids(C):
     """Coarser and finer grids (8 classes / 2 classes per block) and a narrower range (both end bins filled), by the same per-edge
     criterion; the 2 % cap on the allowance belongs to the default grid (the share grows with bins / range) and is not asserted."""

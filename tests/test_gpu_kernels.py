@@ -679,6 +679,29 @@ def test_argmax_confusion_matrix(K):
     assert torch.equal(cm.cpu(), ref)
 
 
+@pytest.mark.parametrize("classes,ldc", [(ldc - 1, ldc) for ldc in range(4, 33, 4)] + [(4, 4), (32, 32), (1, 4)])
+def test_argmax_confusion_at_every_width(K, classes, ldc):
+    """All eight instantiations, the winner against tests/_scores_ref.py's restatement bit for bit: junk in the pad lanes, an exact
+    tie, a NaN above channel 0, targets outside [0, classes) left out of the matrix."""
+    import numpy as np
+    import _scores_ref as S
+    rows = S.sweep_rows(classes, seed=100 + ldc)
+    rng = np.random.default_rng(ldc)
+    tgt = rng.integers(0, classes, S.PIXELS)
+    tgt[[3, 290]] = -1, classes
+    buf = torch.from_numpy(S.padded(rows, ldc)).cuda()
+    cm = torch.zeros(classes * classes, dtype=torch.int64, device="cuda")
+    pred = torch.full((S.PIXELS,), -7, dtype=torch.int64, device="cuda")
+    K.argmax_confusion(buf, torch.from_numpy(tgt).cuda(), S.PIXELS, classes, ldc, cm, pred)
+    want = S.first_max(rows)
+    if classes >= 2:
+        assert want[S.TIE_PIXEL] == S.tie_channels(classes)[0] and want[S.NAN_PIXEL] != classes - 1
+    assert np.array_equal(pred.cpu().numpy(), want)
+    valid = (tgt >= 0) & (tgt < classes)
+    ref = np.bincount(tgt[valid] * classes + want[valid], minlength=classes * classes)
+    assert np.array_equal(cm.cpu().numpy(), ref)
+
+
 def test_bn_fold_and_fused_inference_conv(K):
     g = torch.Generator().manual_seed(22)
     n, h, w, ci, co = 2, 12, 14, 64, 128

@@ -217,6 +217,12 @@ def test_cross_entropy(B, case):
     run(B, "ce", case)
 
 
+@cases("ce_width")
+def test_cross_entropy_at_every_launch_width(B, case):
+    """All sixteen widths of ce_fwd and ce_bwd (the tiled kernels to ldc 32, the simple ones beyond) and the eight of ce_fwd_bwd."""
+    run(B, "ce_width", case)
+
+
 @cases("tail")
 def test_discriminator_tail(B, case):
     run(B, "tail", case)

@@ -144,6 +144,58 @@ def test_blend_finish_against_float64_oracle(P, overlap, views, window):
     assert np.array_equal(labels.cpu().numpy()[ok], want.argmax(-1)[ok])
 
 
+def _sweep_classes():
+    import _scores_ref as S
+    return S.SWEEP_CLASSES
+
+
+@pytest.mark.parametrize("classes", _sweep_classes())
+def test_every_row_width(P, classes):
+    """All eight instantiations of the blend, finish and threshold kernels (ceil(classes / 4) = 1 ... 8, both ends of each) on 300
+    pixels: a 15 x 20 frame under one overhanging 32 x 32 tile in two views against the float64 oracle, the finish kernel alone
+    on rows with junk pad lanes, an exact tie and a NaN above channel 0 against tests/_scores_ref.py bit for bit, and the
+    threshold kernel on a batch of three such images."""
+    import _scores_ref as S
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    from uda_aerial_semantic_segmentation_research_amd.engine import ceil4
+    ldc, codes = ceil4(classes), (0, 2)
+    g = P.plan_grid(15, 20, 32, 0.25)
+    assert g.rows * g.cols == 1 and g.h * g.w == S.PIXELS
+    rng = np.random.default_rng(400 + classes)
+    logits = (rng.standard_normal((len(codes), g.th, g.tw, ldc)) * 3).astype(np.float32)
+    logits[..., classes:] = 1e4                                           # garbage in the padding lanes
+    wy, wx = P.window_vector(g.th, "gaussian"), P.window_vector(g.tw, "gaussian")
+    probs, labels = _blend_finish(P, g, torch.from_numpy(logits).cuda(), ldc, codes, classes, wy, wx, per_call=1)
+    want = _blend_oracle(P, g, logits, codes, classes, wy, wx)
+    probs = probs.cpu().numpy()
+    assert (probs[..., classes:] == 0).all()
+    assert np.abs(probs[..., :classes] - want).max() < 2e-6
+    if classes == 1:
+        assert (labels.cpu().numpy() == 0).all()
+    else:
+        ok = _margin_ok(want, 1e-5)
+        assert ok.mean() > 0.99
+        assert np.array_equal(labels.cpu().numpy()[ok], want.argmax(-1)[ok])
+    # finish alone (no weight sum: the argmax of the rows as they are, the buffer untouched)
+    rows = S.sweep_rows(classes, seed=500 + classes)
+    buf = torch.from_numpy(S.padded(rows, ldc)).cuda()
+    before = buf.clone()
+    lab = torch.full((S.PIXELS,), -7, dtype=torch.int64, device="cuda")
+    K.predict_finish(buf, None, S.PIXELS, classes, ldc, lab)
+    am = S.first_max(rows)
+    if classes >= 2:
+        assert am[S.TIE_PIXEL] == S.tie_channels(classes)[0] and am[S.NAN_PIXEL] != classes - 1
+    assert np.array_equal(lab.cpu().numpy(), am)
+    assert torch.equal(torch.nan_to_num(buf, nan=-3.0), torch.nan_to_num(before, nan=-3.0))
+    # threshold: batch 3, [n, hw, ldc] -> [n, classes, hw]
+    z3 = np.stack([S.sweep_rows(classes, seed=600 + 10 * classes + i) for i in range(3)])
+    out = torch.full((3, classes, S.PIXELS), float("nan"), device="cuda")
+    K.predict_threshold(torch.from_numpy(np.stack([S.padded(z, ldc) for z in z3])).cuda(), 3, S.PIXELS, classes, ldc, out)
+    zt = torch.from_numpy(z3).permute(0, 2, 1)
+    assert bool((zt.abs() >= 1e-6).logical_or(zt.isnan()).all())          # no logit at the sigmoid's 0.5
+    assert torch.equal(out.cpu(), (torch.sigmoid(zt) > 0.5).float())
+
+
 @pytest.mark.parametrize("h,w,tile", [(150, 200, 64), (40, 50, 128)])
 def test_d4_round_trip_through_the_gather(P, h, w, tile):
     """Gathered fp32 tiles (cpad 4, lane 3 zero) are a valid classes=3, ldc=4 logits buffer: blending all 8 views back must give

@@ -131,6 +131,66 @@ def test_void_label_and_unaligned_label_buffer(P):
     assert int(raw[0]) == 77 and bool((raw[pixels + 1:] == 77).all())
 
 
+def _sweep_classes():
+    import _scores_ref as S
+    return S.SWEEP_CLASSES
+
+
+@pytest.mark.parametrize("probs", [False, True], ids=["logits", "probs"])
+@pytest.mark.parametrize("classes", _sweep_classes())
+def test_every_row_width(P, classes, probs):
+    """All eight instantiations of conf_hist and pseudo_labels (ceil(classes / 4) = 1 ... 8, both ends of each) at kernel level on
+    300 pixels with junk in the pad lanes, an exact tie of the maximum and a NaN above channel 0 (that pixel is non-finite: void,
+    in no cell, counted on its own).  Winner, labels, counts and table exactly; the confidence by test_against_float64's bar."""
+    import _scores_ref as S
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    bins, pixels, ldc = 1024, S.PIXELS, (classes + 3) // 4 * 4
+    rows = S.sweep_rows(classes, seed=300 + classes, nan=False)
+    if probs:
+        rows = torch.softmax(torch.from_numpy(rows), dim=1).numpy()          # equal logits give equal probabilities: the tie stays
+    if classes >= 2:
+        lo, hi = S.tie_channels(classes)
+        assert rows[S.TIE_PIXEL, lo] == rows[S.TIE_PIXEL, hi] == rows[S.TIE_PIXEL].max()
+        rows[S.NAN_PIXEL, classes - 1] = np.nan
+    am = S.first_max(rows)
+    finite = ~np.isnan(rows).any(axis=1)
+    nbad = int((~finite).sum())
+    assert nbad == (1 if classes >= 2 else 0)
+    r64 = rows[finite].astype(np.float64)
+    if probs:
+        p64, bar = r64.max(axis=1), 0.0                                      # the stored value itself
+    else:
+        p64 = 1.0 / np.exp(r64 - r64.max(axis=1, keepdims=True)).sum(axis=1)
+        x = torch.from_numpy(rows[finite]).cuda()
+        torch_err = float(np.abs(torch.softmax(x, 1).amax(1).double().cpu().numpy() - p64).max())
+        bar = max(MULTIPLE * torch_err, FLOOR_ULPS * ULP1)
+    buf = torch.from_numpy(S.padded(rows, ldc)).cuda()
+    table = torch.zeros(classes, bins, dtype=torch.int64, device="cuda")
+    nonfinite = torch.zeros(1, dtype=torch.int64, device="cuda")
+    K.conf_hist(buf, pixels, classes, ldc, probs, bins, table, nonfinite)
+    thr0 = torch.zeros(classes, dtype=torch.int32, device="cuda")
+    labels = torch.full((pixels,), 77, dtype=torch.uint8, device="cuda")
+    conf = torch.full((pixels,), float("nan"), device="cuda")
+    counts = torch.zeros(classes + 2, dtype=torch.int64, device="cuda")
+    K.pseudo_labels(buf, pixels, classes, ldc, probs, bins, thr0, 255, labels, conf, counts)
+    lab, cf = labels.cpu().numpy().astype(np.int64), conf.cpu().numpy().astype(np.float64)
+    assert np.array_equal(lab, np.where(finite, am, 255))                    # the winner, tie included; the NaN pixel void
+    assert (cf[~finite] == 0.0).all() and float(np.abs(cf[finite] - p64).max()) <= bar
+    b = _bins_of(cf[finite], bins)
+    assert np.array_equal(table.cpu().numpy(), np.bincount(am[finite] * bins + b, minlength=classes * bins).reshape(classes, bins))
+    assert int(nonfinite) == nbad
+    want_counts = np.concatenate([np.bincount(am[finite], minlength=classes), [nbad, nbad]])
+    assert np.array_equal(counts.cpu().numpy(), want_counts)
+    # thresholds that cut: every class keeps the pixels whose bin reaches its threshold
+    thr = torch.full((classes,), bins // 2, dtype=torch.int32, device="cuda")
+    counts.zero_()
+    K.pseudo_labels(buf, pixels, classes, ldc, probs, bins, thr, 255, labels, None, counts)
+    kept = finite.copy()
+    kept[finite] = b >= bins // 2
+    assert np.array_equal(labels.cpu().numpy().astype(np.int64), np.where(kept, am, 255))
+    assert int(counts[classes]) == pixels - int(kept.sum()) and int(counts[classes + 1]) == nbad
+
+
 # --------------------------------------------------------------------------------------------------------- 2. against float64
 F64_CASES = [("scaled", 23, 1), ("low_t", 23, 2), ("high_t", 23, 3), ("ties", 5, 4), ("scaled", 32, 5), ("scaled", 2, 6)]
 

@@ -32,6 +32,13 @@ int hip_fail(hipError_t e, const char* what);
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// blocks of per_block items each, at most cap of them (the grid-stride kernels walk the rest)
+static inline int capped_grid(int64_t items, int per_block, int cap) {
+  const int64_t g = cdiv64(items, per_block);
+  return (int)(g > cap ? cap : g);
+}
+// bin counts of the device histograms (curves.hip, pseudo.hip): their finish kernels give each of 256 threads bins / 256 bins
+static inline bool hist_bins_supported(int bins) { return bins == 256 || bins == 512 || bins == 1024 || bins == 2048 || bins == 4096; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -85,6 +92,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
   return v;
 }
 

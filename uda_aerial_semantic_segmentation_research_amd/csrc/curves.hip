@@ -10,7 +10,7 @@
 // so scores beyond the range fall into the end bins; a NaN score is counted in bin 0 (fmaxf(NaN, 0) = 0).
 // pos[c][b] counts the pixels of target c, neg[c][b] the pixels of every other valid target; a pixel whose target is outside
 // [0, classes) is left out of every table (the rule of argmax_confusion_kernel).  Both tables ACCUMULATE.
-#include "common.h"
+#include "scores_common.h"
 
 namespace udaseg {
 
@@ -40,23 +40,15 @@ __global__ __launch_bounds__(SH_THREADS) void score_hist_kernel(const f32x4* __r
     const int64_t t64 = target[p];
     if (t64 < 0 || t64 >= classes) continue;
     const int t = (int)t64;
+    f32x4 v[LDC4];
+    load_row<LDC4>(logits + p * LDC4, v);
+    float m;
+    const int am = first_max<LDC4>(v, classes, m);
     float z[LDC];
-    float m = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < LDC4; ++k) {
-      const f32x4 v = logits[p * LDC4 + k];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = k * 4 + e;
-        z[c] = v[e];
-        if (c < classes && (c == 0 || v[e] > m)) { m = v[e]; am = c; }
-      }
-    }
     float S = 0.f, Sp = 0.f;
 #pragma unroll
     for (int c = 0; c < LDC; ++c) {
-      z[c] -= m;                                         // <= 0; exactly 0 at the argmax
+      z[c] = v[c / 4][c % 4] - m;                        // <= 0; exactly 0 at the argmax
       if (c < classes) {
         const float e = expf(z[c]);
         S += e;
@@ -152,8 +144,6 @@ __global__ __launch_bounds__(CF_THREADS) void curve_finish_kernel(const unsigned
   }
 }
 
-static bool bins_supported(int bins) { return bins == 256 || bins == 512 || bins == 1024 || bins == 2048 || bins == 4096; }
-
 }  // namespace udaseg
 
 using namespace udaseg;
@@ -161,11 +151,9 @@ using namespace udaseg;
 extern "C" int udaseg_score_hist(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, int bins,
                                  float score_range, int64_t* pos, int64_t* neg, void* stream) {
   UDASEG_CHECK_ARG(logits && target && pos && neg, "score_hist: NULL pointer");
-  UDASEG_CHECK_ARG(pixels > 0 && pixels < ((int64_t)1 << 31) && classes > 0 && classes <= 32 && classes <= ldc && ldc % 4 == 0 &&
-                       ldc <= 32,
-                   "score_hist: need 0 < pixels < 2^31, classes <= 32, ldc %% 4 == 0 (pixels=%lld classes=%d ldc=%d)",
-                   (long long)pixels, classes, ldc);
-  UDASEG_CHECK_ARG(bins_supported(bins), "score_hist: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
+  if (!scores_args_ok("score_hist", pixels, classes, ldc, 32)) return UDASEG_E_BADARG;
+  UDASEG_CHECK_ARG(pixels < ((int64_t)1 << 31), "score_hist: need pixels < 2^31 (pixels=%lld)", (long long)pixels);
+  UDASEG_CHECK_ARG(hist_bins_supported(bins), "score_hist: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
   UDASEG_CHECK_ARG(score_range > 0.f && score_range <= 1e30f, "score_hist: score_range must be positive and finite");
   hipStream_t st = as_stream(stream);
   const int cg = SH_CELLS / (2 * bins);
@@ -175,18 +163,12 @@ extern "C" int udaseg_score_hist(const float* logits, const int64_t* target, int
   if (gx > want) gx = (int)want;
   if (gx < 1) gx = 1;
   const float scale = (float)bins / (2.f * score_range);
-#define SH_CASE(L)                                                                                                          \
-  case L:                                                                                                                   \
-    hipLaunchKernelGGL(score_hist_kernel<L>, dim3(gx, groups), dim3(SH_THREADS), 0, st, (const f32x4*)logits, target, pixels, \
-                       classes, bins, cg, score_range, scale, (unsigned long long*)pos, (unsigned long long*)neg);          \
-    break;
-  switch (ldc / 4) {
-    SH_CASE(1) SH_CASE(2) SH_CASE(3) SH_CASE(4) SH_CASE(5) SH_CASE(6) SH_CASE(7) SH_CASE(8)
-    default:
-      set_error("score_hist: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef SH_CASE
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(score_hist_kernel<decltype(w)::value>, dim3(gx, groups), dim3(SH_THREADS), 0, st, (const f32x4*)logits,
+                           target, pixels, classes, bins, cg, score_range, scale, (unsigned long long*)pos,
+                           (unsigned long long*)neg);
+      }))
+    return unsupported_width("score_hist", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("score_hist launch");
   return UDASEG_OK;
 }
@@ -195,7 +177,7 @@ extern "C" int udaseg_curve_finish(const int64_t* pos, const int64_t* neg, int c
                                    double* auc_slack, int64_t* support, void* stream) {
   UDASEG_CHECK_ARG(pos && neg && auc && ap && auc_slack && support, "curve_finish: NULL pointer");
   UDASEG_CHECK_ARG(classes > 0 && classes <= 32, "curve_finish: need 0 < classes <= 32 (classes=%d)", classes);
-  UDASEG_CHECK_ARG(bins_supported(bins), "curve_finish: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
+  UDASEG_CHECK_ARG(hist_bins_supported(bins), "curve_finish: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(curve_finish_kernel, dim3(classes), dim3(CF_THREADS), 0, st, (const unsigned long long*)pos,
                      (const unsigned long long*)neg, bins, auc, ap, auc_slack, (unsigned long long*)support);

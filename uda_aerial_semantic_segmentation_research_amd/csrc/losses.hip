@@ -8,11 +8,12 @@
 //  * AdversarialLoss' nn.BCEWithLogitsLoss terms (src/models/losses.py:16,33-36,51).  The reference feeds the
 //      discriminator's *probabilities* into the with-logits loss; these kernels are agnostic: they compute
 //      mean(softplus(x) - x*label) of whatever x is.
-#include "common.h"
+#include "scores_common.h"
 
 namespace udaseg {
 
 constexpr int CE_BLOCKS = 1024;
+constexpr int CE_SIMPLE_BLOCKS = 4096;   // the one-thread-per-pixel backward kernels of ldc > 32
 constexpr int CE_MAXC = 64;
 
 // One thread per pixel, logits row in registers (classes <= 64, ldc % 4 == 0).  HBM-bound: 4*ldc B/pixel read.
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(256) void ce_opt_bwd_kernel(const f32x4* __restrict
 // ---- validation metrics: per-pixel argmax + confusion matrix (SegmentationTrainer.calculate_metrics, reference
 // src/models/train.py:225-243; confusion-matrix definition src/analysis/metrics.py:17-29: bincount(C*true + pred)).
 // One thread per pixel, row in registers; the block's histogram lives in LDS (classes <= 32 -> 4 KiB of counters), one
-// global atomic per non-empty cell per block.  argmax tie rule = torch.argmax: first maximal index.
+// global atomic per non-empty cell per block.  argmax tie rule = first_max (scores_common.h).
 template <int LDC4>
 __global__ __launch_bounds__(256) void argmax_confusion_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                                int64_t pixels, int classes, unsigned long long* __restrict__ cm,
@@ -589,19 +590,10 @@ __global__ __launch_bounds__(256) void argmax_confusion_kernel(const f32x4* __re
   __syncthreads();
   const int64_t T = (int64_t)gridDim.x * blockDim.x;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += T) {
-    float best = -INFINITY;
-    int bi = 0;
-#pragma unroll
-    for (int k = 0; k < LDC4; ++k) {
-      const f32x4 v = logits[p * LDC4 + k];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = k * 4 + e;
-        if (c < classes && (v[e] > best || (c == 0))) {
-          if (c == 0 || v[e] > best) { best = v[e]; bi = c; }
-        }
-      }
-    }
+    f32x4 v[LDC4];
+    load_row<LDC4>(logits + p * LDC4, v);
+    float best;
+    const int bi = first_max<LDC4>(v, classes, best);
     if (pred_out) pred_out[p] = bi;
     const int t = (int)target[p];
     if ((unsigned)t < (unsigned)classes) atomicAdd(&hist[t * classes + bi], 1u);
@@ -746,20 +738,12 @@ extern "C" int udaseg_ce_fwd(const float* logits, const int64_t* target, int64_t
   UDASEG_CHECK_ARG(pixels > 0 && classes > 0 && classes <= ldc && ldc % 4 == 0 && ldc <= CE_MAXC,
                    "ce_fwd: need 0 < classes <= ldc <= %d, ldc %% 4 == 0 (classes=%d ldc=%d)", CE_MAXC, classes, ldc);
   hipStream_t st = as_stream(stream);
-  int grid = (int)((pixels + 255) / 256 > CE_BLOCKS ? CE_BLOCKS : (pixels + 255) / 256);
-#define CE_FWD_CASE(L)                                                                                                 \
-  case L:                                                                                                              \
-    hipLaunchKernelGGL(ce_fwd_kernel<L>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, pixels, classes, lse, \
-                       partials);                                                                                      \
-    break;
-  switch (ldc / 4) {
-    CE_FWD_CASE(1) CE_FWD_CASE(2) CE_FWD_CASE(3) CE_FWD_CASE(4) CE_FWD_CASE(5) CE_FWD_CASE(6) CE_FWD_CASE(7) CE_FWD_CASE(8)
-    CE_FWD_CASE(9) CE_FWD_CASE(10) CE_FWD_CASE(11) CE_FWD_CASE(12) CE_FWD_CASE(13) CE_FWD_CASE(14) CE_FWD_CASE(15) CE_FWD_CASE(16)
-    default:
-      set_error("ce_fwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_FWD_CASE
+  const int grid = capped_grid(pixels, 256, CE_BLOCKS);
+  if (!dispatch_width<16>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(ce_fwd_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, pixels,
+                           classes, lse, partials);
+      }))
+    return unsupported_width("ce_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_fwd launch");
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, pixels, loss);
   UDASEG_LAUNCH_CHECK("ce_finish launch");
@@ -773,20 +757,12 @@ extern "C" int udaseg_ce_fwd_bwd(const float* logits, const int64_t* target, int
                    "ce_fwd_bwd: need 0 < classes <= ldc <= 32, ldc %% 4 == 0 (classes=%d ldc=%d)", classes, ldc);
   UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_fwd_bwd: colsum and colsum_partials come together");
   hipStream_t st = as_stream(stream);
-  const int64_t nchunks = (pixels + 255) / 256;
-  const int grid = (int)(nchunks > CE_BLOCKS ? CE_BLOCKS : nchunks);
-#define CE_FB_CASE(L)                                                                                                    \
-  case L:                                                                                                                \
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<L>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, pixels, classes,  \
-                       partials, (f32x4*)dlogits, colsum_partials);                                                      \
-    break;
-  switch (ldc / 4) {
-    CE_FB_CASE(1) CE_FB_CASE(2) CE_FB_CASE(3) CE_FB_CASE(4) CE_FB_CASE(5) CE_FB_CASE(6) CE_FB_CASE(7) CE_FB_CASE(8)
-    default:
-      set_error("ce_fwd_bwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_FB_CASE
+  const int grid = capped_grid(pixels, 256, CE_BLOCKS);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(ce_fwd_bwd_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, pixels,
+                           classes, partials, (f32x4*)dlogits, colsum_partials);
+      }))
+    return unsupported_width("ce_fwd_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_fwd_bwd launch");
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, pixels, loss);
   UDASEG_LAUNCH_CHECK("ce_finish launch");
@@ -817,64 +793,35 @@ extern "C" int udaseg_ce_bwd(const float* logits, const int64_t* target, const f
   UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_bwd: colsum and colsum_partials come together");
   UDASEG_CHECK_ARG(colsum == nullptr || ldc <= 32, "ce_bwd: fused column sums need ldc <= 32");
   hipStream_t st = as_stream(stream);
-  if (ldc <= 32) {
-    const int64_t nchunks = (pixels + 255) / 256;
-    const int grid = (int)(nchunks > CE_BLOCKS ? CE_BLOCKS : nchunks);
-#define CE_BWD_CASE(L)                                                                                                   \
-  case L:                                                                                                                \
-    hipLaunchKernelGGL(ce_bwd_kernel<L>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, lse, grad_out, pixels, \
-                       classes, (f32x4*)dlogits, colsum_partials);                                                       \
-    break;
-    switch (ldc / 4) {
-      CE_BWD_CASE(1) CE_BWD_CASE(2) CE_BWD_CASE(3) CE_BWD_CASE(4) CE_BWD_CASE(5) CE_BWD_CASE(6) CE_BWD_CASE(7) CE_BWD_CASE(8)
-      default:
-        set_error("ce_bwd: unsupported ldc %d", ldc);
-        return UDASEG_E_UNSUPPORTED;
-    }
-#undef CE_BWD_CASE
-    UDASEG_LAUNCH_CHECK("ce_bwd launch");
-    if (colsum) {
-      hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
-      UDASEG_LAUNCH_CHECK("colsum_finish launch");
-    }
-    return UDASEG_OK;
-  }
-  int grid = (int)((pixels + 255) / 256 > 4096 ? 4096 : (pixels + 255) / 256);
-#define CE_BWD_CASE(L)                                                                                                   \
-  case L:                                                                                                                \
-    hipLaunchKernelGGL(ce_bwd_simple_kernel<L>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, lse, grad_out, \
-                       pixels, classes, (f32x4*)dlogits);                                                                \
-    break;
-  switch (ldc / 4) {
-    CE_BWD_CASE(9) CE_BWD_CASE(10) CE_BWD_CASE(11) CE_BWD_CASE(12) CE_BWD_CASE(13) CE_BWD_CASE(14) CE_BWD_CASE(15) CE_BWD_CASE(16)
-    default:
-      set_error("ce_bwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_BWD_CASE
+  const int grid = capped_grid(pixels, 256, ldc <= 32 ? CE_BLOCKS : CE_SIMPLE_BLOCKS);
+  if (!dispatch_width<16>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if constexpr (W <= 8)
+          hipLaunchKernelGGL(ce_bwd_kernel<W>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, lse, grad_out, pixels,
+                             classes, (f32x4*)dlogits, colsum_partials);
+        else
+          hipLaunchKernelGGL(ce_bwd_simple_kernel<W>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, lse, grad_out,
+                             pixels, classes, (f32x4*)dlogits);
+      }))
+    return unsupported_width("ce_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_bwd launch");
+  if (colsum) {
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
+    UDASEG_LAUNCH_CHECK("colsum_finish launch");
+  }
   return UDASEG_OK;
 }
 
 extern "C" int udaseg_argmax_confusion(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc,
                                        int64_t* confusion, int64_t* pred, void* stream) {
   UDASEG_CHECK_ARG(logits && target && confusion, "argmax_confusion: NULL pointer");
-  UDASEG_CHECK_ARG(pixels > 0 && classes > 0 && classes <= 32 && classes <= ldc && ldc % 4 == 0 && ldc <= 32,
-                   "argmax_confusion: need classes <= 32, ldc %% 4 == 0 (classes=%d ldc=%d)", classes, ldc);
-  hipStream_t st = as_stream(stream);
-  int grid = (int)((pixels + 255) / 256 > 1024 ? 1024 : (pixels + 255) / 256);
-#define AMX_CASE(L)                                                                                                      \
-  case L:                                                                                                                \
-    hipLaunchKernelGGL(argmax_confusion_kernel<L>, dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, pixels,   \
-                       classes, (unsigned long long*)confusion, pred);                                                   \
-    break;
-  switch (ldc / 4) {
-    AMX_CASE(1) AMX_CASE(2) AMX_CASE(3) AMX_CASE(4) AMX_CASE(5) AMX_CASE(6) AMX_CASE(7) AMX_CASE(8)
-    default:
-      set_error("argmax_confusion: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef AMX_CASE
+  if (!scores_args_ok("argmax_confusion", pixels, classes, ldc, 32)) return UDASEG_E_BADARG;
+  const int grid = capped_grid(pixels, 256, 1024);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(argmax_confusion_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, as_stream(stream),
+                           (const f32x4*)logits, target, pixels, classes, (unsigned long long*)confusion, pred);
+      }))
+    return unsupported_width("argmax_confusion", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("argmax_confusion launch");
   return UDASEG_OK;
 }
@@ -905,7 +852,7 @@ extern "C" int udaseg_gap_linear_sigmoid_bwd(const float* dp, const float* p, co
   UDASEG_CHECK_ARG(n > 0 && hw > 0 && c > 0 && c % 4 == 0, "gap_linear_sigmoid_bwd: bad shape");
   hipStream_t st = as_stream(stream);
   const int64_t total = (int64_t)n * hw * (c / 4);
-  int grid = (int)((total + 511) / 512 > 2048 ? 2048 : (total + 511) / 512);
+  const int grid = capped_grid(total, 512, 2048);
   hipLaunchKernelGGL(gap_bwd_broadcast_kernel, dim3(grid), dim3(256), 0, st, dp, p, (const f32x4*)w, (f32x4*)dz, n, hw, c / 4, 1);
   UDASEG_LAUNCH_CHECK("gap_bwd_broadcast launch");
   hipLaunchKernelGGL(gap_bwd_param_kernel, dim3((c + 255) / 256), dim3(256), 0, st, dp, p, pooled, dw, db, n, c, accumulate_param, 1);
@@ -971,7 +918,7 @@ extern "C" int udaseg_gap_linear_bwd(const float* dlogit, const float* pooled, c
   UDASEG_CHECK_ARG(n > 0 && hw > 0 && c > 0 && c % 4 == 0, "gap_linear_bwd: bad shape");
   hipStream_t st = as_stream(stream);
   const int64_t total = (int64_t)n * hw * (c / 4);
-  int grid = (int)((total + 511) / 512 > 2048 ? 2048 : (total + 511) / 512);
+  const int grid = capped_grid(total, 512, 2048);
   hipLaunchKernelGGL(gap_bwd_broadcast_kernel, dim3(grid), dim3(256), 0, st, dlogit, (const float*)nullptr, (const f32x4*)w,
                      (f32x4*)dz, n, hw, c / 4, 0);
   UDASEG_LAUNCH_CHECK("gap_bwd_broadcast launch");
@@ -1014,8 +961,7 @@ extern "C" int udaseg_ce_target_stats(const int64_t* target, const float* weight
   UDASEG_CHECK_ARG(pixels > 0 && classes > 0 && classes <= CE_MAXC, "ce_target_stats: need 0 < classes <= %d (classes=%d)", CE_MAXC,
                    classes);
   hipStream_t st = as_stream(stream);
-  const int64_t nb = (pixels + 255) / 256;
-  const int grid = (int)(nb > CE_BLOCKS ? CE_BLOCKS : nb);
+  const int grid = capped_grid(pixels, 256, CE_BLOCKS);
   hipLaunchKernelGGL(ce_target_stats_kernel, dim3(grid), dim3(256), 0, st, target, weight, pixels, classes, has_ignore, ignore_index,
                      partials);
   UDASEG_LAUNCH_CHECK("ce_target_stats launch");
@@ -1023,11 +969,6 @@ extern "C" int udaseg_ce_target_stats(const int64_t* target, const float* weight
   UDASEG_LAUNCH_CHECK("ce_target_stats_finish launch");
   return UDASEG_OK;
 }
-
-#define CE_OPT_SWITCH_1_8(CASE) \
-  CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#define CE_OPT_SWITCH_9_16(CASE) \
-  CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
 
 extern "C" int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes,
                                      int ldc, int has_ignore, int64_t ignore_index, float eps, int mean, const double* denom,
@@ -1039,25 +980,18 @@ extern "C" int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target,
   UDASEG_CHECK_ARG(!mean || denom, "ce_opt_fwd_bwd: the 'mean' reduction needs the denominator of udaseg_ce_target_stats");
   UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_opt_fwd_bwd: colsum and colsum_partials come together");
   hipStream_t st = as_stream(stream);
-  const int64_t nchunks = (pixels + 255) / 256;
-  const int grid = (int)(nchunks > CE_BLOCKS ? CE_BLOCKS : nchunks);
+  const int grid = capped_grid(pixels, 256, CE_BLOCKS);
   const double* dn = mean ? denom : nullptr;
-#define CE_OFB_CASE(L)                                                                                                       \
-  case L:                                                                                                                    \
-    if (eps != 0.f)                                                                                                          \
-      hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<L, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, \
-                         pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);     \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<L, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, \
-                         pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);     \
-    break;
-  switch (ldc / 4) {
-    CE_OPT_SWITCH_1_8(CE_OFB_CASE)
-    default:
-      set_error("ce_opt_fwd_bwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_OFB_CASE
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (eps != 0.f)
+          hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<W, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight,
+                             pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);
+        else
+          hipLaunchKernelGGL((ce_opt_fwd_bwd_kernel<W, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight,
+                             pixels, classes, has_ignore, ignore_index, eps, dn, partials, (f32x4*)dlogits, colsum_partials);
+      }))
+    return unsupported_width("ce_opt_fwd_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_fwd_bwd launch");
   hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, dn, loss);
   UDASEG_LAUNCH_CHECK("ce_opt_finish launch");
@@ -1076,24 +1010,17 @@ extern "C" int udaseg_ce_opt_fwd(const float* logits, const int64_t* target, con
   UDASEG_CHECK_ARG(lse && partials && (loss || loss_px), "ce_opt_fwd: NULL pointer");
   UDASEG_CHECK_ARG(!mean || denom, "ce_opt_fwd: the 'mean' reduction needs the denominator of udaseg_ce_target_stats");
   hipStream_t st = as_stream(stream);
-  const int grid = (int)((pixels + 255) / 256 > CE_BLOCKS ? CE_BLOCKS : (pixels + 255) / 256);
-#define CE_OF_CASE(L)                                                                                                         \
-  case L:                                                                                                                     \
-    if (eps != 0.f)                                                                                                           \
-      hipLaunchKernelGGL((ce_opt_fwd_kernel<L, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels, \
-                         classes, has_ignore, ignore_index, eps, lse, loss_px, partials);                                     \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((ce_opt_fwd_kernel<L, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels, \
-                         classes, has_ignore, ignore_index, eps, lse, loss_px, partials);                                     \
-    break;
-  switch (ldc / 4) {
-    CE_OPT_SWITCH_1_8(CE_OF_CASE)
-    CE_OPT_SWITCH_9_16(CE_OF_CASE)
-    default:
-      set_error("ce_opt_fwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_OF_CASE
+  const int grid = capped_grid(pixels, 256, CE_BLOCKS);
+  if (!dispatch_width<16>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (eps != 0.f)
+          hipLaunchKernelGGL((ce_opt_fwd_kernel<W, true>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels,
+                             classes, has_ignore, ignore_index, eps, lse, loss_px, partials);
+        else
+          hipLaunchKernelGGL((ce_opt_fwd_kernel<W, false>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, pixels,
+                             classes, has_ignore, ignore_index, eps, lse, loss_px, partials);
+      }))
+    return unsupported_width("ce_opt_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_fwd launch");
   if (loss) {
     hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? denom : (const double*)nullptr, loss);
@@ -1113,32 +1040,21 @@ extern "C" int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, con
   UDASEG_CHECK_ARG((colsum == nullptr) == (colsum_partials == nullptr), "ce_opt_bwd: colsum and colsum_partials come together");
   UDASEG_CHECK_ARG(colsum == nullptr || ldc <= 32, "ce_opt_bwd: fused column sums need ldc <= 32");
   hipStream_t st = as_stream(stream);
-  const int64_t nchunks = (pixels + 255) / 256;
   const double* dn = mean ? denom : nullptr;
-  const int grid = (int)(nchunks > (ldc <= 32 ? CE_BLOCKS : 4096) ? (ldc <= 32 ? CE_BLOCKS : 4096) : nchunks);
-#define CE_OB_LAUNCH(L, S, TI)                                                                                               \
-  hipLaunchKernelGGL((ce_opt_bwd_kernel<L, S, TI>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight, lse, \
-                     grad_out, grad_px, pixels, classes, has_ignore, ignore_index, eps, dn, (f32x4*)dlogits, colsum_partials)
-#define CE_OB_CASE_T(L)                      \
-  case L:                                    \
-    if (eps != 0.f) CE_OB_LAUNCH(L, true, true); \
-    else CE_OB_LAUNCH(L, false, true);       \
-    break;
-#define CE_OB_CASE_S(L)                       \
-  case L:                                     \
-    if (eps != 0.f) CE_OB_LAUNCH(L, true, false); \
-    else CE_OB_LAUNCH(L, false, false);       \
-    break;
-  switch (ldc / 4) {
-    CE_OPT_SWITCH_1_8(CE_OB_CASE_T)
-    CE_OPT_SWITCH_9_16(CE_OB_CASE_S)
-    default:
-      set_error("ce_opt_bwd: unsupported ldc %d", ldc);
-      return UDASEG_E_UNSUPPORTED;
-  }
-#undef CE_OB_CASE_T
-#undef CE_OB_CASE_S
-#undef CE_OB_LAUNCH
+  const int grid = capped_grid(pixels, 256, ldc <= 32 ? CE_BLOCKS : CE_SIMPLE_BLOCKS);
+  if (!dispatch_width<16>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        constexpr bool TILED = W <= 8;
+        if (eps != 0.f)
+          hipLaunchKernelGGL((ce_opt_bwd_kernel<W, true, TILED>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight,
+                             lse, grad_out, grad_px, pixels, classes, has_ignore, ignore_index, eps, dn, (f32x4*)dlogits,
+                             colsum_partials);
+        else
+          hipLaunchKernelGGL((ce_opt_bwd_kernel<W, false, TILED>), dim3(grid), dim3(256), 0, st, (const f32x4*)logits, target, weight,
+                             lse, grad_out, grad_px, pixels, classes, has_ignore, ignore_index, eps, dn, (f32x4*)dlogits,
+                             colsum_partials);
+      }))
+    return unsupported_width("ce_opt_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_bwd launch");
   if (colsum) {
     hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);

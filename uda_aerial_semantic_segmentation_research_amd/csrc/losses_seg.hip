@@ -4,7 +4,7 @@
 //   ConsistencyLoss              :53-108   (symmetric temperature KL, 'batchmean')
 // Logits are NHWC rows [pixel][ldc] with `classes` valid channels (ldc % 4 == 0, ldc <= 32), as produced by Unet.
 // One thread per pixel, softmax row in registers, wave/block reductions, f64 cross-block accumulation.
-#include "common.h"
+#include "scores_common.h"
 
 namespace udaseg {
 
@@ -336,34 +336,83 @@ static int check_seg(const void* logits, int64_t pixels, int classes, int ldc, c
                    "%s: need classes <= ldc <= 32, ldc %% 4 == 0 (classes=%d ldc=%d)", who, classes, ldc);
   return UDASEG_OK;
 }
-static int grid_pix(int64_t pixels) {
-  const int64_t g = (pixels + 255) / 256;
-  return (int)(g > SL_BLOCKS ? SL_BLOCKS : g);
+static int grid_pix(int64_t pixels) { return capped_grid(pixels, 256, SL_BLOCKS); }
+
+// The Dice / focal launches behind both forms of their entry points: ign = the *_ignore form, void labels (ignore_index, any int64)
+// honoured; otherwise the IGN = false kernels, which never read ignore_index.  who: the entry point, for the messages.
+static int dice_fwd(const char* who, const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes,
+                    int ldc, float smooth, float eps, int pooled, double* sums, float* coef, float* loss, bool ign,
+                    int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pix_per_image, classes, ldc, who);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && sums && coef && loss && batch > 0, "%s: NULL pointer", who);
+  hipStream_t st = as_stream(stream);
+  const int gx = capped_grid(pix_per_image, 256, 256);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((ign ? dice_stats_kernel<W, true> : dice_stats_kernel<W, false>), dim3(gx, batch), dim3(256), 0, st,
+                           (const f32x4*)logits, target, pix_per_image, classes, sums, ignore_index);
+      }))
+    return unsupported_width(who, "ldc", ldc);
+  UDASEG_LAUNCH_CHECK("dice_stats launch");
+  hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, batch, classes, smooth, eps, pooled, loss, coef);
+  UDASEG_LAUNCH_CHECK("dice_finish launch");
+  return UDASEG_OK;
 }
 
-#define SEG_DISPATCH(KERN, GRID, ...)                                                                       \
-  switch (ldc / 4) {                                                                                        \
-    case 1: hipLaunchKernelGGL(KERN<1>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 2: hipLaunchKernelGGL(KERN<2>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 3: hipLaunchKernelGGL(KERN<3>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 4: hipLaunchKernelGGL(KERN<4>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 5: hipLaunchKernelGGL(KERN<5>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 6: hipLaunchKernelGGL(KERN<6>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    case 7: hipLaunchKernelGGL(KERN<7>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                        \
-    default: hipLaunchKernelGGL(KERN<8>, GRID, dim3(256), 0, st, __VA_ARGS__); break;                       \
-  }
+static int dice_bwd(const char* who, const float* logits, const int64_t* target, const float* coef, const float* grad_out,
+                    float weight, int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits, int accumulate, bool ign,
+                    int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pix_per_image, classes, ldc, who);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && coef && dlogits && batch > 0, "%s: NULL pointer", who);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((ign ? dice_bwd_kernel<W, true> : dice_bwd_kernel<W, false>), dim3(grid_pix(pix_per_image * batch)),
+                           dim3(256), 0, as_stream(stream), (const f32x4*)logits, target, coef, grad_out, weight, pix_per_image,
+                           batch, classes, (f32x4*)dlogits, accumulate, ignore_index);
+      }))
+    return unsupported_width(who, "ldc", ldc);
+  UDASEG_LAUNCH_CHECK("dice_bwd launch");
+  return UDASEG_OK;
+}
 
-#define SEG_DISPATCH_IGN(KERN, GRID, ...)                                                                   \
-  switch (ldc / 4) {                                                                                        \
-    case 1: hipLaunchKernelGGL((KERN<1, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 2: hipLaunchKernelGGL((KERN<2, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 3: hipLaunchKernelGGL((KERN<3, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 4: hipLaunchKernelGGL((KERN<4, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 5: hipLaunchKernelGGL((KERN<5, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 6: hipLaunchKernelGGL((KERN<6, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    case 7: hipLaunchKernelGGL((KERN<7, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;                \
-    default: hipLaunchKernelGGL((KERN<8, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
-  }
+static int focal_fwd(const char* who, const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                     float gamma, int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss, int accumulate,
+                     bool ign, int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pixels, classes, ldc, who);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && partials && loss, "%s: NULL pointer", who);
+  hipStream_t st = as_stream(stream);
+  const int grid = grid_pix(pixels);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((ign ? focal_fwd_kernel<W, true> : focal_fwd_kernel<W, false>), dim3(grid), dim3(256), 0, st,
+                           (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials, ignore_index);
+      }))
+    return unsupported_width(who, "ldc", ldc);
+  UDASEG_LAUNCH_CHECK("focal_fwd launch");
+  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
+  UDASEG_LAUNCH_CHECK("focal_finish launch");
+  return UDASEG_OK;
+}
+
+static int focal_bwd(const char* who, const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                     float gamma, const float* grad_out, float weight, int64_t pixels, int classes, int ldc, float* dlogits,
+                     int accumulate, bool ign, int64_t ignore_index, void* stream) {
+  int rc = check_seg(logits, pixels, classes, ldc, who);
+  if (rc) return rc;
+  UDASEG_CHECK_ARG(target && dlogits, "%s: NULL pointer", who);
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((ign ? focal_bwd_kernel<W, true> : focal_bwd_kernel<W, false>), dim3(grid_pix(pixels)), dim3(256), 0,
+                           as_stream(stream), (const f32x4*)logits, target, class_weights, alpha, gamma, grad_out, weight, pixels,
+                           classes, (f32x4*)dlogits, accumulate, ignore_index);
+      }))
+    return unsupported_width(who, "ldc", ldc);
+  UDASEG_LAUNCH_CHECK("focal_bwd launch");
+  return UDASEG_OK;
+}
 
 }  // namespace udaseg
 
@@ -373,58 +422,53 @@ extern "C" int udaseg_seg_partials(void) { return SL_BLOCKS; }
 
 extern "C" int udaseg_dice_fwd(const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes, int ldc,
                                float smooth, float eps, int pooled, double* sums, float* coef, float* loss, void* stream) {
-  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_fwd");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && sums && coef && loss && batch > 0, "dice_fwd: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  const int gx = (int)((pix_per_image + 255) / 256 > 256 ? 256 : (pix_per_image + 255) / 256);
-  SEG_DISPATCH(dice_stats_kernel, dim3(gx, batch), (const f32x4*)logits, target, pix_per_image, classes, sums, (int64_t)0)
-  UDASEG_LAUNCH_CHECK("dice_stats launch");
-  hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, batch, classes, smooth, eps, pooled, loss, coef);
-  UDASEG_LAUNCH_CHECK("dice_finish launch");
-  return UDASEG_OK;
+  return dice_fwd("dice_fwd", logits, target, batch, pix_per_image, classes, ldc, smooth, eps, pooled, sums, coef, loss, false, 0,
+                  stream);
+}
+extern "C" int udaseg_dice_fwd_ignore(const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes,
+                                      int ldc, float smooth, float eps, int pooled, double* sums, float* coef, float* loss,
+                                      int64_t ignore_index, void* stream) {
+  return dice_fwd("dice_fwd_ignore", logits, target, batch, pix_per_image, classes, ldc, smooth, eps, pooled, sums, coef, loss, true,
+                  ignore_index, stream);
 }
 
 extern "C" int udaseg_dice_bwd(const float* logits, const int64_t* target, const float* coef, const float* grad_out, float weight,
                                int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits, int accumulate,
                                void* stream) {
-  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_bwd");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && coef && dlogits && batch > 0, "dice_bwd: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  SEG_DISPATCH(dice_bwd_kernel, dim3(grid_pix(pix_per_image * batch)), (const f32x4*)logits, target, coef, grad_out, weight,
-               pix_per_image, batch, classes, (f32x4*)dlogits, accumulate, (int64_t)0)
-  UDASEG_LAUNCH_CHECK("dice_bwd launch");
-  return UDASEG_OK;
+  return dice_bwd("dice_bwd", logits, target, coef, grad_out, weight, batch, pix_per_image, classes, ldc, dlogits, accumulate, false,
+                  0, stream);
+}
+extern "C" int udaseg_dice_bwd_ignore(const float* logits, const int64_t* target, const float* coef, const float* grad_out,
+                                      float weight, int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits,
+                                      int accumulate, int64_t ignore_index, void* stream) {
+  return dice_bwd("dice_bwd_ignore", logits, target, coef, grad_out, weight, batch, pix_per_image, classes, ldc, dlogits, accumulate,
+                  true, ignore_index, stream);
 }
 
 extern "C" int udaseg_focal_fwd(const float* logits, const int64_t* target, const float* class_weights, float alpha, float gamma,
                                 int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss, int accumulate,
                                 void* stream) {
-  int rc = check_seg(logits, pixels, classes, ldc, "focal_fwd");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && partials && loss, "focal_fwd: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  const int grid = grid_pix(pixels);
-  SEG_DISPATCH(focal_fwd_kernel, dim3(grid), (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials,
-               (int64_t)0)
-  UDASEG_LAUNCH_CHECK("focal_fwd launch");
-  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
-  UDASEG_LAUNCH_CHECK("focal_finish launch");
-  return UDASEG_OK;
+  return focal_fwd("focal_fwd", logits, target, class_weights, alpha, gamma, pixels, classes, ldc, mean, partials, loss, accumulate,
+                   false, 0, stream);
+}
+extern "C" int udaseg_focal_fwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                                       float gamma, int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss,
+                                       int accumulate, int64_t ignore_index, void* stream) {
+  return focal_fwd("focal_fwd_ignore", logits, target, class_weights, alpha, gamma, pixels, classes, ldc, mean, partials, loss,
+                   accumulate, true, ignore_index, stream);
 }
 
 extern "C" int udaseg_focal_bwd(const float* logits, const int64_t* target, const float* class_weights, float alpha, float gamma,
                                 const float* grad_out, float weight, int64_t pixels, int classes, int ldc, float* dlogits,
                                 int accumulate, void* stream) {
-  int rc = check_seg(logits, pixels, classes, ldc, "focal_bwd");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && dlogits, "focal_bwd: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  SEG_DISPATCH(focal_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)logits, target, class_weights, alpha, gamma, grad_out, weight,
-               pixels, classes, (f32x4*)dlogits, accumulate, (int64_t)0)
-  UDASEG_LAUNCH_CHECK("focal_bwd launch");
-  return UDASEG_OK;
+  return focal_bwd("focal_bwd", logits, target, class_weights, alpha, gamma, grad_out, weight, pixels, classes, ldc, dlogits,
+                   accumulate, false, 0, stream);
+}
+extern "C" int udaseg_focal_bwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
+                                       float gamma, const float* grad_out, float weight, int64_t pixels, int classes, int ldc,
+                                       float* dlogits, int accumulate, int64_t ignore_index, void* stream) {
+  return focal_bwd("focal_bwd_ignore", logits, target, class_weights, alpha, gamma, grad_out, weight, pixels, classes, ldc, dlogits,
+                   accumulate, true, ignore_index, stream);
 }
 
 extern "C" int udaseg_consistency_fwd(const float* z1, const float* z2, float temperature, int batch, int64_t pixels, int classes,
@@ -434,7 +478,11 @@ extern "C" int udaseg_consistency_fwd(const float* z1, const float* z2, float te
   UDASEG_CHECK_ARG(z2 && partials && loss && batch > 0 && temperature > 0.f, "consistency_fwd: bad arguments");
   hipStream_t st = as_stream(stream);
   const int grid = grid_pix(pixels);
-  SEG_DISPATCH(consistency_fwd_kernel, dim3(grid), (const f32x4*)z1, (const f32x4*)z2, 1.f / temperature, pixels, classes, partials)
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(consistency_fwd_kernel<decltype(w)::value>, dim3(grid), dim3(256), 0, st, (const f32x4*)z1,
+                           (const f32x4*)z2, 1.f / temperature, pixels, classes, partials);
+      }))
+    return unsupported_width("consistency_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("consistency_fwd launch");
   // (KL(p2||p1) + KL(p1||p2)) / 2, each 'batchmean' = sum / batch
   hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, 2.0 * (double)batch, loss, 0);
@@ -448,67 +496,12 @@ extern "C" int udaseg_consistency_bwd(const float* z1, const float* z2, float te
   int rc = check_seg(z1, pixels, classes, ldc, "consistency_bwd");
   if (rc) return rc;
   UDASEG_CHECK_ARG(z2 && (d1 || d2) && batch > 0 && temperature > 0.f, "consistency_bwd: bad arguments");
-  hipStream_t st = as_stream(stream);
-  SEG_DISPATCH(consistency_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)z1, (const f32x4*)z2, 1.f / temperature, grad_out,
-               weight, batch, pixels, classes, (f32x4*)d1, (f32x4*)d2, accumulate)
+  if (!dispatch_width<8>(ldc / 4, [&](auto w) {
+        hipLaunchKernelGGL(consistency_bwd_kernel<decltype(w)::value>, dim3(grid_pix(pixels)), dim3(256), 0, as_stream(stream),
+                           (const f32x4*)z1, (const f32x4*)z2, 1.f / temperature, grad_out, weight, batch, pixels, classes,
+                           (f32x4*)d1, (f32x4*)d2, accumulate);
+      }))
+    return unsupported_width("consistency_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("consistency_bwd launch");
-  return UDASEG_OK;
-}
-
-// ---- the Dice / focal entry points with void labels: the same launches with ignore_index (any int64) honoured ----------------
-extern "C" int udaseg_dice_fwd_ignore(const float* logits, const int64_t* target, int batch, int64_t pix_per_image, int classes,
-                                      int ldc, float smooth, float eps, int pooled, double* sums, float* coef, float* loss,
-                                      int64_t ignore_index, void* stream) {
-  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_fwd_ignore");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && sums && coef && loss && batch > 0, "dice_fwd_ignore: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  const int gx = (int)((pix_per_image + 255) / 256 > 256 ? 256 : (pix_per_image + 255) / 256);
-  SEG_DISPATCH_IGN(dice_stats_kernel, dim3(gx, batch), (const f32x4*)logits, target, pix_per_image, classes, sums, ignore_index)
-  UDASEG_LAUNCH_CHECK("dice_stats launch");
-  hipLaunchKernelGGL(dice_finish_kernel, dim3(1), dim3(64), 0, st, sums, batch, classes, smooth, eps, pooled, loss, coef);
-  UDASEG_LAUNCH_CHECK("dice_finish launch");
-  return UDASEG_OK;
-}
-
-extern "C" int udaseg_dice_bwd_ignore(const float* logits, const int64_t* target, const float* coef, const float* grad_out,
-                                      float weight, int batch, int64_t pix_per_image, int classes, int ldc, float* dlogits,
-                                      int accumulate, int64_t ignore_index, void* stream) {
-  int rc = check_seg(logits, pix_per_image, classes, ldc, "dice_bwd_ignore");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && coef && dlogits && batch > 0, "dice_bwd_ignore: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  SEG_DISPATCH_IGN(dice_bwd_kernel, dim3(grid_pix(pix_per_image * batch)), (const f32x4*)logits, target, coef, grad_out, weight,
-                   pix_per_image, batch, classes, (f32x4*)dlogits, accumulate, ignore_index)
-  UDASEG_LAUNCH_CHECK("dice_bwd launch");
-  return UDASEG_OK;
-}
-
-extern "C" int udaseg_focal_fwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
-                                       float gamma, int64_t pixels, int classes, int ldc, int mean, double* partials, float* loss,
-                                       int accumulate, int64_t ignore_index, void* stream) {
-  int rc = check_seg(logits, pixels, classes, ldc, "focal_fwd_ignore");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && partials && loss, "focal_fwd_ignore: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  const int grid = grid_pix(pixels);
-  SEG_DISPATCH_IGN(focal_fwd_kernel, dim3(grid), (const f32x4*)logits, target, class_weights, alpha, gamma, pixels, classes, partials,
-                   ignore_index)
-  UDASEG_LAUNCH_CHECK("focal_fwd launch");
-  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
-  UDASEG_LAUNCH_CHECK("focal_finish launch");
-  return UDASEG_OK;
-}
-
-extern "C" int udaseg_focal_bwd_ignore(const float* logits, const int64_t* target, const float* class_weights, float alpha,
-                                       float gamma, const float* grad_out, float weight, int64_t pixels, int classes, int ldc,
-                                       float* dlogits, int accumulate, int64_t ignore_index, void* stream) {
-  int rc = check_seg(logits, pixels, classes, ldc, "focal_bwd_ignore");
-  if (rc) return rc;
-  UDASEG_CHECK_ARG(target && dlogits, "focal_bwd_ignore: NULL pointer");
-  hipStream_t st = as_stream(stream);
-  SEG_DISPATCH_IGN(focal_bwd_kernel, dim3(grid_pix(pixels)), (const f32x4*)logits, target, class_weights, alpha, gamma, grad_out,
-                   weight, pixels, classes, (f32x4*)dlogits, accumulate, ignore_index)
-  UDASEG_LAUNCH_CHECK("focal_bwd launch");
   return UDASEG_OK;
 }

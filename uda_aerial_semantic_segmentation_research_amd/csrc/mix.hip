@@ -48,12 +48,6 @@ __global__ __launch_bounds__(SEL_THREADS) void classmix_select_kernel(const unsi
   sel[i] = (int32_t)bits;
 }
 
-__device__ __forceinline__ unsigned int mix_wave_sum(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
 struct MixBox { int y0, x0, y1, x1; };
 
 // what a block forms once: its sample, the selection among the classes, the box (empty without boxes)
@@ -80,9 +74,9 @@ __device__ __forceinline__ bool mix_pasted(const MixBlock& k, uint32_t s, int y,
 
 __device__ __forceinline__ void mix_flush(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int* cnt,
                                           unsigned long long* __restrict__ counts, int i) {
-  c0 = mix_wave_sum(c0);
-  c1 = mix_wave_sum(c1);
-  c2 = mix_wave_sum(c2);
+  c0 = wave_sum_u32(c0);
+  c1 = wave_sum_u32(c1);
+  c2 = wave_sum_u32(c2);
   if ((threadIdx.x & 63) == 0) {
     if (c0) atomicAdd(&cnt[0], c0);
     if (c1) atomicAdd(&cnt[1], c1);

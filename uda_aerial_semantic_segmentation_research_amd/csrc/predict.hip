@@ -13,7 +13,7 @@
 //
 // Tile grid (one axis of length L, effective tile t, stride s): origin o_i = max(0, min(i*s, L - t)) for i = 0 .. n-1,
 // n = 1 if L <= t else ceil((L - t) / s) + 1.  Tiles are numbered raster, row-major: k = i*cols + j.
-#include "common.h"
+#include "scores_common.h"
 
 namespace udaseg {
 
@@ -81,8 +81,7 @@ __global__ __launch_bounds__(BLEND_BX * BLEND_BY) void predict_blend_kernel(
   if (x >= x1 || y >= y1) return;
   const size_t pix = (size_t)y * w + x;
   f32x4 a[NV];
-#pragma unroll
-  for (int q = 0; q < NV; ++q) a[q] = *reinterpret_cast<const f32x4*>(acc + pix * ldp + 4 * q);
+  load_row<NV>(acc + pix * ldp, a);
   float ws = wsum[pix];
   bool touched = false;
   // candidate tile rows / columns: every i with o_i <= y < o_i + th lies in [ (y-th)/s , y/s + 1 ] (the +1 catches the flush
@@ -108,8 +107,7 @@ __global__ __launch_bounds__(BLEND_BX * BLEND_BY) void predict_blend_kernel(
         const int yy = (code & 2) ? th - 1 - ay : ay, xx = (code & 4) ? tw - 1 - ax : ax;
         const float* row = logits + ((((size_t)(k - first) * nv + v) * th + yy) * tw + xx) * ldc;
         f32x4 l[NV];
-#pragma unroll
-        for (int q = 0; q < NV; ++q) l[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);
+        load_row<NV>(row, l);
         float m = -INFINITY;
 #pragma unroll
         for (int q = 0; q < NV; ++q)
@@ -145,6 +143,8 @@ __global__ __launch_bounds__(BLEND_BX * BLEND_BY) void predict_blend_kernel(
   wsum[pix] = ws;
 }
 
+// The row is read, divided and written back in place, so its load stays written out here: with load_row the compiler no longer splits
+// the pixel loop on `wsum`, and the kernel is 8 % slower at a 4000 x 6000 frame (profiles/score_dispatch_refactor.txt).
 template <int NV>
 __global__ __launch_bounds__(256) void predict_finish_kernel(float* __restrict__ probs, int ldc, const float* __restrict__ wsum,
                                                              int64_t pixels, int classes, int64_t* __restrict__ labels) {
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void predict_finish_kernel(float* __restrict__
     float* row = probs + p * ldc;
     f32x4 v[NV];
 #pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);
+    for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);   // not load_row: see above
     if (wsum) {
       const float ws = wsum[p];
 #pragma unroll
@@ -161,16 +161,8 @@ __global__ __launch_bounds__(256) void predict_finish_kernel(float* __restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[q][e] = 4 * q + e < classes ? v[q][e] / ws : 0.f;
     }
-    float best = -INFINITY;
-    int bi = 0;
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        if (c < classes && (c == 0 || v[q][e] > best)) { best = v[q][e]; bi = c; }
-      }
-    labels[p] = bi;
+    float best;
+    labels[p] = first_max<NV>(v, classes, best);
     if (wsum) {
 #pragma unroll
       for (int q = 0; q < NV; ++q) *reinterpret_cast<f32x4*>(row + 4 * q) = v[q];
@@ -239,7 +231,7 @@ extern "C" int udaseg_predict_gather_u8(const uint8_t* image, int h, int w, int 
   int nv;
   const uint32_t codes = pack_views(views, &nv);
   const int tp = th * tw;
-  const int gx = cdiv(tp, 256) > 256 ? 256 : cdiv(tp, 256);
+  const int gx = capped_grid(tp, 256, 256);
   hipStream_t st = as_stream(stream);
   if (out_bf16)
     hipLaunchKernelGGL(predict_gather_kernel<true>, dim3(gx, tiles * nv), dim3(256), 0, st, image, h, w, th, tw, cols, sy, sx,
@@ -253,30 +245,13 @@ extern "C" int udaseg_predict_gather_u8(const uint8_t* image, int h, int w, int 
   return UDASEG_OK;
 }
 
-#define PREDICT_CHECK_CLASSES(what, ld)                                                                                       \
-  UDASEG_CHECK_ARG(ld >= 4 && ld % 4 == 0, what ": " #ld " must be a positive multiple of 4, got %d", ld);                   \
-  UDASEG_CHECK_ARG(classes >= 1 && classes <= 32, what ": classes must lie in 1..32, got %d", classes);                      \
-  UDASEG_CHECK_ARG(classes <= ld, what ": classes %d > " #ld " %d", classes, ld)
-
-#define PREDICT_DISPATCH_NV(nv4, KERNEL, ...)                                                                                 \
-  switch (nv4) {                                                                                                               \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                                                                 \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                                                                 \
-    case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                                                                 \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                                                                 \
-    case 5: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;                                                                 \
-    case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;                                                                 \
-    case 7: hipLaunchKernelGGL(KERNEL<7>, __VA_ARGS__); break;                                                                 \
-    default: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;                                                                \
-  }
-
 extern "C" int udaseg_predict_blend(const float* logits, int ldc, int h, int w, int th, int tw, int rows, int cols, int sy, int sx,
                                     int first, int tiles, int views, int classes, const float* win_y, const float* win_x,
                                     float* acc, int ldp, float* wsum, void* stream) {
   UDASEG_CHECK_ARG(logits && win_y && win_x && acc && wsum, "predict_blend: bad arguments");
-  PREDICT_CHECK_CLASSES("predict_blend", ldc);
-  PREDICT_CHECK_CLASSES("predict_blend", ldp);
   PREDICT_CHECK_GRID("predict_blend");
+  if (!scores_args_ok("predict_blend", (int64_t)h * w, classes, ldc)) return UDASEG_E_BADARG;
+  if (!scores_args_ok("predict_blend", (int64_t)h * w, classes, ldp, INT_MAX, "ldp")) return UDASEG_E_BADARG;
   int nv;
   const uint32_t codes = pack_views(views, &nv);
   // the batch's bounding box inside the frame: its tile rows, and its tile columns when it lies in one row
@@ -289,30 +264,39 @@ extern "C" int udaseg_predict_blend(const float* logits, int ldc, int h, int w, 
     x1 = std::min(w, std::max(0, std::min((k1 % cols) * sx, w - tw)) + tw);
   }
   const dim3 grid(cdiv(x1 - x0, BLEND_BX), cdiv(y1 - y0, BLEND_BY));
-  PREDICT_DISPATCH_NV(cdiv(classes, 4), predict_blend_kernel, grid, dim3(BLEND_BX, BLEND_BY), 0, as_stream(stream), logits, ldc,
-                      h, w, th, tw, rows, cols, sy, sx, first, tiles, codes, nv, classes, win_y, win_x, acc, ldp, wsum, y0, x0,
-                      y1, x1);
+  if (!dispatch_width<8>(cdiv(classes, 4), [&](auto nw) {
+        hipLaunchKernelGGL(predict_blend_kernel<decltype(nw)::value>, grid, dim3(BLEND_BX, BLEND_BY), 0, as_stream(stream), logits,
+                           ldc, h, w, th, tw, rows, cols, sy, sx, first, tiles, codes, nv, classes, win_y, win_x, acc, ldp, wsum, y0,
+                           x0, y1, x1);
+      }))
+    return unsupported_width("predict_blend", "classes", classes);
   UDASEG_LAUNCH_CHECK("predict_blend launch");
   return UDASEG_OK;
 }
 
 extern "C" int udaseg_predict_finish(float* probs, const float* wsum, int64_t pixels, int classes, int ldc, int64_t* labels,
                                      void* stream) {
-  UDASEG_CHECK_ARG(probs && labels && pixels > 0, "predict_finish: bad arguments");
-  PREDICT_CHECK_CLASSES("predict_finish", ldc);
-  const int64_t blocks = std::min<int64_t>(cdiv64(pixels, 256), 8192);
-  PREDICT_DISPATCH_NV(cdiv(classes, 4), predict_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), probs,
-                      ldc, wsum, pixels, classes, labels);
+  UDASEG_CHECK_ARG(probs && labels, "predict_finish: bad arguments");
+  if (!scores_args_ok("predict_finish", pixels, classes, ldc)) return UDASEG_E_BADARG;
+  const int blocks = capped_grid(pixels, 256, 8192);
+  if (!dispatch_width<8>(cdiv(classes, 4), [&](auto nw) {
+        hipLaunchKernelGGL(predict_finish_kernel<decltype(nw)::value>, dim3(blocks), dim3(256), 0, as_stream(stream), probs, ldc, wsum,
+                           pixels, classes, labels);
+      }))
+    return unsupported_width("predict_finish", "classes", classes);
   UDASEG_LAUNCH_CHECK("predict_finish launch");
   return UDASEG_OK;
 }
 
 extern "C" int udaseg_predict_threshold(const float* logits, int n, int hw, int classes, int ldc, float* out, void* stream) {
   UDASEG_CHECK_ARG(logits && out && n > 0 && hw > 0 && n < 65536, "predict_threshold: bad arguments");
-  PREDICT_CHECK_CLASSES("predict_threshold", ldc);
-  const int gx = cdiv(hw, 256) > 1024 ? 1024 : cdiv(hw, 256);
-  PREDICT_DISPATCH_NV(cdiv(classes, 4), predict_threshold_kernel, dim3(gx, n), dim3(256), 0, as_stream(stream), logits, ldc, hw,
-                      classes, out);
+  if (!scores_args_ok("predict_threshold", (int64_t)n * hw, classes, ldc)) return UDASEG_E_BADARG;
+  const int gx = capped_grid(hw, 256, 1024);
+  if (!dispatch_width<8>(cdiv(classes, 4), [&](auto nw) {
+        hipLaunchKernelGGL(predict_threshold_kernel<decltype(nw)::value>, dim3(gx, n), dim3(256), 0, as_stream(stream), logits, ldc, hw,
+                           classes, out);
+      }))
+    return unsupported_width("predict_threshold", "classes", classes);
   UDASEG_LAUNCH_CHECK("predict_threshold launch");
   return UDASEG_OK;
 }

@@ -6,7 +6,7 @@
 //
 // The shared definition (pixel_conf below, used by BOTH pixel kernels, so that histogram and labelling cannot disagree).
 // scores: padded NHWC fp32 [pixels][ldc], ldc % 4 == 0, 0 < classes <= 32, classes <= ldc; only channels < classes count.
-//   probs == 0 (logits z):     c^ = first maximum of z (the comparison rule of score_hist_kernel), m = z[c^],
+//   probs == 0 (logits z):     c^ = first maximum of z (first_max of scores_common.h), m = z[c^],
 //                              S = sum_{c < classes} expf(z_c - m) in fp32 (four partial sums, channel c in sum c % 4,
 //                              folded as (s0 + s1) + (s2 + s3): a third of the rounding of one chain), confidence p = 1 / S
 //   probs == 1 (probabilities q, predict_large's accumulator view):   c^ = first maximum of q, p = q[c^]
@@ -26,7 +26,7 @@
 // scores, hundreds of clocks of a CU's share of the memory rate, against at most 64 clocks when every lane hits the same top
 // bin; score_hist_kernel issues 23 such atomics per pixel and runs at the memory rate (profiles/curves_bench.txt).
 // tools/bench_pseudo.py reports both pixel kernels against a device copy of the same bytes.
-#include "common.h"
+#include "scores_common.h"
 
 namespace udaseg {
 
@@ -39,21 +39,12 @@ struct PixelConf {
 template <int NV>
 __device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, int classes, int probs) {
   f32x4 v[NV];
-#pragma unroll
-  for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);
-  float m = -INFINITY;
-  int am = 0;
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = 4 * q + e;
-      if (c < classes && (c == 0 || v[q][e] > m)) { m = v[q][e]; am = c; }
-    }
+  load_row<NV>(row, v);
+  float m;
   PixelConf r;
-  r.cls = am;
+  r.cls = first_max<NV>(v, classes, m);
   if (probs) {
-    bool nan = false;                                      // the comparison above steps over a NaN beyond channel 0
+    bool nan = false;                                      // first_max steps over a NaN beyond channel 0
 #pragma unroll
     for (int q = 0; q < NV; ++q)
 #pragma unroll
@@ -75,12 +66,6 @@ __device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, i
 }
 
 __device__ __forceinline__ int conf_bin(float p, int bins) { return min((int)floorf(p * (float)bins), bins - 1); }
-
-__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
-  return v;
-}
 
 constexpr int CH_CELLS = 32768;
 constexpr int CH_THREADS = 1024;
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(CH_THREADS) void conf_hist_kernel(const float* __re
     if (c >= 0 && c < nc) atomicAdd(&cells[c * bins + conf_bin(r.p, bins)], 1u);
   }
   if (blockIdx.y == 0) {
-    bad = wave_sum_u(bad);
+    bad = wave_sum_u32(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&cells[tab], bad);
   }
   __syncthreads();
@@ -232,8 +217,8 @@ __global__ __launch_bounds__(PL_THREADS) void pseudo_labels_kernel(const float* 
       }
     }
   }
-  nvoid = wave_sum_u(nvoid);
-  nbad = wave_sum_u(nbad);
+  nvoid = wave_sum_u32(nvoid);
+  nbad = wave_sum_u32(nbad);
   if (lane == 0) {
     if (nvoid) atomicAdd(&cnt[32], nvoid);
     if (nbad) atomicAdd(&cnt[33], nbad);
@@ -247,15 +232,13 @@ __global__ __launch_bounds__(PL_THREADS) void pseudo_labels_kernel(const float* 
   }
 }
 
-static bool pseudo_bins_supported(int bins) { return bins == 256 || bins == 512 || bins == 1024 || bins == 2048 || bins == 4096; }
-
-static bool scores_args_ok(const char* who, const void* scores, int64_t pixels, int classes, int ldc, int probs, int bins) {
-  if (!(pixels > 0 && pixels < ((int64_t)1 << 31) && classes > 0 && classes <= 32 && classes <= ldc && ldc % 4 == 0)) {
-    set_error("%s: need 0 < pixels < 2^31, 0 < classes <= 32, classes <= ldc, ldc %% 4 == 0 (pixels=%lld classes=%d ldc=%d)", who,
-              (long long)pixels, classes, ldc);
+static bool pseudo_args_ok(const char* who, const void* scores, int64_t pixels, int classes, int ldc, int probs, int bins) {
+  if (!scores_args_ok(who, pixels, classes, ldc)) return false;
+  if (pixels >= ((int64_t)1 << 31)) {
+    set_error("%s: need pixels < 2^31 (pixels=%lld)", who, (long long)pixels);
     return false;
   }
-  if (!pseudo_bins_supported(bins)) {
+  if (!hist_bins_supported(bins)) {
     set_error("%s: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", who, bins);
     return false;
   }
@@ -274,28 +257,10 @@ static bool scores_args_ok(const char* who, const void* scores, int64_t pixels, 
 
 using namespace udaseg;
 
-#define PSEUDO_DISPATCH_NV(nv, kernel, grid, block, lds, st, ...)                       \
-  switch (nv) {                                                                         \
-    case 1: hipLaunchKernelGGL(kernel<1>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 2: hipLaunchKernelGGL(kernel<2>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 3: hipLaunchKernelGGL(kernel<3>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 4: hipLaunchKernelGGL(kernel<4>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 5: hipLaunchKernelGGL(kernel<5>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 6: hipLaunchKernelGGL(kernel<6>, grid, block, lds, st, __VA_ARGS__); break;    \
-    case 7: hipLaunchKernelGGL(kernel<7>, grid, block, lds, st, __VA_ARGS__); break;    \
-    default: hipLaunchKernelGGL(kernel<8>, grid, block, lds, st, __VA_ARGS__); break;   \
-  }
-
-template <int NV>
-static hipError_t conf_hist_allow_lds() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(conf_hist_kernel<NV>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             CH_LDS_MAX);
-}
-
 extern "C" int udaseg_conf_hist(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, int64_t* hist,
                                 int64_t* nonfinite, void* stream) {
   UDASEG_CHECK_ARG(scores && hist && nonfinite, "conf_hist: NULL pointer");
-  if (!scores_args_ok("conf_hist", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
+  if (!pseudo_args_ok("conf_hist", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
   hipStream_t st = as_stream(stream);
   const int nv = cdiv(classes, 4);
   const int cg = min(classes, CH_CELLS / bins);            // classes per group
@@ -305,16 +270,10 @@ extern "C" int udaseg_conf_hist(const float* scores, int64_t pixels, int classes
   static std::atomic<bool> attr_done[9];
   if (lds > 48 * 1024 && !attr_done[nv]) {
     hipError_t e = hipSuccess;
-    switch (nv) {
-      case 1: e = conf_hist_allow_lds<1>(); break;
-      case 2: e = conf_hist_allow_lds<2>(); break;
-      case 3: e = conf_hist_allow_lds<3>(); break;
-      case 4: e = conf_hist_allow_lds<4>(); break;
-      case 5: e = conf_hist_allow_lds<5>(); break;
-      case 6: e = conf_hist_allow_lds<6>(); break;
-      case 7: e = conf_hist_allow_lds<7>(); break;
-      default: e = conf_hist_allow_lds<8>(); break;
-    }
+    dispatch_width<8>(nv, [&](auto w) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conf_hist_kernel<decltype(w)::value>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS_MAX);
+    });
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conf_hist)");
     attr_done[nv] = true;
   }
@@ -322,8 +281,11 @@ extern "C" int udaseg_conf_hist(const float* scores, int64_t pixels, int classes
   const int64_t want = cdiv64(pixels, CH_THREADS);
   if (gx > want) gx = (int)want;
   if (gx < 1) gx = 1;
-  PSEUDO_DISPATCH_NV(nv, conf_hist_kernel, dim3(gx, groups), dim3(CH_THREADS), lds, st, scores, pixels, classes, ldc, probs, bins, cg,
-                     tab, (unsigned long long*)hist, (unsigned long long*)nonfinite);
+  if (!dispatch_width<8>(nv, [&](auto w) {
+        hipLaunchKernelGGL(conf_hist_kernel<decltype(w)::value>, dim3(gx, groups), dim3(CH_THREADS), lds, st, scores, pixels, classes,
+                           ldc, probs, bins, cg, tab, (unsigned long long*)hist, (unsigned long long*)nonfinite);
+      }))
+    return unsupported_width("conf_hist", "classes", classes);
   UDASEG_LAUNCH_CHECK("conf_hist launch");
   return UDASEG_OK;
 }
@@ -332,7 +294,7 @@ extern "C" int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bi
                                         int32_t* thr_bins, int64_t* support, void* stream) {
   UDASEG_CHECK_ARG(hist && portion && thr_bins && support, "pseudo_thresholds: NULL pointer");
   UDASEG_CHECK_ARG(classes > 0 && classes <= 32, "pseudo_thresholds: need 0 < classes <= 32 (classes=%d)", classes);
-  UDASEG_CHECK_ARG(pseudo_bins_supported(bins), "pseudo_thresholds: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
+  UDASEG_CHECK_ARG(hist_bins_supported(bins), "pseudo_thresholds: bins must be 256, 512, 1024, 2048 or 4096 (bins=%d)", bins);
   UDASEG_CHECK_ARG(0 <= k_floor && k_floor <= k_cap && k_cap <= bins - 1,
                    "pseudo_thresholds: need 0 <= k_floor <= k_cap <= bins - 1 (k_floor=%d k_cap=%d bins=%d)", k_floor, k_cap, bins);
   hipLaunchKernelGGL(pseudo_thresholds_kernel, dim3(classes), dim3(PT_THREADS), 0, as_stream(stream), (const unsigned long long*)hist,
@@ -345,14 +307,16 @@ extern "C" int udaseg_pseudo_labels(const float* scores, int64_t pixels, int cla
                                     const int32_t* thr_bins, int void_label, uint8_t* labels, float* conf, int64_t* counts,
                                     void* stream) {
   UDASEG_CHECK_ARG(scores && thr_bins && labels && counts, "pseudo_labels: NULL pointer");
-  if (!scores_args_ok("pseudo_labels", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
+  if (!pseudo_args_ok("pseudo_labels", scores, pixels, classes, ldc, probs, bins)) return UDASEG_E_BADARG;
   UDASEG_CHECK_ARG(void_label >= classes && void_label <= 255,
                    "pseudo_labels: need classes <= void_label <= 255 (void_label=%d classes=%d)", void_label, classes);
-  const int64_t want = cdiv64(cdiv64(pixels, 256), PL_THREADS / 64);
-  const int gx = (int)(want > PL_MAX_BLOCKS ? PL_MAX_BLOCKS : want);
+  const int gx = capped_grid(cdiv64(pixels, 256), PL_THREADS / 64, PL_MAX_BLOCKS);
   const int vec_ok = (reinterpret_cast<uintptr_t>(labels) & 3) == 0;
-  PSEUDO_DISPATCH_NV(cdiv(classes, 4), pseudo_labels_kernel, dim3(gx), dim3(PL_THREADS), 0, as_stream(stream), scores, pixels, classes,
-                     ldc, probs, bins, thr_bins, void_label, labels, conf, (unsigned long long*)counts, vec_ok);
+  if (!dispatch_width<8>(cdiv(classes, 4), [&](auto w) {
+        hipLaunchKernelGGL(pseudo_labels_kernel<decltype(w)::value>, dim3(gx), dim3(PL_THREADS), 0, as_stream(stream), scores, pixels,
+                           classes, ldc, probs, bins, thr_bins, void_label, labels, conf, (unsigned long long*)counts, vec_ok);
+      }))
+    return unsupported_width("pseudo_labels", "classes", classes);
   UDASEG_LAUNCH_CHECK("pseudo_labels launch");
   return UDASEG_OK;
 }

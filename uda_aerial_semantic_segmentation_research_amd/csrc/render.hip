@@ -70,12 +70,6 @@ __device__ __forceinline__ unsigned int blend_px(unsigned int b, unsigned int c,
   return r | (g << 8) | (bl << 16);
 }
 
-__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
 // BASE: UDASEG_RENDER_BASE_*.  Pixels are held as packed words r | g << 8 | b << 16.
 template <bool I64, int BASE, bool OUTLINE, bool COUNTS, bool TRUTH>
 __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {

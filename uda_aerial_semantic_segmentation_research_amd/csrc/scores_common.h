@@ -1,0 +1,72 @@
+// Shared by every kernel that walks a padded NHWC buffer of per-pixel class scores: [pixels][ldc] fp32, classes <= ldc,
+// ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, curves.hip, pseudo.hip, predict.hip).  Such a kernel is a
+// template on its row width in f32x4 vectors -- LDC4 = ldc / 4 where the width is also the row stride, NV = cdiv(classes, 4) where
+// ldc stays a runtime argument -- so here are the one width dispatcher, the one row reader and the one tie rule of the winner.
+#pragma once
+#include <limits.h>
+#include <type_traits>
+#include <utility>
+
+#include "common.h"
+
+namespace udaseg {
+
+template <typename F, int... I>
+static inline bool dispatch_width_seq(int width, F& f, std::integer_sequence<int, I...>) {
+  return ((width == I + 1 && (f(std::integral_constant<int, I + 1>{}), true)) || ...);
+}
+// f(std::integral_constant<int, W>{}) for the W in 1..MAXW equal to width; false (and no call) when there is none.
+template <int MAXW, typename F>
+static inline bool dispatch_width(int width, F&& f) {
+  return dispatch_width_seq(width, f, std::make_integer_sequence<int, MAXW>{});
+}
+static inline int unsupported_width(const char* who, const char* what, int value) {
+  set_error("%s: unsupported %s %d", who, what, value);
+  return UDASEG_E_UNSUPPORTED;
+}
+
+// The first NV vectors of one pixel's row, from a typed pointer (the LDC4 kernels: row = logits + p * LDC4) or a float one.
+template <int NV>
+__device__ __forceinline__ void load_row(const f32x4* row, f32x4 (&v)[NV]) {
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = row[q];
+}
+template <int NV>
+__device__ __forceinline__ void load_row(const float* row, f32x4 (&v)[NV]) {
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = *reinterpret_cast<const f32x4*>(row + 4 * q);
+}
+
+// THE tie rule of PseudoLabeler, confusion_matrix, ScoreHistogram and predict_large, torch.argmax's: the first maximal channel
+// below `classes`.  Channel 0 seeds the maximum whatever it holds; a NaN beyond channel 0 never compares greater and is stepped over.
+// (The running maximum is a local and every score is read once: written on `best` directly the compiler kept branches where the
+// kernels' own loops had selects, profiles/score_dispatch_refactor.txt.)
+template <int NV>
+__device__ __forceinline__ int first_max(const f32x4 (&v)[NV], int classes, float& best) {
+  float m = -INFINITY;
+  int am = 0;
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * q + e;
+      const float x = v[q][e];
+      if (c < classes && (c == 0 || x > m)) { m = x; am = c; }
+    }
+  best = m;
+  return am;
+}
+
+// The shape of a score buffer whose winner is taken (at most 32 classes: the per-block class tables are that long).
+// ld_name: what the entry point calls the row stride.
+static inline bool scores_args_ok(const char* who, int64_t pixels, int classes, int ld, int max_ld = INT_MAX,
+                                  const char* ld_name = "ldc") {
+  if (pixels > 0 && classes > 0 && classes <= 32 && classes <= ld && ld % 4 == 0 && ld <= max_ld) return true;
+  char limit[16] = "";
+  if (max_ld != INT_MAX) snprintf(limit, sizeof limit, " <= %d", max_ld);
+  set_error("%s: need 0 < pixels, 0 < classes <= 32, classes <= %s%s, %s %% 4 == 0 (pixels=%lld classes=%d %s=%d)", who, ld_name,
+            limit, ld_name, (long long)pixels, classes, ld_name, ld);
+  return false;
+}
+
+}  // namespace udaseg
