@@ -347,6 +347,33 @@ int udaseg_consistency_bwd(const float* z1, const float* z2, float temperature, 
                            int batch, int64_t pixels, int classes, int ldc, float* d1, float* d2, int accumulate,
                            void* stream);
 
+/* ---- output-space adaptation (AdvEnt, Vu et al., CVPR 2019; maximum squares, Chen et al., ICCV 2019), csrc/advent.hip ----
+ * Same logits layout as above: fp32 [pixels][ldc], 2 <= classes <= ldc <= 32, ldc % 4 == 0 (log C divides, so classes >= 2);
+ * only lanes < classes are read, the pad lanes may hold any finite junk.  With s = 1 / log(classes), lp = log_softmax(z),
+ * p = exp(lp):
+ *   I_c = p_c > 0 ? -s * p_c * lp_c : 0      weighted self-information; a lane whose probability is 0 (underflow, a -inf logit)
+ *                                            contributes exactly 0 and gets a gradient of exactly 0 -- it is never 0 * inf
+ *   H   = sum_c I_c                          normalised entropy, in [0, 1]
+ * udaseg_selfinfo_fwd: maps[pixels][cpad] (fp32, or bf16 when out_bf16 != 0; classes <= cpad <= 32, cpad % 4 == 0 for fp32 and
+ * cpad % 8 == 0 for bf16; cpad may differ from ldc) = I_c in the lanes < classes and exactly 0 in the lanes [classes, cpad): a
+ * convolution reads this buffer in place.  entropy[pixels] (fp32, NULL = not wanted) = H. */
+int udaseg_selfinfo_fwd(const float* logits, int64_t pixels, int classes, int ldc, void* maps, int cpad, int out_bf16,
+                        float* entropy, void* stream);
+/* dmaps[pixels][cpad] (fp32, or bf16 when in_bf16 != 0; pad lanes ignored) = the gradient with respect to the maps;
+ * with g_c = -s * (lp_c + 1) * dmaps_c for c < classes:  dlogits[pixels][ldc]_k = p_k * (g_k - sum_c p_c * g_c), pad lanes
+ * written as exactly 0. */
+int udaseg_selfinfo_bwd(const float* logits, const void* dmaps, int64_t pixels, int classes, int ldc, int cpad, int in_bf16,
+                        float* dlogits, void* stream);
+/* The direct part, loss and gradient in ONE pass over the logits (as udaseg_ce_fwd_bwd):
+ *   kind 0, entropy (MinEnt):  loss = (1 / pixels) * sum_p H_p;   dlogits_k = -(s / pixels) * p_k * (lp_k + H_nat),
+ *                              H_nat = -sum_c p_c * lp_c
+ *   kind 1, maximum squares:   loss = -(1 / (2 * pixels)) * sum_p sum_c p_c^2;   dlogits_k = -(1 / pixels) * p_k * (p_k - sum_c p_c^2)
+ * dlogits[pixels][ldc] (NULL = not wanted) is the gradient for an upstream gradient of 1, pad lanes exactly 0; entropy[pixels]
+ * (NULL = not wanted) = H whatever the kind; partials: udaseg_seg_partials() doubles of scratch.  The loss is a fixed-order sum
+ * (no float atomics): the same bits on every call, with and without dlogits / entropy. */
+int udaseg_entropy_loss(const float* logits, int64_t pixels, int classes, int ldc, int kind, double* partials, float* loss,
+                        float* dlogits, float* entropy, void* stream);
+
 /* ---- validation metrics (SegmentationTrainer.calculate_metrics, train.py:225-243; src/analysis/metrics.py:17-29):
  * confusion[t*classes + argmax(logits[p])] += 1 over all pixels (int64, caller-zeroed); pred[p] = argmax (optional).
  * classes <= 32, ldc <= 32. */

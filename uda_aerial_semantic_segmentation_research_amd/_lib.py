@@ -110,6 +110,9 @@ SIGNATURES = {
     "udaseg_focal_bwd": (_I, [_P, _P, _P, _F, _F, _P, _F, _L, _I, _I, _P, _I, _P]),
     "udaseg_consistency_fwd": (_I, [_P, _P, _F, _I, _L, _I, _I, _P, _P, _P]),
     "udaseg_consistency_bwd": (_I, [_P, _P, _F, _P, _F, _I, _L, _I, _I, _P, _P, _I, _P]),
+    "udaseg_selfinfo_fwd": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P]),
+    "udaseg_selfinfo_bwd": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P]),
+    "udaseg_entropy_loss": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "udaseg_argmax_confusion": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "udaseg_score_hist": (_I, [_P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
     "udaseg_curve_finish": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

@@ -377,6 +377,15 @@ OPERANDS = {
     "udaseg_consistency_bwd": [T("z1", f32, "pixels*ldc"), T("z2", f32, "pixels*ldc"), F("temperature"),
                                T("grad_out", f32, 1, True), F("weight"), I("batch"), I("pixels"), I("classes"), I("ldc"),
                                T("d1", f32, "pixels*ldc", True), T("d2", f32, "pixels*ldc", True), I("accumulate"), S],
+    # ---- output-space adaptation: self-information maps [pixels][cpad] (a convolution's in-place input), entropy losses
+    "udaseg_selfinfo_fwd": [T("logits", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"),
+                            T("maps", "(bf16 if out_bf16 else f32)", "pixels*cpad"), I("cpad"), I("out_bf16"),
+                            T("entropy", f32, "pixels", True), S],
+    "udaseg_selfinfo_bwd": [T("logits", f32, "pixels*ldc"), T("dmaps", "(bf16 if in_bf16 else f32)", "pixels*cpad"), I("pixels"),
+                            I("classes"), I("ldc"), I("cpad"), I("in_bf16"), T("dlogits", f32, "pixels*ldc"), S],
+    "udaseg_entropy_loss": [T("logits", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("kind"),
+                            T("partials", f64, "seg_partials()"), T("loss", f32, 1), T("dlogits", f32, "pixels*ldc", True),
+                            T("entropy", f32, "pixels", True), S],
     # ---- discriminator tail
     "udaseg_gap_linear_sigmoid_fwd": [T("z", f32, "n*hw*c"), T("w", f32, "c"), T("b", f32, 1), T("partial", f32, "n*gap_splits(hw)*c"),
                                       T("pooled", f32, "n*c"), T("p", f32, "n"), I("n"), I("hw"), I("c"), S],

@@ -752,6 +752,29 @@ def consistency_bwd(z1, z2, temperature, grad_out, weight, batch, pixels, classe
                                               st), "consistency_bwd")
 
 
+def selfinfo_fwd(logits_base, pixels, classes, ldc, maps, cpad, entropy=None, st=None):
+    """maps [pixels * cpad] fp32 or bf16 = the weighted self-information -p log p / log C of softmax(logits), zeros in the pad
+    lanes; entropy [pixels] fp32 or None = its sum over the classes."""
+    check(ops.udaseg_selfinfo_fwd(logits_base, pixels, classes, ldc, maps, cpad, int(maps.dtype == torch.bfloat16), entropy, st),
+          "selfinfo_fwd")
+
+
+def selfinfo_bwd(logits_base, dmaps, pixels, classes, ldc, cpad, dlogits, st=None):
+    """dlogits [pixels * ldc] fp32 = the gradient of the logits from dmaps [pixels * cpad] (fp32 or bf16), the maps' gradient."""
+    check(ops.udaseg_selfinfo_bwd(logits_base, dmaps, pixels, classes, ldc, cpad, int(dmaps.dtype == torch.bfloat16), dlogits, st),
+          "selfinfo_bwd")
+
+
+ENTROPY_KINDS = {"entropy": 0, "max_squares": 1}
+
+
+def entropy_loss(logits_base, pixels, classes, ldc, kind, partials, loss, dlogits=None, entropy=None, st=None):
+    """loss = mean normalised entropy (kind 'entropy') or -mean sum p^2 / 2 ('max_squares') of softmax(logits); dlogits (optional) its
+    gradient for an upstream gradient of 1, made in the same pass; entropy (optional) [pixels] the per-pixel normalised entropy."""
+    check(ops.udaseg_entropy_loss(logits_base, pixels, classes, ldc, ENTROPY_KINDS[kind], partials, loss, dlogits, entropy, st),
+          "entropy_loss")
+
+
 def gap_linear_sigmoid_fwd(z, w, b, st=None):
     n, h, wd, c = z.shape
     hw = h * wd

@@ -527,6 +527,69 @@ class ConsistencyLoss(nn.Module):
         return torch.nn.functional.cosine_similarity(torch.softmax(pred1, dim=1), torch.softmax(pred2, dim=1), dim=1)
 
 
+class _EntropyFunction(torch.autograd.Function):
+    """Entropy / maximum-squares loss of a prediction (csrc/advent.hip).  As ``_CrossEntropyFunction``'s fused branch: when the
+    input needs a gradient it is made in the forward's pass over the logits; backward only scales it if it has to.  A second
+    backward through a retained graph re-runs the entry point."""
+
+    @staticmethod
+    def forward(ctx, logits, kind):
+        n, c, h, w = logits.shape
+        buf, ldc = _padded_nhwc(logits.detach())
+        dev = logits.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        parts = torch.empty(K.seg_partials(), device=dev, dtype=torch.float64)
+        dl = torch.empty((n, h, w, ldc), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        K.entropy_loss(buf, n * h * w, c, ldc, kind, parts, loss, dl)
+        ctx.meta, ctx.fused = (n, c, h, w, ldc, kind), dl
+        ctx.save_for_backward(buf)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, c, h, w, ldc, kind = ctx.meta
+        g = grad_out.detach().to(torch.float32).contiguous()
+        dl, ctx.fused = ctx.fused, None                # consumed: scaled in place below
+        if dl is None:
+            buf, = ctx.saved_tensors
+            dl = torch.empty((n, h, w, ldc), device=buf.device, dtype=torch.float32)
+            K.entropy_loss(buf, n * h * w, c, ldc, kind, torch.empty(K.seg_partials(), device=buf.device, dtype=torch.float64),
+                           torch.empty((), device=buf.device, dtype=torch.float32), dl)
+        K.scale_unless_one(dl, g)
+        return dl.permute(0, 3, 1, 2)[:, :c], None
+
+
+class EntropyLoss(nn.Module):
+    """The direct part of output-space adaptation: a loss of the prediction alone, no labels (target frames).
+
+    ``kind='entropy'`` (MinEnt, Vu et al., CVPR 2019): the mean over the pixels of the normalised entropy
+    ``-sum_c p_c log p_c / log C`` in ``[0, 1]``.  ``kind='max_squares'`` (Chen et al., ICCV 2019): ``-mean_pixels sum_c p_c^2 / 2``,
+    whose gradient does not vanish on the confident pixels the way the entropy's does.  A class whose probability is 0 contributes
+    exactly 0 to the loss and to the gradient.  ``forward(logits [B,C,H,W]) -> scalar``, ``2 <= C <= 32``."""
+
+    def __init__(self, kind="entropy"):
+        super().__init__()
+        if kind not in K.ENTROPY_KINDS:
+            raise ValueError(f"EntropyLoss: kind must be one of {sorted(K.ENTROPY_KINDS)}, got {kind!r}")
+        self.kind = kind
+
+    def extra_repr(self):
+        return f"kind={self.kind!r}"
+
+    def forward(self, logits):
+        _check_prediction("EntropyLoss", logits)
+        return _EntropyFunction.apply(logits, self.kind)
+
+
+def _check_prediction(who, logits):
+    """A prediction the output-space kernels take: on the GPU, [B,C,H,W], 2 <= C <= 32 (log C divides)."""
+    if logits.dim() != 4:
+        raise ValueError(f"{who}: expected predictions [B,C,H,W], got {tuple(logits.shape)}")
+    if not 2 <= logits.shape[1] <= 32:
+        raise ValueError(f"{who}: 2 to 32 classes are supported by the HIP kernels, got {logits.shape[1]}")
+    _need_gpu(logits, who)
+
+
 class FineTuningLoss(nn.Module):
     """Phase-3 objective: ramped consistency + ramped domain confusion (+ Dice on labelled samples when given).
 
