@@ -230,25 +230,27 @@ def stats_ref(ref):
 
 class Grader:
     """Collects the verdicts of one case so that every figure is logged before the first assertion fires."""
+    PREFIX, LEG = "conv-grade", "d_trunc"
+
     def __init__(self, tag, log=print):
         self.tag, self.bad, self.log = tag, [], log
 
     def grade(self, what, got, ref, bf16_out):
         ok, e, A, d_rne, d_trunc, where = verdict(got, ref, bf16_out)
         a_rne = max(MARGIN * d_rne, FLOOR)
-        self.log(f"conv-grade {self.tag} | {what} | {'bf16' if bf16_out else 'fp32'} | e {e:.3e} d_rne {d_rne:.3e} d_trunc {d_trunc:.3e} "
+        self.log(f"{self.PREFIX} {self.tag} | {what} | {'bf16' if bf16_out else 'fp32'} | e {e:.3e} d_rne {d_rne:.3e} {self.LEG} {d_trunc:.3e} "
                  f"bar {A:.3e} e/bar {e / A:.3f} e/bar_rne {e / a_rne:.3f} at {where}")
         if not ok:
             self.bad.append(f"{what}: e {e:.3e} > bar {A:.3e} at {where}")
 
     def exact(self, what, got, want):
         same = np.array_equal(np.asarray(got), np.asarray(want))
-        self.log(f"conv-grade {self.tag} | {what} | {'exact' if same else 'DIFFERS'}")
+        self.log(f"{self.PREFIX} {self.tag} | {what} | {'exact' if same else 'DIFFERS'}")
         if not same:
             self.bad.append(f"{what}: not bit for bit")
 
     def note(self, what, ok, text):
-        self.log(f"conv-grade {self.tag} | {what} | {text}")
+        self.log(f"{self.PREFIX} {self.tag} | {what} | {text}")
         if not ok:
             self.bad.append(f"{what}: {text}")
 
@@ -329,3 +331,380 @@ def fold_factor(gathered, produced, width, no_fold=False):
     if width % f or produced % 8 or (f == 4 and produced > 16):
         return 1
     return f
+
+
+# =================================================================================== the fp32 convolutions on the three-term split
+# csrc/conv_halo_f32x3.hip, conv_up_f32x3.hip, conv_n16_f32x3.hip, conv_stem_f32x3.hip and the X3 instances of conv_igemm.hip,
+# conv_wgrad.hip, conv_wgrad_halo2.hip (tests/test_gpu_conv_f32x3_grade.py).  Operands are ARBITRARY fp32 values.  The second leg of
+# a Ref (stored in ``leg_trunc``, logged as d_x3) is the six-product model: both operands split by oracle/f32x3_ref.py::split3, and
+# for every step of at most 16 K-terms the six products x_i w_j (i + j <= 2, smallest first, the kernels' order) are added ONE MATRIX
+# INSTRUCTION AT A TIME to an fp32 accumulator truncated toward minus infinity after each of them; the steps that
+# negated_groups / up_negated_groups name run on the negated accumulator, which truncates toward plus infinity.
+from oracle.f32x3_ref import negated_groups, split3  # noqa: E402
+
+PAIRS = [(ij - j, j) for ij in (2, 1, 0) for j in range(ij + 1)]          # (term of A, term of B), smallest products first
+SENTINEL = -12345.5                                                     # the guard value around every output buffer
+GUARD = 256
+
+
+class X3Grader(Grader):
+    PREFIX, LEG = "f32x3-grade", "d_x3"
+
+
+def _terms(v):
+    return [t.astype(F64) for t in split3(np.asarray(v, dtype=F32))]
+
+
+def x3_matmul(A, B, steps=None, drop=()):
+    """The six-product model of A @ B.  steps: [(columns of K, negated)] in the kernel's order (None: 16 consecutive terms, no sign
+    pattern); drop: pairs (i, j) left out (mutants)."""
+    sa, sb = _terms(A), _terms(B)
+    kk = np.shape(A)[1]
+    if steps is None:
+        steps = [(slice(j, j + GROUP), False) for j in range(0, kk, GROUP)]
+    acc = np.zeros((np.shape(A)[0], np.shape(B)[1]), dtype=F32)
+    for cols, neg in steps:
+        a, b = [t[:, cols] for t in sa], [t[cols] for t in sb]
+        for i, j in PAIRS:
+            if (i, j) in drop:
+                continue
+            p = a[i] @ b[j]
+            acc = -trunc_to_fp32_toward_minus_inf(-(acc.astype(F64) + p)) if neg else trunc_to_fp32_toward_minus_inf(acc.astype(F64) + p)
+    return acc
+
+
+def x3_exact(A, B, drop=(), flip=None):
+    """sum over the kept pairs of A_i @ B_j in float64, nothing truncated; flip: columns of K accumulated with the wrong sign."""
+    sa, sb = _terms(A), _terms(B)
+    out = np.zeros((np.shape(A)[0], np.shape(B)[1]), dtype=F64)
+    for i, j in PAIRS:
+        if (i, j) not in drop:
+            out += sa[i] @ sb[j]
+            if flip is not None:
+                out -= 2.0 * (sa[i][:, flip] @ sb[j][flip])
+    return out
+
+
+def halo3_steps(gathered, signs=True):
+    """K loop of conv3x3_f32x3_kernel / _ws_kernel over im2col columns (tap (dy, dx) outer, channel inner): 16-channel chunk outer,
+    dx, then dy; group G = 3 chunk + dx carries the sign (csrc/halo_common.h::f3_negated_groups)."""
+    nk16 = cdiv(gathered, 16)
+    neg = negated_groups(nk16) if signs else ()
+    return [((dy * 3 + dx) * gathered + np.arange(16 * c, min(16 * c + 16, gathered)), 3 * c + dx in neg)
+            for c in range(nk16) for dx in range(3) for dy in range(3)]
+
+
+def x3_fwd(x, w, stride, pad, steps=None):
+    mm = lambda A, B: x3_matmul(A, B, steps)  # noqa: E731
+    return Ref(torch_fwd(x, w, stride, pad, torch.float64), torch_fwd(np.abs(x), np.abs(w), stride, pad, torch.float64),
+               torch_fwd(x, w, stride, pad, torch.float32), im2col_fwd(x, w, stride, pad, mm))
+
+
+def x3_dgrad(dy, w, stride, pad, hi, wi, steps=None):
+    mm = lambda A, B: x3_matmul(A, B, steps)  # noqa: E731
+    return Ref(torch_dgrad(dy, w, stride, pad, hi, wi, torch.float64), torch_dgrad(np.abs(dy), np.abs(w), stride, pad, hi, wi, torch.float64),
+               torch_dgrad(dy, w, stride, pad, hi, wi, torch.float32), im2col_dgrad(dy, w, stride, pad, hi, wi, mm))
+
+
+def x3_wgrad(x, dy, k, stride, pad):
+    """K is the pixel axis; the per-tile, per-block sign pattern of the weight-gradient kernels is not restated: no signs."""
+    return Ref(torch_wgrad(x, dy, k, stride, pad, torch.float64), torch_wgrad(np.abs(x), np.abs(dy), k, stride, pad, torch.float64),
+               torch_wgrad(x, dy, k, stride, pad, torch.float32), im2col_wgrad(x, dy, k, stride, pad, x3_matmul))
+
+
+def bn_apply_f32(y, scale, shift, slope):
+    """act(fma(y, scale, shift)) with ONE fp32 rounding of the fused multiply-add, what the in-staging transform and bn_apply store."""
+    z = (np.asarray(y, dtype=F64) * np.asarray(scale, dtype=F64) + np.asarray(shift, dtype=F64)).astype(F32)
+    return z if slope is None else leaky(z, slope, F32)
+
+
+def bn_sums_ref(ref, prev_y, mean, rstd, gamma, beta, slope):
+    """The two BatchNorm-backward sums of the epilogue of a data gradient: per channel sum_p g m and sum_p g m y_hat with
+    m = act'(fma(y, gamma rstd, beta - mean gamma rstd)) and y_hat = (y - mean) rstd, as two Refs: float64 definitions on r64, the
+    magnitudes sum_p mag |m| and sum_p mag |m y_hat|, both legs the sequential fp32 cumsum over the pixels of the model's gradient."""
+    c = ref.r64.shape[-1]
+    y = np.asarray(prev_y, dtype=F32).reshape(-1, c)
+    sc = (np.asarray(gamma, dtype=F32) * np.asarray(rstd, dtype=F32)).astype(F32)
+    sh = (np.asarray(beta, dtype=F32) - (np.asarray(mean, dtype=F32) * sc).astype(F32)).astype(F32)
+    arg = y.astype(F64) * sc + sh
+    m = np.where(arg > 0, 1.0, float(F32(slope)))
+    yh32 = ((y - np.asarray(mean, dtype=F32)).astype(F32) * np.asarray(rstd, dtype=F32)).astype(F32)
+    yh = (y.astype(F64) - np.asarray(mean, dtype=F64)) * np.asarray(rstd, dtype=F64)
+    r, mg, l = ref.r64.reshape(-1, c), ref.mag.reshape(-1, c), ref.leg_trunc.reshape(-1, c)
+    g32 = (l * m.astype(F32)).astype(F32)
+    c1 = np.cumsum(g32, axis=0, dtype=F32)[-1]
+    c2 = np.cumsum((g32 * yh32).astype(F32), axis=0, dtype=F32)[-1]
+    return (Ref((r * m).sum(0), (mg * np.abs(m)).sum(0), c1, c1), Ref((r * m * yh).sum(0), (mg * np.abs(m * yh)).sum(0), c2, c2),
+            float(np.abs(arg).min()))
+
+
+def randn_f32(rng, shape, scale=1.0, binades=0):
+    """randn as fp32 (NOT bf16-representable); binades b: every element times 2^randint(-b / 2, b / 2)."""
+    v = rng.standard_normal(shape) * scale
+    if binades:
+        v = v * np.exp2(rng.integers(-(binades // 2), binades // 2, size=shape))
+    return v.astype(F32)
+
+
+# ----------------------------------------------------------------------------------------- tier A: mutants the bar must reject
+def fwd_mutants(x, w, stride, pad, old=None):
+    """Wrong float64 evaluations of conv(x, w) (+ old): name -> output.  'border tap': the outputs of the last column never see
+    the tap one column to their left (centre row); 'product (0,1)': the first-order product x_0 w_1 is left out everywhere."""
+    x, w = np.asarray(x, dtype=F32), np.asarray(w, dtype=F32)
+    k = w.shape[1]
+    base = im2col_fwd(x, w, stride, pad)
+    add = 0.0 if old is None else np.asarray(old, dtype=F64)
+    out = {}
+    if k >= 2:
+        only = np.zeros_like(w)
+        only[:, k // 2, k // 2 - 1] = w[:, k // 2, k // 2 - 1]
+        m = base.copy()
+        m[:, :, -1] -= im2col_fwd(x, only, stride, pad)[:, :, -1]
+        out["border tap"] = m + add
+    w2 = w.copy()
+    w2[..., -1] = 0
+    out["last gathered channel"] = im2col_fwd(x, w2, stride, pad) + add
+    if w.shape[0] > 1:
+        w3 = w.copy()
+        w3[-1] = w[-2]
+        out["last produced channel"] = im2col_fwd(x, w3, stride, pad) + add
+    if old is not None:
+        out["old twice"] = base + 2.0 * add
+    out["product (0,1)"] = im2col_fwd(x, w, stride, pad, lambda A, B: x3_exact(A, B, drop=((0, 1),))) + add
+    return out
+
+
+# ------------------------------------------------------------------------- tier B: operands the kernel has no excuse to be off on
+# Every term of every output is an integer multiple of one power of two u and mag / u <= 2^23: all partial sums in any order, every
+# addend of every matrix instruction and the accumulator fit one 24-bit window, so the only correct fp32 output is r64 itself.
+FAMILIES = {"x1w3": (1, 3, 2.0 ** -17, ((0, 0), (0, 1), (0, 2))), "x3w1": (3, 1, 2.0 ** -17, ((0, 0), (1, 0), (2, 0))),
+            "x2w2": (2, 2, 2.0 ** -20, ((0, 0), (0, 1), (1, 0), (1, 1)))}      # terms of x, of w, u, the products that are not zero
+WINDOW = 2.0 ** 23
+
+
+def exact_values(rng, shape, terms, density):
+    """terms 1: {-1, 0, 1}; 2: +-(1 + m 2^-10), m in {1, 3}; 3: +-(1 + 2^-9 + c 2^-17), c in {1, 3, 5, 7} (2^-9 is below half a bf16
+    ulp of 1 and c 2^-17 below half an ulp of 2^-9: three terms each; a NEGATIVE middle term would make the remainder representable
+    and leave two) -- zero with probability 1 - density."""
+    s = rng.choice([-1.0, 1.0], size=shape)
+    if terms == 2:
+        s = s * (1.0 + rng.choice([1.0, 3.0], size=shape) * 2.0 ** -10)
+    if terms == 3:
+        s = s * (1.0 + 2.0 ** -9 + rng.choice([1.0, 3.0, 5.0, 7.0], size=shape) * 2.0 ** -17)
+    return (s * (rng.random(shape) < density)).astype(F32)
+
+
+def exact_pair(seed, family, xshape, wshape, mag_of, k_terms, extra=0.0):
+    """(x, w, tries) of one family, the sparse side(s) thinned until max(mag_of(|x|, |w|) + extra) / u <= 2^23.  k_terms: the
+    longest sum; the first density aims at a quarter of the window.  A draw that leaves fewer than 5 % of the outputs non-zero (a
+    handful of operands, as at a 2 x 2 output) is drawn again at the same density."""
+    tx, tw, u, _ = FAMILIES[family]
+    k_terms = min(k_terms, float(np.max(mag_of(np.ones(xshape, F32), np.ones(wshape, F32)))))      # the longest sum at THIS shape
+    room = WINDOW * u / 4.0
+    dens = min(1.0, room / k_terms) if family != "x2w2" else min(1.0, (room / k_terms) ** 0.5)
+    for tries in range(200):
+        rng = np.random.default_rng([seed, tries])
+        x = exact_values(rng, xshape, tx, dens if tx < 3 else 1.0)
+        w = exact_values(rng, wshape, tw, dens if tw < 3 else 1.0)
+        if float(np.max(mag_of(np.abs(x), np.abs(w)) + extra)) / u > WINDOW:
+            dens *= 0.8
+        elif (mag_of(x, w) != 0).mean() >= 0.05:
+            return x, w, tries
+    raise AssertionError("no sparsity fits the window")
+
+
+def small_ints(rng, shape):
+    return rng.integers(-1, 2, size=shape).astype(F32)
+
+
+def count_terms(v):
+    """Number of non-zero split3 terms of every element."""
+    return sum((t != 0).astype(np.int64) for t in split3(np.asarray(v, dtype=F32)))
+
+
+# ------------------------------------------------------------------------------- tile arithmetic of csrc/conv_halo_f32x3.hip
+F3_CFG = {1: (0, 4, 1, 2, 32), 2: (0, 2, 2, 4, 32), 3: (0, 2, 2, 2, 32), 4: (0, 4, 2, 4, 32), 5: (1, 2, 2, 4, 32), 6: (1, 2, 2, 2, 32),
+          7: (1, 4, 1, 2, 32), 8: (1, 4, 1, 4, 32), 9: (1, 2, 2, 1, 16), 10: (1, 2, 2, 2, 16), 11: (1, 4, 1, 2, 16), 12: (1, 4, 1, 1, 16)}
+
+
+def f3_tile(cfg):
+    """(TH, TW, channels per block) of launch_f3's configuration: TH = WM RPW (32 / TW), 32 WN channels."""
+    _, wm, wn, rpw, tw = F3_CFG[cfg]
+    return wm * rpw * (32 // tw), tw, 32 * wn
+
+
+def f3_symbol(cfg, bnin=False):
+    ws, wm, wn, rpw, tw = F3_CFG[cfg]
+    t = "true" if bnin else "false"
+    return ("conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, %s>" % (wm, wn, rpw, tw, t)) if ws else ("conv3x3_f32x3_kernel<%d, %d, %d, %s>" % (wm, wn, rpw, t))
+
+
+def f3_applicable(n, h, w, gathered, produced, up_ca=0):
+    """csrc/conv_halo_f32x3.hip::f3_applicable for a 3x3 / stride 1 / pad 1 layer."""
+    if gathered % 8 or produced % 4:
+        return False
+    if up_ca > 0 and (up_ca % 16 or (gathered - up_ca) % 16 or h % 2 or w % 2):
+        return False
+    return n * h * w * max(gathered, produced) * 4 < 2 ** 31
+
+
+def n16_steps(gathered):
+    """K loop of conv3x3_n16_f32x3_kernel (v_mfma_f32_16x16x32_bf16: two taps of a 16-channel chunk per step) over im2col columns:
+    chunk outer, tap pair j inner; group G = 5 chunk + j carries the sign (up_negated_groups(5 chunks))."""
+    from oracle.f32x3_ref import up_negated_groups
+    nk = cdiv(gathered, 16)
+    neg = up_negated_groups(5 * nk)
+    return [(np.concatenate([t * gathered + np.arange(16 * c, min(16 * c + 16, gathered)) for t in (2 * j, 2 * j + 1) if t < 9]), 5 * c + j in neg)
+            for c in range(nk) for j in range(5)]
+
+
+def n16_applicable(n, h, w, gathered):
+    """csrc/conv_n16_f32x3.hip::n16_applicable for a 3x3 / stride 1 / pad 1 layer producing 16 channels."""
+    return gathered % 8 == 0 and 8 <= gathered <= 32 and w >= 16 and n * h * w * 32 * 4 < 2 ** 31
+
+
+def stem_applicable(n, h, w, ci, co):
+    return ci == 4 and co == 64 and h >= 2 and w >= 2 and h % 2 == 0 and w % 2 == 0
+
+
+def x3_shared_applicable(ci, co):
+    """The shared-source launchers take the split only for > 32 produced channels (forward: co, data gradient: ci; weight
+    gradient: co > 32 and channel counts that are multiples of 8)."""
+    return co > 32 and ci > 32 and ci % 8 == 0 and co % 8 == 0
+
+
+def wgrad_up_config(n, h, w, ci, co, up_ca):
+    """csrc/conv_wgrad_halo2.hip::h2up_config: 0 refused; 1 / 3: 32-pixel-wide tiles of a (64 / 32 produced channels), 2: 16-pixel."""
+    if h % 2 or w % 2 or h < 2 or w < 2 or up_ca <= 0 or up_ca > ci or up_ca % 64 or co % 32 or w // 2 < 16:
+        return 0
+    if co % 64:
+        return 3 if w // 2 >= 32 else 0
+    return 1 if w // 2 >= 32 else 2
+
+
+# ------------------------------------------------------------ the phase kernels (csrc/conv_up_f32x3.hip), in their own K order
+UP_CFG = {1: (2, 2, 1, 32), 2: (2, 2, 2, 32), 3: (4, 1, 1, 32), 4: (4, 1, 2, 32), 5: (2, 2, 1, 16), 6: (2, 2, 2, 16), 7: (4, 1, 1, 16),
+          8: (2, 2, 4, 32)}           # WM, WN, RPW, TW; 8 is the data gradient's (the forward runs 2 there)
+
+
+def up_tile(cfg, dgrad):
+    """(TH, TW in pixels of a, channels per block, symbol) of launch_up's configuration."""
+    wm, wn, rpw, tw = UP_CFG[2 if cfg == 8 and not dgrad else cfg]
+    return wm * rpw * (32 // tw), tw, 32 * wn, "conv_up_%s_f32x3_kernel<%d, %d, %d, %d>" % ("dgrad" if dgrad else "fwd", wm, wn, rpw, tw)
+
+
+def up_applicable(h, w, ci, co, up_ca, dgrad=False):
+    """csrc/conv_up_f32x3.hip::up_applicable (h, w: the OUTPUT's extents); the data gradient gathers co in pieces of 8."""
+    return not (h % 2 or w % 2 or h < 2 or w < 2 or up_ca <= 0 or up_ca > ci or up_ca % 16 or co % 4 or ci % 4 or (dgrad and co % 8))
+
+
+def up_fwd_phases(a, w_up, mm):
+    """conv3x3(nearest_x2(a), w_up) as the four 2x2 phase convolutions on the oracle's fp32 pre-summed weights: for phase (py, px)
+    mm(A [pixels of a][(u, v, channel)], B [(u, v, channel)][co], px) -> [pixels][co].  a NHWC, w_up OHWI."""
+    from oracle.f32x3_ref import phase_weights
+    a = np.asarray(a, dtype=F32)
+    n, h, w, ca = a.shape
+    pw = phase_weights(np.ascontiguousarray(np.asarray(w_up, dtype=F32).transpose(0, 3, 1, 2)))      # [py][px][co][ca][u][v]
+    co = pw.shape[2]
+    y = None
+    for py in range(2):
+        for px in range(2):
+            A, _ = im2col(a, 2, 1, ((1 - py, py), (1 - px, px)))
+            out = np.asarray(mm(A, pw[py, px].transpose(2, 3, 1, 0).reshape(4 * ca, co).astype(F64), px))
+            if y is None:
+                y = np.zeros((n, 2 * h, 2 * w, co), dtype=out.dtype)
+            y[:, py::2, px::2] = out.reshape(n, h, w, co)
+    return y
+
+
+def up_fwd_steps(ca, px, signs=True):
+    """K loop of conv_up_fwd_f32x3_kernel as one output phase sees it: chunk outer, column offset v (group G = 4 chunk + 2 px + v),
+    row offset u inner."""
+    from oracle.f32x3_ref import up_negated_groups
+    nk = cdiv(ca, 16)
+    neg = up_negated_groups(4 * nk) if signs else ()
+    return [((u * 2 + v) * ca + np.arange(16 * c, min(16 * c + 16, ca)), 4 * c + 2 * px + v in neg) for c in range(nk) for v in range(2) for u in range(2)]
+
+
+def up_dgrad_matrices(dy, w_up):
+    """The phase data gradient as one product: A [pixels of a][(py, px, u, v, dy channel)] @ B [...][ca]."""
+    from oracle.f32x3_ref import phase_weights
+    dy = np.asarray(dy, dtype=F64)
+    n, h2, w2, co = dy.shape
+    h, w = h2 // 2, w2 // 2
+    pw = phase_weights(np.ascontiguousarray(np.asarray(w_up, dtype=F32).transpose(0, 3, 1, 2))).astype(F64)
+    ca = pw.shape[3]
+    cols, rows = [], []
+    for py in range(2):
+        for px in range(2):
+            g = np.pad(dy[:, py::2, px::2], ((0, 0), (1, 1), (1, 1), (0, 0)))
+            for u in range(2):
+                for v in range(2):
+                    di, dj = 1 - py - u, 1 - px - v                      # da[i, j] takes g[i + di, j + dj]
+                    cols.append(g[:, 1 + di:1 + di + h, 1 + dj:1 + dj + w].reshape(n * h * w, co))
+                    rows.append(pw[py, px, :, :, u, v])                  # [co][ca]
+    return np.concatenate(cols, axis=1), np.concatenate(rows, axis=0), (n, h, w, ca)
+
+
+def up_dgrad_steps(co, signs=True):
+    """K loop of conv_up_dgrad_f32x3_kernel: chunk of dy channels outer, phase (group G = 4 chunk + 2 py + px), its four taps inner."""
+    from oracle.f32x3_ref import up_negated_groups
+    nk = cdiv(co, 16)
+    neg = up_negated_groups(4 * nk) if signs else ()
+    return [(((2 * py + px) * 4 + t) * co + np.arange(16 * c, min(16 * c + 16, co)), 4 * c + 2 * py + px in neg)
+            for c in range(nk) for py in range(2) for px in range(2) for t in range(4)]
+
+
+def pool2(v):
+    """Sum over the 2x2 pixel blocks: the gradient of nearest_x2."""
+    v = np.asarray(v)
+    return v[:, 0::2, 0::2] + v[:, 0::2, 1::2] + v[:, 1::2, 0::2] + v[:, 1::2, 1::2]
+
+
+def x3_up_fwd(a, w_up):
+    x = upcat(a, None)
+    return Ref(torch_fwd(x, w_up, 1, 1, torch.float64), torch_fwd(np.abs(x), np.abs(w_up), 1, 1, torch.float64), torch_fwd(x, w_up, 1, 1, torch.float32),
+               up_fwd_phases(a, w_up, lambda A, B, px: x3_matmul(A, B, up_fwd_steps(np.shape(a)[3], px))))
+
+
+def x3_up_dgrad(dy, w_up):
+    """Gradient of a through conv3x3(nearest_x2(a), w_up): r64 the true operation (transpose convolution, 2x2 sum), the model on the
+    phase weights."""
+    n, h, w, co = np.shape(dy)
+    A, B, shape = up_dgrad_matrices(dy, w_up)
+    full32 = torch_dgrad(dy, w_up, 1, 1, h, w, torch.float32)
+    rne = (((full32[:, 0::2, 0::2] + full32[:, 0::2, 1::2]).astype(F32) + full32[:, 1::2, 0::2]).astype(F32) + full32[:, 1::2, 1::2]).astype(F32)
+    return Ref(pool2(torch_dgrad(dy, w_up, 1, 1, h, w, torch.float64)), pool2(torch_dgrad(np.abs(dy), np.abs(w_up), 1, 1, h, w, torch.float64)), rne,
+               x3_matmul(A, B, up_dgrad_steps(co)).reshape(shape))
+
+
+def wgrad_h2_config(h, w, ci, co, up_ca=0):
+    """csrc/conv_wgrad_halo2.hip::h2_config for a 3x3 / stride 1 / pad 1 layer without its two pair-packed 16-channel forms: 0 refused;
+    1: 64 x 64 channel blocks, 2: the same on 16-pixel-wide tiles (w < 32), 3: 64 gathered x 32 produced, 4: 32 x 32."""
+    cfg = 0
+    if ci % 64 == 0 and co % 64 == 0:
+        cfg = 2 if w < 32 else 1
+    elif ci % 64 == 0 and co % 32 == 0:
+        cfg = 3
+    elif ci % 32 == 0 and co % 32 == 0:
+        cfg = 4
+    if cfg == 0 or w < 16 or (cfg != 2 and w < 32):
+        return 0
+    if up_ca > 0:
+        if up_ca >= ci or h % 2 or w % 2:
+            return 0
+        if up_ca % 64:
+            if up_ca % 32 or w < 32:
+                return 0
+            cfg = 4
+    return cfg
+
+
+def wgrad_pair_config(h, w, ci, co, up_ca=0, pair=7):
+    """The two pair-packed forms h2_config tries first (fp32 only; WGRAD_PAIR bits 1 | 2: 16 gathered channels and <= 16 | <= 32
+    produced; bit 4: 32 up-sampled channels without a skip half -> 16): 5, 6 or 0."""
+    if up_ca == 0 and ci == 16 and 8 <= co <= 32 and co % 8 == 0 and w % 2 == 0 and w >= 16 and pair & (1 if co <= 16 else 2):
+        return 5
+    if up_ca == 32 and ci == 32 and co == 16 and h % 2 == 0 and w % 2 == 0 and w >= 16 and pair & 4:
+        return 6
+    return 0

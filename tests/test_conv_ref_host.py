@@ -1,11 +1,16 @@
 """tests/_conv_ref.py proven on the CPU before it judges a kernel (tests/test_gpu_conv_bf16_grade.py): the im2col products against
 torch's double-precision convolution and autograd, the truncation on hand-made values, the one-sidedness of the truncating leg,
 two negative controls (a truncating bf16 store, a dropped term) that must FAIL the verdicts, and the tile arithmetic of the
-launchers that the GPU cases rely on."""
+launchers that the GPU cases rely on.
+
+For the fp32 split kernels (tests/test_gpu_conv_f32x3_grade.py, cases in tests/_conv_f32x3_cases.py): for every case of the GPU file,
+tier A's bar rejects five mutants of the float64 model, and tier B's operands are exact (one 24-bit window, the intended split
+terms, six-product model == float64, every exercised product and the sign pattern visible in >= 1 % of the outputs)."""
 import numpy as np
 import pytest
 import torch
 
+import _conv_f32x3_cases as C
 import _conv_ref as R
 from _conv_ref import F32, F64
 
@@ -213,3 +218,335 @@ def test_the_shapes_reach_every_launch_regime():
     # the pixel fold: 16 channels fold four pixels while the folded output fits 64 columns, 32 channels fold two, width permitting
     assert R.fold_factor(16, 16, 64) == 4 and R.fold_factor(32, 16, 14) == 2 and R.fold_factor(16, 24, 13) == 1
     assert R.fold_factor(16, 16, 64, no_fold=True) == 1 and R.fold_factor(16, 24, 12) == 1 and R.fold_factor(64, 16, 64) == 1
+
+
+# ================================================================================== the fp32 split kernels: tier A and tier B
+def test_six_product_model_on_hand_made_values():
+    rng = np.random.default_rng(11)
+    A, B = R.randn_f32(rng, (40, 50), binades=20), R.randn_f32(rng, (50, 7), binades=20)
+    exact = A.astype(F64) @ B.astype(F64)
+    mag = np.abs(A).astype(F64) @ np.abs(B).astype(F64)
+    assert rel(R.x3_exact(A, B), exact, mag) <= 2.0 ** -23            # what the three left-out products are worth
+    assert rel(R.x3_exact(A, B, drop=((0, 2),)), exact, mag) <= 2.0 ** -15 and rel(R.x3_exact(A, B, drop=((0, 1),)), exact, mag) >= 2.0 ** -12
+    plain = R.x3_matmul(A, B)
+    assert plain.dtype == F32 and rel(plain, exact, mag) <= 4e-6
+    # without a sign pattern the model is never above its own untruncated sum; with every step negated never below
+    six = R.x3_exact(A, B)
+    every = [(slice(j, j + 16), True) for j in range(0, 50, 16)]
+    assert (plain.astype(F64) <= six + 2.0 ** -48 * mag).all() and (R.x3_matmul(A, B, every).astype(F64) >= six - 2.0 ** -48 * mag).all()
+    # bf16 operands have one term: one product, the bf16 model
+    Ab, Bb = R.bf16_round(A), R.bf16_round(B)
+    assert np.array_equal(R.x3_matmul(Ab, Bb), R.trunc_matmul(Ab.astype(F64), Bb.astype(F64)))
+    # the K loop of the halo kernels visits every im2col column once, and the groups [q1, q3) are the negated ones
+    for g in (8, 16, 24, 72):
+        steps = R.halo3_steps(g)
+        cols = np.concatenate([c for c, _ in steps])
+        assert np.array_equal(np.sort(cols), np.arange(9 * g)) and all(len(c) <= 16 for c, _ in steps)
+        assert sum(neg for _, neg in steps) == 3 * len(R.negated_groups(R.cdiv(g, 16))) > 0
+
+
+def test_f3_tile_table_and_case_lists():
+    """The launcher's table (csrc/conv_halo_f32x3.hip::launch_f3) and what the grade needs of the case lists."""
+    assert [R.f3_tile(c) for c in range(1, 13)] == [(8, 32, 32), (8, 32, 64), (4, 32, 64), (16, 32, 64), (8, 32, 64), (4, 32, 64), (8, 32, 32),
+                                                     (16, 32, 32), (4, 16, 64), (8, 16, 64), (16, 16, 32), (8, 16, 32)]
+    assert R.f3_symbol(4) == "conv3x3_f32x3_kernel<4, 2, 4, false>" and R.f3_symbol(12, True) == "conv3x3_f32x3_ws_kernel<4, 1, 1, false, 16, true>"
+    for cfg in range(1, 13):
+        th, tw, cb = R.f3_tile(cfg)
+        mine = [c for c in C.F3_CASES if c[0] == cfg]
+        assert {(c[4], c[5]) for c in mine} >= {(8, 4), (72, 68)}
+        assert all(c[2] == th + 1 for c in mine) and {c[3] for c in mine} == {tw, tw + 2}
+        prod = {c[5] for c in mine}
+        assert min(prod) < cb and max(prod) > cb and any(q % cb for q in prod)
+    cases = C.F3_CASES + C.F3_BNIN
+    refused = [c for c in cases if not R.f3_applicable(*c[1:6])]          # (the data gradient gathers g and produces p like the forward)
+    refused += [c for c in C.F3_UP if not R.f3_applicable(c[1], c[2], c[3], c[4] + c[5], c[6], up_ca=c[4])]
+    assert 10 * len(refused) <= len(cases) + len(C.F3_UP) and not refused
+    assert {c[0] for c in C.F3_BNIN} == {3, 6} and {(c[4], c[5]) for c in C.F3_UP} == {(16, 0), (16, 16), (48, 32)}
+    assert sum(c[6] == "binades" for c in C.F3_CASES) == 3
+
+
+def reject_all(ref, mutants, what):
+    assert R.verdict(ref.leg_rne, ref, False)[0] and R.verdict(ref.leg_trunc, ref, False)[0], what
+    for name, got in mutants.items():
+        ok, e, A = R.verdict(got, ref, False)[:3]
+        assert not ok, f"{what}: the bar {A:.3e} lets the mutant '{name}' pass (e {e:.3e})"
+    return sorted(mutants)
+
+
+ALL5 = ["border tap", "last gathered channel", "last produced channel", "old twice", "product (0,1)"]
+
+
+def one_per_shape(cases):
+    """Configurations with the same tile share a case's operands: one host test per distinct shape covers every case."""
+    seen = {}
+    for c in cases:
+        seen.setdefault(C.shape_of(c), c)
+    assert sorted(seen, key=repr) == C.unique_shapes(cases)
+    return list(seen.values())
+
+
+F3_A, F3_B = one_per_shape(C.F3_CASES), one_per_shape([c[:6] for c in C.F3_CASES if c[6] == "randn"])
+
+
+@pytest.mark.parametrize("case", F3_A, ids=[C.f3_id(c) for c in F3_A])
+def test_f3_tier_a_bar_rejects_the_mutants(case):
+    cfg, n, h, w, g, p, mode = case
+    o = C.f3_tier_a(case)
+    A = R.bar(o["fwd"])[0]
+    assert A <= (4e-5 if mode == "binades" else 8e-6)               # an fp32-grade bar
+    old = o["old"]
+    assert reject_all(R.epilogue(o["fwd"], old=old), R.fwd_mutants(o["x"], o["wt"], 1, 1, old), "forward") == ALL5
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wd"], 1, 1, h, w)
+    assert reject_all(R.epilogue(o["dgrad"], old=old), R.fwd_mutants(d, wf, 1, pads, old), "data gradient") == ALL5
+    s1, s2, margin = R.bn_sums_ref(o["dgrad"], o["prev_y"], o["mean"], o["rstd"], o["gamma"], o["beta"], SLOPE_)
+    assert margin > 1e-4                                            # no activation argument within rounding distance of zero
+    assert R.verdict(s1.leg_rne, s1, False)[0] and R.verdict(s2.leg_rne, s2, False)[0]
+
+
+SLOPE_ = C.SLOPE
+
+
+@pytest.mark.parametrize("case", one_per_shape(C.F3_BNIN), ids=[C.f3_id(c) for c in one_per_shape(C.F3_BNIN)])
+def test_f3_bnin_tier_a_bar_rejects_the_mutants(case):
+    o = C.f3_bnin_a(case)
+    m = R.fwd_mutants(o["z"], o["wt"], 1, 1)
+    m["transform skipped"] = R.im2col_fwd(o["y_prev"], o["wt"], 1, 1)
+    reject_all(o["fwd"], m, "forward behind the in-staging transform")
+
+
+@pytest.mark.parametrize("case", one_per_shape(C.F3_UP), ids=[C.up_id(c) for c in one_per_shape(C.F3_UP)])
+def test_f3_fused_input_tier_a_bar_rejects_the_mutants(case):
+    o = C.f3_up_a(case)
+    m = R.fwd_mutants(R.upcat(o["a"], o["skip"]), o["wt"], 1, 1)
+    shifted = np.roll(R.upcat(o["a"], o["skip"]), 1, axis=2)        # the up-sampled pixel pairs taken one column off
+    m["up-sampling off by one column"] = R.im2col_fwd(shifted, o["wt"], 1, 1)
+    reject_all(o["fwd"], m, "fused decoder input")
+
+
+def check_tier_b(t, family, steps, dgrad_to=None, pad=1, stride=1):
+    """The four conditions of tier B on one launch's operands."""
+    tx, tw, u, pairs = R.FAMILIES[family]
+    assert float(t["mag"].max()) / u <= 2.0 ** 23, "window"
+    nx, nw = R.count_terms(t["xin"]), R.count_terms(t["w"])
+    assert set(np.unique(nx)) <= {0, tx} and set(np.unique(nw)) <= {0, tw} and (nx == tx).any() and (nw == tw).any(), "split terms"
+    if dgrad_to is None:
+        xx, ww, pp = t["xin"], t["w"], pad
+    else:
+        xx, ww, pp = R.dgrad_as_forward(t["xin"], t["w"], stride, pad, *dgrad_to)
+    six = R.im2col_fwd(xx, ww, 1 if dgrad_to else stride, pp, R.x3_exact)
+    assert np.array_equal(six, t["r64"]), "six products != float64"
+    assert np.array_equal(t["r64"].astype(F32).astype(F64), t["r64"])
+    assert np.array_equal(np.round(t["r64"] / u) * u, t["r64"])
+    for pr in pairs:
+        m = R.im2col_fwd(xx, ww, 1 if dgrad_to else stride, pp, lambda A, B: R.x3_exact(A, B, drop=(pr,)))
+        assert (m != t["r64"]).mean() >= 0.01, f"product {pr} is invisible"
+    if steps is not None:
+        flip = np.concatenate([c for c, neg in steps if neg][:3])
+        m = R.im2col_fwd(xx, ww, 1, pp, lambda A, B: R.x3_exact(A, B, flip=flip))
+        assert (m != t["r64"]).mean() >= 0.01, "the sign pattern is invisible"
+
+
+@pytest.mark.parametrize("family", sorted(R.FAMILIES))
+@pytest.mark.parametrize("case", F3_B, ids=[C.f3_id(c) for c in F3_B])
+def test_f3_tier_b_operands_are_exact(case, family):
+    cfg, n, h, w, g, p = case[:6]
+    f, d = C.f3_tier_b(case, family)
+    check_tier_b(f, family, R.halo3_steps(g))
+    check_tier_b(d, family, R.halo3_steps(g), dgrad_to=(h, w))
+    assert f["x"].shape == (n, h, w, g) and d["r64"].shape == (n, h, w, p) and np.abs(f["bias"]).max() <= 1 and np.abs(d["old"]).max() <= 1
+
+
+@pytest.mark.parametrize("family", sorted(R.FAMILIES))
+def test_f3_bnin_and_fused_input_tier_b_operands_are_exact(family):
+    for case in one_per_shape(C.F3_BNIN):
+        check_tier_b(C.f3_bnin_b(case, family), family, R.halo3_steps(case[4]))
+    for case in one_per_shape(C.F3_UP):
+        t = C.f3_up_b(case, family)
+        check_tier_b(t, family, R.halo3_steps(case[4] + case[5]))
+        assert np.array_equal(t["xin"], R.upcat(t["a"], t["skip"]))
+
+
+# ----------------------------------------------------------------- sixteen-wide tile, stem, shared-source split, weight gradients
+def test_the_other_launchers_accept_every_listed_case():
+    """The predicates' arithmetic, restated: no case of these lists is refused (the cap is one in ten)."""
+    assert all(R.n16_applicable(*c) for c in C.N16) and {c[3] for c in C.N16} == {g for g in range(1, 65) if R.n16_applicable(2, 9, 34, g)}
+    assert all(R.stem_applicable(n, h, w, 4, 64) for n, h, w in C.STEM)
+    assert all(R.x3_shared_applicable(c[3], c[4]) for c in C.X3)
+    assert {c[5:] for c in C.X3} == {(3, 2, 1), (1, 2, 0), (4, 2, 1), (3, 1, 1)}
+    assert [R.wgrad_up_config(n, h, w, ca + cs, co, ca) for n, h, w, ca, cs, co in C.WG_UP] == [2, 1, 3, 2]
+    assert {R.wgrad_h2_config(h, w, ci, co) for n, h, w, ci, co in C.WG_HALO} == {1, 2, 3, 4}       # every channel-block shape
+    assert all(R.wgrad_h2_config(h, w, ci, co) for n, h, w, ci, co in C.WG_BNIN + [c[:5] for c in C.WG_SLICE])
+    assert [R.wgrad_h2_config(h, w, ca + cs, co, ca) for n, h, w, ca, cs, co in C.WG_HALO_UP] == [1, 4, 2]
+    assert all(R.wgrad_pair_config(h, w, ci, co) == 5 for n, h, w, ci, co in C.WG_PAIR) and {c[4] for c in C.WG_PAIR} == {8, 16, 24, 32}
+    assert all(R.wgrad_pair_config(h, w, ca + cs, co, ca) == 6 for n, h, w, ca, cs, co in C.WG_PAIR_UP)
+    for c in C.WG_PAIR + C.WG_PAIR_UP + C.WG_HALO + C.WG_BNIN + C.WG_HALO_UP + C.WG_UP + [x[:5] for x in C.WG_SLICE]:
+        assert 64 <= c[0] * c[1] * c[2] <= 700
+    for g in (8, 16, 24, 32):
+        steps = R.n16_steps(g)
+        assert np.array_equal(np.sort(np.concatenate([c for c, _ in steps])), np.arange(9 * g)) and all(len(c) <= 32 for c, _ in steps)
+
+
+@pytest.mark.parametrize("case", C.N16, ids=["n%d_%dx%d_g%d" % c for c in C.N16])
+def test_n16_tier_a_and_b(case):
+    n, h, w, g = case
+    o = C.n16_tier_a(case)
+    reject_all(o["fwd"], R.fwd_mutants(o["x"], o["wt"], 1, 1), "forward")
+    m = R.fwd_mutants(o["z"], o["wt"], 1, 1)
+    m["transform skipped"] = R.im2col_fwd(o["x"], o["wt"], 1, 1)
+    reject_all(o["fwd_z"], m, "forward behind the transform")
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wd"], 1, 1, h, w)
+    reject_all(o["dgrad"], R.fwd_mutants(d, wf, 1, pads), "data gradient")
+    assert R.bn_sums_ref(o["dgrad"], o["prev_y"], o["mean"], o["rstd"], o["gamma"], o["beta"], 0.0)[2] > 1e-4
+    for family in sorted(R.FAMILIES):
+        f, z, b = C.n16_tier_b(case, family)
+        check_tier_b(f, family, R.n16_steps(g))
+        check_tier_b(z, family, R.n16_steps(g))
+        check_tier_b(b, family, R.n16_steps(g), dgrad_to=(h, w))
+
+
+@pytest.mark.parametrize("case", C.STEM, ids=["n%d_%dx%d" % c for c in C.STEM])
+def test_stem_tier_a_and_b(case):
+    o = C.stem_tier_a(case)
+    reject_all(o["fwd"], R.fwd_mutants(o["x"], o["wt"], 2, 3), "stem forward")
+    for family in sorted(R.FAMILIES):
+        check_tier_b(C.stem_tier_b(case, family), family, None, pad=3, stride=2)
+
+
+def wgrad_mutants(x, dy, k, stride, pad, old):
+    """Wrong float64 weight gradients: one pixel (the first of the last image) never summed, the border tap of the last column skipped, the last produced
+    channel's gradient taken from the previous dy channel, old added twice, the first-order product dropped."""
+    base = R.im2col_wgrad(x, dy, k, stride, pad)
+    add = np.asarray(old, dtype=F64)
+    x2 = np.array(x, dtype=F32)
+    x2[-1, 0, 0] = 0
+    dy2 = np.array(dy, dtype=F32)
+    dy2[..., -1] = dy2[..., -2]
+    dy3 = np.array(dy, dtype=F32)
+    dy3[:, :, -1] = 0
+    out = {}
+    if k > 1:                                # (a 1x1 window has no border tap)
+        m = base.copy()
+        m[:, k // 2, k // 2 - 1] = R.im2col_wgrad(x, dy3, k, stride, pad)[:, k // 2, k // 2 - 1]
+        out["border tap"] = m + add
+    out.update({"one pixel": R.im2col_wgrad(x2, dy, k, stride, pad) + add,
+            "last produced channel": R.im2col_wgrad(x, dy2, k, stride, pad) + add, "old twice": base + 2.0 * add,
+            "product (0,1)": R.im2col_wgrad(x, dy, k, stride, pad, lambda A, B: R.x3_exact(A, B, drop=((1, 0),))) + add})
+    return out
+
+
+def check_wgrad_tier_b(t, family):
+    tx, tw, u, pairs = R.FAMILIES[family]
+    k, s, p = t["geom"]
+    assert float(t["mag"].max()) / u <= 2.0 ** 23
+    nx, nw = R.count_terms(t["xin"]), R.count_terms(t["w"])
+    assert set(np.unique(nx)) <= {0, tx} and set(np.unique(nw)) <= {0, tw} and (nx == tx).any() and (nw == tw).any()
+    assert np.array_equal(R.im2col_wgrad(t["xin"], t["w"], k, s, p, R.x3_exact), t["r64"])
+    assert np.array_equal(t["r64"].astype(F32).astype(F64), t["r64"])
+    for i, j in pairs:                       # the matrix product is dy^T @ im2col(x): (term of dy, term of x)
+        m = R.im2col_wgrad(t["xin"], t["w"], k, s, p, lambda A, B: R.x3_exact(A, B, drop=((j, i),)))
+        assert (m != t["r64"]).mean() >= 0.01, f"product {(i, j)} is invisible"
+
+
+@pytest.mark.parametrize("case", C.X3, ids=["n%d_%dx%d_ci%d_co%d_k%d_s%d_p%d" % c for c in C.X3])
+def test_shared_source_split_tier_a_and_b(case):
+    n, h, w, ci, co, k, s, p = case
+    o = C.x3_tier_a(case)
+    m = R.fwd_mutants(o["x"], o["wt"], s, p)
+    if k == 1:
+        assert "border tap" not in m
+    reject_all(o["fwd"], m, "forward")
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wt"], s, p, h, w)
+    md = R.fwd_mutants(d, wf, 1, pads)
+    md.pop("border tap", None)               # (the dilated dy of a strided layer has zero columns: that mutant may change nothing)
+    reject_all(o["dgrad"], md, "data gradient")
+    reject_all(R.epilogue(o["wgrad"], old=o["oldw"]), wgrad_mutants(o["x"], o["dy"], k, s, p, o["oldw"]), "weight gradient")
+    for family in sorted(R.FAMILIES):
+        f, b, g = C.x3_tier_b(case, family)
+        check_tier_b(f, family, None, pad=p, stride=s)
+        check_tier_b(b, family, None, dgrad_to=(h, w), pad=p, stride=s)
+        check_wgrad_tier_b(g, family)
+
+
+WG_ALL = [("halo", c) for c in C.WG_HALO + C.WG_PAIR] + [("halo_up", c) for c in C.WG_PAIR_UP] + [("halo_up", c) for c in C.WG_HALO_UP] + [("bnin", c) for c in C.WG_BNIN] + \
+         [("up", c) for c in C.WG_UP] + [("halo", c[:5]) for c in C.WG_SLICE]
+
+
+@pytest.mark.parametrize("kind,case", WG_ALL, ids=["%s-%s" % (k, "_".join(map(str, c))) for k, c in WG_ALL])
+def test_weight_gradient_tier_a_and_b(kind, case):
+    o = C.wg_tier_a(kind, case)
+    reject_all(R.epilogue(o["wgrad"], old=o["oldw"]), wgrad_mutants(o["x"], o["dy"], 3, 1, 1, o["oldw"]), "weight gradient")
+    for family in sorted(R.FAMILIES):
+        check_wgrad_tier_b(C.wg_tier_b(kind, case, family), family)
+
+
+# ------------------------------------------------------------------------------------------------------------ the phase kernels
+UP_ONE = one_per_shape(C.UP)
+
+
+def test_phase_kernel_tiles_and_cases():
+    assert [R.up_tile(c, True)[:3] for c in range(1, 9)] == [(2, 32, 64), (4, 32, 64), (4, 32, 32), (8, 32, 32), (4, 16, 64), (8, 16, 64), (8, 16, 32),
+                                                              (8, 32, 64)]
+    assert R.up_tile(8, False) == R.up_tile(2, False) and R.up_tile(7, False)[3] == "conv_up_fwd_f32x3_kernel<4, 1, 1, 16>"
+    refused = [c for c in C.UP if not R.up_applicable(c[2], c[3], c[4] + c[5], c[6], c[4], dgrad=True)]
+    assert not refused
+    for cfg in range(1, 9):
+        mine = [c for c in C.UP if c[0] == cfg]
+        th, tw = R.up_tile(cfg, True)[:2]
+        assert {(c[2], c[3]) for c in mine} == {(2, 2), (2 * th + 2, 2 * tw + 2)}
+        assert {c[4] for c in mine} == {16, 48} and {c[5] for c in mine} == {0, 16} and {c[6] for c in mine} == {8, 40}
+    # the phase form IS the convolution on the up-sampled tensor, and its K loops visit every column once
+    rng = np.random.default_rng(4)
+    a, w = R.randn_f32(rng, (2, 3, 5, 16)), R.randn_f32(rng, (8, 3, 3, 16), 0.1)
+    f = R.x3_up_fwd(a, w)
+    assert rel(R.up_fwd_phases(a, w, lambda A, B, px: A @ B), f.r64, f.mag) <= 1e-6          # (the pre-sums are rounded to fp32)
+    dy = R.randn_f32(rng, (2, 6, 10, 8))
+    g = R.x3_up_dgrad(dy, w)
+    A, B, shape = R.up_dgrad_matrices(dy, w)
+    assert rel((A @ B).reshape(shape), g.r64, g.mag) <= 1e-6 and g.r64.shape == a.shape
+    assert np.array_equal(np.sort(np.concatenate([c for c, _ in R.up_dgrad_steps(8)])), np.arange(16 * 8))
+    assert np.array_equal(np.sort(np.concatenate([c for c, _ in R.up_fwd_steps(48, 1)])), np.arange(4 * 48))
+
+
+@pytest.mark.parametrize("case", UP_ONE, ids=[C.up_id(c) for c in UP_ONE])
+def test_phase_kernels_tier_a_and_b(case):
+    cfg, n, h, w, ca, cs, co = case
+    o = C.up_tier_a(case)
+    w_up = np.ascontiguousarray(o["wt"][..., :ca])
+    m = R.fwd_mutants(R.upcat(o["a"], None), w_up, 1, 1, o["old"])
+    m["up-sampling off by one column"] = R.im2col_fwd(np.roll(R.upcat(o["a"], None), 1, axis=2), w_up, 1, 1) + o["old"]
+    if w == 2:
+        m.pop("up-sampling off by one column")          # (a has one column: the roll is the identity)
+    reject_all(R.epilogue(o["fwd"], old=o["old"]), m, "phase forward")
+    dg = R.epilogue(o["dgrad"], old=o["olda"])
+    d, wf, pads = R.dgrad_as_forward(o["dy"], w_up, 1, 1, h, w)
+    md = {k: R.pool2(v) + o["olda"] for k, v in R.fwd_mutants(d, wf, 1, pads).items()}
+    md["old twice"] = dg.r64 + o["olda"]
+    md["2x2 sum misses a pixel"] = dg.r64 - R.im2col_fwd(d, wf, 1, pads)[:, 1::2, 1::2]
+    if w == 2:
+        md.pop("border tap")
+    reject_all(dg, md, "phase data gradient")
+    from oracle.f32x3_ref import UP_TAPS, phase_weights
+    for family in sorted(R.FAMILIES):
+        f, b = C.up_tier_b(case, family)
+        tx, tw_, u, pairs = R.FAMILIES[family]
+        for t in (f, b):
+            assert float(t["mag"].max()) / u <= 2.0 ** 23
+            # the packer's fp32 pre-sums of up to four weights lose nothing: every phase weight equals its float64 sum
+            pw = phase_weights(np.ascontiguousarray(t["w"].transpose(0, 3, 1, 2)))
+            w64 = t["w"].astype(F64).transpose(0, 3, 1, 2)
+            for (py, u), kys in UP_TAPS.items():
+                for (px, v), kxs in UP_TAPS.items():
+                    assert np.array_equal(pw[py, px, :, :, u, v].astype(F64), sum(w64[:, :, ky, kx] for ky in kys for kx in kxs))
+            assert set(np.unique(R.count_terms(t["xin"]))) <= {0, tx} and set(np.unique(R.count_terms(t["w"]))) <= {0, tw_}
+        assert np.array_equal(R.up_fwd_phases(f["a"], f["w"], lambda A, B, px: R.x3_exact(A, B)), f["r64"]), "phase six products != float64"
+        A, B, shape = R.up_dgrad_matrices(b["x"], b["w"])
+        assert np.array_equal(R.x3_exact(A, B).reshape(shape), b["r64"])
+        for pr in pairs:
+            mf = R.up_fwd_phases(f["a"], f["w"], lambda A_, B_, px: R.x3_exact(A_, B_, drop=(pr,)))
+            assert (mf != f["r64"]).mean() >= 0.01 and (R.x3_exact(A, B, drop=(pr,)).reshape(shape) != b["r64"]).mean() >= 0.01, pr
+        flip = lambda steps: np.concatenate([c for c, neg in steps if neg][:2])  # noqa: E731
+        mf = R.up_fwd_phases(f["a"], f["w"], lambda A_, B_, px: R.x3_exact(A_, B_, flip=flip(R.up_fwd_steps(ca, px))))
+        assert (mf != f["r64"]).mean() >= 0.01
+        # one mis-signed group shows (at the 2 x 2 output most taps of a group fall outside a: some group, not each)
+        negs = [c for c, neg in R.up_dgrad_steps(co) if neg]
+        assert any((R.x3_exact(A, B, flip=np.concatenate(negs[i:i + 4])).reshape(shape) != b["r64"]).mean() >= 0.01 for i in range(0, len(negs), 4))
