@@ -447,6 +447,36 @@ int udaseg_classmix_u8(const uint8_t* src, const uint8_t* src_masks, const uint8
                        const int32_t* sel, const int32_t* boxes, int n, int h, int w, int classes, int void_label, uint8_t* out,
                        uint8_t* out_masks, int64_t* counts, void* stream);
 
+/* ---- Fourier-domain style transfer of source frames to a target's style (FDA, Yang & Soatto 2020; the amplitude mix of Xu et al.
+ * 2021; an extension, the reference has no counterpart), csrc/fda.hip.  Frames are uint8 [n][h][w][3].  With K = 2 bmax + 1,
+ * 0 <= bmax <= (min(h, w) - 1) / 2, and ku = u + bmax, kv = v + bmax for the frequencies u, v in [-bmax, bmax]:
+ *     out = src + Re(IDFT(D)),  D[u][v] = lam (|F_t[u][v]| - |F_s[u][v]|) F_s[u][v] / |F_s[u][v]| for |u|, |v| <= b, 0 elsewhere.
+ * Twiddle tables: tw[k] = (cos, sin)(2 pi k / L) for k in [0, L), L = h and L = w, made on the host in float64; the analysis reads
+ * them as float64 [L][2], the synthesis their float32 roundings; the index is (u * y) mod L in integers.  Every entry point
+ * refuses (non-zero, nothing launched) a NULL required pointer, n, h or w <= 0, n*h*w >= 2^31, bmax outside its range and an output
+ * range that overlaps an operand.  b and pick are device tables: the kernels clamp b[i] to [-1, bmax] and pick[i] to [0, m).
+ *
+ * Analysis, float64 from the exact integer pixels: coeffs[i][c][ku][kv] = sum_y sum_x frames[i][y][x][c] e^{-2 pi i (u y / h + v x / w)}
+ * as (re, im), float64 [n][3][K][K][2], in two stages through rows_ws, float64 [n][3][h][K][2] (the sums over x).  No atomics: the
+ * same frames give the same bits. */
+int udaseg_fda_spectrum_u8(const uint8_t* frames, const double* tw_h, const double* tw_w, int n, int h, int w, int bmax,
+                           double* rows_ws, double* coeffs, void* stream);
+/* amps[j] = sqrt(re_j^2 + im_j^2) of count coefficients: the target side's float64 [m][3][K][K] table from its coefficients. */
+int udaseg_fda_amplitude(const double* coeffs, int64_t count, double* amps, void* stream);
+/* delta[i][c][ku][kv] = D / (h w) as (re, im), float32 [n][3][K][K][2].  coeffs: the source's; amps: float64 [m][3][K][K]; pick
+ * int32 [n]: the row of amps that styles sample i; b int32 [n]: the sample's band half-width, -1 for none (delta is 0 outside
+ * |u|, |v| <= b[i]); lam float32 [n] in [0, 1].  Where |F_s| <= 1e-9 * 255 * h * w the unit phasor F_s / |F_s| is taken as 1. */
+int udaseg_fda_delta(const double* coeffs, const double* amps, const int32_t* pick, const int32_t* b, const float* lam, int n, int m,
+                     int h, int w, int bmax, float* delta, void* stream);
+/* Synthesis, float32: v = src + sum_{u, v} Re(delta[u][v] e^{+2 pi i (u y / h + v x / w)}) per value; field (float32 [n][h][w][3],
+ * may be NULL) = v; out (uint8 [n][h][w][3], may be NULL; one of the two is required) = v rounded half to even, then clamped to
+ * [0, 255]; counts (int64 [n][2], may be NULL, ACCUMULATES) += {values with v < 0, values with v > 255}.  cols_ws: float32
+ * [n][3][K][w][2], the sums over v, written by a pre-kernel.  tw_h, tw_w: float32 [h][2], [w][2].  A sample with b[i] = -1 is
+ * copied.  Two forms with identical bytes, chosen per launch: the frame tile is moved in 16-byte accesses when w % 16 == 0 and src
+ * and out are 16-byte aligned, in bytes otherwise. */
+int udaseg_fda_apply_u8(const uint8_t* src, const float* delta, const int32_t* b, const float* tw_h, const float* tw_w, int n, int h,
+                        int w, int bmax, float* cols_ws, uint8_t* out, float* field, int64_t* counts, void* stream);
+
 /* ---- rendering of label maps: colour masks, overlays, error maps, outlines, class counts in one pass (reference predict.py
  * create_colored_mask / create_overlay / test_model's class distribution, train.py _log_predictions).  Per pixel of image i of
  * n images [h][w], all tensors contiguous:

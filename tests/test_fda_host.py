@@ -1,0 +1,288 @@
+"""CPU checks of the Fourier style transfer (fda.py): the numpy mirror tests/_fda_ref.py against an independent partial-DFT
+evaluation and the properties its cases must have for the GPU tests to mean something, the documented draws, every argument
+refusal of the public functions, the rows of the entry points in the three tables, and the library's own refusals.  No GPU."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import _fda_ref as R
+
+TAU = 2e-3            # the largest tolerance tests/test_gpu_fda.py may use: the near-boundary share below is certified at it
+
+
+@pytest.fixture(scope="module")
+def F():
+    from uda_aerial_semantic_segmentation_research_amd import fda
+    return fda
+
+
+# ------------------------------------------------------------------------------------------------------- the mirror itself
+@pytest.mark.parametrize("case", R.CASES, ids=R.case_id)
+def test_mirror_self_checks(case):
+    n, h, w, b = case
+    ref = R.reference(case)
+    field = ref["field"]
+    # an independent float64 evaluation (dense partial DFT, the contract's own form) agrees with the full-FFT mirror
+    other = R.partial_transfer(ref["src"], ref["tgt"], ref["b"], ref["lam"])
+    worst = float(np.abs(other - field).max())
+    below, above = float((field < 0).mean()), float((field > 255).mean())
+    near = float(R.near_half(field, TAU).mean())
+    print(f"{R.case_id(case)}: partial DFT against full FFT {worst:.2e}, below 0 {100 * below:.2f} %, above 255 {100 * above:.2f} %, "
+          f"smallest band amplitude {ref['smallest']:.2e}, within {TAU} of a rounding boundary {100 * near:.2f} %")
+    assert worst <= 1e-9
+    bmax = max(max(b), 0)
+    spec = np.abs(R.low_spectrum(ref["src"], bmax) - R.partial_spectrum(ref["src"], bmax)).max() / (255.0 * h * w)
+    assert spec <= 1e-12
+    if case not in R.CASES[:2]:
+        assert below > 0 and above > 0                                       # the clamp and both counters are exercised
+    assert ref["smallest"] >= 1e-7                                           # no case sits near the degenerate rule
+    assert near < 0.01
+    for i in range(n):
+        if b[i] < 0:
+            assert np.array_equal(field[i], ref["src"][i])
+
+
+def test_mirror_properties():
+    """lam = 0 returns the source; b = 0 moves the channel means to the mix of the two means and nothing else; the degenerate rule
+    fires on a constant source."""
+    src, tgt = R.frames(2, 17, 31)
+    out, _ = R.transfer(src, tgt, [5, 5], [0.0, 0.0])
+    assert np.abs(out - src).max() < 1e-10
+    out, _ = R.transfer(src, tgt, [0, 0], [1.0, 0.5])
+    ms, mt = src.mean(axis=(1, 2)), tgt.mean(axis=(1, 2))
+    assert np.abs((out - src) - (np.array([1.0, 0.5])[:, None] * (mt - ms))[:, None, None, :]).max() < 1e-10
+    const = np.full((1, 16, 16, 3), 77, dtype=np.uint8)
+    tg = R.frames(1, 16, 16)[1]
+    out, smallest = R.transfer(const, tg, [3], [1.0])
+    assert smallest <= R.DEGENERATE
+    want = R.partial_transfer(const, tg, [3], [1.0])                         # phase 0 everywhere: the target's amplitudes on cosines
+    assert np.abs(out - want).max() < 1e-9 and np.abs(out - 77).max() > 1
+
+
+# ------------------------------------------------------------------------------------------------------------------- draws
+def test_band_of_and_the_draws(F):
+    assert F.band_of(0.01, 512, 512) == 5 and F.band_of(0.09, 512, 512) == 46 and F.band_of(0.05, 256, 300) == 12
+    assert F.band_of(0.0, 7, 9) == 0 and F.band_of(0.5, 16, 16) == 7 and F.band_of(0.5, 17, 31) == 8 and F.band_of(0.3, 1, 1) == 0
+    assert F.max_band(1, 9) == 0 and F.max_band(16, 16) == 7 and F.max_band(17, 31) == 8
+    n, h, w = 200, 96, 128
+    b = F.draw_bands(n, h, w, torch.Generator().manual_seed(3), beta=(0.02, 0.2), p=0.7)
+    u = torch.rand(n, 2, generator=torch.Generator().manual_seed(3), dtype=torch.float64).numpy()
+    want = np.floor(96 * (0.02 + u[:, 0] * 0.18)).astype(np.int32)
+    want[u[:, 1] >= 0.7] = -1
+    assert b.dtype == torch.int32 and tuple(b.shape) == (n,) and not b.is_cuda and np.array_equal(b.numpy(), want)
+    assert 0.2 < float((want < 0).mean()) < 0.4 and want.max() <= 19 and want[want >= 0].min() >= 1
+    assert (F.draw_bands(50, 9, 9, torch.Generator().manual_seed(1), beta=(0.5, 0.5)).numpy() == 4).all()       # capped
+    assert (F.draw_bands(50, 9, 9, torch.Generator().manual_seed(1), p=0.0).numpy() == -1).all()
+    lam = F.draw_strengths(n, torch.Generator().manual_seed(4), lam=(0.25, 0.75))
+    u = torch.rand(n, generator=torch.Generator().manual_seed(4), dtype=torch.float64).numpy()
+    assert lam.dtype == torch.float32 and np.array_equal(lam.numpy(), (0.25 + u * 0.5).astype(np.float32))
+    assert (F.draw_strengths(5, torch.Generator().manual_seed(4)).numpy() == 1.0).all()
+    # one generator, the documented order: bands, then strengths
+    g = torch.Generator().manual_seed(9)
+    b2, l2 = F.draw_bands(4, 64, 48, g), F.draw_strengths(4, g, (0.0, 1.0))
+    g = torch.Generator().manual_seed(9)
+    ub = torch.rand(4, 2, generator=g, dtype=torch.float64).numpy()
+    ul = torch.rand(4, generator=g, dtype=torch.float64).numpy()
+    assert np.array_equal(b2.numpy(), np.floor(48 * (0.01 + ub[:, 0] * 0.04)).astype(np.int32))
+    assert np.array_equal(l2.numpy(), ul.astype(np.float32))
+
+
+def test_draw_refusals(F):
+    for bad in (dict(beta=(0.1, 0.05)), dict(beta=(-0.1, 0.2)), dict(beta=(0.1, 0.6)), dict(beta=0.1), dict(p=1.5), dict(p=-0.1),
+                dict(p="x")):
+        with pytest.raises(ValueError):
+            F.draw_bands(3, 8, 8, None, **bad)
+    for n, h, w in ((0, 8, 8), (3, 0, 8), (3, 8, -1), (2.5, 8, 8)):
+        with pytest.raises(ValueError):
+            F.draw_bands(n, h, w)
+    for bad in ((0.5, 0.2), (-0.1, 0.5), (0.0, 1.1), 1.0):
+        with pytest.raises(ValueError):
+            F.draw_strengths(3, None, bad)
+    with pytest.raises(ValueError):
+        F.draw_strengths(0)
+    for beta in (-0.01, 0.51, "x"):
+        with pytest.raises(ValueError):
+            F.band_of(beta, 8, 8)
+    with pytest.raises(ValueError):
+        F.band_of(0.1, 0, 8)
+
+
+# -------------------------------------------------------------------------------------------------------- public functions
+def test_public_functions_refuse_bad_arguments_on_cpu_tensors(F, monkeypatch):
+    """Every refusal comes before the device is asked for: on this machine _device() would raise RuntimeError (no GPU), so a
+    ValueError shows the order."""
+    monkeypatch.setattr(F, "_device", lambda: (_ for _ in ()).throw(AssertionError("the device was reached")))
+    n, h, w = 2, 8, 12
+    src = torch.zeros((n, h, w, 3), dtype=torch.uint8)
+    tgt = torch.zeros((n, h, w, 3), dtype=torch.uint8)
+    amps = torch.zeros((n, 3, 5, 5), dtype=torch.float64)
+    b = torch.tensor([2, -1], dtype=torch.int32)
+    for frames in (src.float(), src[0], src[..., :2], torch.zeros((0, h, w, 3), dtype=torch.uint8), "frames"):
+        with pytest.raises(ValueError):
+            F.low_spectrum(frames, 1)
+        with pytest.raises(ValueError):
+            F.amplitudes(frames, 1)
+        with pytest.raises(ValueError):
+            F.transfer(frames, tgt, b)
+    for bmax in (-1, 4, 1.0, True):                                           # max_band(8, 12) = 3
+        with pytest.raises(ValueError):
+            F.low_spectrum(src, bmax)
+    bad_calls = [
+        dict(tgt=tgt[:, :7]), dict(tgt=tgt.float()), dict(tgt=None), dict(tgt=amps[:, :2]), dict(tgt=amps[:, :, :4, :4]),
+        dict(tgt=amps[:, :, :, :3]), dict(tgt=torch.zeros((n, 3, 9, 9), dtype=torch.float64)),          # K = 9: bmax 4 > 3
+        dict(tgt=amps, bmax=1),
+        dict(b=b.long()), dict(b=b[:1]), dict(b=torch.tensor([2, -2], dtype=torch.int32)), dict(b=torch.tensor([4, 0], dtype=torch.int32)),
+        dict(tgt=amps, b=torch.tensor([3, 0], dtype=torch.int32)),                                     # above the table's bmax
+        dict(lam=torch.tensor([1.0, 0.5], dtype=torch.float64)), dict(lam=torch.tensor([1.0], dtype=torch.float32)),
+        dict(lam=torch.tensor([1.5, 0.5], dtype=torch.float32)), dict(lam=torch.tensor([-0.1, 0.5], dtype=torch.float32)),
+        dict(pick=torch.tensor([0, 2], dtype=torch.int32)), dict(pick=torch.tensor([-1, 0], dtype=torch.int32)),
+        dict(pick=torch.tensor([0, 1], dtype=torch.int64)), dict(tgt=tgt[:1]),                         # fewer targets, no pick
+        dict(dtype=torch.float16), dict(bmax=4), dict(bmax=-1),
+    ]
+    for kw in bad_calls:
+        args = dict(src=src, tgt=tgt, b=b, lam=None, pick=None, dtype=torch.uint8, bmax=None)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            F.transfer(args["src"], args["tgt"], args["b"], args["lam"], args["pick"], dtype=args["dtype"], bmax=args["bmax"])
+    with pytest.raises(ValueError):
+        F.AmplitudeBank(-1, 4)
+    with pytest.raises(ValueError):
+        F.AmplitudeBank(2, 0)
+    bank = F.AmplitudeBank(2, 4)
+    assert len(bank) == 0
+    for call in (bank.table, lambda: bank.draw(2), lambda: F.transfer(src, bank, b)):
+        with pytest.raises(ValueError):
+            call()
+    with pytest.raises(ValueError):
+        bank.add(src.float())
+    with pytest.raises(ValueError):
+        F.AmplitudeBank(4, 4).add(src)                                        # bmax 4 > max_band(8, 12)
+    for kw in (dict(beta=(0.2, 0.1)), dict(lam=(0.5, 1.5)), dict(p=2.0)):
+        with pytest.raises(ValueError):
+            F.StyledLoader([], [], **kw)
+
+
+class _Batches:
+    def __init__(self, batches):
+        self.batches = batches
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
+def test_styled_loader_refuses_mismatched_batches(F, monkeypatch):
+    monkeypatch.setattr(F, "_device", lambda: torch.device("cpu"))           # the refusals come before any kernel
+    u8 = lambda *s: torch.zeros(s, dtype=torch.uint8)      # noqa: E731
+    good = (u8(2, 8, 12, 3), u8(2, 8, 12))
+    for source, target in (([good], [u8(2, 8, 10, 3)]),                       # another H x W
+                           ([good], [u8(1, 8, 12, 3)]),                       # fewer target frames than source samples
+                           ([good[0]], [u8(2, 8, 12, 3)]),                    # no masks
+                           ([(good[0], u8(2, 8, 11))], [u8(2, 8, 12, 3)]),
+                           ([(good[0].float(), good[1])], [u8(2, 8, 12, 3)])):
+        loader = F.StyledLoader(_Batches(source), _Batches(target))
+        assert len(loader) == 1
+        with pytest.raises(ValueError):
+            next(iter(loader))
+    bank = F.AmplitudeBank(1, 4)
+    loader = F.StyledLoader(_Batches([good, good]), bank, beta=(0.1, 0.3))    # needs bmax 2
+    assert len(loader) == 2
+    with pytest.raises(ValueError, match="bmax"):
+        next(iter(loader))
+
+
+# ------------------------------------------------------------------------------------------------------------ operand rows
+ENTRIES = ("udaseg_fda_spectrum_u8", "udaseg_fda_delta", "udaseg_fda_apply_u8", "udaseg_fda_amplitude")
+
+
+def test_operand_rows():
+    from uda_aerial_semantic_segmentation_research_amd import _lib, _operands as O, kernels as K
+    assert callable(K.fda_spectrum_u8) and callable(K.fda_delta) and callable(K.fda_apply_u8) and callable(K.fda_amplitude)
+    header = open(__file__.replace("tests/test_fda_host.py", "include/udaseg.h")).read()
+    for e in ENTRIES:
+        assert e in _lib.SIGNATURES and e in O.OPERANDS and f"int {e}(" in header
+        assert len(O.OPERANDS[e]) == len(_lib.SIGNATURES[e][1]) and _lib.SIGNATURES[e][0] is ctypes.c_int
+    opt = {e: {r[1]: r[4] for r in O.OPERANDS[e] if r[0] == "tensor"} for e in ENTRIES}
+    assert opt["udaseg_fda_spectrum_u8"] == {"frames": False, "tw_h": False, "tw_w": False, "rows_ws": False, "coeffs": False}
+    assert opt["udaseg_fda_delta"] == {"coeffs": False, "amps": False, "pick": False, "b": False, "lam": False, "delta": False}
+    assert opt["udaseg_fda_apply_u8"] == {"src": False, "delta": False, "b": False, "tw_h": False, "tw_w": False, "cols_ws": False,
+                                          "out": True, "field": True, "counts": True}
+    n, m, h, w, bmax = 3, 2, 9, 7, 2
+    k = 2 * bmax + 1
+    f64, f32, i32, u8, i64 = torch.float64, torch.float32, torch.int32, torch.uint8, torch.int64
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in O.requirements("udaseg_fda_spectrum_u8", None, None, None, n, h, w, bmax, None, None, 0)}
+    assert req == {"frames": (u8, n * h * w * 3), "tw_h": (f64, 2 * h), "tw_w": (f64, 2 * w), "rows_ws": (f64, n * 3 * h * k * 2),
+                   "coeffs": (f64, n * 3 * k * k * 2)}
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in O.requirements("udaseg_fda_amplitude", None, 50, None, 0)}
+    assert req == {"coeffs": (f64, 100), "amps": (f64, 50)}
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in
+           O.requirements("udaseg_fda_delta", None, None, None, None, None, n, m, h, w, bmax, None, 0)}
+    assert req == {"coeffs": (f64, n * 3 * k * k * 2), "amps": (f64, m * 3 * k * k), "pick": (i32, n), "b": (i32, n), "lam": (f32, n),
+                   "delta": (f32, n * 3 * k * k * 2)}
+    req = {nm: (dt, cnt) for nm, dt, cnt, _ in
+           O.requirements("udaseg_fda_apply_u8", None, None, None, None, None, n, h, w, bmax, None, None, None, None, 0)}
+    assert req == {"src": (u8, n * h * w * 3), "delta": (f32, n * 3 * k * k * 2), "b": (i32, n), "tw_h": (f32, 2 * h),
+                   "tw_w": (f32, 2 * w), "cols_ws": (f32, n * 3 * k * w * 2), "out": (u8, n * h * w * 3), "field": (f32, n * h * w * 3),
+                   "counts": (i64, n * 2)}
+
+
+def _caller(fn, names, good):
+    def call(**kw):
+        args = list(good)
+        for k, v in kw.items():
+            args[names.index(k)] = v
+        return fn(*args)
+    return call
+
+
+def test_library_refuses_bad_arguments_before_any_launch():
+    """The C entry points return an error code and launch nothing (no GPU here): NULL pointers, the extents, bmax outside
+    [0, (min(h, w) - 1) / 2], and an output range that overlaps an operand or another output."""
+    from uda_aerial_semantic_segmentation_research_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(1 << 20)
+    a = (ctypes.addressof(buf) + 15) & ~15
+    slot = lambda i: a + 65536 * i      # noqa: E731
+    n, m, h, w, bmax = 2, 2, 8, 12, 3                                         # K = 7; frames 576 B, coeffs 4704 B, rows_ws 5376 B
+    huge = dict(n=1 << 11, h=1 << 10, w=1 << 10)
+
+    names = ["frames", "tw_h", "tw_w", "n", "h", "w", "bmax", "rows_ws", "coeffs", "stream"]
+    frames, tw_h, tw_w, rows_ws, coeffs = (slot(i) for i in range(5))
+    call = _caller(lib.udaseg_fda_spectrum_u8, names, [frames, tw_h, tw_w, n, h, w, bmax, rows_ws, coeffs, None])
+    for kw in (dict(frames=None), dict(tw_h=None), dict(tw_w=None), dict(rows_ws=None), dict(coeffs=None), dict(n=0), dict(h=0),
+               dict(w=-1), huge, dict(bmax=-1), dict(bmax=4), dict(h=6),
+               dict(coeffs=frames + 575), dict(coeffs=tw_h + 127), dict(coeffs=tw_w - 4703), dict(rows_ws=frames), dict(rows_ws=tw_w + 191),
+               dict(coeffs=rows_ws + 5375), dict(rows_ws=coeffs + 4703)):
+        assert call(**kw) != 0, kw
+        assert lib.udaseg_last_error()
+    assert call(bmax=4) != 0 and b"bmax" in lib.udaseg_last_error()
+    assert call(coeffs=frames) != 0 and b"overlaps" in lib.udaseg_last_error()
+
+    call = _caller(lib.udaseg_fda_amplitude, ["coeffs", "count", "amps", "stream"], [slot(0), 100, slot(1), None])
+    for kw in (dict(coeffs=None), dict(amps=None), dict(count=0), dict(count=-5), dict(amps=slot(0) + 1599), dict(amps=slot(0) - 799)):
+        assert call(**kw) != 0, kw
+
+    names = ["coeffs", "amps", "pick", "b", "lam", "n", "m", "h", "w", "bmax", "delta", "stream"]
+    coeffs, amps, pick, b, lam, delta = (slot(i) for i in range(6))           # delta 2352 B, amps 2352 B
+    call = _caller(lib.udaseg_fda_delta, names, [coeffs, amps, pick, b, lam, n, m, h, w, bmax, delta, None])
+    for kw in (dict(coeffs=None), dict(amps=None), dict(pick=None), dict(b=None), dict(lam=None), dict(delta=None), dict(n=0), dict(m=0),
+               dict(h=0), dict(w=0), huge, dict(bmax=-1), dict(bmax=4), dict(delta=coeffs + 4703), dict(delta=amps - 2351),
+               dict(delta=pick + 7), dict(delta=b - 2351), dict(delta=lam)):
+        assert call(**kw) != 0, kw
+        assert lib.udaseg_last_error()
+
+    names = ["src", "delta", "b", "tw_h", "tw_w", "n", "h", "w", "bmax", "cols_ws", "out", "field", "counts", "stream"]
+    src, delta, b, tw_h, tw_w, cols_ws, out, field, counts = (slot(i) for i in range(9))   # cols_ws 4032 B, field 2304 B, counts 32 B
+    call = _caller(lib.udaseg_fda_apply_u8, names, [src, delta, b, tw_h, tw_w, n, h, w, bmax, cols_ws, out, field, counts, None])
+    for kw in (dict(src=None), dict(delta=None), dict(b=None), dict(tw_h=None), dict(tw_w=None), dict(cols_ws=None),
+               dict(out=None, field=None), dict(n=0), dict(h=-3), dict(w=0), huge, dict(bmax=-1), dict(bmax=4),
+               dict(out=src), dict(out=src + 575), dict(field=src - 2303), dict(out=delta + 2351), dict(cols_ws=delta), dict(counts=b + 4),
+               dict(field=tw_h + 63), dict(out=tw_w - 575), dict(out=cols_ws + 4031), dict(field=out + 575), dict(counts=field + 2303),
+               dict(counts=cols_ws)):
+        assert call(**kw) != 0, kw
+        assert lib.udaseg_last_error()
+    assert call(out=None, field=None) != 0 and b"out, field" in lib.udaseg_last_error()

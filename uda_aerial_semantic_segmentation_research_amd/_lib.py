@@ -121,6 +121,10 @@ SIGNATURES = {
     "udaseg_pseudo_labels": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "udaseg_classmix_select": (_I, [_P, _I, _I, _L, _P, _P, _P]),
     "udaseg_classmix_u8": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "udaseg_fda_spectrum_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_fda_amplitude": (_I, [_P, _L, _P, _P]),
+    "udaseg_fda_delta": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_fda_apply_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "udaseg_render_u8": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -340,6 +340,16 @@ OPERANDS = {
                            T("tgt_masks", u8, "n*h*w", True), T("sel", i32, "n"), T("boxes", i32, "n*4", True), I("n"), I("h"), I("w"),
                            I("classes"), I("void_label"), T("out", u8, "n*h*w*3"), T("out_masks", u8, "n*h*w"),
                            T("counts", i64, "n*3", True), S],
+    # ---- Fourier style transfer (K = 2*bmax+1 frequencies per axis)
+    "udaseg_fda_spectrum_u8": [T("frames", u8, "n*h*w*3"), T("tw_h", f64, "h*2"), T("tw_w", f64, "w*2"), I("n"), I("h"), I("w"),
+                               I("bmax"), T("rows_ws", f64, "n*3*h*(2*bmax+1)*2"), T("coeffs", f64, "n*3*(2*bmax+1)**2*2"), S],
+    "udaseg_fda_amplitude": [T("coeffs", f64, "count*2"), I("count"), T("amps", f64, "count"), S],
+    "udaseg_fda_delta": [T("coeffs", f64, "n*3*(2*bmax+1)**2*2"), T("amps", f64, "m*3*(2*bmax+1)**2"), T("pick", i32, "n"),
+                         T("b", i32, "n"), T("lam", f32, "n"), I("n"), I("m"), I("h"), I("w"), I("bmax"),
+                         T("delta", f32, "n*3*(2*bmax+1)**2*2"), S],
+    "udaseg_fda_apply_u8": [T("src", u8, "n*h*w*3"), T("delta", f32, "n*3*(2*bmax+1)**2*2"), T("b", i32, "n"), T("tw_h", f32, "h*2"),
+                            T("tw_w", f32, "w*2"), I("n"), I("h"), I("w"), I("bmax"), T("cols_ws", f32, "n*3*(2*bmax+1)*w*2"),
+                            T("out", u8, "n*h*w*3", True), T("field", f32, "n*h*w*3", True), T("counts", i64, "n*2", True), S],
     "udaseg_render_u8": [T("labels", "(i64 if labels_i64 else u8)", "n*h*w"), T("truth", "(i64 if labels_i64 else u8)", "n*h*w", True),
                          I("labels_i64"), T("base", "(u8 if base_kind == 1 else (bf16 if base_kind == 3 else f32))",
                                             "n*h*w*(3 if base_kind == 1 else (8 if base_kind == 3 else 4))", True), I("base_kind"),

@@ -133,6 +133,29 @@ def classmix_u8(src, src_masks, tgt, tgt_masks, sel, boxes, n, h, w, classes, vo
           "classmix_u8")
 
 
+def fda_spectrum_u8(frames, tw_h, tw_w, n, h, w, bmax, rows_ws, coeffs, st=None):
+    """coeffs [n,3,K,K,2] float64 = the K x K lowest frequencies (K = 2 bmax + 1) of every channel of uint8 frames [n,h,w,3], through
+    rows_ws [n,3,h,K,2] float64; tw_h [h,2] / tw_w [w,2]: the float64 (cos, sin) tables (fda.py's module docstring)."""
+    check(ops.udaseg_fda_spectrum_u8(frames, tw_h, tw_w, n, h, w, bmax, rows_ws, coeffs, st), "fda_spectrum_u8")
+
+
+def fda_amplitude(coeffs, count, amps, st=None):
+    """amps [count] float64 = the moduli of count (re, im) float64 coefficients."""
+    check(ops.udaseg_fda_amplitude(coeffs, count, amps, st), "fda_amplitude")
+
+
+def fda_delta(coeffs, amps, pick, b, lam, n, m, h, w, bmax, delta, st=None):
+    """delta [n,3,K,K,2] float32 = lam (|F_t| - |F_s|) F_s / |F_s| / (h w) inside every sample's band b [n] int32, 0 outside; amps
+    [m,3,K,K] float64, pick [n] int32 the row of amps per sample, lam [n] float32."""
+    check(ops.udaseg_fda_delta(coeffs, amps, pick, b, lam, n, m, h, w, bmax, delta, st), "fda_delta")
+
+
+def fda_apply_u8(src, delta, b, tw_h, tw_w, n, h, w, bmax, cols_ws, out, field, counts, st=None):
+    """out [n,h,w,3] uint8 and / or field [n,h,w,3] float32 = src + the real inverse transform of delta; counts [n,2] int64 or None
+    += values below 0, above 255; cols_ws [n,3,K,w,2] float32; tw_h / tw_w: the float32 tables."""
+    check(ops.udaseg_fda_apply_u8(src, delta, b, tw_h, tw_w, n, h, w, bmax, cols_ws, out, field, counts, st), "fda_apply_u8")
+
+
 RENDER_BASE_NONE, RENDER_BASE_U8, RENDER_BASE_F32, RENDER_BASE_BF16 = 0, 1, 2, 3
 _RENDER_HOST = {}
 
