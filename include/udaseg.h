@@ -422,6 +422,43 @@ int udaseg_pseudo_thresholds(const int64_t* hist, int classes, int bins, const d
 int udaseg_pseudo_labels(const float* scores, int64_t pixels, int classes, int ldc, int probs, int bins, const int32_t* thr_bins,
                          int void_label, uint8_t* labels, float* conf, int64_t* counts, void* stream);
 
+/* ---- prototype-rectified pseudo-labels (ProDA, Zhang et al. 2021; an extension, the reference has no feature-space component).
+ * feat: padded NHWC fp32 [pixels][ldf], 16-byte aligned, dim % 4 == 0, 4 <= dim <= 64, dim <= ldf, ldf % 4 == 0, 0 < pixels < 2^31;
+ * only channels < dim are read.  0 < classes <= 32.
+ * accumulate: for a pixel with labels[p] = c < classes and finite features sums[c][j] += f_j, sq[c] += sum_j f_j^2,
+ * counts[c] += 1; a label >= classes adds to counts[classes]; a pixel with a non-finite feature in a channel < dim adds to
+ * counts[classes + 1] and to nothing else (whatever its label).  sums: float64 [classes][dim], sq: float64 [classes], counts:
+ * int64 [classes + 2]; all three ACCUMULATE across calls.  Every addition and every square is float64 (features are widened on
+ * load; a pixel's squared norm is the float64 sum over ascending j of the exact squares, ONE number that is then added), so a
+ * cell differs from any other float64 summation of the same n_c numbers by at most n_c 2^-52 sum|x|; the order of the atomic
+ * additions is not fixed. */
+int udaseg_proto_accumulate(const float* feat, int ldf, int dim, const uint8_t* labels, int64_t pixels, int classes, double* sums,
+                            double* sq, int64_t* counts, void* stream);
+/* One small block; IEEE float64 with every product, quotient and sum rounded on its own (no fused multiply-add), bit for bit
+ * proto.update_mirror.  For a class c with n = counts[c] >= min_pixels (min_pixels >= 1): mean_j = sums[c][j] / (double)n,
+ * s = max(sq[c] / (double)n - sum_j mean_j * mean_j, 0) (the sum over ascending j from 0.0); if seen[c] == 0: proto[c] = mean,
+ * spread[c] = s, seen[c] = 1; else proto[c][j] = momentum * proto[c][j] + (1 - momentum) * mean_j and spread[c] likewise
+ * (0 <= momentum <= 1).  Then last_counts = counts (int64 [classes + 2]) and, with clear != 0, sums = sq = counts = 0.
+ * With tau_scale > 0: t = tau_scale * ((sum over the seen c, ascending, of spread[c]) / n_seen) and inv_tau[0] = (float)(1 / t)
+ * when t is finite and positive, else 0; with tau_scale <= 0 inv_tau is left as the caller filled it (a fixed temperature).
+ * proto: float64 [classes][dim], spread: float64 [classes], seen: int32 [classes], inv_tau: fp32 [1]. */
+int udaseg_proto_update(double* sums, double* sq, int64_t* counts, int classes, int dim, double momentum, int64_t min_pixels,
+                        double tau_scale, int clear, double* proto, double* spread, int32_t* seen, int64_t* last_counts,
+                        float* inv_tau, void* stream);
+/* out: fp32 [pixels][ldc], 16-byte aligned like scores ([pixels][ldc], ldc % 4 == 0, classes <= ldc); one pass, no atomics,
+ * the same bits on every run.  Per pixel in fp32:
+ *   probs == 0: m = the first maximum of the logits z, e_c = expf(z_c - m), S = sum_c e_c (udaseg_conf_hist's four chains),
+ *               p_c = e_c * (1 / S);   probs == 1: p_c = the given probabilities
+ *   d_c = sum_j (f_j - (float)proto[c][j])^2 (four chains, channel j in chain j % 4, folded as (s0 + s1) + (s2 + s3))
+ *   over the seen classes d* = min d_c and u_c = expf(-(d_c - d*) * inv_tau[0]); u_c = 0 for an unseen class; u_c = 1 for all
+ *   when no class is seen;   r_c = p_c * u_c, R = sum_c r_c, out_c = r_c / R;   channels classes .. ldc - 1 are written 0.
+ * A row is NaN in every channel < classes when a feature in a channel < dim or a score in a channel < classes is not finite,
+ * a probability lies outside [0, 1] (probs == 1), or R is zero or not finite: udaseg_pseudo_labels / udaseg_conf_hist with
+ * probs == 1 then count the pixel as NON-FINITE.  inv_tau == 0 gives p renormalised over the seen classes; a very large
+ * inv_tau gives the nearest seen prototype's class wherever its p is positive. */
+int udaseg_proto_rectify(const float* feat, int ldf, int dim, const float* scores, int ldc, int classes, int probs,
+                         const double* proto, const int32_t* seen, const float* inv_tau, int64_t pixels, float* out, void* stream);
+
 /* ---- cross-domain class mixing of a source and a target batch (DACS, Tranheden et al. 2021; ClassMix, Olsson et al. 2021; an
  * extension, the reference has no counterpart).  Integers only: every output is exact.
  * Selection, per source mask i, from the [n][256] table of udaseg_mask_hist_u8 (1 <= classes <= 32, min_pixels >= 1):

@@ -335,6 +335,16 @@ OPERANDS = {
     "udaseg_pseudo_labels": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
                              T("thr_bins", i32, "classes"), I("void_label"), T("labels", u8, "pixels"), T("conf", f32, "pixels", True),
                              T("counts", i64, "classes+2"), S],
+    # ---- prototype rectification (features: NHWC rows of ldf floats, dim of them used)
+    "udaseg_proto_accumulate": [T("feat", f32, "pixels*ldf"), I("ldf"), I("dim"), T("labels", u8, "pixels"), I("pixels"), I("classes"),
+                                T("sums", f64, "classes*dim"), T("sq", f64, "classes"), T("counts", i64, "classes+2"), S],
+    "udaseg_proto_update": [T("sums", f64, "classes*dim"), T("sq", f64, "classes"), T("counts", i64, "classes+2"), I("classes"),
+                            I("dim"), F("momentum"), I("min_pixels"), F("tau_scale"), I("clear"), T("proto", f64, "classes*dim"),
+                            T("spread", f64, "classes"), T("seen", i32, "classes"), T("last_counts", i64, "classes+2"),
+                            T("inv_tau", f32, 1), S],
+    "udaseg_proto_rectify": [T("feat", f32, "pixels*ldf"), I("ldf"), I("dim"), T("scores", f32, "pixels*ldc"), I("ldc"), I("classes"),
+                             I("probs"), T("proto", f64, "classes*dim"), T("seen", i32, "classes"), T("inv_tau", f32, 1), I("pixels"),
+                             T("out", f32, "pixels*ldc"), S],
     "udaseg_classmix_select": [T("hist", i64, "n*256"), I("n"), I("classes"), I("min_pixels"), T("keys", i32, "n*2"), T("sel", i32, "n"), S],
     "udaseg_classmix_u8": [T("src", u8, "n*h*w*3"), T("src_masks", u8, "n*h*w"), T("tgt", u8, "n*h*w*3"),
                            T("tgt_masks", u8, "n*h*w", True), T("sel", i32, "n"), T("boxes", i32, "n*4", True), I("n"), I("h"), I("w"),

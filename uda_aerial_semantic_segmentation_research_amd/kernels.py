@@ -120,6 +120,27 @@ def pseudo_labels(scores_base, pixels, classes, ldc, probs, bins, thr_bins, void
                                    counts, st), "pseudo_labels")
 
 
+def proto_accumulate(feat_base, ldf, dim, labels, pixels, classes, sums, sq, counts, st=None):
+    """sums [classes * dim] / sq [classes] float64, counts [classes + 2] int64 += the per-class feature sums, squared norms and pixel
+    counts of feat [pixels * ldf] fp32 under labels [pixels] uint8 (then the labels beyond the classes, then the non-finite pixels)."""
+    check(ops.udaseg_proto_accumulate(feat_base, ldf, dim, labels, pixels, classes, sums, sq, counts, st), "proto_accumulate")
+
+
+def proto_update(sums, sq, counts, classes, dim, momentum, min_pixels, tau_scale, clear, proto, spread, seen, last_counts, inv_tau,
+                 st=None):
+    """proto / spread / seen from the accumulated batch (first sight or EMA), last_counts = counts, the accumulators zeroed with
+    ``clear``, inv_tau [1] fp32 from the spreads with ``tau_scale > 0``; include/udaseg.h has the arithmetic."""
+    check(ops.udaseg_proto_update(sums, sq, counts, classes, dim, float(momentum), int(min_pixels), float(tau_scale),
+                                  int(bool(clear)), proto, spread, seen, last_counts, inv_tau, st), "proto_update")
+
+
+def proto_rectify(feat_base, ldf, dim, scores_base, ldc, classes, probs, proto, seen, inv_tau, pixels, out, st=None):
+    """out [pixels * ldc] fp32 = the class probabilities of scores [pixels * ldc] re-weighted by the distance of feat [pixels * ldf]
+    to the seen prototypes and renormalised; NaN rows for non-finite pixels."""
+    check(ops.udaseg_proto_rectify(feat_base, ldf, dim, scores_base, ldc, classes, int(bool(probs)), proto, seen, inv_tau, pixels,
+                                   out, st), "proto_rectify")
+
+
 def classmix_select(hist, n, classes, min_pixels, keys, sel, st=None):
     """sel [n] int32 = the class selection of every source mask from its row of the [n,256] int64 mask histogram and its Philox
     key (keys [n,2] int32 bit patterns): half of the present classes, rounded up (mix.py's module docstring has the rule)."""
