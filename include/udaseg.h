@@ -374,6 +374,45 @@ int udaseg_selfinfo_bwd(const float* logits, const void* dmaps, int64_t pixels, 
 int udaseg_entropy_loss(const float* logits, int64_t pixels, int classes, int ldc, int kind, double* partials, float* loss,
                         float* dlogits, float* entropy, void* stream);
 
+/* ---- distillation: a loss between student logits and a teacher DISTRIBUTION with pixel and image weights (Hinton et al. 2015;
+ * symmetric cross entropy, Wang et al., ICCV 2019; an extension, the reference has no counterpart).  Loss and gradient in ONE
+ * pass over the logits, as udaseg_ce_fwd_bwd.
+ * logits: fp32 [pixels][ldc], teacher: fp32 [pixels][ldt], pixels = batch * pix_per_image, both 16-byte aligned,
+ * 2 <= classes <= ld <= 32, ld % 4 == 0, ldt may differ from ldc; only lanes < classes are read.  Per pixel, in fp32:
+ *   lp = log_softmax(z), p = exp(lp) of the student
+ *   probs == 0: q = softmax(t * teacher_inv_temp), lq = log_softmax(t * teacher_inv_temp);  probs == 1: q_c = t_c, lq_c = logf(q_c)
+ *   Q = sum_c q_c
+ *   kind 0 (soft CE):    l = -sum_c q_c * lp_c;           kind 1 (KL(q||p)):  l = sum_c q_c * (lq_c - lp_c)
+ *                        dl/dz_k = Q * p_k - q_k for both; a lane with q_c == 0 contributes exactly 0 (never 0 * inf)
+ *   kind 2 (symmetric):  l = alpha * (-sum_c q_c * lp_c) + beta * sum_c p_c * g_c,  g_c = -max(lq_c, log_floor) (log_floor < 0),
+ *                        g_c = -log_floor where q_c == 0;   dl/dz_k = alpha * (Q * p_k - q_k) + beta * p_k * (g_k - sum_c p_c * g_c);
+ *                        a lane with p_c == 0 contributes exactly 0 to the reverse term
+ * w_p = weight_px[p] * weight_img[p / pix_per_image] (fp32 product; either pointer NULL = 1).  A pixel is VOID -- loss exactly 0,
+ * gradient exactly 0 in all ldc lanes -- when w_p == 0, when w_p is negative or not finite, when a teacher lane < classes (times
+ * teacher_inv_temp for probs == 0) is not finite, or, with probs == 1, when a q_c lies outside [0, 1] or Q == 0.
+ * stats (NULL = not wanted): int64 [3], ACCUMULATED with integer atomics: counted pixels, void by weight 0, void otherwise.
+ * loss = sum_p w_p * l_p, divided by pixels when mean != 0, by *denom (device f64, udaseg_pixel_weight_sum) when denom != NULL
+ * (*denom == 0: NaN); mean and denom exclude each other.  partials: udaseg_seg_partials() doubles of scratch; the loss is a
+ * fixed-order sum (no float atomics): the same bits on every call, with and without dlogits / colsum.
+ * dlogits[pixels][ldc] (NULL = not wanted): the gradient for an upstream gradient of 1, divided like the loss, pad lanes exactly 0.
+ * colsum[ldc] with colsum_partials[udaseg_seg_partials() * ldc] (both or neither): the gradient's per-class sums, as
+ * udaseg_ce_fwd_bwd's (the head convolution's bias gradient). */
+int udaseg_soft_ce_fwd_bwd(const float* logits, const float* teacher, const float* weight_px, const float* weight_img, int batch,
+                           int64_t pix_per_image, int classes, int ldc, int ldt, int probs, int kind, float teacher_inv_temp,
+                           float alpha, float beta, float log_floor, int mean, const double* denom, double* partials, float* loss,
+                           float* dlogits, float* colsum_partials, float* colsum, int64_t* stats, void* stream);
+/* denom[0] = the fixed-order f64 sum of w_p (as above) over the pixels whose weight does not void them (w_p > 0 and finite);
+ * counts: int64 [2] = zero weights, negative or non-finite weights (written).  Reads only the weights, as udaseg_ce_target_stats
+ * reads only the targets.  partials: 3 * udaseg_seg_partials() doubles of scratch.  Both weight pointers NULL: denom = pixels. */
+int udaseg_pixel_weight_sum(const float* weight_px, const float* weight_img, int batch, int64_t pix_per_image, double* partials,
+                            double* denom, int64_t* counts, void* stream);
+/* Per image i: above[i] (int64, written) = its pixels whose winner confidence is >= tau, the confidence being exactly
+ * udaseg_conf_hist's (1 / S for logits, q[c^] for probabilities); nonfinite[i] (int64, written) = its NON-FINITE pixels, which
+ * are in no count; share[i] = (float)((double)above[i] / pix_per_image).  Integer atomics only: exact, the same on every run.
+ * scores: fp32 [batch * pix_per_image][ldc], 16-byte aligned, 0 < classes <= 32, classes <= ldc, ldc % 4 == 0; batch <= 65535. */
+int udaseg_conf_share(const float* scores, int batch, int64_t pix_per_image, int classes, int ldc, int probs, float tau,
+                      int64_t* above, int64_t* nonfinite, float* share, void* stream);
+
 /* ---- validation metrics (SegmentationTrainer.calculate_metrics, train.py:225-243; src/analysis/metrics.py:17-29):
  * confusion[t*classes + argmax(logits[p])] += 1 over all pixels (int64, caller-zeroed); pred[p] = argmax (optional).
  * classes <= 32, ldc <= 32. */

@@ -1,0 +1,218 @@
+"""The distillation kernels (csrc/distill.hip: udaseg_soft_ce_fwd_bwd, udaseg_pixel_weight_sum, udaseg_conf_share) against the
+float64 restatement of tests/_distill_ref.py (proven against torch's double-precision autograd by tests/test_distill_host.py),
+called at kernel level through kernels.py; then ``SoftCrossEntropyLoss`` and ``pseudo.confidence_share`` through autograd.
+
+The bar is the project's, ``_norm_ref.bar``: with e = |kernel - f64| / magnitude and d = |fp32 leg - f64| / magnitude element-wise,
+max(e) <= max(4 x max(d), 2^-22), the loss scalar and the column sums included, no element masked out; the magnitudes are defined
+in tests/_distill_ref.py.  Both inputs sit in padded NHWC buffers whose pad lanes hold 7.0 and one lane 1e30; every output buffer is
+pre-filled with NaN; pad lanes of the gradient and every lane of a void pixel must come back exactly 0; the loss must be the same
+bits with and without dlogits / colsum and across two calls; the counters, ``above`` and ``share`` must equal the mirror exactly.
+
+Shapes: classes 2, 5, 12, 23, 32 (ldc 4, 8, 12, 24, 32) by batch x pix_per_image 1 x 1, 3 x 85 (image boundaries inside a wave),
+1 x 257; ldt != ldc both ways; 1024 * 256 + 3 pixels at 23 classes, where a thread takes a second grid-stride pixel.  All three
+kinds, logits and probabilities, every reduction, with both weights, each alone and none.  Rows (tests/_distill_ref.py ``make_case``):
+random at scale 3, one-hot teacher probabilities, a saturated student, NaN teacher rows, a probability of 1.5, all-zero and
+sub-normalised probabilities, weight_px 0 / negative / NaN, an image with weight_img 0 -- mixed into every case and each alone at one
+pixel.  tests/test_distill_host.py runs the same grading with the float32 leg (and six mutations of it) in the kernels' place.
+Set UDASEG_DEVIATION_LOG to a file name to collect the figures.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _distill_ref as D
+from _distill_ref import F32
+from _parity import RTOL, check
+
+pytestmark = pytest.mark.gpu
+NAN = float("nan")
+
+
+def _log(line):
+    print(line)
+    path = os.environ.get("UDASEG_DEVIATION_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(line + "\n")
+
+
+def nans(shape, dtype=torch.float32):
+    return torch.full(shape, NAN, dtype=dtype, device="cuda")
+
+
+class GpuBackend:
+    """tests/_distill_ref.py's operations on the HIP kernels, numpy in and out."""
+    def __init__(self):
+        from uda_aerial_semantic_segmentation_research_amd import _lib, kernels as K
+        _lib.require_gpu()
+        self.K = K
+        self._held = {}
+
+    def dev(self, a):
+        """The device copy of a host array, made once per array (a case calls with the same buffers many times)."""
+        if a is None:
+            return None
+        hit = self._held.get(id(a))
+        if hit is None or hit[0] is not a:
+            if len(self._held) > 16:
+                self._held.clear()
+            hit = self._held[id(a)] = (a, torch.from_numpy(np.ascontiguousarray(a)).cuda())
+        return hit[1]
+
+    def soft_ce(self, zbuf, tbuf, wpx, wimg, batch, ppi, classes, probs, kind, hp, reduction, want_grad, want_colsum):
+        K = self.K
+        pixels, ldc = zbuf.shape
+        denom = None
+        if reduction == "weighted_mean":
+            denom = nans((1,), torch.float64)
+            K.pixel_weight_sum(self.dev(wpx), self.dev(wimg), batch, ppi, nans((3 * K.seg_partials(),), torch.float64), denom,
+                               torch.zeros(2, dtype=torch.int64, device="cuda"))
+        loss = nans(())
+        d = nans((pixels, ldc)) if want_grad else None
+        parts = nans((K.seg_partials() * ldc,)) if want_colsum else None
+        cs = nans((ldc,)) if want_colsum else None
+        stats = torch.zeros(3, dtype=torch.int64, device="cuda")
+        K.soft_ce_fwd_bwd(self.dev(zbuf), self.dev(tbuf), self.dev(wpx), self.dev(wimg), batch, ppi, classes, ldc, tbuf.shape[1], probs,
+                          kind, hp["inv_temp"], hp["alpha"], hp["beta"], hp["log_floor"], reduction == "mean", denom,
+                          nans((K.seg_partials(),), torch.float64), loss, d, parts, cs, stats)
+        host = lambda t: None if t is None else t.cpu().numpy()              # noqa: E731
+        return F32(host(loss)), host(d), host(cs), host(stats)
+
+    def pixel_weight_sum(self, wpx, wimg, batch, ppi):
+        K = self.K
+        denom, counts = nans((1,), torch.float64), torch.full((2,), -1, dtype=torch.int64, device="cuda")
+        K.pixel_weight_sum(self.dev(wpx), self.dev(wimg), batch, ppi, nans((3 * K.seg_partials(),), torch.float64), denom, counts)
+        return denom.cpu().numpy()[0], counts.cpu().numpy()
+
+    def conf_share(self, sbuf, batch, ppi, classes, probs, tau):
+        above = torch.full((batch,), -1, dtype=torch.int64, device="cuda")
+        nonfinite = torch.full((batch,), -1, dtype=torch.int64, device="cuda")
+        share = nans((batch,))
+        self.K.conf_share(self.dev(sbuf), batch, ppi, classes, sbuf.shape[1], probs, tau, above, nonfinite, share)
+        return above.cpu().numpy(), nonfinite.cpu().numpy(), share.cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def backend():
+    return GpuBackend()
+
+
+# ------------------------------------------------------------------------------------------------------------ kernel level
+@pytest.mark.parametrize("classes", D.CLASSES)
+@pytest.mark.parametrize("shape", D.SHAPES)
+def test_kernels_meet_the_bar(backend, shape, classes):
+    D.grade_case(backend, shape[0], shape[1], classes, 100 * classes + shape[1], _log).done()
+
+
+@pytest.mark.parametrize("row_kind", D.ROW_KINDS)
+def test_kernels_meet_the_bar_on_single_rows(backend, row_kind):
+    for classes in D.CLASSES:
+        D.grade_case(backend, 1, 1, classes, 7 * classes, _log, row_kind=row_kind).done()
+
+
+@pytest.mark.parametrize("classes,ldc,ldt", [(5, 8, 32), (5, 16, 8), (23, 24, 32)])
+def test_kernels_meet_the_bar_with_unequal_strides(backend, classes, ldc, ldt):
+    D.grade_case(backend, 3, 85, classes, 41, _log, ldc=ldc, ldt=ldt, combos=D.COVER).done()
+
+
+def test_kernels_meet_the_bar_past_the_grid(backend):
+    """1024 * 256 + 3 pixels: three threads take a second grid-stride pixel (about 25 MB of logits at 23 classes)."""
+    D.grade_case(backend, D.BIG[0], D.BIG[1], 23, 5, _log, combos=D.COVER[:3], weight_variants=False).done()
+
+
+@pytest.mark.parametrize("classes", D.CLASSES)
+def test_conf_share_is_the_mirror_exactly(backend, classes):
+    for batch, ppi in ((1, 1), (3, 85), (2, 4 * 256 + 1)):
+        D.grade_share(backend, batch, ppi, classes, 11 * classes + ppi, _log).done()
+    D.grade_share(backend, 3, 85, classes, 5, _log, ldc=32).done()
+
+
+def test_conf_share_past_the_grid(backend):
+    """More pixels per image than 256 blocks of 256 threads cover at once."""
+    D.grade_share(backend, 2, 256 * 256 + 77, 23, 3, _log).done()
+
+
+# ------------------------------------------------------------------------------------------------------------ module level
+@pytest.mark.parametrize("kind,probs,reduction", [("ce", False, "mean"), ("kl", True, "weighted_mean"), ("symmetric", True, "sum"),
+                                                  ("symmetric", False, "weighted_mean"), ("kl", False, "sum")])
+def test_module_forward_and_backward_through_autograd(kind, probs, reduction):
+    from uda_aerial_semantic_segmentation_research_amd.losses import SoftCrossEntropyLoss
+    g = torch.Generator().manual_seed(3)
+    n, c, h, w = 2, 5, 16, 24
+    z = 3.0 * torch.randn(n, c, h, w, generator=g)
+    t = 3.0 * torch.randn(n, c, h, w, generator=g)
+    if probs:
+        t = torch.softmax(t, 1)
+        t[0, :, 3, 3] = 0.0
+        t[0, 2, 3, 3] = 1.0                                    # one-hot
+    t[1, :, 0, 5] = NAN                                        # what proto.rectify writes at a bad pixel
+    pw = 0.25 + 1.5 * torch.rand(n, h, w, generator=g)
+    pw[0, 1, :4] = 0.0
+    pw[1, 2, 2] = -1.0
+    iw = torch.tensor([0.75, 0.5])
+    kw = dict(kind=kind, teacher_temperature=1.5, alpha=0.75, beta=1.25, log_floor=-4.0, reduction=reduction)
+    x = z.double().requires_grad_()
+    want, dead = D.torch_soft_loss(x, t.double(), probs, kind, 1.5, 0.75, 1.25, -4.0, reduction, pw.double(), iw.double())
+    (0.3 * want).backward()
+    loss_fn = SoftCrossEntropyLoss(**kw)
+    leaf = z.cuda().requires_grad_()
+    loss = 0.3 * loss_fn(leaf, t.cuda(), probs=probs, pixel_weight=pw.cuda(), image_weight=iw.cuda())
+    assert abs(loss.item() - 0.3 * want.item()) <= RTOL * abs(0.3 * want.item()), (loss.item(), 0.3 * want.item())
+    assert loss_fn.last_stats.tolist() == [int((~dead).sum()), 4, int(dead.sum()) - 4]
+    loss.backward(retain_graph=True)                           # an upstream gradient of 0.3: the in-place scaling
+    first, leaf.grad = leaf.grad.clone(), None
+    loss.backward()                                            # second backward: the entry point runs again
+    assert torch.equal(first, leaf.grad)
+    check(first, x.grad, f"{kind} gradient")
+    assert not first.cpu()[dead[:, None].expand_as(first)].any()                   # void pixels: exactly 0
+    with torch.no_grad():
+        plain = loss_fn(z.cuda(), t.cuda(), probs=probs, pixel_weight=pw.cuda(), image_weight=iw.cuda())
+    assert not plain.requires_grad and (0.3 * plain).item() == loss.item()         # the same kernel without dlogits: the same bits
+    with pytest.raises(ValueError, match="never receives a gradient"):
+        loss_fn(leaf, t.cuda().requires_grad_(), probs=probs)
+    with pytest.raises(ValueError, match="pixel_weight"):
+        loss_fn(leaf, t.cuda(), probs=probs, pixel_weight=pw.cuda()[:, :-1])
+    with pytest.raises(ValueError, match="teacher must be"):
+        loss_fn(leaf, t.cuda()[:, :-1], probs=probs)
+
+
+def test_module_reads_a_models_padded_logits_in_place_and_feeds_the_bias_gradient():
+    """Logits as ``Unet.forward`` returns them (a view of a padded NHWC buffer) and probabilities as ``proto.rectify`` returns them:
+    no layout kernel; the column sums land in the side table the head convolution's backward reads."""
+    from uda_aerial_semantic_segmentation_research_amd import losses as L
+    g = torch.Generator().manual_seed(8)
+    n, c, h, w, ldc = 2, 5, 8, 8, 8
+    zb = torch.full((n, h, w, ldc), 7.0)
+    zb[..., :c] = 3.0 * torch.randn(n, h, w, c, generator=g)
+    tb = torch.full((n, h, w, ldc), 1e30)
+    tb[..., :c] = torch.softmax(3.0 * torch.randn(n, h, w, c, generator=g), -1)
+    zv = zb.cuda().permute(0, 3, 1, 2)[:, :c].requires_grad_()
+    tv = tb.cuda().permute(0, 3, 1, 2)[:, :c]
+    assert L._padded_nhwc(zv.detach())[0].data_ptr() == zv.data_ptr() and L._padded_nhwc(tv)[0].data_ptr() == tv.data_ptr()
+    loss = L.SoftCrossEntropyLoss("kl")(zv, tv, probs=True)
+    loss.backward()
+    x = zb[..., :c].permute(0, 3, 1, 2).double().requires_grad_()
+    want, _ = D.torch_soft_loss(x, tb[..., :c].permute(0, 3, 1, 2).double(), True, "kl", 1.0, 1.0, 1.0, -4.0, "mean", None, None)
+    want.backward()
+    assert abs(loss.item() - want.item()) <= RTOL * abs(want.item())
+    check(zv.grad, x.grad, "gradient of padded logits")
+    (colsum,) = L.COLSUM_SIDE_TABLE.values()
+    check(colsum[:c], x.grad.sum((0, 2, 3)), "column sums")
+    assert not colsum[c:].any()
+    L.COLSUM_SIDE_TABLE.clear()
+
+
+def test_confidence_share_through_the_module(backend):
+    from uda_aerial_semantic_segmentation_research_amd.pseudo import confidence_share
+    n, c, h, w = 3, 23, 5, 17
+    for probs, tau in ((False, 0.968), (True, 0.5)):
+        s = D.make_scores(n, h * w, c, 21, int(probs), tau)
+        nchw = torch.from_numpy(s).view(n, h, w, c).permute(0, 3, 1, 2).contiguous().cuda()
+        share, above, nonfinite = confidence_share(nchw, tau, probs=probs, return_counts=True)
+        want = D.conf_share(s, n, h * w, int(probs), tau)
+        assert share.dtype == torch.float32 and share.shape == (n,) and share.is_cuda
+        assert np.array_equal(above.cpu().numpy(), want[0]) and np.array_equal(nonfinite.cpu().numpy(), want[1])
+        assert np.array_equal(share.cpu().numpy(), want[2])
+        assert torch.equal(confidence_share(nchw, tau, probs=probs), share)

@@ -113,6 +113,9 @@ SIGNATURES = {
     "udaseg_selfinfo_fwd": (_I, [_P, _L, _I, _I, _P, _I, _I, _P, _P]),
     "udaseg_selfinfo_bwd": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "udaseg_entropy_loss": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "udaseg_soft_ce_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "udaseg_pixel_weight_sum": (_I, [_P, _P, _I, _L, _P, _P, _P, _P]),
+    "udaseg_conf_share": (_I, [_P, _I, _L, _I, _I, _I, _F, _P, _P, _P, _P]),
     "udaseg_argmax_confusion": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "udaseg_score_hist": (_I, [_P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
     "udaseg_curve_finish": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

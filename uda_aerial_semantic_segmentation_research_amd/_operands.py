@@ -406,6 +406,19 @@ OPERANDS = {
     "udaseg_entropy_loss": [T("logits", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("kind"),
                             T("partials", f64, "seg_partials()"), T("loss", f32, 1), T("dlogits", f32, "pixels*ldc", True),
                             T("entropy", f32, "pixels", True), S],
+    # ---- distillation: student logits [pixels][ldc] against a teacher distribution [pixels][ldt], pixels = batch*pix_per_image
+    "udaseg_soft_ce_fwd_bwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("teacher", f32, "batch*pix_per_image*ldt"),
+                               T("weight_px", f32, "batch*pix_per_image", True), T("weight_img", f32, "batch", True), I("batch"),
+                               I("pix_per_image"), I("classes"), I("ldc"), I("ldt"), I("probs"), I("kind"), F("teacher_inv_temp"),
+                               F("alpha"), F("beta"), F("log_floor"), I("mean"), T("denom", f64, 1, True),
+                               T("partials", f64, "seg_partials()"), T("loss", f32, 1),
+                               T("dlogits", f32, "batch*pix_per_image*ldc", True),
+                               T("colsum_partials", f32, "seg_partials()*ldc", True), T("colsum", f32, "ldc", True),
+                               T("stats", i64, 3, True), S],
+    "udaseg_pixel_weight_sum": [T("weight_px", f32, "batch*pix_per_image", True), T("weight_img", f32, "batch", True), I("batch"),
+                                I("pix_per_image"), T("partials", f64, "3*seg_partials()"), T("denom", f64, 1), T("counts", i64, 2), S],
+    "udaseg_conf_share": [T("scores", f32, "batch*pix_per_image*ldc"), I("batch"), I("pix_per_image"), I("classes"), I("ldc"),
+                          I("probs"), F("tau"), T("above", i64, "batch"), T("nonfinite", i64, "batch"), T("share", f32, "batch"), S],
     # ---- discriminator tail
     "udaseg_gap_linear_sigmoid_fwd": [T("z", f32, "n*hw*c"), T("w", f32, "c"), T("b", f32, 1), T("partial", f32, "n*gap_splits(hw)*c"),
                                       T("pooled", f32, "n*c"), T("p", f32, "n"), I("n"), I("hw"), I("c"), S],

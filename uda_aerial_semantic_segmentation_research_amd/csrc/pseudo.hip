@@ -4,7 +4,8 @@
 // tiny kernel turns the histogram into one threshold BIN per class (udaseg_pseudo_thresholds), and one more pass writes the
 // uint8 masks with everything below its class's threshold marked void (udaseg_pseudo_labels).  No sort, integer counters only.
 //
-// The shared definition (pixel_conf below, used by BOTH pixel kernels, so that histogram and labelling cannot disagree).
+// The shared definition (pixel_conf of scores_common.h, used by BOTH pixel kernels and by udaseg_conf_share of distill.hip, so that
+// histogram, labelling and share cannot disagree).
 // scores: padded NHWC fp32 [pixels][ldc], ldc % 4 == 0, 0 < classes <= 32, classes <= ldc; only channels < classes count.
 //   probs == 0 (logits z):     c^ = first maximum of z (first_max of scores_common.h), m = z[c^],
 //                              S = sum_{c < classes} expf(z_c - m) in fp32 (four partial sums, channel c in sum c % 4,
@@ -29,41 +30,6 @@
 #include "scores_common.h"
 
 namespace udaseg {
-
-struct PixelConf {
-  int cls;        // c^
-  float p;        // confidence
-  bool finite;
-};
-
-template <int NV>
-__device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, int classes, int probs) {
-  f32x4 v[NV];
-  load_row<NV>(row, v);
-  float m;
-  PixelConf r;
-  r.cls = first_max<NV>(v, classes, m);
-  if (probs) {
-    bool nan = false;                                      // first_max steps over a NaN beyond channel 0
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) nan |= 4 * q + e < classes && v[q][e] != v[q][e];
-    r.p = m;
-    r.finite = !nan && m >= 0.f && m <= 1.f;
-  } else {
-    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};                       // channel c adds into partial sum c % 4: four short chains
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (4 * q + e < classes) s4[e] += expf(v[q][e] - m);   // exactly 1 at the maximum, so S >= 1 whenever it is a number
-    const float S = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    r.p = 1.f / S;
-    r.finite = __builtin_isfinite(r.p);
-  }
-  return r;
-}
 
 __device__ __forceinline__ int conf_bin(float p, int bins) { return min((int)floorf(p * (float)bins), bins - 1); }
 

@@ -1,5 +1,5 @@
 // Shared by every kernel that walks a padded NHWC buffer of per-pixel class scores: [pixels][ldc] fp32, classes <= ldc,
-// ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, curves.hip, pseudo.hip, predict.hip).  Such a kernel is a
+// ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, curves.hip, pseudo.hip, predict.hip, distill.hip).  Such a kernel is a
 // template on its row width in f32x4 vectors -- LDC4 = ldc / 4 where the width is also the row stride, NV = cdiv(classes, 4) where
 // ldc stays a runtime argument -- so here are the one width dispatcher, the one row reader and the one tie rule of the winner.
 #pragma once
@@ -55,6 +55,43 @@ __device__ __forceinline__ int first_max(const f32x4 (&v)[NV], int classes, floa
     }
   best = m;
   return am;
+}
+
+// The winner of one pixel and its confidence, THE definition of pseudo.hip (its header comment states it) and of
+// udaseg_conf_share (distill.hip): one function, so that a histogram, a labelling and a share cannot disagree.
+struct PixelConf {
+  int cls;        // c^
+  float p;        // confidence
+  bool finite;
+};
+
+template <int NV>
+__device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, int classes, int probs) {
+  f32x4 v[NV];
+  load_row<NV>(row, v);
+  float m;
+  PixelConf r;
+  r.cls = first_max<NV>(v, classes, m);
+  if (probs) {
+    bool nan = false;                                      // first_max steps over a NaN beyond channel 0
+#pragma unroll
+    for (int q = 0; q < NV; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) nan |= 4 * q + e < classes && v[q][e] != v[q][e];
+    r.p = m;
+    r.finite = !nan && m >= 0.f && m <= 1.f;
+  } else {
+    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};                       // channel c adds into partial sum c % 4: four short chains
+#pragma unroll
+    for (int q = 0; q < NV; ++q)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (4 * q + e < classes) s4[e] += expf(v[q][e] - m);   // exactly 1 at the maximum, so S >= 1 whenever it is a number
+    const float S = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    r.p = 1.f / S;
+    r.finite = __builtin_isfinite(r.p);
+  }
+  return r;
 }
 
 // The shape of a score buffer whose winner is taken (at most 32 classes: the per-block class tables are that long).

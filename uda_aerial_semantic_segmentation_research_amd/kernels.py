@@ -819,6 +819,35 @@ def entropy_loss(logits_base, pixels, classes, ldc, kind, partials, loss, dlogit
           "entropy_loss")
 
 
+SOFT_CE_KINDS = {"ce": 0, "kl": 1, "symmetric": 2}
+
+
+def soft_ce_fwd_bwd(logits_base, teacher_base, weight_px, weight_img, batch, pix_per_image, classes, ldc, ldt, probs, kind,
+                    teacher_inv_temp, alpha, beta, log_floor, mean, denom, partials, loss, dlogits=None, colsum_partials=None,
+                    colsum=None, stats=None, st=None):
+    """loss = the weighted soft cross entropy ('ce'), KL(teacher || student) ('kl') or symmetric cross entropy ('symmetric') of the
+    student logits [pixels * ldc] against the teacher's logits or probabilities [pixels * ldt]; dlogits / colsum (optional) the
+    gradient for an upstream gradient of 1 and its per-class sums, made in the same pass; stats (optional) int64 [3], accumulated.
+    include/udaseg.h has the arithmetic and the void rule."""
+    check(ops.udaseg_soft_ce_fwd_bwd(logits_base, teacher_base, weight_px, weight_img, batch, pix_per_image, classes, ldc, ldt,
+                                     int(bool(probs)), SOFT_CE_KINDS[kind], float(teacher_inv_temp), float(alpha), float(beta),
+                                     float(log_floor), int(bool(mean)), denom, partials, loss, dlogits, colsum_partials, colsum,
+                                     stats, st), "soft_ce_fwd_bwd")
+
+
+def pixel_weight_sum(weight_px, weight_img, batch, pix_per_image, partials, denom, counts, st=None):
+    """denom [1] f64 = the sum of weight_px[p] * weight_img[image of p] over the pixels whose weight is positive and finite;
+    counts int64 [2] = zero weights, negative or non-finite weights."""
+    check(ops.udaseg_pixel_weight_sum(weight_px, weight_img, batch, pix_per_image, partials, denom, counts, st), "pixel_weight_sum")
+
+
+def conf_share(scores_base, batch, pix_per_image, classes, ldc, probs, tau, above, nonfinite, share, st=None):
+    """Per image: above = pixels whose winner confidence (conf_hist's) is >= tau, nonfinite = its non-finite pixels,
+    share = above / pix_per_image (fp32)."""
+    check(ops.udaseg_conf_share(scores_base, batch, pix_per_image, classes, ldc, int(bool(probs)), float(tau), above, nonfinite,
+                                share, st), "conf_share")
+
+
 def gap_linear_sigmoid_fwd(z, w, b, st=None):
     n, h, wd, c = z.shape
     hw = h * wd

@@ -581,6 +581,138 @@ class EntropyLoss(nn.Module):
         return _EntropyFunction.apply(logits, self.kind)
 
 
+class _SoftCrossEntropyFunction(torch.autograd.Function):
+    """Soft-target loss of student logits against a teacher distribution (csrc/distill.hip), shaped like
+    ``_CrossEntropyOptFunction``: for 'weighted_mean' one launch over the weights alone makes D first; then ONE pass reads both
+    rows and, when the logits need a gradient, writes it already scaled with the head's bias gradient (column sums); backward
+    only scales it if it has to.  A second backward through a retained graph re-runs the entry point."""
+
+    @staticmethod
+    def forward(ctx, logits, tbuf, ldt, probs, wpx, wimg, cfg, stats):
+        n, c, h, w = logits.shape
+        buf, ldc = _padded_nhwc(logits.detach())
+        dev = logits.device
+        denom = None
+        if cfg["reduction"] == 'weighted_mean':
+            denom = torch.empty(1, device=dev, dtype=torch.float64)
+            K.pixel_weight_sum(wpx, wimg, n, h * w, torch.empty(3 * K.seg_partials(), device=dev, dtype=torch.float64), denom,
+                               torch.empty(2, device=dev, dtype=torch.int64))
+        ctx.meta = (n, c, h, w, ldc, ldt, probs, cfg)
+        ctx.save_for_backward(buf, tbuf, wpx, wimg, denom)
+        ctx.fused = None
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        if ctx.needs_input_grad[0]:
+            ctx.fused = _SoftCrossEntropyFunction._run(ctx.meta, buf, tbuf, wpx, wimg, denom, loss, stats, True)
+        else:
+            _SoftCrossEntropyFunction._run(ctx.meta, buf, tbuf, wpx, wimg, denom, loss, stats, False)
+        return loss
+
+    @staticmethod
+    def _run(meta, buf, tbuf, wpx, wimg, denom, loss, stats, grad):
+        n, c, h, w, ldc, ldt, probs, cfg = meta
+        dev = buf.device
+        partials = torch.empty(K.seg_partials(), device=dev, dtype=torch.float64)
+        dl = parts = colsum = None
+        if grad:
+            dl = torch.empty((n, h, w, ldc), device=dev, dtype=torch.float32)
+            parts = torch.empty(K.seg_partials() * ldc, device=dev, dtype=torch.float32)
+            colsum = torch.empty(ldc, device=dev, dtype=torch.float32)
+        K.soft_ce_fwd_bwd(buf, tbuf, wpx, wimg, n, h * w, c, ldc, ldt, probs, cfg["kind"], cfg["inv_temp"], cfg["alpha"], cfg["beta"],
+                          cfg["log_floor"], cfg["reduction"] == 'mean', denom, partials, loss, dl, parts, colsum, stats)
+        return [dl, colsum] if grad else None
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, c, h, w = ctx.meta[:4]
+        g = grad_out.detach().to(torch.float32).contiguous()
+        fused, ctx.fused = ctx.fused, None             # consumed: scaled in place below
+        if fused is None:
+            buf, tbuf, wpx, wimg, denom = ctx.saved_tensors
+            fused = _SoftCrossEntropyFunction._run(ctx.meta, buf, tbuf, wpx, wimg, denom,
+                                                   torch.empty((), device=buf.device, dtype=torch.float32), None, True)
+        dl, colsum = fused
+        K.scale_unless_one(dl, g, colsum)
+        COLSUM_SIDE_TABLE.clear()
+        COLSUM_SIDE_TABLE[dl.data_ptr()] = colsum
+        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 7
+
+
+class SoftCrossEntropyLoss(nn.Module):
+    """A loss between student logits and a teacher DISTRIBUTION, with per-pixel and per-image weights: distillation.
+
+    ``forward(logits [N,C,H,W], teacher [N,C,H,W], probs=False, pixel_weight=None [N,H,W], image_weight=None [N]) -> scalar``,
+    ``2 <= C <= 32``.  The teacher is logits, softened as ``softmax(teacher / teacher_temperature)`` (Hinton et al. 2015; the
+    student is not softened and no ``T^2`` is applied), or with ``probs=True`` probabilities taken as they are (what
+    ``proto.rectify`` and ``predict_large(..., return_probs=True)`` produce).  It never receives a gradient, and a teacher tensor
+    that requires one raises.  With ``q`` the teacher's distribution, ``p`` the student's and ``Q = sum_c q_c``:
+
+    * ``kind='ce'``: ``-sum_c q_c log p_c``;  ``kind='kl'``: ``sum_c q_c (log q_c - log p_c)`` -- the same gradient ``Q p - q``;
+    * ``kind='symmetric'`` (Wang et al., ICCV 2019): ``alpha * ce + beta * sum_c p_c g_c``, ``g_c = -max(log q_c, log_floor)``
+      (the paper's ``A = -4``; ``-log_floor`` where ``q_c == 0``).
+
+    Pixel ``p`` of image ``i`` weighs ``w = pixel_weight[p] * image_weight[i]`` (missing: 1).  A pixel is *void* -- loss and
+    gradient exactly 0 -- when ``w`` is 0, negative or not finite, when its teacher row holds a non-finite value (the NaN rows of
+    ``proto.rectify``), or, with ``probs``, a value outside ``[0, 1]`` or only zeros.  ``reduction``: 'mean' divides the weighted
+    sum by ``N*H*W`` (DACS's and DAFormer's ``mean(q_i * ce_p)``), 'sum' by nothing, 'weighted_mean' by the sum of the weights
+    that do not void their pixel (all void: NaN, as ``CrossEntropyLoss`` over void labels only).  ``last_stats``: device int64
+    ``[counted, void by a zero weight, void otherwise]`` of the last call, written by the loss's own launch: read it when convenient.
+    """
+
+    REDUCTIONS = ('mean', 'sum', 'weighted_mean')
+
+    def __init__(self, kind="ce", teacher_temperature=1.0, alpha=1.0, beta=1.0, log_floor=-4.0, reduction='mean'):
+        super().__init__()
+        import math
+        if kind not in K.SOFT_CE_KINDS:
+            raise ValueError(f"SoftCrossEntropyLoss: kind must be one of {sorted(K.SOFT_CE_KINDS)}, got {kind!r}")
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"SoftCrossEntropyLoss: reduction must be one of {self.REDUCTIONS}, got {reduction!r}")
+        t = float(teacher_temperature)
+        if not (t > 0.0 and math.isfinite(t)):
+            raise ValueError(f"SoftCrossEntropyLoss: teacher_temperature must be positive and finite, got {teacher_temperature}")
+        if not (math.isfinite(float(alpha)) and math.isfinite(float(beta))):
+            raise ValueError(f"SoftCrossEntropyLoss: alpha and beta must be finite, got {alpha} and {beta}")
+        if not (float(log_floor) < 0.0 and math.isfinite(float(log_floor))):
+            raise ValueError(f"SoftCrossEntropyLoss: log_floor must be negative and finite, got {log_floor}")
+        self.kind, self.reduction = kind, reduction
+        self.teacher_temperature, self.alpha, self.beta, self.log_floor = t, float(alpha), float(beta), float(log_floor)
+        self.last_stats = None
+
+    def extra_repr(self):
+        return (f"kind={self.kind!r}, teacher_temperature={self.teacher_temperature}, alpha={self.alpha}, beta={self.beta}, "
+                f"log_floor={self.log_floor}, reduction={self.reduction!r}")
+
+    def forward(self, logits, teacher, probs=False, pixel_weight=None, image_weight=None):
+        _check_prediction("SoftCrossEntropyLoss", logits)
+        n, c, h, w = logits.shape
+        if not torch.is_tensor(teacher) or tuple(teacher.shape) != (n, c, h, w):
+            raise ValueError(f"SoftCrossEntropyLoss: teacher must be a [{n},{c},{h},{w}] tensor like the logits, got "
+                             f"{tuple(getattr(teacher, 'shape', ()))}")
+        if teacher.requires_grad:
+            raise ValueError("SoftCrossEntropyLoss: the teacher never receives a gradient; pass teacher.detach()")
+        for name, t, shape in (("pixel_weight", pixel_weight, (n, h, w)), ("image_weight", image_weight, (n,))):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or not t.is_floating_point():
+                raise ValueError(f"SoftCrossEntropyLoss: {name} must be a floating-point tensor of shape {shape}, got "
+                                 f"{tuple(getattr(t, 'shape', ()))}")
+            if t.requires_grad:
+                raise ValueError(f"SoftCrossEntropyLoss: {name} never receives a gradient; pass {name}.detach()")
+        for name, t in (("teacher", teacher), ("pixel_weight", pixel_weight), ("image_weight", image_weight)):
+            if t is not None and t.device != logits.device:
+                raise RuntimeError(f"SoftCrossEntropyLoss: {name} must live on the logits' GPU (no CPU path in this build)")
+        tbuf, ldt = _padded_nhwc(teacher)
+        dev = logits.device
+        wpx = None if pixel_weight is None else pixel_weight.to(torch.float32).contiguous()
+        wimg = None if image_weight is None else image_weight.to(torch.float32).contiguous()
+        cfg = dict(kind=self.kind, inv_temp=1.0 / self.teacher_temperature, alpha=self.alpha, beta=self.beta,
+                   log_floor=self.log_floor, reduction=self.reduction)
+        stats = torch.zeros(3, device=dev, dtype=torch.int64)
+        out = _SoftCrossEntropyFunction.apply(logits, tbuf, ldt, bool(probs), wpx, wimg, cfg, stats)
+        self.last_stats = stats
+        return out
+
+
 def _check_prediction(who, logits):
     """A prediction the output-space kernels take: on the GPU, [B,C,H,W], 2 <= C <= 32 (log C divides)."""
     if logits.dim() != 4:

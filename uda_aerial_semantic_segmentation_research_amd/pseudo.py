@@ -210,6 +210,25 @@ def pseudo_labels(outputs, thr_bins, void=255, probs=False, return_confidence=Fa
     return (labels, conf) if return_confidence else labels
 
 
+def confidence_share(outputs, tau, probs=False, return_counts=False):
+    """Device fp32 ``[N]``: per image, the share of pixels whose winner confidence (the module docstring's, the one the table is
+    made of) is ``>= tau`` -- the per-image weight ``q_i`` of DACS and DAFormer, made without a host read and exact: integer
+    counters, ``share[i] = float32(float64(above[i]) / (H * W))``.  Non-finite pixels are in no count.  ``outputs``: ``[N,C,H,W]``
+    logits, or probabilities with ``probs``.  With ``return_counts`` also the device int64 ``[N]`` counts ``above`` and ``nonfinite``."""
+    from . import kernels as K
+    if not torch.is_tensor(outputs) or outputs.dim() != 4:
+        raise ValueError(f"confidence_share: scores must be a [N,C,H,W] tensor, got {tuple(getattr(outputs, 'shape', ()))}")
+    tau = float(tau)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError(f"confidence_share: tau must lie in [0, 1], got {tau}")
+    classes = _check_classes(int(outputs.shape[1]))
+    buf, ldc, n, h, w = _scores("confidence_share", outputs, classes)
+    counts = torch.empty((2, n), dtype=torch.int64, device=outputs.device)
+    share = torch.empty(n, dtype=torch.float32, device=outputs.device)
+    K.conf_share(buf, n, h * w, classes, ldc, probs, tau, counts[0], counts[1], share)
+    return (share, counts[0], counts[1]) if return_counts else share
+
+
 class _LabelledLoader:
     """``(frames_u8, masks_u8)`` device batches of a loader of uint8 frames: what ``data.DeviceAugmentedLoader`` wraps."""
 
