@@ -497,6 +497,45 @@ int udaseg_proto_update(double* sums, double* sq, int64_t* counts, int classes, 
  * inv_tau gives the nearest seen prototype's class wherever its p is positive. */
 int udaseg_proto_rectify(const float* feat, int ldf, int dim, const float* scores, int ldc, int classes, int probs,
                          const double* proto, const int32_t* seen, const float* inv_tau, int64_t pixels, float* out, void* stream);
+/* ---- prototype contrast and structure losses (ProDA's structure learning; ProCA, Jiang et al. 2022; SePiCo, Xie et al. 2023): the
+ * prototypes shape the features.  feat, dim, ldf, classes, proto, seen, inv_tau as above (proto is staged once per block as fp32).
+ * Both entry points share ONE row routine, per pixel in fp32:
+ *   d_c = sum_j (f_j - (float)proto[c][j])^2 (udaseg_proto_rectify's four chains, the same bits), d* = min d_c over the seen classes,
+ *   a_c = -(d_c - d*) * inv_tau[0],  S = sum over the seen c of expf(a_c) (four chains, class c in chain c % 4),  L = logf(S),
+ *   s_c = expf(a_c - L) for a seen class, 0 for an unseen one: the pixel's soft assignment to the seen prototypes.
+ * assign: out fp32 [pixels][ldc] (16-byte aligned, classes <= ldc, ldc % 4 == 0) = s; channels classes .. ldc - 1 are written 0; a
+ * row is NaN in every channel < classes when a feature in a channel < dim is not finite (the probs == 1 void convention of
+ * udaseg_pseudo_labels, udaseg_soft_ce_fwd_bwd and udaseg_proto_rectify); while no class is seen s_c = 1 / classes for all
+ * classes (rectify's "u = 1 for all").  One pass, no atomics, the same bits on every run. */
+int udaseg_proto_assign(const float* feat, int ldf, int dim, int classes, int ldc, const double* proto, const int32_t* seen,
+                        const float* inv_tau, int64_t pixels, float* out, void* stream);
+/* The cross entropy of s against a target distribution over the classes, and its gradient with respect to the FEATURES, in one
+ * pass; pixels = batch * pix_per_image.  Exactly one of labels and target is non-NULL:
+ *   labels: uint8 [pixels] (hard):  t_c = [c == labels[p]]
+ *   target: fp32 [pixels][ldt] probabilities, 16-byte aligned, classes <= ldt, ldt % 4 == 0 (soft; udaseg_proto_assign's and
+ *           udaseg_proto_rectify's outputs are read in place):  t_c = target[c] for a seen class, 0 for an unseen one -- the mass on
+ *           unseen classes is dropped
+ *   T = sum_c t_c (four chains);  l = sum_c t_c * (-a_c) + T * L (a lane with t_c == 0 contributes exactly 0), for a hard label
+ *   (d_y - d*) * inv_tau + L;  dl/df_j = 2 * inv_tau * sum_c (T * s_c - t_c) * P_cj, P the staged fp32 prototypes, summed over
+ *   ascending c with fused multiply-adds.  The f_j terms of sum_c (T s_c - t_c)(f_j - P_cj) cancel identically and are not formed.
+ *   The prototypes get no gradient: they are EMA state.
+ * w_p = weight_px[p] * weight_img[p / pix_per_image] (fp32 product; either pointer NULL = 1).  A pixel is VOID -- loss exactly 0,
+ * gradient exactly 0 in all ldf lanes -- for the first of these causes that holds:
+ *   1. w_p is 0, negative or not finite;
+ *   2. hard: the label is >= classes or its class is unseen; soft: a target lane < classes is not finite or outside [0, 1], or T == 0;
+ *   3. a feature in a channel < dim is not finite.
+ * stats (NULL = not wanted): int64 [4], ACCUMULATED with integer atomics: counted pixels, then the pixels void by cause 1, 2, 3.
+ * While no class is seen every pixel falls under cause 1 or 2.  While inv_tau[0] == 0 (or is negative or NaN: no temperature yet)
+ * the pixels are counted as usual and the loss and the gradient of every one of them are exactly 0.
+ * loss, mean, denom, partials: as udaseg_soft_ce_fwd_bwd (sum_p w_p * l_p divided by pixels, by *denom from
+ * udaseg_pixel_weight_sum -- *denom == 0: NaN -- or by 1; udaseg_seg_partials() doubles of scratch; a fixed-order sum without float
+ * atomics: the same bits on every call, with and without dfeat).
+ * dfeat fp32 [pixels][ldf] (NULL = not wanted; 16-byte aligned): the gradient for an upstream gradient of 1, divided like the
+ * loss; lanes dim .. ldf - 1 are written 0. */
+int udaseg_proto_contrast_fwd_bwd(const float* feat, int ldf, int dim, const uint8_t* labels, const float* target, int ldt,
+                                  const float* weight_px, const float* weight_img, int batch, int64_t pix_per_image, int classes,
+                                  const double* proto, const int32_t* seen, const float* inv_tau, int mean, const double* denom,
+                                  double* partials, float* loss, float* dfeat, int64_t* stats, void* stream);
 
 /* ---- cross-domain class mixing of a source and a target batch (DACS, Tranheden et al. 2021; ClassMix, Olsson et al. 2021; an
  * extension, the reference has no counterpart).  Integers only: every output is exact.

@@ -125,6 +125,8 @@ SIGNATURES = {
     "udaseg_proto_accumulate": (_I, [_P, _I, _I, _P, _L, _I, _P, _P, _P, _P]),
     "udaseg_proto_update": (_I, [_P, _P, _P, _I, _I, C.c_double, _L, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
     "udaseg_proto_rectify": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
+    "udaseg_proto_assign": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
+    "udaseg_proto_contrast_fwd_bwd": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "udaseg_classmix_select": (_I, [_P, _I, _I, _L, _P, _P, _P]),
     "udaseg_classmix_u8": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "udaseg_fda_spectrum_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

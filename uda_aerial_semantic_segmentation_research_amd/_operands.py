@@ -345,6 +345,16 @@ OPERANDS = {
     "udaseg_proto_rectify": [T("feat", f32, "pixels*ldf"), I("ldf"), I("dim"), T("scores", f32, "pixels*ldc"), I("ldc"), I("classes"),
                              I("probs"), T("proto", f64, "classes*dim"), T("seen", i32, "classes"), T("inv_tau", f32, 1), I("pixels"),
                              T("out", f32, "pixels*ldc"), S],
+    # ---- prototype contrast (exactly one of labels / target; the library checks that)
+    "udaseg_proto_assign": [T("feat", f32, "pixels*ldf"), I("ldf"), I("dim"), I("classes"), I("ldc"), T("proto", f64, "classes*dim"),
+                            T("seen", i32, "classes"), T("inv_tau", f32, 1), I("pixels"), T("out", f32, "pixels*ldc"), S],
+    "udaseg_proto_contrast_fwd_bwd": [T("feat", f32, "batch*pix_per_image*ldf"), I("ldf"), I("dim"),
+                                      T("labels", u8, "batch*pix_per_image", True), T("target", f32, "batch*pix_per_image*ldt", True),
+                                      I("ldt"), T("weight_px", f32, "batch*pix_per_image", True), T("weight_img", f32, "batch", True),
+                                      I("batch"), I("pix_per_image"), I("classes"), T("proto", f64, "classes*dim"),
+                                      T("seen", i32, "classes"), T("inv_tau", f32, 1), I("mean"), T("denom", f64, 1, True),
+                                      T("partials", f64, "seg_partials()"), T("loss", f32, 1),
+                                      T("dfeat", f32, "batch*pix_per_image*ldf", True), T("stats", i64, 4, True), S],
     "udaseg_classmix_select": [T("hist", i64, "n*256"), I("n"), I("classes"), I("min_pixels"), T("keys", i32, "n*2"), T("sel", i32, "n"), S],
     "udaseg_classmix_u8": [T("src", u8, "n*h*w*3"), T("src_masks", u8, "n*h*w"), T("tgt", u8, "n*h*w*3"),
                            T("tgt_masks", u8, "n*h*w", True), T("sel", i32, "n"), T("boxes", i32, "n*4", True), I("n"), I("h"), I("w"),

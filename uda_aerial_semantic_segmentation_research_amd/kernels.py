@@ -141,6 +141,23 @@ def proto_rectify(feat_base, ldf, dim, scores_base, ldc, classes, probs, proto, 
                                    out, st), "proto_rectify")
 
 
+def proto_assign(feat_base, ldf, dim, classes, ldc, proto, seen, inv_tau, pixels, out, st=None):
+    """out [pixels * ldc] fp32 = the soft assignment of feat [pixels * ldf] to the seen prototypes (softmax of -d / tau over them);
+    NaN rows for non-finite pixels, 1 / classes everywhere while no class is seen."""
+    check(ops.udaseg_proto_assign(feat_base, ldf, dim, classes, ldc, proto, seen, inv_tau, pixels, out, st), "proto_assign")
+
+
+def proto_contrast_fwd_bwd(feat_base, ldf, dim, labels, target_base, ldt, weight_px, weight_img, batch, pix_per_image, classes, proto,
+                           seen, inv_tau, mean, denom, partials, loss, dfeat=None, stats=None, st=None):
+    """loss = the weighted cross entropy of the pixels' prototype assignment against uint8 labels [pixels] or a target distribution
+    [pixels * ldt] (exactly one of them); dfeat (optional) [pixels * ldf] its gradient with respect to the FEATURES for an upstream
+    gradient of 1, made in the same pass; stats (optional) int64 [4], accumulated.  include/udaseg.h has the arithmetic and the
+    void rule."""
+    check(ops.udaseg_proto_contrast_fwd_bwd(feat_base, ldf, dim, labels, target_base, ldt, weight_px, weight_img, batch,
+                                            pix_per_image, classes, proto, seen, inv_tau, int(bool(mean)), denom, partials, loss,
+                                            dfeat, stats, st), "proto_contrast_fwd_bwd")
+
+
 def classmix_select(hist, n, classes, min_pixels, keys, sel, st=None):
     """sel [n] int32 = the class selection of every source mask from its row of the [n,256] int64 mask histogram and its Philox
     key (keys [n,2] int32 bit patterns): half of the present classes, rounded up (mix.py's module docstring has the rule)."""

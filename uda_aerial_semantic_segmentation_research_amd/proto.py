@@ -29,6 +29,13 @@ Deviations from ProDA: the weights are ``exp(-(d - d_min) / tau)`` renormalised 
 distance in the decoder's 16 channels, not in a 256-channel ASPP output; the prototypes follow the RAW winner of the current
 teacher in one streaming EMA per batch (ProDA's initialisation rule applied online) and there is no second-stage distillation.
 
+The prototypes also SHAPE the features (ProDA's target structure learning; ProCA, SePiCo: csrc/proto_contrast.hip, INTEGRATION.md
+"Prototype contrast and structure learning"): ``assign`` is a pixel's soft assignment to the seen prototypes, the softmax of
+``-(d_c - d*) * inv_tau`` over them (``udaseg_proto_assign``; ``assign_mirror``), and ``PrototypeContrastLoss`` the cross entropy of
+that assignment against a label mask or another distribution, differentiated with respect to the FEATURES in the same pass
+(``udaseg_proto_contrast_fwd_bwd``; ``contrast_mirror``); the prototypes receive no gradient.  ``structure.StructureTrainer`` trains
+with both.
+
 Use, in place of ``teacher.OnlineLabeler`` in the mean-teacher recipe::
 
     labeler = proto.PrototypeLabeler(mt, num_classes=23, portion=0.2, cap=0.9, halve_every=100, rectify_after=200)
@@ -163,6 +170,99 @@ def rectify_mirror(features, scores, proto, seen, inv_tau, probs=False):
         out = r / R
     out[bad] = np.nan
     return out
+
+
+def _mirror_operands(features, proto, seen):
+    f = np.asarray(features, dtype=np.float64)
+    pr = np.asarray(proto, dtype=np.float64).astype(np.float32).astype(np.float64)
+    seen = np.asarray(seen).astype(bool)
+    if f.ndim != 2 or pr.ndim != 2 or pr.shape[1] != f.shape[1]:
+        raise ValueError(f"features [P, D], proto [C, D] expected, got {f.shape}, {pr.shape}")
+    if seen.shape != (pr.shape[0],):
+        raise ValueError(f"seen must be [{pr.shape[0]}], got {seen.shape}")
+    return f, pr, seen
+
+
+def _assignment(f, pr, seen, it):
+    """(a [P, C], L [P], s [P, C]) of the contract over the seen classes (at least one); unseen columns: a = 0, s = 0."""
+    d = ((f[:, None, :] - pr[None, :, :]) ** 2).sum(axis=2)
+    dmin = d[:, seen].min(axis=1, keepdims=True)
+    a = np.where(seen[None, :], -(d - dmin) * it, 0.0)
+    L = np.log(np.where(seen[None, :], np.exp(a), 0.0).sum(axis=1))
+    return a, L, np.where(seen[None, :], np.exp(a - L[:, None]), 0.0)
+
+
+def assign_mirror(features, proto, seen, inv_tau):
+    """``udaseg_proto_assign``'s contract in numpy float64: the softmax of ``-(d_c - d*) * inv_tau`` over the seen classes, 0 for
+    an unseen one, ``1 / C`` everywhere while none is seen, NaN rows for non-finite features.  ``features [P, D]``, ``proto
+    [C, D]`` (rounded to float32 first, as the kernel stages it), ``seen [C]``.  Returns ``[P, C]`` float64.  Needs no GPU."""
+    f, pr, seen = _mirror_operands(features, proto, seen)
+    with np.errstate(all="ignore"):
+        if seen.any():
+            out = _assignment(f, pr, seen, np.float64(inv_tau))[2]
+        else:
+            out = np.full((f.shape[0], pr.shape[0]), 1.0 / pr.shape[0])
+        out[~np.isfinite(f).all(axis=1)] = np.nan
+    return out
+
+
+CONTRAST_REDUCTIONS = ("mean", "sum", "weighted_mean")
+
+
+def contrast_mirror(features, target, proto, seen, inv_tau, pixel_weight=None, image_weight=None, batch=1, reduction="mean"):
+    """``udaseg_proto_contrast_fwd_bwd``'s contract in numpy float64.  ``features [P, D]``; ``target``: an integer ``[P]`` array
+    (hard labels) or a float ``[P, C]`` array (a distribution per pixel); ``proto [C, D]`` (rounded to float32 first), ``seen
+    [C]``; ``pixel_weight [P]``, ``image_weight [batch]`` (``P = batch * pixels per image``; their product is taken in float32, the
+    number the kernel tests).  Returns ``(loss, grad [P, D], stats int64 [4], why [P])``: ``why`` 0 = the pixel counts, 1 = void
+    by its weight, 2 = by its label or target, 3 = by a non-finite feature; ``stats`` counts them.  Needs no GPU."""
+    if reduction not in CONTRAST_REDUCTIONS:
+        raise ValueError(f"reduction must be one of {CONTRAST_REDUCTIONS}, got {reduction!r}")
+    f, pr, seen = _mirror_operands(features, proto, seen)
+    P, C = f.shape[0], pr.shape[0]
+    if not isinstance(batch, (int, np.integer)) or batch < 1 or P % batch:
+        raise ValueError(f"batch must divide the {P} pixels, got {batch}")
+    it = np.float64(inv_tau)
+    w = np.ones(P, dtype=np.float32) if pixel_weight is None else np.asarray(pixel_weight, dtype=np.float32).reshape(-1).copy()
+    if w.shape != (P,):
+        raise ValueError(f"pixel_weight must have {P} elements, got {w.shape}")
+    if image_weight is not None:
+        wi = np.asarray(image_weight, dtype=np.float32)
+        if wi.shape != (batch,):
+            raise ValueError(f"image_weight must be [{batch}], got {wi.shape}")
+        with np.errstate(all="ignore"):
+            w = (w * np.repeat(wi, P // batch)).astype(np.float32)
+    tg = np.asarray(target)
+    hard = tg.ndim == 1
+    if (hard and (tg.shape != (P,) or tg.dtype.kind not in "iu")) or (not hard and tg.shape != (P, C)):
+        raise ValueError(f"target must be an integer [{P}] or a float [{P}, {C}] array, got {tg.dtype} {tg.shape}")
+    with np.errstate(all="ignore"):
+        w_ok = (w > 0) & np.isfinite(w)
+        if hard:
+            inr = (tg >= 0) & (tg < C)
+            t = np.zeros((P, C))
+            t[np.nonzero(inr)[0], tg[inr]] = 1.0
+            t_ok = inr & seen[np.where(inr, tg, 0)]
+        else:
+            t32 = tg.astype(np.float32)
+            t_ok = ((t32 >= 0) & (t32 <= 1)).all(axis=1)
+            t = np.where(seen[None, :] & t_ok[:, None], t32.astype(np.float64), 0.0)    # the mass on unseen classes is dropped
+            t_ok &= t.sum(axis=1) > 0
+        why = np.where(~w_ok, 1, np.where(~t_ok, 2, np.where(~np.isfinite(f).all(axis=1), 3, 0)))
+        stats = np.array([(why == k).sum() for k in range(4)], dtype=np.int64)
+        div = {"mean": float(P), "sum": 1.0}.get(reduction)
+        if div is None:
+            div = float(w[w_ok].astype(np.float64).sum())
+        grad = np.zeros_like(f)
+        live = np.nonzero(why == 0)[0]
+        if not (it > 0) or not seen.any() or not len(live):
+            return (0.0 if div else float("nan")), grad, stats, why
+        a, L, s = _assignment(f[live], pr, seen, it)
+        tl, wl = t[live], w[live].astype(np.float64)
+        T = tl.sum(axis=1)
+        l = (tl * -a).sum(axis=1) + T * L
+        loss = (wl * l).sum() / div if div else float("nan")
+        grad[live] = (2.0 * it * wl / div)[:, None] * ((T[:, None] * s - tl) @ pr) if div else 0.0
+    return float(loss), grad, stats, why
 
 
 # ------------------------------------------------------------------------------------------------------------ device side
@@ -318,6 +418,142 @@ def rectify(features, outputs, bank, probs=False):
     out = torch.empty((n, h, w, ldc), dtype=torch.float32, device=features.device)
     K.proto_rectify(fbuf, ldf, bank.dim, sbuf, ldc, C, probs, bank.prototypes, bank.seen, bank.inv_tau, n * h * w, out)
     return out.permute(0, 3, 1, 2)[:, :C]
+
+
+def assign(features, bank):
+    """``[N,C,H,W]`` soft assignment of ``[N,D,H,W]`` features to ``bank``'s seen prototypes: the softmax of ``-d / tau`` over
+    them, a distribution per pixel (``assign_mirror`` states it; a strided view of a padded NHWC buffer, which
+    ``PrototypeContrastLoss`` and ``SoftCrossEntropyLoss(probs=True)`` read in place).  NaN rows mark pixels with a non-finite
+    feature.  One kernel, no host sync, no gradient."""
+    from . import kernels as K
+    if not isinstance(bank, PrototypeBank):
+        raise ValueError(f"assign: bank must be a PrototypeBank, got {type(bank).__name__}")
+    C = bank.num_classes
+    fbuf, ldf, n, h, w = _nhwc("assign", "features", features, bank.dim)
+    bank._ensure(features.device)
+    ldc = (C + 3) // 4 * 4
+    out = torch.empty((n, h, w, ldc), dtype=torch.float32, device=features.device)
+    K.proto_assign(fbuf, ldf, bank.dim, C, ldc, bank.prototypes, bank.seen, bank.inv_tau, n * h * w, out)
+    return out.permute(0, 3, 1, 2)[:, :C]
+
+
+class _PrototypeContrastFunction(torch.autograd.Function):
+    """``losses._SoftCrossEntropyFunction``'s shape on the features: for 'weighted_mean' one launch over the weights alone makes
+    D; then ONE pass makes the loss and, when the features need a gradient, the gradient already scaled; backward only scales it
+    if it has to.  A second backward through a retained graph re-runs the entry point."""
+
+    @staticmethod
+    def forward(ctx, features, fbuf, ldf, labels, tbuf, ldt, wpx, wimg, bank, reduction, stats, want_grad):
+        from . import kernels as K
+        n, d, h, w = features.shape
+        dev = features.device
+        denom = None
+        if reduction == "weighted_mean":
+            denom = torch.empty(1, device=dev, dtype=torch.float64)
+            K.pixel_weight_sum(wpx, wimg, n, h * w, torch.empty(3 * K.seg_partials(), device=dev, dtype=torch.float64), denom,
+                               torch.empty(2, device=dev, dtype=torch.int64))
+        ctx.meta = (n, d, h, w, ldf, ldt, bank, reduction)
+        ctx.save_for_backward(fbuf, labels, tbuf, wpx, wimg, denom)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        # want_grad: whether a graph is being recorded at all (inside forward grad mode is always off, and under no_grad
+        # needs_input_grad still names a leaf that requires one)
+        ctx.dfeat = _PrototypeContrastFunction._run(ctx.meta, fbuf, labels, tbuf, wpx, wimg, denom, loss, stats,
+                                                    want_grad and ctx.needs_input_grad[0])
+        return loss
+
+    @staticmethod
+    def _run(meta, fbuf, labels, tbuf, wpx, wimg, denom, loss, stats, grad):
+        from . import kernels as K
+        n, d, h, w, ldf, ldt, bank, reduction = meta
+        dev = fbuf.device
+        dfeat = torch.empty((n, h, w, ldf), device=dev, dtype=torch.float32) if grad else None
+        K.proto_contrast_fwd_bwd(fbuf, ldf, d, labels, tbuf, ldt, wpx, wimg, n, h * w, bank.num_classes, bank.prototypes, bank.seen,
+                                 bank.inv_tau, reduction == "mean", denom, torch.empty(K.seg_partials(), device=dev, dtype=torch.float64),
+                                 loss, dfeat, stats)
+        return dfeat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import kernels as K
+        n, d, h, w = ctx.meta[:4]
+        g = grad_out.detach().to(torch.float32).contiguous()
+        dfeat, ctx.dfeat = ctx.dfeat, None                 # consumed: scaled in place below
+        if dfeat is None:
+            fbuf, labels, tbuf, wpx, wimg, denom = ctx.saved_tensors
+            dfeat = _PrototypeContrastFunction._run(ctx.meta, fbuf, labels, tbuf, wpx, wimg, denom,
+                                                    torch.empty((), device=fbuf.device, dtype=torch.float32), None, True)
+        K.scale_unless_one(dfeat, g)
+        return (dfeat.permute(0, 3, 1, 2)[:, :d],) + (None,) * 11
+
+
+class PrototypeContrastLoss(torch.nn.Module):
+    """Cross entropy between a pixel's soft assignment to ``bank``'s prototypes and a target over the classes, as a loss on the
+    FEATURES: it pulls a feature toward the prototypes its target names and away from the others (module docstring,
+    ``contrast_mirror`` states the arithmetic).  The prototypes receive no gradient: they are EMA state.
+
+    ``forward(features [N,D,H,W], target, pixel_weight=None [N,H,W], image_weight=None [N]) -> scalar``.  ``features``: fp32 or
+    bf16, as ``forward_parts(x, ("logits", "decoder"))`` yields them (read in place).  ``target``: a uint8 ``[N,H,W]`` mask (other
+    integer masks are clamped to 0..255) -- ProCA's pixel-to-prototype contrast on labelled pixels -- or a float ``[N,C,H,W]``
+    distribution (``assign``'s and ``rectify``'s outputs are read in place) -- ProDA's consistency between two views' assignments.
+    A pixel is *void* -- loss and gradient exactly 0 -- when its weight is 0, negative or not finite; when its label is beyond the
+    classes or names an unseen class; when its target row holds a value that is not finite or outside ``[0, 1]`` or has no mass on
+    a seen class; when one of its features is not finite.  While the bank has seen no class or has no temperature yet the loss
+    is 0.  ``reduction`` as ``SoftCrossEntropyLoss``.  ``last_stats``: device int64 ``[counted, void by weight, void by label or
+    target, void by a non-finite feature]`` of the last call: read it when convenient."""
+
+    REDUCTIONS = CONTRAST_REDUCTIONS
+
+    def __init__(self, bank, reduction="mean"):
+        super().__init__()
+        if not isinstance(bank, PrototypeBank):
+            raise ValueError(f"PrototypeContrastLoss: bank must be a PrototypeBank, got {type(bank).__name__}")
+        if reduction not in self.REDUCTIONS:
+            raise ValueError(f"PrototypeContrastLoss: reduction must be one of {self.REDUCTIONS}, got {reduction!r}")
+        self.bank, self.reduction = bank, reduction
+        self.last_stats = None
+
+    def extra_repr(self):
+        return f"classes={self.bank.num_classes}, dim={self.bank.dim}, reduction={self.reduction!r}"
+
+    def forward(self, features, target, pixel_weight=None, image_weight=None):
+        who = "PrototypeContrastLoss"
+        C = self.bank.num_classes
+        fbuf, ldf, n, h, w = _nhwc(who, "features", features, self.bank.dim)
+        dev = features.device
+        if not torch.is_tensor(target):
+            raise ValueError(f"{who}: target must be a [{n},{h},{w}] integer mask or a [{n},{C},{h},{w}] float distribution, got "
+                             f"{type(target).__name__}")
+        if target.requires_grad:
+            raise ValueError(f"{who}: the target never receives a gradient; pass target.detach()")
+        for name, t, shape in (("pixel_weight", pixel_weight, (n, h, w)), ("image_weight", image_weight, (n,))):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or not t.is_floating_point():
+                raise ValueError(f"{who}: {name} must be a floating-point tensor of shape {shape}, got "
+                                 f"{tuple(getattr(t, 'shape', ()))}")
+            if t.requires_grad:
+                raise ValueError(f"{who}: {name} never receives a gradient; pass {name}.detach()")
+        for name, t in (("target", target), ("pixel_weight", pixel_weight), ("image_weight", image_weight)):
+            if t is not None and t.device != dev:
+                raise RuntimeError(f"{who}: {name} must live on the features' GPU (no CPU path in this build)")
+        labels = tbuf = None
+        ldt = 0
+        if target.is_floating_point():
+            if tuple(target.shape) != (n, C, h, w):
+                raise ValueError(f"{who}: a soft target must be a [{n},{C},{h},{w}] tensor, got {tuple(target.shape)}")
+            tbuf, ldt, _, _, _ = _nhwc(who, "target", target, C)
+        else:
+            if tuple(target.shape) != (n, h, w) or target.dtype == torch.bool:
+                raise ValueError(f"{who}: a hard target must be a [{n},{h},{w}] integer mask, got {target.dtype} {tuple(target.shape)}")
+            labels = (target if target.dtype == torch.uint8 else target.clamp(0, 255).to(torch.uint8)).contiguous()
+        self.bank._ensure(dev)
+        wpx = None if pixel_weight is None else pixel_weight.to(torch.float32).contiguous()
+        wimg = None if image_weight is None else image_weight.to(torch.float32).contiguous()
+        stats = torch.zeros(4, device=dev, dtype=torch.int64)
+        out = _PrototypeContrastFunction.apply(features, fbuf, ldf, labels, tbuf, ldt, wpx, wimg, self.bank, self.reduction, stats,
+                                               torch.is_grad_enabled())
+        self.last_stats = stats
+        return out
 
 
 def domain_gap(bank_a, bank_b):
