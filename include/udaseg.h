@@ -620,6 +620,44 @@ int udaseg_render_u8(const void* labels, const void* truth, int labels_i64, cons
                      int n, int h, int w, int classes, int has_ignore, int ignore_index, const int32_t* alpha, const float* denorm,
                      int outline, uint8_t* out, int64_t* counts, int64_t* agreement, void* stream);
 
+/* ---- label boundary distances: band erosion, boundary weight maps, Boundary IoU / trimap counters (csrc/boundary.hip;
+ * tests/_boundary_ref.py is the numpy mirror, every product is integers or a table lookup and is bit for bit).  A label map is n
+ * images [h][w], contiguous: uint8 (labels_i64 == 0) or int64 (== 1; 8-byte aligned; a value outside [0, 255] reads as 255).
+ * With has_ignore == 1 the pixels whose value (after that rule) equals ignore_index, in [0, 255], are VOID; with has_ignore == 0
+ * no pixel is void and ignore_index is only range-checked.
+ *   boundary pixel  p is a boundary pixel if some 4-neighbour q INSIDE the same image has L(q) != L(p) and neither p nor q is void.
+ *                   The frame's edge is no boundary (the rule of udaseg_render_u8's outline); images never see each other.
+ *   D2(p)           the minimum over the boundary pixels b of the same image of (py - by)^2 + (px - bx)^2
+ *   d2(p)           D2(p) if D2(p) <= radius^2, else radius^2 + 1 ("far"; also when the image has no boundary pixel).  A boundary
+ *                   pixel has d2 = 0; a void pixel has a d2 like any other.  0 <= radius <= 32.
+ * The cap makes the two-pass form exact: g(y, x) = the smallest |dy| <= radius with (y + dy, x) a boundary pixel, else
+ * radius + 1; D2(y, x) = min over |dx| <= radius with g(y, x + dx) <= radius of dx^2 + g(y, x + dx)^2.
+ * Limits of every entry point, refused with a message before any launch: 0 < n <= 65535, h, w >= 1, h * w < 2^31,
+ * 0 <= radius <= 32, ignore_index (and void_label) in [0, 255], 1 <= classes <= 255. */
+/* (tile height << 16) | tile width of the launch at this radius: the counters' (stats != 0) or the other three products'. */
+int udaseg_boundary_tile(int radius, int stats);
+/* d2: int32 [n][h][w] = d2(p). */
+int udaseg_boundary_d2(const void* labels, int labels_i64, int n, int h, int w, int radius, int has_ignore, int ignore_index,
+                       int32_t* d2, void* stream);
+/* out: float32 [n][h][w] = table[slot(p)]; table: DEVICE float32 [radius^2 + 3]; slot(p) = d2(p) (0 .. radius^2 + 1) for a pixel
+ * that is not void, radius^2 + 2 for a void pixel.  The table's bits are copied, nothing is computed. */
+int udaseg_boundary_lookup(const void* labels, int labels_i64, int n, int h, int w, int radius, int has_ignore, int ignore_index,
+                           const float* table, float* out, void* stream);
+/* out: uint8 [n][h][w] = void_label where p is not void and d2(p) <= radius^2, else L(p) (a void pixel keeps ignore_index).
+ * counts (NULL or int64 [n][2], ACCUMULATES): counts[i] += {pixels of image i this call set to void_label, pixels of image i that
+ * were void already}. */
+int udaseg_boundary_erode(const void* labels, int labels_i64, int n, int h, int w, int radius, int has_ignore, int ignore_index,
+                          int void_label, uint8_t* out, int64_t* counts, void* stream);
+/* Band counters of two maps of one dtype and shape.  truth's void pixels are as above; a pixel of pred is void where pred equals
+ * ignore_index OR truth is void there (has_ignore == 1).  The inner band of class c in a map M is {p : M(p) = c, p not void in M,
+ * d2_M(p) <= radius^2}, d2_M taken of M with M's void pixels.
+ *   stats  (int64 [classes][3], ACCUMULATES): stats[c] += {|band_T(c)|, |band_P(c)|, |band_T(c) n band_P(c)|}
+ *   trimap (int64 [2], ACCUMULATES): += {pixels not void in truth with d2_T <= radius^2, those among them with pred == truth
+ *          (pred not void)}
+ * A label >= classes that is not void counts in no band of stats; it makes boundaries like any label and counts in trimap. */
+int udaseg_boundary_stats(const void* pred, const void* truth, int labels_i64, int n, int h, int w, int radius, int classes,
+                          int has_ignore, int ignore_index, int64_t* stats, int64_t* trimap, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

@@ -134,6 +134,11 @@ SIGNATURES = {
     "udaseg_fda_delta": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "udaseg_fda_apply_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "udaseg_render_u8": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "udaseg_boundary_tile": (_I, [_I, _I]),
+    "udaseg_boundary_d2": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_boundary_lookup": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_boundary_erode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_boundary_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

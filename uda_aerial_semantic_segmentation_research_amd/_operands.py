@@ -50,6 +50,7 @@ def T(name, dtype, count, opt=False):
 _HALF = "n*(hi//2)*(wi//2)"          # pixels of the half-resolution source of a fused decoder input
 _ACT_BF = "(f32 if out_f32 else bf16)"
 _BIL = "(bf16 if bf16_ else f32)"
+_LAB = "(i64 if labels_i64 else u8)"
 
 OPERANDS = {
     # ---- library state / queries (no device pointers)
@@ -376,6 +377,17 @@ OPERANDS = {
                          T("table", u8, 768), I("n"), I("h"), I("w"), I("classes"), I("has_ignore"), I("ignore_index"), H("alpha"),
                          H("denorm"), I("outline"), T("out", u8, "n*h*w*3"), T("counts", i64, "n*256", True),
                          T("agreement", i64, "n*3", True), S],
+    # ---- label boundary distances (radius R: the table has R*R + 3 slots)
+    "udaseg_boundary_tile": [I("radius"), I("stats")],
+    "udaseg_boundary_d2": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("radius"), I("has_ignore"),
+                           I("ignore_index"), T("d2", i32, "n*h*w"), S],
+    "udaseg_boundary_lookup": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("radius"), I("has_ignore"),
+                               I("ignore_index"), T("table", f32, "radius*radius+3"), T("out", f32, "n*h*w"), S],
+    "udaseg_boundary_erode": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("radius"), I("has_ignore"),
+                              I("ignore_index"), I("void_label"), T("out", u8, "n*h*w"), T("counts", i64, "n*2", True), S],
+    "udaseg_boundary_stats": [T("pred", _LAB, "n*h*w"), T("truth", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"),
+                              I("radius"), I("classes"), I("has_ignore"), I("ignore_index"), T("stats", i64, "classes*3"),
+                              T("trimap", i64, 2), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

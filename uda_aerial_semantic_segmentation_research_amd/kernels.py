@@ -218,6 +218,43 @@ def render_u8(labels, truth, base, table, n, h, w, classes, ignore_index, alpha,
                                counts, agreement, st), "render_u8")
 
 
+# ---- label boundary distances (boundary.py; csrc/boundary.hip).  labels: uint8 or int64 [n,h,w]; ignore_index: an int or None
+def _boundary_head(labels, radius, ignore_index):
+    n, h, w = labels.shape
+    return (int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(radius), int(ignore_index is not None),
+            0 if ignore_index is None else int(ignore_index))
+
+
+def boundary_tile(radius, stats=False):
+    """(tile height, tile width) of the launch at this radius."""
+    v = _lib.load().udaseg_boundary_tile(int(radius), int(bool(stats)))
+    if v < 0:
+        check(v, "boundary_tile")
+    return v >> 16, v & 0xffff
+
+
+def boundary_d2(labels, radius, ignore_index, d2, st=None):
+    """d2 [n,h,w] int32 = the capped squared distance to the nearest label boundary (radius * radius + 1: further than radius)."""
+    check(ops.udaseg_boundary_d2(labels, *_boundary_head(labels, radius, ignore_index), d2, st), "boundary_d2")
+
+
+def boundary_lookup(labels, radius, ignore_index, table, out, st=None):
+    """out [n,h,w] fp32 = table[d2] (table [radius * radius + 3] fp32 on the device; the last slot is the void pixels')."""
+    check(ops.udaseg_boundary_lookup(labels, *_boundary_head(labels, radius, ignore_index), table, out, st), "boundary_lookup")
+
+
+def boundary_erode(labels, radius, ignore_index, void_label, out, counts, st=None):
+    """out [n,h,w] uint8 = labels with void_label within radius of a boundary; counts [n,2] int64 or None += voided, void before."""
+    check(ops.udaseg_boundary_erode(labels, *_boundary_head(labels, radius, ignore_index), int(void_label), out, counts, st),
+          "boundary_erode")
+
+
+def boundary_stats(pred, truth, radius, classes, ignore_index, stats, trimap, st=None):
+    """stats [classes,3] / trimap [2] int64 += the band counters of pred against truth (one dtype, one shape)."""
+    i64, n, h, w, r, has, ign = _boundary_head(truth, radius, ignore_index)
+    check(ops.udaseg_boundary_stats(pred, truth, i64, n, h, w, r, int(classes), has, ign, stats, trimap, st), "boundary_stats")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,
