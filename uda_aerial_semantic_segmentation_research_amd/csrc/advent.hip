@@ -4,8 +4,8 @@
 // Logits are NHWC rows [pixel][ldc] with `classes` valid channels (ldc % 4 == 0, ldc <= 32), as produced by Unet; the maps are
 // rows [pixel][cpad] of fp32 or bf16 that a convolution reads in place, so their pad lanes are written as zeros.
 // One thread per pixel, softmax row in registers, wave/block reductions, f64 cross-block partials and a finish kernel: the
-// pattern of losses_seg.hip.
-#include "scores_common.h"
+// pattern of losses_seg.hip, with loss_reduce.h's block partial and finish.
+#include "loss_reduce.h"
 
 namespace udaseg {
 
@@ -183,18 +183,7 @@ __global__ __launch_bounds__(256) void entropy_loss_kernel(const f32x4* __restri
       }
     }
   }
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// loss = (sum of the n block partials, in a fixed order) / divisor
-__global__ void entropy_finish_kernel(const double* __restrict__ partials, int n, double divisor, float* __restrict__ loss) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) *loss = (float)(s / divisor);
+  block_partial(local, red, partials);
 }
 
 // Shared argument rules: the score buffer's shape, log C divides, and the map rows a convolution reads in place.
@@ -267,8 +256,6 @@ extern "C" int udaseg_entropy_loss(const float* logits, int64_t pixels, int clas
       }))
     return unsupported_width("entropy_loss", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("entropy_loss launch");
-  hipLaunchKernelGGL(entropy_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, kind == 0 ? (double)pixels : -2.0 * (double)pixels,
-                     loss);
-  UDASEG_LAUNCH_CHECK("entropy_finish launch");
-  return UDASEG_OK;
+  return launch_loss_finish(partials, grid, kind == 0 ? (double)pixels : -2.0 * (double)pixels, nullptr, loss, 0, st,
+                            "entropy_finish launch");
 }

@@ -2,7 +2,8 @@
 // 2015; symmetric cross entropy, Wang et al., ICCV 2019, the loss ProDA's later stages train with; the per-image weight is
 // DACS's / DAFormer's share of confident pixels).  fp32, HBM-bound, the family of losses.hip / losses_seg.hip / advent.hip:
 // one thread per pixel row, both rows in registers, loss and gradient in ONE pass over the logits (ce_fwd_bwd_kernel's LDS tile:
-// whole contiguous lines out, column sums on the way), fixed-order f64 block partials, integer atomics for the counters only.
+// whole contiguous lines out, column sums on the way), loss_reduce.h's fixed-order f64 block partials and finish kernels, integer
+// atomics for the counters only.
 //
 //   student z: [pixels][ldc], teacher t: [pixels][ldt]; only lanes < classes are read.   lp = log_softmax(z), p = exp(lp)
 //   probs == 0:  q = softmax(t * teacher_inv_temp), lq = log_softmax(t * teacher_inv_temp)        probs == 1:  q = t, lq = logf(q)
@@ -19,7 +20,7 @@
 //   gradient of 1, i.e. already carries w_p / D.
 #include <float.h>
 
-#include "scores_common.h"
+#include "loss_reduce.h"
 
 namespace udaseg {
 
@@ -74,6 +75,9 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const f32x4* __restrict__ 
                                                       f32x4* __restrict__ dlogits, float* __restrict__ colpart,
                                                       unsigned long long* __restrict__ stats) {
 #pragma clang fp contract(off)
+  // The LDS tile is GradTile's (loss_reduce.h), written out: this kernel takes the barriers only when `grad` and stores only when
+  // `dlogits`, and it sits at a cliff of the register allocator -- through the helper <6, true> took 176 VGPRs for 145 and the
+  // symmetric loss of 8 x 512 x 512 pixels 0.257 ms for 0.233 (profiles/loss_reduce_refactor.txt).  Same map, same order.
   constexpr int LDC = LDC4 * 4;
   constexpr int NG = 256 / LDC;
   __shared__ __attribute__((aligned(16))) float tile[256 * LDC];
@@ -190,9 +194,8 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const f32x4* __restrict__ 
       __syncthreads();
     }
   }
-  local = wave_sum_d(local);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
   if (colpart && rg < NG) colred[rg * LDC + cc] = colacc;
+  block_partial(local, red, partials);   // its barrier is the column sums' too
   if (stats) {
 #pragma unroll
     for (int k = 0; k < DS_STATS; ++k) {
@@ -200,36 +203,11 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const f32x4* __restrict__ 
       if ((tid & 63) == 0 && n) atomicAdd(&stats[k], (unsigned long long)n);
     }
   }
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
   if (colpart && tid < LDC) {
     float s = 0.f;
     for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
     colpart[(size_t)blockIdx.x * LDC + tid] = s;
   }
-}
-
-// loss = (sum of the n block partials, in a fixed order) / D;  D == 0 under a device denominator (every weight void): NaN, the
-// 0 / 0 of a weighted mean, as ce_opt_finish_kernel.  single wave
-__global__ void soft_ce_finish_kernel(const double* __restrict__ partials, int n, double pixels, int mean,
-                                      const double* __restrict__ denom, float* __restrict__ loss) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) *loss = mean ? (float)(s / pixels) : (denom ? (*denom == 0.0 ? NAN : (float)(s / *denom)) : (float)s);
-}
-
-// column sums of the block partials: losses.hip's colsum_finish_kernel (one 256-thread block per column, fixed-order tree)
-__global__ __launch_bounds__(256) void soft_colsum_finish_kernel(const float* __restrict__ colpart, int nblocks, int ldc,
-                                                                 float* __restrict__ colsum) {
-  __shared__ float red[4];
-  const int c = blockIdx.x;
-  float s = 0.f;
-  for (int b = threadIdx.x; b < nblocks; b += 256) s += colpart[(size_t)b * ldc + c];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) colsum[c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // partials[k][block], k = 0: sum of w_p over the pixels whose weight counts (f64), 1: zero weights, 2: negative / non-finite
@@ -249,33 +227,7 @@ __global__ __launch_bounds__(256) void pixel_weight_sum_kernel(const float* __re
     nbad += why == 2;
   }
   double v[3] = {d, (double)nz, (double)nbad};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    v[k] = wave_sum_d(v[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    partials[(size_t)k * gridDim.x + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-  }
-}
-
-// single wave: denom = D, counts = [n_zero, n_invalid]
-__global__ void pixel_weight_sum_finish_kernel(const double* __restrict__ partials, int n, double* __restrict__ denom,
-                                               int64_t* __restrict__ counts) {
-  double s[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) a += partials[(size_t)k * n + i];
-    s[k] = wave_sum_d(a);
-  }
-  if (threadIdx.x == 0) {
-    *denom = s[0];
-    counts[0] = (int64_t)s[1];
-    counts[1] = (int64_t)s[2];
-  }
+  block_partial_rows<3>(v, red, partials);
 }
 
 // above[i] += pixels of image i (blockIdx.y) whose winner confidence (pixel_conf: udaseg_conf_hist's) is >= tau, nonfinite[i] +=
@@ -310,12 +262,6 @@ __global__ __launch_bounds__(256) void conf_share_kernel(const float* __restrict
 __global__ void conf_share_finish_kernel(const unsigned long long* __restrict__ above, int batch, double ppi, float* __restrict__ share) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < batch) share[i] = (float)((double)above[i] / ppi);
-}
-
-static bool image_grid_ok(const char* who, int batch, int64_t ppi) {
-  if (batch > 0 && ppi > 0 && ppi <= INT64_MAX / batch) return true;
-  set_error("%s: need batch > 0, pix_per_image > 0 (batch=%d pix_per_image=%lld)", who, batch, (long long)ppi);
-  return false;
 }
 
 }  // namespace udaseg
@@ -357,13 +303,9 @@ extern "C" int udaseg_soft_ce_fwd_bwd(const float* logits, const float* teacher,
       }))
     return unsupported_width("soft_ce_fwd_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("soft_ce launch");
-  hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, (double)pixels, mean, denom, loss);
-  UDASEG_LAUNCH_CHECK("soft_ce_finish launch");
-  if (colsum) {
-    hipLaunchKernelGGL(soft_colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum);
-    UDASEG_LAUNCH_CHECK("soft_colsum_finish launch");
-  }
-  return UDASEG_OK;
+  // mean and denom exclude each other (above): D = pixels, *denom or 1
+  const int rc = launch_loss_finish(partials, grid, mean ? (double)pixels : 1.0, denom, loss, 0, st, "soft_ce_finish launch");
+  return rc || !colsum ? rc : launch_colsum_finish(colsum_partials, grid, ldc, colsum, 0, st, "soft_colsum_finish launch");
 }
 
 extern "C" int udaseg_pixel_weight_sum(const float* weight_px, const float* weight_img, int batch, int64_t pix_per_image,
@@ -375,9 +317,7 @@ extern "C" int udaseg_pixel_weight_sum(const float* weight_px, const float* weig
   const int grid = capped_grid(pixels, 256, udaseg_seg_partials());
   hipLaunchKernelGGL(pixel_weight_sum_kernel, dim3(grid), dim3(256), 0, st, weight_px, weight_img, pixels, pix_per_image, partials);
   UDASEG_LAUNCH_CHECK("pixel_weight_sum launch");
-  hipLaunchKernelGGL(pixel_weight_sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, denom, counts);
-  UDASEG_LAUNCH_CHECK("pixel_weight_sum_finish launch");
-  return UDASEG_OK;
+  return launch_rows_finish(3, partials, grid, denom, counts, st, "pixel_weight_sum_finish launch");
 }
 
 extern "C" int udaseg_conf_share(const float* scores, int batch, int64_t pix_per_image, int classes, int ldc, int probs, float tau,

@@ -8,7 +8,8 @@
 //  * AdversarialLoss' nn.BCEWithLogitsLoss terms (src/models/losses.py:16,33-36,51).  The reference feeds the
 //      discriminator's *probabilities* into the with-logits loss; these kernels are agnostic: they compute
 //      mean(softplus(x) - x*label) of whatever x is.
-#include "scores_common.h"
+// The block partials, the LDS gradient tile and the finish kernels of the cross-entropy kernels are loss_reduce.h's.
+#include "loss_reduce.h"
 
 namespace udaseg {
 
@@ -49,18 +50,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const f32x4* __restrict__ l
     lse[p] = l;
     local += (double)(l - xt);
   }
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void ce_finish_kernel(const double* __restrict__ partials, int n, int64_t pixels, float* __restrict__ loss) {
-  // single wave: deterministic final sum
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) *loss = (float)(s / (double)pixels);
+  block_partial(local, red, partials);
 }
 
 // Generic fallback (ldc > 32): one thread per pixel, strided 16-B stores.
@@ -87,22 +77,19 @@ __global__ __launch_bounds__(256) void ce_bwd_simple_kernel(const f32x4* __restr
   }
 }
 
-// ldc <= 32: blocks walk 256-pixel chunks; gradients go through an LDS tile so the HBM stores are whole contiguous
-// lines (per-thread 96-B-strided 16-B stores ran at 1.7 TB/s), and the same tile yields the per-class column sums =
-// the segmentation head's bias gradient (saves a separate 200 MB pass).  colpart: [gridDim.x][LDC] or null.
+// ldc <= 32: blocks walk 256-pixel chunks; gradients go out through the LDS tile (GradTile, loss_reduce.h), which also yields
+// the per-class column sums.  colpart: [gridDim.x][LDC] or null.
 template <int LDC4>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                      const float* __restrict__ lse, const float* __restrict__ grad_out,
                                                      int64_t pixels, int classes, f32x4* __restrict__ dlogits,
                                                      float* __restrict__ colpart) {
-  constexpr int LDC = LDC4 * 4;
-  constexpr int NG = 256 / LDC;  // row groups for the column sums
-  __shared__ __attribute__((aligned(16))) float tile[256 * LDC];
-  __shared__ float colred[NG * LDC];
+  using Tile = GradTile<LDC4>;
+  __shared__ __attribute__((aligned(16))) float tile[256 * Tile::LDC];
+  __shared__ float colred[Tile::NG * Tile::LDC];
   const int tid = threadIdx.x;
   const float scale = (grad_out ? *grad_out : 1.f) / (float)pixels;
   const int64_t nchunks = (pixels + 255) / 256;
-  const int cc = tid % LDC, rg = tid / LDC;
   float colacc = 0.f;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int64_t p = chunk * 256 + tid;
@@ -118,33 +105,14 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const f32x4* __restrict__ l
           const int c = k * 4 + e;
           g[e] = c < classes ? (expf(v[e] - l) - (c == t ? 1.f : 0.f)) * scale : 0.f;
         }
-        *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+        Tile::put(tile, k, g);
       }
     } else {
-#pragma unroll
-      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      Tile::put_zero(tile);
     }
-    __syncthreads();
-    const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
-#pragma unroll
-    for (int it = 0; it < LDC4; ++it) {
-      const int idx = it * 256 + tid;
-      if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
-    }
-    if (colpart && rg < NG) {
-      for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
-    }
-    __syncthreads();
+    Tile::flush(tile, chunk, pixels, dlogits, colpart != nullptr, colacc);
   }
-  if (colpart) {
-    if (rg < NG) colred[rg * LDC + cc] = colacc;
-    __syncthreads();
-    if (tid < LDC) {
-      float s = 0.f;
-      for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
-      colpart[(size_t)blockIdx.x * LDC + tid] = s;
-    }
-  }
+  if (colpart) Tile::finish(colred, colpart, colacc);
 }
 
 // Forward and backward in ONE pass over the logits (round 5): the loss partials of ce_fwd_kernel (same pixel-to-thread map, same
@@ -156,15 +124,13 @@ template <int LDC4>
 __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
                                                          int64_t pixels, int classes, double* __restrict__ partials,
                                                          f32x4* __restrict__ dlogits, float* __restrict__ colpart) {
-  constexpr int LDC = LDC4 * 4;
-  constexpr int NG = 256 / LDC;
-  __shared__ __attribute__((aligned(16))) float tile[256 * LDC];
-  __shared__ float colred[NG * LDC];
+  using Tile = GradTile<LDC4>;
+  __shared__ __attribute__((aligned(16))) float tile[256 * Tile::LDC];
+  __shared__ float colred[Tile::NG * Tile::LDC];
   __shared__ double red[4];
   const int tid = threadIdx.x;
   const float scale = 1.f / (float)pixels;
   const int64_t nchunks = (pixels + 255) / 256;
-  const int cc = tid % LDC, rg = tid / LDC;
   float colacc = 0.f;
   double local = 0.0;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
@@ -200,34 +166,16 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(const f32x4* __restrict
           const int c = k * 4 + e;
           g[e] = c < classes ? (expf(v[k][e] - l) - (c == t ? 1.f : 0.f)) * scale : 0.f;
         }
-        *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+        Tile::put(tile, k, g);
       }
     } else {
-#pragma unroll
-      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      Tile::put_zero(tile);
     }
-    __syncthreads();
-    const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
-#pragma unroll
-    for (int it = 0; it < LDC4; ++it) {
-      const int idx = it * 256 + tid;
-      if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
-    }
-    if (colpart && rg < NG) {
-      for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
-    }
-    __syncthreads();
+    Tile::flush(tile, chunk, pixels, dlogits, colpart != nullptr, colacc);
   }
-  local = wave_sum_d(local);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
-  if (colpart && rg < NG) colred[rg * LDC + cc] = colacc;
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-  if (colpart && tid < LDC) {
-    float s = 0.f;
-    for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
-    colpart[(size_t)blockIdx.x * LDC + tid] = s;
-  }
+  if (colpart) Tile::put_columns(colred, colacc);
+  block_partial(local, red, partials);   // its barrier is the column sums' too
+  if (colpart) Tile::write_columns(colred, colpart);
 }
 
 // x[i] *= *g unless *g == 1 (then the launch returns at once: the gradient made for an upstream gradient of 1 is already right)
@@ -238,22 +186,6 @@ __global__ void scale_unless_one_kernel(f32x4* __restrict__ x, int64_t n4, float
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int64_t i = i0; i < n4; i += T) x[i] = x[i] * s;
   if (x2 != nullptr && i0 < n2) x2[i0] *= s;
-}
-
-// colsum[c] (+)= sum over blocks of colpart[b][c]: one 256-thread block per column, fixed-order tree => deterministic
-__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ colpart, int nblocks, int ldc,
-                                                            float* __restrict__ colsum, int accumulate) {
-  __shared__ float red[4];
-  const int c = blockIdx.x;
-  float s = 0.f;
-  for (int b = threadIdx.x; b < nblocks; b += 256) s += colpart[(size_t)b * ldc + c];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float t = (red[0] + red[1]) + (red[2] + red[3]);
-    colsum[c] = accumulate ? colsum[c] + t : t;
-  }
 }
 
 // ---- cross entropy with options: class weights w, ignore_index, label smoothing eps, reductions none / sum / mean --------------
@@ -291,34 +223,7 @@ __global__ __launch_bounds__(256) void ce_target_stats_kernel(const int64_t* __r
     }
   }
   double v[4] = {d, (double)nvalid, (double)nvoid, (double)ninvalid};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[k] = wave_sum_d(v[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    partials[(size_t)k * gridDim.x + blockIdx.x] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-  }
-}
-
-// single wave: denom = D, stats = [n_valid, n_void, n_invalid]
-__global__ void ce_target_stats_finish_kernel(const double* __restrict__ partials, int n, double* __restrict__ denom,
-                                              int64_t* __restrict__ stats) {
-  double s[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) a += partials[(size_t)k * n + i];
-    s[k] = wave_sum_d(a);
-  }
-  if (threadIdx.x == 0) {
-    *denom = s[0];
-    stats[0] = (int64_t)s[1];
-    stats[1] = (int64_t)s[2];
-    stats[2] = (int64_t)s[3];
-  }
+  block_partial_rows<4>(v, red, partials);
 }
 
 // The per-pixel terms shared by the optioned kernels.  wsh: the class weights in LDS (1 where no weights were given).
@@ -376,10 +281,9 @@ __global__ __launch_bounds__(256) void ce_opt_fwd_bwd_kernel(const f32x4* __rest
                                                              int has_ignore, int64_t ignore_index, float eps,
                                                              const double* __restrict__ denom, double* __restrict__ partials,
                                                              f32x4* __restrict__ dlogits, float* __restrict__ colpart) {
-  constexpr int LDC = LDC4 * 4;
-  constexpr int NG = 256 / LDC;
-  __shared__ __attribute__((aligned(16))) float tile[256 * LDC];
-  __shared__ float colred[NG * LDC];
+  using Tile = GradTile<LDC4>;
+  __shared__ __attribute__((aligned(16))) float tile[256 * Tile::LDC];
+  __shared__ float colred[Tile::NG * Tile::LDC];
   __shared__ double red[4];
   __shared__ float wsh[32];
   const int tid = threadIdx.x;
@@ -391,7 +295,6 @@ __global__ __launch_bounds__(256) void ce_opt_fwd_bwd_kernel(const f32x4* __rest
   const float scale = denom ? (float)(1.0 / *denom) : 1.f;
   const float om = SMOOTH ? 1.f - eps : 1.f, es = SMOOTH ? eps / (float)classes : 0.f;
   const int64_t nchunks = (pixels + 255) / 256;
-  const int cc = tid % LDC, rg = tid / LDC;
   float colacc = 0.f;
   double local = 0.0;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
@@ -420,44 +323,16 @@ __global__ __launch_bounds__(256) void ce_opt_fwd_bwd_kernel(const f32x4* __rest
           const int c = k * 4 + e;
           g[e] = c < classes ? ce_opt_grad<SMOOTH>(v[k][e], l, c == t, a, pk, ek, wsh[c]) : 0.f;
         }
-        *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+        Tile::put(tile, k, g);
       }
     } else {
-#pragma unroll
-      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      Tile::put_zero(tile);
     }
-    __syncthreads();
-    const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
-#pragma unroll
-    for (int it = 0; it < LDC4; ++it) {
-      const int idx = it * 256 + tid;
-      if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
-    }
-    if (colpart && rg < NG) {
-      for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
-    }
-    __syncthreads();
+    Tile::flush(tile, chunk, pixels, dlogits, colpart != nullptr, colacc);
   }
-  local = wave_sum_d(local);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
-  if (colpart && rg < NG) colred[rg * LDC + cc] = colacc;
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-  if (colpart && tid < LDC) {
-    float s = 0.f;
-    for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
-    colpart[(size_t)blockIdx.x * LDC + tid] = s;
-  }
-}
-
-// loss = sum of the block partials, divided by D for 'mean'; D == 0 (all void, or only zero-weight classes): NaN, whatever the
-// smoothing term sums to -- torch's 0 / 0 in the weighted mean of its first term
-__global__ void ce_opt_finish_kernel(const double* __restrict__ partials, int n, const double* __restrict__ denom,
-                                     float* __restrict__ loss) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) *loss = denom ? (*denom == 0.0 ? NAN : (float)(s / *denom)) : (float)s;
+  if (colpart) Tile::put_columns(colred, colacc);
+  block_partial(local, red, partials);   // its barrier is the column sums' too
+  if (colpart) Tile::write_columns(colred, colpart);
 }
 
 // Two-pass route, forward: lse[p] kept for the backward, loss_px[p] = l_p ('none'; may be null), block partials of sum l_p.
@@ -489,10 +364,7 @@ __global__ __launch_bounds__(256) void ce_opt_fwd_kernel(const f32x4* __restrict
     if (loss_px) loss_px[p] = lp;
     local += (double)lp;
   }
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  block_partial(local, red, partials);
 }
 
 // Two-pass route, backward.  The upstream gradient is the scalar *grad_out (null = 1) times, for 'none', grad_px[p].
@@ -504,10 +376,9 @@ __global__ __launch_bounds__(256) void ce_opt_bwd_kernel(const f32x4* __restrict
                                                          int64_t pixels, int classes, int has_ignore, int64_t ignore_index, float eps,
                                                          const double* __restrict__ denom, f32x4* __restrict__ dlogits,
                                                          float* __restrict__ colpart) {
-  constexpr int LDC = LDC4 * 4;
-  constexpr int NG = TILED ? 256 / LDC : 1;
-  __shared__ __attribute__((aligned(16))) float tile[TILED ? 256 * LDC : 4];
-  __shared__ float colred[NG * LDC];
+  using Tile = GradTile<LDC4>;
+  __shared__ __attribute__((aligned(16))) float tile[256 * Tile::LDC];   // !TILED: nothing touches the two, and they take no LDS
+  __shared__ float colred[Tile::NG * Tile::LDC];
   __shared__ float wsh[CE_MAXC];
   const int tid = threadIdx.x;
   if (tid < CE_MAXC) wsh[tid] = tid < classes ? (weight ? weight[tid] : 1.f) : 0.f;
@@ -518,7 +389,6 @@ __global__ __launch_bounds__(256) void ce_opt_bwd_kernel(const f32x4* __restrict
   const float scale = (grad_out ? *grad_out : 1.f) * (denom ? (float)(1.0 / *denom) : 1.f);
   const float om = SMOOTH ? 1.f - eps : 1.f, es = SMOOTH ? eps / (float)classes : 0.f;
   const int64_t nchunks = (pixels + 255) / 256;
-  const int cc = tid % LDC, rg = tid / LDC;
   float colacc = 0.f;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int64_t p = chunk * 256 + tid;
@@ -542,39 +412,18 @@ __global__ __launch_bounds__(256) void ce_opt_bwd_kernel(const f32x4* __restrict
           const int c = k * 4 + e;
           g[e] = c < classes ? ce_opt_grad<SMOOTH>(v[e], l, c == t, a, pk, ek, wsh[c]) : 0.f;
         }
-        if (TILED) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = g;
+        if (TILED) Tile::put(tile, k, g);
         else dlogits[p * LDC4 + k] = g;
       }
     } else if (TILED) {
-#pragma unroll
-      for (int k = 0; k < LDC4; ++k) *reinterpret_cast<f32x4*>(tile + tid * LDC + k * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      Tile::put_zero(tile);
     } else if (p < pixels) {
 #pragma unroll
       for (int k = 0; k < LDC4; ++k) dlogits[p * LDC4 + k] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (TILED) {
-      __syncthreads();
-      const int64_t base4 = chunk * 256 * LDC4, lim4 = pixels * LDC4;
-#pragma unroll
-      for (int it = 0; it < LDC4; ++it) {
-        const int idx = it * 256 + tid;
-        if (base4 + idx < lim4) dlogits[base4 + idx] = reinterpret_cast<const f32x4*>(tile)[idx];
-      }
-      if (colpart && rg < NG) {
-        for (int r = rg; r < 256; r += NG) colacc += tile[r * LDC + cc];
-      }
-      __syncthreads();
-    }
+    if (TILED) Tile::flush(tile, chunk, pixels, dlogits, colpart != nullptr, colacc);
   }
-  if (TILED && colpart) {
-    if (rg < NG) colred[rg * LDC + cc] = colacc;
-    __syncthreads();
-    if (tid < LDC) {
-      float s = 0.f;
-      for (int g2 = 0; g2 < NG; ++g2) s += colred[g2 * LDC + tid];
-      colpart[(size_t)blockIdx.x * LDC + tid] = s;
-    }
-  }
+  if (TILED && colpart) Tile::finish(colred, colpart, colacc);
 }
 
 // ---- validation metrics: per-pixel argmax + confusion matrix (SegmentationTrainer.calculate_metrics, reference
@@ -745,9 +594,7 @@ extern "C" int udaseg_ce_fwd(const float* logits, const int64_t* target, int64_t
       }))
     return unsupported_width("ce_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_fwd launch");
-  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, pixels, loss);
-  UDASEG_LAUNCH_CHECK("ce_finish launch");
-  return UDASEG_OK;
+  return launch_loss_finish(partials, grid, (double)pixels, nullptr, loss, 0, st, "ce_finish launch");
 }
 
 extern "C" int udaseg_ce_fwd_bwd(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, double* partials,
@@ -764,13 +611,8 @@ extern "C" int udaseg_ce_fwd_bwd(const float* logits, const int64_t* target, int
       }))
     return unsupported_width("ce_fwd_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_fwd_bwd launch");
-  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, pixels, loss);
-  UDASEG_LAUNCH_CHECK("ce_finish launch");
-  if (colsum) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
-    UDASEG_LAUNCH_CHECK("colsum_finish launch");
-  }
-  return UDASEG_OK;
+  const int rc = launch_loss_finish(partials, grid, (double)pixels, nullptr, loss, 0, st, "ce_finish launch");
+  return rc || !colsum ? rc : launch_colsum_finish(colsum_partials, grid, ldc, colsum, 0, st);
 }
 
 extern "C" int udaseg_scale_unless_one(float* x, int64_t count, float* x2, int count2, const float* g, void* stream) {
@@ -805,11 +647,7 @@ extern "C" int udaseg_ce_bwd(const float* logits, const int64_t* target, const f
       }))
     return unsupported_width("ce_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_bwd launch");
-  if (colsum) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
-    UDASEG_LAUNCH_CHECK("colsum_finish launch");
-  }
-  return UDASEG_OK;
+  return colsum ? launch_colsum_finish(colsum_partials, grid, ldc, colsum, 0, st) : UDASEG_OK;
 }
 
 extern "C" int udaseg_argmax_confusion(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc,
@@ -965,9 +803,7 @@ extern "C" int udaseg_ce_target_stats(const int64_t* target, const float* weight
   hipLaunchKernelGGL(ce_target_stats_kernel, dim3(grid), dim3(256), 0, st, target, weight, pixels, classes, has_ignore, ignore_index,
                      partials);
   UDASEG_LAUNCH_CHECK("ce_target_stats launch");
-  hipLaunchKernelGGL(ce_target_stats_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, denom, stats);
-  UDASEG_LAUNCH_CHECK("ce_target_stats_finish launch");
-  return UDASEG_OK;
+  return launch_rows_finish(4, partials, grid, denom, stats, st, "ce_target_stats_finish launch");
 }
 
 extern "C" int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes,
@@ -993,13 +829,8 @@ extern "C" int udaseg_ce_opt_fwd_bwd(const float* logits, const int64_t* target,
       }))
     return unsupported_width("ce_opt_fwd_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_fwd_bwd launch");
-  hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, dn, loss);
-  UDASEG_LAUNCH_CHECK("ce_opt_finish launch");
-  if (colsum) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
-    UDASEG_LAUNCH_CHECK("colsum_finish launch");
-  }
-  return UDASEG_OK;
+  rc = launch_loss_finish(partials, grid, 1.0, dn, loss, 0, st, "ce_opt_finish launch");
+  return rc || !colsum ? rc : launch_colsum_finish(colsum_partials, grid, ldc, colsum, 0, st);
 }
 
 extern "C" int udaseg_ce_opt_fwd(const float* logits, const int64_t* target, const float* weight, int64_t pixels, int classes,
@@ -1022,11 +853,7 @@ extern "C" int udaseg_ce_opt_fwd(const float* logits, const int64_t* target, con
       }))
     return unsupported_width("ce_opt_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_fwd launch");
-  if (loss) {
-    hipLaunchKernelGGL(ce_opt_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? denom : (const double*)nullptr, loss);
-    UDASEG_LAUNCH_CHECK("ce_opt_finish launch");
-  }
-  return UDASEG_OK;
+  return loss ? launch_loss_finish(partials, grid, 1.0, mean ? denom : nullptr, loss, 0, st, "ce_opt_finish launch") : UDASEG_OK;
 }
 
 extern "C" int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, const float* weight, const float* lse,
@@ -1056,9 +883,5 @@ extern "C" int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, con
       }))
     return unsupported_width("ce_opt_bwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("ce_opt_bwd launch");
-  if (colsum) {
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(ldc), dim3(256), 0, st, colsum_partials, grid, ldc, colsum, 0);
-    UDASEG_LAUNCH_CHECK("colsum_finish launch");
-  }
-  return UDASEG_OK;
+  return colsum ? launch_colsum_finish(colsum_partials, grid, ldc, colsum, 0, st) : UDASEG_OK;
 }

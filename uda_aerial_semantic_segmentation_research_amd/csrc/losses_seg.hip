@@ -3,8 +3,9 @@
 //   WeightedSegmentationLoss     :154-215  (focal-weighted cross entropy + Dice)
 //   ConsistencyLoss              :53-108   (symmetric temperature KL, 'batchmean')
 // Logits are NHWC rows [pixel][ldc] with `classes` valid channels (ldc % 4 == 0, ldc <= 32), as produced by Unet.
-// One thread per pixel, softmax row in registers, wave/block reductions, f64 cross-block accumulation.
-#include "scores_common.h"
+// One thread per pixel, softmax row in registers, wave/block reductions, f64 cross-block accumulation; the block partials and
+// the finish of the focal and consistency sums are loss_reduce.h's.
+#include "loss_reduce.h"
 
 namespace udaseg {
 
@@ -205,20 +206,7 @@ __global__ __launch_bounds__(256) void focal_fwd_kernel(const f32x4* __restrict_
     const float pt = expf(-ce);
     local += (double)(alpha * powf(fmaxf(1.f - pt, 0.f), gamma) * ce);
   }
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void sum_finish_kernel(const double* __restrict__ partials, int n, double divisor, float* __restrict__ out, int accumulate) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) {
-    const float v = (float)(s / divisor);
-    *out = accumulate ? *out + v : v;
-  }
+  block_partial(local, red, partials);
 }
 
 // df/dce = alpha * [(1-pt)^gamma + ce * gamma * (1-pt)^(gamma-1) * pt];  dce/dz_k = w_t * (p_k - [k == t])
@@ -283,10 +271,7 @@ __global__ __launch_bounds__(256) void consistency_fwd_kernel(const f32x4* __res
       if (c < classes) acc += (expf(l1[c]) - expf(l2[c])) * (l1[c] - l2[c]);
     local += (double)acc;
   }
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  block_partial(local, red, partials);
 }
 
 // dz1 = s/T * [ (p1 - p2) + p1 * ((l1 - l2) - kl12) ],  dz2 symmetric;  s = grad_out * weight / (2 * batch)
@@ -392,9 +377,7 @@ static int focal_fwd(const char* who, const float* logits, const int64_t* target
       }))
     return unsupported_width(who, "ldc", ldc);
   UDASEG_LAUNCH_CHECK("focal_fwd launch");
-  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, mean ? (double)pixels : 1.0, loss, accumulate);
-  UDASEG_LAUNCH_CHECK("focal_finish launch");
-  return UDASEG_OK;
+  return launch_loss_finish(partials, grid, mean ? (double)pixels : 1.0, nullptr, loss, accumulate, st, "focal_finish launch");
 }
 
 static int focal_bwd(const char* who, const float* logits, const int64_t* target, const float* class_weights, float alpha,
@@ -485,9 +468,7 @@ extern "C" int udaseg_consistency_fwd(const float* z1, const float* z2, float te
     return unsupported_width("consistency_fwd", "ldc", ldc);
   UDASEG_LAUNCH_CHECK("consistency_fwd launch");
   // (KL(p2||p1) + KL(p1||p2)) / 2, each 'batchmean' = sum / batch
-  hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, 2.0 * (double)batch, loss, 0);
-  UDASEG_LAUNCH_CHECK("consistency_finish launch");
-  return UDASEG_OK;
+  return launch_loss_finish(partials, grid, 2.0 * (double)batch, nullptr, loss, 0, st, "consistency_finish launch");
 }
 
 extern "C" int udaseg_consistency_bwd(const float* z1, const float* z2, float temperature, const float* grad_out, float weight,

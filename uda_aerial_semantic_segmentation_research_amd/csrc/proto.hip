@@ -334,19 +334,6 @@ __global__ __launch_bounds__(PR_THREADS) void proto_rectify_kernel(const float* 
   }
 }
 
-static bool proto_dims_ok(const char* who, int classes, int dim) {
-  if (classes > 0 && classes <= 32 && dim >= 4 && dim <= 64 && dim % 4 == 0) return true;
-  set_error("%s: need 0 < classes <= 32, 4 <= dim <= 64, dim %% 4 == 0 (classes=%d dim=%d)", who, classes, dim);
-  return false;
-}
-
-static bool proto_feat_ok(const char* who, int64_t pixels, int classes, int dim, int ldf) {
-  if (!proto_dims_ok(who, classes, dim)) return false;
-  if (pixels > 0 && pixels < ((int64_t)1 << 31) && ldf >= dim && ldf % 4 == 0) return true;
-  set_error("%s: need 0 < pixels < 2^31, dim <= ldf, ldf %% 4 == 0 (pixels=%lld dim=%d ldf=%d)", who, (long long)pixels, dim, ldf);
-  return false;
-}
-
 }  // namespace udaseg
 
 using namespace udaseg;

@@ -11,15 +11,16 @@
 // grid-stride, the prototypes staged once per block as fp32 in LDS and read as broadcasts, a template on the number of class
 // vectors so that the class loops unroll, the channel loops rolled.  The distance pass holds 4 NV accumulator vectors; the
 // gradient pass holds the 4 NV coefficients T s_c - t_c and ONE accumulator vector per channel quad: neither f nor d lives
-// across it.  Weights, divisor, block partials and the fixed-order loss scalar are distill.hip's (udaseg_soft_ce_fwd_bwd): no
-// float atomics, integer atomics for the counters only.  Measured (profiles/contrast_bench.txt, 8 x 512 x 512 pixels, 16 channels, 23
+// across it.  Weights and divisor are distill.hip's (udaseg_soft_ce_fwd_bwd), the block partials and the fixed-order loss scalar
+// loss_reduce.h's: no float atomics, integer atomics for the counters only.  Measured (profiles/contrast_bench.txt, 8 x 512 x 512 pixels, 16 channels, 23
 // classes): 0.195 ms, 3.4 x a device copy of the same bytes -- the pass is bound by its 3 C D multiply-adds and 2 C exponentials per
 // pixel, not by its two streams; udaseg_proto_assign, the same pass without the gradient loop, takes 0.70 of it.
-#include "scores_common.h"
+#include "loss_reduce.h"
 
 namespace udaseg {
 
 constexpr int PC_THREADS = 256;
+static_assert(PC_THREADS == 256, "block_partial (loss_reduce.h) sums the four waves of a 256-thread block");
 constexpr int PC_MAX_BLOCKS = 4096;       // udaseg_proto_assign: proto_rectify_kernel's grid
 constexpr int PC_STATS = 4;               // counted, void by weight, void by label / target, void by a non-finite feature
 
@@ -219,8 +220,7 @@ __global__ __launch_bounds__(PC_THREADS) void proto_contrast_kernel(const float*
       for (int q = q0; q < lf; ++q) *reinterpret_cast<f32x4*>(grow + 4 * q) = f32x4{0.f, 0.f, 0.f, 0.f};   // void: all ldf lanes
     }
   }
-  local = wave_sum_d(local);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
+  block_partial(local, red, partials);
   if (stats) {
 #pragma unroll
     for (int s = 0; s < PC_STATS; ++s) {
@@ -228,29 +228,6 @@ __global__ __launch_bounds__(PC_THREADS) void proto_contrast_kernel(const float*
       if ((tid & 63) == 0 && n) atomicAdd(&stats[s], (unsigned long long)n);
     }
   }
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// distill.hip's soft_ce_finish_kernel: loss = (sum of the n block partials, in a fixed order) / D; D == 0 under a device
-// denominator (every weight void): NaN.  single wave
-__global__ void proto_contrast_finish_kernel(const double* __restrict__ partials, int n, double pixels, int mean,
-                                             const double* __restrict__ denom, float* __restrict__ loss) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) s += partials[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) *loss = mean ? (float)(s / pixels) : (denom ? (*denom == 0.0 ? NAN : (float)(s / *denom)) : (float)s);
-}
-
-// proto.hip's argument checks, restated (they are static there): the same shapes are accepted.
-static bool contrast_feat_ok(const char* who, int64_t pixels, int classes, int dim, int ldf) {
-  if (!(classes > 0 && classes <= 32 && dim >= 4 && dim <= 64 && dim % 4 == 0)) {
-    set_error("%s: need 0 < classes <= 32, 4 <= dim <= 64, dim %% 4 == 0 (classes=%d dim=%d)", who, classes, dim);
-    return false;
-  }
-  if (pixels > 0 && pixels < ((int64_t)1 << 31) && ldf >= dim && ldf % 4 == 0) return true;
-  set_error("%s: need 0 < pixels < 2^31, dim <= ldf, ldf %% 4 == 0 (pixels=%lld dim=%d ldf=%d)", who, (long long)pixels, dim, ldf);
-  return false;
 }
 
 }  // namespace udaseg
@@ -259,7 +236,7 @@ using namespace udaseg;
 
 extern "C" int udaseg_proto_assign(const float* feat, int ldf, int dim, int classes, int ldc, const double* proto, const int32_t* seen,
                                    const float* inv_tau, int64_t pixels, float* out, void* stream) {
-  if (!contrast_feat_ok("proto_assign", pixels, classes, dim, ldf)) return UDASEG_E_BADARG;
+  if (!proto_feat_ok("proto_assign", pixels, classes, dim, ldf)) return UDASEG_E_BADARG;
   if (!scores_args_ok("proto_assign", pixels, classes, ldc)) return UDASEG_E_BADARG;
   UDASEG_CHECK_ARG(feat && proto && seen && inv_tau && out, "proto_assign: NULL pointer");
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
@@ -279,11 +256,9 @@ extern "C" int udaseg_proto_contrast_fwd_bwd(const float* feat, int ldf, int dim
                                              int classes, const double* proto, const int32_t* seen, const float* inv_tau, int mean,
                                              const double* denom, double* partials, float* loss, float* dfeat, int64_t* stats,
                                              void* stream) {
-  UDASEG_CHECK_ARG(batch > 0 && pix_per_image > 0 && pix_per_image <= INT64_MAX / batch,
-                   "proto_contrast_fwd_bwd: need batch > 0, pix_per_image > 0 (batch=%d pix_per_image=%lld)", batch,
-                   (long long)pix_per_image);
+  if (!image_grid_ok("proto_contrast_fwd_bwd", batch, pix_per_image)) return UDASEG_E_BADARG;
   const int64_t pixels = (int64_t)batch * pix_per_image;
-  if (!contrast_feat_ok("proto_contrast_fwd_bwd", pixels, classes, dim, ldf)) return UDASEG_E_BADARG;
+  if (!proto_feat_ok("proto_contrast_fwd_bwd", pixels, classes, dim, ldf)) return UDASEG_E_BADARG;
   UDASEG_CHECK_ARG((labels != nullptr) != (target != nullptr),
                    "proto_contrast_fwd_bwd: exactly one of labels (hard) and target (soft) must be given");
   if (target && !scores_args_ok("proto_contrast_fwd_bwd", pixels, classes, ldt, INT_MAX, "ldt")) return UDASEG_E_BADARG;
@@ -301,7 +276,6 @@ extern "C" int udaseg_proto_contrast_fwd_bwd(const float* feat, int ldf, int dim
       }))
     return unsupported_width("proto_contrast_fwd_bwd", "classes", classes);
   UDASEG_LAUNCH_CHECK("proto_contrast launch");
-  hipLaunchKernelGGL(proto_contrast_finish_kernel, dim3(1), dim3(64), 0, st, partials, grid, (double)pixels, mean, denom, loss);
-  UDASEG_LAUNCH_CHECK("proto_contrast_finish launch");
-  return UDASEG_OK;
+  // mean and denom exclude each other (above): D = pixels, *denom or 1
+  return launch_loss_finish(partials, grid, mean ? (double)pixels : 1.0, denom, loss, 0, st, "proto_contrast_finish launch");
 }

@@ -1,5 +1,6 @@
 // Shared by every kernel that walks a padded NHWC buffer of per-pixel class scores: [pixels][ldc] fp32, classes <= ldc,
-// ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, curves.hip, pseudo.hip, predict.hip, distill.hip).  Such a kernel is a
+// ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, advent.hip, distill.hip, curves.hip, pseudo.hip, predict.hip,
+// proto.hip, proto_contrast.hip; loss_reduce.h builds on it for what follows a loss kernel's row arithmetic).  Such a kernel is a
 // template on its row width in f32x4 vectors -- LDC4 = ldc / 4 where the width is also the row stride, NV = cdiv(classes, 4) where
 // ldc stays a runtime argument -- so here are the one width dispatcher, the one row reader and the one tie rule of the winner.
 #pragma once
@@ -103,6 +104,26 @@ static inline bool scores_args_ok(const char* who, int64_t pixels, int classes, 
   if (max_ld != INT_MAX) snprintf(limit, sizeof limit, " <= %d", max_ld);
   set_error("%s: need 0 < pixels, 0 < classes <= 32, classes <= %s%s, %s %% 4 == 0 (pixels=%lld classes=%d %s=%d)", who, ld_name,
             limit, ld_name, (long long)pixels, classes, ld_name, ld);
+  return false;
+}
+
+// The prototype table [classes][dim] and the feature rows [pixels][ldf] of proto.hip and proto_contrast.hip.
+static inline bool proto_dims_ok(const char* who, int classes, int dim) {
+  if (classes > 0 && classes <= 32 && dim >= 4 && dim <= 64 && dim % 4 == 0) return true;
+  set_error("%s: need 0 < classes <= 32, 4 <= dim <= 64, dim %% 4 == 0 (classes=%d dim=%d)", who, classes, dim);
+  return false;
+}
+static inline bool proto_feat_ok(const char* who, int64_t pixels, int classes, int dim, int ldf) {
+  if (!proto_dims_ok(who, classes, dim)) return false;
+  if (pixels > 0 && pixels < ((int64_t)1 << 31) && ldf >= dim && ldf % 4 == 0) return true;
+  set_error("%s: need 0 < pixels < 2^31, dim <= ldf, ldf %% 4 == 0 (pixels=%lld dim=%d ldf=%d)", who, (long long)pixels, dim, ldf);
+  return false;
+}
+
+// batch images of pix_per_image pixels each (distill.hip, proto_contrast.hip): the product fits an int64
+static inline bool image_grid_ok(const char* who, int batch, int64_t ppi) {
+  if (batch > 0 && ppi > 0 && ppi <= INT64_MAX / batch) return true;
+  set_error("%s: need batch > 0, pix_per_image > 0 (batch=%d pix_per_image=%lld)", who, batch, (long long)ppi);
   return false;
 }
 
