@@ -434,6 +434,51 @@ int udaseg_score_hist(const float* logits, const int64_t* target, int64_t pixels
 int udaseg_curve_finish(const int64_t* pos, const int64_t* neg, int classes, int bins, double* auc, double* ap,
                         double* auc_slack, int64_t* support, void* stream);
 
+/* ---- calibration of the winner's confidence (csrc/calib.hip): reliability tables, expected calibration error, temperature fit.
+ * (The reference bins a host copy of the softmax with numpy.)  scores / logits: padded NHWC fp32 [pixels][ldc], 16-byte aligned,
+ * 0 < classes <= 32, classes <= ldc, ldc % 4 == 0, 0 < pixels < 2^31; target: int64 [pixels], a target outside [0, classes) is
+ * VOID and left out of everything.  inv_temp: device float [1], the reciprocal temperature beta (NULL: beta = 1); a beta that is
+ * not a positive finite number makes every pixel of the call non-finite.  ONE definition of the confidence, udaseg_conf_hist's:
+ *   c^ = first maximum of z, m = z[c^], p = 1 / sum_{j < classes} expf((z_j - m) * beta), the sum as four partial sums by j % 4,
+ *   then (s0 + s1) + (s2 + s3); with inv_temp == NULL bit for bit udaseg_conf_share's and udaseg_conf_hist's p;
+ *   probs == 1 (probabilities q; inv_temp must be NULL): c^ = first maximum of q, p = q[c^].
+ * A pixel with a valid target is NON-FINITE when p is not a finite number in [0, 1] (a NaN or +inf logit, all logits -inf; with
+ * probs also a NaN in any channel < classes): it is in no table.
+ *   b = min((int)floorf(p * (float)bins), bins - 1),  2 <= bins <= 64
+ *   tables: uint64 [3][classes][bins], indexed by the PREDICTED class c^:
+ *     tables[0][c^][b] += 1;  tables[1][c^][b] += (c^ == target);  tables[2][c^][b] += __float2uint_rn(p * 16777216.f)
+ *   (the confidence in 2^-24 fixed point: integer sums, independent of order, below 2^55 at 2^31 pixels).
+ *   counters: int64 [3] += the pixels in the tables, the void pixels, the non-finite pixels (they sum to `pixels`).
+ * Both buffers ACCUMULATE across calls; the caller zeroes them once.  Integer atomics only: exact, the same on every run.
+ * The kernel's grid covers 512 * 256 pixels per sweep and strides over the rest. */
+int udaseg_calib_hist(const float* scores, const int64_t* target, int64_t pixels, int classes, int ldc, int probs,
+                      const float* inv_temp, int bins, int64_t* tables, int64_t* counters, void* stream);
+/* From the tables, in float64 and a fixed order (bins 0 .. bins - 1): n_b, a_b, q_b = count, correct, conf_q of bin b summed over the
+ * classes (integers), N = sum n_b.  out: double [6] =
+ *   N;  accuracy = sum a_b / N;  mean_conf = sum q_b / 2^24 / N;  ece = sum_b |a_b - q_b / 2^24| / N;
+ *   mce = max over the non-empty bins of |a_b / n_b - q_b / 2^24 / n_b|;  gap = mean_conf - accuracy (positive: over-confident).
+ * per_class: double [4][classes] = n_c, acc_c, conf_c, ece_c: the same quantities over the pixels PREDICTED as c.
+ * Everything but the counts is NaN where its denominator is 0. */
+int udaseg_calib_finish(const int64_t* tables, int classes, int bins, double* out, double* per_class, void* stream);
+/* The negative log likelihood of the target under softmax(beta z) and its first two derivatives in beta.  Per pixel with a valid
+ * target t, in fp32, d_j = z_j - m (m as above), e_j = expf(beta * d_j), S = sum e_j, A = sum e_j d_j, B = sum e_j d_j^2 (each as
+ * four partial sums by j % 4):
+ *   nll = logf(S) - beta * d_t;   mu = A / S;   g1 = mu - d_t  (= d nll / d beta);   g2 = B / S - mu * mu  (= d^2 nll / d beta^2)
+ * A pixel whose three terms are not all finite is skipped and counted in counters[2].  sums: double [4] += n, sum nll, sum g1,
+ * sum g2 over the counted pixels -- float64 sums in the fixed order of the loss kernels (thread: its pixels in order; block:
+ * block_partial_rows; grid: one wave over the block partials), so two identical call sequences give identical bits.  sums
+ * ACCUMULATES across calls (a loader pass is one sum); counters: int64 [3] += counted, void, non-finite.
+ * partials: 4 * udaseg_seg_partials() doubles of scratch. */
+int udaseg_calib_nll(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, const float* inv_temp,
+                     double* partials, double* sums, int64_t* counters, void* stream);
+/* One guarded Newton step on beta = inv_temp[0] (the NLL is convex in beta, not in the temperature), in float64:
+ *   if n > 0, sum g2 > 0, every sum finite and beta positive and finite:
+ *     beta' = beta - sum g1 / sum g2, clamped to [beta / 4, 4 beta], then to [1 / 64, 64], stored as fp32;
+ *   otherwise beta is unchanged.
+ * state: double [4] = mean nll, mean g1 (NaN when n == 0), (double)(fp32 beta') - beta, state[3] + 1 (the number of steps taken
+ * since the caller zeroed it).  sums is zeroed for the next pass. */
+int udaseg_calib_step(double* sums, float* inv_temp, double* state, void* stream);
+
 /* ---- class-balanced pseudo-labels of unlabelled target frames (CBST, Zou et al. 2018; an extension, the reference's phase 3 is
  * consistency only).  scores: padded NHWC fp32 [pixels][ldc], 16-byte aligned, ldc % 4 == 0, 0 < classes <= 32, classes <= ldc,
  * 0 < pixels < 2^31; only channels < classes are read.  ONE definition serves both pixel entry points:

@@ -119,6 +119,10 @@ SIGNATURES = {
     "udaseg_argmax_confusion": (_I, [_P, _P, _L, _I, _I, _P, _P, _P]),
     "udaseg_score_hist": (_I, [_P, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
     "udaseg_curve_finish": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "udaseg_calib_hist": (_I, [_P, _P, _L, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "udaseg_calib_finish": (_I, [_P, _I, _I, _P, _P, _P]),
+    "udaseg_calib_nll": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+    "udaseg_calib_step": (_I, [_P, _P, _P, _P]),
     "udaseg_conf_hist": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_pseudo_thresholds": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
     "udaseg_pseudo_labels": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

@@ -329,6 +329,14 @@ OPERANDS = {
     "udaseg_curve_finish": [T("pos", i64, "classes*bins"), T("neg", i64, "classes*bins"), I("classes"), I("bins"),
                             T("auc", f64, "classes"), T("ap", f64, "classes"), T("auc_slack", f64, "classes"),
                             T("support", i64, "2*classes"), S],
+    "udaseg_calib_hist": [T("scores", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"), I("probs"),
+                          T("inv_temp", f32, 1, True), I("bins"), T("tables", i64, "3*classes*bins"), T("counters", i64, 3), S],
+    "udaseg_calib_finish": [T("tables", i64, "3*classes*bins"), I("classes"), I("bins"), T("out", f64, 6),
+                            T("per_class", f64, "4*classes"), S],
+    "udaseg_calib_nll": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
+                         T("inv_temp", f32, 1, True), T("partials", f64, "4*seg_partials()"), T("sums", f64, 4),
+                         T("counters", i64, 3), S],
+    "udaseg_calib_step": [T("sums", f64, 4), T("inv_temp", f32, 1), T("state", f64, 4), S],
     "udaseg_conf_hist": [T("scores", f32, "pixels*ldc"), I("pixels"), I("classes"), I("ldc"), I("probs"), I("bins"),
                          T("hist", i64, "classes*bins"), T("nonfinite", i64, 1), S],
     "udaseg_pseudo_thresholds": [T("hist", i64, "classes*bins"), I("classes"), I("bins"), T("portion", f64, "classes"), I("k_floor"),

@@ -102,6 +102,28 @@ def curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st=None):
     check(ops.udaseg_curve_finish(pos, neg, classes, bins, auc, ap, auc_slack, support, st), "curve_finish")
 
 
+def calib_hist(scores_base, target, pixels, classes, ldc, probs, inv_temp, bins, tables, counters, st=None):
+    """tables [3 * classes * bins] int64 += count / correct / conf_q by predicted class and confidence bin, counters [3] += in the
+    tables / void / non-finite (they accumulate).  inv_temp: device fp32 [1] or None (beta = 1)."""
+    check(ops.udaseg_calib_hist(scores_base, target, pixels, classes, ldc, int(bool(probs)), inv_temp, bins, tables, counters, st),
+          "calib_hist")
+
+
+def calib_finish(tables, classes, bins, out, per_class, st=None):
+    check(ops.udaseg_calib_finish(tables, classes, bins, out, per_class, st), "calib_finish")
+
+
+def calib_nll(logits_base, target, pixels, classes, ldc, inv_temp, partials, sums, counters, st=None):
+    """sums [4] f64 += n, sum nll, sum d nll / d beta, sum d2 nll / d beta2 (fixed-order sums; they accumulate).
+    partials: 4 * seg_partials() doubles of scratch."""
+    check(ops.udaseg_calib_nll(logits_base, target, pixels, classes, ldc, inv_temp, partials, sums, counters, st), "calib_nll")
+
+
+def calib_step(sums, inv_temp, state, st=None):
+    """One guarded Newton step on inv_temp [1] from sums [4]; sums is zeroed, state [4] f64 written."""
+    check(ops.udaseg_calib_step(sums, inv_temp, state, st), "calib_step")
+
+
 def conf_hist(scores_base, pixels, classes, ldc, probs, bins, hist, nonfinite, st=None):
     """hist [classes * bins] int64 += the histogram of the winning class's confidence, nonfinite [1] += the pixels without one
     (they accumulate)."""
