@@ -708,3 +708,136 @@ def wgrad_pair_config(h, w, ci, co, up_ca=0, pair=7):
     if up_ca == 32 and ci == 32 and co == 16 and h % 2 == 0 and w % 2 == 0 and w >= 16 and pair & 4:
         return 6
     return 0
+
+
+# =================================================================================== the fp32 convolutions on the fp32 matrix pipe
+# csrc/conv_small.hip and the non-bf16, non-X3 instances of csrc/conv_igemm.hip and csrc/conv_wgrad.hip
+# (tests/test_gpu_conv_f32_grade.py, cases in tests/_conv_f32_cases.py).  Operands are arbitrary fp32 values and enter the matrix
+# instruction unrounded.  The second leg of a Ref (stored in ``leg_trunc``, logged as d_mfma) is rne_matmul: an fp32 accumulator to
+# which the sum of ``group`` products is added with ONE round-to-nearest per matrix instruction, in im2col order (taps outer,
+# channels inner; the pixel axis for the weight gradient).  The K-slices, the split-K partial sums and the order of their atomics are
+# not restated: their error is of the same size as one more rounding per slice, far below the margin of 4.
+MFMA_32 = 2                               # K terms per v_mfma_f32_32x32x2_f32: conv_igemm_kernel, conv_wgrad_kernel
+MFMA_16 = 4                               # K terms per v_mfma_f32_16x16x4_f32: conv3x3_small_kernel, conv3x3_small_wgrad_kernel
+
+
+class F32Grader(Grader):
+    PREFIX, LEG = "f32-grade", "d_mfma"
+
+
+def rne_matmul(A, B, group):
+    """A @ B with an fp32 accumulator: acc = fp32(acc + sum of ``group`` products), the sum formed in float64 (exact to 2^-53 of
+    its magnitude for fp32 operands: 'the exact sum'), one round-to-nearest-even per step, in the order of the K axis."""
+    A, B = np.asarray(A, dtype=F64), np.asarray(B, dtype=F64)
+    acc = np.zeros((A.shape[0], B.shape[1]), dtype=F32)
+    for j in range(0, A.shape[1], group):
+        acc = (acc.astype(F64) + A[:, j:j + group] @ B[j:j + group]).astype(F32)
+    return acc
+
+
+def f32_fwd(x, w, stride, pad, group):
+    mm = lambda A, B: rne_matmul(A, B, group)  # noqa: E731
+    return Ref(torch_fwd(x, w, stride, pad, torch.float64), torch_fwd(np.abs(x), np.abs(w), stride, pad, torch.float64),
+               torch_fwd(x, w, stride, pad, torch.float32), im2col_fwd(x, w, stride, pad, mm))
+
+
+def f32_dgrad(dy, w, stride, pad, hi, wi, group):
+    mm = lambda A, B: rne_matmul(A, B, group)  # noqa: E731
+    return Ref(torch_dgrad(dy, w, stride, pad, hi, wi, torch.float64), torch_dgrad(np.abs(dy), np.abs(w), stride, pad, hi, wi, torch.float64),
+               torch_dgrad(dy, w, stride, pad, hi, wi, torch.float32), im2col_dgrad(dy, w, stride, pad, hi, wi, mm))
+
+
+def f32_wgrad(x, dy, k, stride, pad, group):
+    """K is the pixel axis."""
+    mm = lambda A, B: rne_matmul(A, B, group)  # noqa: E731
+    return Ref(torch_wgrad(x, dy, k, stride, pad, torch.float64), torch_wgrad(np.abs(x), np.abs(dy), k, stride, pad, torch.float64),
+               torch_wgrad(x, dy, k, stride, pad, torch.float32), im2col_wgrad(x, dy, k, stride, pad, mm))
+
+
+def f32_mutants(x, w, stride, pad, old=None):
+    """fwd_mutants plus the two an fp32-pipe kernel could hide behind a 1e-3 bar: the weights rounded to bf16 (a tail path that
+    stages one operand in bf16), and the lowest of the three split terms of x never multiplied (a split kernel without its low
+    term: about 2^-17 of the magnitude)."""
+    out = fwd_mutants(x, w, stride, pad, old)
+    add = 0.0 if old is None else np.asarray(old, dtype=F64)
+    out["bf16 operand"] = im2col_fwd(x, bf16_round(np.asarray(w, dtype=F32)), stride, pad) + add
+    out["low split term"] = im2col_fwd(x, w, stride, pad, lambda A, B: x3_exact(A, B, drop=((2, 0),))) + add
+    return out
+
+
+# -------------------------------------------------------------------------- the launchers' arithmetic, restated (fp32 pipe)
+def small_applicable(k, stride, pad, gathered, produced):
+    """csrc/conv_small.hip::small_conv_applicable: 3x3 / stride 1 / pad 1 and at most two 16-channel groups in all."""
+    return k == 3 and stride == 1 and pad == 1 and cdiv(gathered, 16) * cdiv(produced, 16) <= 2
+
+
+def small_symbol(gathered, produced, wgrad=False):
+    return "conv3x3_small_%skernel<%d, %d>" % ("wgrad_" if wgrad else "", cdiv(gathered, 16), cdiv(produced, 16))
+
+
+def small_blocks(n, h, w, per_cu):
+    """(tiles, blocks) of a small-kernel launch: 16 x 16 pixel tiles, at most 256 x per_cu blocks that loop over them (per_cu: 6 for
+    <1, 1> and <1, 2>, 3 for <2, 1>, 2 for the weight gradient)."""
+    tiles = n * cdiv(h, 16) * cdiv(w, 16)
+    return tiles, min(tiles, 256 * per_cu)
+
+
+def k_slices(m, produced, taps, plain):
+    """csrc/conv_igemm.hip::k_slices: a plain (no bias / activation / residual) single-class fp32 launch with fewer than 384 tiles of
+    64 x 64 splits its taps into two slices that add atomically."""
+    if not plain or taps < 2:
+        return 1
+    tiles = cdiv(m, 64) * cdiv(produced, 64)
+    if tiles >= 384:
+        return 1
+    return max(1, min((511 + tiles) // tiles, 2, taps))
+
+
+IGEMM_TILES = {1: (128, 128, 2, 2), 2: (128, 64, 2, 2), 3: (64, 64, 2, 2), 4: (128, 32, 4, 1)}
+
+
+def igemm_f32_tile(produced, override=0):
+    """launch_igemm's choice on the fp32 pipe: IGEMM_TILE, else 64 x 64 above 32 produced channels and 128 x 32 up to 32."""
+    return override if override else (3 if produced > 32 else 4)
+
+
+def igemm_f32_uniform(gathered, taps, generic, up_ca=0):
+    """finish_args for fp32: whole 32-element K tiles per tap, at most 32 taps in all classes together; GENERIC_GATHER does not
+    apply to the fused up-sample + concat input (which exists on the uniform loop only)."""
+    return not (generic and up_ca == 0) and gathered % 32 == 0 and up_ca % 32 == 0 and taps <= 32
+
+
+def igemm_f32_symbol(tile, uniform, up=False):
+    return "conv_igemm_kernel<%d, %d, %d, %d, false, %s, %s>" % (IGEMM_TILES[tile] + ("true" if uniform else "false", "true" if up else "false"))
+
+
+def wgrad_f32_tile(produced):
+    """conv2d_wgrad_impl on the fp32 pipe: (BMW, BNW, WAVES_M, WAVES_N)."""
+    return (64, 64, 2, 2) if produced > 32 else (32, 128, 1, 4)
+
+
+def wgrad_f32_plan(n, h, w, ci, co, k, stride, pad, blocks=0, generic=False, src_c=None, up=False):
+    """(symbol, splits, pixels per split, M) of launch_wgrad<...>(fp32): the gather is row-uniform when the output width is a
+    multiple of the 256 / (BNW / 4) rows one load pass covers; a 1x1 / stride 1 / pad 0 layer is rewritten as ONE row of M pixels."""
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    m = n * ho * wo
+    bmw, bnw, wm, wn = wgrad_f32_tile(co)
+    if k == 1 and stride == 1 and pad == 0 and not up:
+        wo = m
+    uniform = not generic and wo % (256 // (bnw // 4)) == 0
+    tiles = cdiv(co, bmw) * cdiv(k * k * (src_c or ci), bnw)
+    splits = max(1, min(cdiv(blocks if blocks >= 64 else 3072, tiles), cdiv(m, 256)))
+    kchunk = cdiv(cdiv(m, splits), 32) * 32
+    return "conv_wgrad_kernel<%d, %d, %d, %d, %s>" % (bmw, bnw, wm, wn, "true" if uniform else "false"), cdiv(m, kchunk), kchunk, m
+
+
+def bn_fold_ref(w, bias, gamma, beta, rm, rv, eps, dt):
+    """(w', b', |terms of b'|) of csrc/norm_act.hip::bn_fold_kernel in dtype dt: s = gamma / sqrt(rv + eps), w' = w s,
+    b' = beta + (bias - rm) s."""
+    g, v = np.asarray(gamma, dtype=dt), np.asarray(rv, dtype=dt)
+    s = (g / np.sqrt((v + dt(F32(eps))).astype(dt)).astype(dt)).astype(dt)      # eps reaches the kernel as an fp32 number
+    wf = (np.asarray(w, dtype=dt) * s.reshape((-1,) + (1,) * (np.ndim(w) - 1))).astype(dt)
+    b0 = np.zeros_like(g) if bias is None else np.asarray(bias, dtype=dt)
+    bf = (np.asarray(beta, dtype=dt) + ((b0 - np.asarray(rm, dtype=dt)).astype(dt) * s).astype(dt)).astype(dt)
+    mag = np.abs(np.asarray(beta, dtype=F64)) + (np.abs(b0.astype(F64)) + np.abs(np.asarray(rm, dtype=F64))) * np.abs(s.astype(F64))
+    return wf, bf, mag

@@ -550,3 +550,291 @@ def test_phase_kernels_tier_a_and_b(case):
         # one mis-signed group shows (at the 2 x 2 output most taps of a group fall outside a: some group, not each)
         negs = [c for c, neg in R.up_dgrad_steps(co) if neg]
         assert any((R.x3_exact(A, B, flip=np.concatenate(negs[i:i + 4])).reshape(shape) != b["r64"]).mean() >= 0.01 for i in range(0, len(negs), 4))
+
+
+# =========================================================== the fp32-pipe kernels (tests/test_gpu_conv_f32_grade.py, _conv_f32_cases.py)
+import _conv_f32_cases as C32  # noqa: E402
+
+
+def test_rne_matmul_on_hand_made_values():
+    h = 2.0 ** -24                                   # half an ulp of 1
+    ones = np.ones((3, 1))
+    # 1, h, h: one product per step both halves are ties that round to even (1); two per step the same; all in one step: exact
+    assert R.rne_matmul([[1.0, h, h]], ones, 1)[0, 0] == 1.0 and R.rne_matmul([[1.0, h, h]], ones, 2)[0, 0] == 1.0
+    assert R.rne_matmul([[1.0, h, h]], ones, 4)[0, 0] == F32(1.0 + 2 * h)
+    # the small terms first: their exact sum 2h enters in one rounding
+    assert R.rne_matmul([[h, h, 1.0]], ones, 2)[0, 0] == F32(1.0 + 2 * h) and R.rne_matmul([[h, 1.0, h]], ones, 2)[0, 0] == 1.0
+    # a tie above an odd mantissa rounds UP to the even neighbour; the products themselves are never rounded
+    assert R.rne_matmul([[1.0 + 2 * h, h]], np.ones((2, 1)), 1)[0, 0] == F32(1.0 + 4 * h)
+    a = float(F32(1.0 + 2 * h))
+    assert R.rne_matmul([[a, -1.0]], [[a], [1.0 + 4 * h]], 2)[0, 0] == F32(a * a - (1.0 + 4 * h)) == F32(4 * h * h)
+    rng = np.random.default_rng(21)
+    A, B = R.randn_f32(rng, (30, 37), binades=12), R.randn_f32(rng, (37, 5), binades=12)
+    ex, mag = A.astype(F64) @ B.astype(F64), np.abs(A).astype(F64) @ np.abs(B).astype(F64)
+    for g in (R.MFMA_32, R.MFMA_16):
+        got = R.rne_matmul(A, B, g)
+        assert got.dtype == F32 and rel(got, ex, mag) <= R.cdiv(37, g) * 2.0 ** -24
+    assert np.array_equal(R.rne_matmul(A, B, 64), ex.astype(F32))
+    assert not np.array_equal(R.rne_matmul(A, B, 2), R.rne_matmul(A, B, 4))              # the group is part of the model
+
+
+def parity_classes(h, w, k, s, p):
+    """(rows, columns, taps) of every parity class of a data gradient, as conv2d_dgrad_impl builds them."""
+    out = []
+    for ph in range(s):
+        for pw in range(s):
+            taps = sum((ph + p - r) % s == 0 for r in range(k)) * sum((pw + p - q) % s == 0 for q in range(k))
+            out.append(((h - ph + s - 1) // s, (w - pw + s - 1) // s, taps))
+    return out
+
+
+def test_the_f32_shapes_reach_every_launch_regime():
+    """small_conv_applicable, k_slices, the tile choice and the uniform / row_uniform conditions, restated in _conv_ref: every case of
+    _conv_f32_cases reaches the regime its comment claims."""
+    cd = R.cdiv
+    assert {c[5:] for c in C32.IG} == {(3, 1, 1), (3, 2, 1), (1, 2, 0), (4, 2, 1), (7, 2, 3), (5, 2, 2)}
+    for c in C32.IG:
+        n, h, w, ci, co, k, s, p = c
+        ho, wo = C32.out_hw(h, w, k, s, p)
+        m = n * ho * wo
+        assert not R.small_applicable(k, s, p, ci, co) and not R.small_applicable(k, s, p, co, ci)
+        assert R.k_slices(m, co, k * k, True) == (1 if k == 1 else 2) and R.k_slices(m, co, k * k, False) == 1       # plain: sliced atomics
+        assert m <= 128 * 192 and (s == 1 or k == 1 or sum(t for _, _, t in parity_classes(h, w, k, s, p)) == k * k)
+    # IG[0]: a full and a ragged row tile, a full and a ragged column tile at EVERY tile: fast and generic epilogue in one launch
+    n, h, w, ci, co = C32.IG[0][:5]
+    for bm, bn, _, _ in R.IGEMM_TILES.values():
+        assert (n * h * w) // bm >= 1 and (n * h * w) % bm and co // bn >= 1 and co % bn
+    # the two gather loops: ci = 32 switches with GENERIC_GATHER, ci = 40 and the 49-tap stem are generic whatever the switch
+    assert R.igemm_f32_uniform(32, 9, False) and not R.igemm_f32_uniform(32, 9, True) and not R.igemm_f32_uniform(40, 9, False)
+    assert R.igemm_f32_uniform(64, 9, False) and not R.igemm_f32_uniform(136, 9, False)          # the data gradients of IG[1], IG[0]
+    assert not R.igemm_f32_uniform(4, 49, False) and not R.igemm_f32_uniform(64, 49, False) and R.igemm_f32_uniform(32, 25, False)
+    assert R.igemm_f32_uniform(64, 1, False) and R.igemm_f32_uniform(32, 16, False)
+    assert any(c[4] % 32 for c in C32.IG) and any(c[4] <= 32 for c in C32.IG) and any(c[3] == 4 for c in C32.IG)
+    assert R.igemm_f32_tile(24) == 4 and R.igemm_f32_tile(40) == 3 and R.igemm_f32_tile(24, 1) == 1
+    assert R.igemm_f32_symbol(4, False) == "conv_igemm_kernel<128, 32, 4, 1, false, false, false>"
+    assert R.igemm_f32_symbol(1, True, up=True) == "conv_igemm_kernel<128, 128, 2, 2, false, true, true>"
+    # odd extents under stride 2: the parity classes differ in rows and columns; 1x1/2: one class has the tap, three are empty
+    assert len({(r, q) for r, q, _ in parity_classes(11, 17, 3, 2, 1)}) == 4 and len({(r, q) for r, q, _ in parity_classes(9, 13, 5, 2, 2)}) == 4
+    assert sorted(t for _, _, t in parity_classes(11, 17, 1, 2, 0)) == [0, 0, 0, 1]
+    # the unsliced plain store: >= 384 tiles of 64 x 64, whole tiles of the forced shape (the fast epilogue everywhere), uniform loop
+    for tile, (n, h, w, ci, co) in C32.LARGE.items():
+        bm, bn = R.IGEMM_TILES[tile][:2]
+        m = n * h * w
+        assert cd(m, 64) * cd(co, 64) >= 384 and R.k_slices(m, co, 9, True) == 1 and m % bm == 0 and co % bn == 0
+        assert R.igemm_f32_uniform(ci, 9, False) and not R.small_applicable(3, 1, 1, ci, co) and m * max(ci, co) <= 128 * 192 * 64
+    # conv2d_dgrad_bnreduce_ok, restated: heuristic tile, no K-slices, whole tiles (64 x 64 above 32 produced channels, else 128 x 32)
+    for n, h, w, ci, co in C32.BNR:
+        m = n * h * w
+        assert not R.small_applicable(3, 1, 1, co, ci) and R.k_slices(m, ci, 9, True) == 1 and R.igemm_f32_uniform(co, 9, False)
+        assert (m % 64 == 0 and ci % 64 == 0) if ci > 32 else (m % 128 == 0 and ci % 32 == 0)
+    assert {R.igemm_f32_tile(c[3]) for c in C32.BNR} == {3, 4}
+    n, h, w, ci, co, split = C32.SPLIT
+    assert all(split % bn == 0 for _, bn, _, _ in R.IGEMM_TILES.values()) and 0 < split < ci and R.k_slices(n * h * w, ci, 9, True) == 2
+    assert not R.small_applicable(3, 1, 1, co, ci) and R.igemm_f32_uniform(co, 9, False) and not R.igemm_f32_uniform(co, 9, True)
+    for n, h, w, ca, cs, co in C32.UPCAT:
+        assert R.igemm_f32_uniform(ca + cs, 9, True, up_ca=ca) and not R.small_applicable(3, 1, 1, ca + cs, co) and h % 2 == 0 and w % 2 == 0
+    assert {c[4] for c in C32.UPCAT} == {0, 32}
+    # the small kernels: all three instantiations in both directions, partial tiles, a partial K group, one-pixel width, and both block regimes
+    assert {R.small_symbol(g, p) for _, _, _, g, p in C32.SM} == {"conv3x3_small_kernel<%s>" % t for t in ("1, 1", "2, 1", "1, 2")}
+    assert R.small_symbol(8, 24, wgrad=True) == "conv3x3_small_wgrad_kernel<1, 2>"
+    for n, h, w, g, p in C32.SM:
+        assert R.small_applicable(3, 1, 1, g, p) and R.small_applicable(3, 1, 1, p, g)
+    assert any(g == 8 for _, _, _, g, _ in C32.SM) and any(p == 24 for *_, p in C32.SM) and any(w == 1 for _, _, w, _, _ in C32.SM)
+    assert any(h % 16 and w % 16 and h > 16 and w > 16 and C32.sm_up(c) for c in C32.SM for _, h, w, _, _ in [c])
+    for sym, per_cu in (("1, 1", 6), ("1, 2", 6), ("2, 1", 3)):
+        mine = [R.small_blocks(n, h, w, per_cu) for n, h, w, g, p in C32.SM if R.small_symbol(g, p).endswith("<%s>" % sym)]
+        assert any(t > b for t, b in mine) and any(t == b and t < 256 for t, b in mine), sym          # several tiles per block; fewer tiles than blocks
+    assert all(R.small_blocks(n, h, w, 2)[0] > R.small_blocks(n, h, w, 2)[1] == 512 for n, h, w, _, _ in C32.SM[9:])      # the weight gradient's 512 blocks
+    # conv_wgrad_kernel: both tiles under both gathers, one split / many splits / a split ending inside an image, the 1x1 rewrite
+    plan = R.wgrad_f32_plan
+    for case, blocks in C32.WG:
+        assert not R.small_applicable(case[5], case[6], case[7], case[3], case[4])
+        assert plan(*case, generic=True)[0].endswith("false>")
+    syms = {plan(*case, blocks=b, generic=g)[0] for case, bl in C32.WG for b in bl for g in (False, True)}
+    assert syms == {"conv_wgrad_kernel<64, 64, 2, 2, %s>" % u for u in ("true", "false")} | {"conv_wgrad_kernel<32, 128, 1, 4, %s>" % u for u in ("true", "false")}
+    big = C32.WG[0][0]
+    assert [plan(*big, blocks=b)[1:] for b in (0, 64, 4096)] == [(12, 256, 3072), (6, 512, 3072), (12, 256, 3072)]
+    assert plan(*C32.WG[2][0])[1] == 1 and plan(*C32.WG[3][0])[1] == 1 and plan(*C32.WG[1][0])[1] == 12
+    sp, chunk, m = plan(*C32.WG[4][0])[1:]
+    assert (sp, chunk, m) == (2, 256, 480) and chunk % (10 * 16) != 0                       # the first split ends inside the second image
+    assert plan(*C32.WG[5][0])[0].endswith("true>") and plan(*C32.WG[6][0])[0].endswith("false>") and C32.WG[5][0][5:] == (7, 2, 3)
+    assert plan(*C32.WG[7][0])[0] == "conv_wgrad_kernel<64, 64, 2, 2, true>" and C32.WG[7][0][2] % 16 != 0      # row-uniform through a.wo = M only
+    assert plan(*C32.WG[8][0])[0] == "conv_wgrad_kernel<32, 128, 1, 4, true>" and plan(*C32.WG[9][0])[0].endswith("true>") and C32.WG[9][0][6] == 2
+    for n, h, w, ca, cs, co in C32.WG_PART:
+        geom = (n, h, w, ca + cs, co, 3, 1, 1)
+        assert plan(*geom, src_c=ca, up=True)[0].endswith("true>") and plan(*geom, src_c=cs)[0].endswith("true>") and ca % 4 == 0 and cs % 4 == 0
+    assert {R.wgrad_f32_tile(c[5])[0] for c in C32.WG_PART} == {64, 32}
+
+
+ALL7 = sorted(ALL5 + ["bf16 operand", "low split term"])
+# What tier A can and cannot see of a dropped low split term: it perturbs every product by at most 2^-17 of itself with a random sign,
+# so over K products the worst element of the output is off by about 4 x 2^-18 / sqrt(K) of its magnitude -- about 1e-6 at K = 256, the
+# size of the bar, and BELOW the rounding noise of any correct fp32 accumulation beyond that (measured on the float64 mutant: 1.0e-6
+# at K = 288, 3e-7 at K = 3072).  Tier A must reject it wherever the longest sum has at most LOW_TERM_K products; at every K tier B
+# catches it exactly: check_tier_b / check_wgrad_tier_b prove that product (2, 0) alone changes >= 1 % of the outputs bit for bit.
+LOW_TERM_K = 256
+
+
+def f32_expect(mutants, k_terms):
+    if k_terms > LOW_TERM_K:
+        mutants.pop("low split term")
+    return mutants
+F32_BAR = 2e-6                            # "an fp32-grade bar": both legs are a few 1e-7, x 4
+
+
+@pytest.mark.parametrize("case", C32.IG, ids=[C32.ig_id(c) for c in C32.IG])
+def test_f32_igemm_tier_a_and_b(case):
+    n, h, w, ci, co, k, s, p = case
+    o = C32.ig_tier_a(case)
+    A, d_rne, d_mfma = R.bar(o["fwd"])
+    wide = 2.0 if case in C32.IG_BINADES else 1.0          # (over 12 binades single terms dominate some elements: the legs' worst element is worse)
+    assert R.FLOOR <= A <= wide * F32_BAR and 0 < d_rne < wide * 5e-7 and 0 < d_mfma < wide * 5e-7
+    got = reject_all(R.epilogue(o["fwd"], old=o["old"]), f32_expect(R.f32_mutants(o["x"], o["wt"], s, p, o["old"]), k * k * ci), "forward")
+    assert got == [m for m in ALL7 if (k > 1 or m != "border tap") and (k * k * ci <= LOW_TERM_K or m != "low split term")]
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wt"], s, p, h, w)
+    md = f32_expect(R.f32_mutants(d, wf, 1, pads, o["oldx"]), max(t for _, _, t in parity_classes(h, w, k, s, p)) * co)
+    if s > 1:
+        md.pop("border tap", None)           # (the dilated dy of a strided layer has zero columns: that mutant may change nothing)
+    reject_all(R.epilogue(o["dgrad"], old=o["oldx"]), md, "data gradient")
+    s1, s2 = R.stats_ref(o["fwd"])
+    l = o["fwd"].leg_rne.reshape(-1, co).astype(F64)
+    assert R.verdict(l.sum(0), s1, False)[0] and R.verdict((l * l).sum(0), s2, False)[0]
+    for family in C32.FAMILIES:
+        f, b = C32.ig_tier_b(case, family)
+        check_tier_b(f, family, None, pad=p, stride=s)
+        check_tier_b(b, family, None, dgrad_to=(h, w), pad=p, stride=s)
+        assert np.abs(f["bias"]).max() <= 1 and np.abs(f["res"]).max() <= 1 and f["res"].shape == f["r64"].shape
+    f = C32.ig_tier_b(case, "x3w1")[0]         # a bf16-rounded x shows in tier B as well
+    assert (R.im2col_fwd(R.bf16_round(f["x"]), f["w"], s, p) != f["r64"]).mean() >= 0.01
+
+
+def test_f32_other_igemm_cases_tier_a_and_b():
+    """The unsliced shape of tile 4 (the smallest of LARGE), the split and the fused decoder input."""
+    shape = C32.LARGE[4]
+    o = C32.large_tier_a(shape)
+    assert R.bar(o["fwd"])[0] <= F32_BAR
+    assert reject_all(o["fwd"], f32_expect(R.f32_mutants(o["x"], o["wt"], 1, 1), 9 * shape[3]), "unsliced forward") == [m for m in ALL7 if m not in ("old twice", "low split term")]
+    n, h, w, ci, co, split = C32.SPLIT
+    o = C32.split_tier_a()
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wt"], 1, 1, h, w)
+    m = f32_expect(R.f32_mutants(d, wf, 1, pads), 9 * co)
+    swapped = R.im2col_fwd(d, wf, 1, pads)
+    m["halves swapped"] = np.concatenate([swapped[..., ci - split:], swapped[..., :ci - split]], axis=3)
+    reject_all(o["dgrad"], m, "split data gradient")
+    for case in C32.UPCAT:
+        o = C32.upcat_tier_a(case)
+        cat = R.upcat(o["a"], o["skip"])
+        m = f32_expect(R.f32_mutants(cat, o["wt"], 1, 1), 9 * cat.shape[3])
+        m["up-sampling off by one column"] = R.im2col_fwd(np.roll(cat, 1, axis=2), o["wt"], 1, 1)
+        reject_all(o["fwd"], m, "fused decoder input")
+    for family in C32.FAMILIES:
+        t = C32.large_tier_b(shape, family)       # (the window and the representability; the per-product proofs run at the small shapes)
+        assert float(t["mag"].max()) / R.FAMILIES[family][2] <= 2.0 ** 23 and np.array_equal(t["r64"].astype(F32).astype(F64), t["r64"])
+        assert (t["r64"] != 0).mean() >= 0.05
+        check_tier_b(C32.split_tier_b(family), family, None, dgrad_to=(h, w))
+        for case in C32.UPCAT:
+            t = C32.upcat_tier_b(case, family)
+            check_tier_b(t, family, None)
+            assert np.array_equal(t["xin"], R.upcat(t["a"], t["skip"]))
+    for case in C32.BNR:
+        assert case[0] * case[1] * case[2] * max(case[3:]) <= 128 * 192 * 64
+    o = C32.bnr_tier_a(C32.BNR[1])
+    s1, s2, margin = R.bn_sums_ref(o["dgrad"], o["prev_y"], o["mean"], o["rstd"], o["gamma"], o["beta"], SLOPE_)
+    assert margin > 1e-4 and R.verdict(s1.leg_rne, s1, False)[0] and R.verdict(s2.leg_rne, s2, False)[0]
+
+
+def f32_wgrad_mutants(x, dy, k, s, p, old):
+    m = wgrad_mutants(x, dy, k, s, p, old)
+    add = np.asarray(old, dtype=F64)
+    m["bf16 operand"] = R.im2col_wgrad(x, R.bf16_round(np.asarray(dy, dtype=F32)), k, s, p) + add
+    m["low split term"] = R.im2col_wgrad(x, dy, k, s, p, lambda A, B: R.x3_exact(A, B, drop=((2, 0),))) + add
+    return m
+
+
+SM_HOST = [C32.SM[0], C32.SM[1], C32.SM[3], C32.SM[7]]      # <1, 1>, <1, 2> over 12 binades, <2, 1>, one pixel wide (the many-tile shapes draw
+                                                            # from the same generators; what they add is the block loop, proven above)
+
+
+@pytest.mark.parametrize("case", SM_HOST, ids=[C32.sm_id(c) for c in SM_HOST])
+def test_f32_small_tier_a_and_b(case):
+    n, h, w, g, p = case
+    o = C32.sm_tier_a(case)
+    wide = 2.0 if case in C32.SM_BINADES else 1.0
+    assert R.bar(o["fwd"])[0] <= wide * F32_BAR and R.bar(o["wgrad"])[0] <= wide * F32_BAR
+    m = f32_expect(R.f32_mutants(o["x"], o["wt"], 1, 1, o["old"]), 9 * g)
+    d, wf, pads = R.dgrad_as_forward(o["dy"], o["wd"], 1, 1, h, w)
+    md = f32_expect(R.f32_mutants(d, wf, 1, pads, o["old"]), 9 * g)
+    mw = f32_expect(f32_wgrad_mutants(o["x"], o["dyw"], 3, 1, 1, o["oldw"]), n * h * w)
+    if w == 1:                               # (the tap one column to the left of the only column reads padding)
+        m.pop("border tap"), md.pop("border tap"), mw.pop("border tap")
+    reject_all(R.epilogue(o["fwd"], old=o["old"]), m, "forward")
+    reject_all(R.epilogue(o["dgrad"], old=o["old"]), md, "flipped launch")
+    reject_all(R.epilogue(o["wgrad"], old=o["oldw"]), mw, "weight gradient")
+    mz = f32_expect(f32_wgrad_mutants(o["z"], o["dyw"], 3, 1, 1, o["oldw"]), n * h * w)
+    mz["transform skipped"] = R.im2col_wgrad(o["y_prev"], o["dyw"], 3, 1, 1) + o["oldw"]
+    if w == 1:
+        mz.pop("border tap")
+    reject_all(R.epilogue(o["wgrad_z"], old=o["oldw"]), mz, "weight gradient behind the transform")
+    if C32.sm_up(case):
+        up = R.upcat(o["a"], None)
+        mu = f32_expect(R.f32_mutants(up, o["wt"], 1, 1), 9 * g)
+        mu["up-sampling off by one column"] = R.im2col_fwd(np.roll(up, 1, axis=2), o["wt"], 1, 1)
+        reject_all(o["fwd_up"], mu, "up-sampled source")
+        reject_all(o["wgrad_zup"], {"not up-sampled": R.im2col_wgrad(o["z"], o["dyw"], 3, 1, 1)}, "weight gradient behind the up-sampling")
+    for family in C32.FAMILIES:
+        t = C32.sm_tier_b(case, family)
+        check_tier_b(t["fwd"], family, None)
+        check_tier_b(t["dgrad"], family, None, dgrad_to=(h, w))
+        check_wgrad_tier_b(t["wgrad"], family)
+        check_wgrad_tier_b(t["wgrad_z"], family)
+        if C32.sm_up(case):
+            check_tier_b(t["fwd_up"], family, None)
+            check_wgrad_tier_b(t["wgrad_up"], family)
+            assert np.array_equal(t["fwd_up"]["xin"], R.upcat(t["fwd_up"]["a"], None))
+
+
+WG_HOST = [C32.WG[i][0] for i in (0, 1, 2, 5, 7, 9)]      # both tiles, one split (144 pixels: the low split term shows), the stem, 1x1/1, stride 2
+
+
+@pytest.mark.parametrize("case", WG_HOST, ids=[C32.ig_id(c) for c in WG_HOST])
+def test_f32_wgrad_tier_a_and_b(case):
+    n, h, w, ci, co, k, s, p = case
+    o = C32.wg_tier_a(case)
+    assert R.bar(o["wgrad"])[0] <= F32_BAR
+    pixels = R.wgrad_f32_plan(*case)[3]
+    got = reject_all(R.epilogue(o["wgrad"], old=o["oldw"]), f32_expect(f32_wgrad_mutants(o["x"], o["dy"], k, s, p, o["oldw"]), pixels), "weight gradient")
+    assert ("low split term" in got) == (pixels <= LOW_TERM_K) and "bf16 operand" in got
+    for family in C32.FAMILIES:
+        check_wgrad_tier_b(C32.wg_tier_b(case, family), family)
+
+
+def test_f32_wgrad_part_and_fused_x3_and_bn_fold_references():
+    case = C32.WG_PART[0]
+    n, h, w, ca, cs, co = case
+    o = C32.part_tier_a(case)
+    m = f32_expect(f32_wgrad_mutants(o["x"], o["dy"], 3, 1, 1, o["oldw"]), n * h * w)
+    only_up = R.im2col_wgrad(R.upcat(o["a"], np.zeros_like(o["skip"])), o["dy"], 3, 1, 1) + o["oldw"]
+    m["skip half missing"] = only_up
+    reject_all(R.epilogue(o["wgrad"], old=o["oldw"]), m, "channel slices")
+    for family in C32.FAMILIES:
+        t = C32.part_tier_b(case, family)
+        check_wgrad_tier_b(t, family)
+        assert np.array_equal(t["xin"], R.upcat(t["a"], t["skip"]))
+        f = C32.x3_fused_tier_b(family)
+        check_tier_b(f, family, None)
+        assert np.abs(f["bias"]).max() + np.abs(f["res"]).max() <= 2
+    o = C32.x3_fused_tier_a()
+    n, h, w, ci, co, k, s, p = C32.X3_FUSED
+    ref = R.epilogue(o["fwd"], bias=o["bias"], residual=o["res"], slope=0.0)
+    assert R.verdict(ref.leg_rne, ref, False)[0] and not R.verdict(R.epilogue(o["fwd"], bias=o["bias"], slope=0.0).r64, ref, False)[0]
+    # bn_fold: the float64 restatement is the definition; the fp32 restatement stays within a few ulp of it at every variance scale
+    import _norm_ref as N
+    for case in C32.BN_FOLD:
+        b = C32.bn_fold_operands(case)
+        args = (b["w"], b["bias"], b["gamma"], b["beta"], b["rm"], b["rv"], C32.BN_EPS)
+        w64, b64, mag = R.bn_fold_ref(*args, F64)
+        w32, b32, _ = R.bn_fold_ref(*args, F32)
+        s = b["gamma"].astype(F64) / np.sqrt(b["rv"].astype(F64) + F64(F32(C32.BN_EPS)))
+        assert np.allclose(w64, b["w"] * s[:, None, None, None], rtol=1e-14) and np.allclose(b64, b["beta"] + (b["bias"].astype(F64) - b["rm"]) * s, rtol=1e-12, atol=1e-14)
+        assert N.bar(w32, w64, np.abs(w64))[0] <= 2.0 ** -20 and N.bar(b32, b64, mag)[0] <= 2.0 ** -20 and w32.dtype == F32
+    assert {c[0] for c in C32.BN_FOLD} == {4, 24, 64}
