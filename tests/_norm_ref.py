@@ -1,5 +1,5 @@
 """numpy restatement of the streaming kernels every training step runs: training- and eval-mode BatchNorm with its fused
-activation / residual add and their backward (csrc/norm_act.hip, bf16 storage: csrc/elem_bf16.hip), ``act_bwd``,
+activation / residual add and their backward (csrc/norm_act.hip, both storages from one body per kernel), ``act_bwd``,
 ``channel_sum``, ``bn_finalize`` and Adam (csrc/optim.hip).
 
 Test infrastructure, in the manner of ``_resize_ref`` / ``_clahe_ref``: the per-element arithmetic is written once, generically

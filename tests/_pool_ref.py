@@ -1,6 +1,6 @@
 """numpy restatement of the glue between the convolutions, NHWC: max_pool2d(3, 2, 1) with its stored tap bytes and its backward,
-nearest and bilinear x2 up-sampling + concat with their backward, the NCHW -> NHWC layout pass (csrc/pool_resize.hip, the bf16 twins in
-csrc/elem_bf16.hip, csrc/bilinear.hip), the launch arithmetic of those files, the cases tests/test_gpu_pool_grade.py runs and the
+nearest and bilinear x2 up-sampling + concat with their backward, the NCHW -> NHWC layout pass (csrc/pool_resize.hip in both storages,
+csrc/bilinear.hip; the bf16 cast: csrc/elem_bf16.hip), the launch arithmetic of those files, the cases tests/test_gpu_pool_grade.py runs and the
 mutants tests/test_pool_ref_host.py shows those cases to reject.
 
 Test infrastructure in the manner of ``_norm_ref``: sums are written once, generically over the float type ``elem`` -- ``np.float64``
@@ -209,7 +209,7 @@ CAP, CAP_ITEMS, ROWS_CAP, BLOCK = 4096, 8192, 65535, 256
 
 
 def grid_for(items, per_thread=2):
-    """Blocks of csrc/pool_resize.hip grid_for and csrc/elem_bf16.hip grid_for8 (the same arithmetic)."""
+    """Blocks of csrc/common.h grid_for, which both storages launch with (grid_for8: the name the bf16 cases use here)."""
     return max(min((items + BLOCK * per_thread - 1) // (BLOCK * per_thread), CAP), 1)
 
 

@@ -1,5 +1,5 @@
 """The streaming kernels of every training step -- BatchNorm forward / backward with its fused activation and residual add
-(csrc/norm_act.hip, bf16 storage: csrc/elem_bf16.hip), act_bwd, channel_sum, the accumulate flags of the pooling / up-sampling
+(csrc/norm_act.hip, both storages from one body per kernel), act_bwd, channel_sum, the accumulate flags of the pooling / up-sampling
 backward (csrc/pool_resize.hip) and Adam (csrc/optim.hip) -- against the float64 restatement of tests/_norm_ref.py
 (proven against torch's double-precision autograd by tests/test_norm_ref_host.py).
 

@@ -1,6 +1,6 @@
 """The glue between the convolutions -- max pool forward / backward with its stored tap bytes, nearest and bilinear x2 up-sampling +
-concat forward / backward, nchw_to_nhwc, the bf16 cast, fill / axpy / scale / add_i64 (csrc/pool_resize.hip, their bf16 twins in
-csrc/elem_bf16.hip, csrc/bilinear.hip) -- element by element against the float64 restatement of tests/_pool_ref.py, which
+concat forward / backward, nchw_to_nhwc, the bf16 cast, fill / axpy / scale / add_i64 (csrc/pool_resize.hip in both storages,
+csrc/bilinear.hip; the cast: csrc/elem_bf16.hip) -- element by element against the float64 restatement of tests/_pool_ref.py, which
 tests/test_pool_ref_host.py proves against torch's float64 CPU results and shows to reject every mutant through the checks made here.
 
 Two tiers.  EXACT: operands are integers in [-128, 128] (bf16-representable; the pools draw from five values so that maxima tie),

@@ -8,46 +8,9 @@
 // row oy is oy/2 - 0.25 clamped at 0, so every output is a fixed 0.75 / 0.25 blend of two neighbouring rows and columns
 // (edges clamp):   out[2k] = 0.25 in[max(k-1, 0)] + 0.75 in[k],   out[2k+1] = 0.75 in[k] + 0.25 in[min(k+1, h-1)].
 // Backward is in gather form (each input pixel sums its <= 4x4 dependants with the transposed weights): no atomics.
-#include "common.h"
+#include "vec16.h"
 
 namespace udaseg {
-
-template <bool BF>
-struct Vec16 {   // one 16-byte vector: 4 fp32 or 8 bf16 channels, widened to fp32 for arithmetic
-  static constexpr int N = BF ? 8 : 4;
-  float v[N];
-  __device__ __forceinline__ static Vec16 load(const void* base, int64_t idx) {
-    Vec16 r;
-    const f32x4 raw = static_cast<const f32x4*>(base)[idx];
-    if constexpr (BF) {
-      const unsigned* u = reinterpret_cast<const unsigned*>(&raw);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        r.v[2 * i] = __builtin_bit_cast(float, u[i] << 16);
-        r.v[2 * i + 1] = __builtin_bit_cast(float, u[i] & 0xffff0000u);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) r.v[i] = raw[i];
-    }
-    return r;
-  }
-  __device__ __forceinline__ void store(void* base, int64_t idx) const {
-    f32x4 raw;
-    if constexpr (BF) {
-      unsigned* u = reinterpret_cast<unsigned*>(&raw);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const __bf16 lo = (__bf16)v[2 * i], hi = (__bf16)v[2 * i + 1];     // round to nearest even
-        u[i] = (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) raw[i] = v[i];
-    }
-    static_cast<f32x4*>(base)[idx] = raw;
-  }
-};
 
 // source rows / columns and the weight of the SECOND one for output index o of a length-2*len axis
 __device__ __forceinline__ void bilinear_src(int o, int len, int& i0, int& i1, float& l1) {
@@ -143,25 +106,6 @@ __global__ void bilinear_upcat_bwd_a_kernel(const void* __restrict__ dout, void*
   }
 }
 
-template <bool BF>
-__global__ void upcat_bwd_skip_any_kernel(const void* __restrict__ dout, void* __restrict__ dskip, int64_t pixels, int caq,
-                                          int cbq, int accumulate) {
-  const int ctq = caq + cbq;
-  const int64_t total = pixels * cbq;
-  const int64_t T = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += T) {
-    const int q = (int)(i % cbq);
-    const int64_t p = i / cbq;
-    Vec16<BF> g = Vec16<BF>::load(dout, p * ctq + caq + q);
-    if (accumulate) {
-      const Vec16<BF> old = Vec16<BF>::load(dskip, i);
-#pragma unroll
-      for (int e = 0; e < Vec16<BF>::N; ++e) g.v[e] += old.v[e];
-    }
-    g.store(dskip, i);
-  }
-}
-
 static inline int grid_items(int64_t items) {
   int64_t g = (items + 255) / 256;
   if (g > 8192) g = 8192;
@@ -207,12 +151,7 @@ extern "C" int udaseg_upsample2x_bilinear_concat_bwd(const void* dout, void* da,
   }
   if (dskip && cb > 0) {
     const int64_t pixels = (int64_t)n * 4 * h * w;
-    if (bf16)
-      hipLaunchKernelGGL(upcat_bwd_skip_any_kernel<true>, dim3(grid_items(pixels * (cb / g))), dim3(256), 0, st, dout, dskip,
-                         pixels, ca / g, cb / g, accumulate_dskip);
-    else
-      hipLaunchKernelGGL(upcat_bwd_skip_any_kernel<false>, dim3(grid_items(pixels * (cb / g))), dim3(256), 0, st, dout, dskip,
-                         pixels, ca / g, cb / g, accumulate_dskip);
+    launch_upcat_bwd_skip(bf16 != 0, grid_items(pixels * (cb / g)), dout, dskip, pixels, ca / g, cb / g, accumulate_dskip, st);
     UDASEG_LAUNCH_CHECK("upsample2x_bilinear_concat_bwd(skip) launch");
   }
   return UDASEG_OK;

@@ -37,6 +37,13 @@ static inline int capped_grid(int64_t items, int per_block, int cap) {
   const int64_t g = cdiv64(items, per_block);
   return (int)(g > cap ? cap : g);
 }
+// blocks of 256 threads with per_thread items each, at most 4096 (the flat grid-stride kernels of both storages)
+static inline int grid_for(int64_t items, int per_thread = 2) {
+  int64_t g = (items + 256LL * per_thread - 1) / (256LL * per_thread);
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (int)g;
+}
 // bin counts of the device histograms (curves.hip, pseudo.hip): their finish kernels give each of 256 threads bins / 256 bins
 static inline bool hist_bins_supported(int bins) { return bins == 256 || bins == 512 || bins == 1024 || bins == 2048 || bins == 4096; }
 
@@ -251,6 +258,11 @@ bool small_wgrad_applicable(int k, int stride, int pad, int ci, int co, int ntil
 int launch_small_wgrad(const float* x, const float* dy, float* dw, int n, int h, int wd, int ci, int co, int accumulate,
                        hipStream_t s, int up = 0, const float* in_scale = nullptr, const float* in_shift = nullptr,
                        int in_act = 0, float in_slope = 0.f);
+
+// the skip half of an up-sample + concat backward (pool_resize.hip; nearest and bilinear share it): dskip (+)= dout[.., caq ..]
+// over `pixels` output pixels, channel counts in 16-byte vectors; the caller chooses the grid and checks the launch
+void launch_upcat_bwd_skip(bool bf16, int grid, const void* dout, void* dskip, int64_t pixels, int caq, int cbq, int accumulate,
+                           hipStream_t s);
 
 // live launch timing (bench.py roofline leg): per API call (prof_*) and per kernel launch (kprof_*).  The launchers keep their
 // kernel id / "attribute set" flags in function-local std::atomic statics: launches come from two host threads' streams, a racing

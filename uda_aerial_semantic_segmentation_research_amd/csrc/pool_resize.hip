@@ -1,45 +1,52 @@
-// Layout, pooling and resize glue of the encoder-decoder, NHWC fp32 (gfx950).  All HBM-bound streams.
+// Layout, pooling and resize glue of the encoder-decoder, NHWC in fp32 or bf16 storage (gfx950).  All HBM-bound streams over
+// 16-byte vectors (Vec16<BF>: 4 fp32 or 8 bf16 channels); where the two storages run the same algorithm the kernel is written
+// once and instantiated by both extern "C" entry points.
 //
 // Replaces, inside smp.Unet.forward / autograd (reference src/models/train.py:341,343):
 //   max_pool2d(3,2,1) of the ResNet stem, F.interpolate(scale_factor=2, mode='nearest') + torch.cat([up, skip], 1)
 //   of every decoder block (trace fixture: 5 upsample_nearest2d, 4 cat, order [upsampled, skip]),
 // and the NCHW batch the DataLoader hands over (train.py:337).
-#include "common.h"
+#include "vec16.h"
 
 namespace udaseg {
 
-__global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int c, int64_t hw, int cpad,
+template <bool BF>
+__global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, f32x4* __restrict__ y, int c, int64_t hw, int cq,
                                     int64_t total_pix) {
-  // one thread per pixel: c strided plane reads (coalesced across lanes), one contiguous cpad-float write
+  // one thread per pixel: c strided plane reads (coalesced across lanes), one contiguous write of cq 16-byte vectors
+  constexpr int N = Vec16<BF>::N;
   const int64_t T = (int64_t)gridDim.x * blockDim.x;
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total_pix; p += T) {
     const int64_t n = p / hw, s = p - n * hw;
     const float* src = x + n * c * hw + s;
-    float* dst = y + p * cpad;
-    for (int k = 0; k < cpad; k += 4) {
-      f32x4 v;
+    for (int k = 0; k < cq; ++k) {
+      Vec16<BF> v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (k + e) < c ? src[(int64_t)(k + e) * hw] : 0.f;
-      *reinterpret_cast<f32x4*>(dst + k) = v;
+      for (int e = 0; e < N; ++e) v.v[e] = (k * N + e) < c ? src[(int64_t)(k * N + e) * hw] : 0.f;
+      y[p * cq + k] = v.raw();
     }
   }
 }
 
-// max_pool2d(kernel 3, stride 2, pad 1).  idx = first maximal tap in row-major window order (torch CPU kernel's rule:
-// update on (val > max) || isnan(val)).
+// max_pool2d(kernel 3, stride 2, pad 1).  idx (one byte per channel) = first maximal tap in row-major window order (torch CPU
+// kernel's rule: update on (val > max) || isnan(val)).
+template <bool BF>
 __global__ void maxpool_fwd_kernel(const f32x4* __restrict__ x, f32x4* __restrict__ y, uint32_t* __restrict__ idx, int n,
-                                   int h, int w, int c4, int ho, int wo) {
-  const int64_t total = (int64_t)n * ho * wo * c4;
+                                   int h, int w, int cq, int ho, int wo) {
+  constexpr int N = Vec16<BF>::N;
+  const int64_t total = (int64_t)n * ho * wo * cq;
   const int64_t T = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += T) {
-    const int q = (int)(i % c4);
-    int64_t r = i / c4;
+    const int q = (int)(i % cq);
+    int64_t r = i / cq;
     const int ox = (int)(r % wo);
     r /= wo;
     const int oy = (int)(r % ho);
     const int ni = (int)(r / ho);
-    f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    uint32_t bi[4] = {0, 0, 0, 0};
+    // set by the first tap in bounds (the window's centre row and column always are).  A plain array, widened into a Vec16 only
+    // for the store: as a Vec16 the bf16 kernel took 8 more VGPRs and 9 % more instructions.
+    float best[N];
+    uint32_t bi[N];
     bool first = true;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
@@ -49,19 +56,24 @@ __global__ void maxpool_fwd_kernel(const f32x4* __restrict__ x, f32x4* __restric
       for (int kx = 0; kx < 3; ++kx) {
         const int ix = ox * 2 - 1 + kx;
         if ((unsigned)ix >= (unsigned)w) continue;
-        const f32x4 v = x[((int64_t)(ni * h + iy) * w + ix) * c4 + q];
+        const Vec16<BF> v = Vec16<BF>::from(x[((int64_t)(ni * h + iy) * w + ix) * cq + q]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (first || v[e] > best[e] || v[e] != v[e]) {
-            best[e] = v[e];
+        for (int e = 0; e < N; ++e) {
+          if (first || v.v[e] > best[e] || v.v[e] != v.v[e]) {
+            best[e] = v.v[e];
             bi[e] = (uint32_t)(ky * 3 + kx);
           }
         }
         first = false;
       }
     }
-    y[i] = best;
-    idx[i] = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+    Vec16<BF> o;
+#pragma unroll
+    for (int e = 0; e < N; ++e) o.v[e] = best[e];
+    y[i] = o.raw();
+    const uint32_t lo = bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24);
+    if constexpr (BF) reinterpret_cast<uint2*>(idx)[i] = make_uint2(lo, bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24));
+    else idx[i] = lo;
   }
 }
 
@@ -146,18 +158,104 @@ __global__ void upcat_bwd_a_kernel(const f32x4* __restrict__ dout, f32x4* __rest
   }
 }
 
-__global__ void upcat_bwd_skip_kernel(const f32x4* __restrict__ dout, f32x4* __restrict__ dskip, int64_t pixels, int ca4,
-                                      int cb4, int accumulate) {
-  const int ct4 = ca4 + cb4;
-  const int64_t total = pixels * cb4;
+// The bf16 storage runs maxpool_bwd and upcat_bwd_a in the flat 64-bit-index form; the fp32 row-grid form above is the known-faster one.
+__global__ void maxpool_bwd_bf16_kernel(const f32x4* __restrict__ dy, const uint2* __restrict__ idx, f32x4* __restrict__ dx,
+                                        int n, int h, int w, int c8, int ho, int wo, int accumulate) {
+  const int64_t total = (int64_t)n * h * w * c8;
   const int64_t T = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += T) {
-    const int q = (int)(i % cb4);
-    const int64_t p = i / cb4;
-    f32x4 g = dout[p * ct4 + ca4 + q];
-    if (accumulate) g += dskip[i];
-    dskip[i] = g;
+    const int q = (int)(i % c8);
+    int64_t r = i / c8;
+    const int ix = (int)(r % w);
+    r /= w;
+    const int iy = (int)(r % h);
+    const int ni = (int)(r / h);
+    float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // a plain array, as in maxpool_fwd_kernel: as a Vec16 the kernel ran 6 % slower
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int ty = iy + 1 - ky;
+      if (ty < 0 || (ty & 1)) continue;
+      const int oy = ty >> 1;
+      if (oy >= ho) continue;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int tx = ix + 1 - kx;
+        if (tx < 0 || (tx & 1)) continue;
+        const int ox = tx >> 1;
+        if (ox >= wo) continue;
+        const int64_t o = ((int64_t)(ni * ho + oy) * wo + ox) * c8 + q;
+        const uint2 id = idx[o];
+        const Vec16<true> d = Vec16<true>::from(dy[o]);
+        const uint32_t me = (uint32_t)(ky * 3 + kx);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const uint32_t word = e < 4 ? id.x : id.y;
+          if (((word >> (8 * (e & 3))) & 0xffu) == me) g[e] += d.v[e];
+        }
+      }
+    }
+    if (accumulate) {
+      const Vec16<true> old = Vec16<true>::from(dx[i]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += old.v[e];
+    }
+    Vec16<true> o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.v[e] = g[e];
+    dx[i] = o.raw();
   }
+}
+
+__global__ void upcat_bwd_a_bf16_kernel(const f32x4* __restrict__ dout, f32x4* __restrict__ da, int n, int h, int w, int ca8,
+                                        int ct8, int accumulate) {
+  const int W = 2 * w;
+  const int64_t total = (int64_t)n * h * w * ca8;
+  const int64_t T = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += T) {
+    const int q = (int)(i % ca8);
+    int64_t r = i / ca8;
+    const int x = (int)(r % w);
+    r /= w;
+    const int y = (int)(r % h);
+    const int ni = (int)(r / h);
+    const int64_t p00 = ((int64_t)(ni * 2 * h + 2 * y) * W + 2 * x);
+    Vec16<true> g = Vec16<true>::from(dout[p00 * ct8 + q]);
+    g += Vec16<true>::from(dout[(p00 + 1) * ct8 + q]);
+    g += Vec16<true>::from(dout[(p00 + W) * ct8 + q]);
+    g += Vec16<true>::from(dout[(p00 + W + 1) * ct8 + q]);
+    if (accumulate) g += Vec16<true>::from(da[i]);
+    da[i] = g.raw();
+  }
+}
+
+// the skip half of the concat's gradient: a strided copy (or accumulation) of channel vectors caq .. caq + cbq - 1 of dout
+template <bool BF>
+__global__ void upcat_bwd_skip_kernel(const f32x4* __restrict__ dout, f32x4* __restrict__ dskip, int64_t pixels, int caq,
+                                      int cbq, int accumulate) {
+  const int ctq = caq + cbq;
+  const int64_t total = pixels * cbq;
+  const int64_t T = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += T) {
+    const int q = (int)(i % cbq);
+    const int64_t p = i / cbq;
+    f32x4 raw = dout[p * ctq + caq + q];
+    if (accumulate) {
+      Vec16<BF> g = Vec16<BF>::from(raw);
+      g += Vec16<BF>::from(dskip[i]);
+      raw = g.raw();
+    }
+    dskip[i] = raw;
+  }
+}
+
+void launch_upcat_bwd_skip(bool bf16, int grid, const void* dout, void* dskip, int64_t pixels, int caq, int cbq, int accumulate,
+                           hipStream_t s) {
+  if (bf16)
+    hipLaunchKernelGGL(upcat_bwd_skip_kernel<true>, dim3(grid), dim3(256), 0, s, (const f32x4*)dout, (f32x4*)dskip, pixels, caq, cbq,
+                       accumulate);
+  else
+    hipLaunchKernelGGL(upcat_bwd_skip_kernel<false>, dim3(grid), dim3(256), 0, s, (const f32x4*)dout, (f32x4*)dskip, pixels, caq, cbq,
+                       accumulate);
 }
 
 __global__ void fill_kernel(float* __restrict__ p, int64_t n, float v) {
@@ -179,13 +277,6 @@ __global__ void add_i64_kernel(long long* __restrict__ p, int64_t n, long long v
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += T) p[i] += v;
 }
 
-static inline int grid_for(int64_t items, int per_thread = 2) {
-  int64_t g = (items + 256LL * per_thread - 1) / (256LL * per_thread);
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace udaseg
 
 using namespace udaseg;
@@ -194,8 +285,18 @@ extern "C" int udaseg_nchw_to_nhwc(const float* x, float* y, int n, int c, int h
   UDASEG_CHECK_ARG(x && y && n > 0 && c > 0 && h > 0 && w > 0, "nchw_to_nhwc: bad arguments");
   UDASEG_CHECK_ARG(cpad >= c && cpad % 4 == 0, "nchw_to_nhwc: cpad must be a multiple of 4 and >= c");
   const int64_t hw = (int64_t)h * w, total = hw * n;
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), x, y, c, hw, cpad, total);
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), x, (f32x4*)y, c, hw,
+                     cpad / 4, total);
   UDASEG_LAUNCH_CHECK("nchw_to_nhwc launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_nchw_to_nhwc_bf16(const float* x, void* y, int n, int c, int h, int w, int cpad, void* stream) {
+  UDASEG_CHECK_ARG(x && y && n > 0 && c > 0 && h > 0 && w > 0 && cpad >= c && cpad % 8 == 0, "nchw_to_nhwc_bf16: bad arguments");
+  const int64_t hw = (int64_t)h * w, total = hw * n;
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), x, (f32x4*)y, c, hw,
+                     cpad / 8, total);
+  UDASEG_LAUNCH_CHECK("nchw_to_nhwc_bf16 launch");
   return UDASEG_OK;
 }
 
@@ -203,9 +304,19 @@ extern "C" int udaseg_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, i
   UDASEG_CHECK_ARG(x && y && idx && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, "maxpool_fwd: bad arguments");
   const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)n * ho * wo * (c / 4);
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), (const f32x4*)x, (f32x4*)y,
-                     (uint32_t*)idx, n, h, w, c / 4, ho, wo);
+  hipLaunchKernelGGL(maxpool_fwd_kernel<false>, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), (const f32x4*)x,
+                     (f32x4*)y, (uint32_t*)idx, n, h, w, c / 4, ho, wo);
   UDASEG_LAUNCH_CHECK("maxpool_fwd launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_maxpool3x3s2_fwd_bf16(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, void* stream) {
+  UDASEG_CHECK_ARG(x && y && idx && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "maxpool_fwd_bf16: bad arguments");
+  const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
+  const int64_t total = (int64_t)n * ho * wo * (c / 8);
+  hipLaunchKernelGGL(maxpool_fwd_kernel<true>, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), (const f32x4*)x,
+                     (f32x4*)y, (uint32_t*)idx, n, h, w, c / 8, ho, wo);
+  UDASEG_LAUNCH_CHECK("maxpool_fwd_bf16 launch");
   return UDASEG_OK;
 }
 
@@ -219,6 +330,17 @@ extern "C" int udaseg_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, floa
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(gx, gy), dim3(256), 0, as_stream(stream), (const f32x4*)dy,
                      (const uint32_t*)idx, (f32x4*)dx, n, h, w, c / 4, ho, wo, accumulate);
   UDASEG_LAUNCH_CHECK("maxpool_bwd launch");
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_maxpool3x3s2_bwd_bf16(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c,
+                                            int accumulate, void* stream) {
+  UDASEG_CHECK_ARG(dy && idx && dx && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "maxpool_bwd_bf16: bad arguments");
+  const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
+  const int64_t total = (int64_t)n * h * w * (c / 8);
+  hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(grid_for(total, 1)), dim3(256), 0, as_stream(stream), (const f32x4*)dy,
+                     (const uint2*)idx, (f32x4*)dx, n, h, w, c / 8, ho, wo, accumulate);
+  UDASEG_LAUNCH_CHECK("maxpool_bwd_bf16 launch");
   return UDASEG_OK;
 }
 
@@ -249,9 +371,27 @@ extern "C" int udaseg_upsample2x_concat_bwd(const float* dout, float* da, float*
   }
   if (dskip && cb > 0) {
     const int64_t pixels = (int64_t)n * 4 * h * w;
-    hipLaunchKernelGGL(upcat_bwd_skip_kernel, dim3(grid_for(pixels * (cb / 4))), dim3(256), 0, st, (const f32x4*)dout,
-                       (f32x4*)dskip, pixels, ca / 4, cb / 4, accumulate_dskip);
+    launch_upcat_bwd_skip(false, grid_for(pixels * (cb / 4)), dout, dskip, pixels, ca / 4, cb / 4, accumulate_dskip, st);
     UDASEG_LAUNCH_CHECK("upsample2x_concat_bwd(skip) launch");
+  }
+  return UDASEG_OK;
+}
+
+extern "C" int udaseg_upsample2x_concat_bwd_bf16(const void* dout, void* da, void* dskip, int n, int h, int w, int ca, int cb,
+                                                 int accumulate_da, int accumulate_dskip, void* stream) {
+  UDASEG_CHECK_ARG(dout && n > 0 && h > 0 && w > 0 && ca > 0 && ca % 8 == 0 && cb >= 0 && cb % 8 == 0,
+                   "upsample2x_concat_bwd_bf16: bad arguments");
+  hipStream_t st = as_stream(stream);
+  if (da) {
+    const int64_t total = (int64_t)n * h * w * (ca / 8);
+    hipLaunchKernelGGL(upcat_bwd_a_bf16_kernel, dim3(grid_for(total, 1)), dim3(256), 0, st, (const f32x4*)dout, (f32x4*)da, n, h,
+                       w, ca / 8, (ca + cb) / 8, accumulate_da);
+    UDASEG_LAUNCH_CHECK("upsample2x_concat_bwd_bf16(a) launch");
+  }
+  if (dskip && cb > 0) {
+    const int64_t pixels = (int64_t)n * 4 * h * w;
+    launch_upcat_bwd_skip(true, grid_for(pixels * (cb / 8)), dout, dskip, pixels, ca / 8, cb / 8, accumulate_dskip, st);
+    UDASEG_LAUNCH_CHECK("upsample2x_concat_bwd_bf16(skip) launch");
   }
   return UDASEG_OK;
 }
