@@ -292,11 +292,11 @@ GRADE_CASES = [(23, 16, 3.0, 1.0, 0), (32, 16, 3.0, 1.0, 0), (2, 4, 3.0, 1.0, 0)
 GRADE_PIXELS = 20000
 
 
-def grade_case(C, D, scale, tau_scale, probs, device="cuda", rectify=None):
+def grade_case(C, D, scale, tau_scale, probs, device="cuda", rectify=None, pixels=GRADE_PIXELS):
     """One grading case -> dict of figures.  ``rectify(feat, scores, proto, inv_tau) -> [P, C]`` is the implementation under
     test (None: only torch's own error, which needs no GPU)."""
     g = torch.Generator().manual_seed(100 * C + D + int(10 * scale))
-    proto, feat, logits = _rectify_inputs(GRADE_PIXELS, C, D, g, scale)
+    proto, feat, logits = _rectify_inputs(pixels, C, D, g, scale)
     scores = torch.softmax(logits, 1) if probs else logits
     inv_tau = float(np.float32(1.0 / (tau_scale * D)))
     ref = rectify_mirror(feat.numpy(), scores.numpy(), proto.numpy(), np.ones(C), inv_tau, probs=bool(probs))

@@ -26,8 +26,8 @@ __global__ __launch_bounds__(256) void prepare_batch_kernel(const uint8_t* __res
     if (code & 2) y = h - 1 - y;
     if (code & 4) x = w - 1 - x;
     const int sp = (code & 1) ? x * w + y : y * w + x;        // transpose needs h == w (checked by the caller)
-    store_normalized<BF16>(out, ((size_t)ni * hw + p) * cpad, cpad, nm, (float)img[sp * 3 + 0], (float)img[sp * 3 + 1],
-                           (float)img[sp * 3 + 2]);
+    const uint8_t* px = img + (size_t)sp * 3;                 // sp * 3 passes 2^31 from 715 827 883 pixels on
+    store_normalized<BF16>(out, ((size_t)ni * hw + p) * cpad, cpad, nm, (float)px[0], (float)px[1], (float)px[2]);
     if (msk) out_masks[(size_t)ni * hw + p] = (int64_t)msk[sp];
   }
 }
