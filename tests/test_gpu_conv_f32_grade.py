@@ -22,15 +22,16 @@ of tier A with its epilogue (bias + ReLU, residual, accumulation onto old).
 Every launch asserts from prof_kernels() that its own instantiation ran once and nothing else ran; routes are forced with the
 switchboard only (F32_SPLIT = 0, IGEMM_TILE, GENERIC_GATHER, WGRAD_GENERIC, WGRAD_BLOCKS), restored to -1 afterwards.
 
-Symbols of the fixed table (csrc/api.hip) that run here under a route assertion:
+Symbols that run here under a route assertion (the timing table of csrc/api.hip knows every kernel by the name it registers on
+its first launch; there is no fixed table and no numeric id any more):
   conv_igemm_kernel<128, 128, 2, 2 | 128, 64, 2, 2 | 64, 64, 2, 2 | 128, 32, 4, 1, false, false, false>   (generic loop)
   conv_igemm_kernel<..., false, true, false>   (uniform-tap loop),  conv_igemm_kernel<..., false, true, true>   (fused input)
   conv3x3_small_kernel<1, 1 | 2, 1 | 1, 2>,  conv3x3_small_wgrad_kernel<1, 1 | 2, 1 | 1, 2>   (small_wgrad_fold_kernel carries no
   timing record of its own: it is graded through the weight gradient it finishes)
   conv_wgrad_kernel<64, 64, 2, 2, false | true>,  conv_wgrad_kernel<32, 128, 1, 4, false | true>
-Not reachable: the table's two lumped names "conv_igemm_kernel<*, bf16>" and "conv_wgrad_bf16_kernel" are never booked (bf16
-launches register their own symbols, graded in test_gpu_conv_bf16_grade.py), and the dynamic names conv_wgrad_kernel<128, ...> exist
-only in launch_wgrad's bookkeeping: conv2d_wgrad_impl instantiates the 128-row tile for bf16 alone, no fp32 entry point leads there.
+Not reachable: conv_wgrad_kernel<128, ...> is compiled (launch_wgrad is one template for both storages) but never launched and so
+never registered: conv2d_wgrad_impl takes the 128-row tile for bf16 alone, no fp32 entry point leads there.  The bf16 launches
+register their own symbols, graded in test_gpu_conv_bf16_grade.py.
 
 Set UDASEG_DEVIATION_LOG to a file name to collect the figures (profiles/conv_f32_grade.txt).
 """

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.h"
+#include "launch.h"
 #include "options.h"
 
 namespace udaseg {
@@ -34,51 +35,54 @@ struct KRec {
   hipEvent_t a, b;
   double flops;
 };
-// exactly the symbols rocprofv3 prints (minus "void udaseg::" and the parameter list), so HIP-event and rocprof averages
-// can be compared per kernel
-static const char* const g_knames_fixed[PROF_NKERNELS] = {
-    "conv_igemm_kernel<128, 128, 2, 2, false, false, false>", "conv_igemm_kernel<128, 64, 2, 2, false, false, false>",
-    "conv_igemm_kernel<64, 64, 2, 2, false, false, false>",   "conv_igemm_kernel<128, 32, 4, 1, false, false, false>",
-    "conv3x3_small_kernel<1, 1>",                             "conv3x3_small_kernel<2, 1>",
-    "conv3x3_small_kernel<1, 2>",                             "conv_wgrad_kernel<64, 64, 2, 2, false>",
-    "conv_wgrad_kernel<32, 128, 1, 4, false>",                "conv3x3_small_wgrad_kernel<1, 1>",
-    "conv3x3_small_wgrad_kernel<2, 1>",                       "conv3x3_small_wgrad_kernel<1, 2>",
-    "conv_igemm_kernel<*, bf16>",                             "conv_wgrad_bf16_kernel",
-    "conv_igemm_kernel<128, 128, 2, 2, false, true, false>",  "conv_igemm_kernel<128, 64, 2, 2, false, true, false>",
-    "conv_igemm_kernel<64, 64, 2, 2, false, true, false>",    "conv_igemm_kernel<128, 32, 4, 1, false, true, false>",
-    "conv_wgrad_kernel<64, 64, 2, 2, true>",                  "conv_wgrad_kernel<32, 128, 1, 4, true>",
-    "conv_igemm_kernel<128, 128, 2, 2, false, true, true>",   "conv_igemm_kernel<128, 64, 2, 2, false, true, true>",
-    "conv_igemm_kernel<64, 64, 2, 2, false, true, true>",     "conv_igemm_kernel<128, 32, 4, 1, false, true, true>"};
-// ids 0 .. PROF_NKERNELS-1 are the fixed table above; kernels added later register their rocprofv3 symbol on first launch
-// (kprof_id) and get the next id, up to PROF_MAX_KERNELS
+// Every kernel registers the symbol rocprofv3 prints for it (minus "void udaseg::" and the parameter list, so HIP-event and
+// rocprof averages can be compared per kernel) on its first launch and gets the next id, up to PROF_MAX_KERNELS: ids follow the
+// order of first launches, readers key by name (udaseg_prof_kernel_name).
 constexpr int PROF_MAX_KERNELS = 160;
 static std::vector<KRec> g_krecs[PROF_MAX_KERNELS];
-static char g_knames_dyn[PROF_MAX_KERNELS][160];
-static int g_nkernels = PROF_NKERNELS;
+static char g_knames[PROF_MAX_KERNELS][160];
+static int g_nkernels = 0;
 
 // Launches come from the compute and the weight-gradient streams, possibly from different host threads: registration is
-// serialised (callers cache the id in a function-local static; a racing first call of two threads registers the name once and
+// serialised (callers cache the id in their KernelRec; a racing first call of two threads registers the name once and
 // both get the same id).  A full table is reported, not silently aliased: the bench's per-kernel figures must not mix symbols.
 static std::mutex g_kprof_mutex;
 int kprof_id(const char* name) {
   std::lock_guard<std::mutex> lock(g_kprof_mutex);
-  for (int k = PROF_NKERNELS; k < g_nkernels; ++k)
-    if (strcmp(g_knames_dyn[k], name) == 0) return k;
+  for (int k = 0; k < g_nkernels; ++k)
+    if (strcmp(g_knames[k], name) == 0) return k;
   if (g_nkernels >= PROF_MAX_KERNELS) {
     static bool warned = false;
     if (!warned) {
       fprintf(stderr, "libudaseg_hip: kernel-timing table full (%d symbols); '%s' and later symbols are booked under '%s'\n",
-              PROF_MAX_KERNELS, name, g_knames_dyn[PROF_NKERNELS]);
+              PROF_MAX_KERNELS, name, g_knames[0]);
       warned = true;
     }
-    return PROF_NKERNELS;
+    return 0;
   }
-  strncpy(g_knames_dyn[g_nkernels], name, sizeof(g_knames_dyn[0]) - 1);
+  strncpy(g_knames[g_nkernels], name, sizeof(g_knames[0]) - 1);
   return g_nkernels++;
 }
-static const char* kname(int kid) {
-  if (kid < 0 || kid >= g_nkernels) return "";
-  return kid < PROF_NKERNELS ? g_knames_fixed[kid] : g_knames_dyn[kid];
+static const char* kname(int kid) { return kid < 0 || kid >= g_nkernels ? "" : g_knames[kid]; }
+
+// CU count per device, 0 = not asked yet.  A racing first call of two threads stores the same number twice.
+static std::atomic<int> g_cus[16] = {};
+int device_cus() {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess || dev < 0 || dev >= 16) {
+    (void)hip_fail(e != hipSuccess ? e : hipErrorInvalidDevice, "hipGetDevice(device_cus)");
+    return 0;
+  }
+  int cus = g_cus[dev];
+  if (cus > 0) return cus;
+  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess || cus <= 0) {
+    (void)hip_fail(e != hipSuccess ? e : hipErrorInvalidValue, "hipDeviceGetAttribute(multiprocessor count)");
+    return 0;
+  }
+  g_cus[dev] = cus;
+  return cus;
 }
 static std::vector<ProfRec> g_recs[2];
 static std::vector<hipEvent_t> g_pool;

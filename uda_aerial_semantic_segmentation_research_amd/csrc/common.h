@@ -264,26 +264,15 @@ int launch_small_wgrad(const float* x, const float* dy, float* dw, int n, int h,
 void launch_upcat_bwd_skip(bool bf16, int grid, const void* dout, void* dskip, int64_t pixels, int caq, int cbq, int accumulate,
                            hipStream_t s);
 
-// live launch timing (bench.py roofline leg): per API call (prof_*) and per kernel launch (kprof_*).  The launchers keep their
-// kernel id / "attribute set" flags in function-local std::atomic statics: launches come from two host threads' streams, a racing
-// first call registers the same name twice (kprof_id is serialised and returns the same id) and sets the same attribute twice.
-constexpr int PROF_NKERNELS = 24;
-int kprof_id(const char* rocprof_symbol);   // id of a kernel symbol outside the fixed table (registered on first use)
+// live launch timing (bench.py roofline leg): per API call (prof_*) and per kernel launch (kprof_*).  Every kernel is known to the
+// timing table by the symbol rocprofv3 prints for it, registered on its first launch (kprof_id); ids follow that order and mean
+// nothing outside the process.  A launcher keeps the id, and its "LDS opted in" flag, in one function-local KernelRec per kernel
+// instantiation (launch.h: launch_kernel for the convolutions, KTimer for the bandwidth-bound kernels).  Launches come from two
+// host threads' streams: a racing first call registers the same name twice (kprof_id is serialised and returns the same id) and
+// sets the same attribute twice.
+int kprof_id(const char* rocprof_symbol);   // id of a kernel symbol (registered on first use)
 hipEvent_t kprof_begin(hipStream_t s);
 void kprof_end(int kid, hipEvent_t a, hipStream_t s, double flops);
-// RAII form for the bandwidth-bound kernels: `work` carries their ALGORITHMIC BYTES (bench.py reports TB/s for symbols that do
-// not start with "conv").  Costs one static-int test per call when profiling is off.
-struct KTimer {
-  std::atomic<int>* kid;
-  hipStream_t s;
-  hipEvent_t ev;
-  double work;
-  KTimer(std::atomic<int>* k, const char* rocprof_symbol, hipStream_t st, double w) : kid(k), s(st), work(w) {
-    if (*kid < 0) *kid = kprof_id(rocprof_symbol);
-    ev = kprof_begin(s);
-  }
-  ~KTimer() { kprof_end(*kid, ev, s, work); }
-};
 void prof_begin(int family, hipStream_t s);
 void prof_suspend(int on);
 void prof_end(int family, hipStream_t s, double flops, int kind, const udaseg_conv_desc* d);

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -1159,56 +1160,21 @@ void launch_halo_stats_fold(double* sscr, int co, double* stats, hipStream_t s) 
 template <int KS, int CK, int WM, int WN, int RPW, int TW>
 static int launch_halo_t(HaloArgs a, hipStream_t s, double flops) {
   using C = HaloCfg<KS, CK, WM, WN, RPW, TW>;
-  auto kern = conv_halo_bf16_kernel<KS, CK, WM, WN, RPW, TW>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done && C::LDS > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_halo_bf16)");
-    attr_done = true;
-  }
-  a.ntx = cdiv(a.w, TW);
-  a.nty = cdiv(a.h, C::TH);
-  a.ncb = cdiv(a.co, 32 * WN);
-  a.nk16 = (a.ci + 15) / 16;
-  const long long blocks = (long long)a.n * a.nty * a.ntx * a.ncb * (KS == 2 && a.ncls > 1 ? a.ncls : 1);
+  static KernelRec rec("hipFuncSetAttribute(conv_halo_bf16)", "conv_halo_bf16_kernel<%d, %d, %d, %d, %d, %d>", KS, CK, WM, WN, RPW, TW);
+  const long long blocks = tile_launch_shape(a, C::TH, TW, 32 * WN, s, KS == 2 && a.ncls > 1 ? a.ncls : 1);
   if (blocks <= 0) return UDASEG_OK;
   a.timeline = (g_timeline && blocks <= g_timeline_blocks) ? g_timeline : nullptr;
-  a.sscr = nullptr;
-  if (a.stats != nullptr && blocks > 1024) a.sscr = halo_stats_scratch(a.co, s);
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_halo_bf16_kernel<%d, %d, %d, %d, %d, %d>", KS, CK, WM, WN, RPW, TW);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv_halo_bf16 launch");
-  if (a.sscr != nullptr) {
-    launch_halo_stats_fold(a.sscr, a.co, a.stats, s);
-    UDASEG_LAUNCH_CHECK("halo_stats_fold launch");
-  }
-  return UDASEG_OK;
+  const int rc = launch_kernel(rec, conv_halo_bf16_kernel<KS, CK, WM, WN, RPW, TW>, dim3((unsigned)blocks), dim3(C::NT), C::LDS, C::LDS, s,
+                               flops, "conv_halo_bf16 launch", a);
+  return fold_stats(rc, a, s);
 }
 
 template <int CK, int WM, int WN>
 static int launch_stream_t(HaloArgs a, hipStream_t s, double flops) {
   using C = StreamCfg<CK, WM, WN>;
-  auto kern = conv1x1_stream_bf16_kernel<CK, WM, WN>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done && C::LDS > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv1x1_stream_bf16)");
-    attr_done = true;
-  }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hip_fail(hipGetLastError(), "hipGetDeviceProperties");
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  static KernelRec rec("hipFuncSetAttribute(conv1x1_stream_bf16)", "conv1x1_stream_bf16_kernel<%d, %d, %d>", CK, WM, WN);
+  const int cus = device_cus();
+  if (cus <= 0) return UDASEG_E_HIP;
   a.ncb = cdiv(a.co, 32 * WN);
   a.nk16 = (a.ci + 15) / 16;
   const long long tiles = cdiv64((long long)a.n * a.h * a.w, C::TP);
@@ -1216,36 +1182,16 @@ static int launch_stream_t(HaloArgs a, hipStream_t s, double flops) {
   long long P = cus / a.ncb;                 // one 8-wave block per CU
   if (P < 1) P = 1;
   if (P > tiles) P = tiles;
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv1x1_stream_bf16_kernel<%d, %d, %d>", CK, WM, WN);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(P * a.ncb)), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv1x1_stream_bf16 launch");
-  return UDASEG_OK;
+  return launch_kernel(rec, conv1x1_stream_bf16_kernel<CK, WM, WN>, dim3((unsigned)(P * a.ncb)), dim3(C::NT), C::LDS, C::LDS, s, flops,
+                       "conv1x1_stream_bf16 launch", a);
 }
 
 template <int PBW>
 static int launch_gemm_t(HaloArgs a, hipStream_t s, double flops) {
   using C = GemmCfg<PBW>;
-  auto kern = conv1x1_gemm_bf16_kernel<PBW>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv1x1_gemm_bf16)");
-    attr_done = true;
-  }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hip_fail(hipGetLastError(), "hipGetDeviceProperties");
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  static KernelRec rec("hipFuncSetAttribute(conv1x1_gemm_bf16)", "conv1x1_gemm_bf16_kernel<%d>", PBW);
+  const int cus = device_cus();
+  if (cus <= 0) return UDASEG_E_HIP;
   a.ncb = cdiv(a.co, C::BN);
   a.nk16 = (a.ci + 15) / 16;
   const long long tiles = cdiv64((long long)a.n * a.h * a.w, C::BM) * a.ncb;
@@ -1256,17 +1202,8 @@ static int launch_gemm_t(HaloArgs a, hipStream_t s, double flops) {
   const long long per = cdiv64(tiles, grid);
   grid = cdiv64(tiles, per);
   a.sscr = nullptr;
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[64];
-    snprintf(nm, sizeof(nm), "conv1x1_gemm_bf16_kernel<%d>", PBW);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv1x1_gemm_bf16 launch");
-  return UDASEG_OK;
+  return launch_kernel(rec, conv1x1_gemm_bf16_kernel<PBW>, dim3((unsigned)grid), dim3(C::NT), C::LDS, C::LDS, s, flops,
+                       "conv1x1_gemm_bf16 launch", a);
 }
 
 static int launch_gemm(HaloArgs a, hipStream_t s, double flops) {

@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -785,127 +786,44 @@ __global__ void pack_frag_batched_f32x3_kernel(const float* __restrict__ w32, co
 template <int WM, int WN, int RPW, int TW = 32>
 static int launch_f3_ws_t(F3Args a, hipStream_t s, double flops) {
   using C = F3WsCfg<WM, WN, RPW, TW>;
-  auto kern = conv3x3_f32x3_ws_kernel<WM, WN, RPW, false, TW>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_f32x3_ws)");
-    attr_done = true;
-  }
-  a.ntx = cdiv(a.w, C::TW);
-  a.nty = cdiv(a.h, C::TH);
-  a.ncb = cdiv(a.co, 32 * C::WN);
-  a.nk16 = (a.ci + 15) / 16;
+  const long long blocks = tile_launch_shape(a, C::TH, C::TW, 32 * C::WN, s);
   a.q1 = a.q3 = -1;
   if (f3_signs_on()) f3_negated_groups(a.nk16, a.q1, a.q3);
-  const long long blocks = (long long)a.n * a.nty * a.ntx * a.ncb;
   if (blocks <= 0) return UDASEG_OK;
-  a.sscr = nullptr;
-  if (a.stats != nullptr && blocks > 1024) a.sscr = halo_stats_scratch(a.co, s);
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, false>", WM, WN, RPW, TW);      // the rocprofv3 symbol
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
+  // the kernel of this launch, its record and its text; the stamped twin is booked under the plain symbol
+  static KernelRec plain("hipFuncSetAttribute(conv3x3_f32x3_ws)", "conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, false>", WM, WN, RPW, TW);
+  KernelRec* rec = &plain;
+  auto kern = conv3x3_f32x3_ws_kernel<WM, WN, RPW, false, TW>;
+  const char* what = "conv3x3_f32x3_ws launch";
   if (a.in_scale != nullptr) {          // the instantiation that transforms x while it stages (F3Args::in_scale)
-    auto kern_xf = conv3x3_f32x3_ws_kernel<WM, WN, RPW, false, TW, true>;
-    static std::atomic<bool> xf_attr{false};
-    if (!xf_attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_xf), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-      if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_f32x3_ws, in-staging transform)");
-      xf_attr = true;
-    }
-    static std::atomic<int> kid_xf{-1};             // its own rocprofv3 symbol
-    if (kid_xf < 0) {
-      char nm[96];
-      snprintf(nm, sizeof(nm), "conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, true>", WM, WN, RPW, TW);
-      kid_xf = kprof_id(nm);
-    }
-    hipLaunchKernelGGL(kern_xf, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-    kprof_end(kid_xf, ev, s, flops);
-    UDASEG_LAUNCH_CHECK("conv3x3_f32x3_ws (in-staging transform) launch");
-    if (a.sscr != nullptr) {
-      launch_halo_stats_fold(a.sscr, a.co, a.stats, s);
-      UDASEG_LAUNCH_CHECK("halo_stats_fold launch");
-    }
-    return UDASEG_OK;
+    static KernelRec xf("hipFuncSetAttribute(conv3x3_f32x3_ws, in-staging transform)", "conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, true>",
+                        WM, WN, RPW, TW);
+    rec = &xf;
+    kern = conv3x3_f32x3_ws_kernel<WM, WN, RPW, false, TW, true>;
+    what = "conv3x3_f32x3_ws (in-staging transform) launch";
   } else if (g_timeline != nullptr && blocks * 16 <= (long long)g_timeline_blocks * 6) {      // stamped twin (diagnosis only)
-    auto kern_tl = conv3x3_f32x3_ws_kernel<WM, WN, RPW, true, TW>;
-    static std::atomic<bool> tl_attr{false};
-    if (!tl_attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_tl), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-      if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_f32x3_ws timeline twin)");
-      tl_attr = true;
-    }
+    static KernelRec tl("hipFuncSetAttribute(conv3x3_f32x3_ws timeline twin)", "conv3x3_f32x3_ws_kernel<%d, %d, %d, false, %d, false>",
+                        WM, WN, RPW, TW);
+    rec = &tl;
+    kern = conv3x3_f32x3_ws_kernel<WM, WN, RPW, true, TW>;
     a.timeline = g_timeline;
-    hipLaunchKernelGGL(kern_tl, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-  } else {
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
   }
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv3x3_f32x3_ws launch");
-  if (a.sscr != nullptr) {
-    launch_halo_stats_fold(a.sscr, a.co, a.stats, s);
-    UDASEG_LAUNCH_CHECK("halo_stats_fold launch");
-  }
-  return UDASEG_OK;
+  return fold_stats(launch_kernel(*rec, kern, dim3((unsigned)blocks), dim3(C::NT), C::LDS, C::LDS, s, flops, what, a), a, s);
 }
 
 template <int WM, int WN, int RPW>
 static int launch_f3_t(F3Args a, hipStream_t s, double flops) {
   using C = F3Cfg<WM, WN, RPW>;
-  auto kern = conv3x3_f32x3_kernel<WM, WN, RPW>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done && C::LDS > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_f32x3)");
-    attr_done = true;
-  }
-  a.ntx = cdiv(a.w, C::TW);
-  a.nty = cdiv(a.h, C::TH);
-  a.ncb = cdiv(a.co, 32 * WN);
-  a.nk16 = (a.ci + 15) / 16;
+  const long long blocks = tile_launch_shape(a, C::TH, C::TW, 32 * WN, s);
   a.q1 = a.q3 = -1;
   if (f3_signs_on()) f3_negated_groups(a.nk16, a.q1, a.q3);
-  const long long blocks = (long long)a.n * a.nty * a.ntx * a.ncb;
   if (blocks <= 0) return UDASEG_OK;
-  a.sscr = nullptr;
-  if (a.stats != nullptr && blocks > 1024) a.sscr = halo_stats_scratch(a.co, s);
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv3x3_f32x3_kernel<%d, %d, %d, false>", WM, WN, RPW);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  if (a.in_scale != nullptr) {
-    auto kern_xf = conv3x3_f32x3_kernel<WM, WN, RPW, true>;
-    static std::atomic<bool> xf_attr{false};
-    if (!xf_attr && C::LDS > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_xf), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-      if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_f32x3, in-staging transform)");
-      xf_attr = true;
-    }
-    static std::atomic<int> kid_xf{-1};             // its own rocprofv3 symbol
-    if (kid_xf < 0) {
-      char nm[96];
-      snprintf(nm, sizeof(nm), "conv3x3_f32x3_kernel<%d, %d, %d, true>", WM, WN, RPW);
-      kid_xf = kprof_id(nm);
-    }
-    hipLaunchKernelGGL(kern_xf, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-    kprof_end(kid_xf, ev, s, flops);
-  } else {
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-    kprof_end(kid, ev, s, flops);
-  }
-  UDASEG_LAUNCH_CHECK("conv3x3_f32x3 launch");
-  if (a.sscr != nullptr) {
-    launch_halo_stats_fold(a.sscr, a.co, a.stats, s);
-    UDASEG_LAUNCH_CHECK("halo_stats_fold launch");
-  }
-  return UDASEG_OK;
+  static KernelRec plain("hipFuncSetAttribute(conv3x3_f32x3)", "conv3x3_f32x3_kernel<%d, %d, %d, false>", WM, WN, RPW);
+  static KernelRec xf("hipFuncSetAttribute(conv3x3_f32x3, in-staging transform)", "conv3x3_f32x3_kernel<%d, %d, %d, true>", WM, WN, RPW);
+  const bool in_xf = a.in_scale != nullptr;
+  return fold_stats(launch_kernel(in_xf ? xf : plain, in_xf ? conv3x3_f32x3_kernel<WM, WN, RPW, true> : conv3x3_f32x3_kernel<WM, WN, RPW>,
+                                  dim3((unsigned)blocks), dim3(C::NT), C::LDS, C::LDS, s, flops, "conv3x3_f32x3 launch", a),
+                    a, s);
 }
 
 static int f3_enabled() { return f32_halo_enabled() ? 1 : 0; }      // UDASEG_OPT_F32_HALO = 0: every fp32 layer on the fp32-MFMA kernels

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -824,14 +825,10 @@ int g_timeline_blocks = 0;
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool BF, bool UNI, bool UP, bool X3 = false>
 static int launch_cfg_t(const IgemmArgs& a, hipStream_t s) {
-  static std::atomic<bool> attr_done{false};
   constexpr int lds = igemm_lds_bytes<BM, BN, X3>();
-  auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, BF, UNI, UP, X3>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_igemm)");
-    attr_done = true;
-  }
+  // every instantiation reports under its own rocprofv3 symbol
+  static KernelRec rec("hipFuncSetAttribute(conv_igemm)", "conv_igemm_kernel<%d, %d, %d, %d, %s, %s, %s%s>", BM, BN, WAVES_M, WAVES_N,
+                       BF ? "true" : "false", UNI ? "true" : "false", UP ? "true" : "false", X3 ? ", true" : "");
   IgemmArgs b = a;
   const int nt = cdiv(a.co, BN);
   double flops = 0.0;
@@ -848,23 +845,7 @@ static int launch_cfg_t(const IgemmArgs& a, hipStream_t s) {
   }
   b.timeline = (g_timeline && b.tile_begin[a.nclass] <= g_timeline_blocks) ? g_timeline : nullptr;
   dim3 grid((unsigned)b.tile_begin[a.nclass]), block(256);
-  constexpr int tile_id = (BM == 128 && BN == 128) ? 0 : (BM == 128 && BN == 64) ? 1 : (BM == 64) ? 2 : 3;
-  int kid = UP ? 20 + tile_id : (UNI ? 14 + tile_id : tile_id);
-  if constexpr (BF || X3) {      // bf16 / X3 instantiations report under their own rocprofv3 symbol (round 2 lumped them into one id)
-    static std::atomic<int> bf_kid{-1};
-    if (bf_kid < 0) {
-      char nm[96];
-      snprintf(nm, sizeof(nm), "conv_igemm_kernel<%d, %d, %d, %d, %s, %s, %s%s>", BM, BN, WAVES_M, WAVES_N, BF ? "true" : "false",
-               UNI ? "true" : "false", UP ? "true" : "false", X3 ? ", true" : "");
-      bf_kid = kprof_id(nm);
-    }
-    kid = bf_kid;
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, grid, block, lds, s, b);
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv_igemm launch");
-  return UDASEG_OK;
+  return launch_kernel(rec, conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, BF, UNI, UP, X3>, grid, block, lds, lds, s, flops, "conv_igemm launch", b);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -339,32 +340,17 @@ static int launch_n16(N16Args a, hipStream_t s, double flops) {
   const long long ntiles = (long long)a.n * a.nty * a.ntx;
   if (ntiles <= 0) return UDASEG_OK;
   if (ntiles >= (1LL << 31)) return UDASEG_E_UNSUPPORTED;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-              ? pr.multiProcessorCount : 256;
-  }
+  const int cus = device_cus();
+  if (cus <= 0) return UDASEG_E_HIP;
   const long long resident = (long long)cus * (a.nk16 == 1 ? 3 : 2);      // blocks that fit the chip at once (48 / 63 KB of LDS each)
   const long long blocks = ntiles < resident ? ntiles : resident;
   a.sscr = nullptr;
-  const bool xf = a.in_scale != nullptr;
-  auto kern = xf ? conv3x3_n16_f32x3_kernel<true> : conv3x3_n16_f32x3_kernel<false>;
-  static std::atomic<bool> attr_done[2] = {{false}, {false}};
-  if (!attr_done[xf]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       C::LDS_HALO + 2 * C::WCHUNK);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv3x3_n16_f32x3)");
-    attr_done[xf] = true;
-  }
-  static std::atomic<int> kid[2] = {{-1}, {-1}};
-  if (kid[xf] < 0) kid[xf] = kprof_id(xf ? "conv3x3_n16_f32x3_kernel<true>" : "conv3x3_n16_f32x3_kernel<false>");
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::NT), lds, s, a);
-  kprof_end(kid[xf], ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv3x3_n16_f32x3 launch");
-  return UDASEG_OK;
+  static KernelRec plain("hipFuncSetAttribute(conv3x3_n16_f32x3)", "conv3x3_n16_f32x3_kernel<false>");
+  static KernelRec xf("hipFuncSetAttribute(conv3x3_n16_f32x3)", "conv3x3_n16_f32x3_kernel<true>");
+  const bool in_xf = a.in_scale != nullptr;
+  // opts in to the two-chunk form's LDS, launches with what this launch's nk16 needs
+  return launch_kernel(in_xf ? xf : plain, in_xf ? conv3x3_n16_f32x3_kernel<true> : conv3x3_n16_f32x3_kernel<false>, dim3((unsigned)blocks),
+                       dim3(C::NT), lds, C::LDS_HALO + 2 * C::WCHUNK, s, flops, "conv3x3_n16_f32x3 launch", a);
 }
 
 }  // namespace udaseg

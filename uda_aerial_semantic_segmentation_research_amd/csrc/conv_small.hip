@@ -12,6 +12,7 @@
 //   * blocks are persistent over tiles; wgrad accumulates in registers across all its tiles and writes ONE partial
 //     per block (no atomics on the 2-5 K hot addresses), a second tiny kernel folds the partials.
 #include "common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -463,6 +464,9 @@ static int small_grid(int ntiles, int blocks_per_cu) {
   return ntiles < g ? ntiles : g;
 }
 
+// (gathered, produced) 16-channel groups -> index of the instantiation <1, 1> / <2, 1> / <1, 2>, or -1
+static int small_index(int G, int T) { return G == 1 && T == 1 ? 0 : G == 2 && T == 1 ? 1 : G == 1 && T == 2 ? 2 : -1; }
+
 // ---- dispatch helpers used by conv_igemm.hip / conv_wgrad.hip ----------------------------------------------------
 bool small_conv_applicable(int k, int stride, int pad, int ci_gather, int co_out) {
   if (k != 3 || stride != 1 || pad != 1) return false;
@@ -482,22 +486,16 @@ int launch_small_conv(const float* x, const float* w, const float* bias, float* 
   const int G = cdiv(ci, 16), T = cdiv(co, 16);
   dim3 block(256);
   const double fl = 2.0 * (double)n * h * wd * co * 9.0 * ci;
-  hipEvent_t ev = kprof_begin(s);
-  if (G == 1 && T == 1) {
-    hipLaunchKernelGGL((conv3x3_small_kernel<1, 1>), dim3(small_grid(a.ntiles, 6)), block, 0, s, a);
-    kprof_end(4, ev, s, fl);
-  } else if (G == 2 && T == 1) {
-    hipLaunchKernelGGL((conv3x3_small_kernel<2, 1>), dim3(small_grid(a.ntiles, 3)), block, 0, s, a);
-    kprof_end(5, ev, s, fl);
-  } else if (G == 1 && T == 2) {
-    hipLaunchKernelGGL((conv3x3_small_kernel<1, 2>), dim3(small_grid(a.ntiles, 6)), block, 0, s, a);
-    kprof_end(6, ev, s, fl);
-  } else {
+  // the three instantiations, indexed by small_index(G, T): records, kernels, blocks per CU
+  static KernelRec rec[3] = {{nullptr, "conv3x3_small_kernel<1, 1>"}, {nullptr, "conv3x3_small_kernel<2, 1>"}, {nullptr, "conv3x3_small_kernel<1, 2>"}};
+  void (*const kern[3])(SmallArgs) = {conv3x3_small_kernel<1, 1>, conv3x3_small_kernel<2, 1>, conv3x3_small_kernel<1, 2>};
+  const int per_cu[3] = {6, 3, 6};
+  const int k = small_index(G, T);
+  if (k < 0) {
     set_error("small conv: unsupported channel groups G=%d T=%d", G, T);
     return UDASEG_E_UNSUPPORTED;
   }
-  UDASEG_LAUNCH_CHECK("conv3x3_small launch");
-  return UDASEG_OK;
+  return launch_kernel(rec[k], kern[k], dim3(small_grid(a.ntiles, per_cu[k])), block, 0, 0, s, fl, "conv3x3_small launch", a);
 }
 
 bool small_wgrad_applicable(int k, int stride, int pad, int ci, int co, int ntiles) {
@@ -525,21 +523,16 @@ int launch_small_wgrad(const float* x, const float* dy, float* dw, int n, int h,
   const int grid = small_grid(a.ntiles, 2);
   dim3 block(256);
   const double fl = 2.0 * (double)n * h * wd * co * 9.0 * ci;
-  hipEvent_t ev = kprof_begin(s);
-  if (G == 1 && T == 1) {
-    hipLaunchKernelGGL((conv3x3_small_wgrad_kernel<1, 1>), dim3(grid), block, 0, s, a);
-    kprof_end(9, ev, s, fl);
-  } else if (G == 2 && T == 1) {
-    hipLaunchKernelGGL((conv3x3_small_wgrad_kernel<2, 1>), dim3(grid), block, 0, s, a);
-    kprof_end(10, ev, s, fl);
-  } else if (G == 1 && T == 2) {
-    hipLaunchKernelGGL((conv3x3_small_wgrad_kernel<1, 2>), dim3(grid), block, 0, s, a);
-    kprof_end(11, ev, s, fl);
-  } else {
+  static KernelRec rec[3] = {{nullptr, "conv3x3_small_wgrad_kernel<1, 1>"}, {nullptr, "conv3x3_small_wgrad_kernel<2, 1>"},
+                             {nullptr, "conv3x3_small_wgrad_kernel<1, 2>"}};
+  void (*const kern[3])(SmallWgradArgs) = {conv3x3_small_wgrad_kernel<1, 1>, conv3x3_small_wgrad_kernel<2, 1>, conv3x3_small_wgrad_kernel<1, 2>};
+  const int k = small_index(G, T);
+  if (k < 0) {
     set_error("small wgrad: unsupported channel groups G=%d T=%d", G, T);
     return UDASEG_E_UNSUPPORTED;
   }
-  UDASEG_LAUNCH_CHECK("conv3x3_small_wgrad launch");
+  const int rc = launch_kernel(rec[k], kern[k], dim3(grid), block, 0, 0, s, fl, "conv3x3_small_wgrad launch", a);
+  if (rc != UDASEG_OK) return rc;
   const int out = 16 * T * 9 * 16 * G;
   if (!accumulate) {
     hipError_t e = hipMemsetAsync(dw, 0, (size_t)co * 9 * ci * sizeof(float), s);

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -252,29 +253,14 @@ extern "C" int udaseg_conv2d_fwd_stem_f32x3(const udaseg_conv_desc* d, const flo
   a.y_bytes = (unsigned)((long long)d->n * d->ho * d->wo * 256);
   const long long ntiles = (long long)d->n * a.nty * a.ntx;
   if (ntiles <= 0) return UDASEG_OK;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-              ? pr.multiProcessorCount : 256;
-  }
+  const int cus = device_cus();
+  if (cus <= 0) return UDASEG_E_HIP;
   const long long blocks = ntiles < cus ? ntiles : cus;      // one 8-wave block per CU (119 KB of LDS)
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_f32x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_stem_f32x3)");
-    attr_done = true;
-  }
-  static std::atomic<int> kid{-1};
-  if (kid < 0) kid = kprof_id("conv_stem_f32x3_kernel");
+  static KernelRec rec("hipFuncSetAttribute(conv_stem_f32x3)", "conv_stem_f32x3_kernel");
   hipStream_t st = as_stream(stream);
   prof_begin(0, st);
-  hipEvent_t ev = kprof_begin(st);
-  hipLaunchKernelGGL(conv_stem_f32x3_kernel, dim3((unsigned)blocks), dim3(C::NT), C::LDS, st, a);
-  kprof_end(kid, ev, st, udaseg_conv_flops(d));
+  const int rc = launch_kernel(rec, conv_stem_f32x3_kernel, dim3((unsigned)blocks), dim3(C::NT), C::LDS, C::LDS, st, udaseg_conv_flops(d),
+                               "conv_stem_f32x3 launch", a);
   prof_end(0, st, udaseg_conv_flops(d), 0, d);
-  UDASEG_LAUNCH_CHECK("conv_stem_f32x3 launch");
-  return UDASEG_OK;
+  return rc;
 }

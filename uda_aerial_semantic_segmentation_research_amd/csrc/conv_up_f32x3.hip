@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -730,46 +731,15 @@ __global__ void pack_up_batched_f32x3_kernel(const float* __restrict__ w32, cons
 template <int WM, int WN, int RPW, int TW, bool DGRAD>
 static int launch_up_t(UpArgs a, hipStream_t s, double flops) {
   using C = UpCfg<WM, WN, RPW, TW, 4>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e;
-    if constexpr (DGRAD)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up_dgrad_f32x3_kernel<WM, WN, RPW, TW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    else
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up_fwd_f32x3_kernel<WM, WN, RPW, TW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_up_f32x3)");
-    attr_done = true;
-  }
-  a.ntx = cdiv(a.w, C::TW);
-  a.nty = cdiv(a.h, C::TH);
-  a.ncb = cdiv(a.co, 32 * C::WN);
-  a.nk16 = (a.ci + 15) / 16;
+  static KernelRec rec("hipFuncSetAttribute(conv_up_f32x3)", "conv_up_%s_f32x3_kernel<%d, %d, %d, %d>", DGRAD ? "dgrad" : "fwd", WM, WN, RPW, TW);
+  const long long blocks = tile_launch_shape(a, C::TH, C::TW, 32 * C::WN, s);
   a.q1 = a.q3 = -1;
   if (f3_signs_on()) up_negated_groups(4 * a.nk16, a.q1, a.q3);
-  const long long blocks = (long long)a.n * a.nty * a.ntx * a.ncb;
   if (blocks <= 0) return UDASEG_OK;
-  a.sscr = nullptr;
-  if (a.stats != nullptr && blocks > 1024) a.sscr = halo_stats_scratch(a.co, s);
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_up_%s_f32x3_kernel<%d, %d, %d, %d>", DGRAD ? "dgrad" : "fwd", WM, WN, RPW, TW);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  if constexpr (DGRAD)
-    hipLaunchKernelGGL((conv_up_dgrad_f32x3_kernel<WM, WN, RPW, TW>), dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-  else
-    hipLaunchKernelGGL((conv_up_fwd_f32x3_kernel<WM, WN, RPW, TW>), dim3((unsigned)blocks), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, flops);
-  UDASEG_LAUNCH_CHECK("conv_up_f32x3 launch");
-  if (a.sscr != nullptr) {
-    launch_halo_stats_fold(a.sscr, a.co, a.stats, s);
-    UDASEG_LAUNCH_CHECK("halo_stats_fold launch");
-  }
-  return UDASEG_OK;
+  void (*kern)(UpArgs);       // only the direction's own kernel is instantiated
+  if constexpr (DGRAD) kern = conv_up_dgrad_f32x3_kernel<WM, WN, RPW, TW>;
+  else kern = conv_up_fwd_f32x3_kernel<WM, WN, RPW, TW>;
+  return fold_stats(launch_kernel(rec, kern, dim3((unsigned)blocks), dim3(C::NT), C::LDS, C::LDS, s, flops, "conv_up_f32x3 launch", a), a, s);
 }
 
 // configuration of a launch: (a's extents, produced channels).  1: 2 x 32 a-pixels x 64 channels; 2: 4 x 32 x 64; 3: 4 x 32 x 32;

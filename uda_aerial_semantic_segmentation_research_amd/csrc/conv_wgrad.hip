@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -858,21 +859,11 @@ static int launch_wgrad_x3(WgradArgs a, int accumulate, hipStream_t s) {
                   xb <= (1LL << 30) && dyb <= (1LL << 30);
   a.x_bytes = (unsigned)xb;
   a.dy_bytes = (unsigned)dyb;
-  hipEvent_t ev = kprof_begin(s);
-  if (a.row_uniform)
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, true>), grid, block, 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, false>), grid, block, 0, s, a);
-  static std::atomic<int> kidx[2] = {{-1}, {-1}};
-  std::atomic<int>& kid = kidx[a.row_uniform ? 1 : 0];
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_wgrad_x3_kernel<%d, %d, %d, %d, %s>", BMW, BNW, WAVES_M, WAVES_N, a.row_uniform ? "true" : "false");
-    kid = kprof_id(nm);
-  }
-  kprof_end(kid, ev, s, 2.0 * (double)a.M * a.co * a.J);
-  UDASEG_LAUNCH_CHECK("conv_wgrad_x3 launch");
-  return UDASEG_OK;
+  static KernelRec rec[2] = {{nullptr, "conv_wgrad_x3_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
+                             {nullptr, "conv_wgrad_x3_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}};
+  return launch_kernel(rec[a.row_uniform], a.row_uniform ? conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, true>
+                                                         : conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, false>,
+                       grid, block, 0, 0, s, 2.0 * (double)a.M * a.co * a.J, "conv_wgrad_x3 launch", a);
 }
 
 template <int BMW, int BNW, int WAVES_M, int WAVES_N>
@@ -924,52 +915,22 @@ static int launch_wgrad(WgradArgs a, int accumulate, hipStream_t s, bool bf16 = 
       grid = dim3((unsigned)(tiles * splits), 1u);
     }
   }
-  hipEvent_t ev = kprof_begin(s);
-  if (bf16) {
-    constexpr int b_rows16 = 256 / (BNW / 8);
-    const long long xb16 = (long long)a.M / (a.ho * a.wo) * (a.up ? (a.hi >> 1) * (a.wi >> 1) : a.hi * a.wi) * a.ci * 2,
-                    dyb16 = (long long)a.M * a.co * 2;
-    a.row_uniform = !opt_get(UDASEG_OPT_WGRAD_GENERIC) && a.wo % b_rows16 == 0 && xb16 <= (1LL << 30) && dyb16 <= (1LL << 30);
-    a.x_bytes = (unsigned)xb16;
-    a.dy_bytes = (unsigned)dyb16;
-    if (a.row_uniform)
-      hipLaunchKernelGGL((conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, false>), grid, block, 0, s, a);
-    static std::atomic<int> kid16[2] = {{-1}, {-1}};     // one id per rocprofv3 symbol (round 2 lumped the bf16 instantiations into one)
-    std::atomic<int>& kid = kid16[a.row_uniform ? 1 : 0];
-    if (kid < 0) {
-      char nm[96];
-      snprintf(nm, sizeof(nm), "conv_wgrad_bf16_kernel<%d, %d, %d, %d, %s>", BMW, BNW, WAVES_M, WAVES_N, a.row_uniform ? "true" : "false");
-      kid = kprof_id(nm);
-    }
-    kprof_end(kid, ev, s, 2.0 * (double)a.M * a.co * a.J);
-  } else {
-    constexpr int b_rows = 256 / (BNW / 4);
-    const long long xb = (long long)a.M / (a.ho * a.wo) * (a.up ? (a.hi >> 1) * (a.wi >> 1) : a.hi * a.wi) * a.ci * 4,
-                    dyb = (long long)a.M * a.co * 4;
-    a.row_uniform = !opt_get(UDASEG_OPT_WGRAD_GENERIC) && a.wo % b_rows == 0 && xb <= (1LL << 30) && dyb <= (1LL << 30);
-    a.x_bytes = (unsigned)xb;
-    a.dy_bytes = (unsigned)dyb;
-    if (a.row_uniform)
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, true>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, false>), grid, block, 0, s, a);
-    int kid32 = (a.row_uniform ? 18 : 7) + (BMW == 64 ? 0 : 1);      // the fixed table knows the 64 x 64 and 32 x 128 symbols
-    if (BMW == 128) {
-      static std::atomic<int> kid128[2] = {{-1}, {-1}};
-      std::atomic<int>& k = kid128[a.row_uniform ? 1 : 0];
-      if (k < 0) {
-        char nm[96];
-        snprintf(nm, sizeof(nm), "conv_wgrad_kernel<%d, %d, %d, %d, %s>", BMW, BNW, WAVES_M, WAVES_N, a.row_uniform ? "true" : "false");
-        k = kprof_id(nm);
-      }
-      kid32 = k;
-    }
-    kprof_end(kid32, ev, s, 2.0 * (double)a.M * a.co * a.J);
-  }
-  UDASEG_LAUNCH_CHECK("conv_wgrad launch");
-  return UDASEG_OK;
+  // one record per rocprofv3 symbol: [bf16][row_uniform]
+  static KernelRec rec[2][2] = {{{nullptr, "conv_wgrad_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
+                                 {nullptr, "conv_wgrad_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}},
+                                {{nullptr, "conv_wgrad_bf16_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
+                                 {nullptr, "conv_wgrad_bf16_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}}};
+  const int es = bf16 ? 2 : 4;                        // bytes per element; a thread stages 16 bytes of a dy row
+  const int b_rows = 256 / (BNW / (16 / es));
+  const long long xb = (long long)a.M / (a.ho * a.wo) * (a.up ? (a.hi >> 1) * (a.wi >> 1) : a.hi * a.wi) * a.ci * es,
+                  dyb = (long long)a.M * a.co * es;
+  a.row_uniform = !opt_get(UDASEG_OPT_WGRAD_GENERIC) && a.wo % b_rows == 0 && xb <= (1LL << 30) && dyb <= (1LL << 30);
+  a.x_bytes = (unsigned)xb;
+  a.dy_bytes = (unsigned)dyb;
+  void (*kern)(WgradArgs);
+  if (bf16) kern = a.row_uniform ? conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
+  else kern = a.row_uniform ? conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
+  return launch_kernel(rec[bf16][a.row_uniform], kern, grid, block, 0, 0, s, 2.0 * (double)a.M * a.co * a.J, "conv_wgrad launch", a);
 }
 
 

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "halo_common.h"
+#include "launch.h"
 
 namespace udaseg {
 
@@ -836,62 +837,33 @@ static int launch_h2_t(const udaseg_conv_desc* d, const void* x, const void* x2,
   a.x_bytes = (unsigned)(up_ca > 0 ? (long long)d->n * (d->hi / 2) * (d->wi / 2) * up_ca * C::ES : px * d->ci * C::ES);
   a.x2_bytes = (unsigned)(up_ca > 0 ? px * (d->ci - up_ca) * C::ES : 0);
   a.dy_bytes = (unsigned)(px * d->co * C::ES);
+  // the kernel of this launch, its record and its text; the stamped twin is booked under the plain symbol
+  static KernelRec plain("hipFuncSetAttribute(conv_wgrad_h2)", "conv_wgrad_h2_kernel<%d, %d, %d, %d, %d, %d, %s, false, false>", PL, COQ, CIQ,
+                         TR, TWK, NSTW, DB ? "true" : "false");
+  KernelRec* rec = &plain;
   auto kern = conv_wgrad_h2_kernel<PL, COQ, CIQ, TR, TWK, NSTW, DB>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_h2)");
-    attr_done = true;
-  }
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_wgrad_h2_kernel<%d, %d, %d, %d, %d, %d, %s, false, false>", PL, COQ, CIQ, TR, TWK, NSTW, DB ? "true" : "false");
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
+  const char* what = "conv_wgrad_h2 launch";
   if constexpr (PL == 3 && COQ == 2 && CIQ == 2 && TWK == 2) {      // the dominant configuration has a stamped twin (diagnosis only)
     // (never for a launch that transforms x while staging: the twin has no XF form and would multiply the RAW tensor)
     if (g_timeline != nullptr && a.in_scale == nullptr && (long long)a.pairs * P * 16 <= (long long)g_timeline_blocks * 6) {
-      auto kern_tl = conv_wgrad_h2_kernel<PL, COQ, CIQ, TR, TWK, NSTW, DB, true>;
-      static std::atomic<bool> tl_attr{false};
-      if (!tl_attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_tl), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_h2 timeline twin)");
-        tl_attr = true;
-      }
+      static KernelRec tl("hipFuncSetAttribute(conv_wgrad_h2 timeline twin)", "conv_wgrad_h2_kernel<%d, %d, %d, %d, %d, %d, %s, false, false>",
+                          PL, COQ, CIQ, TR, TWK, NSTW, DB ? "true" : "false");
+      rec = &tl;
+      kern = conv_wgrad_h2_kernel<PL, COQ, CIQ, TR, TWK, NSTW, DB, true>;
+      what = "conv_wgrad_h2 (timeline) launch";
       a.timeline = g_timeline;
-      hipLaunchKernelGGL(kern_tl, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, s, a);
-      kprof_end(kid, ev, s, 2.0 * (double)px * d->co * 9.0 * d->ci);
-      UDASEG_LAUNCH_CHECK("conv_wgrad_h2 (timeline) launch");
-      return UDASEG_OK;
     }
   }
   if constexpr (PL == 3) {
     if (a.in_scale != nullptr) {          // the instantiation that transforms x while it stages (WgradH2Args::in_scale)
-      auto kern_xf = conv_wgrad_h2_kernel<PL, COQ, CIQ, TR, TWK, NSTW, DB, false, true>;
-      static std::atomic<bool> xf_attr{false};
-      if (!xf_attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_xf), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_h2, in-staging transform)");
-        xf_attr = true;
-      }
-      static std::atomic<int> kid_xf{-1};
-      if (kid_xf < 0) {
-        char nm[112];
-        snprintf(nm, sizeof(nm), "conv_wgrad_h2_kernel<%d, %d, %d, %d, %d, %d, %s, false, true>", PL, COQ, CIQ, TR, TWK, NSTW, DB ? "true" : "false");
-        kid_xf = kprof_id(nm);
-      }
-      hipLaunchKernelGGL(kern_xf, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, s, a);
-      kprof_end(kid_xf, ev, s, 2.0 * (double)px * d->co * 9.0 * d->ci);
-      UDASEG_LAUNCH_CHECK("conv_wgrad_h2 (in-staging transform) launch");
-      return UDASEG_OK;
+      static KernelRec xf("hipFuncSetAttribute(conv_wgrad_h2, in-staging transform)",
+                          "conv_wgrad_h2_kernel<%d, %d, %d, %d, %d, %d, %s, false, true>", PL, COQ, CIQ, TR, TWK, NSTW, DB ? "true" : "false");
+      rec = &xf;
+      kern = conv_wgrad_h2_kernel<PL, COQ, CIQ, TR, TWK, NSTW, DB, false, true>;
+      what = "conv_wgrad_h2 (in-staging transform) launch";
     }
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, 2.0 * (double)px * d->co * 9.0 * d->ci);
-  UDASEG_LAUNCH_CHECK("conv_wgrad_h2 launch");
-  return UDASEG_OK;
+  return launch_kernel(*rec, kern, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, C::LDS, s, 2.0 * (double)px * d->co * 9.0 * d->ci, what, a);
 }
 
 template <typename C>
@@ -919,23 +891,12 @@ static int launch_h2p_t(const udaseg_conv_desc* d, const void* x, const void* dy
   if constexpr (!C::UP) {
     if (xf) kern = conv_wgrad_h2_kernel<3, C, true>;
   }
-  static std::atomic<bool> attr_done[2] = {};
-  if (!attr_done[xf]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_h2, pair-packed)");
-    attr_done[xf] = true;
-  }
-  static std::atomic<int> kid[2] = {{-1}, {-1}};
-  if (kid[xf] < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_wgrad_h2_kernel<3, udaseg::H2P%s<%d, %d>, %s>", C::UP ? "U" : "", C::TR, C::TWK, xf ? "true" : "false");
-    kid[xf] = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid[xf], ev, s, 2.0 * (double)px * d->co * 9.0 * d->ci);
-  UDASEG_LAUNCH_CHECK("conv_wgrad_h2 (pair-packed) launch");
-  return UDASEG_OK;
+  static KernelRec rec[2] = {{"hipFuncSetAttribute(conv_wgrad_h2, pair-packed)", "conv_wgrad_h2_kernel<3, udaseg::H2P%s<%d, %d>, false>",
+                              C::UP ? "U" : "", C::TR, C::TWK},
+                             {"hipFuncSetAttribute(conv_wgrad_h2, pair-packed)", "conv_wgrad_h2_kernel<3, udaseg::H2P%s<%d, %d>, true>",
+                              C::UP ? "U" : "", C::TR, C::TWK}};
+  return launch_kernel(rec[xf], kern, dim3((unsigned)(a.pairs * P)), dim3(C::NT), C::LDS, C::LDS, s, 2.0 * (double)px * d->co * 9.0 * d->ci,
+                       "conv_wgrad_h2 (pair-packed) launch", a);
 }
 
 int launch_wgrad_h2(const udaseg_conv_desc* d, const void* x, const void* x2, int up_ca, const void* dy, float* dw, bool f32,
@@ -1227,24 +1188,9 @@ static int launch_h2up_t(const udaseg_conv_desc* d, const float* a_, int up_ca, 
   const long long pa = (long long)a.n * a.h * a.w;
   a.x_bytes = (unsigned)(pa * up_ca * 4);
   a.dy_bytes = (unsigned)(4 * pa * d->co * 4);
-  auto kern = conv_wgrad_up_kernel<COQ, CIQ, TR, TWK>;
-  static std::atomic<bool> attr_done{false};
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(conv_wgrad_up)");
-    attr_done = true;
-  }
-  static std::atomic<int> kid{-1};
-  if (kid < 0) {
-    char nm[96];
-    snprintf(nm, sizeof(nm), "conv_wgrad_up_kernel<%d, %d, %d, %d>", COQ, CIQ, TR, TWK);
-    kid = kprof_id(nm);
-  }
-  hipEvent_t ev = kprof_begin(s);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(2 * a.pairs * P)), dim3(C::NT), C::LDS, s, a);
-  kprof_end(kid, ev, s, 2.0 * (double)pa * d->co * 16.0 * up_ca);
-  UDASEG_LAUNCH_CHECK("conv_wgrad_up launch");
-  return UDASEG_OK;
+  static KernelRec rec("hipFuncSetAttribute(conv_wgrad_up)", "conv_wgrad_up_kernel<%d, %d, %d, %d>", COQ, CIQ, TR, TWK);
+  return launch_kernel(rec, conv_wgrad_up_kernel<COQ, CIQ, TR, TWK>, dim3((unsigned)(2 * a.pairs * P)), dim3(C::NT), C::LDS, C::LDS, s,
+                       2.0 * (double)pa * d->co * 16.0 * up_ca, "conv_wgrad_up launch", a);
 }
 
 }  // namespace udaseg

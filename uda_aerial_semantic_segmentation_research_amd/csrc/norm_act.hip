@@ -10,6 +10,7 @@
 // (vectors per pixel) == 0, hence every thread meets the same channels on every grid-stride step and keeps its per-channel
 // partials in registers; one LDS pass folds the rows of a block, one f64 atomic per channel per block folds the blocks (f64:
 // the cross-block order no longer shows after rounding to f32).
+#include "launch.h"
 #include "vec16.h"
 
 namespace udaseg {
@@ -444,8 +445,8 @@ extern "C" int udaseg_bn_stats_bf16(const void* y, int64_t pixels, int c, double
   UDASEG_CHECK_ARG(y && sums, "bn_stats_bf16: NULL pointer");
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, reduce_max_blocks());
-  static std::atomic<int> kid_bn_stats_bf16_kernel{-1};
-  KTimer kt_bn_stats_bf16_kernel(&kid_bn_stats_bf16_kernel, "bn_stats_bf16_kernel", as_stream(stream), (double)pixels * c * 2.0);
+  static KernelRec rec_bn_stats_bf16_kernel(nullptr, "bn_stats_bf16_kernel");
+  KTimer kt_bn_stats_bf16_kernel(rec_bn_stats_bf16_kernel, as_stream(stream), (double)pixels * c * 2.0);
   hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(s.grid), dim3(s.bs), 0, as_stream(stream), (const f32x4*)y, n8, s.c4, sums);
   UDASEG_LAUNCH_CHECK("bn_stats_bf16 launch");
   return UDASEG_OK;
@@ -461,8 +462,8 @@ extern "C" int udaseg_bn_apply(const float* y, const double* sums, const float* 
   UDASEG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_apply: running_mean/var must come together");
   const int64_t n4 = pixels * (c / 4);
   const StreamShape s = stream_shape(n4, c / 4, 2048, apply_per_thread());
-  static std::atomic<int> kid_ba{-1};
-  KTimer kt_ba(&kid_ba, "bn_apply_kernel", as_stream(stream), (double)pixels * c * 4.0 * (residual ? 3.0 : 2.0));
+  static KernelRec rec_ba(nullptr, "bn_apply_kernel");
+  KTimer kt_ba(rec_ba, as_stream(stream), (double)pixels * c * 4.0 * (residual ? 3.0 : 2.0));
   hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(s.grid), dim3(s.bs), (size_t)2 * s.c4 * sizeof(float4), as_stream(stream), (const f32x4*)y, sums, gamma, beta,
                      (const f32x4*)residual, (f32x4*)z, n4, s.c4, pixels, eps, momentum, running_mean, running_var,
                      save_mean, save_rstd, act, slope);
@@ -479,8 +480,8 @@ extern "C" int udaseg_bn_apply_bf16(const void* y, const double* sums, const flo
   UDASEG_CHECK_ARG(y && sums && gamma && beta && z, "bn_apply_bf16: NULL pointer");
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, 2048, apply_per_thread());
-  static std::atomic<int> kid_bn_apply_bf16_kernel{-1};
-  KTimer kt_bn_apply_bf16_kernel(&kid_bn_apply_bf16_kernel, "bn_apply_bf16_kernel", as_stream(stream), (double)pixels * c * 2.0 * (residual ? 3.0 : 2.0));
+  static KernelRec rec_bn_apply_bf16_kernel(nullptr, "bn_apply_bf16_kernel");
+  KTimer kt_bn_apply_bf16_kernel(rec_bn_apply_bf16_kernel, as_stream(stream), (double)pixels * c * 2.0 * (residual ? 3.0 : 2.0));
   hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(s.grid), dim3(s.bs), (size_t)2 * c * sizeof(float), as_stream(stream),
                      (const f32x4*)y, sums, gamma, beta, (const f32x4*)residual, (f32x4*)z, n8, s.c4, pixels, eps, momentum,
                      running_mean, running_var, save_mean, save_rstd, act, slope);
@@ -522,8 +523,8 @@ extern "C" int udaseg_bn_bwd_reduce(const float* dz, const float* z, const float
                    "bn_bwd_reduce: an activation follows the norm: pass z, or gamma and beta to re-evaluate its argument");
   const int64_t n4 = pixels * (c / 4);
   const StreamShape s = stream_shape(n4, c / 4, reduce_max_blocks());
-  static std::atomic<int> kid_br{-1};
-  KTimer kt_br(&kid_br, "bn_bwd_reduce_kernel", as_stream(stream), (double)pixels * c * 4.0 * (z ? 3.0 : 2.0));
+  static KernelRec rec_br(nullptr, "bn_bwd_reduce_kernel");
+  KTimer kt_br(rec_br, as_stream(stream), (double)pixels * c * 4.0 * (z ? 3.0 : 2.0));
   hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(s.grid), dim3(s.bs), 0, as_stream(stream), (const f32x4*)dz, (const f32x4*)z,
                      (const f32x4*)y, save_mean, save_rstd, gamma, beta, n4, s.c4, bsums, act, slope);
   UDASEG_LAUNCH_CHECK("bn_bwd_reduce launch");
@@ -538,8 +539,8 @@ extern "C" int udaseg_bn_bwd_reduce_bf16(const void* dz, const void* z, const vo
   UDASEG_CHECK_ARG(dz && y && save_mean && save_rstd && bsums && (act == UDASEG_ACT_NONE || z), "bn_bwd_reduce_bf16: NULL pointer");
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, reduce_max_blocks());
-  static std::atomic<int> kid_bn_bwd_reduce_bf16_kernel{-1};
-  KTimer kt_bn_bwd_reduce_bf16_kernel(&kid_bn_bwd_reduce_bf16_kernel, "bn_bwd_reduce_bf16_kernel", as_stream(stream), (double)pixels * c * 2.0 * (act != UDASEG_ACT_NONE ? 3.0 : 2.0));
+  static KernelRec rec_bn_bwd_reduce_bf16_kernel(nullptr, "bn_bwd_reduce_bf16_kernel");
+  KTimer kt_bn_bwd_reduce_bf16_kernel(rec_bn_bwd_reduce_bf16_kernel, as_stream(stream), (double)pixels * c * 2.0 * (act != UDASEG_ACT_NONE ? 3.0 : 2.0));
   hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(s.grid), dim3(s.bs), 0, as_stream(stream), (const f32x4*)dz,
                      (const f32x4*)z, (const f32x4*)y, save_mean, save_rstd, (const float*)nullptr, (const float*)nullptr, n8,
                      s.c4, bsums, act, slope);
@@ -559,8 +560,8 @@ extern "C" int udaseg_bn_bwd_apply(const float* dz, const float* z, const float*
                    "bn_bwd_apply: an activation follows the norm: pass z, or beta to re-evaluate its argument");
   const int64_t n4 = pixels * (c / 4);
   const StreamShape s = stream_shape(n4, c / 4, 2048, apply_per_thread());
-  static std::atomic<int> kid_bw{-1};
-  KTimer kt_bw(&kid_bw, "bn_bwd_apply_kernel", as_stream(stream), (double)pixels * c * 4.0 * ((z ? 4.0 : 3.0) + (dres ? 1.0 : 0.0)));
+  static KernelRec rec_bw(nullptr, "bn_bwd_apply_kernel");
+  KTimer kt_bw(rec_bw, as_stream(stream), (double)pixels * c * 4.0 * ((z ? 4.0 : 3.0) + (dres ? 1.0 : 0.0)));
   hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(s.grid), dim3(s.bs), (size_t)6 * s.c4 * sizeof(float4), as_stream(stream), (const f32x4*)dz, (const f32x4*)z,
                      (const f32x4*)y, save_mean, save_rstd, gamma, beta, bsums, (f32x4*)dy, (f32x4*)dres, dgamma, dbeta, n4, s.c4,
                      pixels, act, slope, accumulate_dy, accumulate_dres, accumulate_param, (const float*)nullptr,
@@ -583,8 +584,8 @@ extern "C" int udaseg_bn_bwd_apply_bf16(const void* dz, const void* z, const voi
                    UDASEG_BN_BWD_APPLY_BF16_MAX_C);
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, 2048, apply_per_thread());
-  static std::atomic<int> kid_bwa{-1};
-  KTimer kt_bwa(&kid_bwa, "bn_bwd_apply_bf16_kernel", as_stream(stream), (double)pixels * c * 2.0 * ((act != UDASEG_ACT_NONE ? 4.0 : 3.0) + (dres ? 1.0 : 0.0)));
+  static KernelRec rec_bwa(nullptr, "bn_bwd_apply_bf16_kernel");
+  KTimer kt_bwa(rec_bwa, as_stream(stream), (double)pixels * c * 2.0 * ((act != UDASEG_ACT_NONE ? 4.0 : 3.0) + (dres ? 1.0 : 0.0)));
   hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(s.grid), dim3(s.bs), (size_t)5 * c * sizeof(float), as_stream(stream),
                      (const f32x4*)dz, (const f32x4*)z, (const f32x4*)y, save_mean, save_rstd, gamma, (const float*)nullptr, bsums,
                      (f32x4*)dy, (f32x4*)dres, dgamma, dbeta, n8, s.c4, pixels, act, slope, accumulate_dy, accumulate_dres,
@@ -607,8 +608,8 @@ extern "C" int udaseg_bn_bwd_apply_recompute_bf16(const void* dz, const void* y,
                    UDASEG_BN_BWD_RECOMPUTE_BF16_MAX_C);
   const int64_t n8 = pixels * (c / 8);
   const StreamShape s = stream_shape(n8, c / 8, 2048, apply_per_thread());
-  static std::atomic<int> kid_bwr{-1};
-  KTimer kt_bwr(&kid_bwr, "bn_bwd_apply_bf16_kernel", as_stream(stream), (double)pixels * c * 2.0 * 3.0);
+  static KernelRec rec_bwr(nullptr, "bn_bwd_apply_bf16_kernel");
+  KTimer kt_bwr(rec_bwr, as_stream(stream), (double)pixels * c * 2.0 * 3.0);
   hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(s.grid), dim3(s.bs), (size_t)7 * c * sizeof(float), as_stream(stream),
                      (const f32x4*)dz, (const f32x4*)nullptr, (const f32x4*)y, save_mean, save_rstd, gamma, (const float*)nullptr,
                      bsums, (f32x4*)dy, (f32x4*)nullptr, dgamma, dbeta, n8, s.c4, pixels, act, slope, 0, 0, 0, fwd_scale, fwd_shift);
