@@ -300,6 +300,52 @@ int udaseg_ce_opt_bwd(const float* logits, const int64_t* target, const float* w
                       const float* grad_px, int64_t pixels, int classes, int ldc, int has_ignore, int64_t ignore_index, float eps,
                       int mean, const double* denom, float* dlogits, float* colsum_partials, float* colsum, void* stream);
 
+/* ---- hard-pixel mining for the cross entropy (csrc/ohem.hip): OHEM (keep p < thresh, but at least min_kept pixels) and the
+ * bootstrapped / top-k cross entropy (keep the hardest fraction), exact on the device: no sort, no host read, same bits every run.
+ * logits: padded NHWC fp32 [pixels][ldc], ldc % 4 == 0, classes <= ldc <= 32, 0 < pixels < 2^31; target int64; weight optional.
+ *   valid(p):      as udaseg_ce_opt_*.  A valid pixel whose row (channels < classes) is not all finite is NON-FINITE: void,
+ *                  counted on its own, loss and gradient exactly 0.
+ *   confidence:    m = the first maximum of the row, S = sum_c expf(z_c - m) in udaseg_conf_hist's order, p = expf(z_t - m) / S of
+ *                  the TARGET class: 0 <= p <= 1, so the fp32 bits of p are an order-preserving unsigned integer below 2^30.
+ *                  conf[pixel] = p; -1.0f at void, out-of-range and non-finite pixels.
+ *   selection:     n = number of valid finite pixels; k = min_kept, or ceil(fraction * n) in float64 when fraction >= 0;
+ *                  q = the k-th smallest p (1-indexed); -inf when k == 0, +inf when k > n.
+ *                  kept(p) iff conf[p] >= 0 and (p < thresh or p <= q).  Ties at q are ALL kept: the kept set depends on the
+ *                  values alone (not on pixel order or launch shape) and holds at least min(k, n) pixels.  Top-k is thresh = 0.
+ *   loss:          l = -w[t] * log softmax(z)[t] over the kept pixels; 'mean' divides by D = the fixed-order f64 sum of w[t]
+ *                  over the kept pixels (no kept pixel: NaN loss, all-zero gradient; 'sum': 0).
+ *   gradient:      exactly 0 in all ldc lanes of every pixel that is not kept.
+ * The k-th smallest is a three-level radix select over the 30 value bits, 10 bits a level (bits 29..20, 19..10, 9..0).
+ * hist: int64 [1024] per level, ZEROED BY THE CALLER.  state: int64 [UDASEG_KTH_STATE], ZEROED BY THE CALLER before level 0:
+ *   state[0]  prefix: the bits of q found so far (after level L, bits 29 .. 20 - 10 L); after level 2 the exact fp32 bits of q
+ *   state[1]  rank still to find inside the prefix's bin (1-indexed; 0: nothing is selected, k == 0 or n == 0)
+ *   state[2]  n          state[3]  k          state[4]  flags: bit 0 k == 0, bit 1 k >= n          state[5]  levels done
+ *   state[6..7] unused (0)
+ * udaseg_kth_hist + udaseg_kth_select are a primitive of their own: the exact k-th smallest of a device buffer of floats in
+ * [0, 2); a value with its sign bit set or >= 2 (-1.0f, inf, NaN) is skipped and not counted in n. */
+#define UDASEG_KTH_STATE 8
+/* One pass over the logits: conf, hist0 += the histogram of bits 29..20 of p over the valid finite pixels,
+ * counters[0..2] += {void (== ignore_index), out-of-range targets, non-finite rows} (int64, zeroed by the caller). */
+int udaseg_ohem_conf(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, int has_ignore,
+                     int64_t ignore_index, float* conf, int64_t* hist0, int64_t* counters, void* stream);
+/* hist += the 10-bit histogram of `level` (0, 1, 2) over the values whose higher bits equal state's prefix (level 0: all values
+ * in [0, 2); state may be NULL there). */
+int udaseg_kth_hist(const float* values, int64_t count, int level, const int64_t* state, int64_t* hist, void* stream);
+/* One block, bounded loops.  Level 0: n = the histogram's total, k from min_kept (>= 0; fraction < 0) or from fraction (in
+ * [0, 1]); every level: the bin that holds the rank, into state.  Levels 1 and 2 ignore min_kept and fraction. */
+int udaseg_kth_select(const int64_t* hist, int level, int64_t min_kept, double fraction, int64_t* state, void* stream);
+/* out[0] = q, out[1] = max(q, thresh) from a state after level 2. */
+int udaseg_kth_value(const int64_t* state, float thresh, float* out, void* stream);
+/* One pass over conf, target and weight (no logits): *denom = D (f64, udaseg_ce_target_stats' order), counts[0..1] = {valid finite,
+ * kept} pixels, keep[p] = 1 / 0 (uint8, optional); partials: 3*udaseg_ce_partials() doubles. */
+int udaseg_ohem_denom(const float* conf, const int64_t* target, const float* weight, int64_t pixels, int classes, float thresh,
+                      const int64_t* state, double* partials, double* denom, int64_t* counts, uint8_t* keep, void* stream);
+/* udaseg_ce_opt_fwd_bwd with the keep predicate, read from conf and state (what the selection itself used): loss, dlogits for an
+ * upstream gradient of 1 (divided by *denom when mean != 0), optional column sums.  dlogits == NULL: the loss alone. */
+int udaseg_ce_ohem_fwd_bwd(const float* logits, const int64_t* target, const float* weight, const float* conf, const int64_t* state,
+                           float thresh, int64_t pixels, int classes, int ldc, int mean, const double* denom, double* partials,
+                           float* loss, float* dlogits, float* colsum_partials, float* colsum, void* stream);
+
 /* ---- the reference's other segmentation losses (src/models/losses.py), same logits layout as udaseg_ce_* (ldc <= 32) ----
  * udaseg_seg_partials(): doubles of scratch the *_fwd calls below need in `partials`. */
 int udaseg_seg_partials(void);

@@ -1,0 +1,395 @@
+"""Hard-pixel mining for the cross entropy on the device (csrc/ohem.hip, losses.OhemCrossEntropyLoss / TopKCrossEntropyLoss) against
+the numpy mirror tests/_ohem_ref.py.
+
+What is integer work is compared for EQUALITY: the mirror's selection is applied to the confidences the kernel wrote, and the keep
+mask, q (as bits), n, k and every counter must be equal.  What is floating point is graded element-wise against float64 under
+tests/_grade.Grader's bar max(4 x max(d), 2^-22), d the deviation of the same arithmetic in fp32: the confidences, and the loss,
+the gradient and the column sums of the mirror GIVEN THE KERNEL'S KEEP MASK.  Every pixel that is not kept holds exact zeros in all
+ldc lanes of the gradient.
+
+Inputs: logits 3 * randn; the target is the argmax at 70 % of the pixels and random elsewhere; 10 % void (255), a few targets out
+of range, one row with an inf.  Pad lanes of the logits hold junk (7.0, one lane 1e30), the gradient buffer is pre-filled with junk.
+CASES holds a thresh-dominated selection (q < thresh) and a k-dominated one (q >= thresh); ``preconditions`` states that, and that
+no kept set is empty or everything, from the mirror alone (it runs without a GPU).
+"""
+import numpy as np
+import pytest
+import torch
+
+import _ohem_ref as R
+from _grade import Grader
+
+pytestmark = pytest.mark.gpu
+
+GRID_PIXELS = 1024 * 256                 # pixels one full grid of the pixel kernels takes in one trip (udaseg_ce_partials() blocks)
+SHAPES = [(2, 5, 9, 7),                  # 126 pixels: less than one chunk; ldc 8 with three pad lanes
+          (2, 23, 37, 41),               # 3034 pixels: eleven full chunks and a tail; ldc 24 with one pad lane
+          (1, 32, 16, 16),               # ldc 32: no pad lane
+          (1, 5, 513, 512)]              # 262 656 pixels: two chunks past one full grid, the grid-stride loops run twice
+IGN = 255
+# thresh, min_kept as a share of the pixels / keep_fraction, class weights, reduction
+CASES = {"thresh_dominated": dict(thresh=0.7, min_share=0.02, weighted=False, mean=True),
+         "k_dominated": dict(thresh=0.05, min_share=0.3, weighted=True, mean=True),
+         "top_quarter_sum": dict(fraction=0.25, weighted=True, mean=False)}
+
+
+class OhemGrader(Grader):
+    PREFIX = "ohem-grade"
+
+
+@pytest.fixture(scope="module")
+def env():
+    from uda_aerial_semantic_segmentation_research_amd import _lib, kernels, losses
+    _lib.require_gpu()
+    return kernels, losses, _lib.load().udaseg_ce_partials()
+
+
+def ceil4(c):
+    return (c + 3) // 4 * 4
+
+
+_INPUTS = {}
+
+
+def inputs(shape):
+    """(z [N,C,H,W] fp32, t [N,H,W] int64, weights [C]) as the module docstring says; made once per shape."""
+    if shape not in _INPUTS:
+        n, c, h, w = shape
+        g = torch.Generator().manual_seed(50 + SHAPES.index(shape))
+        z = torch.randn(n, c, h, w, generator=g) * 3.0
+        t = z.argmax(1)
+        r = torch.rand(n, h, w, generator=g)
+        rnd = torch.randint(0, c, (n, h, w), generator=g)
+        t = torch.where(r < 0.3, rnd, t)
+        r = torch.rand(n, h, w, generator=g)
+        t[r < 0.10] = IGN
+        t[(r >= 0.10) & (r < 0.12)] = c
+        t[(r >= 0.12) & (r < 0.13)] = -3
+        flat_t = t.view(-1)
+        live = ((flat_t >= 0) & (flat_t < c)).nonzero()[:, 0]
+        px = int(live[len(live) // 2])                       # a pixel with a valid target gets an inf: non-finite
+        zf = z.permute(0, 2, 3, 1).reshape(-1, c)
+        zf[px, (int(flat_t[px]) + 1) % c] = float("inf")
+        z = zf.reshape(n, h, w, c).permute(0, 3, 1, 2).contiguous()
+        wt = torch.rand(c, generator=g) + 0.1
+        _INPUTS[shape] = (z, t, wt)
+    return _INPUTS[shape]
+
+
+def rows(z):
+    n, c, h, w = z.shape
+    return z.permute(0, 2, 3, 1).reshape(-1, c).numpy()
+
+
+def case_args(shape, case):
+    cfg = CASES[case]
+    pixels = shape[0] * shape[2] * shape[3]
+    if "fraction" in cfg:
+        return dict(thresh=0.0, min_kept=None, fraction=cfg["fraction"])
+    return dict(thresh=cfg["thresh"], min_kept=max(1, int(cfg["min_share"] * pixels)), fraction=None)
+
+
+def preconditions(shapes=SHAPES):
+    """From the mirror alone: no case keeps nothing or everything; the case set has q < thresh and q >= thresh."""
+    seen = set()
+    for shape in shapes:
+        z, t, _ = inputs(shape)
+        conf, _ = R.confidence(rows(z), t.view(-1).numpy(), IGN, R.F32)
+        for case in CASES:
+            a = case_args(shape, case)
+            s = R.select(conf, a["thresh"], a["min_kept"], a["fraction"])
+            assert 0 < s["keep"].sum() < s["n"], (shape, case, int(s["keep"].sum()), s["n"])
+            if a["fraction"] is None:
+                seen.add("thresh" if s["q"] < np.float32(a["thresh"]) else "k")
+    assert seen == {"thresh", "k"}, seen
+
+
+def pipeline(env, z, t, weight, thresh, min_kept, fraction, mean, grad=True):
+    """The launches of OhemCrossEntropyLoss on a buffer with junk in the pad lanes; every result as numpy."""
+    K, _, np_ = env
+    n, c, h, w = z.shape
+    ldc, pixels = ceil4(c), n * h * w
+    buf = torch.full((pixels, ldc), 7.0)
+    buf[:, :c] = z.permute(0, 2, 3, 1).reshape(pixels, c)
+    if ldc > c:
+        buf[:, ldc - 1] = 1e30
+    buf, tgt = buf.cuda(), t.reshape(-1).cuda()
+    wd = None if weight is None else weight.cuda()
+    ws = torch.zeros(3 * K.KTH_BINS + K.KTH_STATE + 5, device="cuda", dtype=torch.int64)
+    hist, state, stats = ws[:3 * K.KTH_BINS].view(3, K.KTH_BINS), ws[3 * K.KTH_BINS:3 * K.KTH_BINS + K.KTH_STATE], ws[-5:]
+    conf = torch.empty(pixels, device="cuda")
+    K.ohem_conf(buf, tgt, pixels, c, ldc, IGN, conf, hist[0], stats[2:5])
+    K.kth_select(hist[0], 0, state, min_kept=min_kept or 0, fraction=-1.0 if fraction is None else fraction)
+    K.kth_refine(conf, hist, state)
+    denom = torch.empty(1, device="cuda", dtype=torch.float64)
+    keep = torch.full((pixels,), 9, device="cuda", dtype=torch.uint8)
+    K.ohem_denom(conf, tgt, wd, pixels, c, thresh, state, torch.empty(3 * np_, device="cuda", dtype=torch.float64), denom, stats[0:2], keep)
+    thr = torch.empty(2, device="cuda")
+    K.kth_value(state, thresh, thr)
+    loss = torch.empty((), device="cuda")
+    partials = torch.empty(np_, device="cuda", dtype=torch.float64)
+    dl = colsum = None
+    if grad:
+        dl = torch.full((pixels, ldc), 123.0, device="cuda")
+        colsum = torch.empty(ldc, device="cuda")
+        K.ce_ohem_fwd_bwd(buf, tgt, wd, conf, state, thresh, pixels, c, ldc, mean, denom, partials, loss, dl,
+                          torch.empty(np_ * ldc, device="cuda"), colsum)
+    else:
+        K.ce_ohem_fwd_bwd(buf, tgt, wd, conf, state, thresh, pixels, c, ldc, mean, denom, partials, loss)
+    out = dict(conf=conf, hist=hist, state=state, stats=stats, denom=denom, keep=keep, thr=thr, loss=loss, dl=dl, colsum=colsum)
+    return {k: (None if v is None else v.cpu().numpy()) for k, v in out.items()}
+
+
+_RUNS = {}
+
+
+def run(env, shape, case):
+    if (shape, case) not in _RUNS:
+        z, t, wt = inputs(shape)
+        a = case_args(shape, case)
+        _RUNS[(shape, case)] = pipeline(env, z, t, wt if CASES[case]["weighted"] else None, a["thresh"], a["min_kept"], a["fraction"],
+                                        CASES[case]["mean"])
+    return _RUNS[(shape, case)]
+
+
+def fbits(x):
+    return np.asarray(x, dtype=np.float32).reshape(-1).view(np.uint32)
+
+
+def test_the_case_set_meets_its_preconditions(env):
+    preconditions()
+    n, _, h, w = SHAPES[3]
+    assert GRID_PIXELS == 256 * env[2] < n * h * w                              # the last shape does pass one full grid
+
+
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_selection_equals_the_mirror_on_the_kernels_confidences(env, shape, case):
+    z, t, _ = inputs(shape)
+    a = case_args(shape, case)
+    got = run(env, shape, case)
+    live, void, invalid, nonfinite = R.pixel_classes(t.view(-1).numpy(), shape[1], IGN, rows(z))
+    assert nonfinite.sum() == 1 and invalid.sum() > 0 and void.sum() > 0
+    assert ((got["conf"] >= 0) == live).all() and (got["conf"][~live] == -1.0).all()
+    assert (got["conf"][live] <= 1.0).all()
+    s = R.select(got["conf"], a["thresh"], a["min_kept"], a["fraction"])
+    assert 0 < s["keep"].sum() < s["n"]
+    assert (got["keep"] == s["keep"].astype(np.uint8)).all()
+    st = got["state"]
+    assert (int(st[2]), int(st[3])) == (s["n"], s["k"]) and int(st[5]) == 3
+    assert int(st[4]) == (1 if s["k"] <= 0 else 0) | (2 if s["k"] >= s["n"] else 0)
+    assert fbits(got["thr"][0])[0] == fbits(s["q"])[0] == np.uint32(st[0])
+    assert fbits(got["thr"][1])[0] == fbits(max(s["q"], np.float32(a["thresh"])))[0]
+    assert got["stats"].tolist() == [int(live.sum()), int(s["keep"].sum()), int(void.sum()), int(invalid.sum()), 1]
+    assert int(got["hist"][0].sum()) == s["n"]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_confidence_against_float64(env, shape):
+    z, t, _ = inputs(shape)
+    got = run(env, shape, "thresh_dominated")
+    r64, mag = R.confidence(rows(z), t.view(-1).numpy(), IGN, R.F64)
+    r32, _ = R.confidence(rows(z), t.view(-1).numpy(), IGN, R.F32)
+    live = r64 >= 0
+    g = OhemGrader(f"conf {shape}")
+    g.grade("conf", got["conf"][live], r64[live], r32[live], mag[live])
+    g.done()
+
+
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_loss_gradient_and_column_sums_given_the_kernels_keep_mask(env, shape, case):
+    z, t, wt = inputs(shape)
+    c, ldc = shape[1], ceil4(shape[1])
+    got = run(env, shape, case)
+    keep = got["keep"].astype(bool)
+    w = wt.numpy() if CASES[case]["weighted"] else None
+    mean = CASES[case]["mean"]
+    r64 = R.loss_and_grad(rows(z), t.view(-1).numpy(), w, keep, mean, R.F64)
+    r32 = R.loss_and_grad(rows(z), t.view(-1).numpy(), w, keep, mean, R.F32)
+    assert got["denom"][0] == r64["denom"]                                   # a float64 sum of fp32 weights in a fixed order: exact
+    assert (got["dl"][~keep] == 0).all() and (got["dl"][:, c:] == 0).all()   # exact zeros: all ldc lanes of the others, pad lanes
+    assert (got["colsum"][c:] == 0).all()
+    g = OhemGrader(f"{case} {shape}")
+    g.grade("loss", got["loss"], np.float64(r64["loss"][0]), np.float64(r32["loss"][0]), r64["loss"][1])
+    g.grade("grad", got["dl"][:, :c][keep], r64["grad"][0][keep], r32["grad"][0][keep], r64["grad"][1][keep])
+    g.grade("colsum", got["colsum"][:c], r64["colsum"][0], r32["colsum"][0], r64["colsum"][1])
+    g.done()
+
+
+def test_ties_at_q_are_all_kept(env):
+    """Logits from {0, 1}: the confidences take a few values only.  k is placed INSIDE a tie group of the kernel's own confidences;
+    the kept count then exceeds k by exactly what the mirror counts."""
+    K, L, _ = env
+    g = torch.Generator().manual_seed(77)
+    z = torch.randint(0, 2, (2, 5, 24, 24), generator=g).float()
+    t = torch.randint(0, 5, (2, 24, 24), generator=g)
+    t[0, :3] = IGN
+    first = pipeline(env, z, t, None, 0.0, 1, None, True, grad=False)
+    v = np.sort(first["conf"][first["conf"] >= 0])
+    vals, start, count = np.unique(v, return_index=True, return_counts=True)
+    assert len(vals) < 40 and count.max() >= 50
+    grp = int(np.argmax(count))
+    k = int(start[grp]) + int(count[grp]) // 2                                # 1-indexed rank strictly inside the group
+    assert v[k - 1] == v[k] == vals[grp]
+    crit = L.OhemCrossEntropyLoss(thresh=0.0, min_kept=k, ignore_index=IGN, keep_mask=True)
+    zc = z.cuda().requires_grad_(True)
+    crit(zc, t.cuda()).backward()
+    s = R.select(first["conf"], 0.0, k)
+    n_kept = int(crit.last_ohem_stats[1])
+    assert n_kept == int(s["keep"].sum()) == int(start[grp] + count[grp]) and n_kept > k
+    assert (crit.last_keep_mask.cpu().numpy().reshape(-1) == s["keep"]).all()
+    assert fbits(crit.last_threshold[0].item())[0] == fbits(vals[grp])[0]
+    gz = zc.grad.permute(0, 2, 3, 1).reshape(-1, 5).cpu().numpy()
+    assert (gz[~s["keep"]] == 0).all() and (np.abs(gz[s["keep"]]).sum(1) > 0).all()
+
+
+@pytest.mark.parametrize("fraction", (0.25, 1.0, 1e-7))
+def test_top_k(env, fraction):
+    _, L, _ = env
+    shape = SHAPES[1]
+    z, t, wt = inputs(shape)
+    got = pipeline(env, z, t, wt, 0.0, None, fraction, True)
+    s = R.select(got["conf"], 0.0, fraction=fraction)
+    assert s["k"] == {0.25: -(-s["n"] // 4), 1.0: s["n"], 1e-7: 1}[fraction]
+    assert (got["keep"] == s["keep"]).all() and int(got["state"][3]) == s["k"] and int(got["stats"][1]) == int(s["keep"].sum()) >= s["k"]
+    crit = L.TopKCrossEntropyLoss(fraction, weight=wt, ignore_index=IGN, keep_mask=True).cuda()
+    zc = z.cuda().requires_grad_(True)
+    loss = crit(zc, t.cuda())
+    loss.backward()
+    assert fbits(loss.item())[0] == fbits(got["loss"])[0]                      # the module is these launches
+    assert (crit.last_keep_mask.cpu().numpy().reshape(-1) == s["keep"]).all()
+    assert crit.last_ohem_stats.tolist() == got["stats"].tolist()
+    gz = zc.grad.permute(0, 2, 3, 1).reshape(-1, shape[1]).cpu().numpy()
+    assert (fbits(gz) == fbits(got["dl"][:, :shape[1]])).all()
+
+
+def test_min_kept_beyond_n_keeps_all_and_equals_cross_entropy(env):
+    _, L, _ = env
+    shape = SHAPES[1]
+    c = shape[1]
+    z, t, _ = inputs(shape)
+    live, _, _, nonfinite = R.pixel_classes(t.view(-1).numpy(), c, IGN, rows(z))
+    crit = L.OhemCrossEntropyLoss(thresh=0.3, min_kept=10 ** 9, ignore_index=IGN, keep_mask=True)
+    zc = z.cuda().requires_grad_(True)
+    loss = crit(zc, t.cuda())
+    loss.backward()
+    assert (crit.last_keep_mask.cpu().numpy().reshape(-1).astype(bool) == live).all()
+    assert crit.last_ohem_stats.tolist()[:2] == [int(live.sum())] * 2 and crit.last_threshold[0].item() == float("inf")
+    t_ce = t.clone().view(-1)
+    t_ce[torch.from_numpy(nonfinite)] = IGN                                   # "on the finite pixels"
+    z_ce = z.clone()
+    z_ce[~torch.isfinite(z_ce)] = 0.0
+    zc2 = z_ce.cuda().requires_grad_(True)
+    loss_ce = L.CrossEntropyLoss(ignore_index=IGN)(zc2, t_ce.view(t.shape).cuda())
+    loss_ce.backward()
+    r64 = R.loss_and_grad(rows(z), t.view(-1).numpy(), None, live, True, R.F64)
+    r32 = R.loss_and_grad(rows(z), t.view(-1).numpy(), None, live, True, R.F32)
+    g = OhemGrader(f"keep-all {shape}")
+    for name, lv, gv in (("ohem", loss, zc.grad), ("cross-entropy", loss_ce, zc2.grad)):
+        gz = gv.permute(0, 2, 3, 1).reshape(-1, c).cpu().numpy()
+        assert (gz[~live] == 0).all()
+        g.grade(f"{name} loss", lv.item(), np.float64(r64["loss"][0]), np.float64(r32["loss"][0]), r64["loss"][1])
+        g.grade(f"{name} grad", gz[live], r64["grad"][0][live], r32["grad"][0][live], r64["grad"][1][live])
+    g.done()
+
+
+def test_all_void_batch(env):
+    _, L, _ = env
+    z = torch.randn(1, 5, 20, 20, generator=torch.Generator().manual_seed(1))
+    t = torch.full((1, 20, 20), IGN)
+    for reduction, check in (("mean", np.isnan), ("sum", lambda v: v == 0.0)):
+        crit = L.OhemCrossEntropyLoss(thresh=0.7, min_kept=10, ignore_index=IGN, reduction=reduction)
+        zc = z.cuda().requires_grad_(True)
+        loss = crit(zc, t.cuda())
+        loss.backward()
+        assert check(loss.item()), (reduction, loss.item())
+        assert (zc.grad == 0).all()
+        assert crit.last_ohem_stats.tolist() == [0, 0, 400, 0, 0]
+
+
+def test_autograd_upstream_gradient_second_backward_and_no_grad(env):
+    _, L, _ = env
+    z, t, wt = inputs(SHAPES[1])
+    crit = L.OhemCrossEntropyLoss(thresh=0.7, min_kept=100, weight=wt, ignore_index=IGN).cuda()
+    zc = z.cuda().requires_grad_(True)
+    loss = crit(zc, t.cuda())
+    g1, = torch.autograd.grad(loss, zc, retain_graph=True)
+    g2, = torch.autograd.grad(loss, zc, retain_graph=True)                    # a second backward: the launch again on conf / state
+    assert torch.equal(g1.view(torch.int32), g2.view(torch.int32))
+    g3, = torch.autograd.grad(loss * 2.5, zc)
+    assert torch.equal(g3, g1 * 2.5) and float(g1.abs().sum()) > 0
+    loss_b = crit(z.cuda().requires_grad_(True), t.cuda())
+    with torch.no_grad():
+        loss_ng = crit(z.cuda(), t.cuda())
+    assert not loss_ng.requires_grad
+    assert fbits(loss.item())[0] == fbits(loss_b.item())[0] == fbits(loss_ng.item())[0]
+
+
+def test_two_calls_are_bit_identical(env):
+    _, L, _ = env
+    z, t, wt = inputs(SHAPES[3])
+    crit = L.OhemCrossEntropyLoss(thresh=0.6, min_kept=5000, weight=wt, ignore_index=IGN).cuda()
+    res = []
+    for _ in range(2):
+        zc = z.cuda().requires_grad_(True)
+        loss = crit(zc, t.cuda())
+        loss.backward()
+        res.append((loss.detach().clone(), zc.grad.clone(), crit.last_ohem_stats.clone(), crit.last_threshold.clone()))
+    for a, b in zip(*res):
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b)
+    assert int(res[0][2][1]) > 0
+
+
+def test_head_bias_gradient_comes_from_the_mined_column_sums(env):
+    """r18 Unet, 2x3x64x64, train mode: the head conv's bias gradient (handed over through COLSUM_SIDE_TABLE by the mined pass)
+    equals the pixel sum of the float64 gradient of the same logits over the kernel's kept pixels."""
+    _, L, _ = env
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(7)
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23).cuda().train()
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 3, 64, 64, generator=g)
+    t = torch.randint(0, 23, (2, 64, 64), generator=g)
+    t[torch.rand(2, 64, 64, generator=g) < 0.3] = IGN
+    wt = torch.rand(23, generator=g) + 0.1
+    crit = L.OhemCrossEntropyLoss(thresh=0.05, min_kept=1000, weight=wt, ignore_index=IGN, keep_mask=True).cuda()
+    logits = net(x.cuda())
+    loss = crit(logits, t.cuda())
+    loss.backward()
+    keep = crit.last_keep_mask.cpu().numpy().reshape(-1).astype(bool)
+    assert 1000 <= keep.sum() < (t != IGN).sum()
+    ref = R.loss_and_grad(rows(logits.detach().float().cpu()), t.view(-1).numpy(), wt.numpy(), keep, True, R.F64)
+    assert abs(loss.item() - ref["loss"][0]) < 1e-5 * abs(ref["loss"][0])
+    bias_grad = net.segmentation_head[0].bias.grad.cpu().numpy().astype(np.float64)
+    err = np.abs(bias_grad - ref["colsum"][0]).max() / np.abs(ref["colsum"][0]).max()
+    print(f"head bias gradient vs float64 pixel sum over the kept pixels: {err:.2e}")
+    assert err < 1e-3
+
+
+def test_trainer_runs_with_the_mined_loss(env):
+    """SegmentationTrainer(criterion=OhemCrossEntropyLoss(...)) on a two-batch uint8 loader with 255 in the masks."""
+    _, L, _ = env
+    from uda_aerial_semantic_segmentation_research_amd import data as D
+    from uda_aerial_semantic_segmentation_research_amd.optim import FusedAdam
+    from uda_aerial_semantic_segmentation_research_amd.train import SegmentationTrainer
+    from uda_aerial_semantic_segmentation_research_amd.unet import Unet
+    torch.manual_seed(11)
+    g = torch.Generator().manual_seed(5)
+    batches = []
+    for _ in range(2):
+        img = torch.randint(0, 256, (2, 64, 64, 3), generator=g, dtype=torch.uint8)
+        msk = torch.randint(0, 23, (2, 64, 64), generator=g, dtype=torch.uint8)
+        msk[:, :16] = IGN
+        batches.append((img, msk))
+    loader = D.DeviceAugmentedLoader(batches, generator=torch.Generator().manual_seed(9))
+    net = Unet("resnet18", encoder_weights=None, in_channels=3, classes=23)
+    crit = L.OhemCrossEntropyLoss(thresh=0.7, min_kept=500, ignore_index=IGN)
+    tr = SegmentationTrainer(net, torch.device("cuda", 0), criterion=crit)
+    assert tr.criterion is crit
+    train_loss = tr.train_epoch(loader, FusedAdam(net.parameters(), lr=1e-4), 1)
+    n, kept, void, invalid, nonfinite = crit.last_ohem_stats.tolist()
+    assert np.isfinite(train_loss) and void > 0 and invalid == 0 and nonfinite == 0 and n + void == 2 * 64 * 64
+    assert 500 <= kept <= n
+    q, edge = crit.last_threshold.tolist()
+    assert 0.0 <= q <= 1.0 and edge == max(q, np.float32(0.7))

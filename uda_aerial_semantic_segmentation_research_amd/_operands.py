@@ -322,6 +322,21 @@ OPERANDS = {
                           I("classes"), I("ldc"), I("has_ignore"), I("ignore_index"), F("eps"), I("mean"), T("denom", f64, 1, True),
                           T("dlogits", f32, "pixels*ldc"), T("colsum_partials", f32, "ce_partials()*ldc", True),
                           T("colsum", f32, "ldc", True), S],
+    # hard-pixel mining: conf = the target class's confidence (-1 at void pixels), hist = 1024 bins per radix level,
+    # state = the select's int64 [8] (include/udaseg.h), counters = [void, invalid, non-finite], counts = [valid finite, kept]
+    "udaseg_ohem_conf": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
+                         I("has_ignore"), I("ignore_index"), T("conf", f32, "pixels"), T("hist0", i64, 1024), T("counters", i64, 3), S],
+    "udaseg_kth_hist": [T("values", f32, "count"), I("count"), I("level"), T("state", i64, 8, True), T("hist", i64, 1024), S],
+    "udaseg_kth_select": [T("hist", i64, 1024), I("level"), I("min_kept"), F("fraction"), T("state", i64, 8), S],
+    "udaseg_kth_value": [T("state", i64, 8), F("thresh"), T("out", f32, 2), S],
+    "udaseg_ohem_denom": [T("conf", f32, "pixels"), T("target", i64, "pixels"), T("weight", f32, "classes", True), I("pixels"),
+                          I("classes"), F("thresh"), T("state", i64, 8), T("partials", f64, "3*ce_partials()"), T("denom", f64, 1),
+                          T("counts", i64, 2), T("keep", u8, "pixels", True), S],
+    "udaseg_ce_ohem_fwd_bwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("weight", f32, "classes", True),
+                               T("conf", f32, "pixels"), T("state", i64, 8), F("thresh"), I("pixels"), I("classes"), I("ldc"),
+                               I("mean"), T("denom", f64, 1, True), T("partials", f64, "ce_partials()"), T("loss", f32, 1),
+                               T("dlogits", f32, "pixels*ldc", True), T("colsum_partials", f32, "ce_partials()*ldc", True),
+                               T("colsum", f32, "ldc", True), S],
     "udaseg_argmax_confusion": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
                                 T("confusion", i64, "classes*classes"), T("pred", i64, "pixels", True), S],
     "udaseg_score_hist": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"), I("bins"),

@@ -16,6 +16,33 @@
 
 namespace udaseg {
 
+// The row arithmetic the optioned cross entropy (losses.hip) and the hard-pixel-mining cross entropy (ohem.hip) share.
+// valid(p): the target names a class and is not ignore_index.
+__device__ __forceinline__ bool ce_valid(int64_t t, int classes, int has_ignore, int64_t ignore_index) {
+  return (uint64_t)t < (uint64_t)classes && !(has_ignore && t == ignore_index);
+}
+// lse = mx + logf(sum_c expf(z_c - mx)) with the classes summed left to right; xt = z_t.
+template <int LDC4>
+__device__ __forceinline__ float ce_row_lse(const f32x4 (&v)[LDC4], int classes, int t, float& xt) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < LDC4; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (k * 4 + e < classes) mx = fmaxf(mx, v[k][e]);
+  float sum = 0.f;
+  xt = 0.f;
+#pragma unroll
+  for (int k = 0; k < LDC4; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (k * 4 + e < classes) {
+        sum += expf(v[k][e] - mx);
+        if (k * 4 + e == t) xt = v[k][e];
+      }
+  return mx + logf(sum);
+}
+
 // partials[blockIdx.x] = the block's sum of `local`.  red: 4 doubles of LDS.  One barrier.
 __device__ __forceinline__ void block_partial(double local, double* red, double* partials) {
   local = wave_sum_d(local);

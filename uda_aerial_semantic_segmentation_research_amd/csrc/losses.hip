@@ -195,10 +195,6 @@ __global__ void scale_unless_one_kernel(f32x4* __restrict__ x, int64_t n4, float
 //   dl_p/dz_k = (1-eps) * w[t] * (P_k - [k==t]) + (eps/C) * (P_k * sum_c w[c] - w[k])       exactly 0 at void pixels, all ldc lanes
 //   'mean' divides both by D = sum over valid p of w[t_p], which ce_target_stats_kernel makes from the targets alone (8 B/pixel)
 //   BEFORE the one pass over the logits, so that pass writes the gradient already scaled.
-__device__ __forceinline__ bool ce_valid(int64_t t, int classes, int has_ignore, int64_t ignore_index) {
-  return (uint64_t)t < (uint64_t)classes && !(has_ignore && t == ignore_index);
-}
-
 // partials[k][block], k = 0: sum of w[t] over valid pixels (f64), 1..3: valid / void (== ignore_index) / invalid pixel counts
 // (whole numbers < 2^53: exact in f64).  Fixed pixel-to-thread map and fixed-order reductions: two calls give the same bits.
 __global__ __launch_bounds__(256) void ce_target_stats_kernel(const int64_t* __restrict__ target, const float* __restrict__ weight,
@@ -226,28 +222,8 @@ __global__ __launch_bounds__(256) void ce_target_stats_kernel(const int64_t* __r
   block_partial_rows<4>(v, red, partials);
 }
 
-// The per-pixel terms shared by the optioned kernels.  wsh: the class weights in LDS (1 where no weights were given).
-template <int LDC4>
-__device__ __forceinline__ float ce_row_lse(const f32x4 (&v)[LDC4], int classes, int t, float& xt) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < LDC4; ++k)
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (k * 4 + e < classes) mx = fmaxf(mx, v[k][e]);
-  float sum = 0.f;
-  xt = 0.f;
-#pragma unroll
-  for (int k = 0; k < LDC4; ++k)
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (k * 4 + e < classes) {
-        sum += expf(v[k][e] - mx);
-        if (k * 4 + e == t) xt = v[k][e];
-      }
-  return mx + logf(sum);
-}
-
+// The per-pixel terms shared by the optioned kernels (ce_valid and ce_row_lse: loss_reduce.h, shared with ohem.hip).
+// wsh: the class weights in LDS (1 where no weights were given).
 template <int LDC4, bool SMOOTH>
 __device__ __forceinline__ float ce_opt_pixel_loss(const f32x4 (&v)[LDC4], int classes, float l, float xt, float wt, float om, float es,
                                                    const float* wsh) {

@@ -1,6 +1,6 @@
 // Shared by every kernel that walks a padded NHWC buffer of per-pixel class scores: [pixels][ldc] fp32, classes <= ldc,
 // ldc % 4 == 0, only channels < classes count (losses.hip, losses_seg.hip, advent.hip, distill.hip, curves.hip, pseudo.hip, predict.hip,
-// proto.hip, proto_contrast.hip; loss_reduce.h builds on it for what follows a loss kernel's row arithmetic).  Such a kernel is a
+// proto.hip, proto_contrast.hip, ohem.hip; loss_reduce.h builds on it for what follows a loss kernel's row arithmetic).  Such a kernel is a
 // template on its row width in f32x4 vectors -- LDC4 = ldc / 4 where the width is also the row stride, NV = cdiv(classes, 4) where
 // ldc stays a runtime argument -- so here are the one width dispatcher, the one row reader and the one tie rule of the winner.
 #pragma once
@@ -58,6 +58,19 @@ __device__ __forceinline__ int first_max(const f32x4 (&v)[NV], int classes, floa
   return am;
 }
 
+// S = sum over c < classes of expf(z_c - m), m the row's maximum: channel c adds into partial sum c % 4 (four short chains), folded
+// as (s0 + s1) + (s2 + s3).  The maximum's term is exactly 1, so S >= 1 whenever it is a number (pixel_conf below, ohem.hip).
+template <int NV>
+__device__ __forceinline__ float exp_sum(const f32x4 (&v)[NV], int classes, float m) {
+  f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * q + e < classes) s4[e] += expf(v[q][e] - m);
+  return (s4[0] + s4[1]) + (s4[2] + s4[3]);
+}
+
 // The winner of one pixel and its confidence, THE definition of pseudo.hip (its header comment states it) and of
 // udaseg_conf_share (distill.hip): one function, so that a histogram, a labelling and a share cannot disagree.
 struct PixelConf {
@@ -82,14 +95,7 @@ __device__ __forceinline__ PixelConf pixel_conf(const float* __restrict__ row, i
     r.p = m;
     r.finite = !nan && m >= 0.f && m <= 1.f;
   } else {
-    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};                       // channel c adds into partial sum c % 4: four short chains
-#pragma unroll
-    for (int q = 0; q < NV; ++q)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (4 * q + e < classes) s4[e] += expf(v[q][e] - m);   // exactly 1 at the maximum, so S >= 1 whenever it is a number
-    const float S = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    r.p = 1.f / S;
+    r.p = 1.f / exp_sum<NV>(v, classes, m);
     r.finite = __builtin_isfinite(r.p);
   }
   return r;

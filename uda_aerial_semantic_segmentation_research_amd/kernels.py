@@ -812,6 +812,69 @@ def ce_opt_bwd(logits_base, target, weight, lse, grad_out, grad_px, pixels, clas
           "ce_opt_bwd")
 
 
+KTH_BINS, KTH_STATE = 1024, 8            # bins per radix level, int64 words of the select's state (include/udaseg.h)
+
+
+def ohem_conf(logits_base, target, pixels, classes, ldc, ignore_index, conf, hist0, counters, st=None):
+    """conf = the target class's confidence per pixel (-1 at void / out-of-range / non-finite pixels), hist0 += its level-0 histogram,
+    counters += [void, invalid, non-finite]."""
+    check(ops.udaseg_ohem_conf(logits_base, target, pixels, classes, ldc, *_ignore_args(ignore_index), conf, hist0, counters, st),
+          "ohem_conf")
+
+
+def kth_hist(values, level, state, hist, st=None):
+    check(ops.udaseg_kth_hist(values, values.numel(), level, state, hist, st), "kth_hist")
+
+
+def kth_select(hist, level, state, min_kept=0, fraction=-1.0, st=None):
+    check(ops.udaseg_kth_select(hist, level, int(min_kept), float(fraction), state, st), "kth_select")
+
+
+def kth_value(state, thresh, out, st=None):
+    """out = [q, max(q, thresh)] of a state after level 2."""
+    check(ops.udaseg_kth_value(state, float(thresh), out, st), "kth_value")
+
+
+def kth_refine(values, hist, state, st=None):
+    """Levels 1 and 2 of the radix select, after level 0's select: ``hist`` int64 [3, 1024] (zeroed), ``state`` int64 [8]."""
+    for level in (1, 2):
+        kth_hist(values, level, state, hist[level], st)
+        kth_select(hist[level], level, state, st=st)
+
+
+def kth_smallest(values, k):
+    """The exact k-th smallest (1-indexed) of a contiguous fp32 device buffer of values in [0, 2), as a device fp32 scalar: a
+    three-level radix select (csrc/ohem.hip), no sort, nothing read back, the same bits on every call.  Values with the sign bit
+    set or >= 2 (-1.0, inf, NaN) are skipped; with n values left, k == 0 gives -inf and k > n gives +inf (so that ``v <= result``
+    selects exactly the ``min(k, n)`` smallest and every tie of the last one)."""
+    if values.dtype != torch.float32 or values.numel() == 0:
+        raise ValueError(f"kth_smallest: need a non-empty fp32 tensor, got {values.dtype} with {values.numel()} elements")
+    if int(k) < 0:
+        raise ValueError(f"kth_smallest: k must be >= 0, got {k}")
+    flat = values.reshape(-1)
+    ws = torch.zeros(3 * KTH_BINS + KTH_STATE, device=values.device, dtype=torch.int64)
+    hist, state = ws[:3 * KTH_BINS].view(3, KTH_BINS), ws[3 * KTH_BINS:]
+    kth_hist(flat, 0, None, hist[0])
+    kth_select(hist[0], 0, state, min_kept=k)
+    kth_refine(flat, hist, state)
+    out = torch.empty(2, device=values.device, dtype=torch.float32)
+    kth_value(state, 0.0, out)
+    return out[0]
+
+
+def ohem_denom(conf, target, weight, pixels, classes, thresh, state, partials, denom, counts, keep=None, st=None):
+    """denom = sum of weight[t] over the kept pixels (f64), counts = [valid finite, kept], keep = the optional uint8 map."""
+    check(ops.udaseg_ohem_denom(conf, target, weight, pixels, classes, float(thresh), state, partials, denom, counts, keep, st),
+          "ohem_denom")
+
+
+def ce_ohem_fwd_bwd(logits_base, target, weight, conf, state, thresh, pixels, classes, ldc, mean, denom, partials, loss, dlogits=None,
+                    colsum_partials=None, colsum=None, st=None):
+    """Cross entropy over the kept pixels, loss and (already scaled) gradient in ONE pass over the logits; dlogits None: loss only."""
+    check(ops.udaseg_ce_ohem_fwd_bwd(logits_base, target, weight, conf, state, float(thresh), pixels, classes, ldc, int(mean), denom,
+                                     partials, loss, dlogits, colsum_partials, colsum, st), "ce_ohem_fwd_bwd")
+
+
 def seg_partials():
     return ops.udaseg_seg_partials()
 

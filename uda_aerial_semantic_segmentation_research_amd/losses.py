@@ -3,6 +3,9 @@
 * ``CrossEntropyLoss``  -- ``nn.CrossEntropyLoss()`` exactly as the reference constructs it (no arguments: mean
   reduction, no class weights, no ignore_index, no label smoothing; reference ``src/models/train.py:208``); with
   ``weight`` / ``ignore_index`` / ``reduction`` / ``label_smoothing`` the optioned kernels (void labels).
+* ``OhemCrossEntropyLoss``, ``TopKCrossEntropyLoss`` -- the cross entropy over the hard pixels only (online hard example mining /
+  bootstrapped top-k; an extension), selected exactly on the device by a radix select (csrc/ohem.hip; INTEGRATION.md
+  "Hard-pixel mining").
 * ``AdversarialLoss``   -- mirror of reference ``src/models/losses.py:7-51`` (same constructor, same two methods).
   As upstream, BCE-*with-logits* is applied to whatever the discriminator returns (its sigmoid output).
 * ``DiceLoss``, ``WeightedSegmentationLoss``, ``ConsistencyLoss``, ``FineTuningLoss``, ``calculate_class_weights`` --
@@ -246,6 +249,176 @@ class CrossEntropyLoss(nn.Module):
                                              self.label_smoothing, stats)
         self.last_target_stats = stats
         return out
+
+
+class _OhemCrossEntropyFunction(torch.autograd.Function):
+    """Cross entropy over the hard pixels (csrc/ohem.hip).  One pass over the logits makes the target class's confidence per pixel
+    and its level-0 histogram; a three-level radix select finds the exact k-th smallest confidence on the device; one pass over the
+    confidences makes the 'mean' denominator and the counters; then ``ce_ohem_fwd_bwd`` reads the logits once more and writes the
+    loss and the gradient, already scaled, with the head's bias gradient (column sums).  ``ws``: the zeroed int64 workspace
+    [3 * 1024 histogram bins | 8 words of select state | 5 statistics]."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, mean, thresh, min_kept, fraction, ws, thr, keep):
+        n, c, h, w = logits.shape
+        buf, ldc = _padded_nhwc(logits.detach())
+        tgt = target.contiguous()
+        pixels = n * h * w
+        dev = logits.device
+        np_ = _load().udaseg_ce_partials()
+        nb = 3 * K.KTH_BINS
+        hist, state, stats = ws[:nb].view(3, K.KTH_BINS), ws[nb:nb + K.KTH_STATE], ws[nb + K.KTH_STATE:]
+        conf = torch.empty(pixels, device=dev, dtype=torch.float32)
+        K.ohem_conf(buf, tgt, pixels, c, ldc, ignore_index, conf, hist[0], stats[2:5])
+        K.kth_select(hist[0], 0, state, min_kept=min_kept, fraction=fraction)
+        K.kth_refine(conf, hist, state)
+        denom = torch.empty(1, device=dev, dtype=torch.float64)
+        K.ohem_denom(conf, tgt, weight, pixels, c, thresh, state, torch.empty(3 * np_, device=dev, dtype=torch.float64), denom,
+                     stats[0:2], keep)
+        K.kth_value(state, thresh, thr)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        partials = torch.empty(np_, device=dev, dtype=torch.float64)
+        ctx.meta = (n, c, h, w, ldc, mean, thresh)
+        ctx.fused = None
+        ctx.save_for_backward(buf, tgt, weight, conf, state, denom)
+        if ctx.needs_input_grad[0]:
+            dl, parts, colsum = _OhemCrossEntropyFunction._grad_buffers(n, h, w, ldc, np_, dev)
+            K.ce_ohem_fwd_bwd(buf, tgt, weight, conf, state, thresh, pixels, c, ldc, mean, denom, partials, loss, dl, parts, colsum)
+            ctx.fused = [dl, colsum]
+        else:
+            K.ce_ohem_fwd_bwd(buf, tgt, weight, conf, state, thresh, pixels, c, ldc, mean, denom, partials, loss)
+        return loss
+
+    @staticmethod
+    def _grad_buffers(n, h, w, ldc, np_, dev):
+        return (torch.empty((n, h, w, ldc), device=dev, dtype=torch.float32), torch.empty(np_ * ldc, device=dev, dtype=torch.float32),
+                torch.empty(ldc, device=dev, dtype=torch.float32))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, c, h, w, ldc, mean, thresh = ctx.meta
+        g = grad_out.detach().to(torch.float32).contiguous()
+        if ctx.fused is not None:
+            dl, colsum = ctx.fused
+            ctx.fused = None                           # consumed
+        else:                                          # a second backward through a retained graph: the same launch on the saved
+            buf, tgt, weight, conf, state, denom = ctx.saved_tensors      # conf and state, so the same kept set and the same bits
+            np_ = _load().udaseg_ce_partials()
+            dl, parts, colsum = _OhemCrossEntropyFunction._grad_buffers(n, h, w, ldc, np_, buf.device)
+            K.ce_ohem_fwd_bwd(buf, tgt, weight, conf, state, thresh, n * h * w, c, ldc, mean, denom,
+                              torch.empty(np_, device=buf.device, dtype=torch.float64),
+                              torch.empty((), device=buf.device, dtype=torch.float32), dl, parts, colsum)
+        K.scale_unless_one(dl, g, colsum)
+        COLSUM_SIDE_TABLE.clear()
+        COLSUM_SIDE_TABLE[dl.data_ptr()] = colsum
+        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 10
+
+
+class OhemCrossEntropyLoss(nn.Module):
+    """Per-pixel cross entropy over the HARD pixels only: online hard example mining (Shrivastava et al. 2016) in its per-pixel
+    form, and with ``keep_fraction`` the bootstrapped / top-k cross entropy (Wu et al. 2016).  ``[N,C,H,W]`` logits (C <= 32) and
+    ``[N,H,W]`` integer targets, as ``CrossEntropyLoss``.
+
+    A pixel is *valid* as for ``CrossEntropyLoss`` (``target != ignore_index`` and ``0 <= target < C``); a valid pixel whose logits
+    are not all finite is void as well (loss and gradient exactly 0) and counted on its own.  With ``p`` the softmax probability
+    of the target class at a valid finite pixel and ``n`` the number of such pixels:
+
+    * OHEM: a pixel is kept iff ``p < thresh`` or ``p <= q``, ``q`` the ``min_kept``-th smallest ``p`` -- the pixels below the
+      threshold, but at least ``min(min_kept, n)`` of them.
+    * top-k (``keep_fraction=f`` in (0, 1]): kept iff ``p <= q``, ``q`` the ``ceil(f * n)``-th smallest ``p``.
+
+    ``q`` is exact (a radix select on the device: no sort, no bins, nothing read back, the same bits on every run) and pixels that
+    tie with ``q`` are all kept, so the kept set depends on the values alone.  The loss is ``-weight[t] * log_softmax(z)[t]`` over
+    the kept pixels; 'mean' divides by the sum of ``weight[t]`` over them (no kept pixel: NaN loss and an all-zero gradient, the
+    convention of ``CrossEntropyLoss`` for an all-void batch; 'sum': 0).  The gradient is exactly 0 at every pixel not kept.
+    Label smoothing is not supported: selection statistic and loss would no longer be monotone in each other.
+
+    After a call, all on the device and written by the loss's own launches (read them when convenient):
+
+    * ``last_ohem_stats``: int64 ``[n_valid_finite, n_kept, n_void, n_invalid, n_nonfinite]``;
+    * ``last_threshold``: fp32 ``[q, max(q, thresh)]`` (``q`` is -inf when k == 0 and +inf when k > n);
+    * ``last_keep_mask``: uint8 ``[N,H,W]``, made only with ``keep_mask=True``.
+
+    Under data parallelism each rank selects on its own batch (its own ``n``, ``q`` and denominator), as each rank of torch's
+    DistributedDataParallel divides by its own count.
+    """
+
+    def __init__(self, thresh=0.7, min_kept=100_000, keep_fraction=None, weight=None, ignore_index=None, reduction='mean',
+                 keep_mask=False, label_smoothing=0.0):
+        super().__init__()
+        who = type(self).__name__
+        if float(label_smoothing) != 0.0:
+            raise ValueError(f"{who}: label smoothing is not supported (the selection statistic and the loss would no longer be "
+                             f"monotone in each other), got {label_smoothing}")
+        if reduction not in ('sum', 'mean'):
+            raise ValueError(f"{who}: reduction must be 'sum' or 'mean', got {reduction!r}")
+        if keep_fraction is not None:
+            if thresh != 0.7 or min_kept != 100_000:
+                raise ValueError(f"{who}: keep_fraction (top-k mode) excludes thresh and min_kept")
+            if not 0.0 < float(keep_fraction) <= 1.0:
+                raise ValueError(f"{who}: keep_fraction must lie in (0, 1], got {keep_fraction}")
+            thresh, min_kept, keep_fraction = 0.0, 0, float(keep_fraction)
+        else:
+            if not 0.0 <= float(thresh) <= 1.0:
+                raise ValueError(f"{who}: thresh must lie in [0, 1], got {thresh}")
+            if isinstance(min_kept, bool) or int(min_kept) != min_kept or not 0 <= int(min_kept) < 2 ** 63:
+                raise ValueError(f"{who}: min_kept must be a non-negative integer, got {min_kept!r}")
+        if weight is not None:
+            weight = torch.as_tensor(weight)
+            if weight.dim() != 1 or weight.numel() == 0:
+                raise ValueError(f"{who}: weight must be a 1-D tensor of C class weights, got shape {tuple(weight.shape)}")
+            if weight.numel() > 32:
+                raise ValueError(f"{who}: at most 32 classes are supported by the HIP kernels, got {weight.numel()} weights")
+            weight = weight.detach().to(torch.float32).clone()
+        self.register_buffer('weight', weight)
+        self.thresh, self.min_kept, self.keep_fraction = float(thresh), int(min_kept), keep_fraction
+        self.ignore_index = _check_ignore_index(who, ignore_index)
+        self.reduction = reduction
+        self.keep_mask = bool(keep_mask)
+        self.last_ohem_stats = self.last_threshold = self.last_keep_mask = None
+
+    def extra_repr(self):
+        mode = f"keep_fraction={self.keep_fraction}" if self.keep_fraction is not None else f"thresh={self.thresh}, min_kept={self.min_kept}"
+        return f"{mode}, ignore_index={self.ignore_index}, reduction={self.reduction!r}"
+
+    def forward(self, input, target):
+        who = type(self).__name__
+        if input.device.type != "cuda":
+            raise RuntimeError(f"{who}: logits must live on the GPU (no CPU path in this build)")
+        if input.dim() != 4 or target.dim() != 3 or input.shape[0] != target.shape[0] or input.shape[2:] != target.shape[1:]:
+            raise ValueError(f"expected logits [N,C,H,W] and target [N,H,W]; got {tuple(input.shape)} and {tuple(target.shape)}")
+        n, c, h, w = input.shape
+        if c > 32:
+            raise ValueError(f"{who}: at most 32 classes are supported by the HIP kernels, got {c}")
+        if n * h * w >= 2 ** 31:
+            raise ValueError(f"{who}: at most 2^31 - 1 pixels per call, got {n * h * w}")
+        if target.dtype != torch.int64:
+            target = target.long()
+        weight = self.weight
+        if weight is not None:
+            if weight.numel() != c:
+                raise ValueError(f"{who}: weight has {weight.numel()} entries for {c} classes")
+            weight = weight.to(device=input.device, dtype=torch.float32).contiguous()
+        dev = input.device
+        ws = torch.zeros(3 * K.KTH_BINS + K.KTH_STATE + 5, device=dev, dtype=torch.int64)
+        thr = torch.empty(2, device=dev, dtype=torch.float32)
+        keep = torch.empty((n, h, w), device=dev, dtype=torch.uint8) if self.keep_mask else None
+        fraction = -1.0 if self.keep_fraction is None else self.keep_fraction
+        out = _OhemCrossEntropyFunction.apply(input, target.to(dev), weight, self.ignore_index, self.reduction == 'mean', self.thresh,
+                                              self.min_kept, fraction, ws, thr, keep)
+        self.last_ohem_stats = ws[3 * K.KTH_BINS + K.KTH_STATE:]
+        self.last_threshold = thr
+        self.last_keep_mask = keep
+        return out
+
+
+class TopKCrossEntropyLoss(OhemCrossEntropyLoss):
+    """The bootstrapped / top-k cross entropy: ``OhemCrossEntropyLoss(keep_fraction=...)``, the hardest ``ceil(keep_fraction * n)``
+    of the ``n`` valid finite pixels (and every pixel that ties with the last of them)."""
+
+    def __init__(self, keep_fraction, weight=None, ignore_index=None, reduction='mean', keep_mask=False):
+        super().__init__(keep_fraction=keep_fraction, weight=weight, ignore_index=ignore_index, reduction=reduction,
+                         keep_mask=keep_mask)
 
 
 class _BCEPairFunction(torch.autograd.Function):
