@@ -76,7 +76,9 @@ int udaseg_version(void);
 #define UDASEG_OPT_WGRAD_UP_BLOCKS 32       /* UDASEG_WGRAD_UP_BLOCKS: blocks of a conv_wgrad_up_kernel launch (0: 96; udaseg_wgrad_up_set_blocks) */
 #define UDASEG_OPT_WGRAD_PAIR 33            /* UDASEG_WGRAD_PAIR: fp32 weight gradients of 16-channel inputs on the pair-packed halo kernel: bit 0 the 16 -> 16 layers, bit 1 those of 24 / 32 produced channels, bit 2 the up-sampled 32 -> 16 layer without a skip half; 0: all on conv3x3_small_wgrad_kernel */
 #define UDASEG_OPT_WGRAD_PAIR_BLOCKS 34     /* UDASEG_WGRAD_PAIR_BLOCKS: blocks of a pair-packed halo weight-gradient launch (0: 120) */
-#define UDASEG_OPT_COUNT 35
+#define UDASEG_OPT_STEM_WGRAD_BN 35        /* UDASEG_STEM_WGRAD_BN: 0: udaseg_conv_stem_wgrad_bn_ok answers no (the stem's BatchNorm apply pass + split-K weight gradient, A/B) */
+#define UDASEG_OPT_STEM_WGRAD_BLOCKS 36    /* UDASEG_STEM_WGRAD_BLOCKS: cap on the blocks of a conv_small_ci_wgrad_kernel launch (0: one per CU; udaseg_stem_wgrad_set_blocks) */
+#define UDASEG_OPT_COUNT 37
 int udaseg_set_option(int key, int value);
 int udaseg_get_option(int key);
 int udaseg_option_count(void);
@@ -1160,6 +1162,21 @@ int udaseg_conv2d_dgrad_n16_f32x3(const udaseg_conv_desc* d, const float* dy, co
  *      (3 planes of 28 * 512 bf16).  Replaces udaseg_conv2d_fwd_bnstats (conv_igemm_kernel, generic gather) on that layer. ---- */
 int udaseg_conv_stem_f32x3_ok(const udaseg_conv_desc* d);
 int udaseg_conv2d_fwd_stem_f32x3(const udaseg_conv_desc* d, const float* x, const void* wfrag, float* y, double* stats, void* stream);
+/* The stem's weight gradient with the apply half of its BatchNorm backward in the staging (csrc/conv_stem_wgrad.hip,
+ * conv_small_ci_wgrad_kernel, v_mfma_f32_32x32x2_f32): autograd's aten::convolution_backward of ResNet.conv1 and the dy of bn1's
+ * aten::native_batch_norm_backward, reached by loss.backward() (reference src/models/train.py:343).  The stem has no data gradient,
+ * so dy = udaseg_bn_bwd_apply(dz, y) has one reader: here it is formed from dz and y while they are staged (the same fp32
+ * arithmetic from the same sums; the mask re-evaluated from y, so ReLU / leaky layers WITHOUT a residual input only) and never
+ * stored.  dW[64][7][7][4] (+)= over the 147 live (ky, kx, c) columns, the fourth-channel entries are not touched; dgamma / dbeta as
+ * udaseg_bn_bwd_apply writes them (accumulate_param).  bsums: udaseg_bn_bwd_reduce's.  Replaces udaseg_bn_bwd_apply +
+ * udaseg_conv2d_wgrad on that layer; UDASEG_OPT_STEM_WGRAD_BN = 0 makes the query answer no. */
+int udaseg_conv_stem_wgrad_bn_ok(const udaseg_conv_desc* d);
+int udaseg_conv2d_wgrad_stem_bn(const udaseg_conv_desc* d, const float* x, const float* dz, const float* y, const float* save_mean,
+                                const float* save_rstd, const float* gamma, const float* beta, const double* bsums, int act,
+                                float slope, float* dw, float* dgamma, float* dbeta, int accumulate, int accumulate_param,
+                                void* stream);
+/* tests / tuning: cap on the blocks of that launch (0 = the default, one per CU) */
+int udaseg_stem_wgrad_set_blocks(int blocks);
 
 /* ---- diagnosis: while a device buffer of 6 * blocks u64 is registered, every implicit-GEMM launch of at most `blocks` blocks
  *      writes per block {entry, first tile load, end of K loop, exit} (100 MHz wall-clock ticks), HW_ID and XCC_ID into it

@@ -217,6 +217,9 @@ SIGNATURES = {
     "udaseg_wgrad_up_set_blocks": (_I, [_I]),
     "udaseg_conv_stem_f32x3_ok": (_I, [_D]),
     "udaseg_conv2d_fwd_stem_f32x3": (_I, [_D, _P, _P, _P, _P, _P]),
+    "udaseg_conv_stem_wgrad_bn_ok": (_I, [_D]),
+    "udaseg_conv2d_wgrad_stem_bn": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P, _I, _I, _P]),
+    "udaseg_stem_wgrad_set_blocks": (_I, [_I]),
     "udaseg_conv_n16_f32x3_ok": (_I, [_D, _I]),
     "udaseg_conv2d_fwd_n16_f32x3": (_I, [_D, _P, _P, _P, _I, _F, _P, _P, _P, _P]),
     "udaseg_conv2d_dgrad_n16_f32x3": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P]),
@@ -237,7 +240,7 @@ SIGNATURES = {
 
 # The library's switchboard (include/udaseg.h UDASEG_OPT_*, table in csrc/api.hip): name -> key.  The ONE Python mirror of it;
 # tests/test_abi.py checks it against udaseg_option_count / udaseg_option_name.  kernels.set_option / get_option take these names.
-OPTIONS = {"GENERIC_GATHER": 0, "F32_SPLIT": 1, "WGRAD_GENERIC": 2, "F32_HALO": 3, "F3_CFG": 4, "F3_WS": 5, "F3_SIGNS": 6, "IGEMM_TILE": 7, "IGEMM_X3": 8, "NO_FOLD": 9, "WGRAD_X3_BLOCKS": 10, "WGRAD_BLOCKS": 11, "WGRAD_NO_XCD": 12, "WGRAD_X3": 13, "NO_WGRAD_HALO": 14, "WGRAD_F3_BLOCKS": 15, "WGRAD_HALO_BLOCKS": 16, "WGRAD_DEEP_BLOCKS": 17, "WGRAD_DB": 18, "REDUCE_BLOCKS": 19, "BN_APPLY_PT": 20, "GEMM_1X1_TILE": 21, "GEMM_1X1": 22, "GEMM_1X1_MAXM": 23, "NO_STREAM": 24, "HALO_CFG": 25, "NO_HALO": 26, "NO_HALO_S2": 27, "HALO_W16": 28, "HALO_DEEP": 29, "HALO_S2_CK": 30, "UP_CFG": 31, "WGRAD_UP_BLOCKS": 32, "WGRAD_PAIR": 33, "WGRAD_PAIR_BLOCKS": 34}
+OPTIONS = {"GENERIC_GATHER": 0, "F32_SPLIT": 1, "WGRAD_GENERIC": 2, "F32_HALO": 3, "F3_CFG": 4, "F3_WS": 5, "F3_SIGNS": 6, "IGEMM_TILE": 7, "IGEMM_X3": 8, "NO_FOLD": 9, "WGRAD_X3_BLOCKS": 10, "WGRAD_BLOCKS": 11, "WGRAD_NO_XCD": 12, "WGRAD_X3": 13, "NO_WGRAD_HALO": 14, "WGRAD_F3_BLOCKS": 15, "WGRAD_HALO_BLOCKS": 16, "WGRAD_DEEP_BLOCKS": 17, "WGRAD_DB": 18, "REDUCE_BLOCKS": 19, "BN_APPLY_PT": 20, "GEMM_1X1_TILE": 21, "GEMM_1X1": 22, "GEMM_1X1_MAXM": 23, "NO_STREAM": 24, "HALO_CFG": 25, "NO_HALO": 26, "NO_HALO_S2": 27, "HALO_W16": 28, "HALO_DEEP": 29, "HALO_S2_CK": 30, "UP_CFG": 31, "WGRAD_UP_BLOCKS": 32, "WGRAD_PAIR": 33, "WGRAD_PAIR_BLOCKS": 34, "STEM_WGRAD_BN": 35, "STEM_WGRAD_BLOCKS": 36}
 
 _lib = None
 

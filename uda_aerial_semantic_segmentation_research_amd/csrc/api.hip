@@ -290,7 +290,9 @@ static const OptRow g_opt_rows[UDASEG_OPT_COUNT] = {
     /* 31 UP_CFG */ {"UDASEG_UP_CFG", K_INT, 0},
     /* 32 WGRAD_UP_BLOCKS */ {"UDASEG_WGRAD_UP_BLOCKS", K_INT, 0},
     /* 33 WGRAD_PAIR */ {"UDASEG_WGRAD_PAIR", K_INT, 4},
-    /* 34 WGRAD_PAIR_BLOCKS */ {"UDASEG_WGRAD_PAIR_BLOCKS", K_INT, 0}};
+    /* 34 WGRAD_PAIR_BLOCKS */ {"UDASEG_WGRAD_PAIR_BLOCKS", K_INT, 0},
+    /* 35 STEM_WGRAD_BN */ {"UDASEG_STEM_WGRAD_BN", K_OFF0, 1},
+    /* 36 STEM_WGRAD_BLOCKS */ {"UDASEG_STEM_WGRAD_BLOCKS", K_INT, 0}};
 int g_opt_val[UDASEG_OPT_COUNT];
 static int g_opt_default[UDASEG_OPT_COUNT];
 std::atomic<bool> g_opt_ready{false};

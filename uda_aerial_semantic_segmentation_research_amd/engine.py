@@ -96,6 +96,7 @@ USE_WGRAD_HALO = os.environ.get("UDASEG_WGRAD_HALO", "1") != "0"
 PHASE, N16, STEM, FRAG_BNIN, FRAG_UP_BNIN, FRAG, UPCAT, IGEMM = "phase", "n16", "stem", "frag_bnin", "frag_up_bnin", "frag", "upcat", "igemm"
 FWD_ROUTES = (PHASE, N16, STEM, FRAG_BNIN, FRAG_UP_BNIN, FRAG, UPCAT, IGEMM)
 BNIN, HALO, PART, GENERIC = "bnin", "halo", "part", "generic"       # weight gradient
+STEM_BN = "stem_bn"     # the stem's weight gradient with the apply half of its BatchNorm backward in the staging (Plan.tail_route)
 SPLIT, BNREDUCE = "split", "bnreduce"                              # data gradient, beside PHASE / N16 / FRAG / IGEMM
 _MISS = object()
 
@@ -586,6 +587,9 @@ class Plan:
         # tests, tuning): every cached routing answer below is keyed with the number of overrides made so far
         self.epoch = K.option_epoch()
         self._wgrad_halo = USE_WGRAD_HALO and (self.bf16 or USE_F32_SPLIT)      # halo-resident weight gradients (bf16 / fp32 split)
+        # debug_keep_tape keeps every intermediate of the step for inspection, each layer's dy among them (tests/_step_tape.py reads it
+        # out of Plan.bn_bwd): a backward that never writes a dy (tail_route) is not taken then
+        self.keep_grads = bool(getattr(net, "debug_keep_tape", False))
         if training and save and SIDE_STREAM_WGRAD and PREPACK_DGRAD:
             self._prepack_dgrad_weights()
 
@@ -1079,7 +1083,40 @@ class Plan:
                        False, dres_acc, False, self.st, beta=beta)
         return dz
 
+    def tail_route(self, rec, dx=None, dres=None):
+        """STEM_BN when this layer's backward is one reduce pass + one weight-gradient launch that forms dy = bn_bwd_apply(dz, y) while
+        it stages dz and y (csrc/conv_stem_wgrad.hip): nothing but the weight gradient reads that dy -- no data gradient, no residual
+        branch -- and the mask can be re-evaluated from y.  None: bn_bwd + conv_bwd."""
+        if (self.bf16 or self.keep_grads or dx is not None or dres is not None or rec.has_res or rec.act == ACT_NONE
+                or rec.conv.bias is not None or isinstance(rec.z, LazyAct) or isinstance(rec.x, (UpCat, LazyAct))):
+            return None
+        d = rec.d
+        return STEM_BN if self._cached("stem_bn", (d.n, d.hi, d.wi, d.ci, d.co, d.kh, d.stride, d.pad),
+                                       lambda: K.conv_stem_wgrad_bn_ok(d)) else None
+
+    def _stem_bn_bwd(self, rec, dz):
+        """The STEM_BN route: the two reductions (unless a consumer's data gradient made them), then the fused launch where the weight
+        gradient goes anyway -- the side stream, after the same wait.  dz is read, not overwritten; dgamma / dbeta come from that launch."""
+        bn = rec.bn
+        gamma, beta = self.pvec(bn, "weight"), self.pvec(bn, "bias")
+        bs = self._bnb.pop(id(rec.y), None)
+        if bs is None:
+            bs = self._next_bstats(ceil4(bn.c))
+            K.bn_bwd_reduce(dz, None, rec.y, rec.mean, rec.rstd, bs, rec.act, rec.slope, self.st, gamma=gamma, beta=beta)
+        side = self.side_stream
+        if side is not None:
+            wst = self._side_h
+            K.stream_wait(wst, self._main_h)                    # dz and the sums are final here
+            dz.record_stream(side)
+            self.bstats.record_stream(side)
+        else:
+            wst = self.st
+        K.conv2d_wgrad_stem_bn(rec.d, rec.x, dz, rec.y, rec.mean, rec.rstd, gamma, beta, bs, rec.act, rec.slope, self.gw(rec.conv),
+                               self.gvec(bn, "weight"), self.gvec(bn, "bias"), True, False, wst)
+
     def conv_bn_act_bwd(self, rec, dz, dx=None, dx_acc=False, dres=None, dres_acc=False, prev=None):
+        if self.tail_route(rec, dx, dres) == STEM_BN:
+            return self._stem_bn_bwd(rec, dz)
         dy = self.bn_bwd(rec.bn, rec.y, rec.z, (rec.mean, rec.rstd), dz, rec.act, rec.slope, dres, dres_acc, rec.has_res)
         self.conv_bwd(rec.conv, rec.d, rec.x, dy, dx, dx_acc, prev=prev)
 

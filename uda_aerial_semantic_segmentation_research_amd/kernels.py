@@ -484,6 +484,25 @@ def conv2d_fwd_stem(d, x, wfrag, y, stats=None, st=None):
     check(ops.udaseg_conv2d_fwd_stem_f32x3(d, x, wfrag, y, stats, st), "conv2d_fwd_stem_f32x3")
 
 
+def conv_stem_wgrad_bn_ok(d):
+    """May the stem's weight gradient form dy = bn_bwd_apply(dz, y) in its staging (csrc/conv_stem_wgrad.hip)?  Geometry, the
+    device's LDS and the STEM_WGRAD_BN switch; the caller knows whether the layer has a residual input or an unwritten activation."""
+    return bool(ops.udaseg_conv_stem_wgrad_bn_ok(d))
+
+
+def conv2d_wgrad_stem_bn(d, x, dz, y, save_mean, save_rstd, gamma, beta, bsums, act, slope, dw, dgamma, dbeta, accumulate=True,
+                         accumulate_param=False, st=None):
+    """dW (+)= the 7x7 / stride 2 stem's weight gradient from x and the never-stored dy = bn_bwd_apply(dz, y); dgamma / dbeta as
+    bn_bwd_apply writes them.  bsums: bn_bwd_reduce's."""
+    check(ops.udaseg_conv2d_wgrad_stem_bn(d, x, dz, y, save_mean, save_rstd, gamma, beta, bsums, act, slope, dw, dgamma, dbeta,
+                                          int(accumulate), int(accumulate_param), st), "conv2d_wgrad_stem_bn")
+
+
+def stem_wgrad_set_blocks(blocks):
+    """tests / tuning: cap on the blocks of a conv2d_wgrad_stem_bn launch (0: one per CU)."""
+    check(ops.udaseg_stem_wgrad_set_blocks(int(blocks)), "stem_wgrad_set_blocks")
+
+
 def conv_n16_ok(d, dgrad=False):
     return bool(ops.udaseg_conv_n16_f32x3_ok(d, int(dgrad)))
 
