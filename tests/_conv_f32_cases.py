@@ -240,6 +240,17 @@ def part_tier_a(case):
     return o
 
 
+WG_PART_X3 = WG_PART[:1]                  # the same two launches on conv_wgrad_x3_kernel (F32_SPLIT = 1; co = 72 > 32, ca and cs multiples of 8)
+
+
+@functools.lru_cache(maxsize=None)
+def part_x3_tier_a(case):
+    """part_tier_a's operands with the split grade's reference (the six-product model as tier A's second leg)."""
+    o = dict(part_tier_a(case))
+    o["wgrad"] = R.x3_wgrad(o["x"], o["dy"], 3, 1, 1)
+    return o
+
+
 @functools.lru_cache(maxsize=None)
 def part_tier_b(case, family):
     n, h, w, ca, cs, co = case

@@ -236,7 +236,12 @@ def stem_tier_b(case, family):
 
 # ============================================================ 5. the shared-source kernels with the split (F32_SPLIT = 1)
 # (n, h, w, ci, co, k, stride, pad): 3x3 / stride 2, 1x1 / stride 2, 4x4 / stride 2 / pad 1, 3x3 / stride 1 with 40 -> 72 channels
-X3 = [(1, 10, 14, 40, 72, 3, 2, 1), (1, 10, 14, 40, 72, 1, 2, 0), (1, 10, 14, 40, 72, 4, 2, 1), (1, 10, 14, 40, 72, 3, 1, 1)]
+X3 = [(1, 10, 14, 40, 72, 3, 2, 1), (1, 10, 14, 40, 72, 1, 2, 0), (1, 10, 14, 40, 72, 4, 2, 1), (1, 10, 14, 40, 72, 3, 1, 1),
+      # output widths 7 and 14 above: conv_wgrad_x3_kernel<..., false> only.  Row-uniform (the width a multiple of the 32-row load pass):
+      (1, 8, 32, 40, 72, 3, 1, 1),          # M = 256: ONE split, the plain store
+      (3, 5, 32, 40, 72, 3, 1, 1),          # M = 480 in images of 160: two splits of 256, the first ends INSIDE image 1
+      (1, 17, 64, 40, 72, 3, 2, 1),         # stride 2: 9 x 32 output
+      (2, 12, 12, 40, 72, 1, 1, 0)]         # 1x1/1: row-uniform through the one-row rewrite (wo = M = 288) only
 
 
 def out_hw(h, w, k, s, p):

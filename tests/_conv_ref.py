@@ -826,9 +826,58 @@ def wgrad_f32_plan(n, h, w, ci, co, k, stride, pad, blocks=0, generic=False, src
         wo = m
     uniform = not generic and wo % (256 // (bnw // 4)) == 0
     tiles = cdiv(co, bmw) * cdiv(k * k * (src_c or ci), bnw)
-    splits = max(1, min(cdiv(blocks if blocks >= 64 else 3072, tiles), cdiv(m, 256)))
-    kchunk = cdiv(cdiv(m, splits), 32) * 32
-    return "conv_wgrad_kernel<%d, %d, %d, %d, %s>" % (bmw, bnw, wm, wn, "true" if uniform else "false"), cdiv(m, kchunk), kchunk, m
+    splits, kchunk = wgrad_splits(m, tiles, blocks if blocks >= 64 else 3072, 32)
+    return "conv_wgrad_kernel<%d, %d, %d, %d, %s>" % (bmw, bnw, wm, wn, "true" if uniform else "false"), splits, kchunk, m
+
+
+def wgrad_splits(m, tiles, target, ktile, round8=False):
+    """The split-K planner of csrc/conv_wgrad.hip: (splits, pixels per split).  round8 (bf16): 16 or more splits over more than one
+    tile are rounded to the nearest multiple of 8 that still tiles M, for the XCD-aware block order; some may come out empty."""
+    splits = max(1, min(cdiv(target, tiles), cdiv(m, 256), 65535))
+    kchunk = cdiv(cdiv(m, splits), ktile) * ktile
+    splits = cdiv(m, kchunk)
+    if round8 and splits >= 16 and tiles > 1 and splits % 8:
+        s8 = (splits + 4) // 8 * 8
+        kc = cdiv(cdiv(m, s8), ktile) * ktile
+        if kc * (s8 - 8) < m:
+            splits, kchunk = s8, kc
+    return splits, kchunk
+
+
+def wgrad_bf16_tile(produced):
+    """conv2d_wgrad_impl on bf16 storage: (BMW, BNW, WAVES_M, WAVES_N)."""
+    return (128, 64, 2, 2) if produced >= 128 else (64, 64, 2, 2) if produced > 32 else (32, 128, 1, 4)
+
+
+def _wgrad_geometry(n, h, w, k, stride, pad, up):
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    m = n * ho * wo
+    return m, (m if k == 1 and stride == 1 and pad == 0 and not up else wo)
+
+
+def wgrad_bf16_plan(n, h, w, ci, co, k, stride, pad, blocks=0, generic=False, src_c=None, up=False, no_xcd=False):
+    """(symbol, splits, pixels per split, M, XCD-aware order, empty splits) of launch_wgrad<...>(bf16): 64-pixel K-tiles; a load pass
+    covers 256 / (BNW / 8) rows; 512 blocks wanted (2048 for the 32-row tile at >= 2^20 pixels) unless WGRAD_BLOCKS >= 64."""
+    m, wo = _wgrad_geometry(n, h, w, k, stride, pad, up)
+    bmw, bnw, wm, wn = wgrad_bf16_tile(co)
+    uniform = not generic and wo % (256 // (bnw // 8)) == 0
+    tiles = cdiv(co, bmw) * cdiv(k * k * (src_c or ci), bnw)
+    target = blocks if blocks >= 64 else (2048 if bmw == 32 and m >= 1 << 20 else 512)
+    splits, kchunk = wgrad_splits(m, tiles, target, 64, round8=True)
+    xcd = splits % 8 == 0 and tiles > 1 and not no_xcd
+    sym = "conv_wgrad_bf16_kernel<%d, %d, %d, %d, %s>" % (bmw, bnw, wm, wn, "true" if uniform else "false")
+    return sym, splits, kchunk, m, xcd, splits - cdiv(m, kchunk)
+
+
+def wgrad_x3_plan(n, h, w, ci, co, k, stride, pad, blocks=0, generic=False, src_c=None, up=False):
+    """(symbol, splits, pixels per split, M) of launch_wgrad<X3, 64, 64, 2, 2>: 32-pixel K-tiles, a 32-row load pass; row-uniform needs
+    gathered and produced channels that are multiples of 8 as well; 1024 blocks wanted unless WGRAD_X3_BLOCKS >= 64."""
+    m, wo = _wgrad_geometry(n, h, w, k, stride, pad, up)
+    g = src_c or ci
+    assert co > 32 and g % 8 == 0 and co % 8 == 0, "conv2d_wgrad_impl does not take the split here"
+    uniform = not generic and wo % 32 == 0
+    splits, kchunk = wgrad_splits(m, cdiv(co, 64) * cdiv(k * k * g, 64), blocks if blocks >= 64 else 1024, 32)
+    return "conv_wgrad_x3_kernel<64, 64, 2, 2, %s>" % ("true" if uniform else "false"), splits, kchunk, m
 
 
 def bn_fold_ref(w, bias, gamma, beta, rm, rv, eps, dt):

@@ -372,7 +372,15 @@ def test_the_other_launchers_accept_every_listed_case():
     assert all(R.n16_applicable(*c) for c in C.N16) and {c[3] for c in C.N16} == {g for g in range(1, 65) if R.n16_applicable(2, 9, 34, g)}
     assert all(R.stem_applicable(n, h, w, 4, 64) for n, h, w in C.STEM)
     assert all(R.x3_shared_applicable(c[3], c[4]) for c in C.X3)
-    assert {c[5:] for c in C.X3} == {(3, 2, 1), (1, 2, 0), (4, 2, 1), (3, 1, 1)}
+    assert {c[5:] for c in C.X3} == {(3, 2, 1), (1, 2, 0), (4, 2, 1), (3, 1, 1), (1, 1, 0)}
+    # conv_wgrad_x3_kernel: the first four cases are generic (output widths 7 and 14), the last four row-uniform unless WGRAD_GENERIC
+    xp = R.wgrad_x3_plan
+    assert all(xp(*c)[0] == "conv_wgrad_x3_kernel<64, 64, 2, 2, false>" for c in C.X3[:4])
+    assert all(xp(*c)[0] == "conv_wgrad_x3_kernel<64, 64, 2, 2, true>" and xp(*c, generic=True)[0].endswith("false>") for c in C.X3[4:])
+    assert xp(*C.X3[4])[1:] == (1, 256, 256)                                                 # one split: the plain store
+    assert xp(*C.X3[5])[1:] == (2, 256, 480) and 256 % (5 * 32) != 0                          # the first split ends inside image 1
+    assert xp(*C.X3[6])[1:] == (2, 160, 288) and C.out_hw(17, 64, 3, 2, 1) == (9, 32) and C.X3[6][6] == 2
+    assert C.X3[7][5:] == (1, 1, 0) and C.X3[7][2] % 32 != 0 and xp(*C.X3[7])[3] % 32 == 0       # row-uniform through a.wo = M only
     assert [R.wgrad_up_config(n, h, w, ca + cs, co, ca) for n, h, w, ca, cs, co in C.WG_UP] == [2, 1, 3, 2]
     assert {R.wgrad_h2_config(h, w, ci, co) for n, h, w, ci, co in C.WG_HALO} == {1, 2, 3, 4}       # every channel-block shape
     assert all(R.wgrad_h2_config(h, w, ci, co) for n, h, w, ci, co in C.WG_BNIN + [c[:5] for c in C.WG_SLICE])
@@ -664,6 +672,12 @@ def test_the_f32_shapes_reach_every_launch_regime():
         geom = (n, h, w, ca + cs, co, 3, 1, 1)
         assert plan(*geom, src_c=ca, up=True)[0].endswith("true>") and plan(*geom, src_c=cs)[0].endswith("true>") and ca % 4 == 0 and cs % 4 == 0
     assert {R.wgrad_f32_tile(c[5])[0] for c in C32.WG_PART} == {64, 32}
+    # the same halves on conv_wgrad_x3_kernel: both row-uniform (a 32-pixel-wide output), generic under WGRAD_GENERIC
+    for n, h, w, ca, cs, co in C32.WG_PART_X3:
+        geom = (n, h, w, ca + cs, co, 3, 1, 1)
+        for kw in (dict(src_c=ca, up=True), dict(src_c=cs)):
+            assert R.wgrad_x3_plan(*geom, **kw)[0].endswith("true>") and R.wgrad_x3_plan(*geom, generic=True, **kw)[0].endswith("false>")
+    assert C32.WG_PART_X3 == C32.WG_PART[:1]
 
 
 ALL7 = sorted(ALL5 + ["bf16 operand", "low split term"])
@@ -838,3 +852,27 @@ def test_f32_wgrad_part_and_fused_x3_and_bn_fold_references():
         assert np.allclose(w64, b["w"] * s[:, None, None, None], rtol=1e-14) and np.allclose(b64, b["beta"] + (b["bias"].astype(F64) - b["rm"]) * s, rtol=1e-12, atol=1e-14)
         assert N.bar(w32, w64, np.abs(w64))[0] <= 2.0 ** -20 and N.bar(b32, b64, mag)[0] <= 2.0 ** -20 and w32.dtype == F32
     assert {c[0] for c in C32.BN_FOLD} == {4, 24, 64}
+
+
+def test_the_bf16_weight_gradient_cases_reach_their_plans():
+    """launch_wgrad<..., bf16>, restated in _conv_ref.wgrad_bf16_plan: the split-K cases of tests/test_gpu_conv_bf16_grade.py reach both
+    ungraded tiles under both gathers, the XCD-aware block order with and without empty splits, and the two-dimensional grid."""
+    import test_gpu_conv_bf16_grade as B16
+    plan = R.wgrad_bf16_plan
+    got = [plan(*c, generic=bool(g), no_xcd=bool(x)) for c, g, x in B16.WG_SPLITK]
+    big, small = "conv_wgrad_bf16_kernel<128, 64, 2, 2, %s>", "conv_wgrad_bf16_kernel<32, 128, 1, 4, %s>"
+    assert [t[0] for t in got] == [big % "true", big % "false", small % "true", small % "false", big % "true", big % "true", big % "true"]
+    # M = 480 in images of 160 (5 x 32) / (10 x 16): two splits of 256, the first ends inside image 1; too few splits for the XCD order
+    assert all(t[1:] == (2, 256, 480, False, 0) for t in got[:4]) and 256 % 160 != 0
+    assert got[4][1:] == (16, 256, 4096, True, 0)                     # 9 tiles, 16 splits of 256 in XCD-aware order
+    assert got[5][1:] == (24, 256, 5376, True, 3)                     # 21 splits rounded up to 24: three empty ones
+    assert got[6][1:] == (24, 256, 5376, False, 3)                    # WGRAD_NO_XCD: the same plan on the two-dimensional grid
+    assert R.cdiv(128, 128) * R.cdiv(9 * 64, 64) == 9 and R.wgrad_splits(5376, 9, 512, 64) == (21, 256)
+    # every case of the older lists is the 64 x 64 or the 128 x 64 tile with fewer than 16 splits: what the cases above add
+    for c in B16.IGEMM + [s + (3, 1, 1) for s in B16.WG]:
+        assert plan(*c)[1] < 16 and not plan(*c)[0].startswith(small[:28])
+    n, h, w, ca, cs, co = B16.WG_PART
+    geom = (n, h, w, ca + cs, co, 3, 1, 1)
+    for kw in (dict(src_c=ca, up=True), dict(src_c=cs)):
+        assert plan(*geom, **kw)[0] == "conv_wgrad_bf16_kernel<64, 64, 2, 2, true>" and plan(*geom, generic=True, **kw)[0].endswith("false>")
+    assert ca % 8 == 0 and cs % 8 == 0 and h % 2 == 0 and w % 2 == 0

@@ -417,16 +417,16 @@ def igemm_launches(K, G, case, tile, generic, no_fold=False, mode="randn", epilo
                     np.broadcast_to(R.leaky(c["bias"][co - 1:], SLOPE, F32), (n, d.ho, d.wo)))
 
 
-def wgrad_launches(K, G, case, mode="randn", tag=""):
+def wgrad_launches(K, G, case, mode="randn", tag="", expect="conv_wgrad_bf16_kernel<", c=None):
     n, h, w, ci, co, k, s, p = case
-    c = igemm_case(case, mode)
+    c = c or igemm_case(case, mode)
     d = K.conv_desc(n, h, w, ci, co, k, s, p)
     xd, dyd = dev(c["x"]), dev(c["dy"])
     dw = nan_out((co, k, k, ci), torch.float32)
-    ran(K, G, tag + "wgrad", "conv_wgrad_bf16_kernel<", lambda: K.conv2d_wgrad_bf16(d, xd, dyd, dw))
+    ran(K, G, tag + "wgrad", expect, lambda: K.conv2d_wgrad_bf16(d, xd, dyd, dw))
     G.grade(tag + "wgrad over NaN -> fp32", host(dw), c["wgrad"], False)
     dwa = dev(c["oldw"], torch.float32)
-    ran(K, G, tag + "wgrad accumulate", "conv_wgrad_bf16_kernel<", lambda: K.conv2d_wgrad_bf16(d, xd, dyd, dwa, accumulate=True))
+    ran(K, G, tag + "wgrad accumulate", expect, lambda: K.conv2d_wgrad_bf16(d, xd, dyd, dwa, accumulate=True))
     G.grade(tag + "wgrad accumulated onto fp32", host(dwa), R.epilogue(c["wgrad"], old=c["oldw"]), False)
 
 
@@ -537,4 +537,62 @@ def test_wgrad_1x1_row_form_and_operand_edges(K):
         dwa = dev(c["oldw"], torch.float32)
         ran(K, G, f"{mode} wgrad halo", "conv_wgrad_h2_kernel<", lambda: K.conv2d_wgrad_halo(d, dev(c["x"]), None, dev(c["dy"]), dwa))
         G.grade(f"{mode} wgrad halo accumulated onto fp32", host(dwa), R.epilogue(c["wgrad"], old=c["oldw"]), False)
+    G.done()
+
+
+# ================================================================================= conv_wgrad_bf16_kernel: tiles, gathers, block order
+# (n, h, w, ci, co, k, stride, pad), WGRAD_GENERIC, WGRAD_NO_XCD.  The 128 x 64 tile (co >= 128: a 32-row load pass) at an output width
+# of 32 and the 32 x 128 tile (co <= 32: a 16-row pass) at 16, M = 480 in three images: two splits, the first ends inside image 1.
+# The XCD-aware block order needs a multiple of 8 >= 16 splits of >= 256 pixels: M = 4096 (16 splits) and M = 5376 (21 splits
+# rounded to 24, three of them empty), the latter also on the two-dimensional grid.
+WG_SPLITK = [((3, 5, 32, 64, 128, 3, 1, 1), 0, 0), ((3, 5, 32, 64, 128, 3, 1, 1), 1, 0),
+             ((3, 10, 16, 64, 24, 3, 1, 1), 0, 0), ((3, 10, 16, 64, 24, 3, 1, 1), 1, 0),
+             ((1, 64, 64, 64, 128, 3, 1, 1), 0, 0), ((1, 84, 64, 64, 128, 3, 1, 1), 0, 0), ((1, 84, 64, 64, 128, 3, 1, 1), 0, 1)]
+WG_PART = (2, 16, 32, 32, 40, 72)          # conv2d_wgrad_part: (n, h, w, ca, cs, co)
+
+
+@functools.lru_cache(maxsize=None)
+def wgrad_case(case):
+    """Operands and the reference of a weight gradient alone (igemm_case forms the forward and the data gradient as well)."""
+    n, h, w, ci, co, k, s, p = case
+    rng = np.random.default_rng(seed_of("wgrad", case))
+    ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+    x, dy = R.randn_bf16(rng, (n, h, w, ci)), R.randn_bf16(rng, (n, ho, wo, co))
+    return dict(x=x, dy=dy, oldw=rng.standard_normal((co, k, k, ci)).astype(F32), wgrad=R.wgrad(x, dy, k, s, p))
+
+
+@pytest.mark.parametrize("case,generic,no_xcd", WG_SPLITK,
+                         ids=[("n%d_%dx%d_ci%d_co%d_k%d_s%d_p%d" % c) + ("-generic" if g else "-uniform") + ("-noxcd" if x else "") for c, g, x in WG_SPLITK])
+def test_wgrad_split_k_tiles_and_block_order(K, case, generic, no_xcd):
+    """conv2d_wgrad_bf16 on conv_wgrad_bf16_kernel<128, 64, 2, 2, *> and <32, 128, 1, 4, *> under both gathers, and the XCD-aware
+    one-dimensional block order with and without empty splits; the symbol by name from the launcher's arithmetic restated in
+    _conv_ref.wgrad_bf16_plan (asserted on the CPU in tests/test_conv_ref_host.py)."""
+    G = R.Grader(f"wgrad split-K {case} generic{generic} no_xcd{no_xcd}", _log)
+    sym = R.wgrad_bf16_plan(*case, generic=bool(generic), no_xcd=bool(no_xcd))[0]
+    with options(K, WGRAD_GENERIC=generic, WGRAD_NO_XCD=no_xcd):
+        wgrad_launches(K, G, case, expect=sym, c=wgrad_case(case))
+    G.done()
+
+
+@pytest.mark.parametrize("generic", [0, 1], ids=["uniform", "generic"])
+def test_wgrad_channel_slices(K, generic):
+    """conv2d_wgrad_part on bf16 tensors: the up-sampled half (c_off = 0, read through nearest_x2) and the skip half (c_off = ca) of
+    the weight gradient over cat([nearest_x2(a), skip]), two launches accumulating into one fp32 dW."""
+    n, h, w, ca, cs, co = WG_PART
+    rng = np.random.default_rng(seed_of("wgrad part", WG_PART))
+    G = R.Grader(f"wgrad part {WG_PART} generic{generic}", _log)
+    a, skip, dy = R.randn_bf16(rng, (n, h // 2, w // 2, ca)), R.randn_bf16(rng, (n, h, w, cs)), R.randn_bf16(rng, (n, h, w, co))
+    oldw = rng.standard_normal((co, 3, 3, ca + cs)).astype(F32)
+    geom = (n, h, w, ca + cs, co, 3, 1, 1)
+    sym_a = R.wgrad_bf16_plan(*geom, generic=bool(generic), src_c=ca, up=True)[0]
+    sym_s = R.wgrad_bf16_plan(*geom, generic=bool(generic), src_c=cs)[0]
+    d = K.conv_desc(*geom)
+    dw = dev(oldw, torch.float32)
+    with options(K, WGRAD_GENERIC=generic):
+        ran(K, G, "part up", sym_a, lambda: K.conv2d_wgrad_part(d, dev(a), 0, True, dev(dy), dw, True))
+        half = host(dw).copy()
+        G.exact("skip channels after the up-sampled half's launch", half[..., ca:], oldw[..., ca:])
+        ran(K, G, "part skip", sym_s, lambda: K.conv2d_wgrad_part(d, dev(skip), ca, False, dev(dy), dw, True))
+    G.exact("up-sampled channels after the skip half's launch", host(dw)[..., :ca], half[..., :ca])
+    G.grade("wgrad of both halves accumulated onto fp32", host(dw), R.epilogue(R.wgrad(R.upcat(a, skip), dy, 3, 1, 1), old=oldw), False)
     G.done()

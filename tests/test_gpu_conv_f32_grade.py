@@ -29,9 +29,9 @@ its first launch; there is no fixed table and no numeric id any more):
   conv3x3_small_kernel<1, 1 | 2, 1 | 1, 2>,  conv3x3_small_wgrad_kernel<1, 1 | 2, 1 | 1, 2>   (small_wgrad_fold_kernel carries no
   timing record of its own: it is graded through the weight gradient it finishes)
   conv_wgrad_kernel<64, 64, 2, 2, false | true>,  conv_wgrad_kernel<32, 128, 1, 4, false | true>
-Not reachable: conv_wgrad_kernel<128, ...> is compiled (launch_wgrad is one template for both storages) but never launched and so
-never registered: conv2d_wgrad_impl takes the 128-row tile for bf16 alone, no fp32 entry point leads there.  The bf16 launches
-register their own symbols, graded in test_gpu_conv_bf16_grade.py.
+conv_wgrad_kernel<128, ...> does not exist: the storage is a compile-time parameter of launch_wgrad, and conv2d_wgrad_impl takes
+the 128-row tile for bf16 alone.  The bf16 launches register their own symbols, graded in test_gpu_conv_bf16_grade.py; the channel
+slices are graded on conv_wgrad_x3_kernel as well (F32_SPLIT = 1).
 
 Set UDASEG_DEVIATION_LOG to a file name to collect the figures (profiles/conv_f32_grade.txt).
 """
@@ -378,19 +378,19 @@ def test_wgrad_split_k(K, case, blocks, generic):
     G.done()
 
 
-@pytest.mark.parametrize("generic", (0, 1), ids=("uniform", "generic"))
-@pytest.mark.parametrize("case", C.WG_PART, ids=["n%d_%dx%d_ca%d_cs%d_co%d" % c for c in C.WG_PART])
-def test_wgrad_channel_slices(K, case, generic):
+def channel_slices(K, case, generic, split):
     """conv2d_wgrad_part: the up-sampled half (c_off = 0, read through nearest_x2) and the skip half (c_off = ca) of the weight
-    gradient over cat([nearest_x2(a), skip]), two launches accumulating into one dW."""
+    gradient over cat([nearest_x2(a), skip]), two launches accumulating into one dW.  split: on conv_wgrad_x3_kernel, with the
+    split grade's bar; else on conv_wgrad_kernel."""
     n, h, w, ca, cs, co = case
-    G = R.F32Grader(f"wgrad part {case} {'generic' if generic else 'uniform'}", _log)
-    o = C.part_tier_a(case)
+    G = (R.X3Grader if split else R.F32Grader)(f"wgrad part {'x3 ' if split else ''}{case} {'generic' if generic else 'uniform'}", _log)
+    o = C.part_x3_tier_a(case) if split else C.part_tier_a(case)
     geom = (n, h, w, ca + cs, co, 3, 1, 1)
-    sym_a = R.wgrad_f32_plan(*geom, generic=bool(generic), src_c=ca, up=True)[0]
-    sym_s = R.wgrad_f32_plan(*geom, generic=bool(generic), src_c=cs)[0]
+    plan = R.wgrad_x3_plan if split else R.wgrad_f32_plan
+    sym_a = plan(*geom, generic=bool(generic), src_c=ca, up=True)[0]
+    sym_s = plan(*geom, generic=bool(generic), src_c=cs)[0]
     d = K.conv_desc(*geom)
-    with options(K, F32_SPLIT=0, WGRAD_GENERIC=generic):
+    with options(K, F32_SPLIT=split, WGRAD_GENERIC=generic):
         dw = Out(o["oldw"].shape, o["oldw"])
         ran(K, G, "part up", sym_a, lambda: K.conv2d_wgrad_part(d, dev(o["a"]), 0, True, dev(o["dy"]), dw.t, True))
         half = dw.host().copy()
@@ -408,6 +408,20 @@ def test_wgrad_channel_slices(K, case, generic):
             outs.append(e)
     guards(G, "wgrad part", *outs)
     G.done()
+
+
+@pytest.mark.parametrize("generic", (0, 1), ids=("uniform", "generic"))
+@pytest.mark.parametrize("case", C.WG_PART, ids=["n%d_%dx%d_ca%d_cs%d_co%d" % c for c in C.WG_PART])
+def test_wgrad_channel_slices(K, case, generic):
+    """The two halves on conv_wgrad_kernel<64, 64, 2, 2, *> / <32, 128, 1, 4, *> (F32_SPLIT = 0)."""
+    channel_slices(K, case, generic, 0)
+
+
+@pytest.mark.parametrize("generic", (0, 1), ids=("uniform", "generic"))
+@pytest.mark.parametrize("case", C.WG_PART_X3, ids=["n%d_%dx%d_ca%d_cs%d_co%d" % c for c in C.WG_PART_X3])
+def test_wgrad_channel_slices_on_the_split(K, case, generic):
+    """The two halves on conv_wgrad_x3_kernel<64, 64, 2, 2, *> (F32_SPLIT = 1): the up and c_off paths of its two gathers."""
+    channel_slices(K, case, generic, 1)
 
 
 # ======================================================================= 4. conv2d_fwd_fused on an X3 instance (F32_SPLIT = 1)

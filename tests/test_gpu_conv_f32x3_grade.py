@@ -419,7 +419,7 @@ def test_shared_source_split(K, case):
     G = R.X3Grader(f"x3 {case}", _log)
     o = C.x3_tier_a(case)
     d = K.conv_desc(n, h, w, ci, co, k, s, p)
-    ig, wg = ("conv_igemm_kernel<", ", true>"), ("conv_wgrad_x3_kernel<", ">")
+    ig, wg = ("conv_igemm_kernel<", ", true>"), (R.wgrad_x3_plan(*case)[0], "")        # the generic or the row-uniform gather, by name
 
     def wpair(wt):
         wd = dev(wt)

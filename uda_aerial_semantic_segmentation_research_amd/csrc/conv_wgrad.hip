@@ -44,7 +44,7 @@ struct WgradArgs {
   int kchunk;        // pixels per split (multiple of 32)
   int use_atomic;
   float inv_ci, inv_kw, inv_wo, inv_ho;
-  int row_uniform;   // host-side selector of the row-uniform gather (see conv_wgrad_kernel)
+  int row_uniform;   // host-side selector of the row-uniform gather (WgradRowGather)
   unsigned x_bytes, dy_bytes;
   // A launch may produce only a channel SLICE of dW -- the weight gradient of a convolution over a virtual concatenation
   // (fused decoder input cat([up(a), skip])) is one launch per source: x is that source ([..][ci] with ci = ITS channel
@@ -65,13 +65,165 @@ struct WgradArgs {
   int xcd_tiles, xcd_splits;
 };
 
+// ---------------------------------------------------------------------------------------- what the three kernels share
+// conv_wgrad_kernel (fp32 pipe), conv_wgrad_bf16_kernel (bf16 storage) and conv_wgrad_x3_kernel (fp32 split three ways onto the bf16
+// pipe) differ in how a staged tile is written to LDS and multiplied; the block and tap decode, the two gathers' address arithmetic,
+// the accumulator zeroing and the epilogue are the pieces below.
+
+struct WgradTile { int co0, j0, kbeg, kend; };   // first dW row and column of the block's tile, its pixel range [kbeg, kend)
+
+template <int BMW, int BNW>
+__device__ __forceinline__ WgradTile wgrad_tile(const WgradArgs& a, int tile_id, int split_id) {
+  const int ntj = (a.J + BNW - 1) / BNW;
+  const int kbeg = split_id * a.kchunk;
+  return {(tile_id / ntj) * BMW, (tile_id % ntj) * BNW, kbeg, min(a.M, kbeg + a.kchunk)};
+}
+
+struct WgradTap { int tap, dy, dx, c; };   // column j of the launch's J axis: tap = j / ci at input offset (dy, dx), channel c of the source
+
+__device__ __forceinline__ WgradTap wgrad_tap(const WgradArgs& a, int j) {
+  const int tap = fast_div(j, a.ci, a.inv_ci);
+  const int r = fast_div(tap, a.kw, a.inv_kw);
+  return {tap, r - a.pad, (tap - r * a.kw) - a.pad, j - tap * a.ci};
+}
+
+constexpr unsigned WG_OOB = 0x80000000u;   // a byte offset outside any buffer range: the load returns zeros
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wgrad_rsrc(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+
+// Row-uniform gather.  When the output width is a multiple of the rows one load pass covers, the pixels of a pass share their image
+// row: (image, oy, first ox) are SCALARS updated once per K-tile, a thread's gather address is scalar + per-thread constant, and the
+// bounds test is two adds and two compares; loads are range-checked buffer loads (invalid lanes get an out-of-range offset and read
+// zeros).  The generic loop spends two divisions and a 64-bit address per gathered row per K-tile in the VALU, which on gfx950 shares
+// its ALUs with the fp32 MFMA.
+// The state: per-thread constants and per-pass scalars of the NEXT tile to load (tiles are loaded in order).  ES: bytes per element,
+// KT: pixels per K-tile; pass p of dy covers rows arow + A_ROWS * p, of x rows brow + B_ROWS * p.  The kernels issue the loads.
+template <int ES, int KT, int A_PASS, int A_ROWS, int B_PASS, int B_ROWS>
+struct WgradRowGather {
+  unsigned u_ac[A_PASS], u_bc;
+  int u_bdy, u_bx;
+  int s_ni[B_PASS], s_oy[B_PASS], s_ox[B_PASS];
+  unsigned s_dyoff;
+
+  __device__ __forceinline__ void init(const WgradArgs& a, int kbeg, int arow, int a_co, bool a_ok, int brow, const WgradTap& b, bool b_ok) {
+#pragma unroll
+    for (int p = 0; p < A_PASS; ++p)
+      u_ac[p] = a_ok ? (unsigned)((arow + A_ROWS * p) * a.co + a_co) * (unsigned)ES : WG_OOB;
+    u_bdy = b.dy;
+    u_bx = brow * a.stride + b.dx;
+    // up-sampled source: the column part of (ix >> 1) splits into scalar + constant because a pass starts at an even ox;
+    // the row part (iy >> 1) depends on the parity of the scalar oy and is formed per load
+    u_bc = !b_ok ? WG_OOB
+                 : a.up ? (unsigned)((u_bx >> 1) * a.ci + b.c) * (unsigned)ES
+                        : (unsigned)((b.dy * a.wi + brow * a.stride + b.dx) * a.ci + b.c) * (unsigned)ES;
+    s_dyoff = (unsigned)kbeg * (unsigned)a.co * (unsigned)ES;
+#pragma unroll
+    for (int p = 0; p < B_PASS; ++p) {
+      const int m = kbeg + B_ROWS * p;          // uniform
+      const int t1 = m / a.wo;
+      s_ox[p] = m - t1 * a.wo;
+      s_ni[p] = t1 / a.ho;
+      s_oy[p] = t1 - s_ni[p] * a.ho;
+    }
+  }
+  // byte offset of this thread's piece of dy in pass p of the next tile; dy_advance() once all passes are requested
+  __device__ __forceinline__ unsigned dy_offset(int p) const { return u_ac[p] + s_dyoff; }
+  __device__ __forceinline__ void dy_advance(const WgradArgs& a) { s_dyoff += (unsigned)(KT * ES) * (unsigned)a.co; }
+  // byte offset of this thread's piece of x in pass p of the next tile (WG_OOB outside the image; inside: the tap is in bounds);
+  // x_advance(p) once the load is requested
+  __device__ __forceinline__ unsigned x_offset(const WgradArgs& a, int p, bool& inside) const {
+    const int oys = s_oy[p] * a.stride, oxs = s_ox[p] * a.stride;                                   // scalars
+    inside = (unsigned)(oys + u_bdy) < (unsigned)a.hi && (unsigned)(oxs + u_bx) < (unsigned)a.wi;
+    unsigned voff;
+    if (a.up) {   // uniform branch
+      const int w2 = a.wi >> 1;
+      const unsigned s_off = (unsigned)((s_ni[p] * (a.hi >> 1) * w2 + (oxs >> 1)) * a.ci) * (unsigned)ES;   // scalar
+      voff = u_bc + s_off + (unsigned)(((oys + u_bdy) >> 1) * w2 * a.ci) * (unsigned)ES;
+    } else {
+      const unsigned s_off = (unsigned)(((s_ni[p] * a.hi + oys) * a.wi + oxs) * a.ci) * (unsigned)ES;        // scalar
+      voff = u_bc + s_off;
+    }
+    return inside ? voff : WG_OOB;
+  }
+  __device__ __forceinline__ unsigned x_offset(const WgradArgs& a, int p) const {
+    bool inside;
+    return x_offset(a, p, inside);
+  }
+  // pass p moves on by one K-tile; wo is a multiple of B_ROWS, so a pass never straddles image rows.  Called AFTER the pass's load
+  // is requested: with the walk ahead of the load (one call for both) the 32 x 128 fp32 tile, four passes per K-tile, ran 12 us of
+  // 790 slower at 8 x 512 x 512 x 64 -> 16 in every leg (profiles/wgrad_shared_refactor.txt)
+  __device__ __forceinline__ void x_advance(const WgradArgs& a, int p) {
+    s_ox[p] += KT;
+    while (s_ox[p] >= a.wo) {
+      s_ox[p] -= a.wo;
+      if (++s_oy[p] == a.ho) {
+        s_oy[p] = 0;
+        ++s_ni[p];
+      }
+    }
+  }
+};
+
+// Generic gather: output pixel m -> (image, oy, ox), and the pixel index of tap t's source element (false: outside the image)
+struct WgradPixel { int ni, oy, ox; };
+
+__device__ __forceinline__ WgradPixel wgrad_pixel(const WgradArgs& a, int m) {
+  const int t1 = fast_div(m, a.wo, a.inv_wo);
+  const int ni = fast_div(t1, a.ho, a.inv_ho);
+  return {ni, t1 - ni * a.ho, m - t1 * a.wo};
+}
+
+__device__ __forceinline__ bool wgrad_source(const WgradArgs& a, const WgradPixel& o, const WgradTap& t, size_t& pix) {
+  const int iy = o.oy * a.stride + t.dy, ix = o.ox * a.stride + t.dx;
+  if ((unsigned)iy >= (unsigned)a.hi || (unsigned)ix >= (unsigned)a.wi) return false;
+  pix = a.up ? (size_t)(o.ni * (a.hi >> 1) + (iy >> 1)) * (a.wi >> 1) + (ix >> 1) : (size_t)(o.ni * a.hi + iy) * a.wi + ix;
+  return true;
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void wgrad_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+}
+
+// A wave's TM x TN accumulators of 32 x 32 -> dW, first row co_w and first column j_w.  D reg v of lane (lr, lh): row co =
+// (v&3) + 8*(v>>2) + 4*lh, col j = lr; one 128-B row segment per half-wave.
+template <int TM, int TN>
+__device__ __forceinline__ void wgrad_store(const WgradArgs& a, const f32x16 (&acc)[TM][TN], int co_w, int j_w, int lr, int lh) {
+  int col[TN];   // this lane's dW column per tile: (tap, c) of the launch's source -> tap * ci_full + c_off + c
+#pragma unroll
+  for (int jn = 0; jn < TN; ++jn) {
+    const int jj = j_w + jn * 32 + lr;
+    const WgradTap t = wgrad_tap(a, jj);
+    col[jn] = jj < a.J ? t.tap * a.ci_full + a.c_off + t.c : -1;
+  }
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int co = co_w + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
+      if (co >= a.co) continue;
+#pragma unroll
+      for (int jn = 0; jn < TN; ++jn) {
+        if (col[jn] >= 0) {
+          float* dst = a.dw + (size_t)co * a.J_ld + col[jn];
+          if (a.use_atomic) atomicAdd(dst, acc[i][jn][v]);
+          else *dst = acc[i][jn][v];
+        }
+      }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- fp32 pipe
 constexpr int WBK = 32;  // pixels per K-tile
 
-// ROWU = true: row-uniform gather.  When the output width is a multiple of the rows one load pass covers, the pixels of a
-// pass share their image row: (image, oy, first ox) are SCALARS updated once per K-tile, a thread's gather address is
-// scalar + per-thread constant, and the bounds test is two adds and two compares; loads are range-checked buffer loads
-// (invalid lanes get an out-of-range offset and read zeros).  The generic loop spends two divisions and a 64-bit address
-// per gathered row per K-tile in the VALU, which on gfx950 shares its ALUs with the fp32 MFMA.
+// ROWU: the row-uniform gather (WgradRowGather), else the generic one.
 template <int BMW, int BNW, int WAVES_M, int WAVES_N, bool ROWU>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
   constexpr int WM = BMW / WAVES_M, WN = BNW / WAVES_N;
@@ -88,127 +240,60 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
   const int wm = (wave / WAVES_N) * WM, wn = (wave % WAVES_N) * WN;
-
-  const int ntj = (a.J + BNW - 1) / BNW;
-  const int co0 = (blockIdx.x / ntj) * BMW;
-  const int j0 = (blockIdx.x % ntj) * BNW;
-  const int kbeg = blockIdx.y * a.kchunk;
-  const int kend = min(a.M, kbeg + a.kchunk);
+  const WgradTile t = wgrad_tile<BMW, BNW>(a, blockIdx.x, blockIdx.y);
 
   // A (dy) slot: column aq (4 channels), rows arow + A_ROWS*p
   const int aq = tid % AQ, arow = tid / AQ;
-  const int a_co = co0 + aq * 4;
+  const int a_co = t.co0 + aq * 4;
   const bool a_ok = a_co < a.co;
   // B (x gather) slot: column bq -> fixed (tap, c)
   const int bq = tid % BQ, brow = tid / BQ;
-  const int j = j0 + bq * 4;
+  const int j = t.j0 + bq * 4;
   const bool b_ok = j < a.J;
-  int b_dy = 0, b_dx = 0, b_c = 0;
-  if (b_ok) {
-    const int tap = fast_div(j, a.ci, a.inv_ci);
-    b_c = j - tap * a.ci;
-    const int r = fast_div(tap, a.kw, a.inv_kw);
-    b_dy = r - a.pad;
-    b_dx = (tap - r * a.kw) - a.pad;
-  }
+  const WgradTap b = b_ok ? wgrad_tap(a, j) : WgradTap{0, 0, 0, 0};
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  wgrad_zero(acc);
 
   f32x4 ra[A_PASS], rb[B_PASS];
-  const int nkt = (kend - kbeg + WBK - 1) / WBK;
+  const int nkt = (t.kend - t.kbeg + WBK - 1) / WBK;
 
-  // row-uniform state: per-thread constants and per-pass scalars of the NEXT tile to load (tiles are loaded in order)
-  unsigned u_ac[A_PASS], u_bc = 0;
-  int u_bdy = 0, u_bx = 0;
-  int s_ni[B_PASS], s_oy[B_PASS], s_ox[B_PASS];
-  unsigned s_dyoff = 0;
+  WgradRowGather<4, WBK, A_PASS, A_ROWS, B_PASS, B_ROWS> g;
   __amdgpu_buffer_rsrc_t rsrc_x, rsrc_dy;
   if constexpr (ROWU) {
-    rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), 0, (int)a.dy_bytes, 0x00020000);
-#pragma unroll
-    for (int p = 0; p < A_PASS; ++p)
-      u_ac[p] = a_ok ? (unsigned)((arow + A_ROWS * p) * a.co + a_co) * 4u : 0x80000000u;
-    u_bdy = b_dy;
-    u_bx = brow * a.stride + b_dx;
-    // up-sampled source: the column part of (ix >> 1) splits into scalar + constant because a pass starts at an even ox;
-    // the row part (iy >> 1) depends on the parity of the scalar oy and is formed per load
-    u_bc = !b_ok ? 0x80000000u
-                 : a.up ? (unsigned)((u_bx >> 1) * a.ci + b_c) * 4u
-                        : (unsigned)((b_dy * a.wi + brow * a.stride + b_dx) * a.ci + b_c) * 4u;
-    s_dyoff = (unsigned)kbeg * (unsigned)a.co * 4u;
-#pragma unroll
-    for (int p = 0; p < B_PASS; ++p) {
-      const int m = kbeg + B_ROWS * p;          // uniform
-      const int t1 = m / a.wo;
-      s_ox[p] = m - t1 * a.wo;
-      s_ni[p] = t1 / a.ho;
-      s_oy[p] = t1 - s_ni[p] * a.ho;
-    }
+    rsrc_x = wgrad_rsrc(a.x, a.x_bytes);
+    rsrc_dy = wgrad_rsrc(a.dy, a.dy_bytes);
+    g.init(a, t.kbeg, arow, a_co, a_ok, brow, b, b_ok);
   }
 
   auto load_tile = [&](int kt) {
     if constexpr (ROWU) {
 #pragma unroll
       for (int p = 0; p < A_PASS; ++p)
-        ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)(u_ac[p] + s_dyoff), 0, 0));
-      s_dyoff += (unsigned)(WBK * 4) * (unsigned)a.co;
+        ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)g.dy_offset(p), 0, 0));
+      g.dy_advance(a);
 #pragma unroll
       for (int p = 0; p < B_PASS; ++p) {
-        const int oys = s_oy[p] * a.stride, oxs = s_ox[p] * a.stride;                                   // scalars
-        const bool ok = (unsigned)(oys + u_bdy) < (unsigned)a.hi && (unsigned)(oxs + u_bx) < (unsigned)a.wi;
-        unsigned voff;
-        if (a.up) {   // uniform branch
-          const int w2 = a.wi >> 1;
-          const unsigned s_off = (unsigned)((s_ni[p] * (a.hi >> 1) * w2 + (oxs >> 1)) * a.ci) * 4u;   // scalar
-          voff = u_bc + s_off + (unsigned)(((oys + u_bdy) >> 1) * w2 * a.ci) * 4u;
-        } else {
-          const unsigned s_off = (unsigned)(((s_ni[p] * a.hi + oys) * a.wi + oxs) * a.ci) * 4u;        // scalar
-          voff = u_bc + s_off;
-        }
-        voff = ok ? voff : 0x80000000u;
-        rb[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)voff, 0, 0));
-        // advance this pass by one K-tile (32 pixels); wo is a multiple of B_ROWS, so a pass never straddles image rows
-        s_ox[p] += WBK;
-        while (s_ox[p] >= a.wo) {
-          s_ox[p] -= a.wo;
-          if (++s_oy[p] == a.ho) {
-            s_oy[p] = 0;
-            ++s_ni[p];
-          }
-        }
+        rb[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)g.x_offset(a, p), 0, 0));
+        g.x_advance(a, p);
       }
       return;
     }
-    const int mb = kbeg + kt * WBK;
+    const int mb = t.kbeg + kt * WBK;
 #pragma unroll
     for (int p = 0; p < A_PASS; ++p) {
       const int m = mb + arow + A_ROWS * p;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (a_ok && m < kend) v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.dy) + (size_t)m * a.co + a_co);
+      if (a_ok && m < t.kend) v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.dy) + (size_t)m * a.co + a_co);
       ra[p] = v;
     }
 #pragma unroll
     for (int p = 0; p < B_PASS; ++p) {
       const int m = mb + brow + B_ROWS * p;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (b_ok && m < kend) {
-        const int t1 = fast_div(m, a.wo, a.inv_wo);
-        const int ox = m - t1 * a.wo;
-        const int ni = fast_div(t1, a.ho, a.inv_ho);
-        const int oy = t1 - ni * a.ho;
-        const int iy = oy * a.stride + b_dy, ix = ox * a.stride + b_dx;
-        if ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) {
-          const size_t pix = a.up ? (size_t)(ni * (a.hi >> 1) + (iy >> 1)) * (a.wi >> 1) + (ix >> 1) : (size_t)(ni * a.hi + iy) * a.wi + ix;
-          v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.x) + pix * (size_t)a.ci + b_c);
-        }
-      }
+      size_t pix;
+      if (b_ok && m < t.kend && wgrad_source(a, wgrad_pixel(a, m), b, pix))
+        v = *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.x) + pix * (size_t)a.ci + b.c);
       rb[p] = v;
     }
   };
@@ -245,30 +330,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
     __syncthreads();
     cur ^= 1;
   }
-
-  // D reg v of lane (lr, lh): row co = (v&3) + 8*(v>>2) + 4*lh, col j = lr
-  int col[TN];   // this lane's dW column per tile: (tap, c) of the launch's source -> tap * ci_full + c_off + c
-#pragma unroll
-  for (int jn = 0; jn < TN; ++jn) {
-    const int jj = j0 + wn + jn * 32 + lr;
-    const int tap = fast_div(jj, a.ci, a.inv_ci);
-    col[jn] = jj < a.J ? tap * a.ci_full + a.c_off + (jj - tap * a.ci) : -1;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int co = co0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-      if (co >= a.co) continue;
-#pragma unroll
-      for (int jn = 0; jn < TN; ++jn) {
-        if (col[jn] >= 0) {
-          float* dst = a.dw + (size_t)co * a.J_ld + col[jn];
-          if (a.use_atomic) atomicAdd(dst, acc[i][jn][v]);
-          else *dst = acc[i][jn][v];
-        }
-      }
-    }
+  wgrad_store(a, acc, t.co0 + wm, t.j0 + wn, lr, lh);
 }
 
 // ---------------------------------------------------------------------------------------------------- bf16 storage
@@ -298,6 +360,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
   constexpr int A_ROWS = 256 / AQ, B_ROWS = 256 / BQ;
   constexpr int A_PASS = (WBKB + A_ROWS - 1) / A_ROWS, B_PASS = (WBKB + B_ROWS - 1) / B_ROWS;
   static_assert(WAVES_M * WAVES_N == 4, "4 waves");
+  static_assert(!ROWU || (WBKB % A_ROWS == 0 && WBKB % B_ROWS == 0), "row-uniform passes must tile the K-tile");
 
   __shared__ __attribute__((aligned(16))) unsigned short As[2][WBKB][LDA];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[2][WBKB][LDB];
@@ -310,44 +373,28 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
   // transposed-read roles inside the 16-lane group
   const int grp = lane >> 4, cb = 16 * (grp & 1), hk = grp >> 1, tq = (lane & 15) >> 2, tp = lane & 3;
 
-  const int ntj = (a.J + BNW - 1) / BNW;
   int tile_id = blockIdx.x, split_id = blockIdx.y;
   if (a.xcd_tiles > 0) {        // see WgradArgs::xcd_tiles
     const int L = blockIdx.x, xcd = L & 7, idx = L >> 3;
     split_id = xcd + 8 * (idx / a.xcd_tiles);
     tile_id = idx % a.xcd_tiles;
   }
-  const int co0 = (tile_id / ntj) * BMW;
-  const int j0 = (tile_id % ntj) * BNW;
-  const int kbeg = split_id * a.kchunk;
-  const int kend = min(a.M, kbeg + a.kchunk);
-  if (kbeg >= a.M) return;          // an empty split of a rounded-up split count (block-uniform, before any barrier)
+  const WgradTile t = wgrad_tile<BMW, BNW>(a, tile_id, split_id);
+  if (t.kbeg >= a.M) return;          // an empty split of a rounded-up split count (block-uniform, before any barrier)
 
   const int aq = tid % AQ, arow = tid / AQ;
-  const int a_co = co0 + aq * 8;
+  const int a_co = t.co0 + aq * 8;
   const bool a_ok = a_co < a.co;
   const int bq = tid % BQ, brow = tid / BQ;
-  const int j = j0 + bq * 8;
+  const int j = t.j0 + bq * 8;
   const bool b_ok = j < a.J;
-  int b_dy = 0, b_dx = 0, b_c = 0;
-  if (b_ok) {
-    const int tap = fast_div(j, a.ci, a.inv_ci);
-    b_c = j - tap * a.ci;
-    const int r = fast_div(tap, a.kw, a.inv_kw);
-    b_dy = r - a.pad;
-    b_dx = (tap - r * a.kw) - a.pad;
-  }
+  const WgradTap b = b_ok ? wgrad_tap(a, j) : WgradTap{0, 0, 0, 0};
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  wgrad_zero(acc);
 
   f32x4 ra[A_PASS], rb[B_PASS];
-  const int nkt = (kend - kbeg + WBKB - 1) / WBKB;
+  const int nkt = (t.kend - t.kbeg + WBKB - 1) / WBKB;
   // producer's BatchNorm + activation on the gathered operand (WgradArgs::in_scale): this thread's 8 channels are fixed
   const bool xform = a.in_scale != nullptr;
   const bool x_relu = a.in_act == UDASEG_ACT_LEAKY && a.in_slope == 0.f;
@@ -356,100 +403,50 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
   if (xform) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      x_sc[e] = b_ok ? a.in_scale[b_c + e] : 0.f;
-      x_sh[e] = b_ok ? a.in_shift[b_c + e] : 0.f;
+      x_sc[e] = b_ok ? a.in_scale[b.c + e] : 0.f;
+      x_sh[e] = b_ok ? a.in_shift[b.c + e] : 0.f;
     }
   }
 
-  // row-uniform gather (see conv_wgrad_kernel): a pass covers B_ROWS consecutive pixels of one image row
-  static_assert(!ROWU || (WBKB % A_ROWS == 0 && WBKB % B_ROWS == 0), "row-uniform passes must tile the K-tile");
-  unsigned u_ac[A_PASS], u_bc = 0;
-  int u_bdy = 0, u_bx = 0;
-  int s_ni[B_PASS], s_oy[B_PASS], s_ox[B_PASS];
-  unsigned s_dyoff = 0;
+  WgradRowGather<2, WBKB, A_PASS, A_ROWS, B_PASS, B_ROWS> g;
   __amdgpu_buffer_rsrc_t rsrc_x, rsrc_dy;
   if constexpr (ROWU) {
-    rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), 0, (int)a.dy_bytes, 0x00020000);
-#pragma unroll
-    for (int p = 0; p < A_PASS; ++p)
-      u_ac[p] = a_ok ? (unsigned)((arow + A_ROWS * p) * a.co + a_co) * 2u : 0x80000000u;
-    u_bdy = b_dy;
-    u_bx = brow * a.stride + b_dx;
-    // up-sampled source: the column part of (ix >> 1) splits into scalar + constant because a pass starts at an even ox;
-    // the row part (iy >> 1) depends on the parity of the scalar oy and is formed per load
-    u_bc = !b_ok ? 0x80000000u
-                 : a.up ? (unsigned)((u_bx >> 1) * a.ci + b_c) * 2u
-                        : (unsigned)((b_dy * a.wi + brow * a.stride + b_dx) * a.ci + b_c) * 2u;
-    s_dyoff = (unsigned)kbeg * (unsigned)a.co * 2u;
-#pragma unroll
-    for (int p = 0; p < B_PASS; ++p) {
-      const int m = kbeg + B_ROWS * p;
-      const int t1 = m / a.wo;
-      s_ox[p] = m - t1 * a.wo;
-      s_ni[p] = t1 / a.ho;
-      s_oy[p] = t1 - s_ni[p] * a.ho;
-    }
+    rsrc_x = wgrad_rsrc(a.x, a.x_bytes);
+    rsrc_dy = wgrad_rsrc(a.dy, a.dy_bytes);
+    g.init(a, t.kbeg, arow, a_co, a_ok, brow, b, b_ok);
   }
 
   auto load_tile = [&](int kt) {
     if constexpr (ROWU) {
 #pragma unroll
       for (int p = 0; p < A_PASS; ++p)
-        ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)(u_ac[p] + s_dyoff), 0, 0));
-      s_dyoff += (unsigned)(WBKB * 2) * (unsigned)a.co;
+        ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)g.dy_offset(p), 0, 0));
+      g.dy_advance(a);
 #pragma unroll
       for (int p = 0; p < B_PASS; ++p) {
-        const int oys = s_oy[p] * a.stride, oxs = s_ox[p] * a.stride;
-        const bool ok = (unsigned)(oys + u_bdy) < (unsigned)a.hi && (unsigned)(oxs + u_bx) < (unsigned)a.wi;
-        unsigned voff;
-        if (a.up) {   // uniform branch
-          const int w2 = a.wi >> 1;
-          const unsigned s_off = (unsigned)((s_ni[p] * (a.hi >> 1) * w2 + (oxs >> 1)) * a.ci) * 2u;
-          voff = u_bc + s_off + (unsigned)(((oys + u_bdy) >> 1) * w2 * a.ci) * 2u;
-        } else {
-          const unsigned s_off = (unsigned)(((s_ni[p] * a.hi + oys) * a.wi + oxs) * a.ci) * 2u;
-          voff = u_bc + s_off;
-        }
-        voff = ok ? voff : 0x80000000u;
-        x_ok = (x_ok & ~(1u << p)) | ((ok && b_ok ? 1u : 0u) << p);
+        bool inside;
+        const unsigned voff = g.x_offset(a, p, inside);
+        x_ok = (x_ok & ~(1u << p)) | ((inside && b_ok ? 1u : 0u) << p);
         rb[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)voff, 0, 0));
-        s_ox[p] += WBKB;
-        while (s_ox[p] >= a.wo) {
-          s_ox[p] -= a.wo;
-          if (++s_oy[p] == a.ho) {
-            s_oy[p] = 0;
-            ++s_ni[p];
-          }
-        }
+        g.x_advance(a, p);
       }
       return;
     }
-    const int mb = kbeg + kt * WBKB;
+    const int mb = t.kbeg + kt * WBKB;
 #pragma unroll
     for (int p = 0; p < A_PASS; ++p) {
       const int row = arow + A_ROWS * p, m = mb + row;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (a_ok && row < WBKB && m < kend) v = *reinterpret_cast<const f32x4*>(dyg + (size_t)m * a.co + a_co);
+      if (a_ok && row < WBKB && m < t.kend) v = *reinterpret_cast<const f32x4*>(dyg + (size_t)m * a.co + a_co);
       ra[p] = v;
     }
 #pragma unroll
     for (int p = 0; p < B_PASS; ++p) {
       const int row = brow + B_ROWS * p, m = mb + row;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      bool inside = false;
-      if (b_ok && row < WBKB && m < kend) {
-        const int t1 = fast_div(m, a.wo, a.inv_wo);
-        const int ox = m - t1 * a.wo;
-        const int ni = fast_div(t1, a.ho, a.inv_ho);
-        const int oy = t1 - ni * a.ho;
-        const int iy = oy * a.stride + b_dy, ix = ox * a.stride + b_dx;
-        if ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) {
-          const size_t pix = a.up ? (size_t)(ni * (a.hi >> 1) + (iy >> 1)) * (a.wi >> 1) + (ix >> 1) : (size_t)(ni * a.hi + iy) * a.wi + ix;
-          v = *reinterpret_cast<const f32x4*>(xg + pix * (size_t)a.ci + b_c);
-          inside = true;
-        }
-      }
+      size_t pix;
+      const bool inside = b_ok && row < WBKB && m < t.kend && wgrad_source(a, wgrad_pixel(a, m), b, pix);
+      if (inside) v = *reinterpret_cast<const f32x4*>(xg + pix * (size_t)a.ci + b.c);
       x_ok = (x_ok & ~(1u << p)) | ((inside ? 1u : 0u) << p);
       rb[p] = v;
     }
@@ -514,29 +511,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const WgradArgs a)
     __syncthreads();
     cur ^= 1;
   }
-
-  int col[TN];   // this lane's dW column per tile: (tap, c) of the launch's source -> tap * ci_full + c_off + c
-#pragma unroll
-  for (int jn = 0; jn < TN; ++jn) {
-    const int jj = j0 + wn + jn * 32 + lr;
-    const int tap = fast_div(jj, a.ci, a.inv_ci);
-    col[jn] = jj < a.J ? tap * a.ci_full + a.c_off + (jj - tap * a.ci) : -1;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int co = co0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-      if (co >= a.co) continue;
-#pragma unroll
-      for (int jn = 0; jn < TN; ++jn) {
-        if (col[jn] >= 0) {
-          float* dst = a.dw + (size_t)co * a.J_ld + col[jn];
-          if (a.use_atomic) atomicAdd(dst, acc[i][jn][v]);
-          else *dst = acc[i][jn][v];
-        }
-      }
-    }
+  wgrad_store(a, acc, t.co0 + wm, t.j0 + wn, lr, lh);
 }
 
 // ---------------------------------------------------------------------------------------------------- fp32 on the bf16 pipe
@@ -568,86 +543,37 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgradArgs a) {
   const int wm = (wave / WAVES_N) * WM, wn = (wave % WAVES_N) * WN;
   const int grp = lane >> 4, cb = 16 * (grp & 1), hk = grp >> 1, tq = (lane & 15) >> 2, tp = lane & 3;
 
-  const int ntj = (a.J + BNW - 1) / BNW;
-  const int co0 = (blockIdx.x / ntj) * BMW;
-  const int j0 = (blockIdx.x % ntj) * BNW;
-  const int kbeg = blockIdx.y * a.kchunk;
-  const int kend = min(a.M, kbeg + a.kchunk);
-  if (kbeg >= a.M) return;
+  const WgradTile t = wgrad_tile<BMW, BNW>(a, blockIdx.x, blockIdx.y);
+  if (t.kbeg >= a.M) return;
 
   const int aq = tid % AQ, arow = tid / AQ;
-  const int a_co = co0 + aq * 8;
+  const int a_co = t.co0 + aq * 8;
   const bool a_ok = a_co < a.co;
   const int bq = tid % BQ, brow = tid / BQ;
-  const int j = j0 + bq * 8;
+  const int j = t.j0 + bq * 8;
   const bool b_ok = j < a.J;
-  int b_dy = 0, b_dx = 0, b_c = 0;
-  if (b_ok) {
-    const int tap = fast_div(j, a.ci, a.inv_ci);
-    b_c = j - tap * a.ci;
-    const int r = fast_div(tap, a.kw, a.inv_kw);
-    b_dy = r - a.pad;
-    b_dx = (tap - r * a.kw) - a.pad;
-  }
+  const WgradTap b = b_ok ? wgrad_tap(a, j) : WgradTap{0, 0, 0, 0};
   // an 8-wide piece of the J axis may straddle two taps when ci is not a multiple of 8 (the stem's 4 padded channels): its two
   // 4-channel halves are gathered separately
   const bool b_two = (a.ci & 7) != 0;
-  int b2_dy = 0, b2_dx = 0, b2_c = 0;
   const bool b2_ok = b_two && (j + 4) < a.J;
-  if (b2_ok) {
-    const int tap = fast_div(j + 4, a.ci, a.inv_ci);
-    b2_c = (j + 4) - tap * a.ci;
-    const int r = fast_div(tap, a.kw, a.inv_kw);
-    b2_dy = r - a.pad;
-    b2_dx = (tap - r * a.kw) - a.pad;
-  }
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  const WgradTap b2 = b2_ok ? wgrad_tap(a, j + 4) : WgradTap{0, 0, 0, 0};
 
   // odd K-tiles (LDS buffer 1) carry -dy and accumulate into acc2, dW = acc - acc2: the bf16 MFMA adder truncates toward minus
   // infinity, and a bias over up to 2^19 pixels is what this sum must not have (conv_igemm.hip, X3)
-  f32x16 acc2[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc2[i][jn][v] = 0.f;
+  f32x16 acc[TM][TN], acc2[TM][TN];
+  wgrad_zero(acc);
+  wgrad_zero(acc2);
 
   u32x4 ra[A_PASS][2], rb[B_PASS][2];
-  const int nkt = (kend - kbeg + WBKX - 1) / WBKX;
+  const int nkt = (t.kend - t.kbeg + WBKX - 1) / WBKX;
 
-  unsigned u_ac[A_PASS], u_bc = 0;
-  int u_bdy = 0, u_bx = 0;
-  int s_ni[B_PASS], s_oy[B_PASS], s_ox[B_PASS];
-  unsigned s_dyoff = 0;
+  WgradRowGather<4, WBKX, A_PASS, A_ROWS, B_PASS, B_ROWS> g;
   __amdgpu_buffer_rsrc_t rsrc_x, rsrc_dy;
   if constexpr (ROWU) {
-    rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), 0, (int)a.dy_bytes, 0x00020000);
-#pragma unroll
-    for (int p = 0; p < A_PASS; ++p)
-      u_ac[p] = a_ok ? (unsigned)((arow + A_ROWS * p) * a.co + a_co) * 4u : 0x80000000u;
-    u_bdy = b_dy;
-    u_bx = brow * a.stride + b_dx;
-    u_bc = !b_ok ? 0x80000000u
-                 : a.up ? (unsigned)((u_bx >> 1) * a.ci + b_c) * 4u
-                        : (unsigned)((b_dy * a.wi + brow * a.stride + b_dx) * a.ci + b_c) * 4u;
-    s_dyoff = (unsigned)kbeg * (unsigned)a.co * 4u;
-#pragma unroll
-    for (int p = 0; p < B_PASS; ++p) {
-      const int m = kbeg + B_ROWS * p;
-      const int t1 = m / a.wo;
-      s_ox[p] = m - t1 * a.wo;
-      s_ni[p] = t1 / a.ho;
-      s_oy[p] = t1 - s_ni[p] * a.ho;
-    }
+    rsrc_x = wgrad_rsrc(a.x, a.x_bytes);
+    rsrc_dy = wgrad_rsrc(a.dy, a.dy_bytes);
+    g.init(a, t.kbeg, arow, a_co, a_ok, brow, b, b_ok);
   }
 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
@@ -655,43 +581,25 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgradArgs a) {
     if constexpr (ROWU) {      // host: ci a multiple of 8 (a piece never straddles taps)
 #pragma unroll
       for (int p = 0; p < A_PASS; ++p) {
-        ra[p][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)(u_ac[p] + s_dyoff), 0, 0);
-        ra[p][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)(u_ac[p] + s_dyoff), 16, 0);
+        ra[p][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)g.dy_offset(p), 0, 0);
+        ra[p][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_dy, (int)g.dy_offset(p), 16, 0);
       }
-      s_dyoff += (unsigned)(WBKX * 4) * (unsigned)a.co;
+      g.dy_advance(a);
 #pragma unroll
       for (int p = 0; p < B_PASS; ++p) {
-        const int oys = s_oy[p] * a.stride, oxs = s_ox[p] * a.stride;
-        const bool ok = (unsigned)(oys + u_bdy) < (unsigned)a.hi && (unsigned)(oxs + u_bx) < (unsigned)a.wi;
-        unsigned voff;
-        if (a.up) {   // uniform branch
-          const int w2 = a.wi >> 1;
-          const unsigned s_off = (unsigned)((s_ni[p] * (a.hi >> 1) * w2 + (oxs >> 1)) * a.ci) * 4u;
-          voff = u_bc + s_off + (unsigned)(((oys + u_bdy) >> 1) * w2 * a.ci) * 4u;
-        } else {
-          const unsigned s_off = (unsigned)(((s_ni[p] * a.hi + oys) * a.wi + oxs) * a.ci) * 4u;
-          voff = u_bc + s_off;
-        }
-        voff = ok ? voff : 0x80000000u;
+        const unsigned voff = g.x_offset(a, p);
         rb[p][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)voff, 0, 0);
         rb[p][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, (int)voff, 16, 0);
-        s_ox[p] += WBKX;
-        while (s_ox[p] >= a.wo) {
-          s_ox[p] -= a.wo;
-          if (++s_oy[p] == a.ho) {
-            s_oy[p] = 0;
-            ++s_ni[p];
-          }
-        }
+        g.x_advance(a, p);
       }
       return;
     }
-    const int mb = kbeg + kt * WBKX;
+    const int mb = t.kbeg + kt * WBKX;
 #pragma unroll
     for (int p = 0; p < A_PASS; ++p) {
       const int row = arow + A_ROWS * p, m = mb + row;
       u32x4 v0 = zero4, v1 = zero4;
-      if (a_ok && row < WBKX && m < kend) {
+      if (a_ok && row < WBKX && m < t.kend) {
         const u32x4* src = reinterpret_cast<const u32x4*>(dyg + (size_t)m * a.co + a_co);
         v0 = src[0];
         if (a_co + 4 < a.co) v1 = src[1];
@@ -703,27 +611,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgradArgs a) {
     for (int p = 0; p < B_PASS; ++p) {
       const int row = brow + B_ROWS * p, m = mb + row;
       u32x4 v0 = zero4, v1 = zero4;
-      if (b_ok && row < WBKX && m < kend) {
-        const int t1 = fast_div(m, a.wo, a.inv_wo);
-        const int ox = m - t1 * a.wo;
-        const int ni = fast_div(t1, a.ho, a.inv_ho);
-        const int oy = t1 - ni * a.ho;
-        {
-          const int iy = oy * a.stride + b_dy, ix = ox * a.stride + b_dx;
-          if ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) {
-            const size_t pix = a.up ? (size_t)(ni * (a.hi >> 1) + (iy >> 1)) * (a.wi >> 1) + (ix >> 1) : (size_t)(ni * a.hi + iy) * a.wi + ix;
-            const u32x4* src = reinterpret_cast<const u32x4*>(xg + pix * (size_t)a.ci + b_c);
-            v0 = src[0];
-            if (!b_two && j + 4 < a.J) v1 = src[1];
-          }
+      if (b_ok && row < WBKX && m < t.kend) {
+        const WgradPixel o = wgrad_pixel(a, m);
+        size_t pix;
+        if (wgrad_source(a, o, b, pix)) {
+          const u32x4* src = reinterpret_cast<const u32x4*>(xg + pix * (size_t)a.ci + b.c);
+          v0 = src[0];
+          if (!b_two && j + 4 < a.J) v1 = src[1];
         }
-        if (b2_ok) {
-          const int iy = oy * a.stride + b2_dy, ix = ox * a.stride + b2_dx;
-          if ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) {
-            const size_t pix = a.up ? (size_t)(ni * (a.hi >> 1) + (iy >> 1)) * (a.wi >> 1) + (ix >> 1) : (size_t)(ni * a.hi + iy) * a.wi + ix;
-            v1 = *reinterpret_cast<const u32x4*>(xg + pix * (size_t)a.ci + b2_c);
-          }
-        }
+        if (b2_ok && wgrad_source(a, o, b2, pix)) v1 = *reinterpret_cast<const u32x4*>(xg + pix * (size_t)a.ci + b2.c);
       }
       rb[p][0] = v0;
       rb[p][1] = v1;
@@ -802,101 +698,40 @@ __global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(const WgradArgs a) {
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int jn = 0; jn < TN; ++jn) acc[i][jn] -= acc2[i][jn];
-  int col[TN];
-#pragma unroll
-  for (int jn = 0; jn < TN; ++jn) {
-    const int jj = j0 + wn + jn * 32 + lr;
-    const int tap = fast_div(jj, a.ci, a.inv_ci);
-    col[jn] = jj < a.J ? tap * a.ci_full + a.c_off + (jj - tap * a.ci) : -1;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int co = co0 + wm + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
-      if (co >= a.co) continue;
-#pragma unroll
-      for (int jn = 0; jn < TN; ++jn) {
-        if (col[jn] >= 0) {
-          float* dst = a.dw + (size_t)co * a.J_ld + col[jn];
-          if (a.use_atomic) atomicAdd(dst, acc[i][jn][v]);
-          else *dst = acc[i][jn][v];
-        }
-      }
-    }
+  wgrad_store(a, acc, t.co0 + wm, t.j0 + wn, lr, lh);
 }
 
-// blocks of an X3 launch: the MFMA phase of a split is ~2.5x shorter than on the fp32 pipe, the fp32 atomics of the partial tiles
-// are not -- fewer, longer splits than launch_wgrad's 3072 (UDASEG_WGRAD_X3_BLOCKS; profiles/r04_igemm_x3.txt: 512 / 1024 / 2048 / 3072 blocks gave the same step)
-template <int BMW, int BNW, int WAVES_M, int WAVES_N>
-static int launch_wgrad_x3(WgradArgs a, int accumulate, hipStream_t s) {
-  const int tiles = cdiv(a.co, BMW) * cdiv(a.J, BNW);
-  int target = opt_get(UDASEG_OPT_WGRAD_X3_BLOCKS);
-  if (target < 64) target = 1024;
+// ---------------------------------------------------------------------------------------------------- host: plan and launch
+enum class WgradPipe { F32, BF16, X3 };   // conv_wgrad_kernel, conv_wgrad_bf16_kernel, conv_wgrad_x3_kernel
+
+// Split-K plan: enough splits for `target` blocks over `tiles` tiles, at least 256 pixels per split, whole K-tiles per split.
+// round8 (bf16): the XCD-aware block order (WgradArgs::xcd_tiles) needs a multiple of 8 splits.
+struct WgradPlan { int splits, kchunk; };
+
+static WgradPlan wgrad_plan(int M, int tiles, int target, int ktile, bool round8) {
   int splits = cdiv(target, tiles);
-  const int max_splits = cdiv(a.M, 256);
+  const int max_splits = cdiv(M, 256);
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;
-  if (splits > 65535) splits = 65535;
-  const int kchunk = cdiv(cdiv(a.M, splits), WBKX) * WBKX;
-  splits = cdiv(a.M, kchunk);
-  a.kchunk = kchunk;
-  a.use_atomic = (splits > 1 || accumulate) ? 1 : 0;
-  if (a.use_atomic && !accumulate) {
-    if (a.J != a.J_ld) {
-      set_error("conv2d_wgrad_part: a channel slice of dW must be accumulated onto a caller-zeroed gradient");
-      return UDASEG_E_BADARG;
-    }
-    hipError_t e = hipMemsetAsync(a.dw, 0, (size_t)a.co * a.J * sizeof(float), s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(dw)");
-  }
-  dim3 grid((unsigned)tiles, (unsigned)splits), block(256);
-  a.xcd_tiles = a.xcd_splits = 0;
-  constexpr int b_rows = 256 / (BNW / 8);
-  const long long xb = (long long)a.M / (a.ho * a.wo) * (a.up ? (a.hi >> 1) * (a.wi >> 1) : a.hi * a.wi) * a.ci * 4,
-                  dyb = (long long)a.M * a.co * 4;
-  a.row_uniform = !opt_get(UDASEG_OPT_WGRAD_GENERIC) && a.wo % b_rows == 0 && a.ci % 8 == 0 && a.co % 8 == 0 &&
-                  xb <= (1LL << 30) && dyb <= (1LL << 30);
-  a.x_bytes = (unsigned)xb;
-  a.dy_bytes = (unsigned)dyb;
-  static KernelRec rec[2] = {{nullptr, "conv_wgrad_x3_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
-                             {nullptr, "conv_wgrad_x3_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}};
-  return launch_kernel(rec[a.row_uniform], a.row_uniform ? conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, true>
-                                                         : conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, false>,
-                       grid, block, 0, 0, s, 2.0 * (double)a.M * a.co * a.J, "conv_wgrad_x3 launch", a);
-}
-
-template <int BMW, int BNW, int WAVES_M, int WAVES_N>
-static int launch_wgrad(WgradArgs a, int accumulate, hipStream_t s, bool bf16 = false) {
-  const int tiles = cdiv(a.co, BMW) * cdiv(a.J, BNW);
-  // enough blocks for ~4 per CU, at least 256 pixels per split (UDASEG_WGRAD_BLOCKS: tuning aid)
-  int target = opt_get(UDASEG_OPT_WGRAD_BLOCKS);      // 0: the defaults below
-  const bool target_from_env = target >= 64;
-  if (!target_from_env) target = 3072;  // measured sweep 512..8192: 68.7 / 79.4 / 80.3 / 85.9 / 87.0 / 89.1 / 88.8 / 88.1 TFLOP/s
-  // bf16: the MFMA phase of a split is 16x shorter, so the fp32 atomics of the partial tiles (blocks x 16 KB at ~1.3 TB/s)
-  // are the launch: 512 blocks measured best (r18 8x512^2 step: 256 / 512 / 768 / 1024 / 2048 / 3072 blocks ->
-  // 1285 / 1398 / 1366 / 1353 / 1326 / 1285 images/s; r50 768^2: 337 / 344 / 338 / 335 / 336 / 332)
-  // (the <= 32-output-channel full-resolution layers -- 32 x 128 tile, 16 KB of partials per block, >= 1 M pixels -- are the
-  // exception: latency-bound at two blocks per CU, 2048 blocks: 185 -> 152, 138 -> 120, 128 -> 109 us at 512^2)
-  const int bf16_target = (BMW == 32 && a.M >= (1 << 20)) ? 2048 : 512;
-  int splits = cdiv(bf16 && !target_from_env ? bf16_target : target, tiles);
-  const int max_splits = cdiv(a.M, 256);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  const int ktile = bf16 ? WBKB : WBK;
-  int kchunk = cdiv(cdiv(a.M, splits), ktile) * ktile;
-  splits = cdiv(a.M, kchunk);
-  if (bf16 && splits >= 16 && tiles > 1 && splits % 8 != 0) {
-    // the XCD-aware block order (WgradArgs::xcd_tiles) needs a multiple of 8 splits: take the nearest one that still tiles M
-    // (a split may come out empty when M / ktile is not divisible: its block returns at once)
+  if (splits > 65535) splits = 65535;       // gridDim.y
+  int kchunk = cdiv(cdiv(M, splits), ktile) * ktile;
+  splits = cdiv(M, kchunk);
+  if (round8 && splits >= 16 && tiles > 1 && splits % 8 != 0) {
+    // take the nearest multiple of 8 that still tiles M (a split may come out empty when M / ktile is not divisible: its block
+    // returns at once)
     const int s8 = ((splits + 4) / 8) * 8;
-    const int kc = cdiv(cdiv(a.M, s8), ktile) * ktile;
-    if ((long long)kc * (s8 - 8) < a.M) {     // at most the last few splits are empty
+    const int kc = cdiv(cdiv(M, s8), ktile) * ktile;
+    if ((long long)kc * (s8 - 8) < M) {     // at most the last few splits are empty
       kchunk = kc;
       splits = s8;
     }
   }
-  a.kchunk = kchunk;
+  return {splits, kchunk};
+}
+
+// A single split that does not accumulate stores its tile; otherwise the blocks add atomically, onto zeros unless the caller's dW is
+// accumulated onto.
+static int wgrad_prepare_dw(WgradArgs& a, int splits, int accumulate, hipStream_t s) {
   a.use_atomic = (splits > 1 || accumulate) ? 1 : 0;
   if (a.use_atomic && !accumulate) {
     if (a.J != a.J_ld) {
@@ -906,32 +741,71 @@ static int launch_wgrad(WgradArgs a, int accumulate, hipStream_t s, bool bf16 = 
     hipError_t e = hipMemsetAsync(a.dw, 0, (size_t)a.co * a.J * sizeof(float), s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(dw)");
   }
-  dim3 grid((unsigned)tiles, (unsigned)splits), block(256);
-  a.xcd_tiles = a.xcd_splits = 0;
-  if (bf16 && splits % 8 == 0 && tiles > 1) {
-    if (!opt_get(UDASEG_OPT_WGRAD_NO_XCD)) {      // 1: A/B
-      a.xcd_tiles = tiles;
-      a.xcd_splits = splits;
-      grid = dim3((unsigned)(tiles * splits), 1u);
-    }
-  }
-  // one record per rocprofv3 symbol: [bf16][row_uniform]
-  static KernelRec rec[2][2] = {{{nullptr, "conv_wgrad_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
-                                 {nullptr, "conv_wgrad_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}},
-                                {{nullptr, "conv_wgrad_bf16_kernel<%d, %d, %d, %d, false>", BMW, BNW, WAVES_M, WAVES_N},
-                                 {nullptr, "conv_wgrad_bf16_kernel<%d, %d, %d, %d, true>", BMW, BNW, WAVES_M, WAVES_N}}};
-  const int es = bf16 ? 2 : 4;                        // bytes per element; a thread stages 16 bytes of a dy row
-  const int b_rows = 256 / (BNW / (16 / es));
+  return UDASEG_OK;
+}
+
+// The row-uniform gather applies when the output width is a multiple of the b_rows rows one x load pass covers and both tensors fit
+// a buffer resource's 32-bit byte offsets (es: bytes per element); UDASEG_OPT_WGRAD_GENERIC = 1: the generic gather everywhere.
+static void wgrad_row_uniform(WgradArgs& a, int es, int b_rows) {
   const long long xb = (long long)a.M / (a.ho * a.wo) * (a.up ? (a.hi >> 1) * (a.wi >> 1) : a.hi * a.wi) * a.ci * es,
                   dyb = (long long)a.M * a.co * es;
   a.row_uniform = !opt_get(UDASEG_OPT_WGRAD_GENERIC) && a.wo % b_rows == 0 && xb <= (1LL << 30) && dyb <= (1LL << 30);
   a.x_bytes = (unsigned)xb;
   a.dy_bytes = (unsigned)dyb;
-  void (*kern)(WgradArgs);
-  if (bf16) kern = a.row_uniform ? conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
-  else kern = a.row_uniform ? conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
-  return launch_kernel(rec[bf16][a.row_uniform], kern, grid, block, 0, 0, s, 2.0 * (double)a.M * a.co * a.J, "conv_wgrad launch", a);
 }
+
+template <WgradPipe PIPE, int BMW, int BNW, int WAVES_M, int WAVES_N>
+static int launch_wgrad(WgradArgs a, int accumulate, hipStream_t s) {
+  constexpr bool bf16 = PIPE == WgradPipe::BF16, x3 = PIPE == WgradPipe::X3;
+  constexpr int ktile = bf16 ? WBKB : x3 ? WBKX : WBK;
+  constexpr int es = bf16 ? 2 : 4;                       // bytes per element
+  constexpr int vec = PIPE == WgradPipe::F32 ? 4 : 8;    // channels a thread stages per row: 16 bytes; X3: two 16-byte loads
+  const int tiles = cdiv(a.co, BMW) * cdiv(a.J, BNW);
+  int target;
+  if constexpr (x3) {
+    // the MFMA phase of a split is ~2.5x shorter than on the fp32 pipe, the fp32 atomics of the partial tiles are not -- fewer, longer
+    // splits than the fp32 pipe's 3072 (UDASEG_WGRAD_X3_BLOCKS; profiles/r04_igemm_x3.txt: 512 / 1024 / 2048 / 3072 blocks gave the same step)
+    target = opt_get(UDASEG_OPT_WGRAD_X3_BLOCKS);
+    if (target < 64) target = 1024;
+  } else {
+    // enough blocks for ~4 per CU, at least 256 pixels per split (UDASEG_WGRAD_BLOCKS: tuning aid; 0: the defaults below)
+    target = opt_get(UDASEG_OPT_WGRAD_BLOCKS);
+    if (target < 64) {
+      target = 3072;  // measured sweep 512..8192: 68.7 / 79.4 / 80.3 / 85.9 / 87.0 / 89.1 / 88.8 / 88.1 TFLOP/s
+      // bf16: the MFMA phase of a split is 16x shorter, so the fp32 atomics of the partial tiles (blocks x 16 KB at ~1.3 TB/s)
+      // are the launch: 512 blocks measured best (r18 8x512^2 step: 256 / 512 / 768 / 1024 / 2048 / 3072 blocks ->
+      // 1285 / 1398 / 1366 / 1353 / 1326 / 1285 images/s; r50 768^2: 337 / 344 / 338 / 335 / 336 / 332)
+      // (the <= 32-output-channel full-resolution layers -- 32 x 128 tile, 16 KB of partials per block, >= 1 M pixels -- are the
+      // exception: latency-bound at two blocks per CU, 2048 blocks: 185 -> 152, 138 -> 120, 128 -> 109 us at 512^2)
+      if constexpr (bf16) target = (BMW == 32 && a.M >= (1 << 20)) ? 2048 : 512;
+    }
+  }
+  const WgradPlan plan = wgrad_plan(a.M, tiles, target, ktile, bf16);
+  a.kchunk = plan.kchunk;
+  const int rc = wgrad_prepare_dw(a, plan.splits, accumulate, s);
+  if (rc != UDASEG_OK) return rc;
+  dim3 grid((unsigned)tiles, (unsigned)plan.splits), block(256);
+  a.xcd_tiles = a.xcd_splits = 0;
+  if (bf16 && plan.splits % 8 == 0 && tiles > 1 && !opt_get(UDASEG_OPT_WGRAD_NO_XCD)) {      // WGRAD_NO_XCD = 1: A/B
+    a.xcd_tiles = tiles;
+    a.xcd_splits = plan.splits;
+    grid = dim3((unsigned)(tiles * plan.splits), 1u);
+  }
+  wgrad_row_uniform(a, es, 256 / (BNW / vec));
+  if (x3 && (a.ci % 8 != 0 || a.co % 8 != 0)) a.row_uniform = 0;      // an 8-wide piece that straddles two taps: generic gather only
+  // one record per rocprofv3 symbol: [row_uniform]
+  static KernelRec rec[2] = {
+      {nullptr, bf16 ? "conv_wgrad_bf16_kernel<%d, %d, %d, %d, false>" : x3 ? "conv_wgrad_x3_kernel<%d, %d, %d, %d, false>" : "conv_wgrad_kernel<%d, %d, %d, %d, false>",
+       BMW, BNW, WAVES_M, WAVES_N},
+      {nullptr, bf16 ? "conv_wgrad_bf16_kernel<%d, %d, %d, %d, true>" : x3 ? "conv_wgrad_x3_kernel<%d, %d, %d, %d, true>" : "conv_wgrad_kernel<%d, %d, %d, %d, true>",
+       BMW, BNW, WAVES_M, WAVES_N}};
+  void (*kern)(WgradArgs);
+  if constexpr (bf16) kern = a.row_uniform ? conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_bf16_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
+  else if constexpr (x3) kern = a.row_uniform ? conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_x3_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
+  else kern = a.row_uniform ? conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, true> : conv_wgrad_kernel<BMW, BNW, WAVES_M, WAVES_N, false>;
+  return launch_kernel(rec[a.row_uniform], kern, grid, block, 0, 0, s, 2.0 * (double)a.M * a.co * a.J, x3 ? "conv_wgrad_x3 launch" : "conv_wgrad launch", a);
+}
+
 
 
 // The halo-resident weight gradients (bf16 and the fp32 three-term split) live in conv_wgrad_halo2.hip since round 4; round 3's
@@ -992,9 +866,9 @@ static int conv2d_wgrad_impl(const udaseg_conv_desc* d, const void* x, int src_c
     // the gathered bytes per FLOP).  Same box, single-stream ms per step, 128 x 64 / 64 x 64: cfg 5 (r50's 1x1 and strided layers)
     // 1.94 / 2.17, cfg 3 (the discriminator's 4x4 / stride 2 layers) 1.06 / 1.24 -- cfg 3 1028 against 982 images/s
     // (profiles/r04_wgrad_tile.txt)
-    rc = d->co >= 128 ? launch_wgrad<128, 64, 2, 2>(a, accumulate, st, true)
-       : d->co > 32   ? launch_wgrad<64, 64, 2, 2>(a, accumulate, st, true)
-                      : launch_wgrad<32, 128, 1, 4>(a, accumulate, st, true);
+    rc = d->co >= 128 ? launch_wgrad<WgradPipe::BF16, 128, 64, 2, 2>(a, accumulate, st)
+       : d->co > 32   ? launch_wgrad<WgradPipe::BF16, 64, 64, 2, 2>(a, accumulate, st)
+                      : launch_wgrad<WgradPipe::BF16, 32, 128, 1, 4>(a, accumulate, st);
   else if (whole && d->kh == d->kw &&
            small_wgrad_applicable(d->kh, d->stride, d->pad, d->ci, d->co, d->n * cdiv(d->hi, 16) * cdiv(d->wi, 16)))
     rc = launch_small_wgrad(static_cast<const float*>(x), static_cast<const float*>(dy), dw, d->n, d->hi, d->wi, d->ci, d->co,
@@ -1003,9 +877,9 @@ static int conv2d_wgrad_impl(const udaseg_conv_desc* d, const void* x, int src_c
   // X3: per call, us, fp32 pipe / X3 (bench.py --layer-table, cfg 2, profiles/r04_igemm_x3.txt): 3x3 / stride 2 74 / 69, 69 / 58, 66 / 72;
   // 1x1 / stride 2 unchanged; the 7x7 stem (4 padded channels: two gathers per 8-wide piece, generic loop) 174 / 215 -- it stays on the
   // fp32 pipe.  What the split buys here is mostly the error (sign-alternated accumulators: l2 2.9e-7 against 3.5e-7 of the fp32 pipe)
-  else if (d->co > 32 && src_c % 8 == 0 && d->co % 8 == 0 && wgrad_x3_on()) rc = launch_wgrad_x3<64, 64, 2, 2>(a, accumulate, st);
-  else if (d->co > 32) rc = launch_wgrad<64, 64, 2, 2>(a, accumulate, st);
-  else rc = launch_wgrad<32, 128, 1, 4>(a, accumulate, st);
+  else if (d->co > 32 && src_c % 8 == 0 && d->co % 8 == 0 && wgrad_x3_on()) rc = launch_wgrad<WgradPipe::X3, 64, 64, 2, 2>(a, accumulate, st);
+  else if (d->co > 32) rc = launch_wgrad<WgradPipe::F32, 64, 64, 2, 2>(a, accumulate, st);
+  else rc = launch_wgrad<WgradPipe::F32, 32, 128, 1, 4>(a, accumulate, st);
   prof_end(1, st, udaseg_conv_flops(&dp), 2, &dp);
   return rc;
 }
