@@ -751,6 +751,39 @@ int udaseg_boundary_erode(const void* labels, int labels_i64, int n, int h, int 
 int udaseg_boundary_stats(const void* pred, const void* truth, int labels_i64, int n, int h, int w, int radius, int classes,
                           int has_ignore, int ignore_index, int64_t* stats, int64_t* trimap, void* stream);
 
+/* ---- connected components of label maps: region ids and areas, a sieve, per-class region statistics (csrc/regions.hip;
+ * tests/_regions_ref.py is the numpy mirror, every product is integers and is compared for equality).  A label map is n images
+ * [h][w], contiguous: uint8 (labels_i64 == 0) or int64 (== 1; 8-byte aligned; a value outside [0, 255] reads as 255).  With
+ * has_ignore == 1 the pixels whose value (after that rule) equals ignore_index, in [0, 255], are VOID; with has_ignore == 0 no
+ * pixel is void and ignore_index is only range-checked (the conventions of udaseg_boundary_*).
+ *   adjacent   two pixels of the SAME image are adjacent if neither is void, they carry the same label, and they are 4-neighbours
+ *              (connectivity == 4) or 8-neighbours (connectivity == 8).  Images never see each other; the frame's edge connects
+ *              nothing.
+ *   component  a class of the transitive closure of "adjacent".
+ *   id(p)      the smallest y * w + x over the pixels of p's component: its first pixel in raster order.  -1 for a void pixel.
+ *              This makes the result unique: the same on every run, whatever order the atomics land in.
+ *   area(p)    the number of pixels of p's component; 0 for a void pixel.
+ * Limits of every entry point, refused with a message before any launch: 0 < n <= 65535, h, w >= 1, h * w < 2^31, connectivity
+ * 4 or 8, ignore_index (and void_label) in [0, 255], 1 <= classes <= 255. */
+/* (tile height << 16) | tile width of the labelling: regions are first labelled per tile and then joined across the seams. */
+int udaseg_regions_tile(void);
+/* ids: int32 [n][h][w] = id(p).  area: int32 [n][h][w] = area(p), or NULL when only the ids are wanted.  The labelling itself
+ * needs one int32 [n][h][w] beside ids (the sizes of the tile-local components, then the ids of their roots): area serves as it;
+ * with area == NULL a stream-ordered allocation of that size is taken and released inside the call. */
+int udaseg_regions_label(const void* labels, int labels_i64, int n, int h, int w, int connectivity, int has_ignore,
+                         int ignore_index, int32_t* ids, int32_t* area, void* stream);
+/* ids, area: what udaseg_regions_label wrote for these labels with the same has_ignore / ignore_index.  min_area: DEVICE int32
+ * [256], a threshold per label, each >= 0.  out: uint8 [n][h][w] = void_label if p is not void and area(p) < min_area[L(p)],
+ * else L(p) (a void pixel keeps ignore_index).  counts (NULL or int64 [n][3], ACCUMULATES): counts[i] += {pixels of image i set
+ * to void_label, components removed, components kept}; a component is counted at its root pixel, where ids[p] == y * w + x. */
+int udaseg_regions_sieve(const void* labels, int labels_i64, const int32_t* ids, const int32_t* area, int n, int h, int w,
+                         int has_ignore, int ignore_index, const int32_t* min_area, int void_label, uint8_t* out, int64_t* counts,
+                         void* stream);
+/* stats (int64 [classes][34], ACCUMULATES): per class c < classes {components, pixels, hist[32]}, hist[floor(log2(area))] += 1
+ * per component of label c, each counted at its root pixel.  A label >= classes that is not void counts nowhere. */
+int udaseg_regions_stats(const void* labels, int labels_i64, const int32_t* ids, const int32_t* area, int n, int h, int w,
+                         int classes, int has_ignore, int ignore_index, int64_t* stats, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

@@ -149,6 +149,10 @@ SIGNATURES = {
     "udaseg_boundary_lookup": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_boundary_erode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_boundary_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_regions_tile": (_I, []),
+    "udaseg_regions_label": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_regions_sieve": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "udaseg_regions_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

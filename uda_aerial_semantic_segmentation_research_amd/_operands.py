@@ -415,6 +415,15 @@ OPERANDS = {
     "udaseg_boundary_stats": [T("pred", _LAB, "n*h*w"), T("truth", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"),
                               I("radius"), I("classes"), I("has_ignore"), I("ignore_index"), T("stats", i64, "classes*3"),
                               T("trimap", i64, 2), S],
+    # ---- connected components (ids and area: int32 per pixel; min_area: one threshold per label value)
+    "udaseg_regions_tile": [],
+    "udaseg_regions_label": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("connectivity"), I("has_ignore"),
+                             I("ignore_index"), T("ids", i32, "n*h*w"), T("area", i32, "n*h*w", True), S],
+    "udaseg_regions_sieve": [T("labels", _LAB, "n*h*w"), I("labels_i64"), T("ids", i32, "n*h*w"), T("area", i32, "n*h*w"), I("n"),
+                             I("h"), I("w"), I("has_ignore"), I("ignore_index"), T("min_area", i32, 256), I("void_label"),
+                             T("out", u8, "n*h*w"), T("counts", i64, "n*3", True), S],
+    "udaseg_regions_stats": [T("labels", _LAB, "n*h*w"), I("labels_i64"), T("ids", i32, "n*h*w"), T("area", i32, "n*h*w"), I("n"),
+                             I("h"), I("w"), I("classes"), I("has_ignore"), I("ignore_index"), T("stats", i64, "classes*34"), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

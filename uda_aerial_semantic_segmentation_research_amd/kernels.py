@@ -277,6 +277,38 @@ def boundary_stats(pred, truth, radius, classes, ignore_index, stats, trimap, st
     check(ops.udaseg_boundary_stats(pred, truth, i64, n, h, w, r, int(classes), has, ign, stats, trimap, st), "boundary_stats")
 
 
+# ---- connected components (regions.py; csrc/regions.hip).  labels: uint8 or int64 [n,h,w]; ignore_index: an int or None
+def regions_tile():
+    """(tile height, tile width) of the labelling: regions are labelled per tile, then joined across the seams."""
+    v = _lib.load().udaseg_regions_tile()
+    return v >> 16, v & 0xffff
+
+
+def regions_label(labels, connectivity, ignore_index, ids, area, st=None):
+    """ids [n,h,w] int32 = the first raster index of every pixel's component (-1: void); area [n,h,w] int32 or None = its size."""
+    n, h, w = labels.shape
+    check(ops.udaseg_regions_label(labels, int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(connectivity),
+                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), ids, area, st),
+          "regions_label")
+
+
+def regions_sieve(labels, ids, area, ignore_index, min_area, void_label, out, counts, st=None):
+    """out [n,h,w] uint8 = labels with void_label on the components smaller than min_area[label] (int32 [256] on the device);
+    counts [n,3] int64 or None += pixels voided, components removed, components kept."""
+    n, h, w = labels.shape
+    check(ops.udaseg_regions_sieve(labels, int(getattr(labels, "dtype", None) == torch.int64), ids, area, n, h, w,
+                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), min_area,
+                                   int(void_label), out, counts, st), "regions_sieve")
+
+
+def regions_stats(labels, ids, area, classes, ignore_index, stats, st=None):
+    """stats [classes,34] int64 += components, pixels and the log2 area histogram [32] of every class."""
+    n, h, w = labels.shape
+    check(ops.udaseg_regions_stats(labels, int(getattr(labels, "dtype", None) == torch.int64), ids, area, n, h, w, int(classes),
+                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), stats, st),
+          "regions_stats")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,

@@ -1,0 +1,248 @@
+"""Connected components of label maps on the device: region ids and areas, a sieve for small regions, per-class region statistics.
+
+One primitive serves all of it (``csrc/regions.hip``; ``include/udaseg.h`` states the rule in full and ``tests/_regions_ref.py``
+is its numpy mirror, compared for equality):
+
+    label ``L``        uint8 or int64 ``[N,H,W]`` (``[H,W]`` is taken as ``N = 1``); an int64 value outside ``[0, 255]`` reads as 255.
+    void               with ``ignore_index`` (``0..255``) the pixels equal to it; with ``ignore_index=None`` no pixel is void.
+    adjacent           two pixels of one image, neither void, with the same label, that are 4-neighbours (``connectivity=4``) or
+                       8-neighbours (``connectivity=8``).  Images never see each other; the frame's edge connects nothing.
+    component          a class of the transitive closure of "adjacent".
+    ``id``             the smallest ``y * W + x`` over the component's pixels (its first pixel in raster order), -1 on a void pixel:
+                       unique, so the same bits on every run.
+    ``area``           the number of pixels of the component, 0 on a void pixel.
+
+What is made of it:
+
+    ``label``          the ids, and the areas if asked for.
+    ``sieve``          a mask with ``void`` on every component smaller than ``min_area`` of its class: a teacher's isolated islands
+                       of a wrong class are confident inside and survive ``boundary.erode``; this removes them (``SievedLoader``
+                       applies it to the batches of ``PseudoLabeler.loader`` / ``OnlineLabeler.loader`` /
+                       ``PrototypeLabeler.loader`` / ``mix.MixedLoader``, before or after ``boundary.ErodedLoader``).
+    ``RegionStats``    components, pixels, mean area and a log2 area histogram per class, accumulated on the device; ``evaluate``
+                       takes them of the predictions and of the truth and gives the fragmentation ratio per class.
+
+Removed regions are voided, not filled with the surrounding label.  CPU tensors raise: there is no CPU path in this build.
+Nothing is read back unless stated.
+"""
+import numpy as np
+import torch
+
+from . import kernels as K
+from .boundary import _check_label, _labels, _on, _out
+
+HIST_BINS = 32                # hist[floor(log2(area))]: area < 2^31
+STAT_COLS = 2 + HIST_BINS     # components, pixels, hist
+_SAME = object()              # sieve's ignore_index default: the void value itself
+
+
+# --------------------------------------------------------------------------------------------------------------- host side
+def _check_connectivity(who, connectivity):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity}")
+    return int(connectivity)
+
+
+def min_area_table(min_area, who="min_area_table"):
+    """The int32 ``[256]`` threshold table of ``sieve`` (numpy): one int for every class, or a sequence / tensor of per-class ints;
+    the classes beyond its length are kept (a threshold of 0).  A negative or non-integer threshold raises."""
+    if torch.is_tensor(min_area):
+        min_area = min_area.detach().cpu().numpy()
+    if isinstance(min_area, bool):
+        raise ValueError(f"{who}: min_area must be an int or a sequence of ints, got {min_area}")
+    if isinstance(min_area, (int, np.integer)):
+        arr = np.full(256, int(min_area), dtype=np.int64)
+    else:
+        a = np.asarray(min_area)
+        if a.ndim != 1 or a.shape[0] > 256 or a.dtype.kind not in "iu":
+            raise ValueError(f"{who}: min_area must be an int or at most 256 per-class ints, got {a.dtype} {a.shape}")
+        arr = np.zeros(256, dtype=np.int64)
+        arr[: a.shape[0]] = a
+    if (arr < 0).any() or (arr > np.iinfo(np.int32).max).any():
+        raise ValueError(f"{who}: every min_area must lie in [0, 2^31 - 1], got {arr.min()} .. {arr.max()}")
+    return arr.astype(np.int32)
+
+
+def summarize(stats):
+    """The measures of ``RegionStats.compute`` from its raw counters (numpy, host): ``stats`` int64 ``[C,34]`` (components, pixels,
+    then ``hist[32]`` with ``hist[k]`` the components of area ``2^k .. 2^(k+1) - 1``, per class).
+
+    ``components`` ``[C]``, ``pixels`` ``[C]``, ``mean_area`` ``[C]`` (NaN for a class without a component), ``hist`` ``[C,32]``."""
+    s = np.asarray(stats).astype(np.int64).reshape(-1, STAT_COLS)
+    comp, pix = s[:, 0], s[:, 1]
+    mean = np.divide(pix.astype(np.float64), comp.astype(np.float64), out=np.full(comp.shape, np.nan), where=comp > 0)
+    return {"components": comp.copy(), "pixels": pix.copy(), "mean_area": mean, "hist": s[:, 2:].copy(), "stats": s}
+
+
+def fragmentation(pred, truth):
+    """``components_pred / components_truth`` per class from two ``summarize`` dicts; NaN where the truth has no component."""
+    p = np.asarray(pred["components"], dtype=np.float64)
+    t = np.asarray(truth["components"], dtype=np.float64)
+    return np.divide(p, t, out=np.full(t.shape, np.nan), where=t > 0)
+
+
+# ------------------------------------------------------------------------------------------------------------- device side
+def label(labels, connectivity=4, ignore_index=None, return_area=False):
+    """int32 ids in the labels' shape (-1 on void pixels); with ``return_area`` the pair ``(ids, area)``, both int32."""
+    conn = _check_connectivity("label", connectivity)
+    ign = _check_label("label", "ignore_index", ignore_index)
+    lab, single = _labels("label", labels)
+    ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)     # the labelling's own scratch when no area is asked for
+    _on(lab.device, K.regions_label, lab, conn, ign, ids, area)
+    if single:
+        ids, area = ids[0], area[0]
+    return (ids, area) if return_area else ids
+
+
+_TABLES = {}
+
+
+def _device_table(who, min_area, dev):
+    arr = min_area_table(min_area, who)
+    key = (arr.tobytes(), str(dev))
+    t = _TABLES.get(key)
+    if t is None:                                                   # callers sieve every batch with the same few tables
+        if len(_TABLES) > 64:
+            _TABLES.clear()
+        t = _TABLES[key] = torch.from_numpy(arr.copy()).to(dev)
+    return t
+
+
+def sieve(labels, min_area, connectivity=4, void=255, ignore_index=_SAME, counts=None, out=None):
+    """The uint8 mask with ``void`` on every component of fewer than ``min_area`` pixels, the labels elsewhere.  ``min_area``: one
+    int, or per-class ints (classes beyond its length are kept).  ``ignore_index``: by default ``void`` itself, so that a void
+    region is no component and is never counted; ``None`` makes every value an ordinary label.  ``counts``: an int64 ``[N,3]``
+    device tensor that ACCUMULATES, per image, the pixels this call voided, the components it removed and those it kept."""
+    conn = _check_connectivity("sieve", connectivity)
+    v = _check_label("sieve", "void", void, none_ok=False)
+    ign = v if ignore_index is _SAME else _check_label("sieve", "ignore_index", ignore_index)
+    lab, single = _labels("sieve", labels)
+    tab = _device_table("sieve", min_area, lab.device)
+    n = lab.shape[0]
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 3)):
+        raise ValueError(f"sieve: counts must be an int64 [{n},3] tensor")
+    out = _out("sieve", "out", out, lab.shape, torch.uint8, lab.device)
+    ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    _on(lab.device, K.regions_label, lab, conn, ign, ids, area)
+    _on(lab.device, K.regions_sieve, lab, ids, area, ign, tab, v, out, counts)
+    return out[0] if single and out.dim() == 3 else out
+
+
+class SievedLoader:
+    """Wraps a loader of ``(frames_u8, masks_u8)`` batches -- ``PseudoLabeler.loader``, ``OnlineLabeler.loader``,
+    ``PrototypeLabeler.loader``, ``mix.MixedLoader``, or ``boundary.ErodedLoader`` over one of them -- and yields ``(frames,
+    sieve(masks, min_area, connectivity, void))``: the teacher's labels without their small islands.  The frames pass through;
+    masks still on the host are moved.  ``last_counts``: the int64 ``[N,3]`` device tensor of the latest batch (pixels voided,
+    components removed, components kept), for logging; nothing is read back here."""
+
+    def __init__(self, loader, min_area, connectivity=4, void=255):
+        self.loader = loader
+        self.min_area = min_area_table(min_area, "SievedLoader")
+        self.connectivity = _check_connectivity("SievedLoader", connectivity)
+        self.void = _check_label("SievedLoader", "void", void, none_ok=False)
+        self.last_counts = None
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for batch in self.loader:
+            if torch.is_tensor(batch) or len(batch) != 2:
+                raise ValueError("SievedLoader: a batch must be a (frames, masks) pair")
+            frames, masks = batch
+            if torch.is_tensor(masks) and masks.device.type != "cuda":
+                masks = masks.to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+            n = 1 if masks.dim() == 2 else int(masks.shape[0])
+            counts = torch.zeros((n, 3), dtype=torch.int64, device=masks.device)
+            out = sieve(masks, self.min_area, self.connectivity, self.void, counts=counts)
+            self.last_counts = counts
+            yield frames, out
+
+
+class RegionStats:
+    """Accumulates the per-class region counters of label maps on the device (``udaseg_regions_stats``).  ``update`` enqueues and
+    does not synchronise; ``compute`` does ONE read-back and returns ``summarize`` of the counters."""
+
+    def __init__(self, num_classes, connectivity=4, ignore_index=None, device=None):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= num_classes <= 255:
+            raise ValueError(f"RegionStats: num_classes must be in 1..255, got {num_classes}")
+        self.num_classes = int(num_classes)
+        self.connectivity = _check_connectivity("RegionStats", connectivity)
+        self.ignore_index = _check_label("RegionStats", "ignore_index", ignore_index)
+        self.device = torch.device(device) if device is not None else None
+        self.table = None              # int64 [C, 34] on the device
+
+    def _ensure(self, device):
+        if self.table is None:
+            if device.type != "cuda":
+                raise RuntimeError("RegionStats: tensors must live on the GPU (no CPU path in this build)")
+            self.device = device
+            self.table = torch.zeros((self.num_classes, STAT_COLS), dtype=torch.int64, device=device)
+        return self.table
+
+    def reset(self):
+        if self.table is not None:
+            self.table.zero_()
+
+    def update(self, pred):
+        """``pred``: a label map (uint8 or int64 ``[N,H,W]`` or ``[H,W]``), or scores ``[N,C,H,W]`` (logits or probabilities),
+        labelled by their first maximum (``udaseg_predict_finish``'s arg-max, at most 32 classes)."""
+        if not torch.is_tensor(pred):
+            raise ValueError("RegionStats.update: pred must be a tensor")
+        if pred.device.type != "cuda":
+            raise RuntimeError("RegionStats.update: pred must live on the GPU (no CPU path in this build)")
+        if pred.dim() == 4:
+            from .losses import _padded_nhwc
+            n, c, h, w = pred.shape
+            if c != self.num_classes:
+                raise ValueError(f"RegionStats.update: scores must be [N,{self.num_classes},H,W], got {tuple(pred.shape)}")
+            buf, ldc = _padded_nhwc(pred.detach())
+            lab = torch.empty((n, h, w), dtype=torch.int64, device=pred.device)
+            _on(pred.device, K.predict_finish, buf, None, n * h * w, c, ldc, lab)
+            pred = lab
+        lab, _ = _labels("RegionStats.update", pred, "pred")
+        tab = self._ensure(lab.device)
+        ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+        area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+        _on(lab.device, K.regions_label, lab, self.connectivity, self.ignore_index, ids, area)
+        _on(lab.device, K.regions_stats, lab, ids, area, self.num_classes, self.ignore_index, tab)
+        return self
+
+    def compute(self):
+        """``summarize`` of the accumulated counters: ``components`` / ``pixels`` / ``mean_area`` [C], ``hist`` [C,32] and the raw
+        ``stats`` [C,34].  ONE device->host transfer of ``34 C`` counters."""
+        return summarize(self._ensure(self.device or torch.device("cuda", torch.cuda.current_device())).cpu().numpy())
+
+
+def evaluate(model, loader, num_classes, device, connectivity=4, ignore_index=None):
+    """Eval-mode pass over ``loader`` (batches of ``(images, masks)``) in the shape of ``boundary.evaluate``: the region counters of
+    the predictions and of the truth accumulate on the device and are read back ONCE each at the end.  Returns ``{"pred", "truth"}``
+    (``RegionStats.compute()``'s dicts) and ``"ratio"``: ``components_pred / components_truth`` per class, NaN where the truth has
+    none -- the fragmentation of the prediction, which IoU does not show."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("evaluate: the model runs on the GPU (no CPU path in this build)")
+    conn = _check_connectivity("evaluate", connectivity)
+    was_training = model.training
+    model.eval()
+    sp = RegionStats(num_classes, conn, ignore_index, device)
+    st = RegionStats(num_classes, conn, ignore_index, device)
+    seen = False
+    with torch.no_grad():
+        for images, masks in loader:
+            images = images.to(device)
+            masks = masks.to(device)
+            if masks.dtype not in (torch.uint8, torch.int64):
+                masks = masks.long()
+            if masks.dim() == 4 and masks.shape[1] == 1:
+                masks = masks[:, 0]
+            sp.update(model(images))
+            st.update(masks)
+            seen = True
+    model.train(was_training)
+    if not seen:
+        raise ValueError("evaluate: the loader is empty")
+    pred, truth = sp.compute(), st.compute()
+    return {"pred": pred, "truth": truth, "ratio": fragmentation(pred, truth)}
