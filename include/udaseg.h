@@ -348,6 +348,39 @@ int udaseg_ce_ohem_fwd_bwd(const float* logits, const int64_t* target, const flo
                            float thresh, int64_t pixels, int classes, int ldc, int mean, const double* denom, double* partials,
                            float* loss, float* dlogits, float* colsum_partials, float* colsum, void* stream);
 
+/* ---- Lovasz-softmax loss (csrc/lovasz.hip; Berman, Rannen Triki, Blaschko 2018): the Jaccard surrogate on a grid of B error bins
+ * instead of a sort.  Integer atomics only and fixed-order float sums: the same bits on every run.
+ * logits: padded NHWC fp32 [pixels][ldc], ldc % 4 == 0, classes <= ldc <= 32, 0 < pixels < 2^31; target int64.
+ *   valid(p):      as udaseg_ce_opt_*; a valid pixel whose row (channels < classes) is not all finite is void too.  Void pixels
+ *                  are in no table and hold exact zeros in all ldc lanes of the gradient.
+ *   group:         the whole batch (images == 1) or one image (images == N; pixels % images == 0).
+ *   error:         p_c = expf(z_c - m) / S (m the row maximum, S as udaseg_conf_hist), e_c = [t == c] ? 1 - p_c : p_c
+ *   grid:          bins = B, a power of two in [64, 4096]; bin(e) = min(B - 1, floor(e B))
+ *   tables:        int32 [images][classes][2][B], ZEROED BY THE CALLER: row 0 the fg pixels (t == c) per bin, row 1 the bg pixels
+ *   coefficients:  bins walked from the top (largest error first); a0, b0 the fg / bg counts strictly above a bin, p, n its own,
+ *                  G the fg total of the (group, class):
+ *                    G > 0:   wf = (1 / (G + b0) + 1 / (G + b0 + n)) / 2,  wb = (G - a0 - p / 2) / ((G + b0) (G + b0 + n))
+ *                    G == 0:  wb = 1 / n in the highest non-empty bin, 0 elsewhere; wf = 0
+ *                  times the reduction factor 1 / (images * present classes of the group) (0 for an absent class), or
+ *                  1 / (images * classes) when all_classes != 0.  coef: fp32 [images][classes][2][B].
+ *   loss:          sum over the valid finite pixels and the classes of e_c * coef[group][c][fg ? 0 : 1][bin(e_c)]
+ *   gradient:      d_c = -coef (fg) / +coef (bg), taken as constants; dz_k = p_k (d_k - sum_c p_c d_c)
+ *   bound:         0 <= (the sort-based loss of the paper) - loss <= sum_c slack[c] <= 1 / B    */
+/* One pass over logits and targets: tables += the error histograms; counters[0..3] += {valid finite, void (== ignore_index),
+ * out-of-range, non-finite} pixels (int64, zeroed by the caller). */
+int udaseg_lovasz_hist(const float* logits, const int64_t* target, int64_t pixels, int classes, int ldc, int has_ignore,
+                       int64_t ignore_index, int images, int bins, int32_t* tables, int64_t* counters, void* stream);
+/* tables -> coef, present[images][classes] (int32 1 / 0: the class has a fg pixel in the group) and slack[classes] (f64, the
+ * reduction-weighted grid bound summed over the groups).  slack_parts: images * classes doubles of scratch. */
+int udaseg_lovasz_table(const int32_t* tables, int images, int classes, int bins, int all_classes, float* coef, int32_t* present,
+                        double* slack_parts, double* slack, void* stream);
+/* The second pass over the logits: *loss, dlogits for an upstream gradient of 1 (NULL: the loss alone), optional column sums.
+ * ce_weight != 0 adds ce_weight * mean over the valid finite pixels of -log p_t and its gradient, the count read from
+ * counters[0] of udaseg_lovasz_hist (no such pixel: NaN).  partials: udaseg_ce_partials() doubles. */
+int udaseg_lovasz_fwd_bwd(const float* logits, const int64_t* target, const float* coef, const int64_t* counters, int64_t pixels,
+                          int classes, int ldc, int has_ignore, int64_t ignore_index, int images, int bins, float ce_weight,
+                          double* partials, float* loss, float* dlogits, float* colsum_partials, float* colsum, void* stream);
+
 /* ---- the reference's other segmentation losses (src/models/losses.py), same logits layout as udaseg_ce_* (ldc <= 32) ----
  * udaseg_seg_partials(): doubles of scratch the *_fwd calls below need in `partials`. */
 int udaseg_seg_partials(void);

@@ -91,6 +91,9 @@ SIGNATURES = {
     "udaseg_kth_value": (_I, [_P, _F, _P, _P]),
     "udaseg_ohem_denom": (_I, [_P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P, _P]),
     "udaseg_ce_ohem_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _F, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "udaseg_lovasz_hist": (_I, [_P, _P, _L, _I, _I, _I, _L, _I, _I, _P, _P, _P]),
+    "udaseg_lovasz_table": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "udaseg_lovasz_fwd_bwd": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "udaseg_dice_fwd_ignore": (_I, [_P, _P, _I, _L, _I, _I, _F, _F, _I, _P, _P, _P, _L, _P]),
     "udaseg_dice_bwd_ignore": (_I, [_P, _P, _P, _P, _F, _I, _L, _I, _I, _P, _I, _L, _P]),
     "udaseg_focal_fwd_ignore": (_I, [_P, _P, _P, _F, _F, _L, _I, _I, _I, _P, _P, _I, _L, _P]),

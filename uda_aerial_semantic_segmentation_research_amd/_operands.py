@@ -341,6 +341,18 @@ OPERANDS = {
                                I("mean"), T("denom", f64, 1, True), T("partials", f64, "ce_partials()"), T("loss", f32, 1),
                                T("dlogits", f32, "pixels*ldc", True), T("colsum_partials", f32, "ce_partials()*ldc", True),
                                T("colsum", f32, "ldc", True), S],
+    # Lovasz-softmax: tables / coef = [images][classes][2][bins], counters = [valid finite, void, invalid, non-finite]
+    "udaseg_lovasz_hist": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
+                           I("has_ignore"), I("ignore_index"), I("images"), I("bins"), T("tables", i32, "images*classes*2*bins"),
+                           T("counters", i64, 4), S],
+    "udaseg_lovasz_table": [T("tables", i32, "images*classes*2*bins"), I("images"), I("classes"), I("bins"), I("all_classes"),
+                            T("coef", f32, "images*classes*2*bins"), T("present", i32, "images*classes"),
+                            T("slack_parts", f64, "images*classes"), T("slack", f64, "classes"), S],
+    "udaseg_lovasz_fwd_bwd": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), T("coef", f32, "images*classes*2*bins"),
+                              T("counters", i64, 4), I("pixels"), I("classes"), I("ldc"), I("has_ignore"), I("ignore_index"),
+                              I("images"), I("bins"), F("ce_weight"), T("partials", f64, "ce_partials()"), T("loss", f32, 1),
+                              T("dlogits", f32, "pixels*ldc", True), T("colsum_partials", f32, "ce_partials()*ldc", True),
+                              T("colsum", f32, "ldc", True), S],
     "udaseg_argmax_confusion": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"),
                                 T("confusion", i64, "classes*classes"), T("pred", i64, "pixels", True), S],
     "udaseg_score_hist": [T("logits", f32, "pixels*ldc"), T("target", i64, "pixels"), I("pixels"), I("classes"), I("ldc"), I("bins"),

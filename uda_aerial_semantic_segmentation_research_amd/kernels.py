@@ -926,6 +926,27 @@ def ce_ohem_fwd_bwd(logits_base, target, weight, conf, state, thresh, pixels, cl
                                      partials, loss, dlogits, colsum_partials, colsum, st), "ce_ohem_fwd_bwd")
 
 
+def lovasz_hist(logits_base, target, pixels, classes, ldc, ignore_index, images, bins, tables, counters, st=None):
+    """tables (int32 [images, classes, 2, bins], zeroed) += the fg / bg error histograms of the Lovasz-softmax loss,
+    counters (int64 [4], zeroed) += [valid finite, void, invalid, non-finite] pixels."""
+    check(ops.udaseg_lovasz_hist(logits_base, target, pixels, classes, ldc, *_ignore_args(ignore_index), images, bins, tables,
+                                 counters, st), "lovasz_hist")
+
+
+def lovasz_table(tables, images, classes, bins, all_classes, coef, present, slack_parts, slack, st=None):
+    """tables -> coef (fp32, the tables' shape; the reduction factor folded in), present (int32 [images, classes]) and
+    slack (f64 [classes], the bound on what the grid costs); slack_parts: f64 [images * classes] scratch."""
+    check(ops.udaseg_lovasz_table(tables, images, classes, bins, int(all_classes), coef, present, slack_parts, slack, st),
+          "lovasz_table")
+
+
+def lovasz_fwd_bwd(logits_base, target, coef, counters, pixels, classes, ldc, ignore_index, images, bins, ce_weight, partials, loss,
+                   dlogits=None, colsum_partials=None, colsum=None, st=None):
+    """Lovasz-softmax loss (+ ce_weight * cross entropy) and its gradient in ONE pass over the logits; dlogits None: loss only."""
+    check(ops.udaseg_lovasz_fwd_bwd(logits_base, target, coef, counters, pixels, classes, ldc, *_ignore_args(ignore_index), images,
+                                    bins, float(ce_weight), partials, loss, dlogits, colsum_partials, colsum, st), "lovasz_fwd_bwd")
+
+
 def seg_partials():
     return ops.udaseg_seg_partials()
 

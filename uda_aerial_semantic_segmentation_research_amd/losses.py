@@ -6,6 +6,8 @@
 * ``OhemCrossEntropyLoss``, ``TopKCrossEntropyLoss`` -- the cross entropy over the hard pixels only (online hard example mining /
   bootstrapped top-k; an extension), selected exactly on the device by a radix select (csrc/ohem.hip; INTEGRATION.md
   "Hard-pixel mining").
+* ``LovaszSoftmaxLoss`` -- the Lovasz-softmax Jaccard surrogate (Berman et al. 2018; an extension), on integer error histograms
+  instead of a sort, with a reported bound on what the grid costs (csrc/lovasz.hip; INTEGRATION.md "Lovasz-softmax").
 * ``AdversarialLoss``   -- mirror of reference ``src/models/losses.py:7-51`` (same constructor, same two methods).
   As upstream, BCE-*with-logits* is applied to whatever the discriminator returns (its sigmoid output).
 * ``DiceLoss``, ``WeightedSegmentationLoss``, ``ConsistencyLoss``, ``FineTuningLoss``, ``calculate_class_weights`` --
@@ -419,6 +421,130 @@ class TopKCrossEntropyLoss(OhemCrossEntropyLoss):
     def __init__(self, keep_fraction, weight=None, ignore_index=None, reduction='mean', keep_mask=False):
         super().__init__(keep_fraction=keep_fraction, weight=weight, ignore_index=ignore_index, reduction=reduction,
                          keep_mask=keep_mask)
+
+
+class _LovaszSoftmaxFunction(torch.autograd.Function):
+    """Lovasz-softmax on a grid of error bins (csrc/lovasz.hip).  One pass over the logits makes the per-class fg / bg error
+    histograms of every group; a tiny launch turns them into the Jaccard-gradient coefficient tables (reduction factor folded
+    in), the present-class map and the grid bound; then ``lovasz_fwd_bwd`` reads the logits once more and writes the loss and
+    the gradient with the head's bias gradient (column sums).  ``tables`` / ``counters`` come zeroed."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, images, bins, all_classes, ce_weight, tables, counters, present, slack):
+        n, c, h, w = logits.shape
+        buf, ldc = _padded_nhwc(logits.detach())
+        tgt = target.contiguous()
+        pixels = n * h * w
+        dev = logits.device
+        np_ = _load().udaseg_ce_partials()
+        K.lovasz_hist(buf, tgt, pixels, c, ldc, ignore_index, images, bins, tables, counters)
+        coef = torch.empty(tables.shape, device=dev, dtype=torch.float32)
+        K.lovasz_table(tables, images, c, bins, all_classes, coef, present, torch.empty(images * c, device=dev, dtype=torch.float64),
+                       slack)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        partials = torch.empty(np_, device=dev, dtype=torch.float64)
+        ctx.meta = (n, c, h, w, ldc, ignore_index, images, bins, ce_weight)
+        ctx.fused = None
+        ctx.save_for_backward(buf, tgt, coef, counters)
+        if ctx.needs_input_grad[0]:
+            dl, parts, colsum = _OhemCrossEntropyFunction._grad_buffers(n, h, w, ldc, np_, dev)
+            K.lovasz_fwd_bwd(buf, tgt, coef, counters, pixels, c, ldc, ignore_index, images, bins, ce_weight, partials, loss, dl, parts,
+                             colsum)
+            ctx.fused = [dl, colsum]
+        else:
+            K.lovasz_fwd_bwd(buf, tgt, coef, counters, pixels, c, ldc, ignore_index, images, bins, ce_weight, partials, loss)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        n, c, h, w, ldc, ignore_index, images, bins, ce_weight = ctx.meta
+        g = grad_out.detach().to(torch.float32).contiguous()
+        if ctx.fused is not None:
+            dl, colsum = ctx.fused
+            ctx.fused = None                           # consumed
+        else:                                          # a second backward through a retained graph: the same launch on the saved
+            buf, tgt, coef, counters = ctx.saved_tensors                  # coefficient tables, so the same bits
+            np_ = _load().udaseg_ce_partials()
+            dl, parts, colsum = _OhemCrossEntropyFunction._grad_buffers(n, h, w, ldc, np_, buf.device)
+            K.lovasz_fwd_bwd(buf, tgt, coef, counters, n * h * w, c, ldc, ignore_index, images, bins, ce_weight,
+                             torch.empty(np_, device=buf.device, dtype=torch.float64),
+                             torch.empty((), device=buf.device, dtype=torch.float32), dl, parts, colsum)
+        K.scale_unless_one(dl, g, colsum)
+        COLSUM_SIDE_TABLE.clear()
+        COLSUM_SIDE_TABLE[dl.data_ptr()] = colsum
+        return (dl.permute(0, 3, 1, 2)[:, :c],) + (None,) * 10
+
+
+class LovaszSoftmaxLoss(nn.Module):
+    """The Lovasz-softmax loss (Berman, Rannen Triki, Blaschko, CVPR 2018): the Lovasz extension of the per-class Jaccard loss,
+    the direct surrogate of mean IoU.  ``[N,C,H,W]`` logits (C <= 32) and ``[N,H,W]`` integer targets, as ``CrossEntropyLoss``.
+
+    For a group of pixels (the batch, or one image with ``per_image=True``) and a class ``c`` the error of a pixel is
+    ``1 - p_c`` where the target is ``c`` and ``p_c`` elsewhere; the exact loss sorts the errors and weights them with the steps
+    of the Jaccard loss.  Here nothing is sorted: the errors are counted into ``bins`` uniform bins per class (integer
+    histograms), every pixel of a bin is treated as tied, and its weight is the average of the two orders "fg first" / "bg
+    first" inside the bin, in closed form.  With ``L`` the exact loss and ``L_B`` this one, ``0 <= L - L_B <= sum(last_slack)
+    <= 1 / bins`` (proved in DESIGN.md); ``L_B == L`` when no bin holds two pixels.  The weights are constants in the backward,
+    as in the paper's implementation.
+
+    * ``classes='present'`` averages over the classes that occur in the group's targets, ``'all'`` over all ``C``;
+      ``per_image=True`` averages the per-image values over all ``N`` images.  A group without a valid pixel, or without a
+      present class under 'present', contributes 0 and still counts as an image.
+    * A pixel is valid as for ``CrossEntropyLoss`` (``target != ignore_index`` and ``0 <= target < C``); a valid pixel whose
+      logits are not all finite is void as well.  Void pixels are in no table and their gradient is exactly 0.
+    * ``ce_weight`` adds ``ce_weight *`` the mean cross entropy over the valid finite pixels in the same pass over the logits
+      (the usual recipe is ``CE + Lovasz``: ``ce_weight=1.0``); with no valid pixel that term is NaN, ``CrossEntropyLoss``'s
+      convention.
+
+    After a call, all on the device and written by the loss's own launches (read them when convenient):
+
+    * ``last_target_stats``: int64 ``[n_valid_finite, n_void, n_invalid, n_nonfinite]``;
+    * ``last_present``: int32 ``[I, C]``, ``I = N`` with ``per_image`` and 1 without;
+    * ``last_slack``: float64 ``[C]``; its sum bounds ``L - L_B`` of the value returned.
+
+    Two calls give the same bits (integer atomics, fixed-order sums).  Under data parallelism each rank forms the loss of its
+    own batch.
+    """
+
+    def __init__(self, classes='present', per_image=False, ignore_index=None, bins=1024, ce_weight=0.0):
+        super().__init__()
+        if classes not in ('present', 'all'):
+            raise ValueError(f"LovaszSoftmaxLoss: classes must be 'present' or 'all', got {classes!r}")
+        if isinstance(bins, bool) or int(bins) != bins or not 64 <= int(bins) <= 4096 or int(bins) & (int(bins) - 1):
+            raise ValueError(f"LovaszSoftmaxLoss: bins must be a power of two in [64, 4096], got {bins!r}")
+        ce_weight = float(ce_weight)
+        if ce_weight != ce_weight or ce_weight in (float("inf"), float("-inf")):
+            raise ValueError(f"LovaszSoftmaxLoss: ce_weight must be finite, got {ce_weight}")
+        self.classes, self.per_image, self.bins, self.ce_weight = classes, bool(per_image), int(bins), ce_weight
+        self.ignore_index = _check_ignore_index("LovaszSoftmaxLoss", ignore_index)
+        self.last_target_stats = self.last_present = self.last_slack = None
+
+    def extra_repr(self):
+        return (f"classes={self.classes!r}, per_image={self.per_image}, ignore_index={self.ignore_index}, bins={self.bins}, "
+                f"ce_weight={self.ce_weight}")
+
+    def forward(self, input, target):
+        if input.device.type != "cuda":
+            raise RuntimeError("LovaszSoftmaxLoss: logits must live on the GPU (no CPU path in this build)")
+        if input.dim() != 4 or target.dim() != 3 or input.shape[0] != target.shape[0] or input.shape[2:] != target.shape[1:]:
+            raise ValueError(f"expected logits [N,C,H,W] and target [N,H,W]; got {tuple(input.shape)} and {tuple(target.shape)}")
+        n, c, h, w = input.shape
+        if c > 32:
+            raise ValueError(f"LovaszSoftmaxLoss: at most 32 classes are supported by the HIP kernels, got {c}")
+        if n * h * w >= 2 ** 31:
+            raise ValueError(f"LovaszSoftmaxLoss: at most 2^31 - 1 pixels per call, got {n * h * w}")
+        if target.dtype != torch.int64:
+            target = target.long()
+        dev = input.device
+        images = n if self.per_image else 1
+        tables = torch.zeros((images, c, 2, self.bins), device=dev, dtype=torch.int32)
+        counters = torch.zeros(4, device=dev, dtype=torch.int64)
+        present = torch.empty((images, c), device=dev, dtype=torch.int32)
+        slack = torch.empty(c, device=dev, dtype=torch.float64)
+        out = _LovaszSoftmaxFunction.apply(input, target.to(dev), self.ignore_index, images, self.bins, self.classes == 'all',
+                                           self.ce_weight, tables, counters, present, slack)
+        self.last_target_stats, self.last_present, self.last_slack = counters, present, slack
+        return out
 
 
 class _BCEPairFunction(torch.autograd.Function):
