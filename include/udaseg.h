@@ -817,6 +817,42 @@ int udaseg_regions_sieve(const void* labels, int labels_i64, const int32_t* ids,
 int udaseg_regions_stats(const void* labels, int labels_i64, const int32_t* ids, const int32_t* area, int n, int h, int w,
                          int classes, int has_ignore, int ignore_index, int64_t* stats, void* stream);
 
+/* ---- CRF refinement of class scores under the frame: mean-field inference of a dense CRF (Kraehenbuehl & Koltun 2011) with the
+ * message passing restricted to a local window (ConvCRF, Teichmann & Cipolla 2018); an extension, the reference has no counterpart
+ * (csrc/crf.hip; tests/_crf_ref.py is the numpy mirror, as plain loops over the neighbours).  No sort, no atomics, every sum in a
+ * fixed order: two calls give the same bits.
+ * Operands: scores fp32 [n][h][w][ldc] as scores_common.h describes (classes <= 32, classes <= ldc, ldc % 4 == 0; logits, or
+ * probabilities with probs == 1); frames uint8 [n][h][w][3]; logp, q0, q, q_out fp32 [n][h][w][ldq], classes <= ldq, ldq % 4 == 0;
+ * valid uint8 [n][h][w].  Every fp32 buffer is 16-byte aligned.
+ * Parameters: radius R in 1..5, dilation d in 1..4 with R * d <= 10; w_app, w_smooth >= 0 and not both 0; theta_beta > 0 enters as
+ * inv2b = fp32(1 / (2 theta_beta^2)), strength >= 0.  s_alpha, s_gamma: fp32 [(2R+1)^2], made on the host in float64 and rounded:
+ *   S_alpha[dy+R][dx+R] = exp(-(dy^2 + dx^2) d^2 / (2 theta_alpha^2)), S_gamma the same with theta_gamma.
+ *   valid     P0_i = softmax(s_i), or s_i / sum_c s_i with probs.  Pixel i is VALID if, over the channels < classes, its row is
+ *             finite (logits), or every value lies in [0, 1] (so none is NaN) and the row sum is positive and finite (probs).
+ *             log P0_i(c) = (s_c - max) - log sum exp(s - max) under logits, log(P0_i(c)) with probs; log 0 = -inf is kept.
+ *   neighbour j = i + d * (dy, dx), |dy|, |dx| <= R, (dy, dx) != (0, 0), inside the SAME image and valid.  Images never see each
+ *             other; the frame's edge contributes nothing.
+ *   weight    col_ij = exp(-c2_ij * inv2b), c2_ij the integer squared RGB distance of the two frame pixels (exact in fp32);
+ *             k_ij = w_app * S_alpha * col_ij + w_smooth * S_gamma;  Z_i = sum_j (w_app * S_alpha + w_smooth * S_gamma): the
+ *             colour-free mass, so the frame's edge and void neighbours are compensated and a pixel whose neighbours all differ
+ *             in colour receives little.
+ *   message   m_i(c) = strength * (sum_j k_ij Q_j(c)) / Z_i, and 0 when Z_i == 0;  0 <= m <= strength.
+ *   update    Q'_i = softmax_c(log P0_i(c) + m_i(c)): Potts compatibility, a Jacobi sweep (every Q_j is the previous sweep's).
+ * An invalid pixel has valid == 0, sends no message, carries no mass, and its rows of q0 and q_out are NaN in the channels
+ * < classes (udaseg_proto_rectify's void row); its logp row is NaN too and is never read.  Channels classes .. ldq - 1 of logp, q0
+ * and q_out are written 0 on every call.  Refused with a message before any launch: a parameter outside the ranges above, n <= 0,
+ * h, w < 1, h * w >= 2^31, more than 2^31 - 1 tiles, a NULL or misaligned pointer, q_out == q. */
+/* (tile height << 16) | tile width of udaseg_crf_step's blocks at this radius and dilation (the height depends on the dilation: a
+ * thread owns two pixels `dilation` rows apart); 0 for parameters outside their ranges. */
+int udaseg_crf_tile(int radius, int dilation);
+/* scores -> logp = log P0, q0 = P0 and the valid flags.  One streaming pass. */
+int udaseg_crf_prepare(const float* scores, int ldc, int classes, int probs, int64_t pixels, float* logp, float* q0, int ldq,
+                       uint8_t* valid, void* stream);
+/* One sweep q -> q_out.  logp and valid: what udaseg_crf_prepare wrote for these scores. */
+int udaseg_crf_step(const float* logp, const float* q, const uint8_t* valid, const uint8_t* frames, int n, int h, int w, int classes,
+                    int ldq, int radius, int dilation, const float* s_alpha, const float* s_gamma, float w_app, float w_smooth,
+                    float inv2b, float strength, float* q_out, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

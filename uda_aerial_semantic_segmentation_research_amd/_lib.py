@@ -156,6 +156,9 @@ SIGNATURES = {
     "udaseg_regions_label": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_regions_sieve": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "udaseg_regions_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_crf_tile": (_I, [_I, _I]),
+    "udaseg_crf_prepare": (_I, [_P, _I, _I, _I, _L, _P, _P, _I, _P, _P]),
+    "udaseg_crf_step": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

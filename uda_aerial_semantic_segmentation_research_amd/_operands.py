@@ -436,6 +436,14 @@ OPERANDS = {
                              T("out", u8, "n*h*w"), T("counts", i64, "n*3", True), S],
     "udaseg_regions_stats": [T("labels", _LAB, "n*h*w"), I("labels_i64"), T("ids", i32, "n*h*w"), T("area", i32, "n*h*w"), I("n"),
                              I("h"), I("w"), I("classes"), I("has_ignore"), I("ignore_index"), T("stats", i64, "classes*34"), S],
+    # ---- CRF refinement (logp, q0, q, q_out: padded NHWC rows of ldq floats; the two spatial tables: (2 radius + 1)^2 floats)
+    "udaseg_crf_tile": [I("radius"), I("dilation")],
+    "udaseg_crf_prepare": [T("scores", f32, "pixels*ldc"), I("ldc"), I("classes"), I("probs"), I("pixels"),
+                           T("logp", f32, "pixels*ldq"), T("q0", f32, "pixels*ldq"), I("ldq"), T("valid", u8, "pixels"), S],
+    "udaseg_crf_step": [T("logp", f32, "n*h*w*ldq"), T("q", f32, "n*h*w*ldq"), T("valid", u8, "n*h*w"), T("frames", u8, "n*h*w*3"),
+                        I("n"), I("h"), I("w"), I("classes"), I("ldq"), I("radius"), I("dilation"),
+                        T("s_alpha", f32, "(2*radius+1)**2"), T("s_gamma", f32, "(2*radius+1)**2"), F("w_app"), F("w_smooth"),
+                        F("inv2b"), F("strength"), T("q_out", f32, "n*h*w*ldq"), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

@@ -309,6 +309,28 @@ def regions_stats(labels, ids, area, classes, ignore_index, stats, st=None):
           "regions_stats")
 
 
+# ---- CRF refinement (crf.py; csrc/crf.hip).  Score rows are padded NHWC: [pixels][ld] fp32
+def crf_tile(radius, dilation):
+    """(tile height, tile width) of ``crf_step``'s blocks at this window."""
+    v = _lib.load().udaseg_crf_tile(int(radius), int(dilation))
+    if v == 0:
+        raise ValueError(f"crf_tile: need 1 <= radius <= 5, 1 <= dilation <= 4, radius * dilation <= 10, got {radius}, {dilation}")
+    return v >> 16, v & 0xffff
+
+
+def crf_prepare(scores, ldc, classes, probs, pixels, logp, q0, ldq, valid, st=None):
+    """logp, q0 [pixels * ldq] fp32 = log P0 and P0 of scores [pixels * ldc]; valid [pixels] uint8; NaN rows at invalid pixels."""
+    check(ops.udaseg_crf_prepare(scores, ldc, classes, int(bool(probs)), pixels, logp, q0, ldq, valid, st), "crf_prepare")
+
+
+def crf_step(logp, q, valid, frames, classes, ldq, radius, dilation, s_alpha, s_gamma, w_app, w_smooth, inv2b, strength, q_out,
+             st=None):
+    """q_out = one mean-field sweep of q under uint8 frames [n,h,w,3]; the spatial tables are fp32 [(2 radius + 1)^2] on the device."""
+    n, h, w, _ = frames.shape
+    check(ops.udaseg_crf_step(logp, q, valid, frames, n, h, w, classes, ldq, int(radius), int(dilation), s_alpha, s_gamma,
+                              float(w_app), float(w_smooth), float(inv2b), float(strength), q_out, st), "crf_step")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,
