@@ -853,6 +853,68 @@ int udaseg_crf_step(const float* logp, const float* q, const uint8_t* valid, con
                     int ldq, int radius, int dilation, const float* s_alpha, const float* s_gamma, float w_app, float w_smooth,
                     float inv2b, float strength, float* q_out, void* stream);
 
+/* ---- window votes of label maps and active label acquisition (RIPU, Xie et al., CVPR 2022; an extension, the reference has no
+ * counterpart; csrc/window.hip; tests/_active_ref.py is the numpy mirror).  A label map is n images [h][w], contiguous: uint8
+ * (labels_i64 == 0) or int64 (== 1; 8-byte aligned; a value outside [0, 255] reads as 255), with has_ignore / ignore_index as for
+ * udaseg_boundary_*.
+ *   void         a pixel is VOID if it equals ignore_index (has_ignore == 1) OR its label is >= classes.
+ *   W(p)         the pixels q of the same image with |qy - py| <= radius, |qx - px| <= radius, inside the image and not void.  The
+ *                window is clipped at the frame, never padded; images never see each other.
+ *   n(p), n_c(p) |W(p)|, and the number of q in W(p) with L(q) = c.
+ *   mode(p)      the class with the largest n_c(p); among tied classes the centre's own label if it is one of them (the centre
+ *                is then not void), else the smallest class index.  With n(p) = 0 there is no mode.
+ *   agreement(p) float32(n_mode(p)) / float32(n(p)), one correctly rounded fp32 division of two exact integers; 0 where n(p) = 0.
+ *   impurity(p)  (n log n - sum_c n_c log n_c) / (n log(classes)), with 0 log 0 = 0: the entropy of the window's label histogram
+ *                over log(classes), in [0, 1]; 0 where n(p) <= 1.  As computed: T[m] = fp32(m log m) comes from a DEVICE fp32 table
+ *                [(2 radius + 1)^2 + 1] the caller passes (made on the host in float64 and rounded once; T[0] = T[1] = 0);
+ *                S = sum over c = 0 .. classes - 1, ascending, of T[n_c] in fp32;  impurity = clamp((T[n] - S) / (float32(n) *
+ *                fp32(log(classes))), 0, 1): one subtraction, one product, one division.  A window of one class gives exactly 0.
+ *   entropy(q)   -sum_c p_c log p_c / log(classes) of softmax(scores), or of the probabilities as they are with probs == 1:
+ *                udaseg_entropy_loss's map (lp_c = (z_c - max) - log sum exp(z - max), p_c = exp(lp_c); a term with p_c = 0 is 0;
+ *                the terms are added in ascending class order).
+ *   uncertainty(p)  (sum of entropy(q) over q in W(p)) / float32(n(p)), 0 where n(p) = 0.  The sum is taken DIRECTLY: per row of the
+ *                window its 2 radius + 1 terms left to right (0 for a position outside W), then the 2 radius + 1 row sums top to
+ *                bottom.  No running add / subtract.
+ *   A(p)         min(A0(p), 1) with A0(p) = impurity(p) * uncertainty(p) for kind 0 (RIPU), impurity(p) for kind 1,
+ *                uncertainty(p) for kind 2.  The cap matters: the fp32 entropy of a uniform row can be 1 + 1 ulp.
+ *   key(p)       1.0f - A(p); but -1.0f where p is void, p is excluded (exclude[p] != 0), A0(p) <= 0 or A0(p) is not finite.
+ *                The CANDIDATES are the pixels with key >= 0; their keys lie in [0, 1], what udaseg_kth_* takes.
+ * Limits, refused with a message before any launch: 0 < n <= 65535, h, w >= 1, h * w < 2^31, 0 <= radius <= 16,
+ * 2 <= classes <= 32, ignore_index (and void_label) in [0, 255].  Two calls give the same bits. */
+/* (tile height << 16) | tile width of the window kernels' launch at this radius. */
+int udaseg_window_tile(int radius);
+/* out: uint8 [n][h][w] = mode(p) for a pixel that is not void; a void pixel gets void_label, unless fill_void == 1 and n(p) > 0:
+ * then it gets mode(p).  agreement (NULL or fp32 [n][h][w]) = agreement(p), of void pixels too.  counts (NULL or int64 [n][3],
+ * ACCUMULATES): counts[i] += {pixels not void whose label changed, void pixels filled, void pixels left}. */
+int udaseg_window_mode(const void* labels, int labels_i64, int n, int h, int w, int radius, int classes, int has_ignore,
+                       int ignore_index, int fill_void, int void_label, uint8_t* out, float* agreement, int64_t* counts,
+                       void* stream);
+/* out: fp32 [n][h][w] = impurity(p), of void pixels too. */
+int udaseg_window_impurity(const void* labels, int labels_i64, int n, int h, int w, int radius, int classes, int has_ignore,
+                           int ignore_index, const float* table, float* out, void* stream);
+/* One pass over padded NHWC scores (scores_common.h: [pixels][ldc] fp32, 16-byte aligned, classes <= ldc, ldc % 4 == 0; the
+ * channels >= classes are never looked at): labels uint8 [pixels] = the first maximal class, entropy fp32 [pixels] = entropy(q).
+ * A row with a non-finite score below `classes` (or whose entropy is not finite) gets label 255 and entropy 0.  counters (int64
+ * [2], ACCUMULATES) += {finite rows, non-finite rows}. */
+int udaseg_acquire_prepare(const float* scores, int ldc, int classes, int probs, int64_t pixels, uint8_t* labels, float* entropy,
+                           int64_t* counters, void* stream);
+/* labels uint8 [n][h][w] (a label >= classes, 255 among them, is void), entropy fp32 [n][h][w] (read at pixels that are not void
+ * only), exclude NULL or uint8 [n][h][w].  score fp32 [n][h][w] = A(p), or 0 where key(p) = -1; key fp32 [n][h][w] = key(p). */
+int udaseg_acquire_score(const uint8_t* labels, const float* entropy, const uint8_t* exclude, int n, int h, int w, int radius,
+                         int classes, int kind, const float* table, float* score, float* key, void* stream);
+/* Per cell of the grid of cell_h x cell_w rectangles anchored at (0, 0) (the last row / column of cells is smaller where the image
+ * is no multiple): a = (sum over the cell's candidates of (1.0f - key), in float64) / (pixels of the cell inside the image), rounded
+ * to fp32 once; cell_key fp32 [n][ceil(h / cell_h)][ceil(w / cell_w)] = 1.0f - a, or -1.0f for a cell without a candidate.  One
+ * wave per cell, partial sums folded in a fixed order. */
+int udaseg_acquire_cells(const float* key, int n, int h, int w, int cell_h, int cell_w, float* cell_key, void* stream);
+/* key fp32 [n][items_per_image], thresholds DEVICE fp32 [n]: mask[i][j] |= 1 where key[i][j] >= 0 and key[i][j] <= thresholds[i]
+ * (uint8 [n][items_per_image]; other entries keep their value).  counts (NULL or int64 [n][2], ACCUMULATES): counts[i] +=
+ * {items selected here whose mask was 0 before, candidates}.  0 < items_per_image < 2^31. */
+int udaseg_acquire_select(const float* key, const float* thresholds, int n, int64_t items_per_image, uint8_t* mask, int64_t* counts,
+                          void* stream);
+/* mask uint8 [n][h][w] |= 1 on every pixel, void or not, whose cell of udaseg_acquire_cells's grid has cell_mask != 0. */
+int udaseg_acquire_expand(const uint8_t* cell_mask, int n, int h, int w, int cell_h, int cell_w, uint8_t* mask, void* stream);
+
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */
 int udaseg_gap_splits(int hw);

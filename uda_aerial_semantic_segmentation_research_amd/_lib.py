@@ -159,6 +159,14 @@ SIGNATURES = {
     "udaseg_crf_tile": (_I, [_I, _I]),
     "udaseg_crf_prepare": (_I, [_P, _I, _I, _I, _L, _P, _P, _I, _P, _P]),
     "udaseg_crf_step": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _P, _P]),
+    "udaseg_window_tile": (_I, [_I]),
+    "udaseg_window_mode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "udaseg_window_impurity": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_acquire_prepare": (_I, [_P, _I, _I, _I, _L, _P, _P, _P, _P]),
+    "udaseg_acquire_score": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "udaseg_acquire_cells": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_acquire_select": (_I, [_P, _P, _I, _L, _P, _P, _P]),
+    "udaseg_acquire_expand": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "udaseg_gap_splits": (_I, [_I]),
     "udaseg_gap_linear_sigmoid_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "udaseg_gap_linear_sigmoid_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

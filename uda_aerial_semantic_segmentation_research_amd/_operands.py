@@ -444,6 +444,24 @@ OPERANDS = {
                         I("n"), I("h"), I("w"), I("classes"), I("ldq"), I("radius"), I("dilation"),
                         T("s_alpha", f32, "(2*radius+1)**2"), T("s_gamma", f32, "(2*radius+1)**2"), F("w_app"), F("w_smooth"),
                         F("inv2b"), F("strength"), T("q_out", f32, "n*h*w*ldq"), S],
+    # ---- window votes and active label acquisition (the m log m table: (2 radius + 1)^2 + 1 floats; cells: a ceil-divided grid)
+    "udaseg_window_tile": [I("radius")],
+    "udaseg_window_mode": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("radius"), I("classes"),
+                           I("has_ignore"), I("ignore_index"), I("fill_void"), I("void_label"), T("out", u8, "n*h*w"),
+                           T("agreement", f32, "n*h*w", True), T("counts", i64, "n*3", True), S],
+    "udaseg_window_impurity": [T("labels", _LAB, "n*h*w"), I("labels_i64"), I("n"), I("h"), I("w"), I("radius"), I("classes"),
+                               I("has_ignore"), I("ignore_index"), T("table", f32, "(2*radius+1)**2+1"), T("out", f32, "n*h*w"), S],
+    "udaseg_acquire_prepare": [T("scores", f32, "pixels*ldc"), I("ldc"), I("classes"), I("probs"), I("pixels"),
+                               T("labels", u8, "pixels"), T("entropy", f32, "pixels"), T("counters", i64, 2), S],
+    "udaseg_acquire_score": [T("labels", u8, "n*h*w"), T("entropy", f32, "n*h*w"), T("exclude", u8, "n*h*w", True), I("n"), I("h"),
+                             I("w"), I("radius"), I("classes"), I("kind"), T("table", f32, "(2*radius+1)**2+1"),
+                             T("score", f32, "n*h*w"), T("key", f32, "n*h*w"), S],
+    "udaseg_acquire_cells": [T("key", f32, "n*h*w"), I("n"), I("h"), I("w"), I("cell_h"), I("cell_w"),
+                             T("cell_key", f32, "n*((h+cell_h-1)//cell_h)*((w+cell_w-1)//cell_w)"), S],
+    "udaseg_acquire_select": [T("key", f32, "n*items_per_image"), T("thresholds", f32, "n"), I("n"), I("items_per_image"),
+                              T("mask", u8, "n*items_per_image"), T("counts", i64, "n*2", True), S],
+    "udaseg_acquire_expand": [T("cell_mask", u8, "n*((h+cell_h-1)//cell_h)*((w+cell_w-1)//cell_w)"), I("n"), I("h"), I("w"),
+                              I("cell_h"), I("cell_w"), T("mask", u8, "n*h*w"), S],
     "udaseg_dice_fwd": [T("logits", f32, "batch*pix_per_image*ldc"), T("target", i64, "batch*pix_per_image"), I("batch"),
                         I("pix_per_image"), I("classes"), I("ldc"), F("smooth"), F("eps"), I("pooled"),
                         T("sums", f64, "batch*3*classes"), T("coef", f32, "batch*2*classes"), T("loss", f32, 1), S],

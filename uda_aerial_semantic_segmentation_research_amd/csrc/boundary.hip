@@ -68,15 +68,6 @@ static inline BdGeom bd_geom(int h, int w, int R, int th, int has_ignore, int ig
   return G;
 }
 
-template <bool I64>
-__device__ __forceinline__ int bd_load(const void* __restrict__ img, int64_t p) {
-  if (I64) {
-    const long long v = reinterpret_cast<const long long*>(img)[p];
-    return (v < 0 || v > 255) ? 255 : (int)v;
-  }
-  return reinterpret_cast<const uint8_t*>(img)[p];
-}
-
 // Steps 1-3 for the tile at (ty0, tx0) of one image: leaves the staged labels in lab and g in gcol.  mask_img (may be null): a
 // second map of the image whose void pixels are void here too (the prediction under the truth).  Ends with a barrier.
 template <bool I64>
@@ -91,8 +82,8 @@ __device__ __forceinline__ void bd_tile(const BdGeom& G, const void* __restrict_
     int v = BD_DEAD;
     if (y >= 0 && y < h && x >= 0 && x < w) {                      // every global read is inside the image
       const int64_t p = (int64_t)y * w + x;
-      v = bd_load<I64>(img, p);
-      if (G.has_ignore && (v == G.ignore_index || (mask_img && bd_load<I64>(mask_img, p) == G.ignore_index))) v = BD_DEAD;
+      v = label_at<I64>(img, p);
+      if (G.has_ignore && (v == G.ignore_index || (mask_img && label_at<I64>(mask_img, p) == G.ignore_index))) v = BD_DEAD;
     }
     lab[i] = (unsigned short)v;
   }

@@ -82,6 +82,16 @@ __device__ __forceinline__ int fast_div(int n, int d, float rcp) {
   return q;
 }
 
+// Pixel p of a label map, uint8 or int64: an int64 value outside [0, 255] reads as 255 (boundary.hip, window.hip).
+template <bool I64>
+__device__ __forceinline__ int label_at(const void* __restrict__ img, int64_t p) {
+  if (I64) {
+    const long long v = reinterpret_cast<const long long*>(img)[p];
+    return (v < 0 || v > 255) ? 255 : (int)v;
+  }
+  return reinterpret_cast<const uint8_t*>(img)[p];
+}
+
 __device__ __forceinline__ float act_apply(float x, int act, float slope) {
   return (act == UDASEG_ACT_LEAKY && x < 0.f) ? x * slope : x;
 }

@@ -331,6 +331,64 @@ def crf_step(logp, q, valid, frames, classes, ldq, radius, dilation, s_alpha, s_
                               float(w_app), float(w_smooth), float(inv2b), float(strength), q_out, st), "crf_step")
 
 
+# ---- window votes and active label acquisition (active.py; csrc/window.hip).  labels: uint8 or int64 [n,h,w]
+def _window_head(labels, radius, classes, ignore_index):
+    n, h, w = labels.shape
+    return (int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(radius), int(classes), int(ignore_index is not None),
+            0 if ignore_index is None else int(ignore_index))
+
+
+def window_tile(radius):
+    """(tile height, tile width) of the window kernels' launch at this radius."""
+    v = _lib.load().udaseg_window_tile(int(radius))
+    if v < 0:
+        check(v, "window_tile")
+    return v >> 16, v & 0xffff
+
+
+def window_mode(labels, radius, classes, ignore_index, fill_void, void_label, out, agreement=None, counts=None, st=None):
+    """out [n,h,w] uint8 = the mode of the window's labels; agreement [n,h,w] fp32 or None = its share of the window; counts [n,3]
+    int64 or None += changed, void filled, void left."""
+    check(ops.udaseg_window_mode(labels, *_window_head(labels, radius, classes, ignore_index), int(bool(fill_void)), int(void_label),
+                                 out, agreement, counts, st), "window_mode")
+
+
+def window_impurity(labels, radius, classes, ignore_index, table, out, st=None):
+    """out [n,h,w] fp32 = the normalised entropy of the window's label histogram (table: fp32 [(2 radius + 1)^2 + 1] of m log m)."""
+    check(ops.udaseg_window_impurity(labels, *_window_head(labels, radius, classes, ignore_index), table, out, st), "window_impurity")
+
+
+def acquire_prepare(scores, ldc, classes, probs, pixels, labels, entropy, counters, st=None):
+    """labels [pixels] uint8 = the first maximal class (255: a non-finite row), entropy [pixels] fp32; counters [2] int64 += finite,
+    non-finite rows."""
+    check(ops.udaseg_acquire_prepare(scores, ldc, classes, int(bool(probs)), pixels, labels, entropy, counters, st), "acquire_prepare")
+
+
+def acquire_score(labels, entropy, exclude, radius, classes, kind, table, score, key, st=None):
+    """score, key [n,h,w] fp32 of uint8 labels and their entropy map; exclude: uint8 [n,h,w] or None; kind 0 / 1 / 2."""
+    n, h, w = labels.shape
+    check(ops.udaseg_acquire_score(labels, entropy, exclude, n, h, w, int(radius), int(classes), int(kind), table, score, key, st),
+          "acquire_score")
+
+
+def acquire_cells(key, cell_h, cell_w, cell_key, st=None):
+    """cell_key [n, ceil(h / cell_h), ceil(w / cell_w)] fp32 = 1 - the mean score of the cell, -1 without a candidate."""
+    n, h, w = key.shape
+    check(ops.udaseg_acquire_cells(key, n, h, w, int(cell_h), int(cell_w), cell_key, st), "acquire_cells")
+
+
+def acquire_select(key, thresholds, mask, counts=None, st=None):
+    """mask [n, ...] uint8 |= (0 <= key <= thresholds[i]); counts [n,2] int64 or None += newly selected, candidates."""
+    n = key.shape[0]
+    check(ops.udaseg_acquire_select(key, thresholds, n, key.numel() // n, mask, counts, st), "acquire_select")
+
+
+def acquire_expand(cell_mask, cell_h, cell_w, mask, st=None):
+    """mask [n,h,w] uint8 |= the rectangles of the selected cells."""
+    n, h, w = mask.shape
+    check(ops.udaseg_acquire_expand(cell_mask, n, h, w, int(cell_h), int(cell_w), mask, st), "acquire_expand")
+
+
 def conv2d_fwd_bf16(d, x, w, bias, residual, y, act=ACT_NONE, slope=0.0, stats=None, st=None):
     """bf16 x / w / residual; y bf16, or fp32 when its dtype says so (logits)."""
     check(ops.udaseg_conv2d_fwd_bf16(d, x, w, bias, residual, y,
