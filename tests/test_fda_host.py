@@ -111,9 +111,9 @@ def test_draw_refusals(F):
 
 # -------------------------------------------------------------------------------------------------------- public functions
 def test_public_functions_refuse_bad_arguments_on_cpu_tensors(F, monkeypatch):
-    """Every refusal comes before the device is asked for: on this machine _device() would raise RuntimeError (no GPU), so a
+    """Every refusal comes before the device is asked for: on this machine current_gpu() would raise RuntimeError (no GPU), so a
     ValueError shows the order."""
-    monkeypatch.setattr(F, "_device", lambda: (_ for _ in ()).throw(AssertionError("the device was reached")))
+    monkeypatch.setattr(F.A, "current_gpu", lambda: (_ for _ in ()).throw(AssertionError("the device was reached")))
     n, h, w = 2, 8, 12
     src = torch.zeros((n, h, w, 3), dtype=torch.uint8)
     tgt = torch.zeros((n, h, w, 3), dtype=torch.uint8)
@@ -176,7 +176,7 @@ class _Batches:
 
 
 def test_styled_loader_refuses_mismatched_batches(F, monkeypatch):
-    monkeypatch.setattr(F, "_device", lambda: torch.device("cpu"))           # the refusals come before any kernel
+    monkeypatch.setattr(F.A, "current_gpu", lambda: torch.device("cpu"))           # the refusals come before any kernel
     u8 = lambda *s: torch.zeros(s, dtype=torch.uint8)      # noqa: E731
     good = (u8(2, 8, 12, 3), u8(2, 8, 12))
     for source, target in (([good], [u8(2, 8, 10, 3)]),                       # another H x W

@@ -155,7 +155,7 @@ def test_one_definition_with_conf_share(C, K):
     """bins = 16, beta = 1 (NULL), every target valid: p * 16 is exact in fp32, so ``p >= k / 16`` and ``floor(16 p) >= k`` are one
     statement and the cumulative counts equal udaseg_conf_share's ``above`` exactly.  Also on probabilities that hold exact 0.5
     and 1.0 values."""
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     z, t, _, _ = _case("c23")
     t = np.where((t >= 0) & (t < 23), t, 0)
     zt = torch.from_numpy(z).cuda()
@@ -167,7 +167,7 @@ def test_one_definition_with_conf_share(C, K):
     for scores, is_probs in ((zt, False), (probs, True)):
         ktab, kcnt, _ = _device_tables(C, scores.cpu().numpy(), t, 16, probs=is_probs)
         assert kcnt.tolist() == [t.size, 0, 0]
-        buf, ldc = _padded_nhwc(scores)
+        buf, ldc = padded_nhwc(scores)
         n, c, h, w = scores.shape
         counts = torch.zeros(2, n, dtype=torch.int64, device="cuda")
         share = torch.empty(n, dtype=torch.float32, device="cuda")
@@ -221,7 +221,7 @@ def test_accumulation_and_determinism(C, K):
     other pixels than the whole's, so the float64 additions happen in another order -- and is held to 1e-13 of the magnitude
     (float64 rounding of at most 8192 terms; the terms themselves are the same fp32 numbers, and on an MI355X the difference
     measured 0: fp32 values of this range sum exactly in float64).  n is exact."""
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     z, t, zf, tf = _case("c23")
     zt, tt = torch.from_numpy(z).cuda(), torch.from_numpy(t).cuda()
     whole = C.ReliabilityHistogram(23, 15, "cuda").update(zt, tt)
@@ -239,7 +239,7 @@ def test_accumulation_and_determinism(C, K):
     def sums_of(parts):
         s, c = torch.zeros(4, dtype=torch.float64, device="cuda"), torch.zeros(3, dtype=torch.int64, device="cuda")
         for zz, ttt in parts:
-            buf, ldc = _padded_nhwc(zz)
+            buf, ldc = padded_nhwc(zz)
             K.calib_nll(buf, ttt.reshape(-1).contiguous(), ttt.numel(), 23, ldc, inv,
                         torch.empty(4 * K.seg_partials(), dtype=torch.float64, device="cuda"), s, c)
         return s, c
@@ -259,9 +259,9 @@ def test_accumulation_and_determinism(C, K):
 @pytest.mark.parametrize("beta", [None, 0.36])
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_nll_sums_against_float64(K, name, beta):
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     z, t, zf, tf = _case(name)
-    buf, ldc = _padded_nhwc(torch.from_numpy(z).cuda())
+    buf, ldc = padded_nhwc(torch.from_numpy(z).cuda())
     inv = None if beta is None else torch.full((1,), beta, dtype=torch.float32, device="cuda")
     sums = torch.zeros(4, dtype=torch.float64, device="cuda")
     cnt = torch.zeros(3, dtype=torch.int64, device="cuda")
@@ -273,14 +273,14 @@ def test_nll_sums_against_float64(K, name, beta):
 def test_step_bit_for_bit(K):
     """Given the DEVICE's own sums, the new beta equals the mirror's bit for bit: one IEEE double division, one subtraction,
     compares, one rounding to fp32 (no multiply feeds an add, so nothing can be contracted)."""
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     z, t, _, _ = _case("c23")
     tt = torch.from_numpy(t).cuda().reshape(-1)
     parts = torch.empty(4 * K.seg_partials(), dtype=torch.float64, device="cuda")
     state = torch.zeros(4, dtype=torch.float64, device="cuda")
     steps = 0
     for scale, beta0 in ((1.0, 1.0), (3.0, 1.0), (3.0, 0.25), (0.25, 2.0), (1.0, 0.7)):
-        buf, ldc = _padded_nhwc(torch.from_numpy(z * np.float32(scale)).cuda())
+        buf, ldc = padded_nhwc(torch.from_numpy(z * np.float32(scale)).cuda())
         inv = torch.full((1,), beta0, dtype=torch.float32, device="cuda")
         sums = torch.zeros(4, dtype=torch.float64, device="cuda")
         K.calib_nll(buf, tt, t.size, 23, ldc, inv, parts, sums, torch.zeros(3, dtype=torch.int64, device="cuda"))

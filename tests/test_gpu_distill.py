@@ -190,7 +190,7 @@ def test_module_reads_a_models_padded_logits_in_place_and_feeds_the_bias_gradien
     tb[..., :c] = torch.softmax(3.0 * torch.randn(n, h, w, c, generator=g), -1)
     zv = zb.cuda().permute(0, 3, 1, 2)[:, :c].requires_grad_()
     tv = tb.cuda().permute(0, 3, 1, 2)[:, :c]
-    assert L._padded_nhwc(zv.detach())[0].data_ptr() == zv.data_ptr() and L._padded_nhwc(tv)[0].data_ptr() == tv.data_ptr()
+    assert L.padded_nhwc(zv.detach())[0].data_ptr() == zv.data_ptr() and L.padded_nhwc(tv)[0].data_ptr() == tv.data_ptr()
     loss = L.SoftCrossEntropyLoss("kl")(zv, tv, probs=True)
     loss.backward()
     x = zb[..., :c].permute(0, 3, 1, 2).double().requires_grad_()

@@ -239,7 +239,7 @@ MOD_SHAPE = (2, 23, 9, 11)
 
 def module_inputs(seed, zero_copy):
     """[N, C, H, W] logits that are either the zero-copy view of a padded NHWC buffer with junk in its pad lanes (what Unet.forward
-    returns; _padded_nhwc takes it as it is) or a non-contiguous NCHW tensor (_padded_nhwc runs its layout kernel)."""
+    returns; padded_nhwc takes it as it is) or a non-contiguous NCHW tensor (padded_nhwc runs its layout kernel)."""
     n, c, h, w = MOD_SHAPE
     rng = np.random.default_rng(seed)
     t = C.make_target(rng, n, h * w, c)

@@ -117,13 +117,13 @@ def test_exact_invariants(P, classes, pixels, bins, probs):
 def test_void_label_and_unaligned_label_buffer(P):
     """Another void value, and the kernel's byte-store route: a labels buffer that starts one byte into an allocation."""
     from uda_aerial_semantic_segmentation_research_amd import kernels as K
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     classes, pixels, bins = 5, 1030, 256
     x = _nchw(_logits("scaled", classes, pixels, seed=5))
     thr = P.ConfidenceHistogram(classes, bins).update(x).thresholds(0.5, cap=1.0)
     ref = P.pseudo_labels(x, thr, void=5, bins=bins).reshape(-1)
     assert int(ref.max()) <= 5 and int((ref == 5).sum()) > 0
-    buf, ldc = _padded_nhwc(x)
+    buf, ldc = padded_nhwc(x)
     raw = torch.full((pixels + 9,), 77, dtype=torch.uint8, device="cuda")
     counts = torch.zeros(classes + 2, dtype=torch.int64, device="cuda")
     K.pseudo_labels(buf, pixels, classes, ldc, 0, bins, thr, 5, raw[1:pixels + 1], None, counts)
@@ -295,11 +295,11 @@ def r18():
 
 
 def test_layouts(P, r18):
-    from uda_aerial_semantic_segmentation_research_amd.losses import _padded_nhwc
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
     g = torch.Generator().manual_seed(1)
     with torch.no_grad():
         out = r18(torch.randn(2, 3, 64, 64, generator=g).cuda())
-    buf, ldc = _padded_nhwc(out)
+    buf, ldc = padded_nhwc(out)
     assert ldc == 24 and buf.data_ptr() == out.data_ptr()            # the zero-copy route
     copy = out.contiguous()
     assert copy.data_ptr() != out.data_ptr() and copy.stride(3) == 1

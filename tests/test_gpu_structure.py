@@ -101,7 +101,7 @@ def test_assign_is_read_in_place_by_the_losses():
     bank = _filled_bank(proto64, seen, R.INV_TAU)
     feats = _nchw(f, n, h, w).cuda()
     a = proto.assign(feats, bank)
-    assert a.shape == (n, C, h, w) and not a.requires_grad and L._padded_nhwc(a)[0].data_ptr() == a.data_ptr()
+    assert a.shape == (n, C, h, w) and not a.requires_grad and L.padded_nhwc(a)[0].data_ptr() == a.data_ptr()
     want = proto.assign_mirror(f, proto64, seen, R.INV_TAU)
     got = a.permute(0, 2, 3, 1).reshape(-1, C).cpu().numpy()
     assert np.array_equal(np.isnan(got), np.isnan(want)) and np.isnan(got).any()

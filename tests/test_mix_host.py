@@ -218,13 +218,13 @@ class _HostOnly:
         self.loader = loader
 
     def __iter__(self):
-        from uda_aerial_semantic_segmentation_research_amd import mix
-        saved = mix._device
-        mix._device = lambda: torch.device("cpu")
+        from uda_aerial_semantic_segmentation_research_amd import _args
+        saved = _args.current_gpu
+        _args.current_gpu = lambda: torch.device("cpu")
         try:
             yield from self.loader
         finally:
-            mix._device = saved
+            _args.current_gpu = saved
 
 
 # ------------------------------------------------------------------------------------------------------------- operand rows

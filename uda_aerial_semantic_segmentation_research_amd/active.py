@@ -30,8 +30,8 @@ anywhere).  Nothing is read back unless stated.
 import numpy as np
 import torch
 
+from . import _args as A
 from . import kernels as K
-from .boundary import _on, _out
 
 MAX_RADIUS = 16
 MAX_CLASSES = 32
@@ -40,51 +40,37 @@ KINDS = {"ripu": 0, "impurity": 1, "uncertainty": 2}
 
 # --------------------------------------------------------------------------------------------------------------- host side
 def _check_radius(who, radius):
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= MAX_RADIUS:
-        raise ValueError(f"{who}: radius must be an int in 0..{MAX_RADIUS}, got {radius}")
-    return int(radius)
+    return A.int_in(who, "radius", radius, 0, MAX_RADIUS)
 
 
 def _check_classes(who, num_classes):
-    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 2 <= num_classes <= MAX_CLASSES:
-        raise ValueError(f"{who}: num_classes must be an int in 2..{MAX_CLASSES}, got {num_classes}")
-    return int(num_classes)
+    return A.int_in(who, "num_classes", num_classes, 2, MAX_CLASSES)
 
 
 def _check_ignore(who, ignore_index, classes):
-    if ignore_index is None:
-        return None
-    if isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)) or not classes <= ignore_index <= 255:
-        raise ValueError(f"{who}: ignore_index must be None or an int in num_classes..255 (a class cannot be void), got {ignore_index}")
-    return int(ignore_index)
+    return A.int_in(who, "ignore_index", ignore_index, classes, 255, True)           # a class cannot be void
 
 
 def _check_kind(who, kind):
-    if kind not in KINDS:
-        raise ValueError(f"{who}: kind must be one of {sorted(KINDS)}, got {kind!r}")
-    return KINDS[kind]
+    return KINDS[A.choice(who, "kind", kind, sorted(KINDS))]
 
 
 def _check_cell(who, cell):
     if cell is None:
         return None
-    c = (cell, cell) if isinstance(cell, (int, np.integer)) and not isinstance(cell, bool) else cell
-    if (not isinstance(c, (tuple, list)) or len(c) != 2
-            or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 for v in c)):
+    c = cell if isinstance(cell, (tuple, list)) else (cell, cell)
+    if len(c) != 2:
         raise ValueError(f"{who}: cell must be None, a positive int or a pair of them, got {cell!r}")
-    return int(c[0]), int(c[1])
+    return A.int_in(who, "cell", c[0], 1), A.int_in(who, "cell", c[1], 1)
 
 
 def _check_budget(who, budget):
-    if isinstance(budget, bool) or not isinstance(budget, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{who}: budget must be a positive int or a float in (0, 1), got {budget!r}")
-    if isinstance(budget, (int, np.integer)):
-        if budget < 1:
-            raise ValueError(f"{who}: an int budget must be >= 1 items per image, got {budget}")
-        return int(budget)
-    if not 0.0 < budget < 1.0:
-        raise ValueError(f"{who}: a float budget must lie in (0, 1), got {budget}")
-    return float(budget)
+    """An int (items per image, >= 1) or a float in (0, 1) (a share of them)."""
+    if isinstance(budget, (float, np.floating)):
+        if not 0.0 < budget < 1.0:
+            raise ValueError(f"{who}: a float budget must lie in (0, 1), got {budget}")
+        return float(budget)
+    return A.int_in(who, "budget", budget, 1)
 
 
 def items_of(budget, items):
@@ -101,38 +87,12 @@ def table_of(radius):
     return (m * np.log(np.maximum(m, 1.0))).astype(np.float32)
 
 
-_TABLES = {}
-
-
 def _device_table(r, dev):
-    """The table of a radius on a device, kept: at most 17 radii per GPU, 4.4 KB each at the most, as ``boundary._device_table``
-    keeps its tables.  The upload is a copy from pageable host memory, which returns only after the bytes are on the device, so a
-    kept table is complete whatever stream reads it later; it is never written again."""
-    key = (r, str(dev))
-    t = _TABLES.get(key)
-    if t is None:
-        t = _TABLES[key] = torch.from_numpy(table_of(r)).to(dev)
-    return t
-
-
-def _on_device(who, name, t, dev):
-    if t is not None and t.device != dev:
-        raise ValueError(f"{who}: {name} is on {t.device}, the maps on {dev}")
+    """The table of a radius on a device, kept (``_args.const_table``): at most 17 radii per GPU, 4.4 KB each at the most."""
+    return A.const_table("active", r, lambda: table_of(r), dev)
 
 
 # ------------------------------------------------------------------------------------------------------------- device side
-def _labels(who, labels, name="masks"):
-    """boundary._labels with the checks in the order value, then place: a wrong dtype or shape is a ValueError on any device."""
-    if not torch.is_tensor(labels):
-        raise ValueError(f"{who}: {name} must be a tensor, got {type(labels).__name__}")
-    if labels.dtype not in (torch.uint8, torch.int64) or labels.dim() not in (2, 3) or labels.numel() == 0:
-        raise ValueError(f"{who}: {name} must be non-empty uint8 or int64 [N,H,W] (or [H,W]), got {labels.dtype} {tuple(labels.shape)}")
-    if labels.device.type != "cuda":
-        raise RuntimeError(f"{who}: {name} must live on the GPU (no CPU path in this build)")
-    single = labels.dim() == 2
-    return (labels[None] if single else labels).contiguous(), single
-
-
 def mode_filter(masks_u8, radius, num_classes, ignore_index=255, fill_void=False, counts=None, return_agreement=False, void=None,
                 out=None):
     """The uint8 label map of the window's vote, in the masks' shape (``[N,H,W]`` or ``[H,W]``; uint8 or int64 in).  A void pixel
@@ -142,18 +102,12 @@ def mode_filter(masks_u8, radius, num_classes, ignore_index=255, fill_void=False
     r = _check_radius("mode_filter", radius)
     c = _check_classes("mode_filter", num_classes)
     ign = _check_ignore("mode_filter", ignore_index, c)
-    v = (255 if ign is None else ign) if void is None else void
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
-        raise ValueError(f"mode_filter: void must be an int in 0..255, got {void}")
-    lab, single = _labels("mode_filter", masks_u8)
-    n = lab.shape[0]
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 3)):
-        raise ValueError(f"mode_filter: counts must be an int64 [{n},3] tensor")
-    out = _out("mode_filter", "out", out, lab.shape, torch.uint8, lab.device)
-    _on_device("mode_filter", "out", out, lab.device)
-    _on_device("mode_filter", "counts", counts, lab.device)
+    v = A.int_in("mode_filter", "void", (255 if ign is None else ign) if void is None else void, 0, 255)
+    lab, single = A.label_maps("mode_filter", masks_u8, "masks")
+    A.counts_tensor("mode_filter", "counts", counts, (lab.shape[0], 3), lab.device)
+    out = A.out_tensor("mode_filter", "out", out, lab.shape, torch.uint8, lab.device)
     agr = torch.empty(lab.shape, dtype=torch.float32, device=lab.device) if return_agreement else None
-    _on(lab.device, K.window_mode, lab, r, c, ign, fill_void, int(v), out, agr, counts)
+    A.on_device(lab.device, K.window_mode, lab, r, c, ign, fill_void, v, out, agr, counts)
     res = out[0] if single and out.dim() == 3 else out
     if return_agreement:
         return res, (agr[0] if single else agr)
@@ -170,50 +124,36 @@ def impurity(masks_u8, radius, num_classes, ignore_index=255, out=None):
     r = _check_radius("impurity", radius)
     c = _check_classes("impurity", num_classes)
     ign = _check_ignore("impurity", ignore_index, c)
-    lab, single = _labels("impurity", masks_u8)
-    out = _out("impurity", "out", out, lab.shape, torch.float32, lab.device)
-    _on_device("impurity", "out", out, lab.device)
-    _on(lab.device, K.window_impurity, lab, r, c, ign, _device_table(r, lab.device), out)
+    lab, single = A.label_maps("impurity", masks_u8, "masks")
+    out = A.out_tensor("impurity", "out", out, lab.shape, torch.float32, lab.device)
+    A.on_device(lab.device, K.window_impurity, lab, r, c, ign, _device_table(r, lab.device), out)
     return out[0] if single and out.dim() == 3 else out
 
 
 def _check_scores(who, scores):
-    if not torch.is_tensor(scores) or scores.dim() != 4:
-        raise ValueError(f"{who}: scores must be a [N,C,H,W] tensor, got {tuple(getattr(scores, 'shape', ()))}")
-    if scores.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"{who}: scores must be float32 or bfloat16, got {scores.dtype}")
-    n, c, h, w = (int(v) for v in scores.shape)
+    n, c, h, w = A.scores_shape(who, scores, max_classes=MAX_CLASSES)
     _check_classes(who, c)
-    if n < 1 or n > 65535 or h < 1 or w < 1 or h * w >= 2 ** 31:
-        raise ValueError(f"{who}: need 1 <= N <= 65535, H, W >= 1 and H * W < 2^31, got {(n, c, h, w)}")
+    if n > 65535:
+        raise ValueError(f"{who}: scores must have N <= 65535, got {(n, c, h, w)}")
     return n, c, h, w
-
-
-def _need_gpu(who, scores):
-    if scores.device.type != "cuda":
-        raise RuntimeError(f"{who}: scores must live on the GPU (no CPU path in this build)")
 
 
 def prepare(scores, probs=False, counters=None):
     """``(labels uint8 [N,H,W], entropy fp32 [N,H,W])`` of ``[N,C,H,W]`` scores in ONE pass: the first maximal class and the
     normalised entropy; a row with a non-finite score gets label 255 and entropy 0.  ``counters``: an int64 ``[2]`` device tensor
     that ACCUMULATES the finite and the non-finite rows."""
-    from .losses import _padded_nhwc
     n, c, h, w = _check_scores("prepare", scores)
-    _need_gpu("prepare", scores)
-    dev = scores.device
+    A.counts_tensor("prepare", "counters", counters, (2,), scores.device)
+    dev = A.same_gpu("prepare", scores=scores)
     if counters is None:
         counters = torch.zeros(2, dtype=torch.int64, device=dev)
-    elif not torch.is_tensor(counters) or counters.dtype != torch.int64 or tuple(counters.shape) != (2,):
-        raise ValueError("prepare: counters must be an int64 [2] tensor")
-    _on_device("prepare", "counters", counters, dev)
     labels = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     entropy = torch.empty((n, h, w), dtype=torch.float32, device=dev)
 
     def run():
-        buf, ldc = _padded_nhwc(scores.detach())
+        buf, ldc = A.padded_nhwc(scores.detach())
         K.acquire_prepare(buf, ldc, c, probs, n * h * w, labels, entropy, counters)
-    _on(dev, run)
+    A.on_device(dev, run)
     return labels, entropy
 
 
@@ -229,11 +169,10 @@ def score_maps(labels_u8, entropy, num_classes, radius=1, kind="ripu", exclude=N
         raise ValueError(f"score_maps: entropy must be a float32 {list(shape)} tensor")
     if exclude is not None and (not torch.is_tensor(exclude) or exclude.dtype != torch.uint8 or tuple(exclude.shape) != shape):
         raise ValueError(f"score_maps: exclude must be None or a uint8 {list(shape)} tensor")
-    if dev.type != "cuda" or entropy.device != dev or (exclude is not None and exclude.device != dev):
-        raise RuntimeError("score_maps: labels, entropy and exclude must live on one GPU (no CPU path in this build)")
+    A.same_gpu("score_maps", labels=labels_u8, entropy=entropy, exclude=exclude)
     score = torch.empty(shape, dtype=torch.float32, device=dev)
     key = torch.empty(shape, dtype=torch.float32, device=dev)
-    _on(dev, K.acquire_score, labels_u8.contiguous(), entropy.contiguous(), None if exclude is None else exclude.contiguous(), r, c,
+    A.on_device(dev, K.acquire_score, labels_u8.contiguous(), entropy.contiguous(), None if exclude is None else exclude.contiguous(), r, c,
         k, _device_table(r, dev), score, key)
     return score, key
 
@@ -249,7 +188,6 @@ def acquisition(scores, radius=1, kind="ripu", probs=False, exclude=None):
     n, c, h, w = _check_scores("acquisition", scores)
     if exclude is not None and (not torch.is_tensor(exclude) or exclude.dtype != torch.uint8 or tuple(exclude.shape) != (n, h, w)):
         raise ValueError(f"acquisition: exclude must be None or a uint8 [{n},{h},{w}] tensor")
-    _need_gpu("acquisition", scores)
     labels, entropy = prepare(scores, probs)
     score, key = score_maps(labels, entropy, c, r, kind, exclude)
     return score, key, labels
@@ -270,11 +208,9 @@ def select(key, budget, cell=None, into=None):
         raise ValueError("select: key must be a non-empty float32 [N,H,W] tensor")
     n, h, w = (int(v) for v in key.shape)
     dev = key.device
-    if into is not None and (not torch.is_tensor(into) or into.dtype != torch.uint8 or tuple(into.shape) != (n, h, w)
-                             or into.device != dev or not into.is_contiguous()):
-        raise ValueError(f"select: into must be a contiguous uint8 [{n},{h},{w}] tensor on the key's device")
-    if dev.type != "cuda":
-        raise RuntimeError("select: key must live on the GPU (no CPU path in this build)")
+    if into is not None:
+        A.out_tensor("select", "into", into, (n, h, w), torch.uint8, dev, contiguous=True)
+    A.same_gpu("select", key=key)
     mask = torch.zeros((n, h, w), dtype=torch.uint8, device=dev) if into is None else into
     counts = torch.zeros((n, 2), dtype=torch.int64, device=dev)
 
@@ -294,7 +230,7 @@ def select(key, budget, cell=None, into=None):
             cell_mask = torch.zeros(k_map.shape, dtype=torch.uint8, device=dev)
             K.acquire_select(k_map, thr, cell_mask, counts)
             K.acquire_expand(cell_mask, cells[0], cells[1], mask)
-    _on(dev, run)
+    A.on_device(dev, run)
     return mask, counts
 
 
@@ -313,9 +249,7 @@ class ActivePool:
         self.kind = kind
         self.budget = _check_budget("ActivePool", budget)
         self.cell = _check_cell("ActivePool", cell)
-        if isinstance(void, bool) or not isinstance(void, (int, np.integer)) or not self.num_classes <= void <= 255:
-            raise ValueError(f"ActivePool: void must be an int in num_classes..255, got {void}")
-        self.void = int(void)
+        self.void = A.int_in("ActivePool", "void", void, self.num_classes, 255)
         self.requested = {}            # frame index -> uint8 [H,W], non-zero where a label was requested
         self.rounds = 0
         self.last_counts = None        # int64 [N,2] device tensor of the latest query: newly selected, candidates
@@ -348,19 +282,12 @@ class ActivePool:
         from .data import prepare_batch
         model = getattr(model_or_teacher, "model", model_or_teacher)
         idx = self._indices(indices)
-        if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
-            raise ValueError("ActivePool.query: frames must be a uint8 [N,H,W,3] tensor")
-        if frames_u8.shape[0] != len(idx):
+        if A.frames_u8("ActivePool.query", frames_u8)[0] != len(idx):
             raise ValueError(f"ActivePool.query: {len(idx)} indices for {frames_u8.shape[0]} frames")
-        if frames_u8.device.type != "cuda":
-            raise RuntimeError("ActivePool.query: frames must live on the GPU (no CPU path in this build)")
-        was = model.training
-        model.eval()
-        try:
+        A.same_gpu("ActivePool.query", frames=frames_u8)
+        with A.eval_mode(model):
             images, _ = prepare_batch(frames_u8, None, None, getattr(model, "compute_dtype", torch.float32))
             out = model(images)
-        finally:
-            model.train(was)
         n, c, h, w = out.shape
         if c != self.num_classes:
             raise ValueError(f"ActivePool.query: the model gives {c} classes, the pool was made for {self.num_classes}")

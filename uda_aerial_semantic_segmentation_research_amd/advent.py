@@ -18,10 +18,11 @@ contributes exactly 0 and receives a gradient of exactly 0.
 """
 import torch
 
+from . import _args as A
 from . import kernels as K
 from .discriminator import DomainDiscriminator
 from .engine import ceil_to, mark_padded_input
-from .losses import _check_prediction, _padded_nhwc
+from .losses import _check_prediction
 
 
 def _map_width(classes, dtype):
@@ -44,7 +45,7 @@ class _SelfInformationFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, dtype):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = A.padded_nhwc(logits.detach())
         cpad = _map_width(c, dtype)
         maps = torch.empty((n, h, w, cpad), device=logits.device, dtype=dtype)
         K.selfinfo_fwd(buf, n * h * w, c, ldc, maps, cpad)
@@ -74,7 +75,7 @@ def self_information(logits, dtype=torch.float32):
     that activation type reads it in place.  Do not write into it."""
     _map_width(0, dtype)
     _check_prediction("self_information", logits)
-    return _SelfInformationFunction.apply(logits, dtype)
+    return A.on_device(logits.device, _SelfInformationFunction.apply, logits, dtype)    # backward: the device's autograd thread
 
 
 def entropy_map(logits):
@@ -82,11 +83,12 @@ def entropy_map(logits):
     gradient (logging, ranking target frames by confidence; ``render`` takes the range as it is)."""
     _check_prediction("entropy_map", logits)
     n, c, h, w = logits.shape
+    dev = logits.device
     with torch.no_grad():
-        buf, ldc = _padded_nhwc(logits.detach())
-        out = torch.empty((n, h, w), device=logits.device, dtype=torch.float32)
-        K.entropy_loss(buf, n * h * w, c, ldc, "entropy", torch.empty(K.seg_partials(), device=logits.device, dtype=torch.float64),
-                       torch.empty((), device=logits.device, dtype=torch.float32), None, out)
+        buf, ldc = A.padded_nhwc(logits.detach())
+        out = torch.empty((n, h, w), device=dev, dtype=torch.float32)
+        A.on_device(dev, K.entropy_loss, buf, n * h * w, c, ldc, "entropy", torch.empty(K.seg_partials(), device=dev, dtype=torch.float64),
+                    torch.empty((), device=dev, dtype=torch.float32), None, out)
     return out
 
 

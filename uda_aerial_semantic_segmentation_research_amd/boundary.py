@@ -31,6 +31,7 @@ import math
 import numpy as np
 import torch
 
+from . import _args as A
 from . import kernels as K
 
 MAX_RADIUS = 32
@@ -40,17 +41,7 @@ _SAME = object()              # erode's ignore_index default: the void value its
 
 # --------------------------------------------------------------------------------------------------------------- host side
 def _check_radius(who, radius):
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= MAX_RADIUS:
-        raise ValueError(f"{who}: radius must be an int in 0..{MAX_RADIUS}, got {radius}")
-    return int(radius)
-
-
-def _check_label(who, name, v, none_ok=True):
-    if v is None and none_ok:
-        return None
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
-        raise ValueError(f"{who}: {name} must be an int in 0..255{' or None' if none_ok else ''}, got {v}")
-    return int(v)
+    return A.int_in(who, "radius", radius, 0, MAX_RADIUS)
 
 
 def radius_of(ratio, h, w):
@@ -102,47 +93,14 @@ def summarize(stats, trimap):
 
 
 # ------------------------------------------------------------------------------------------------------------- device side
-def _labels(who, labels, name="labels"):
-    if not torch.is_tensor(labels):
-        raise ValueError(f"{who}: {name} must be a tensor, got {type(labels).__name__}")
-    if labels.device.type != "cuda":
-        raise RuntimeError(f"{who}: {name} must live on the GPU (no CPU path in this build)")
-    if labels.dtype not in (torch.uint8, torch.int64) or labels.dim() not in (2, 3):
-        raise ValueError(f"{who}: {name} must be uint8 or int64 [N,H,W] (or [H,W]), got {labels.dtype} {tuple(labels.shape)}")
-    single = labels.dim() == 2
-    lab = labels[None] if single else labels
-    if lab.numel() == 0:
-        raise ValueError(f"{who}: {name} are empty: {tuple(labels.shape)}")
-    return lab.contiguous(), single
-
-
-def _out(who, name, out, shape, dtype, dev):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if not torch.is_tensor(out) or out.dtype != dtype or tuple(out.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must be a {dtype} {list(shape)} tensor")
-    return out
-
-
-def _on(dev, fn, *args):
-    """The launch goes to the CURRENT device's stream: make the tensors' device current for it."""
-    if dev.index == torch.cuda.current_device():
-        return fn(*args)
-    with torch.cuda.device(dev):
-        return fn(*args)
-
-
 def distance2(labels, radius, ignore_index=None, out=None):
     """int32 ``d2`` of every pixel, in the labels' shape: 0 on a boundary pixel, ``radius^2 + 1`` further than ``radius`` from all."""
-    lab, single = _labels("distance2", labels)
+    lab, single = A.label_maps("distance2", labels)
     r = _check_radius("distance2", radius)
-    ign = _check_label("distance2", "ignore_index", ignore_index)
-    out = _out("distance2", "out", out, lab.shape, torch.int32, lab.device)
-    _on(lab.device, K.boundary_d2, lab, r, ign, out)
+    ign = A.int_in("distance2", "ignore_index", ignore_index, 0, 255, True)
+    out = A.out_tensor("distance2", "out", out, lab.shape, torch.int32, lab.device)
+    A.on_device(lab.device, K.boundary_d2, lab, r, ign, out)
     return out[0] if single and out.dim() == 3 else out
-
-
-_TABLES = {}
 
 
 def _device_table(who, table, r, dev):
@@ -154,25 +112,19 @@ def _device_table(who, table, r, dev):
     arr = np.ascontiguousarray(np.asarray(table.numpy() if torch.is_tensor(table) else table, dtype=np.float32).reshape(-1))
     if arr.shape[0] != r * r + 3:
         raise ValueError(f"{who}: the table needs radius^2 + 3 = {r * r + 3} entries (table_of / unet_table), got {arr.shape[0]}")
-    key = (arr.tobytes(), str(dev))
-    t = _TABLES.get(key)
-    if t is None:                                                   # callers weigh every batch with the same few tables
-        if len(_TABLES) > 64:
-            _TABLES.clear()
-        t = _TABLES[key] = torch.from_numpy(arr.copy()).to(dev)
-    return t
+    return A.const_table("boundary", arr.tobytes(), arr.copy, dev)      # callers weigh every batch with the same few tables
 
 
 def weight_map(labels, radius, table=None, w0=10.0, sigma=5.0, ignore_index=None, out=None):
     """fp32 weights in the labels' shape: ``table[d2]``, the last entry on void pixels.  ``table``: None (``unet_table(radius, w0,
     sigma)``), ``table_of``'s array, or a float32 device tensor of ``radius^2 + 3`` entries.  The table's bits are copied.  The result
     is what ``SoftCrossEntropyLoss`` / ``PrototypeContrastLoss`` take as ``pixel_weight``."""
-    lab, single = _labels("weight_map", labels)
+    lab, single = A.label_maps("weight_map", labels)
     r = _check_radius("weight_map", radius)
-    ign = _check_label("weight_map", "ignore_index", ignore_index)
+    ign = A.int_in("weight_map", "ignore_index", ignore_index, 0, 255, True)
     tab = _device_table("weight_map", unet_table(r, w0, sigma) if table is None else table, r, lab.device)
-    out = _out("weight_map", "out", out, lab.shape, torch.float32, lab.device)
-    _on(lab.device, K.boundary_lookup, lab, r, ign, tab, out)
+    out = A.out_tensor("weight_map", "out", out, lab.shape, torch.float32, lab.device)
+    A.on_device(lab.device, K.boundary_lookup, lab, r, ign, tab, out)
     return out[0] if single and out.dim() == 3 else out
 
 
@@ -182,15 +134,13 @@ def erode(labels, radius, void=255, ignore_index=_SAME, counts=None, out=None):
     its rim makes no boundary and it does not grow; ``None`` makes every value an ordinary label (a void speck then voids the disc
     around it).  ``counts``: an int64 ``[N,2]`` device tensor that ACCUMULATES, per image, the pixels this call voided and the pixels
     that were void already."""
-    lab, single = _labels("erode", labels)
+    lab, single = A.label_maps("erode", labels)
     r = _check_radius("erode", radius)
-    v = _check_label("erode", "void", void, none_ok=False)
-    ign = v if ignore_index is _SAME else _check_label("erode", "ignore_index", ignore_index)
-    n = lab.shape[0]
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 2)):
-        raise ValueError(f"erode: counts must be an int64 [{n},2] tensor")
-    out = _out("erode", "out", out, lab.shape, torch.uint8, lab.device)
-    _on(lab.device, K.boundary_erode, lab, r, ign, v, out, counts)
+    v = A.int_in("erode", "void", void, 0, 255)
+    ign = v if ignore_index is _SAME else A.int_in("erode", "ignore_index", ignore_index, 0, 255, True)
+    A.counts_tensor("erode", "counts", counts, (lab.shape[0], 2), lab.device)
+    out = A.out_tensor("erode", "out", out, lab.shape, torch.uint8, lab.device)
+    A.on_device(lab.device, K.boundary_erode, lab, r, ign, v, out, counts)
     return out[0] if single and out.dim() == 3 else out
 
 
@@ -204,7 +154,7 @@ class ErodedLoader:
     def __init__(self, loader, radius, void=255):
         self.loader = loader
         self.radius = _check_radius("ErodedLoader", radius)
-        self.void = _check_label("ErodedLoader", "void", void, none_ok=False)
+        self.void = A.int_in("ErodedLoader", "void", void, 0, 255)
         self.last_counts = None
 
     def __len__(self):
@@ -224,7 +174,7 @@ class ErodedLoader:
             yield frames, out
 
 
-class BoundaryStats:
+class BoundaryStats(A.DeviceState):
     """Accumulates the band counters of predictions against truth on the device (``udaseg_boundary_stats``).  ``update`` enqueues
     and does not synchronise; ``compute`` does ONE read-back and returns ``summarize`` of the counters.
 
@@ -234,21 +184,14 @@ class BoundaryStats:
     ``radius`` of a truth boundary that are predicted right."""
 
     def __init__(self, num_classes, radius, ignore_index=None, device=None):
-        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= num_classes <= 255:
-            raise ValueError(f"BoundaryStats: num_classes must be in 1..255, got {num_classes}")
-        self.num_classes = int(num_classes)
+        self.num_classes = A.int_in("BoundaryStats", "num_classes", num_classes, 1, 255)
         self.radius = _check_radius("BoundaryStats", radius)
-        self.ignore_index = _check_label("BoundaryStats", "ignore_index", ignore_index)
+        self.ignore_index = A.int_in("BoundaryStats", "ignore_index", ignore_index, 0, 255, True)
         self.device = torch.device(device) if device is not None else None
         self.tables = None             # int64 [3 C + 2] on the device: stats [C,3], then trimap [2] (one allocation, one transfer)
 
-    def _ensure(self, device):
-        if self.tables is None:
-            if device.type != "cuda":
-                raise RuntimeError("BoundaryStats: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self.tables = torch.zeros(3 * self.num_classes + 2, dtype=torch.int64, device=device)
-        return self.tables
+    def _allocate(self, device):
+        self.tables = torch.zeros(3 * self.num_classes + 2, dtype=torch.int64, device=device)
 
     def reset(self):
         if self.tables is not None:
@@ -257,36 +200,29 @@ class BoundaryStats:
     def update(self, pred, truth):
         """``pred``: a label map like ``truth`` (uint8 or int64 ``[N,H,W]``), or scores ``[N,C,H,W]`` (logits or probabilities),
         labelled by their first maximum (``udaseg_predict_finish``'s arg-max, at most 32 classes)."""
-        if not torch.is_tensor(pred) or not torch.is_tensor(truth):
-            raise ValueError("BoundaryStats.update: pred and truth must be tensors")
-        if pred.device.type != "cuda" or truth.device.type != "cuda":
-            raise RuntimeError("BoundaryStats.update: pred and truth must live on the GPU (no CPU path in this build)")
-        if pred.dim() == 4:
-            from .losses import _padded_nhwc
-            n, c, h, w = pred.shape
-            if c != self.num_classes:
-                raise ValueError(f"BoundaryStats.update: scores must be [N,{self.num_classes},H,W], got {tuple(pred.shape)}")
-            buf, ldc = _padded_nhwc(pred.detach())
+        who = "BoundaryStats.update"
+        if torch.is_tensor(pred) and pred.dim() == 4:
+            buf, ldc, n, c, h, w = A.scores_nchw(who, pred, self.num_classes, "pred")
             lab = torch.empty((n, h, w), dtype=torch.int64, device=pred.device)
-            _on(pred.device, K.predict_finish, buf, None, n * h * w, c, ldc, lab)
+            A.on_device(pred.device, K.predict_finish, buf, None, n * h * w, c, ldc, lab)
             pred = lab
-            if truth.dim() == 4 and truth.shape[1] == 1:
+            if torch.is_tensor(truth) and truth.dim() == 4 and truth.shape[1] == 1:
                 truth = truth[:, 0]
-        p, _ = _labels("BoundaryStats.update", pred, "pred")
-        t, _ = _labels("BoundaryStats.update", truth, "truth")
+        p, _ = A.label_maps(who, pred, "pred")
+        t, _ = A.label_maps(who, truth, "truth")
         if p.shape != t.shape:
-            raise ValueError(f"BoundaryStats.update: pred {tuple(p.shape)} and truth {tuple(t.shape)} differ in shape")
+            raise ValueError(f"{who}: pred {tuple(p.shape)} and truth {tuple(t.shape)} differ in shape")
         if p.dtype != t.dtype:                                      # one dtype for both: the uint8 one is widened (lossless)
             p, t = p.long(), t.long()
-        tab = self._ensure(t.device)
+        tab = self._ensure(A.same_gpu(who, truth=t, pred=p)).tables
         c3 = 3 * self.num_classes
-        _on(t.device, K.boundary_stats, p, t, self.radius, self.num_classes, self.ignore_index, tab[:c3], tab[c3:])
+        A.on_device(t.device, K.boundary_stats, p, t, self.radius, self.num_classes, self.ignore_index, tab[:c3], tab[c3:])
         return self
 
     def compute(self):
         """``summarize`` of the accumulated counters: ``boundary_iou`` [C], ``mean_boundary_iou``, ``trimap_accuracy`` and the raw
         ``stats`` [C,3] / ``trimap`` [2].  ONE device->host transfer of ``3 C + 2`` counters."""
-        t = self._ensure(self.device or torch.device("cuda", torch.cuda.current_device())).cpu().numpy()
+        t = self._ensure().tables.cpu().numpy()
         c3 = 3 * self.num_classes
         return summarize(t[:c3].reshape(-1, 3), t[c3:])
 
@@ -298,10 +234,8 @@ def evaluate(model, loader, num_classes, device, radius=None, ignore_index=None)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model runs on the GPU (no CPU path in this build)")
-    was_training = model.training
-    model.eval()
     stats = None
-    with torch.no_grad():
+    with A.eval_mode(model), torch.no_grad():
         for images, masks in loader:
             images = images.to(device)
             masks = masks.to(device)
@@ -312,7 +246,6 @@ def evaluate(model, loader, num_classes, device, radius=None, ignore_index=None)
                 r = radius_of(DEFAULT_RATIO, outputs.shape[2], outputs.shape[3]) if radius is None else radius
                 stats = BoundaryStats(num_classes, r, ignore_index, device)
             stats.update(outputs, masks)
-    model.train(was_training)
     if stats is None:
         raise ValueError("evaluate: the loader is empty")
     res = stats.compute()

@@ -34,18 +34,14 @@ Temperature scaling
 import numpy as np
 import torch
 
+from . import _args as A
+from . import kernels as K
+
 DEFAULT_BINS = 15
 MAX_BINS = 64
 _Q_ONE = 16777216.0
 OUT_KEYS = ("n", "accuracy", "mean_conf", "ece", "mce", "gap")
 CLASS_KEYS = ("n", "accuracy", "mean_conf", "ece")
-
-
-def _check_shape(num_classes, bins):
-    if not 0 < num_classes <= 32:
-        raise ValueError(f"num_classes must be in 1..32, got {num_classes}")
-    if not 2 <= bins <= MAX_BINS:
-        raise ValueError(f"bins must be in 2..{MAX_BINS}, got {bins}")
 
 
 def reliability_from_tables(tables):
@@ -91,16 +87,7 @@ def reliability_from_tables(tables):
     return out
 
 
-def _flat_targets(masks, pixels, what):
-    if masks.numel() != pixels:
-        raise ValueError(f"{what}: masks must be [N,H,W] or [N,1,H,W] matching the logits, got {tuple(masks.shape)}")
-    tgt = masks.reshape(-1)
-    if tgt.dtype != torch.int64:
-        tgt = tgt.long()
-    return tgt.contiguous()
-
-
-class TemperatureScaler:
+class TemperatureScaler(A.DeviceState):
     """One scalar on the device: ``inv_temp [1]`` fp32, the reciprocal temperature ``beta`` (1 until fitted).  ``fit_logits`` and
     ``fit`` enqueue kernels and never read back; ``scale`` is the bridge to ``PseudoLabeler``, ``confidence_share``, ``predict_large``
     and the trainers, none of which know about temperatures; ``temperature()`` is the one host read, for
@@ -113,20 +100,13 @@ class TemperatureScaler:
         self.state = None                # [4] f64: mean nll, mean g1, last move of beta, steps taken
         self.counters = None             # [3] i64: counted, void, non-finite pixels of every pass so far
 
-    def _ensure(self, device):
-        if self.inv_temp is None:
-            device = torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("TemperatureScaler: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self.inv_temp = torch.ones(1, dtype=torch.float32, device=device)
-            self.sums = torch.zeros(4, dtype=torch.float64, device=device)
-            self.state = torch.zeros(4, dtype=torch.float64, device=device)
-            self.counters = torch.zeros(3, dtype=torch.int64, device=device)
-        return self
+    _need_state = A.DeviceState._ensure       # the spelling the GPU tests build their scalers with (tests/test_gpu_calibration.py)
 
-    def _need_state(self):
-        return self._ensure(self.device or torch.device("cuda"))
+    def _allocate(self, device):
+        self.inv_temp = torch.ones(1, dtype=torch.float32, device=device)
+        self.sums = torch.zeros(4, dtype=torch.float64, device=device)
+        self.state = torch.zeros(4, dtype=torch.float64, device=device)
+        self.counters = torch.zeros(3, dtype=torch.int64, device=device)
 
     def reset(self):
         """beta = 1, no steps taken."""
@@ -139,25 +119,19 @@ class TemperatureScaler:
 
     def accumulate(self, logits, masks):
         """Adds one batch's NLL sums at the current beta to the pass in flight (one launch, no sync)."""
-        from . import kernels as K
-        from .losses import _padded_nhwc
-        if logits.device.type != "cuda" or masks.device.type != "cuda":
-            raise RuntimeError("TemperatureScaler: logits and masks must live on the GPU (no CPU path in this build)")
-        if logits.dim() != 4 or not 0 < logits.shape[1] <= 32:
-            raise ValueError(f"logits must be [N,C,H,W] with C <= 32, got {tuple(logits.shape)}")
-        n, c, h, w = logits.shape
-        tgt = _flat_targets(masks, n * h * w, "TemperatureScaler")
-        self._ensure(logits.device)
-        buf, ldc = _padded_nhwc(logits.detach())
-        parts = torch.empty(4 * K.seg_partials(), dtype=torch.float64, device=logits.device)
-        K.calib_nll(buf, tgt, n * h * w, c, ldc, self.inv_temp, parts, self.sums, self.counters)
+        who = "TemperatureScaler"
+        n, c, h, w = A.scores_shape(who, logits, name="logits")
+        tgt = A.flat_targets(who, masks, n * h * w)
+        dev = self._ensure(A.same_gpu(who, logits=logits, masks=masks)).device
+        buf, ldc = A.padded_nhwc(logits.detach())
+        parts = torch.empty(4 * K.seg_partials(), dtype=torch.float64, device=dev)
+        A.on_device(dev, K.calib_nll, buf, tgt, n * h * w, c, ldc, self.inv_temp, parts, self.sums, self.counters)
         return self
 
     def step(self):
         """One guarded Newton step from the accumulated sums (one launch, no sync); the sums start over."""
-        from . import kernels as K
-        self._need_state()
-        K.calib_step(self.sums, self.inv_temp, self.state)
+        self._ensure()
+        A.on_device(self.device, K.calib_step, self.sums, self.inv_temp, self.state)
         return self
 
     def fit_logits(self, logits, masks, iters=8):
@@ -174,14 +148,11 @@ class TemperatureScaler:
         if device.type != "cuda":
             raise RuntimeError("TemperatureScaler.fit: the model runs on the GPU (no CPU path in this build)")
         self._ensure(device)
-        was_training = model.training
-        model.eval()
-        with torch.no_grad():
+        with A.eval_mode(model), torch.no_grad():
             for _ in range(int(iters)):
                 for images, masks in loader:
                     self.accumulate(model(images.to(device)), masks.to(device))
                 self.step()
-        model.train(was_training)
         return self
 
     def scale(self, logits):
@@ -193,12 +164,12 @@ class TemperatureScaler:
 
     def temperature(self):
         """``1 / beta`` as a Python float: one host read."""
-        return 1.0 / float(self._need_state().inv_temp.item())
+        return 1.0 / float(self._ensure().inv_temp.item())
 
     def report(self):
         """One host read: ``beta``, ``temperature``, the last pass's ``mean_nll`` and ``mean_grad`` (d nll / d beta at the beta before
         the last step), ``last_move`` (of beta), ``steps`` and the pixel counters over all passes."""
-        self._need_state()
+        self._ensure()
         packed = torch.cat([self.inv_temp.double(), self.state, self.counters.double()]).cpu().numpy()
         beta = float(packed[0])
         return {"beta": beta, "temperature": 1.0 / beta, "mean_nll": float(packed[1]), "mean_grad": float(packed[2]),
@@ -208,12 +179,12 @@ class TemperatureScaler:
     _STATE = ("inv_temp", "sums", "state", "counters")
 
     def state_dict(self):
-        self._need_state()
+        self._ensure()
         return {k: getattr(self, k).detach().cpu().clone() for k in self._STATE}
 
     def load_state_dict(self, state):
         """Restores the device state bit for bit."""
-        self._need_state()
+        self._ensure()
         for k in self._STATE:
             dst, src = getattr(self, k), state[k]
             if src.dtype != dst.dtype or src.shape != dst.shape:
@@ -224,28 +195,22 @@ class TemperatureScaler:
         return self
 
 
-class ReliabilityHistogram:
+class ReliabilityHistogram(A.DeviceState):
     """Accumulates the reliability tables of ``[N,C,H,W]`` scores against ``[N,H,W]`` (or ``[N,1,H,W]``) masks on the device.
     ``update`` enqueues one kernel and does not synchronise; ``compute`` enqueues the finishing kernel and returns device tensors;
     ``tables`` reads tables and counters back in ONE transfer."""
 
     def __init__(self, num_classes, bins=DEFAULT_BINS, device=None):
-        _check_shape(num_classes, bins)
-        self.num_classes, self.bins = int(num_classes), int(bins)
+        self.num_classes = A.int_in("ReliabilityHistogram", "num_classes", num_classes, 1, 32)
+        self.bins = A.int_in("ReliabilityHistogram", "bins", bins, 2, MAX_BINS)
         self.device = torch.device(device) if device is not None else None
         self.buffer = None               # [3 * C * B + 3] int64 on the device: the tables, then the counters (one transfer)
 
-    def _ensure(self, device):
-        if self.buffer is None:
-            device = torch.device(device)
-            if device.type != "cuda":
-                raise RuntimeError("ReliabilityHistogram: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self.buffer = torch.zeros(3 * self.num_classes * self.bins + 3, dtype=torch.int64, device=device)
-        return self.buffer
+    def _allocate(self, device):
+        self.buffer = torch.zeros(3 * self.num_classes * self.bins + 3, dtype=torch.int64, device=device)
 
     def _views(self):
-        buf = self._ensure(self.device or torch.device("cuda"))
+        buf = self._ensure().buffer
         return buf[:-3], buf[-3:]
 
     @property
@@ -265,30 +230,24 @@ class ReliabilityHistogram:
     def update(self, outputs, masks, probs=False, scaler=None):
         """``outputs``: logits, or probabilities with ``probs``; ``scaler``: a ``TemperatureScaler`` whose beta the kernel reads from
         device memory (logits only)."""
-        from . import kernels as K
-        from .losses import _padded_nhwc
-        if outputs.device.type != "cuda" or masks.device.type != "cuda":
-            raise RuntimeError("ReliabilityHistogram.update: scores and masks must live on the GPU (no CPU path in this build)")
-        if outputs.dim() != 4 or outputs.shape[1] != self.num_classes:
-            raise ValueError(f"scores must be [N,{self.num_classes},H,W], got {tuple(outputs.shape)}")
+        who = "ReliabilityHistogram.update"
+        n, c, h, w = A.scores_shape(who, outputs, self.num_classes)
         if probs and scaler is not None:
-            raise ValueError("ReliabilityHistogram.update: probabilities take no temperature (probs=True with a scaler)")
-        n, c, h, w = outputs.shape
-        tgt = _flat_targets(masks, n * h * w, "ReliabilityHistogram.update")
-        self._ensure(outputs.device)
+            raise ValueError(f"{who}: probabilities take no temperature (probs=True with a scaler)")
+        tgt = A.flat_targets(who, masks, n * h * w)
+        dev = self._ensure(A.same_gpu(who, scores=outputs, masks=masks)).device
         tables, counters = self._views()
-        buf, ldc = _padded_nhwc(outputs.detach())
-        inv_temp = None if scaler is None else scaler._ensure(outputs.device).inv_temp
-        K.calib_hist(buf, tgt, n * h * w, c, ldc, probs, inv_temp, self.bins, tables, counters)
+        buf, ldc = A.padded_nhwc(outputs.detach())
+        inv_temp = None if scaler is None else scaler._ensure(dev).inv_temp
+        A.on_device(dev, K.calib_hist, buf, tgt, n * h * w, c, ldc, probs, inv_temp, self.bins, tables, counters)
         return self
 
     def compute(self):
         """{'out': [6] float64 (``OUT_KEYS``: n, accuracy, mean_conf, ece, mce, gap), 'per_class': [4, C] float64 (``CLASS_KEYS``),
         'counters': [3] int64} as DEVICE tensors (no host sync)."""
-        from . import kernels as K
         tables, counters = self._views()
         f = torch.empty(6 + 4 * self.num_classes, dtype=torch.float64, device=tables.device)
-        K.calib_finish(tables, self.num_classes, self.bins, f[:6], f[6:])
+        A.on_device(tables.device, K.calib_finish, tables, self.num_classes, self.bins, f[:6], f[6:])
         return {"out": f[:6], "per_class": f[6:].view(4, self.num_classes), "counters": counters}
 
     def tables(self):
@@ -313,10 +272,7 @@ def evaluate(model, loader, num_classes, device, bins=DEFAULT_BINS, scaler=None)
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model runs on the GPU (no CPU path in this build)")
     hist = ReliabilityHistogram(num_classes, bins, device)
-    was_training = model.training
-    model.eval()
-    with torch.no_grad():
+    with A.eval_mode(model), torch.no_grad():
         for images, masks in loader:
             hist.update(model(images.to(device)), masks.to(device), scaler=scaler)
-    model.train(was_training)
     return hist.reliability()

@@ -28,6 +28,8 @@ Use::
 import numpy as np
 import torch
 
+from . import _args as A
+from . import kernels as K
 from . import pseudo, teacher
 from .engine import ceil4
 
@@ -38,30 +40,17 @@ DEFAULTS = dict(radius=3, dilation=2, iterations=5, w_app=10.0, w_smooth=3.0, th
                 strength=1.0)
 
 
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
-    return int(v)
-
-
-def _number(name, v, positive):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a number, got {v!r}") from None
-    if not np.isfinite(f) or f < 0.0 or (positive and f == 0.0):
-        raise ValueError(f"{name} must be finite and {'> 0' if positive else '>= 0'}, got {v!r}")
-    return f
-
-
 def check_params(radius=3, dilation=2, iterations=5, w_app=10.0, w_smooth=3.0, theta_alpha=80.0, theta_beta=13.0, theta_gamma=3.0,
                  strength=1.0):
     """The parameters as a dict of plain numbers; ``ValueError`` for one outside its range (module docstring, ``udaseg.h``)."""
-    p = dict(radius=_int_in("radius", radius, 1, MAX_RADIUS), dilation=_int_in("dilation", dilation, 1, MAX_DILATION),
-             iterations=_int_in("iterations", iterations, 0, MAX_ITERATIONS),
-             w_app=_number("w_app", w_app, False), w_smooth=_number("w_smooth", w_smooth, False),
-             theta_alpha=_number("theta_alpha", theta_alpha, True), theta_beta=_number("theta_beta", theta_beta, True),
-             theta_gamma=_number("theta_gamma", theta_gamma, True), strength=_number("strength", strength, False))
+    who = "crf"
+    p = dict(radius=A.int_in(who, "radius", radius, 1, MAX_RADIUS), dilation=A.int_in(who, "dilation", dilation, 1, MAX_DILATION),
+             iterations=A.int_in(who, "iterations", iterations, 0, MAX_ITERATIONS),
+             w_app=A.number(who, "w_app", w_app, 0.0), w_smooth=A.number(who, "w_smooth", w_smooth, 0.0),
+             theta_alpha=A.number(who, "theta_alpha", theta_alpha, 0.0, lo_open=True),
+             theta_beta=A.number(who, "theta_beta", theta_beta, 0.0, lo_open=True),
+             theta_gamma=A.number(who, "theta_gamma", theta_gamma, 0.0, lo_open=True),
+             strength=A.number(who, "strength", strength, 0.0))
     if p["radius"] * p["dilation"] > MAX_REACH:
         raise ValueError(f"radius * dilation must not exceed {MAX_REACH}, got {p['radius']} * {p['dilation']}")
     if p["w_app"] == 0.0 and p["w_smooth"] == 0.0:
@@ -85,24 +74,6 @@ def inv2b_of(theta_beta):
     return np.float32(1.0 / (2.0 * float(theta_beta) ** 2))
 
 
-def _operands(who, outputs, frames_u8):
-    if not torch.is_tensor(outputs) or outputs.dim() != 4:
-        raise ValueError(f"{who}: scores must be a [N,C,H,W] tensor, got {tuple(getattr(outputs, 'shape', ()))}")
-    if outputs.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"{who}: scores must be float32 or bfloat16, got {outputs.dtype}")
-    n, c, h, w = (int(v) for v in outputs.shape)
-    if not 1 <= c <= 32:
-        raise ValueError(f"{who}: classes must lie in 1..32, got {c}")
-    if n < 1 or h < 1 or w < 1 or h * w >= 2 ** 31:
-        raise ValueError(f"{who}: need N, H, W >= 1 and H * W < 2^31, got {(n, c, h, w)}")
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or tuple(frames_u8.shape) != (n, h, w, 3):
-        raise ValueError(f"{who}: frames must be a uint8 [{n},{h},{w},3] tensor, got "
-                         f"{getattr(frames_u8, 'dtype', type(frames_u8).__name__)} {tuple(getattr(frames_u8, 'shape', ()))}")
-    if outputs.device.type != "cuda" or frames_u8.device != outputs.device:
-        raise RuntimeError(f"{who}: scores and frames must live on one GPU (no CPU path in this build)")
-    return n, c, h, w
-
-
 @torch.no_grad()
 def refine(outputs, frames_u8, radius=3, dilation=2, iterations=5, w_app=10.0, w_smooth=3.0, theta_alpha=80.0, theta_beta=13.0,
            theta_gamma=3.0, strength=1.0, probs=False, out=None):
@@ -115,19 +86,19 @@ def refine(outputs, frames_u8, radius=3, dilation=2, iterations=5, w_app=10.0, w
     The defaults follow ConvCRF's published ratio of appearance to smoothness weight and its colour scale; NOBODY HAS TUNED THEM ON
     THIS DATA.  ``iterations = 0`` returns ``P0``.  ``1 + iterations`` launches, no gradient, no host read; bad parameters raise
     ``ValueError`` before any launch, CPU tensors raise ``RuntimeError``."""
-    from . import kernels as K
-    from .losses import _padded_nhwc
     p = check_params(radius, dilation, iterations, w_app, w_smooth, theta_alpha, theta_beta, theta_gamma, strength)
-    n, c, h, w = _operands("refine", outputs, frames_u8)
-    dev = outputs.device
+    n, c, h, w = A.scores_shape("refine", outputs)
+    A.frames_u8("refine", frames_u8, (n, h, w))
     ldq = ceil4(c)
-    if out is None:
-        out = torch.empty((n, h, w, ldq), dtype=torch.float32, device=dev)
-    elif (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, h, w, ldq) or not out.is_contiguous()
-          or out.device != dev):
-        raise ValueError(f"refine: out must be a contiguous float32 [{n},{h},{w},{ldq}] tensor on the scores' GPU")
-    sbuf, ldc = _padded_nhwc(outputs.detach())
-    frames = frames_u8.contiguous()
+    dev = A.same_gpu("refine", scores=outputs, frames=frames_u8)
+    out = A.out_tensor("refine", "out", out, (n, h, w, ldq), torch.float32, dev, contiguous=True)
+    return A.on_device(dev, _refine, p, outputs, frames_u8.contiguous(), probs, out, n, c, h, w, ldq)
+
+
+def _refine(p, outputs, frames, probs, out, n, c, h, w, ldq):
+    """``refine``'s launches on checked operands, the scores' device current."""
+    dev = outputs.device
+    sbuf, ldc = A.padded_nhwc(outputs.detach())
     T = p["iterations"]
     logp = torch.empty((n, h, w, ldq), dtype=torch.float32, device=dev)
     valid = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
@@ -170,13 +141,7 @@ class CrfLabeler(teacher.OnlineLabeler):
 
     def label(self, frames_u8):
         """uint8 ``[N,H,W]`` masks (device) of uint8 ``[N,H,W,3]`` frames; updates the table and ``self.thr_bins``.  No host read."""
-        was = self._eval()
-        try:
-            with torch.no_grad():
-                out = self._forward(frames_u8)
-        finally:
-            self.model.train(was)
-        q = refine(out, frames_u8, **self.crf)
+        q = refine(self._eval_forward(frames_u8), frames_u8, **self.crf)
         if self.halve_every and self.calls and self.calls % self.halve_every == 0:
             self.halve_(self.hist.table)
         self.calls += 1
@@ -189,8 +154,6 @@ def refine_large(model, frame_u8_hwc, return_probs=False, **kwargs):
     """Label map int64 ``[H,W]`` (and, with ``return_probs``, the refined ``[1,C,H,W]`` probabilities) of one frame of any size
     with ``H * W < 2^31``: ``predict_large(..., return_probs=True)``, then ONE ``refine`` of the whole blended frame, so no tile
     seam is visible in the refinement.  ``kwargs``: ``refine``'s parameters and ``predict_large``'s, told apart by name."""
-    from . import kernels as K
-    from .losses import _padded_nhwc
     from .predict import predict_large
     crf_kwargs = check_params(**{k: kwargs.pop(k) for k in list(kwargs) if k in DEFAULTS})
     _, probs = predict_large(model, frame_u8_hwc, return_probs=True, **kwargs)
@@ -201,8 +164,8 @@ def refine_large(model, frame_u8_hwc, return_probs=False, **kwargs):
     q = refine(probs, frame, probs=True, **crf_kwargs)
     _, c, h, w = q.shape
     labels = torch.empty((h, w), dtype=torch.int64, device=q.device)
-    qbuf, ldq = _padded_nhwc(q)                                    # the buffer q is a view of
-    K.predict_finish(qbuf, None, h * w, c, ldq, labels)
+    qbuf, ldq = A.padded_nhwc(q)                                   # the buffer q is a view of (no launch)
+    A.on_device(q.device, K.predict_finish, qbuf, None, h * w, c, ldq, labels)
     return (labels, q) if return_probs else labels
 
 

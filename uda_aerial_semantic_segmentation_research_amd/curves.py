@@ -32,6 +32,9 @@ From the tables, per class, with ``P = sum pos``, ``N = sum neg``, bins walked f
 import numpy as np
 import torch
 
+from . import _args as A
+from . import kernels as K
+
 SCORE_BINS = 2048
 SCORE_RANGE = 16.0
 SUPPORTED_BINS = (256, 512, 1024, 2048, 4096)
@@ -94,80 +97,60 @@ def curves_from_hist(pos, neg, score_range=SCORE_RANGE):
     return out
 
 
-class ScoreHistogram:
+class ScoreHistogram(A.DeviceState):
     """Accumulates the per-class score histograms of ``[N,C,H,W]`` logits against ``[N,H,W]`` (or ``[N,1,H,W]``) masks on the
     device.  ``update`` enqueues one kernel and does not synchronise; ``compute`` enqueues the finishing kernel and returns
     device tensors; ``curves`` reads the two tables back in ONE transfer and returns ``curves_from_hist`` of them."""
 
     def __init__(self, num_classes, bins=SCORE_BINS, score_range=SCORE_RANGE, device=None):
-        if not 0 < num_classes <= 32:
-            raise ValueError(f"num_classes must be in 1..32, got {num_classes}")
-        if bins not in SUPPORTED_BINS:
-            raise ValueError(f"bins must be one of {SUPPORTED_BINS}, got {bins}")
-        if not score_range > 0:
-            raise ValueError(f"score_range must be positive, got {score_range}")
-        self.num_classes, self.bins, self.score_range = int(num_classes), int(bins), float(score_range)
+        self.num_classes = A.int_in("ScoreHistogram", "num_classes", num_classes, 1, 32)
+        self.bins = int(A.choice("ScoreHistogram", "bins", bins, SUPPORTED_BINS))
+        self.score_range = A.number("ScoreHistogram", "score_range", score_range, 0.0, lo_open=True)
         self.device = torch.device(device) if device is not None else None
         self.tables = None              # [2, C, B] int64 on the device: pos, neg (one allocation, one transfer)
 
-    def _ensure(self, device):
-        if self.tables is None:
-            if device.type != "cuda":
-                raise RuntimeError("ScoreHistogram: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self.tables = torch.zeros(2, self.num_classes, self.bins, dtype=torch.int64, device=device)
-        return self.tables
+    def _allocate(self, device):
+        self.tables = torch.zeros(2, self.num_classes, self.bins, dtype=torch.int64, device=device)
 
     @property
     def pos(self):
-        return self._ensure(self.device or torch.device("cuda"))[0]
+        return self._ensure().tables[0]
 
     @property
     def neg(self):
-        return self._ensure(self.device or torch.device("cuda"))[1]
+        return self._ensure().tables[1]
 
     def reset(self):
         if self.tables is not None:
             self.tables.zero_()
 
     def update(self, outputs, masks):
-        from . import kernels as K
-        from .losses import _padded_nhwc
-        if outputs.device.type != "cuda" or masks.device.type != "cuda":
-            raise RuntimeError("ScoreHistogram.update: logits and masks must live on the GPU (no CPU path in this build)")
-        if outputs.dim() != 4 or outputs.shape[1] != self.num_classes:
-            raise ValueError(f"logits must be [N,{self.num_classes},H,W], got {tuple(outputs.shape)}")
-        n, c, h, w = outputs.shape
-        if masks.numel() != n * h * w:
-            raise ValueError(f"masks must be [N,H,W] or [N,1,H,W] matching the logits, got {tuple(masks.shape)}")
-        t = self._ensure(outputs.device)
-        buf, ldc = _padded_nhwc(outputs.detach())
-        tgt = masks.reshape(-1)
-        if tgt.dtype != torch.int64:
-            tgt = tgt.long()
-        K.score_hist(buf, tgt.contiguous(), n * h * w, c, ldc, self.bins, self.score_range, t[0], t[1])
+        who = "ScoreHistogram.update"
+        n, c, h, w = A.scores_shape(who, outputs, self.num_classes, "logits")
+        tgt = A.flat_targets(who, masks, n * h * w)
+        dev = A.same_gpu(who, logits=outputs, masks=masks)
+        t = self._ensure(dev).tables
+        buf, ldc = A.padded_nhwc(outputs.detach())
+        A.on_device(dev, K.score_hist, buf, tgt, n * h * w, c, ldc, self.bins, self.score_range, t[0], t[1])
         return self
 
     def compute(self):
         """{'auc', 'ap', 'auc_slack': [C] float64, 'support': [C, 2] int64 (P, N)} as DEVICE tensors (no host sync)."""
-        from . import kernels as K
-        t = self._ensure(self.device or torch.device("cuda"))
+        t = self._ensure().tables
         C = self.num_classes
         f = torch.empty(3, C, dtype=torch.float64, device=t.device)
         support = torch.empty(C, 2, dtype=torch.int64, device=t.device)
-        K.curve_finish(t[0], t[1], C, self.bins, f[0], f[1], f[2], support)
+        A.on_device(t.device, K.curve_finish, t[0], t[1], C, self.bins, f[0], f[1], f[2], support)
         return {"auc": f[0], "ap": f[1], "auc_slack": f[2], "support": support}
 
     def curves(self):
         """``curves_from_hist`` of the accumulated tables: ONE device->host transfer of 2 x C x B counters."""
-        t = self._ensure(self.device or torch.device("cuda")).cpu().numpy()
+        t = self._ensure().tables.cpu().numpy()
         return curves_from_hist(t[0], t[1], self.score_range)
 
 
 def class_curves(outputs, masks, num_classes, bins=SCORE_BINS, score_range=SCORE_RANGE):
     """One-shot form: the curves (``curves_from_hist`` dict) of one batch of logits against its masks."""
-    if outputs.device.type != "cuda":
-        raise RuntimeError("class_curves: logits must live on the GPU (no CPU path in this build)")
     return ScoreHistogram(num_classes, bins, score_range, outputs.device).update(outputs, masks).curves()
 
 
@@ -191,13 +174,11 @@ def evaluate(model, loader, num_classes, device, bins=SCORE_BINS, score_range=SC
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model runs on the GPU (no CPU path in this build)")
-    was_training = model.training
-    model.eval()
     hist = ScoreHistogram(num_classes, bins, score_range, device)
     cm = torch.zeros(num_classes, num_classes, dtype=torch.int64, device=device)
     npred = torch.zeros(num_classes, dtype=torch.int64, device=device)
     total = 0
-    with torch.no_grad():
+    with A.eval_mode(model), torch.no_grad():
         for images, masks in loader:
             images = images.to(device)
             masks = masks.to(device).long()
@@ -207,7 +188,6 @@ def evaluate(model, loader, num_classes, device, bins=SCORE_BINS, score_range=SC
             # pixels with a target outside [0, C) are not in the confusion matrix but do count in the reference's distribution
             npred += torch.bincount(outputs.argmax(dim=1).reshape(-1), minlength=num_classes)
             total += masks.numel()
-    model.train(was_training)
     packed = torch.cat([cm.reshape(-1), npred, hist.tables.reshape(-1)]).cpu().numpy()
     k = num_classes
     cmn = packed[:k * k].reshape(k, k)

@@ -53,23 +53,22 @@ import math
 import numpy as np
 import torch
 
-_TABLES = {}
+from . import _args as A
+from . import kernels as K
 
 
 def _check_pair(name, pair, lo_min, hi_max):
-    try:
-        lo, hi = (float(v) for v in pair)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a pair (lo, hi) with {lo_min} <= lo <= hi <= {hi_max}, got {pair}") from None
-    if not lo_min <= lo <= hi <= hi_max:
-        raise ValueError(f"{name} must be a pair (lo, hi) with {lo_min} <= lo <= hi <= {hi_max}, got {pair}")
-    return lo, hi
+    return A.pair("fda", name, pair, lo_min, hi_max)
 
 
 def _check_size(name, v, least=1):
-    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < least:
-        raise ValueError(f"{name} must be an integer >= {least}, got {v}")
-    return int(v)
+    return A.int_in("fda", name, v, least)
+
+
+def _check_p(p):
+    if not isinstance(p, (int, float)):
+        raise ValueError(f"fda: p must be a probability, got {p!r}")
+    return A.number("fda", "p", p, 0.0, 1.0)
 
 
 def max_band(h, w):
@@ -80,13 +79,7 @@ def max_band(h, w):
 def band_of(beta, h, w):
     """``floor(min(h, w) * beta)`` (the original's rule) capped at ``max_band(h, w)``; ``0 <= beta <= 0.5``.  Needs no GPU."""
     cap = max_band(h, w)
-    try:
-        beta = float(beta)
-    except (TypeError, ValueError):
-        raise ValueError(f"beta must be a number in [0, 0.5], got {beta}") from None
-    if not 0.0 <= beta <= 0.5:
-        raise ValueError(f"beta must be a number in [0, 0.5], got {beta}")
-    return min(int(math.floor(min(h, w) * beta)), cap)
+    return min(int(math.floor(min(h, w) * A.number("band_of", "beta", beta, 0.0, 0.5))), cap)
 
 
 def draw_bands(n, h, w, generator=None, beta=(0.01, 0.05), p=1.0):
@@ -95,8 +88,7 @@ def draw_bands(n, h, w, generator=None, beta=(0.01, 0.05), p=1.0):
     n = _check_size("n", n)
     cap = max_band(h, w)
     lo, hi = _check_pair("beta", beta, 0.0, 0.5)
-    if not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
-        raise ValueError(f"p must be a probability, got {p}")
+    p = _check_p(p)
     u = torch.rand(n, 2, generator=generator, dtype=torch.float64).numpy()
     b = np.minimum(np.floor(min(h, w) * (lo + u[:, 0] * (hi - lo))), cap).astype(np.int32)
     b[u[:, 1] >= p] = -1
@@ -111,40 +103,21 @@ def draw_strengths(n, generator=None, lam=(1.0, 1.0)):
     return torch.from_numpy((lo + u * (hi - lo)).astype(np.float32))
 
 
-def _device():
-    from . import _lib
-    _lib.require_gpu()
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _tables(length, dev):
     """(float64 [L,2], float32 [L,2]) device tables of (cos, sin)(2 pi k / L), made once per length and device on the host."""
-    key = (length, str(dev))
-    t = _TABLES.get(key)
-    if t is None:
+    def make():
         ang = 2.0 * np.pi * np.arange(length, dtype=np.float64) / length
         t64 = np.stack([np.cos(ang), np.sin(ang)], axis=1)
-        if len(_TABLES) > 64:
-            _TABLES.clear()
-        t = _TABLES[key] = (torch.from_numpy(t64).to(dev), torch.from_numpy(t64.astype(np.float32)).to(dev))
-    return t
+        return t64, t64.astype(np.float32)
+    return A.const_table("fda", length, make, dev)
 
 
 def _frames_shape(who, name, t):
-    if not torch.is_tensor(t) or t.dtype != torch.uint8:
-        raise ValueError(f"{who}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError(f"{who}: {name} must be [N,H,W,3] with N, H, W >= 1, got {list(t.shape)}")
-    n, h, w = (int(v) for v in t.shape[:3])
-    if n * h * w >= 1 << 31:
-        raise ValueError(f"{who}: N*H*W must stay below 2^31, got {n * h * w}")
-    return n, h, w
+    return A.frames_u8(who, t, name=name, below_2_31=True)
 
 
 def _check_bmax(who, bmax, h, w):
-    if not isinstance(bmax, (int, np.integer)) or isinstance(bmax, bool) or not 0 <= bmax <= max_band(h, w):
-        raise ValueError(f"{who}: bmax must be an integer in [0, {max_band(h, w)}] for {h} x {w} frames, got {bmax}")
-    return int(bmax)
+    return A.int_in(who, f"bmax (for {h} x {w} frames)", bmax, 0, max_band(h, w))
 
 
 def _vector(who, name, t, dtype, n, lo, hi):
@@ -164,29 +137,23 @@ def low_spectrum(frames_u8, bmax):
     """float64 ``[N,3,K,K,2]`` on the device, ``K = 2*bmax+1``: the coefficients ``(re, im)`` of the frequencies ``u, v in [-bmax,
     bmax]`` (index ``u + bmax``, ``v + bmax``) of every channel of uint8 ``[N,H,W,3]`` frames.  A host tensor is moved with one
     asynchronous copy; no synchronisation."""
-    from . import kernels as K
     n, h, w = _frames_shape("low_spectrum", "frames", frames_u8)
     bmax = _check_bmax("low_spectrum", bmax, h, w)
-    dev = _device()
+    dev = A.current_gpu()
     frames = frames_u8.to(dev, non_blocking=True).contiguous()
     k = 2 * bmax + 1
     rows = torch.empty((n, 3, h, k, 2), dtype=torch.float64, device=dev)
     coeffs = torch.empty((n, 3, k, k, 2), dtype=torch.float64, device=dev)
-    K.fda_spectrum_u8(frames, _tables(h, dev)[0], _tables(w, dev)[0], n, h, w, bmax, rows, coeffs)
+    A.on_device(dev, K.fda_spectrum_u8, frames, _tables(h, dev)[0], _tables(w, dev)[0], n, h, w, bmax, rows, coeffs)
     return coeffs
 
 
 def amplitudes(frames_u8, bmax, out=None):
     """float64 ``[N,3,K,K]`` on the device: ``|F|`` of ``low_spectrum(frames_u8, bmax)``, what ``transfer`` takes as a target.
     ``out``: a contiguous device tensor of that shape to write into (rows of an ``AmplitudeBank``)."""
-    from . import kernels as K
     coeffs = low_spectrum(frames_u8, bmax)
-    shape = tuple(coeffs.shape[:4])
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=coeffs.device)
-    elif not (torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == shape and out.is_cuda and out.is_contiguous()):
-        raise ValueError(f"amplitudes: out must be a contiguous float64 {list(shape)} tensor on the GPU")
-    K.fda_amplitude(coeffs, out.numel(), out)
+    out = A.out_tensor("amplitudes", "out", out, coeffs.shape[:4], torch.float64, coeffs.device, contiguous=True)
+    A.on_device(coeffs.device, K.fda_amplitude, coeffs, out.numel(), out)
     return out
 
 
@@ -202,7 +169,6 @@ def transfer(src_frames, tgt_frames_or_amps, b, lam=None, pick=None, out=None, c
     ``out``: a contiguous device tensor of the result's shape and dtype to write into (rows of a larger batch); ``counts``: a
     device int64 ``[N,2]`` table to accumulate into, None for a fresh zeroed one, False to keep none.  ``dtype``: ``torch.uint8``
     (rounded and clamped) or ``torch.float32`` (the real field)."""
-    from . import kernels as K
     who = "transfer"
     n, h, w = _frames_shape(who, "src_frames", src_frames)
     if dtype not in (torch.uint8, torch.float32):
@@ -237,28 +203,25 @@ def transfer(src_frames, tgt_frames_or_amps, b, lam=None, pick=None, out=None, c
             raise ValueError(f"transfer: {n} source samples but {m} target rows and no pick")
         pick = torch.from_numpy(np.arange(n, dtype=np.int32))
     _vector(who, "pick", pick, torch.int32, n, 0, m - 1)
-    dev = _device()
+    dev = A.current_gpu()
     mv = lambda t: t.to(dev, non_blocking=True).contiguous()      # noqa: E731
     src, b, lam, pick = mv(src_frames), mv(b), mv(lam), mv(pick)
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=dtype, device=dev)
-    elif not (torch.is_tensor(out) and out.dtype == dtype and tuple(out.shape) == (n, h, w, 3) and out.is_cuda and out.is_contiguous()):
-        raise ValueError(f"transfer: out must be a contiguous {dtype} [{n}, {h}, {w}, 3] tensor on the GPU")
+    out = A.out_tensor(who, "out", out, (n, h, w, 3), dtype, dev, contiguous=True)
     if counts is None:
         counts = K.zeros((n, 2), torch.int64, dev)
     elif counts is False:
         counts = None
-    elif not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 2):
-        raise ValueError(f"transfer: counts must be an int64 [{n}, 2] tensor, None or False")
+    else:
+        A.counts_tensor(who, "counts", counts, (n, 2), dev)
     amps = mv(target) if target.dtype == torch.float64 else amplitudes(target, bmax)
     k = 2 * bmax + 1
     coeffs = low_spectrum(src, bmax)
     delta = torch.empty((n, 3, k, k, 2), dtype=torch.float32, device=dev)
-    K.fda_delta(coeffs, amps, pick, b, lam, n, m, h, w, bmax, delta)
+    A.on_device(dev, K.fda_delta, coeffs, amps, pick, b, lam, n, m, h, w, bmax, delta)
     cols = torch.empty((n, 3, k, w, 2), dtype=torch.float32, device=dev)
     u8 = dtype == torch.uint8
-    K.fda_apply_u8(src, delta, b, _tables(h, dev)[1], _tables(w, dev)[1], n, h, w, bmax, cols, out if u8 else None,
-                   None if u8 else out, counts)
+    A.on_device(dev, K.fda_apply_u8, src, delta, b, _tables(h, dev)[1], _tables(w, dev)[1], n, h, w, bmax, cols,
+                out if u8 else None, None if u8 else out, counts)
     return out, counts
 
 
@@ -285,7 +248,7 @@ class AmplitudeBank:
         if self.size is None:
             _check_bmax("AmplitudeBank", self.bmax, h, w)
             k = 2 * self.bmax + 1
-            self._amps = torch.empty((self.capacity, 3, k, k), dtype=torch.float64, device=_device())
+            self._amps = torch.empty((self.capacity, 3, k, k), dtype=torch.float64, device=A.current_gpu())
             self.size = (h, w)
         elif self.size != (h, w):
             raise ValueError(f"AmplitudeBank.add: the bank holds {self.size[0]} x {self.size[1]} frames, got {h} x {w}")
@@ -331,9 +294,7 @@ class StyledLoader:
     def __init__(self, source_loader, target, beta=(0.01, 0.05), lam=(1.0, 1.0), p=1.0, generator=None):
         self.beta = _check_pair("beta", beta, 0.0, 0.5)
         self.lam = _check_pair("lam", lam, 0.0, 1.0)
-        if not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
-            raise ValueError(f"p must be a probability, got {p}")
-        self.p = float(p)
+        self.p = _check_p(p)
         self.source_loader, self.target, self.generator = source_loader, target, generator
         self.last_bands = self.last_counts = None
 
@@ -343,7 +304,7 @@ class StyledLoader:
         return min(len(self.source_loader), len(self.target))
 
     def __iter__(self):
-        dev = _device()
+        dev = A.current_gpu()
         bank = self.target if isinstance(self.target, AmplitudeBank) else None
         pairs = ((s, None) for s in self.source_loader) if bank is not None else zip(self.source_loader, self.target)
         for source, target in pairs:

@@ -20,6 +20,7 @@ Inputs may be host or device tensors or numpy arrays (copied once, asynchronousl
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import kernels as K
 from .config import Config
@@ -31,9 +32,7 @@ def _size(who, size):
         h, w = size
     except (TypeError, ValueError):
         raise ValueError(f"{who}: size must be (height, width), got {size!r}") from None
-    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (h, w)) or h < 1 or w < 1:
-        raise ValueError(f"{who}: size must be two integers >= 1 as (height, width), got {size!r}")
-    return int(h), int(w)
+    return A.int_in(who, "size (height, width)", h, 1), A.int_in(who, "size (height, width)", w, 1)
 
 
 def _u8(who, what, x, trailing):
@@ -96,11 +95,11 @@ def resize_frames(images_u8, size, masks_u8=None):
     img = _device(img)
     msk = None if msk is None else _device(msk)
     out = torch.empty((n, h, w, 3), device=img.device, dtype=torch.uint8)
-    K.resize_area_u8(img, out)
+    A.on_device(img.device, K.resize_area_u8, img, out)
     out_m = None
     if msk is not None:
         out_m = torch.empty((n, h, w), device=img.device, dtype=torch.uint8)
-        K.resize_nearest_u8(msk, out_m)
+        A.on_device(img.device, K.resize_nearest_u8, msk, out_m)
     return out, out_m
 
 
@@ -112,21 +111,13 @@ def resize_masks(masks_u8, size):
     _lib.require_gpu()
     msk = _device(msk)
     out = torch.empty((msk.shape[0], h, w), device=msk.device, dtype=torch.uint8)
-    K.resize_nearest_u8(msk, out)
+    A.on_device(msk.device, K.resize_nearest_u8, msk, out)
     return out
 
 
-_TABLES = {}
-
-
 def _aa_tables(H, W, h, w, dev):
-    key = (H, W, h, w, dev)
-    t = _TABLES.get(key)
-    if t is None:
-        if len(_TABLES) >= 16:
-            _TABLES.clear()
-        t = _TABLES[key] = tuple(tuple(torch.from_numpy(a).to(dev) for a in aa_table(L, l)) for L, l in ((H, h), (W, w)))
-    return t
+    """((start, weights) of the rows, (start, weights) of the columns) on the device, kept (``_args.const_table``)."""
+    return tuple(A.const_table("ingest", (L, l), lambda: aa_table(L, l), dev) for L, l in ((H, h), (W, w)))
 
 
 def resize_normalized(images_u8, size, dtype=torch.float32, mean=IMAGENET_MEAN, std=IMAGENET_STD, max_pixel_value=255.0):
@@ -147,7 +138,7 @@ def resize_normalized(images_u8, size, dtype=torch.float32, mean=IMAGENET_MEAN, 
     cpad = 8 if dtype == torch.bfloat16 else 4
     out = torch.empty((n, h, w, cpad), device=img.device, dtype=dtype)
     m255, r255 = normalize_constants(mean, std, max_pixel_value)
-    K.resize_aa_u8(img, ty, tx, m255, r255, out)
+    A.on_device(img.device, K.resize_aa_u8, img, ty, tx, m255, r255, out)
     return _model_input(out)
 
 
@@ -155,18 +146,15 @@ def frame_for_model(model, frame_u8, size=None):
     """One decoded frame ``[H,W,3]`` uint8 of any size -> ``model``'s input at ``size`` (default ``Config.IMAGE_SIZE``) in the
     model's compute dtype, through ``resize_normalized``: the ``Resize`` + ``Normalize`` tail of the reference's ``predict_mask``.
     The input is made on the model's own device."""
-    p = next(iter(model.parameters()), None)
-    if p is None or p.device.type != "cuda":
-        raise RuntimeError("frame_for_model: the model must live on the GPU (no CPU path in this build)")
+    dev = A.model_device(model, "frame_for_model")
     if isinstance(frame_u8, np.ndarray) and frame_u8.ndim == 3:
         frame_u8 = frame_u8[None]
     elif torch.is_tensor(frame_u8) and frame_u8.dim() == 3:
         frame_u8 = frame_u8.unsqueeze(0)
     else:
         raise ValueError(f"frame_for_model: the frame must be uint8 [H,W,3], got {tuple(getattr(frame_u8, 'shape', ()))}")
-    with torch.cuda.device(p.device):
-        return resize_normalized(frame_u8, tuple(Config.IMAGE_SIZE) if size is None else size,
-                                 dtype=getattr(model, "compute_dtype", torch.float32))
+    return A.on_device(dev, resize_normalized, frame_u8, tuple(Config.IMAGE_SIZE) if size is None else size,
+                       getattr(model, "compute_dtype", torch.float32))
 
 
 class ResizingLoader:
@@ -210,9 +198,7 @@ class ClassBalance:
     any size as they are decoded, then ask for the statistics -- one read-back of the ``[N,256]`` table."""
 
     def __init__(self, num_samples):
-        if not isinstance(num_samples, (int, np.integer)) or num_samples < 1:
-            raise ValueError(f"ClassBalance: num_samples must be an integer >= 1, got {num_samples!r}")
-        self.num_samples = int(num_samples)
+        self.num_samples = A.int_in("ClassBalance", "num_samples", num_samples, 1)
         self._seen = np.zeros(self.num_samples, dtype=bool)
         self._hist = None                                      # int64 [N,256] on the device, made by the first update
         self._host = None                                      # its read-back, dropped by every update
@@ -231,7 +217,7 @@ class ClassBalance:
         if self._hist is None:
             self._hist = torch.zeros((self.num_samples, 256), device=msk.device, dtype=torch.int64)
         rows = torch.zeros((idx.size, 256), device=msk.device, dtype=torch.int64)
-        K.mask_hist_u8(msk, rows)
+        A.on_device(msk.device, K.mask_hist_u8, msk, rows)
         self._hist.index_add_(0, torch.from_numpy(idx).to(msk.device), rows)
         self._seen[idx] = True
         self._host = None

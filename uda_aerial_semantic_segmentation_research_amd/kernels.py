@@ -216,6 +216,16 @@ def fda_apply_u8(src, delta, b, tw_h, tw_w, n, h, w, bmax, cols_ws, out, field, 
     check(ops.udaseg_fda_apply_u8(src, delta, b, tw_h, tw_w, n, h, w, bmax, cols_ws, out, field, counts, st), "fda_apply_u8")
 
 
+def _ignore_args(ignore_index):
+    """ignore_index (None or any int64) -> (has_ignore, ignore_index) as the C ABI takes them."""
+    return (0, 0) if ignore_index is None else (1, int(ignore_index))
+
+
+def _label_args(labels):
+    """A label map [n,h,w] (uint8 or int64) -> (labels_i64, n, h, w) as the C ABI takes them."""
+    return (int(getattr(labels, "dtype", None) == torch.int64),) + tuple(getattr(labels, "shape", ()))
+
+
 RENDER_BASE_NONE, RENDER_BASE_U8, RENDER_BASE_F32, RENDER_BASE_BF16 = 0, 1, 2, 3
 _RENDER_HOST = {}
 
@@ -235,16 +245,13 @@ def render_u8(labels, truth, base, table, n, h, w, classes, ignore_index, alpha,
         host = _RENDER_HOST[key] = ((_lib.C.c_int32 * 4)(*[int(v) for v in key[0]]),
                                     None if denorm is None else (_lib.C.c_float * 6)(*[float(v) for v in key[1]]))
     a4, d6 = host
-    check(ops.udaseg_render_u8(labels, truth, int(getattr(labels, "dtype", None) == torch.int64), base, kind, table, n, h, w, classes,
-                               int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), a4, d6, outline, out,
-                               counts, agreement, st), "render_u8")
+    check(ops.udaseg_render_u8(labels, truth, _label_args(labels)[0], base, kind, table, n, h, w, classes, *_ignore_args(ignore_index),
+                               a4, d6, outline, out, counts, agreement, st), "render_u8")
 
 
 # ---- label boundary distances (boundary.py; csrc/boundary.hip).  labels: uint8 or int64 [n,h,w]; ignore_index: an int or None
 def _boundary_head(labels, radius, ignore_index):
-    n, h, w = labels.shape
-    return (int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(radius), int(ignore_index is not None),
-            0 if ignore_index is None else int(ignore_index))
+    return _label_args(labels) + (int(radius),) + _ignore_args(ignore_index)
 
 
 def boundary_tile(radius, stats=False):
@@ -286,26 +293,22 @@ def regions_tile():
 
 def regions_label(labels, connectivity, ignore_index, ids, area, st=None):
     """ids [n,h,w] int32 = the first raster index of every pixel's component (-1: void); area [n,h,w] int32 or None = its size."""
-    n, h, w = labels.shape
-    check(ops.udaseg_regions_label(labels, int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(connectivity),
-                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), ids, area, st),
+    check(ops.udaseg_regions_label(labels, *_label_args(labels), int(connectivity), *_ignore_args(ignore_index), ids, area, st),
           "regions_label")
 
 
 def regions_sieve(labels, ids, area, ignore_index, min_area, void_label, out, counts, st=None):
     """out [n,h,w] uint8 = labels with void_label on the components smaller than min_area[label] (int32 [256] on the device);
     counts [n,3] int64 or None += pixels voided, components removed, components kept."""
-    n, h, w = labels.shape
-    check(ops.udaseg_regions_sieve(labels, int(getattr(labels, "dtype", None) == torch.int64), ids, area, n, h, w,
-                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), min_area,
-                                   int(void_label), out, counts, st), "regions_sieve")
+    i64, n, h, w = _label_args(labels)
+    check(ops.udaseg_regions_sieve(labels, i64, ids, area, n, h, w, *_ignore_args(ignore_index), min_area, int(void_label), out,
+                                   counts, st), "regions_sieve")
 
 
 def regions_stats(labels, ids, area, classes, ignore_index, stats, st=None):
     """stats [classes,34] int64 += components, pixels and the log2 area histogram [32] of every class."""
-    n, h, w = labels.shape
-    check(ops.udaseg_regions_stats(labels, int(getattr(labels, "dtype", None) == torch.int64), ids, area, n, h, w, int(classes),
-                                   int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), stats, st),
+    i64, n, h, w = _label_args(labels)
+    check(ops.udaseg_regions_stats(labels, i64, ids, area, n, h, w, int(classes), *_ignore_args(ignore_index), stats, st),
           "regions_stats")
 
 
@@ -333,9 +336,7 @@ def crf_step(logp, q, valid, frames, classes, ldq, radius, dilation, s_alpha, s_
 
 # ---- window votes and active label acquisition (active.py; csrc/window.hip).  labels: uint8 or int64 [n,h,w]
 def _window_head(labels, radius, classes, ignore_index):
-    n, h, w = labels.shape
-    return (int(getattr(labels, "dtype", None) == torch.int64), n, h, w, int(radius), int(classes), int(ignore_index is not None),
-            0 if ignore_index is None else int(ignore_index))
+    return _label_args(labels) + (int(radius), int(classes)) + _ignore_args(ignore_index)
 
 
 def window_tile(radius):
@@ -910,11 +911,6 @@ def ce_fwd_bwd(logits_base, target, pixels, classes, ldc, partials, loss, dlogit
 def scale_unless_one(x, g, x2=None, st=None):
     """x *= g (and x2 *= g) unless the device scalar ``g`` is exactly 1: then the launch returns at once."""
     check(ops.udaseg_scale_unless_one(x, x.numel(), x2, 0 if x2 is None else x2.numel(), g, st), "scale_unless_one")
-
-
-def _ignore_args(ignore_index):
-    """ignore_index (None or any int64) -> (has_ignore, ignore_index) as the C ABI takes them."""
-    return (0, 0) if ignore_index is None else (1, int(ignore_index))
 
 
 def ce_target_stats(target, weight, pixels, classes, ignore_index, partials, denom, stats, st=None):

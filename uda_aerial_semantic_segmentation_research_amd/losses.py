@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from ._args import padded_nhwc
 from ._lib import load as _load
-from .engine import ceil4
 
 
 # the training step's loss makes its gradient in the forward pass (one read of the logits instead of two); UDASEG_FUSE_CE=0: two passes
@@ -31,23 +31,11 @@ FUSE_CE_BACKWARD = os.environ.get("UDASEG_FUSE_CE", "1") != "0"
 COLSUM_SIDE_TABLE = {}
 
 
-def _padded_nhwc(logits):
-    """[N,C,H,W] logits -> (tensor whose storage is the padded NHWC buffer [N,H,W,ldc], ldc).  Zero-copy when the
-    logits come from ``Unet.forward``; otherwise one layout kernel."""
-    n, c, h, w = logits.shape
-    ldc = ceil4(c)
-    if (logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(3) == ldc and logits.stride(2) == ldc * w
-            and logits.stride(0) == ldc * w * h
-            and logits.untyped_storage().nbytes() - 4 * logits.storage_offset() >= 4 * n * h * w * ldc):
-        return logits.as_strided((n, h, w, ldc), (h * w * ldc, w * ldc, ldc, 1), logits.storage_offset()), ldc
-    return K.nchw_to_nhwc(logits.float().contiguous(), ldc), ldc
-
-
 class _CrossEntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         tgt = target.contiguous()
         pixels = n * h * w
         dev = logits.device
@@ -114,7 +102,7 @@ class _CrossEntropyOptFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, reduction, eps, stats):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         tgt = target.contiguous()
         pixels = n * h * w
         dev = logits.device
@@ -263,7 +251,7 @@ class _OhemCrossEntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, mean, thresh, min_kept, fraction, ws, thr, keep):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         tgt = target.contiguous()
         pixels = n * h * w
         dev = logits.device
@@ -432,7 +420,7 @@ class _LovaszSoftmaxFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index, images, bins, all_classes, ce_weight, tables, counters, present, slack):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         tgt = target.contiguous()
         pixels = n * h * w
         dev = logits.device
@@ -673,7 +661,7 @@ class _SegLossFunction(torch.autograd.Function):
     def forward(ctx, logits, target, class_weights, alpha, gamma, mean, smooth, focal_w, dice_w, dice_eps=1e-7,
                 dice_pooled=False, ignore_index=None):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         dev = logits.device
         loss = torch.zeros((), device=dev, dtype=torch.float32)
         coef = None
@@ -782,8 +770,8 @@ class _ConsistencyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred1, pred2, temperature):
         n, c, h, w = pred1.shape
-        z1, ldc = _padded_nhwc(pred1.detach())
-        z2, _ = _padded_nhwc(pred2.detach())
+        z1, ldc = padded_nhwc(pred1.detach())
+        z2, _ = padded_nhwc(pred2.detach())
         dev = pred1.device
         parts = torch.empty(K.seg_partials(), device=dev, dtype=torch.float64)
         loss = torch.empty((), device=dev, dtype=torch.float32)
@@ -834,7 +822,7 @@ class _EntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, kind):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         dev = logits.device
         loss = torch.empty((), device=dev, dtype=torch.float32)
         parts = torch.empty(K.seg_partials(), device=dev, dtype=torch.float64)
@@ -889,7 +877,7 @@ class _SoftCrossEntropyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, tbuf, ldt, probs, wpx, wimg, cfg, stats):
         n, c, h, w = logits.shape
-        buf, ldc = _padded_nhwc(logits.detach())
+        buf, ldc = padded_nhwc(logits.detach())
         dev = logits.device
         denom = None
         if cfg["reduction"] == 'weighted_mean':
@@ -1000,7 +988,7 @@ class SoftCrossEntropyLoss(nn.Module):
         for name, t in (("teacher", teacher), ("pixel_weight", pixel_weight), ("image_weight", image_weight)):
             if t is not None and t.device != logits.device:
                 raise RuntimeError(f"SoftCrossEntropyLoss: {name} must live on the logits' GPU (no CPU path in this build)")
-        tbuf, ldt = _padded_nhwc(teacher)
+        tbuf, ldt = padded_nhwc(teacher)
         dev = logits.device
         wpx = None if pixel_weight is None else pixel_weight.to(torch.float32).contiguous()
         wimg = None if image_weight is None else image_weight.to(torch.float32).contiguous()

@@ -64,16 +64,12 @@ class DomainAdaptationMetrics:
 def confusion_matrix(outputs, masks, num_classes):
     """[num_classes, num_classes] int64 confusion matrix (rows = target, cols = argmax prediction) on the device:
     one HIP kernel (per-pixel argmax + LDS histogram), no intermediate argmax tensor."""
-    from . import kernels as K
-    from .losses import _padded_nhwc
-    if outputs.device.type != "cuda":
-        raise RuntimeError("confusion_matrix: logits must live on the GPU (no CPU path in this build)")
-    buf, ldc = _padded_nhwc(outputs.detach())
-    cm = torch.zeros(num_classes * num_classes, dtype=torch.int64, device=outputs.device)
-    tgt = masks.reshape(-1)
-    if tgt.dtype != torch.int64:
-        tgt = tgt.long()
-    K.argmax_confusion(buf, tgt.contiguous(), tgt.numel(), num_classes, ldc, cm)
+    from . import _args as A, kernels as K
+    dev = A.same_gpu("confusion_matrix", logits=outputs)
+    buf, ldc = A.padded_nhwc(outputs.detach())
+    cm = torch.zeros(num_classes * num_classes, dtype=torch.int64, device=dev)
+    tgt = A.flat_targets("confusion_matrix", masks, masks.numel())
+    A.on_device(dev, K.argmax_confusion, buf, tgt, tgt.numel(), num_classes, ldc, cm)
     return cm.view(num_classes, num_classes)
 
 

@@ -48,31 +48,26 @@ import math
 import numpy as np
 import torch
 
-from .pseudo import _check_classes, _check_void
+from . import _args as A
+from . import kernels as K
 
 MODES = ("class", "box", "both")
 
 
+def _check_classes(num_classes):
+    return A.int_in("mix", "num_classes", num_classes, 1, 32)
+
+
+def _check_void(void, num_classes):
+    return A.int_in("mix", "void", void, num_classes, 255)                # above the classes, inside uint8
+
+
 def _check_min_pixels(min_pixels):
-    if not isinstance(min_pixels, (int, np.integer)) or min_pixels < 1:
-        raise ValueError(f"min_pixels must be an integer >= 1, got {min_pixels}")
-    return int(min_pixels)
+    return A.int_in("mix", "min_pixels", min_pixels, 1)
 
 
 def _check_share(share):
-    try:
-        lo, hi = (float(v) for v in share)
-    except (TypeError, ValueError):
-        raise ValueError(f"share must be a pair (lo, hi) with 0 < lo <= hi <= 1, got {share}") from None
-    if not 0.0 < lo <= hi <= 1.0:
-        raise ValueError(f"share must be a pair (lo, hi) with 0 < lo <= hi <= 1, got {share}")
-    return lo, hi
-
-
-def _check_mode(mode):
-    if mode not in MODES:
-        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-    return mode
+    return A.pair("mix", "share", share, 0.0, 1.0, lo_open=True)
 
 
 def _keys_u32(keys, n):
@@ -137,8 +132,7 @@ def draw_boxes(n, h, w, generator=None, share=(0.25, 0.5)):
     aspect log-uniform in ``[1/2, 2]`` (the module docstring has the rule).  Needs no GPU."""
     lo, hi = _check_share(share)
     for name, v in (("n", n), ("h", h), ("w", w)):
-        if not isinstance(v, (int, np.integer)) or v < 1:
-            raise ValueError(f"{name} must be an integer >= 1, got {v}")
+        A.int_in("draw_boxes", name, v, 1)
     u = torch.rand(n, 4, generator=generator, dtype=torch.float64).numpy()
     a = lo + u[:, 0] * (hi - lo)
     r = np.exp((2.0 * u[:, 1] - 1.0) * math.log(2.0))
@@ -155,12 +149,6 @@ def draw_keys(n, generator=None):
     return torch.from_numpy(keys.astype(np.uint32).view(np.int32))
 
 
-def _device():
-    from . import _lib
-    _lib.require_gpu()
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _u8(who, name, t, shape=None, dims=None):
     if not torch.is_tensor(t) or t.dtype != torch.uint8:
         raise ValueError(f"{who}: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
@@ -169,13 +157,6 @@ def _u8(who, name, t, shape=None, dims=None):
     if dims is not None and t.dim() != dims:
         raise ValueError(f"{who}: {name} must have {dims} dimensions, got shape {list(t.shape)}")
     return t
-
-
-def _frames_shape(who, name, t):
-    _u8(who, name, t, dims=4)
-    if t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError(f"{who}: {name} must be [N,H,W,3] with N, H, W >= 1, got {list(t.shape)}")
-    return tuple(int(v) for v in t.shape[:3])
 
 
 def _i32(who, name, t, shape):
@@ -189,7 +170,6 @@ def select_classes(src_masks_u8, num_classes, generator=None, min_pixels=1, keys
     """int32 ``[N]`` on the device: the classes to paste of every uint8 ``[N,H,W]`` source mask.  Allocates a zeroed histogram and
     enqueues ``mask_hist_u8`` and the selection kernel; no synchronisation.  ``keys`` (``[N, 2]`` integers) override the draw from
     ``generator`` (a CPU ``torch.Generator``)."""
-    from . import kernels as K
     classes, min_pixels = _check_classes(num_classes), _check_min_pixels(min_pixels)
     _u8("select_classes", "src_masks", src_masks_u8, dims=3)
     n = int(src_masks_u8.shape[0])
@@ -199,13 +179,13 @@ def select_classes(src_masks_u8, num_classes, generator=None, min_pixels=1, keys
         keys = draw_keys(n, generator)
     else:
         keys = torch.from_numpy(_keys_u32(keys, n).view(np.int32))
-    dev = _device()
+    dev = A.current_gpu()
     keys = keys.to(dev, non_blocking=True)
     masks = src_masks_u8.to(dev, non_blocking=True).contiguous()
     hist = torch.zeros((n, 256), dtype=torch.int64, device=dev)
     sel = torch.empty(n, dtype=torch.int32, device=dev)
-    K.mask_hist_u8(masks, hist)
-    K.classmix_select(hist, n, classes, min_pixels, keys, sel)
+    A.on_device(dev, K.mask_hist_u8, masks, hist)
+    A.on_device(dev, K.classmix_select, hist, n, classes, min_pixels, keys, sel)
     return sel
 
 
@@ -215,13 +195,12 @@ def class_mix(src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes=None, num
     elsewhere.  ``tgt_masks`` may be None: every pixel that is not pasted is labelled ``void``.  Host tensors are moved with one
     asynchronous copy each.  ``out``: a ``(frames, masks)`` pair of contiguous device tensors to write into (rows of a larger
     batch); ``counts``: a device int64 ``[N,3]`` table to accumulate into, None for a fresh zeroed one, False to keep none."""
-    from . import kernels as K
     who = "class_mix"
     if num_classes is None:
         raise ValueError("class_mix: num_classes is required")
     classes = _check_classes(num_classes)
     void = _check_void(void, classes)
-    n, h, w = _frames_shape(who, "src_frames", src_frames)
+    n, h, w = A.frames_u8(who, src_frames, name="src_frames")
     _u8(who, "tgt_frames", tgt_frames, (n, h, w, 3))
     _u8(who, "src_masks", src_masks, (n, h, w))
     if tgt_masks is not None:
@@ -235,7 +214,7 @@ def class_mix(src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes=None, num
                 raise ValueError(f"class_mix: boxes must satisfy 0 <= y0 <= y1 <= {h} and 0 <= x0 <= x1 <= {w}, got {b.tolist()}")
     if n * h * w >= 1 << 31:
         raise ValueError(f"class_mix: N*H*W must stay below 2^31, got {n * h * w}")
-    dev = _device()
+    dev = A.current_gpu()
     mv = lambda t: None if t is None else t.to(dev, non_blocking=True).contiguous()      # noqa: E731
     src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes = (mv(t) for t in (src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes))
     if out is None:
@@ -254,9 +233,9 @@ def class_mix(src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes=None, num
         counts = torch.zeros((n, 3), dtype=torch.int64, device=dev)
     elif counts is False:
         counts = None
-    elif not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 3):
-        raise ValueError(f"class_mix: counts must be an int64 [{n}, 3] tensor, None or False")
-    K.classmix_u8(src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes, n, h, w, classes, void, frames, masks, counts)
+    else:
+        A.counts_tensor(who, "counts", counts, (n, 3), dev)
+    A.on_device(dev, K.classmix_u8, src_frames, src_masks, tgt_frames, tgt_masks, sel, boxes, n, h, w, classes, void, frames, masks, counts)
     return frames, masks, counts
 
 
@@ -279,7 +258,7 @@ class MixedLoader:
         self.void = _check_void(void, self.num_classes)
         self.min_pixels = _check_min_pixels(min_pixels)
         self.share = _check_share(share)
-        self.mode = _check_mode(mode)
+        self.mode = A.choice("MixedLoader", "mode", mode, MODES)
         self.source_loader, self.target_loader = source_loader, target_loader
         self.generator, self.include_source = generator, bool(include_source)
         self.last_selection = self.last_counts = None
@@ -288,7 +267,7 @@ class MixedLoader:
         return min(len(self.source_loader), len(self.target_loader))
 
     def __iter__(self):
-        dev = _device()
+        dev = A.current_gpu()
         for source, target in zip(self.source_loader, self.target_loader):
             if torch.is_tensor(source) or len(source) != 2:
                 raise ValueError("MixedLoader: a source batch must be a (frames, masks) pair")
@@ -297,8 +276,8 @@ class MixedLoader:
                 t_frames, t_masks = target, None
             else:
                 t_frames, t_masks = (target[0], target[1]) if len(target) > 1 else (target[0], None)
-            ns, h, w = _frames_shape("MixedLoader", "source frames", s_frames)
-            nt, ht, wt = _frames_shape("MixedLoader", "target frames", t_frames)
+            ns, h, w = A.frames_u8("MixedLoader", s_frames, name="source frames")
+            nt, ht, wt = A.frames_u8("MixedLoader", t_frames, name="target frames")
             if (h, w) != (ht, wt):
                 raise ValueError(f"MixedLoader: source frames are {h} x {w}, target frames {ht} x {wt}")
             _u8("MixedLoader", "source masks", s_masks, (ns, h, w))

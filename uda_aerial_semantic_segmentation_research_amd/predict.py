@@ -18,12 +18,12 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib
 from . import kernels as K
 from .config import Config
 from .data import FLIP_COLS, FLIP_ROWS, IMAGENET_MEAN, IMAGENET_STD, TRANSPOSE, normalize_constants, prepare_batch
 from .engine import ceil4, mark_padded_input
-from .losses import _padded_nhwc
 
 MAX_CLASSES = 32                                   # as the loss kernels: one pixel's class row lives in registers
 VIEWS = {None: (0,), "flips": (0, 2, 4, 6), "d4": tuple(range(8))}     # D4 codes per TTA mode (data.py's convention)
@@ -95,28 +95,6 @@ def view_mask(codes):
     return sum(1 << c for c in codes)
 
 
-def _model_device(model, what):
-    p = next(iter(model.parameters()), None)
-    if p is None or p.device.type != "cuda":
-        raise RuntimeError(f"{what}: the model must live on the GPU (no CPU path in this build)")
-    classes = getattr(model, "classes", None)
-    if classes is not None and not 1 <= classes <= MAX_CLASSES:
-        raise ValueError(f"{what}: classes must lie in 1..{MAX_CLASSES}, got {classes}")
-    return p.device
-
-
-def _logits_nhwc(logits):
-    """[N,C,H,W] fp32 logits -> (padded NHWC buffer [N,H,W,ldc], ldc): zero-copy for ``Unet.forward``'s output (whose ldc is
-    the head's padded width), one layout kernel otherwise."""
-    n, c, h, w = logits.shape
-    ldc = logits.stride(3)
-    if (logits.dtype == torch.float32 and logits.stride(1) == 1 and ldc % 4 == 0 and ldc >= c and logits.stride(2) == ldc * w
-            and logits.stride(0) == ldc * w * h
-            and logits.untyped_storage().nbytes() - 4 * logits.storage_offset() >= 4 * n * h * w * ldc):
-        return logits.as_strided((n, h, w, ldc), (h * w * ldc, w * ldc, ldc, 1), logits.storage_offset()), ldc
-    return _padded_nhwc(logits)
-
-
 def predict_batch(model, images, device="cuda"):
     """Reference ``predict.py:113-130``: ``model.eval()`` (left so), then under ``no_grad`` the argmax over classes of
     ``model(images)`` -> numpy int64 ``[B,H,W]``, ties to the first maximal index as ``torch.argmax``.  ``images`` is any
@@ -126,12 +104,12 @@ def predict_batch(model, images, device="cuda"):
     if dev.type != "cuda":
         raise RuntimeError("predict_batch: device must be a GPU (no CPU path in this build)")
     _lib.require_gpu()
-    _model_device(model, "predict_batch")
+    A.model_device(model, "predict_batch", MAX_CLASSES)
     model.eval()
     with torch.no_grad():
         logits = model(images.to(dev))
         n, c, h, w = logits.shape
-        buf, ldc = _logits_nhwc(logits)
+        buf, ldc = A.logits_nhwc(logits)
         labels = torch.empty((n, h, w), dtype=torch.int64, device=buf.device)
         K.predict_finish(buf, None, n * h * w, c, ldc, labels)
         return labels.cpu().numpy()
@@ -155,7 +133,7 @@ def predict_mask(model, img, device=None, resize=False):
     if dev.type != "cuda":
         raise RuntimeError("predict_mask: device must be a GPU (no CPU path in this build)")
     _lib.require_gpu()
-    _model_device(model, "predict_mask")
+    A.model_device(model, "predict_mask", MAX_CLASSES)
     model.eval()
     try:
         from PIL import Image
@@ -183,7 +161,7 @@ def predict_mask(model, img, device=None, resize=False):
     with torch.no_grad():
         logits = model(x)
         n, c, h, w = logits.shape
-        buf, ldc = _logits_nhwc(logits)
+        buf, ldc = A.logits_nhwc(logits)
         out = torch.empty((n, c, h, w), dtype=torch.float32, device=buf.device)
         K.predict_threshold(buf, n, h * w, c, ldc, out)
     return out.squeeze().cpu().numpy()
@@ -224,7 +202,7 @@ def predict_large(model, image, tile=512, overlap=0.25, batch_size=8, tta=None, 
     if tta == "d4" and g.th != g.tw:
         raise ValueError(f"tta='d4' needs square tiles, got {g.th}x{g.tw} (tiles are clamped to ceil32 of each frame side)")
     _lib.require_gpu()
-    dev = _model_device(model, "predict_large")
+    dev = A.model_device(model, "predict_large", MAX_CLASSES)
     classes = model.classes
     nv, mask = len(codes), view_mask(codes)
     per_fwd = max(1, int(batch_size) // nv)
@@ -258,7 +236,7 @@ def predict_large(model, image, tile=512, overlap=0.25, batch_size=8, tta=None, 
             mark("forward")
             logits = model(xb.permute(0, 3, 1, 2)[:, :3])
             mark("blend")
-            lbuf, ldc = _logits_nhwc(logits)
+            lbuf, ldc = A.logits_nhwc(logits)
             K.predict_blend(lbuf, ldc, args, first, tiles, mask, classes, win_y, win_x, acc, ldp, wsum)
             mark("end")
         labels = torch.empty((h, w), dtype=torch.int64, device=dev)

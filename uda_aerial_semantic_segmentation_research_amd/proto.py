@@ -45,44 +45,31 @@ Use, in place of ``teacher.OnlineLabeler`` in the mean-teacher recipe::
 import numpy as np
 import torch
 
+from . import _args as A
+from . import kernels as K
 from . import pseudo, teacher
-from .pseudo import _check_classes
 
 DECODER_DIM = 16
 
 
 def _check_dim(dim):
-    if not isinstance(dim, (int, np.integer)) or not 4 <= dim <= 64 or dim % 4:
-        raise ValueError(f"dim must be a multiple of 4 in 4..64, got {dim}")
+    if A.int_in("proto", "dim", dim, 4, 64) % 4:
+        raise ValueError(f"proto: dim must be a multiple of 4, got {dim}")
     return int(dim)
 
 
 def _check_momentum(momentum):
-    momentum = float(momentum)
-    if not 0.0 <= momentum <= 1.0:
-        raise ValueError(f"momentum must lie in [0, 1], got {momentum}")
-    return momentum
+    return A.number("proto", "momentum", momentum, 0.0, 1.0)
 
 
 def _check_min_pixels(min_pixels):
-    if not isinstance(min_pixels, (int, np.integer)) or min_pixels < 1:
-        raise ValueError(f"min_pixels must be a positive integer, got {min_pixels}")
-    return int(min_pixels)
+    return A.int_in("proto", "min_pixels", min_pixels, 1)
 
 
 def _check_tau(tau, tau_scale):
     """-> (fixed tau or None for "auto", tau_scale)."""
-    tau_scale = float(tau_scale)
-    if not (np.isfinite(tau_scale) and tau_scale > 0.0):
-        raise ValueError(f"tau_scale must be a positive finite number, got {tau_scale}")
-    if isinstance(tau, str):
-        if tau != "auto":
-            raise ValueError(f"tau must be 'auto' or a positive float, got {tau!r}")
-        return None, tau_scale
-    tau = float(tau)
-    if not (np.isfinite(tau) and tau > 0.0):
-        raise ValueError(f"tau must be 'auto' or a positive float, got {tau}")
-    return tau, tau_scale
+    tau_scale = A.number("proto", "tau_scale", tau_scale, 0.0, lo_open=True)
+    return (None if tau == "auto" else A.number("proto", "tau ('auto' or a float)", tau, 0.0, lo_open=True)), tau_scale
 
 
 # ---------------------------------------------------------------------------------------------------------- host mirrors
@@ -269,19 +256,11 @@ def contrast_mirror(features, target, proto, seen, inv_tau, pixel_weight=None, i
 def _nhwc(who, what, x, channels):
     """[N,channels,H,W] device tensor -> (padded NHWC fp32 buffer, row stride, n, h, w): zero-copy for the views ``forward_parts``
     and ``rectify`` hand out, one layout kernel otherwise (bf16 is widened first)."""
-    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != channels:
-        raise ValueError(f"{who}: {what} must be a [N,{channels},H,W] tensor, got {tuple(getattr(x, 'shape', ()))}")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"{who}: {what} must be float32 or bfloat16, got {x.dtype}")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{who}: {what} must live on the GPU (no CPU path in this build)")
-    from .losses import _padded_nhwc
-    n, _, h, w = x.shape
-    buf, ld = _padded_nhwc(x.detach())
+    buf, ld, n, _, h, w = A.scores_nchw(who, x, channels, what, max_classes=channels)
     return buf, ld, n, h, w
 
 
-class PrototypeBank:
+class PrototypeBank(A.DeviceState):
     """One prototype per class in a ``dim``-channel feature space, with its state on the device (module docstring):
     ``sums [C, D]``, ``sq [C]`` float64 and ``counts [C + 2]`` int64 (the accumulators of the batch), ``prototypes [C, D]``,
     ``spread [C]`` float64, ``seen [C]`` int32, ``last_counts [C + 2]`` int64 (the counts the last update used: per class, labels
@@ -289,34 +268,22 @@ class PrototypeBank:
     enqueue one kernel each and do not synchronise."""
 
     def __init__(self, num_classes, dim=DECODER_DIM, momentum=0.999, min_pixels=16, tau="auto", tau_scale=1.0, device=None):
-        self.num_classes, self.dim = _check_classes(num_classes), _check_dim(dim)
+        self.num_classes, self.dim = A.int_in("PrototypeBank", "num_classes", num_classes, 1, 32), _check_dim(dim)
         self.momentum, self.min_pixels = _check_momentum(momentum), _check_min_pixels(min_pixels)
         self.tau, self.tau_scale = _check_tau(tau, tau_scale)
         self.device = torch.device(device) if device is not None else None
         self.sums = None
         self.updates = 0
 
-    def _ensure(self, device):
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self.sums is None:
-            if device.type != "cuda":
-                raise RuntimeError("PrototypeBank: tensors must live on the GPU (no CPU path in this build)")
-            C, D = self.num_classes, self.dim
-            z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=device)
-            self.device = device
-            self.sums, self.sq, self.counts = z(C, D), z(C), z(C + 2, dtype=torch.int64)
-            self.prototypes, self.spread, self.seen = z(C, D), z(C), z(C, dtype=torch.int32)
-            self.last_counts = z(C + 2, dtype=torch.int64)
-            self.inv_tau = torch.full((1,), 0.0 if self.tau is None else 1.0 / self.tau, dtype=torch.float32, device=device)
-            self._before = z(C, D)              # the prototypes before the last update (report's `moved`)
-            self._seen_before = z(C, dtype=torch.int32)
-        elif device != self.device:
-            raise ValueError(f"PrototypeBank: the bank lives on {self.device}, the tensors on {device}")
-        return self
-
-    def _need_state(self):
-        return self._ensure(self.device or torch.device("cuda"))
+    def _allocate(self, device):
+        C, D = self.num_classes, self.dim
+        z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=device)
+        self.sums, self.sq, self.counts = z(C, D), z(C), z(C + 2, dtype=torch.int64)
+        self.prototypes, self.spread, self.seen = z(C, D), z(C), z(C, dtype=torch.int32)
+        self.last_counts = z(C + 2, dtype=torch.int64)
+        self.inv_tau = torch.full((1,), 0.0 if self.tau is None else 1.0 / self.tau, dtype=torch.float32, device=device)
+        self._before = z(C, D)              # the prototypes before the last update (report's `moved`)
+        self._seen_before = z(C, dtype=torch.int32)
 
     def reset(self):
         """Forget everything: accumulators, prototypes, seen flags; a fixed temperature stays."""
@@ -332,27 +299,27 @@ class PrototypeBank:
     def accumulate(self, features, labels_u8):
         """Adds ``[N,D,H,W]`` features (fp32 or bf16, as ``forward_parts`` yields them) under uint8 ``[N,H,W]`` labels to the
         accumulators.  One kernel (plus one layout kernel for a tensor that is not the padded NHWC view)."""
-        from . import kernels as K
-        buf, ldf, n, h, w = _nhwc("PrototypeBank.accumulate", "features", features, self.dim)
+        who = "PrototypeBank.accumulate"
+        n, _, h, w = A.scores_shape(who, features, self.dim, "features", self.dim)
         if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or tuple(labels_u8.shape) != (n, h, w):
-            raise ValueError(f"PrototypeBank.accumulate: labels must be a uint8 [{n},{h},{w}] tensor, got "
+            raise ValueError(f"{who}: labels must be a uint8 [{n},{h},{w}] tensor, got "
                              f"{getattr(labels_u8, 'dtype', None)} {tuple(getattr(labels_u8, 'shape', ()))}")
-        if labels_u8.device != features.device:
-            raise RuntimeError("PrototypeBank.accumulate: labels must live on the features' GPU (no CPU path in this build)")
-        self._ensure(features.device)
-        K.proto_accumulate(buf, ldf, self.dim, labels_u8.contiguous(), n * h * w, self.num_classes, self.sums, self.sq, self.counts)
+        dev = self._ensure(A.same_gpu(who, features=features, labels=labels_u8)).device
+        buf, ldf = A.padded_nhwc(features.detach())
+        A.on_device(dev, K.proto_accumulate, buf, ldf, self.dim, labels_u8.contiguous(), n * h * w, self.num_classes, self.sums,
+                    self.sq, self.counts)
         return self
 
     def update(self, clear=True):
         """Prototypes, spreads, seen flags and (``tau="auto"``) the temperature from the accumulated pixels; the accumulators
         are zeroed by the same kernel unless ``clear`` is False."""
-        from . import kernels as K
-        self._need_state()
+        self._ensure()
         self._before.copy_(self.prototypes)
         self._seen_before.copy_(self.seen)
-        K.proto_update(self.sums, self.sq, self.counts, self.num_classes, self.dim, self.momentum, self.min_pixels,
-                       self.tau_scale if self.tau is None else 0.0, clear, self.prototypes, self.spread, self.seen,
-                       self.last_counts, self.inv_tau)
+        A.on_device(self.device, K.proto_update, self.sums, self.sq, self.counts, self.num_classes, self.dim, self.momentum,
+                    self.min_pixels,
+                    self.tau_scale if self.tau is None else 0.0, clear, self.prototypes, self.spread, self.seen,
+                    self.last_counts, self.inv_tau)
         self.updates += 1
         return self
 
@@ -360,7 +327,7 @@ class PrototypeBank:
         """Plain dict, ONE host read: per class ``seen``, ``spread`` and ``moved`` (the Euclidean distance its prototype moved in
         the last update; 0 for a class first seen by it), ``last_counts`` (per class), ``last_void`` / ``last_nonfinite`` (the other two
         counters of the last update) and ``tau`` (inf while ``inv_tau`` is 0)."""
-        self._need_state()
+        self._ensure()
         C = self.num_classes
         moved = (self.prototypes - self._before).square().sum(dim=1).sqrt() * (self._seen_before != 0)
         packed = torch.cat([self.seen.double(), self.last_counts.double(), self.spread, moved, self.inv_tau.double()]).cpu().numpy()
@@ -373,7 +340,7 @@ class PrototypeBank:
     _STATE = ("sums", "sq", "counts", "prototypes", "spread", "seen", "last_counts", "inv_tau")
 
     def state_dict(self):
-        self._need_state()
+        self._ensure()
         state = {k: getattr(self, k).detach().cpu().clone() for k in self._STATE}
         state.update(num_classes=self.num_classes, dim=self.dim, momentum=self.momentum, min_pixels=self.min_pixels,
                      tau="auto" if self.tau is None else self.tau, tau_scale=self.tau_scale, updates=self.updates)
@@ -386,7 +353,7 @@ class PrototypeBank:
                              f"channels, the bank for {self.num_classes} x {self.dim}")
         momentum, min_pixels = _check_momentum(state["momentum"]), _check_min_pixels(state["min_pixels"])
         tau, tau_scale = _check_tau(state["tau"], state["tau_scale"])
-        self._need_state()
+        self._ensure()
         for k in self._STATE:
             dst = getattr(self, k)
             src = state[k]
@@ -404,19 +371,18 @@ def rectify(features, outputs, bank, probs=False):
     """``[N,C,H,W]`` rectified probabilities (a strided view of a padded NHWC buffer, which ``ConfidenceHistogram.update`` and
     ``pseudo_labels`` read in place with ``probs=True``) of ``[N,D,H,W]`` features and ``[N,C,H,W]`` logits (or probabilities with
     ``probs``) under ``bank``'s prototypes.  One kernel, no host sync."""
-    from . import kernels as K
     if not isinstance(bank, PrototypeBank):
         raise ValueError(f"rectify: bank must be a PrototypeBank, got {type(bank).__name__}")
     C = bank.num_classes
-    fbuf, ldf, n, h, w = _nhwc("rectify", "features", features, bank.dim)
-    if not torch.is_tensor(outputs) or outputs.dim() != 4 or tuple(outputs.shape) != (n, C, h, w):
-        raise ValueError(f"rectify: scores must be a [{n},{C},{h},{w}] tensor, got {tuple(getattr(outputs, 'shape', ()))}")
-    if outputs.device != features.device:
-        raise RuntimeError("rectify: scores must live on the features' GPU (no CPU path in this build)")
-    sbuf, ldc, _, _, _ = _nhwc("rectify", "scores", outputs, C)
-    bank._ensure(features.device)
-    out = torch.empty((n, h, w, ldc), dtype=torch.float32, device=features.device)
-    K.proto_rectify(fbuf, ldf, bank.dim, sbuf, ldc, C, probs, bank.prototypes, bank.seen, bank.inv_tau, n * h * w, out)
+    n, _, h, w = A.scores_shape("rectify", features, bank.dim, "features", bank.dim)
+    if A.scores_shape("rectify", outputs, C) != (n, C, h, w):
+        raise ValueError(f"rectify: scores must be a [{n},{C},{h},{w}] tensor, got {tuple(outputs.shape)}")
+    dev = bank._ensure(A.same_gpu("rectify", features=features, scores=outputs)).device
+    fbuf, ldf = A.padded_nhwc(features.detach())
+    sbuf, ldc = A.padded_nhwc(outputs.detach())
+    out = torch.empty((n, h, w, ldc), dtype=torch.float32, device=dev)
+    A.on_device(dev, K.proto_rectify, fbuf, ldf, bank.dim, sbuf, ldc, C, probs, bank.prototypes, bank.seen, bank.inv_tau, n * h * w,
+                out)
     return out.permute(0, 3, 1, 2)[:, :C]
 
 
@@ -425,7 +391,6 @@ def assign(features, bank):
     them, a distribution per pixel (``assign_mirror`` states it; a strided view of a padded NHWC buffer, which
     ``PrototypeContrastLoss`` and ``SoftCrossEntropyLoss(probs=True)`` read in place).  NaN rows mark pixels with a non-finite
     feature.  One kernel, no host sync, no gradient."""
-    from . import kernels as K
     if not isinstance(bank, PrototypeBank):
         raise ValueError(f"assign: bank must be a PrototypeBank, got {type(bank).__name__}")
     C = bank.num_classes
@@ -433,7 +398,7 @@ def assign(features, bank):
     bank._ensure(features.device)
     ldc = (C + 3) // 4 * 4
     out = torch.empty((n, h, w, ldc), dtype=torch.float32, device=features.device)
-    K.proto_assign(fbuf, ldf, bank.dim, C, ldc, bank.prototypes, bank.seen, bank.inv_tau, n * h * w, out)
+    A.on_device(features.device, K.proto_assign, fbuf, ldf, bank.dim, C, ldc, bank.prototypes, bank.seen, bank.inv_tau, n * h * w, out)
     return out.permute(0, 3, 1, 2)[:, :C]
 
 
@@ -444,7 +409,6 @@ class _PrototypeContrastFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, fbuf, ldf, labels, tbuf, ldt, wpx, wimg, bank, reduction, stats, want_grad):
-        from . import kernels as K
         n, d, h, w = features.shape
         dev = features.device
         denom = None
@@ -463,7 +427,6 @@ class _PrototypeContrastFunction(torch.autograd.Function):
 
     @staticmethod
     def _run(meta, fbuf, labels, tbuf, wpx, wimg, denom, loss, stats, grad):
-        from . import kernels as K
         n, d, h, w, ldf, ldt, bank, reduction = meta
         dev = fbuf.device
         dfeat = torch.empty((n, h, w, ldf), device=dev, dtype=torch.float32) if grad else None
@@ -474,7 +437,6 @@ class _PrototypeContrastFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import kernels as K
         n, d, h, w = ctx.meta[:4]
         g = grad_out.detach().to(torch.float32).contiguous()
         dfeat, ctx.dfeat = ctx.dfeat, None                 # consumed: scaled in place below
@@ -533,9 +495,7 @@ class PrototypeContrastLoss(torch.nn.Module):
                                  f"{tuple(getattr(t, 'shape', ()))}")
             if t.requires_grad:
                 raise ValueError(f"{who}: {name} never receives a gradient; pass {name}.detach()")
-        for name, t in (("target", target), ("pixel_weight", pixel_weight), ("image_weight", image_weight)):
-            if t is not None and t.device != dev:
-                raise RuntimeError(f"{who}: {name} must live on the features' GPU (no CPU path in this build)")
+        A.same_gpu(who, features=features, target=target, pixel_weight=pixel_weight, image_weight=image_weight)
         labels = tbuf = None
         ldt = 0
         if target.is_floating_point():
@@ -550,8 +510,8 @@ class PrototypeContrastLoss(torch.nn.Module):
         wpx = None if pixel_weight is None else pixel_weight.to(torch.float32).contiguous()
         wimg = None if image_weight is None else image_weight.to(torch.float32).contiguous()
         stats = torch.zeros(4, device=dev, dtype=torch.int64)
-        out = _PrototypeContrastFunction.apply(features, fbuf, ldf, labels, tbuf, ldt, wpx, wimg, self.bank, self.reduction, stats,
-                                               torch.is_grad_enabled())
+        out = A.on_device(dev, _PrototypeContrastFunction.apply, features, fbuf, ldf, labels, tbuf, ldt, wpx, wimg, self.bank,
+                          self.reduction, stats, torch.is_grad_enabled())     # the backward runs on the device's autograd thread
         self.last_stats = stats
         return out
 
@@ -565,7 +525,7 @@ def domain_gap(bank_a, bank_b):
     if (bank_a.num_classes, bank_a.dim) != (bank_b.num_classes, bank_b.dim):
         raise ValueError(f"domain_gap: the banks differ in shape: {bank_a.num_classes} x {bank_a.dim} against "
                          f"{bank_b.num_classes} x {bank_b.dim}")
-    bank_a._need_state()
+    bank_a._ensure()
     bank_b._ensure(bank_a.device)
     dist = (bank_a.prototypes - bank_b.prototypes).square().sum(dim=1).sqrt()
     both = (bank_a.seen != 0) & (bank_b.seen != 0)
@@ -588,12 +548,10 @@ class PrototypeLabeler(teacher.OnlineLabeler):
         if not isinstance(bank, PrototypeBank) or bank.num_classes != self.num_classes:
             raise ValueError(f"bank must be a PrototypeBank of {self.num_classes} classes, got "
                              f"{getattr(bank, 'num_classes', type(bank).__name__)}")
-        if not isinstance(rectify_after, (int, np.integer)) or rectify_after < 0:
-            raise ValueError(f"rectify_after must be a non-negative integer, got {rectify_after}")
         if not hasattr(self.model, "forward_parts"):
             raise ValueError("PrototypeLabeler: the model must offer forward_parts(images, (\"logits\", \"decoder\")), as Unet does")
         self.bank = bank
-        self.rectify_after = int(rectify_after)
+        self.rectify_after = A.int_in("PrototypeLabeler", "rectify_after", rectify_after, 0)
         self.update_bank = bool(update_bank)
         self._zero_thr = None
 
@@ -602,12 +560,8 @@ class PrototypeLabeler(teacher.OnlineLabeler):
         self.device                                         # a model on the CPU: "no CPU path"
         dtype = self.dtype or getattr(self.model, "compute_dtype", torch.float32)
         images, _ = prepare_batch(frames_u8, None, None, dtype)
-        was = self._eval()
-        try:
-            with torch.no_grad():
-                return self.model.forward_parts(images, want)
-        finally:
-            self.model.train(was)
+        with A.eval_mode(self.model), torch.no_grad():
+            return self.model.forward_parts(images, want)
 
     def _raw_winners(self, out):
         if self._zero_thr is None or self._zero_thr.device != out.device:

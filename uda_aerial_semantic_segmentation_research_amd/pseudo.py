@@ -43,26 +43,24 @@ and for one large frame: ``labels_u8, probs = labeler.label_large(frame_u8, tile
 import numpy as np
 import torch
 
+from . import _args as A
+from . import _lib
+from . import kernels as K
+
 BINS = 1024
 SUPPORTED_BINS = (256, 512, 1024, 2048, 4096)
 
 
 def _check_bins(bins):
-    if bins not in SUPPORTED_BINS:
-        raise ValueError(f"bins must be one of {SUPPORTED_BINS}, got {bins}")
-    return int(bins)
+    return int(A.choice("pseudo", "bins", bins, SUPPORTED_BINS))
 
 
 def _check_classes(num_classes):
-    if not isinstance(num_classes, (int, np.integer)) or not 0 < num_classes <= 32:
-        raise ValueError(f"num_classes must be in 1..32, got {num_classes}")
-    return int(num_classes)
+    return A.int_in("pseudo", "num_classes", num_classes, 1, 32)
 
 
 def _check_void(void, num_classes):
-    if not isinstance(void, (int, np.integer)) or not num_classes <= void <= 255:
-        raise ValueError(f"void must be a label in {num_classes}..255 (above the classes, inside uint8), got {void}")
-    return int(void)
+    return A.int_in("pseudo", "void", void, num_classes, 255)             # above the classes, inside uint8
 
 
 def bin_edges(bins=BINS):
@@ -123,18 +121,7 @@ def thresholds_from_hist(hist, portion, floor=0.0, cap=1.0):
     return thr, support
 
 
-def _scores(who, outputs, num_classes):
-    if not torch.is_tensor(outputs) or outputs.device.type != "cuda":
-        raise RuntimeError(f"{who}: the scores must live on the GPU (no CPU path in this build)")
-    if outputs.dim() != 4 or outputs.shape[1] != num_classes:
-        raise ValueError(f"{who}: scores must be [N,{num_classes},H,W], got {tuple(outputs.shape)}")
-    from .losses import _padded_nhwc
-    n, c, h, w = outputs.shape
-    buf, ldc = _padded_nhwc(outputs.detach())
-    return buf, ldc, n, h, w
-
-
-class ConfidenceHistogram:
+class ConfidenceHistogram(A.DeviceState):
     """Accumulates the per-class confidence table of ``[N,C,H,W]`` logits (or probabilities) on the device.  ``update`` enqueues
     one kernel and does not synchronise; ``thresholds`` enqueues the finishing kernel and returns a device tensor."""
 
@@ -144,44 +131,38 @@ class ConfidenceHistogram:
         self._buf = None                # [C * B + 1] int64 on the device: the table, then the non-finite count (one allocation)
         self.support = None             # [C] int64 on the device, written by thresholds()
 
-    def _ensure(self, device):
-        if self._buf is None:
-            if device.type != "cuda":
-                raise RuntimeError("ConfidenceHistogram: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self._buf = torch.zeros(self.num_classes * self.bins + 1, dtype=torch.int64, device=device)
-        return self._buf
+    def _allocate(self, device):
+        self._buf = torch.zeros(self.num_classes * self.bins + 1, dtype=torch.int64, device=device)
 
     @property
     def table(self):
         """``[C, B]`` int64 on the device."""
-        return self._ensure(self.device or torch.device("cuda"))[:-1].view(self.num_classes, self.bins)
+        return self._ensure()._buf[:-1].view(self.num_classes, self.bins)
 
     @property
     def nonfinite(self):
         """``[1]`` int64 on the device: the pixels that are in no cell."""
-        return self._ensure(self.device or torch.device("cuda"))[-1:]
+        return self._ensure()._buf[-1:]
 
     def reset(self):
         if self._buf is not None:
             self._buf.zero_()
 
     def update(self, outputs, probs=False):
-        from . import kernels as K
-        buf, ldc, n, h, w = _scores("ConfidenceHistogram.update", outputs, self.num_classes)
+        buf, ldc, n, _, h, w = A.scores_nchw("ConfidenceHistogram.update", outputs, self.num_classes)
         self._ensure(outputs.device)
-        K.conf_hist(buf, n * h * w, self.num_classes, ldc, probs, self.bins, self.table, self.nonfinite)
+        A.on_device(outputs.device, K.conf_hist, buf, n * h * w, self.num_classes, ldc, probs, self.bins, self.table, self.nonfinite)
         return self
 
     def thresholds(self, portion, floor=0.0, cap=0.9):
         """Device int32 ``[C]`` threshold bins of the accumulated table (no host sync); ``self.support`` gets ``n_c``."""
-        from . import kernels as K
         por = _portions(portion, self.num_classes)
         k_floor, k_cap = _floor_cap_bins(floor, cap, self.bins)
         t = self.table
         thr = torch.empty(self.num_classes, dtype=torch.int32, device=t.device)
         self.support = torch.empty(self.num_classes, dtype=torch.int64, device=t.device)
-        K.pseudo_thresholds(t, self.num_classes, self.bins, torch.from_numpy(por).to(t.device), k_floor, k_cap, thr, self.support)
+        A.on_device(t.device, K.pseudo_thresholds, t, self.num_classes, self.bins, torch.from_numpy(por).to(t.device), k_floor, k_cap,
+                    thr, self.support)
         return thr
 
 
@@ -190,23 +171,19 @@ def pseudo_labels(outputs, thr_bins, void=255, probs=False, return_confidence=Fa
     bin reaches ``thr_bins[class]``, ``void`` elsewhere and at every non-finite pixel.  ``thr_bins``: device int32 ``[C]`` made
     with the same ``bins``.  ``counts``: optional device int64 ``[C + 2]`` to accumulate kept-per-class, void, non-finite into.
     With ``return_confidence`` also the fp32 ``[N,H,W]`` confidence (0 at a non-finite pixel).  No host sync."""
-    from . import kernels as K
     bins = _check_bins(bins)
-    if not torch.is_tensor(outputs) or outputs.dim() != 4:
-        raise ValueError(f"pseudo_labels: scores must be a [N,C,H,W] tensor, got {tuple(getattr(outputs, 'shape', ()))}")
-    classes = _check_classes(int(outputs.shape[1]))
+    n, classes, h, w = A.scores_shape("pseudo_labels", outputs)
     void = _check_void(void, classes)
     if not torch.is_tensor(thr_bins) or thr_bins.dtype != torch.int32 or tuple(thr_bins.shape) != (classes,):
         raise ValueError(f"pseudo_labels: thr_bins must be an int32 [{classes}] tensor")
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (classes + 2,)):
-        raise ValueError(f"pseudo_labels: counts must be an int64 [{classes + 2}] tensor")
-    buf, ldc, n, h, w = _scores("pseudo_labels", outputs, classes)
-    dev = outputs.device
+    A.counts_tensor("pseudo_labels", "counts", counts, (classes + 2,), outputs.device)
+    dev = A.same_gpu("pseudo_labels", scores=outputs, thr_bins=thr_bins)
+    buf, ldc = A.padded_nhwc(outputs.detach())
     labels = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     conf = torch.empty((n, h, w), dtype=torch.float32, device=dev) if return_confidence else None
     if counts is None:
         counts = torch.zeros(classes + 2, dtype=torch.int64, device=dev)
-    K.pseudo_labels(buf, n * h * w, classes, ldc, probs, bins, thr_bins, void, labels, conf, counts)
+    A.on_device(dev, K.pseudo_labels, buf, n * h * w, classes, ldc, probs, bins, thr_bins, void, labels, conf, counts)
     return (labels, conf) if return_confidence else labels
 
 
@@ -215,17 +192,11 @@ def confidence_share(outputs, tau, probs=False, return_counts=False):
     made of) is ``>= tau`` -- the per-image weight ``q_i`` of DACS and DAFormer, made without a host read and exact: integer
     counters, ``share[i] = float32(float64(above[i]) / (H * W))``.  Non-finite pixels are in no count.  ``outputs``: ``[N,C,H,W]``
     logits, or probabilities with ``probs``.  With ``return_counts`` also the device int64 ``[N]`` counts ``above`` and ``nonfinite``."""
-    from . import kernels as K
-    if not torch.is_tensor(outputs) or outputs.dim() != 4:
-        raise ValueError(f"confidence_share: scores must be a [N,C,H,W] tensor, got {tuple(getattr(outputs, 'shape', ()))}")
-    tau = float(tau)
-    if not 0.0 <= tau <= 1.0:
-        raise ValueError(f"confidence_share: tau must lie in [0, 1], got {tau}")
-    classes = _check_classes(int(outputs.shape[1]))
-    buf, ldc, n, h, w = _scores("confidence_share", outputs, classes)
+    tau = A.number("confidence_share", "tau", tau, 0.0, 1.0)
+    buf, ldc, n, classes, h, w = A.scores_nchw("confidence_share", outputs)
     counts = torch.empty((2, n), dtype=torch.int64, device=outputs.device)
     share = torch.empty(n, dtype=torch.float32, device=outputs.device)
-    K.conf_share(buf, n, h * w, classes, ldc, probs, tau, counts[0], counts[1], share)
+    A.on_device(outputs.device, K.conf_share, buf, n, h * w, classes, ldc, probs, tau, counts[0], counts[1], share)
     return (share, counts[0], counts[1]) if return_counts else share
 
 
@@ -276,8 +247,7 @@ class PseudoLabeler:
 
     @property
     def device(self):
-        from .predict import _model_device
-        return _model_device(self.model, "PseudoLabeler")
+        return A.model_device(self.model, "PseudoLabeler", 32)
 
     def _forward(self, frames_u8):
         from .data import prepare_batch
@@ -285,10 +255,10 @@ class PseudoLabeler:
         images, _ = prepare_batch(frames_u8, None, None, dtype)              # Normalize, D4 code 0
         return self.model(images)
 
-    def _eval(self):
-        was = self.model.training
-        self.model.eval()
-        return was
+    def _eval_forward(self, frames_u8):
+        """One eval-mode, no-grad forward; the model's training flag is restored."""
+        with A.eval_mode(self.model), torch.no_grad():
+            return self._forward(frames_u8)
 
     def _finish_fit(self):
         """The thresholds from the accumulated table, and the ONE host read of a fit: thresholds, supports, kept counts and the
@@ -314,19 +284,14 @@ class PseudoLabeler:
     def fit(self, loader_u8):
         """Eval-mode pass over a loader of uint8 ``[N,H,W,3]`` target batches: accumulates the table, sets ``self.thr_bins``
         (device) and the report (one host read).  The model's training flag is restored."""
-        from . import _lib
         _lib.require_gpu()
-        was = self._eval()
         self.hist.reset()
         frames_seen = 0
-        try:
-            with torch.no_grad():
-                for batch in loader_u8:
-                    frames = _frames_of(batch)
-                    self.hist.update(self._forward(frames))
-                    frames_seen += int(frames.shape[0])
-        finally:
-            self.model.train(was)
+        with A.eval_mode(self.model), torch.no_grad():
+            for batch in loader_u8:
+                frames = _frames_of(batch)
+                self.hist.update(self._forward(frames))
+                frames_seen += int(frames.shape[0])
         if not frames_seen:
             raise ValueError("PseudoLabeler.fit: the loader yielded no frames")
         return self._finish_fit()
@@ -339,13 +304,7 @@ class PseudoLabeler:
         """uint8 ``[N,H,W]`` masks (device) of uint8 ``[N,H,W,3]`` frames under the fitted thresholds; eval-mode forward, the
         model's training flag restored."""
         self._need_fit("label")
-        was = self._eval()
-        try:
-            with torch.no_grad():
-                out = self._forward(frames_u8)
-        finally:
-            self.model.train(was)
-        return pseudo_labels(out, self.thr_bins, self.void, bins=self.bins)
+        return pseudo_labels(self._eval_forward(frames_u8), self.thr_bins, self.void, bins=self.bins)
 
     def loader(self, loader_u8):
         """Iterable (with ``__len__``) of ``(frames_u8, masks_u8)`` device batches: wrap it in ``data.DeviceAugmentedLoader``."""
@@ -356,16 +315,13 @@ class PseudoLabeler:
         """The histogram pass for large frames: ``predict_large(..., return_probs=True)`` per uint8 ``[H,W,3]`` frame, the table
         updated with ``probs=True``.  (``predict_large`` leaves the model in eval mode; the flag is restored here.)"""
         from .predict import predict_large
-        was = self.model.training
         self.hist.reset()
         n = 0
-        try:
+        with A.eval_mode(self.model):
             for frame in frames:
                 _, probs = predict_large(self.model, frame, return_probs=True, **predict_large_kwargs)
                 self.hist.update(probs, probs=True)
                 n += 1
-        finally:
-            self.model.train(was)
         if not n:
             raise ValueError("PseudoLabeler.fit_large: no frames")
         return self._finish_fit()
@@ -374,11 +330,8 @@ class PseudoLabeler:
         """-> ``(labels uint8 [H,W], probs)``: ``predict_large``'s blended probabilities labelled with ``probs=True``."""
         from .predict import predict_large
         self._need_fit("label_large")
-        was = self.model.training
-        try:
+        with A.eval_mode(self.model):
             _, probs = predict_large(self.model, frame_u8, return_probs=True, **predict_large_kwargs)
-        finally:
-            self.model.train(was)
         return pseudo_labels(probs, self.thr_bins, self.void, probs=True, bins=self.bins)[0], probs
 
     def report(self):

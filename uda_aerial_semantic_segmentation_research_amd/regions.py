@@ -28,8 +28,8 @@ Nothing is read back unless stated.
 import numpy as np
 import torch
 
+from . import _args as A
 from . import kernels as K
-from .boundary import _check_label, _labels, _on, _out
 
 HIST_BINS = 32                # hist[floor(log2(area))]: area < 2^31
 STAT_COLS = 2 + HIST_BINS     # components, pixels, hist
@@ -38,7 +38,7 @@ _SAME = object()              # sieve's ignore_index default: the void value its
 
 # --------------------------------------------------------------------------------------------------------------- host side
 def _check_connectivity(who, connectivity):
-    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+    if A.int_in(who, "connectivity", connectivity, 4, 8) % 4:
         raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity}")
     return int(connectivity)
 
@@ -85,28 +85,19 @@ def fragmentation(pred, truth):
 def label(labels, connectivity=4, ignore_index=None, return_area=False):
     """int32 ids in the labels' shape (-1 on void pixels); with ``return_area`` the pair ``(ids, area)``, both int32."""
     conn = _check_connectivity("label", connectivity)
-    ign = _check_label("label", "ignore_index", ignore_index)
-    lab, single = _labels("label", labels)
+    ign = A.int_in("label", "ignore_index", ignore_index, 0, 255, True)
+    lab, single = A.label_maps("label", labels)
     ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
     area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)     # the labelling's own scratch when no area is asked for
-    _on(lab.device, K.regions_label, lab, conn, ign, ids, area)
+    A.on_device(lab.device, K.regions_label, lab, conn, ign, ids, area)
     if single:
         ids, area = ids[0], area[0]
     return (ids, area) if return_area else ids
 
 
-_TABLES = {}
-
-
 def _device_table(who, min_area, dev):
     arr = min_area_table(min_area, who)
-    key = (arr.tobytes(), str(dev))
-    t = _TABLES.get(key)
-    if t is None:                                                   # callers sieve every batch with the same few tables
-        if len(_TABLES) > 64:
-            _TABLES.clear()
-        t = _TABLES[key] = torch.from_numpy(arr.copy()).to(dev)
-    return t
+    return A.const_table("regions", arr.tobytes(), arr.copy, dev)      # callers sieve every batch with the same few tables
 
 
 def sieve(labels, min_area, connectivity=4, void=255, ignore_index=_SAME, counts=None, out=None):
@@ -115,18 +106,16 @@ def sieve(labels, min_area, connectivity=4, void=255, ignore_index=_SAME, counts
     region is no component and is never counted; ``None`` makes every value an ordinary label.  ``counts``: an int64 ``[N,3]``
     device tensor that ACCUMULATES, per image, the pixels this call voided, the components it removed and those it kept."""
     conn = _check_connectivity("sieve", connectivity)
-    v = _check_label("sieve", "void", void, none_ok=False)
-    ign = v if ignore_index is _SAME else _check_label("sieve", "ignore_index", ignore_index)
-    lab, single = _labels("sieve", labels)
+    v = A.int_in("sieve", "void", void, 0, 255)
+    ign = v if ignore_index is _SAME else A.int_in("sieve", "ignore_index", ignore_index, 0, 255, True)
+    lab, single = A.label_maps("sieve", labels)
     tab = _device_table("sieve", min_area, lab.device)
-    n = lab.shape[0]
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 3)):
-        raise ValueError(f"sieve: counts must be an int64 [{n},3] tensor")
-    out = _out("sieve", "out", out, lab.shape, torch.uint8, lab.device)
+    A.counts_tensor("sieve", "counts", counts, (lab.shape[0], 3), lab.device)
+    out = A.out_tensor("sieve", "out", out, lab.shape, torch.uint8, lab.device)
     ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
     area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
-    _on(lab.device, K.regions_label, lab, conn, ign, ids, area)
-    _on(lab.device, K.regions_sieve, lab, ids, area, ign, tab, v, out, counts)
+    A.on_device(lab.device, K.regions_label, lab, conn, ign, ids, area)
+    A.on_device(lab.device, K.regions_sieve, lab, ids, area, ign, tab, v, out, counts)
     return out[0] if single and out.dim() == 3 else out
 
 
@@ -141,7 +130,7 @@ class SievedLoader:
         self.loader = loader
         self.min_area = min_area_table(min_area, "SievedLoader")
         self.connectivity = _check_connectivity("SievedLoader", connectivity)
-        self.void = _check_label("SievedLoader", "void", void, none_ok=False)
+        self.void = A.int_in("SievedLoader", "void", void, 0, 255)
         self.last_counts = None
 
     def __len__(self):
@@ -161,26 +150,19 @@ class SievedLoader:
             yield frames, out
 
 
-class RegionStats:
+class RegionStats(A.DeviceState):
     """Accumulates the per-class region counters of label maps on the device (``udaseg_regions_stats``).  ``update`` enqueues and
     does not synchronise; ``compute`` does ONE read-back and returns ``summarize`` of the counters."""
 
     def __init__(self, num_classes, connectivity=4, ignore_index=None, device=None):
-        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 1 <= num_classes <= 255:
-            raise ValueError(f"RegionStats: num_classes must be in 1..255, got {num_classes}")
-        self.num_classes = int(num_classes)
+        self.num_classes = A.int_in("RegionStats", "num_classes", num_classes, 1, 255)
         self.connectivity = _check_connectivity("RegionStats", connectivity)
-        self.ignore_index = _check_label("RegionStats", "ignore_index", ignore_index)
+        self.ignore_index = A.int_in("RegionStats", "ignore_index", ignore_index, 0, 255, True)
         self.device = torch.device(device) if device is not None else None
         self.table = None              # int64 [C, 34] on the device
 
-    def _ensure(self, device):
-        if self.table is None:
-            if device.type != "cuda":
-                raise RuntimeError("RegionStats: tensors must live on the GPU (no CPU path in this build)")
-            self.device = device
-            self.table = torch.zeros((self.num_classes, STAT_COLS), dtype=torch.int64, device=device)
-        return self.table
+    def _allocate(self, device):
+        self.table = torch.zeros((self.num_classes, STAT_COLS), dtype=torch.int64, device=device)
 
     def reset(self):
         if self.table is not None:
@@ -189,31 +171,23 @@ class RegionStats:
     def update(self, pred):
         """``pred``: a label map (uint8 or int64 ``[N,H,W]`` or ``[H,W]``), or scores ``[N,C,H,W]`` (logits or probabilities),
         labelled by their first maximum (``udaseg_predict_finish``'s arg-max, at most 32 classes)."""
-        if not torch.is_tensor(pred):
-            raise ValueError("RegionStats.update: pred must be a tensor")
-        if pred.device.type != "cuda":
-            raise RuntimeError("RegionStats.update: pred must live on the GPU (no CPU path in this build)")
-        if pred.dim() == 4:
-            from .losses import _padded_nhwc
-            n, c, h, w = pred.shape
-            if c != self.num_classes:
-                raise ValueError(f"RegionStats.update: scores must be [N,{self.num_classes},H,W], got {tuple(pred.shape)}")
-            buf, ldc = _padded_nhwc(pred.detach())
+        if torch.is_tensor(pred) and pred.dim() == 4:
+            buf, ldc, n, c, h, w = A.scores_nchw("RegionStats.update", pred, self.num_classes, "pred")
             lab = torch.empty((n, h, w), dtype=torch.int64, device=pred.device)
-            _on(pred.device, K.predict_finish, buf, None, n * h * w, c, ldc, lab)
+            A.on_device(pred.device, K.predict_finish, buf, None, n * h * w, c, ldc, lab)
             pred = lab
-        lab, _ = _labels("RegionStats.update", pred, "pred")
-        tab = self._ensure(lab.device)
+        lab, _ = A.label_maps("RegionStats.update", pred, "pred")
+        tab = self._ensure(lab.device).table
         ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
         area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
-        _on(lab.device, K.regions_label, lab, self.connectivity, self.ignore_index, ids, area)
-        _on(lab.device, K.regions_stats, lab, ids, area, self.num_classes, self.ignore_index, tab)
+        A.on_device(lab.device, K.regions_label, lab, self.connectivity, self.ignore_index, ids, area)
+        A.on_device(lab.device, K.regions_stats, lab, ids, area, self.num_classes, self.ignore_index, tab)
         return self
 
     def compute(self):
         """``summarize`` of the accumulated counters: ``components`` / ``pixels`` / ``mean_area`` [C], ``hist`` [C,32] and the raw
         ``stats`` [C,34].  ONE device->host transfer of ``34 C`` counters."""
-        return summarize(self._ensure(self.device or torch.device("cuda", torch.cuda.current_device())).cpu().numpy())
+        return summarize(self._ensure().table.cpu().numpy())
 
 
 def evaluate(model, loader, num_classes, device, connectivity=4, ignore_index=None):
@@ -225,12 +199,10 @@ def evaluate(model, loader, num_classes, device, connectivity=4, ignore_index=No
     if device.type != "cuda":
         raise RuntimeError("evaluate: the model runs on the GPU (no CPU path in this build)")
     conn = _check_connectivity("evaluate", connectivity)
-    was_training = model.training
-    model.eval()
     sp = RegionStats(num_classes, conn, ignore_index, device)
     st = RegionStats(num_classes, conn, ignore_index, device)
     seen = False
-    with torch.no_grad():
+    with A.eval_mode(model), torch.no_grad():
         for images, masks in loader:
             images = images.to(device)
             masks = masks.to(device)
@@ -241,7 +213,6 @@ def evaluate(model, loader, num_classes, device, connectivity=4, ignore_index=No
             sp.update(model(images))
             st.update(masks)
             seen = True
-    model.train(was_training)
     if not seen:
         raise ValueError("evaluate: the loader is empty")
     pred, truth = sp.compute(), st.compute()

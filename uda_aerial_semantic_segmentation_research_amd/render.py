@@ -32,6 +32,7 @@ import csv
 import numpy as np
 import torch
 
+from . import _args as A
 from . import kernels as K
 from .data import IMAGENET_MEAN, IMAGENET_STD
 
@@ -166,9 +167,6 @@ def format_stats(counts, names):
 
 
 # ------------------------------------------------------------------------------------------------------------- device side
-_TABLES = {}
-
-
 def _table_for(palette, classes, void_color, dev):
     """(device table, classes) of the ``palette`` argument: None (the default palette), ``[K,3]`` colours, or a ready uint8
     ``[256,3]`` device table (then ``classes`` must be given)."""
@@ -177,34 +175,12 @@ def _table_for(palette, classes, void_color, dev):
             raise ValueError(f"a device palette must be the uint8 [256,3] table of palette_table, got {palette.dtype} {tuple(palette.shape)}")
         if classes is None:
             raise ValueError("classes must be given with a ready device table")
-        if not isinstance(classes, (int, np.integer)) or not 1 <= classes <= 256:
-            raise ValueError(f"classes must lie in 1..256, got {classes}")
-        return palette, int(classes)
+        return palette, A.int_in("palette", "classes", classes, 1, 256)
     col = default_palette() if palette is None else (palette.numpy() if torch.is_tensor(palette) else np.asarray(palette))
     if classes is None:
         classes = int(col.shape[0]) if col.ndim == 2 else 0
     arr = table_array(col, classes, void_color)
-    key = (arr.tobytes(), str(dev))
-    t = _TABLES.get(key)
-    if t is None:
-        if len(_TABLES) > 64:
-            _TABLES.clear()
-        t = _TABLES[key] = torch.from_numpy(arr).to(dev)
-    return t, int(classes)
-
-
-def _labels(who, labels, name="labels"):
-    if not torch.is_tensor(labels):
-        raise ValueError(f"{who}: {name} must be a tensor, got {type(labels).__name__}")
-    if labels.device.type != "cuda":
-        raise RuntimeError(f"{who}: {name} must live on the GPU (no CPU path in this build)")
-    if labels.dtype not in (torch.uint8, torch.int64) or labels.dim() not in (2, 3):
-        raise ValueError(f"{who}: {name} must be uint8 or int64 [N,H,W] (or [H,W]), got {labels.dtype} {tuple(labels.shape)}")
-    single = labels.dim() == 2
-    lab = labels[None] if single else labels
-    if lab.numel() == 0:
-        raise ValueError(f"{who}: {name} are empty: {tuple(labels.shape)}")
-    return lab.contiguous(), single
+    return A.const_table("render", arr.tobytes(), lambda: arr, dev), int(classes)
 
 
 def _base(who, frames, n, h, w, single):
@@ -244,19 +220,18 @@ def _base(who, frames, n, h, w, single):
 def _render(who, labels, frames=None, truth=None, ignore_index=None, alphas=(0, 0, 0, 0), palette=None, classes=None,
             void_color=VOID_COLOR, outline=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, counts=None, agreement=None, out=None):
     """The one path to the kernel.  -> (picture, counts, agreement); counts / agreement are what was handed in (None if nothing was)."""
-    lab, single = _labels(who, labels)
+    lab, single = A.label_maps(who, labels)
     n, h, w = lab.shape
     dev = lab.device
     if truth is not None:
-        tru, _ = _labels(who, truth, "truth")
+        tru, _ = A.label_maps(who, truth, "truth")
         if tuple(tru.shape) != (n, h, w):
             raise ValueError(f"{who}: truth must have the labels' shape {(n, h, w)}, got {tuple(tru.shape)}")
         if tru.dtype != lab.dtype:                                 # one dtype for both: the uint8 one is widened (lossless)
             lab, tru = lab.long(), tru.long()
     else:
         tru = None
-    if ignore_index is not None and (not isinstance(ignore_index, (int, np.integer)) or not -2 ** 31 <= ignore_index < 2 ** 31):
-        raise ValueError(f"{who}: ignore_index must be an int (32 bits) or None, got {ignore_index}")
+    A.int_in(who, "ignore_index", ignore_index, -2 ** 31, 2 ** 31 - 1, True)
     table, classes = _table_for(palette, classes, void_color, dev)
     base = None if frames is None else _base(who, frames, n, h, w, single)
     denorm = _denorm_cached(tuple(mean), tuple(std)) if base is not None and base.dtype != torch.uint8 else None
@@ -264,22 +239,12 @@ def _render(who, labels, frames=None, truth=None, ignore_index=None, alphas=(0, 
     if outline is not None:
         r, g, b = _color("outline", OUTLINE_WHITE if outline is True else outline)
         line = r | (g << 8) | (b << 16)
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, 256)):
-        raise ValueError(f"{who}: counts must be an int64 [{n},256] tensor")
-    if agreement is not None:
-        if tru is None:
-            raise ValueError(f"{who}: agreement needs truth")
-        if not torch.is_tensor(agreement) or agreement.dtype != torch.int64 or tuple(agreement.shape) != (n, 3):
-            raise ValueError(f"{who}: agreement must be an int64 [{n},3] tensor")
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3):
-        raise ValueError(f"{who}: out must be a uint8 [{n},{h},{w},3] tensor")
-    if dev.index == torch.cuda.current_device():                   # the launch goes to the CURRENT device's stream
-        K.render_u8(lab, tru, base, table, n, h, w, classes, ignore_index, alphas, denorm, line, out, counts, agreement)
-    else:
-        with torch.cuda.device(dev):
-            K.render_u8(lab, tru, base, table, n, h, w, classes, ignore_index, alphas, denorm, line, out, counts, agreement)
+    A.counts_tensor(who, "counts", counts, (n, 256), dev)
+    if agreement is not None and tru is None:
+        raise ValueError(f"{who}: agreement needs truth")
+    A.counts_tensor(who, "agreement", agreement, (n, 3), dev)
+    out = A.out_tensor(who, "out", out, (n, h, w, 3), torch.uint8, dev)
+    A.on_device(dev, K.render_u8, lab, tru, base, table, n, h, w, classes, ignore_index, alphas, denorm, line, out, counts, agreement)
     return (out[0] if single else out), counts, agreement
 
 
@@ -341,12 +306,12 @@ def render_large(model, frame_u8_hwc, tile=512, overlap=0.25, tta=None, palette=
                  **predict_large_kwargs):
     """``(labels int64 [H,W], overlay uint8 [H,W,3], counts int64 [256])`` of one frame of any size, all on the device:
     ``predict.predict_large`` and then ONE render call over its labels and the frame."""
-    from .predict import _model_device, predict_large
+    from .predict import MAX_CLASSES, predict_large
     if isinstance(frame_u8_hwc, np.ndarray):
         frame_u8_hwc = torch.from_numpy(np.ascontiguousarray(frame_u8_hwc))
     if not torch.is_tensor(frame_u8_hwc):
         raise ValueError(f"render_large: the frame must be a uint8 [H,W,3] array or tensor, got {type(frame_u8_hwc).__name__}")
-    frame = frame_u8_hwc.to(_model_device(model, "render_large"), non_blocking=True)      # the ONE copy of the frame
+    frame = frame_u8_hwc.to(A.model_device(model, "render_large", MAX_CLASSES), non_blocking=True)      # the ONE copy of the frame
     labels = predict_large(model, frame, tile=tile, overlap=overlap, tta=tta, **predict_large_kwargs)
     if classes is None:
         classes = int(model.classes)

@@ -224,12 +224,7 @@ class OnlineLabeler(pseudo.PseudoLabeler):
 
     def label(self, frames_u8):
         """uint8 ``[N,H,W]`` masks (device) of uint8 ``[N,H,W,3]`` frames; updates the table and ``self.thr_bins``.  No host read."""
-        was = self._eval()
-        try:
-            with torch.no_grad():
-                out = self._forward(frames_u8)
-        finally:
-            self.model.train(was)
+        out = self._eval_forward(frames_u8)
         if self.halve_every and self.calls and self.calls % self.halve_every == 0:
             self.halve_(self.hist.table)
         self.calls += 1

@@ -182,11 +182,11 @@ class SegmentationTrainer:
         void colour) and ``/overlay`` (the prediction's colours over the image at 0.5), each handed to ``logger.log_image`` as a uint8
         ``[3,H,W]`` device tensor; the ``[H,W,3]`` pictures stay on ``self.last_renders``."""
         from . import kernels as K, render
-        from .predict import _logits_nhwc
+        from ._args import logits_nhwc
         k = self.num_classes
         logits = outputs[:1]
         _, c, h, w = logits.shape
-        buf, ldc = _logits_nhwc(logits)
+        buf, ldc = logits_nhwc(logits)
         pred = torch.empty((1, h, w), dtype=torch.int64, device=buf.device)
         K.predict_finish(buf, None, h * w, c, ldc, pred)
         pics = {"image": render.overlay(images[:1], pred, alpha=0.0, classes=k),
