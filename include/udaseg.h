@@ -816,6 +816,12 @@ int udaseg_regions_sieve(const void* labels, int labels_i64, const int32_t* ids,
  * per component of label c, each counted at its root pixel.  A label >= classes that is not void counts nowhere. */
 int udaseg_regions_stats(const void* labels, int labels_i64, const int32_t* ids, const int32_t* area, int n, int h, int w,
                          int classes, int has_ignore, int ignore_index, int64_t* stats, void* stream);
+/* The same labelling of an int32 map [n][h][w] (4-byte aligned), for maps of more than 256 values such as a superpixel map: every
+ * value >= 0 is a label of its own and a negative value is VOID; there is no ignore_index.  ids, area: as udaseg_regions_label
+ * writes them (area NULL or int32 [n][h][w]); ids must not be labels itself.  The uint8 / int64 entry point is not changed by it:
+ * the tile kernel is instantiated a third time with its labels as 32-bit words in LDS (48 KB of static LDS in place of 40 KB). */
+int udaseg_regions_label_i32(const int32_t* labels, int n, int h, int w, int connectivity, int32_t* ids, int32_t* area,
+                             void* stream);
 
 /* ---- CRF refinement of class scores under the frame: mean-field inference of a dense CRF (Kraehenbuehl & Koltun 2011) with the
  * message passing restricted to a local window (ConvCRF, Teichmann & Cipolla 2018); an extension, the reference has no counterpart
@@ -914,6 +920,71 @@ int udaseg_acquire_select(const float* key, const float* thresholds, int n, int6
                           void* stream);
 /* mask uint8 [n][h][w] |= 1 on every pixel, void or not, whose cell of udaseg_acquire_cells's grid has cell_mask != 0. */
 int udaseg_acquire_expand(const uint8_t* cell_mask, int n, int h, int w, int cell_h, int cell_w, uint8_t* mask, void* stream);
+
+/* ---- superpixels: an integer SLIC (Achanta et al. 2012) whose superpixels are 4-connected, the majority vote of a label map per
+ * superpixel, the mean of a score map per superpixel, a gather of a per-superpixel table; an extension, the reference has no
+ * counterpart (csrc/superpixels.hip; tests/_superpixels_ref.py is the numpy mirror, compared for equality).  EVERYTHING IS INTEGER
+ * ARITHMETIC: two runs give the same bits in whatever order the atomics land, and there is no float atomic.
+ * Inputs: frames uint8 [n][h][w][3], the three channels used as they are (the colour space is the caller's; no Lab conversion);
+ * step S in [2, 64]; compactness m in [1, 1024]; iterations T in [1, 64]; min_area >= 0; 0 < n <= 65535, 1 <= h, w <= 32768,
+ * h * w < 2^31.  Every entry point refuses anything else with a message that names the argument, before any launch.
+ *   grid     gh = ceil(h / S), gw = ceil(w / S), K = gh * gw clusters per image; cluster k = gy * gw + gx belongs to cell (gy, gx),
+ *            the pixels with y / S == gy and x / S == gx.
+ *   centres  int32 [n][K][6] = (Y, X, C0, C1, C2, count), Y .. C2 in units of 1/16.  Start: y0 = min(gy * S + S / 2, h - 1)
+ *            (integer division), x0 likewise, centre = 16 * (y0, x0, frame[y0][x0][:]), count = 0.  NO GRADIENT PERTURBATION of the
+ *            seeds is applied (SLIC moves a seed to the lowest gradient of its 3 x 3 neighbourhood; this rule does not).
+ *   assign   a pixel (y, x) of cell (gy, gx) considers the clusters of the up to 9 cells (gy + dy, gx + dx), dy, dx in {-1, 0, 1},
+ *            that lie inside the grid, and takes the smallest
+ *                D = S^2 * sum_i (16 c_i - C_i)^2 + m^2 * ((16 y - Y)^2 + (16 x - X)^2)
+ *            in 64-bit integers (D < 2.1e13 for S <= 64, m <= 1024); among equal D the smallest k.  A cluster's pixels therefore lie
+ *            in the 3 x 3 cells around its own: count <= 9 S^2 <= 36864.
+ *   update   per cluster the integer sums of y, x, c0, c1, c2 over its pixels and their count (36864 * 32767 < 2^31: int32); each
+ *            component becomes (16 * sum + count / 2) / count, in 64 bits with integer division.  A cluster with count == 0 keeps its
+ *            centre.  The count is stored in either case.
+ *   iterate  T times: labels = assign(centres), then centres = update(labels).  The centres returned are the last update's.
+ *   connect  Take the 4-connected components of the last labels; a component's root is its first pixel in raster order, its area its
+ *            pixel count.  The MAIN component of cluster k: the one that holds pixel (0, 0) if that carries label k, else the
+ *            component of k with the largest area, ties to the smallest root.  A component is KEPT if it is main and (area >=
+ *            min_area or it holds pixel (0, 0)).  Every other component is ABSORBED: it takes the final label of the pixel just
+ *            before its root -- (y, x - 1) if x > 0, else (y - 1, 0) -- which belongs to a component with a smaller root; applied
+ *            transitively, the chain of roots strictly decreases and ends at a kept component.
+ *            With min_area == 0: every non-empty cluster keeps its main component, and every final superpixel is 4-connected (a
+ *            chain links adjacent components up to a kept one, so what a kept component gathers is connected through it).  With
+ *            min_area > 0 whole clusters may vanish (on a pure-noise frame nearly all do); the connectivity still holds.
+ *   ids      int32 [n][h][w]: the final cluster index in [0, K) of every pixel.
+ *   counts   NULL or int64 [n][4], ACCUMULATES per image {components found, components absorbed, pixels whose label changed,
+ *            clusters that own at least one pixel at the end}. */
+int udaseg_superpixel_slic(const uint8_t* frames, int n, int h, int w, int step, int compactness, int iterations, int min_area,
+                           int32_t* ids, int32_t* centres, int64_t* counts, void* stream);
+/* ONE iteration from given centres (int32 [n][K][6] as udaseg_superpixel_slic or this call wrote them; updated in place).  labels:
+ * NULL, or int32 [n][h][w] that receives the assignment the update was made from. */
+int udaseg_superpixel_assign(const uint8_t* frames, int n, int h, int w, int step, int compactness, int32_t* centres,
+                             int32_t* labels, void* stream);
+/* The connect step alone on a map of cluster indices of the grid of `step`: labels int32 [n][h][w], every value in [0, K); ids and
+ * counts as above (ids may be labels itself).  A value outside [0, K) is no cluster of the grid: a negative pixel stays as it is
+ * and belongs to no component, a component of a value >= K is kept as it is, and a component absorbed into either takes that value. */
+int udaseg_superpixel_connect(const int32_t* labels, int n, int h, int w, int step, int min_area, int32_t* ids, int64_t* counts,
+                              void* stream);
+/* The vote of a label map per superpixel.  ids int32 [n][h][w] with 0 <= ids < clusters (a pixel outside that range belongs to no
+ * superpixel: it counts nowhere and comes out void); masks uint8 (masks_i64 == 0) or int64 (== 1, a value outside [0, 255] reads as
+ * 255) [n][h][w]; a pixel whose mask value is ignore_index (with has_ignore == 1) or >= classes is VOID and is not counted.
+ *   T[k][c]      the pixels of superpixel k whose mask value is class c; labelled(k) = sum_c T[k][c]; size(k) = the pixels of k.
+ *   winner(k)    the class with the largest T[k][c], ties to the smallest class.
+ *   out(p)       winner(k) for a pixel p of k if labelled(k) > 0 and (double)T[k][winner] >= (double)min_share * (double)labelled(k)
+ *                and (double)labelled(k) >= (double)min_cover * (double)size(k); void_label otherwise.  uint8 [n][h][w].
+ *   counts       NULL or int64 [n][3], ACCUMULATES {labelled pixels that come out with another class, void pixels that come out
+ *                with a class, labelled pixels that come out void}.
+ * 1 <= clusters <= 2^28, 1 <= classes <= 255, ignore_index and void_label in [0, 255], min_share and min_cover in [0, 1]. */
+int udaseg_superpixel_vote(const int32_t* ids, const void* masks, int masks_i64, int n, int h, int w, int clusters, int classes,
+                           int has_ignore, int ignore_index, float min_share, float min_cover, int void_label, uint8_t* out,
+                           int64_t* counts, void* stream);
+/* The mean of fp32 values [n][h][w] per superpixel: a pixel counts if its value is finite and lies in [0, 1] (and its id in
+ * [0, clusters)); q = rint(v * 2^24), exact because scaling by a power of two is; the sums are int64.  mean fp32 [n][clusters] =
+ * fp32((double)sum / ((double)count * 2^24)), or -1 where no pixel counts: the form udaseg_kth_hist and udaseg_acquire_select take. */
+int udaseg_superpixel_mean(const float* values, const int32_t* ids, int n, int h, int w, int clusters, float* mean, void* stream);
+/* mask uint8 [n][h][w]: mask[p] |= table[ids[p]] for every pixel with an id in [0, clusters); table uint8 [n][clusters]. */
+int udaseg_superpixel_gather(const int32_t* ids, const uint8_t* table, int n, int h, int w, int clusters, uint8_t* mask,
+                             void* stream);
 
 /* ---- discriminator tail + adversarial BCE: discriminator.py:37-42, losses.py:18-51 ---- */
 /* pooled[n][c] = mean over hw of z; p[n] = sigmoid(dot(pooled[n], w) + b).  partial: [n][splits][c] floats */

@@ -156,6 +156,13 @@ SIGNATURES = {
     "udaseg_regions_label": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "udaseg_regions_sieve": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "udaseg_regions_stats": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "udaseg_regions_label_i32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_superpixel_slic": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "udaseg_superpixel_assign": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_superpixel_connect": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "udaseg_superpixel_vote": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P]),
+    "udaseg_superpixel_mean": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "udaseg_superpixel_gather": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "udaseg_crf_tile": (_I, [_I, _I]),
     "udaseg_crf_prepare": (_I, [_P, _I, _I, _I, _L, _P, _P, _I, _P, _P]),
     "udaseg_crf_step": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _P, _P]),

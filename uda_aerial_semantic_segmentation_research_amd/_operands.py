@@ -51,6 +51,7 @@ _HALF = "n*(hi//2)*(wi//2)"          # pixels of the half-resolution source of a
 _ACT_BF = "(f32 if out_f32 else bf16)"
 _BIL = "(bf16 if bf16_ else f32)"
 _LAB = "(i64 if labels_i64 else u8)"
+_SPK = "((h+step-1)//step)*((w+step-1)//step)"          # clusters per image of a superpixel grid
 
 OPERANDS = {
     # ---- library state / queries (no device pointers)
@@ -436,6 +437,23 @@ OPERANDS = {
                              T("out", u8, "n*h*w"), T("counts", i64, "n*3", True), S],
     "udaseg_regions_stats": [T("labels", _LAB, "n*h*w"), I("labels_i64"), T("ids", i32, "n*h*w"), T("area", i32, "n*h*w"), I("n"),
                              I("h"), I("w"), I("classes"), I("has_ignore"), I("ignore_index"), T("stats", i64, "classes*34"), S],
+    "udaseg_regions_label_i32": [T("labels", i32, "n*h*w"), I("n"), I("h"), I("w"), I("connectivity"), T("ids", i32, "n*h*w"),
+                                 T("area", i32, "n*h*w", True), S],
+    # ---- superpixels (K clusters per image: the ceil-divided grid of `step`, or `clusters` where the caller names the extent)
+    "udaseg_superpixel_slic": [T("frames", u8, "n*h*w*3"), I("n"), I("h"), I("w"), I("step"), I("compactness"), I("iterations"),
+                               I("min_area"), T("ids", i32, "n*h*w"), T("centres", i32, "n*" + _SPK + "*6"),
+                               T("counts", i64, "n*4", True), S],
+    "udaseg_superpixel_assign": [T("frames", u8, "n*h*w*3"), I("n"), I("h"), I("w"), I("step"), I("compactness"),
+                                 T("centres", i32, "n*" + _SPK + "*6"), T("labels", i32, "n*h*w", True), S],
+    "udaseg_superpixel_connect": [T("labels", i32, "n*h*w"), I("n"), I("h"), I("w"), I("step"), I("min_area"), T("ids", i32, "n*h*w"),
+                                  T("counts", i64, "n*4", True), S],
+    "udaseg_superpixel_vote": [T("ids", i32, "n*h*w"), T("masks", "(i64 if masks_i64 else u8)", "n*h*w"), I("masks_i64"), I("n"), I("h"),
+                               I("w"), I("clusters"), I("classes"), I("has_ignore"), I("ignore_index"), F("min_share"), F("min_cover"),
+                               I("void_label"), T("out", u8, "n*h*w"), T("counts", i64, "n*3", True), S],
+    "udaseg_superpixel_mean": [T("values", f32, "n*h*w"), T("ids", i32, "n*h*w"), I("n"), I("h"), I("w"), I("clusters"),
+                               T("mean", f32, "n*clusters"), S],
+    "udaseg_superpixel_gather": [T("ids", i32, "n*h*w"), T("table", u8, "n*clusters"), I("n"), I("h"), I("w"), I("clusters"),
+                                 T("mask", u8, "n*h*w"), S],
     # ---- CRF refinement (logp, q0, q, q_out: padded NHWC rows of ldq floats; the two spatial tables: (2 radius + 1)^2 floats)
     "udaseg_crf_tile": [I("radius"), I("dilation")],
     "udaseg_crf_prepare": [T("scores", f32, "pixels*ldc"), I("ldc"), I("classes"), I("probs"), I("pixels"),

@@ -203,6 +203,11 @@ constexpr int PACK_DGRAD_GRID_X = 256;
 
 void* workspace_ptr(size_t* bytes);   // conv_small.hip: the scratch bound to the current device, or nullptr
 
+// regions.hip: udaseg_regions_label_i32's launches on checked arguments (ids != labels; area [n][h][w] is always needed, as scratch
+// when want_area == 0).  superpixels.hip's connect step labels its cluster map with it.
+int regions_label_i32_launch(const int32_t* labels, int32_t* ids, int32_t* area, int n, int h, int w, int connectivity, int want_area,
+                             hipStream_t st);
+
 // channel_sum (bias gradients): above CHSUM_DIRECT_BLOCKS blocks the per-block partials go into CHSUM_REPLICAS zeroed copies of
 // the output in a stream-ordered scratch allocation and a second tiny kernel folds them -- 2048 blocks adding into one
 // 64-float vector took 415 us for a 67 MB tensor (r02: 24 % of the bf16 adversarial step), 30x its HBM time.

@@ -3,6 +3,7 @@
 //
 // The rule (include/udaseg.h states it in full; tests/_regions_ref.py is its numpy mirror, compared for equality).  Per image:
 //   L(p)     the label: uint8, or int64 with a value outside [0, 255] read as 255; void when has_ignore and L(p) == ignore_index
+//            (udaseg_regions_label_i32: an int32 map, every value >= 0 a label of its own, void when negative)
 //   adjacent two pixels of one image, neither void, with the same label, that are 4- or 8-neighbours (connectivity)
 //   id(p)    the smallest y * w + x over the pixels of p's component (the transitive closure of "adjacent"); -1 on a void pixel
 //   area(p)  the number of pixels of p's component; 0 on a void pixel
@@ -44,10 +45,21 @@ struct RgArgs {
   int want_area;                               // finish
 };
 
-template <bool I64>
+// the label kinds: uint8, int64 (a value outside [0, 255] reads as 255) and int32 (any value >= 0 is a label, a negative one void)
+constexpr int RG_U8 = 0, RG_I64 = 1, RG_I32 = 2;
+template <int KIND>
+constexpr int rg_dead() { return KIND == RG_I32 ? -1 : RG_DEAD; }
+template <int KIND>
+constexpr size_t rg_bytes() { return KIND == RG_I64 ? 8 : KIND == RG_I32 ? 4 : 1; }
+
+template <int KIND>
 __device__ __forceinline__ int rg_load(const void* __restrict__ img, int64_t p, int has_ignore, int ignore_index) {
   int v;
-  if (I64) {
+  if (KIND == RG_I32) {
+    v = reinterpret_cast<const int*>(img)[p];
+    return v < 0 ? -1 : v;
+  }
+  if (KIND == RG_I64) {
     const long long q = reinterpret_cast<const long long*>(img)[p];
     v = (q < 0 || q > 255) ? 255 : (int)q;
   } else {
@@ -106,22 +118,30 @@ __device__ __forceinline__ void rg_unite(int* ids, int a, int b) {
   }
 }
 
-template <bool I64>
+// the tile's labels in LDS: 16 bits hold a uint8 / int64 label or RG_DEAD; an int32 label takes the word (48 KB of LDS in all)
+template <int KIND>
+struct RgLab { typedef unsigned short type; };
+template <>
+struct RgLab<RG_I32> { typedef int type; };
+
+template <int KIND>
 __global__ __launch_bounds__(RG_THREADS) void regions_tile_kernel(RgArgs A) {
+  typedef typename RgLab<KIND>::type lab_t;
+  constexpr int RG_DEAD = rg_dead<KIND>();     // shadows the 16-bit kinds' constant inside this kernel
   __shared__ int par[RG_TILE];
   __shared__ unsigned int cnt[RG_TILE];
-  __shared__ unsigned short lab[RG_TILE];
+  __shared__ lab_t lab[RG_TILE];
   const int tid = threadIdx.x, h = A.h, w = A.w;
   const int ty0 = ((int)blockIdx.x / A.tiles_x) * RG_TH, tx0 = ((int)blockIdx.x % A.tiles_x) * RG_TW;
   const int64_t HW = (int64_t)h * w;
-  const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)blockIdx.y * HW * (I64 ? 8 : 1);
+  const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)blockIdx.y * HW * rg_bytes<KIND>();
   int* ids = A.ids + (size_t)blockIdx.y * HW;
   int* area = A.area + (size_t)blockIdx.y * HW;
   for (int i = tid; i < RG_TILE; i += RG_THREADS) {
     const int y = ty0 + (i >> 6), x = tx0 + (i & 63);
     int v = RG_DEAD;
-    if (y < h && x < w) v = rg_load<I64>(img, (int64_t)y * w + x, A.has_ignore, A.ignore_index);   // every read is inside the image
-    lab[i] = (unsigned short)v;
+    if (y < h && x < w) v = rg_load<KIND>(img, (int64_t)y * w + x, A.has_ignore, A.ignore_index);   // every read is inside the image
+    lab[i] = (lab_t)v;
     // a wave holds one tile row (RG_TW == 64 lanes): every pixel starts at the first pixel of its horizontal run, so the row
     // needs no union at all.  Lane 0 always starts a run, so the mask below is never empty.
     const int lane = tid & 63;
@@ -180,11 +200,12 @@ __global__ __launch_bounds__(RG_THREADS) void regions_tile_kernel(RgArgs A) {
   }
 }
 
-template <bool I64>
+template <int KIND>
 __global__ __launch_bounds__(RG_THREADS) void regions_merge_kernel(RgArgs A) {
+  constexpr int RG_DEAD = rg_dead<KIND>();
   const int tid = threadIdx.x, h = A.h, w = A.w, k = A.level;
   const int64_t HW = (int64_t)h * w;
-  const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)blockIdx.y * HW * (I64 ? 8 : 1);
+  const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)blockIdx.y * HW * rg_bytes<KIND>();
   int* ids = A.ids + (size_t)blockIdx.y * HW;
   // the group's pixels: [gy0, gy1) x [gx0, gx1), clipped to the image (64-bit: 64 << k passes 2^31 for a one-row image)
   const int64_t gy0 = (int64_t)((int)blockIdx.x / A.groups_x) * ((int64_t)RG_TH << k);
@@ -196,26 +217,26 @@ __global__ __launch_bounds__(RG_THREADS) void regions_merge_kernel(RgArgs A) {
   if (xs < gx1) {                              // the vertical seam between columns xs - 1 and xs, over the group's rows
     for (int64_t y = gy0 + tid; y < gy1; y += RG_THREADS) {
       const int64_t a = y * w + xs - 1;
-      const int l = rg_load<I64>(img, a, A.has_ignore, A.ignore_index);
+      const int l = rg_load<KIND>(img, a, A.has_ignore, A.ignore_index);
       if (l == RG_DEAD) continue;
       for (int d = -reach; d <= reach; ++d) {  // a diagonal that leaves the group belongs to the level whose group holds both
         const int64_t yb = y + d;
         if (yb < gy0 || yb >= gy1) continue;
         const int64_t b = yb * w + xs;
-        if (rg_load<I64>(img, b, A.has_ignore, A.ignore_index) == l) rg_unite(ids, (int)a, (int)b);
+        if (rg_load<KIND>(img, b, A.has_ignore, A.ignore_index) == l) rg_unite(ids, (int)a, (int)b);
       }
     }
   }
   if (ys < gy1) {                              // the horizontal seam between rows ys - 1 and ys, over the group's columns
     for (int64_t x = gx0 + tid; x < gx1; x += RG_THREADS) {
       const int64_t a = (ys - 1) * w + x;
-      const int l = rg_load<I64>(img, a, A.has_ignore, A.ignore_index);
+      const int l = rg_load<KIND>(img, a, A.has_ignore, A.ignore_index);
       if (l == RG_DEAD) continue;
       for (int d = -reach; d <= reach; ++d) {
         const int64_t xb = x + d;
         if (xb < gx0 || xb >= gx1) continue;
         const int64_t b = ys * w + xb;
-        if (rg_load<I64>(img, b, A.has_ignore, A.ignore_index) == l) rg_unite(ids, (int)a, (int)b);
+        if (rg_load<KIND>(img, b, A.has_ignore, A.ignore_index) == l) rg_unite(ids, (int)a, (int)b);
       }
     }
   }
@@ -360,21 +381,23 @@ static inline unsigned int rg_flat_grid(int64_t hw) { return (unsigned int)cappe
     if (e__ != hipSuccess) return hip_fail(e__, what);      \
   } while (0)
 
-static int rg_label(RgArgs A, int labels_i64, int n, hipStream_t st) {
+static int rg_label(RgArgs A, int kind, int n, hipStream_t st) {
   const int64_t hw = (int64_t)A.h * A.w;
   A.tiles_x = cdiv(A.w, RG_TW);
   A.tiles_y = cdiv(A.h, RG_TH);
   const dim3 tiles((unsigned int)((int64_t)A.tiles_x * A.tiles_y), (unsigned int)n);   // <= 2^31 / 4096 + the edge tiles
-  if (labels_i64) hipLaunchKernelGGL(regions_tile_kernel<true>, tiles, dim3(RG_THREADS), 0, st, A);
-  else hipLaunchKernelGGL(regions_tile_kernel<false>, tiles, dim3(RG_THREADS), 0, st, A);
+  if (kind == RG_I32) hipLaunchKernelGGL(regions_tile_kernel<RG_I32>, tiles, dim3(RG_THREADS), 0, st, A);
+  else if (kind == RG_I64) hipLaunchKernelGGL(regions_tile_kernel<RG_I64>, tiles, dim3(RG_THREADS), 0, st, A);
+  else hipLaunchKernelGGL(regions_tile_kernel<RG_U8>, tiles, dim3(RG_THREADS), 0, st, A);
   RG_LAUNCHED("regions_label tile launch");
   const int side = A.tiles_x > A.tiles_y ? A.tiles_x : A.tiles_y;
   for (int k = 1; (1 << (k - 1)) < side; ++k) {                                         // ceil(log2(side)) levels
     A.level = k;
     A.groups_x = cdiv(A.tiles_x, 1 << k);
     const dim3 groups((unsigned int)((int64_t)A.groups_x * cdiv(A.tiles_y, 1 << k)), (unsigned int)n);
-    if (labels_i64) hipLaunchKernelGGL(regions_merge_kernel<true>, groups, dim3(RG_THREADS), 0, st, A);
-    else hipLaunchKernelGGL(regions_merge_kernel<false>, groups, dim3(RG_THREADS), 0, st, A);
+    if (kind == RG_I32) hipLaunchKernelGGL(regions_merge_kernel<RG_I32>, groups, dim3(RG_THREADS), 0, st, A);
+    else if (kind == RG_I64) hipLaunchKernelGGL(regions_merge_kernel<RG_I64>, groups, dim3(RG_THREADS), 0, st, A);
+    else hipLaunchKernelGGL(regions_merge_kernel<RG_U8>, groups, dim3(RG_THREADS), 0, st, A);
     RG_LAUNCHED("regions_label merge launch");
   }
   const dim3 flat(rg_flat_grid(hw), (unsigned int)n);
@@ -383,6 +406,20 @@ static int rg_label(RgArgs A, int labels_i64, int n, hipStream_t st) {
   hipLaunchKernelGGL(regions_finish_kernel, flat, dim3(RG_THREADS), 0, st, A);
   RG_LAUNCHED("regions_label finish launch");
   return UDASEG_OK;
+}
+
+// common.h: the 4-connected components of checked int32 maps (superpixels.hip's connect step labels its cluster map with it)
+int regions_label_i32_launch(const int32_t* labels, int32_t* ids, int32_t* area, int n, int h, int w, int connectivity, int want_area,
+                             hipStream_t st) {
+  RgArgs A = {};
+  A.labels = labels;
+  A.ids = ids;
+  A.area = area;
+  A.h = h;
+  A.w = w;
+  A.conn8 = connectivity == 8;
+  A.want_area = want_area;
+  return rg_label(A, RG_I32, n, st);
 }
 
 }  // namespace udaseg
@@ -418,6 +455,29 @@ extern "C" int udaseg_regions_label(const void* labels, int labels_i64, int n, i
   if (area == nullptr) {
     hipError_t e = hipFreeAsync(A.area, st);
     if (rc == UDASEG_OK && e != hipSuccess) return hip_fail(e, "hipFreeAsync(regions_label)");
+  }
+  return rc;
+}
+
+extern "C" int udaseg_regions_label_i32(const int32_t* labels, int n, int h, int w, int connectivity, int32_t* ids, int32_t* area,
+                                        void* stream) {
+  if (int rc = rg_check("regions_label_i32", 0, n, h, w, 0, 0)) return rc;
+  UDASEG_CHECK_ARG(connectivity == 4 || connectivity == 8, "regions_label_i32: connectivity must be 4 or 8, got %d", connectivity);
+  UDASEG_CHECK_ARG(labels && ids, "regions_label_i32: NULL pointer (labels and ids are required)");
+  UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(area)) & 3) == 0,
+                   "regions_label_i32: labels, ids and area must be 4-byte aligned");
+  UDASEG_CHECK_ARG(static_cast<const void*>(labels) != static_cast<const void*>(ids),
+                   "regions_label_i32: ids must not be labels itself (the seams are joined by reading labels after ids is written)");
+  hipStream_t st = as_stream(stream);
+  int32_t* scratch = nullptr;
+  if (area == nullptr) {                       // the tile sizes and the tile-roots' ids still need their [n][h][w] slots
+    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&scratch), sizeof(int) * (size_t)n * h * w, st);
+    if (e != hipSuccess) return hip_fail(e, "hipMallocAsync(regions_label_i32)");
+  }
+  const int rc = regions_label_i32_launch(labels, ids, area ? area : scratch, n, h, w, connectivity, area != nullptr, st);
+  if (scratch) {
+    hipError_t e = hipFreeAsync(scratch, st);
+    if (rc == UDASEG_OK && e != hipSuccess) return hip_fail(e, "hipFreeAsync(regions_label_i32)");
   }
   return rc;
 }

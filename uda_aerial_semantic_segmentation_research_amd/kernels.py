@@ -312,6 +312,53 @@ def regions_stats(labels, ids, area, classes, ignore_index, stats, st=None):
           "regions_stats")
 
 
+def regions_label_i32(labels, connectivity, ids, area, st=None):
+    """``regions_label`` of an int32 map [n,h,w]: every value >= 0 a label of its own, a negative one void."""
+    n, h, w = getattr(labels, "shape", (0, 0, 0))
+    check(ops.udaseg_regions_label_i32(labels, n, h, w, int(connectivity), ids, area, st), "regions_label_i32")
+
+
+# ---- superpixels (superpixels.py; csrc/superpixels.hip).  ids / labels: int32 [n,h,w]; centres: int32 [n,K,6]
+def superpixel_slic(frames, step, compactness, iterations, min_area, ids, centres, counts=None, st=None):
+    """ids [n,h,w] int32 = the 4-connected integer SLIC superpixels of uint8 frames [n,h,w,3]; centres [n,K,6] int32 = the last
+    update's; counts [n,4] int64 or None += components found, absorbed, pixels relabelled, clusters left."""
+    n, h, w, _ = frames.shape
+    check(ops.udaseg_superpixel_slic(frames, n, h, w, int(step), int(compactness), int(iterations), int(min_area), ids, centres,
+                                     counts, st), "superpixel_slic")
+
+
+def superpixel_assign(frames, step, compactness, centres, labels=None, st=None):
+    """One iteration from ``centres`` (updated in place); labels [n,h,w] int32 or None = the assignment it was made from."""
+    n, h, w, _ = frames.shape
+    check(ops.udaseg_superpixel_assign(frames, n, h, w, int(step), int(compactness), centres, labels, st), "superpixel_assign")
+
+
+def superpixel_connect(labels, step, min_area, ids, counts=None, st=None):
+    """ids = the connect step of ``superpixel_slic`` alone on cluster indices of the grid of ``step`` (ids may be labels)."""
+    n, h, w = labels.shape
+    check(ops.udaseg_superpixel_connect(labels, n, h, w, int(step), int(min_area), ids, counts, st), "superpixel_connect")
+
+
+def superpixel_vote(ids, masks, clusters, classes, ignore_index, min_share, min_cover, void_label, out, counts=None, st=None):
+    """out [n,h,w] uint8 = the winning class of every pixel's superpixel, or void_label; counts [n,3] int64 or None += changed,
+    filled, voided."""
+    i64, n, h, w = _label_args(masks)
+    check(ops.udaseg_superpixel_vote(ids, masks, i64, n, h, w, int(clusters), int(classes), *_ignore_args(ignore_index),
+                                     float(min_share), float(min_cover), int(void_label), out, counts, st), "superpixel_vote")
+
+
+def superpixel_mean(values, ids, clusters, mean, st=None):
+    """mean [n,clusters] fp32 = the mean of the values in [0, 1] of every superpixel, -1 where it has none."""
+    n, h, w = ids.shape
+    check(ops.udaseg_superpixel_mean(values, ids, n, h, w, int(clusters), mean, st), "superpixel_mean")
+
+
+def superpixel_gather(ids, table, clusters, mask, st=None):
+    """mask [n,h,w] uint8 |= table[n,clusters][ids]."""
+    n, h, w = ids.shape
+    check(ops.udaseg_superpixel_gather(ids, table, n, h, w, int(clusters), mask, st), "superpixel_gather")
+
+
 # ---- CRF refinement (crf.py; csrc/crf.hip).  Score rows are padded NHWC: [pixels][ld] fp32
 def crf_tile(radius, dilation):
     """(tile height, tile width) of ``crf_step``'s blocks at this window."""

@@ -15,6 +15,7 @@ is its numpy mirror, compared for equality):
 What is made of it:
 
     ``label``          the ids, and the areas if asked for.
+    ``label_ids``      the same of an int32 map of more than 256 values (a superpixel map): a negative value is void.
     ``sieve``          a mask with ``void`` on every component smaller than ``min_area`` of its class: a teacher's isolated islands
                        of a wrong class are confident inside and survive ``boundary.erode``; this removes them (``SievedLoader``
                        applies it to the batches of ``PseudoLabeler.loader`` / ``OnlineLabeler.loader`` /
@@ -90,6 +91,25 @@ def label(labels, connectivity=4, ignore_index=None, return_area=False):
     ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
     area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)     # the labelling's own scratch when no area is asked for
     A.on_device(lab.device, K.regions_label, lab, conn, ign, ids, area)
+    if single:
+        ids, area = ids[0], area[0]
+    return (ids, area) if return_area else ids
+
+
+def label_ids(ids_i32, connectivity=4, return_area=False):
+    """``label`` of an int32 map ``[N,H,W]`` (or ``[H,W]``) of more than 256 values, such as ``superpixels.slic``'s ids: every value
+    ``>= 0`` is a label of its own and a negative value is void (there is no ``ignore_index``).  int32 ids in the map's shape (-1
+    on void pixels); with ``return_area`` the pair ``(ids, area)``."""
+    conn = _check_connectivity("label_ids", connectivity)
+    if not (torch.is_tensor(ids_i32) and ids_i32.dtype == torch.int32 and ids_i32.dim() in (2, 3) and ids_i32.numel() > 0):
+        raise ValueError(f"label_ids: ids must be a non-empty int32 [N,H,W] (or [H,W]) tensor, got "
+                         f"{getattr(ids_i32, 'dtype', type(ids_i32).__name__)} {tuple(getattr(ids_i32, 'shape', ()))}")
+    A.same_gpu("label_ids", ids=ids_i32)
+    single = ids_i32.dim() == 2
+    lab = (ids_i32[None] if single else ids_i32).contiguous()
+    ids = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)
+    area = torch.empty(lab.shape, dtype=torch.int32, device=lab.device)     # the labelling's own scratch when no area is asked for
+    A.on_device(lab.device, K.regions_label_i32, lab, conn, ids, area)
     if single:
         ids, area = ids[0], area[0]
     return (ids, area) if return_area else ids
