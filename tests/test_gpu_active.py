@@ -355,3 +355,22 @@ def test_pool_queries_twice_and_trains_on_the_sparse_masks(A):
     other = A.ActivePool(5, budget=budget)
     other.load_state_dict(state, device="cuda")
     assert all(torch.equal(other.requested[i], pool.requested[i]) for i in idx) and other.coverage() == pool.coverage()
+
+
+def test_select_counts_accumulate_per_image_and_an_image_without_candidates_adds_nothing(K):
+    """acquire_select's counters at 2 x 1500 items (two blocks an image, a ragged last wave), into a buffer that holds 5 already: image
+    0 selects by the mirror's threshold, image 1 has no candidate and keeps its 5 (no atomic is issued for it)."""
+    rs = np.random.RandomState(21)
+    key = rs.rand(2, 1500).astype(np.float32)
+    key[0, ::5] = -1.0
+    key[1] = -1.0
+    k = 300
+    sel, cnt, _ = R.select(key, k)
+    assert cnt[0, 0] >= k and cnt[0, 1] == 1200 and cnt[1].tolist() == [0, 0]
+    thr = np.array([np.sort(key[0][key[0] >= 0])[k - 1], 0.5], dtype=np.float32)
+    mask = torch.zeros((2, 1500), dtype=torch.uint8, device="cuda")
+    counts = torch.full((2, 2), 5, dtype=torch.int64, device="cuda")
+    K.acquire_select(torch.from_numpy(key).cuda(), torch.from_numpy(thr).cuda(), mask, counts)
+    assert np.array_equal(_np(mask), sel) and np.array_equal(_np(counts), 5 + cnt)
+    K.acquire_select(torch.from_numpy(key).cuda(), torch.from_numpy(thr).cuda(), mask, counts)     # nothing is new the second time
+    assert np.array_equal(_np(mask), sel) and np.array_equal(_np(counts), 5 + cnt + np.array([[0, 1200], [0, 0]]))

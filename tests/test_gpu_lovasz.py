@@ -275,3 +275,23 @@ def test_trainer_runs_with_the_lovasz_criterion(env):
     assert np.isfinite(train_loss) and train_loss > 0
     assert void > 0 and invalid == 0 and nonfinite == 0 and n + void == 2 * 64 * 64
     assert 0.0 <= float(crit.last_slack.sum()) <= 1.0 / 1024 * (1 + 1e-12) and int(crit.last_present.sum()) > 0
+
+
+def test_hist_counters_accumulate_and_a_zero_kind_issues_nothing(env):
+    """lovasz_hist's four pixel counters at 2 x 5 x 25 x 30 (1500 pixels, 750 an image: 512-thread blocks with a ragged last wave,
+    one block an image adding into the same four words), into a buffer that holds 9 already; no target is out of range and no row is
+    non-finite, so two of the four stay at 9.  Counted by the mirror's pixel_classes."""
+    K = env[0]
+    n, c, h, w, bins = 2, 5, 25, 30, 64
+    ldc, pixels = 8, n * h * w
+    g = torch.Generator().manual_seed(12)
+    buf = torch.randn(pixels, ldc, generator=g)
+    t = torch.randint(0, c, (pixels,), generator=g)
+    t[::9] = IGN
+    live, void, invalid, nonfinite = R.pixel_classes(t.numpy(), c, IGN, buf[:, :c].numpy())
+    assert void.sum() > 0 and invalid.sum() == 0 and nonfinite.sum() == 0
+    tables = torch.zeros((n, c, 2, bins), device="cuda", dtype=torch.int32)
+    counters = torch.full((4,), 9, device="cuda", dtype=torch.int64)
+    K.lovasz_hist(buf.cuda(), t.cuda(), pixels, c, ldc, IGN, n, bins, tables, counters)
+    assert counters.tolist() == [9 + int(live.sum()), 9 + int(void.sum()), 9, 9]
+    assert int(tables.sum()) == c * int(live.sum())                             # every live pixel puts one error a class

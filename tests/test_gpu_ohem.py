@@ -393,3 +393,27 @@ def test_trainer_runs_with_the_mined_loss(env):
     assert 500 <= kept <= n
     q, edge = crit.last_threshold.tolist()
     assert 0.0 <= q <= 1.0 and edge == max(q, np.float32(0.7))
+
+
+def test_conf_counters_accumulate_and_a_launch_without_events_leaves_them(env):
+    """ohem_conf's void / invalid / non-finite counters at 1500 pixels (six chunks over more than one block, a ragged last wave),
+    into a buffer that holds 11 already: first a launch in which none of the three events happens (no atomic is issued, the buffer
+    keeps its 11), then one with all three, counted by the mirror's pixel_classes."""
+    K = env[0]
+    pixels, c, ldc = 1500, 5, 8
+    g = torch.Generator().manual_seed(11)
+    buf = torch.randn(pixels, ldc, generator=g)
+    t = torch.randint(0, c, (pixels,), generator=g)
+    counters = torch.full((3,), 11, dtype=torch.int64, device="cuda")
+    hist = torch.zeros(K.KTH_BINS, dtype=torch.int64, device="cuda")
+    conf = torch.empty(pixels, device="cuda")
+    K.ohem_conf(buf.cuda(), t.cuda(), pixels, c, ldc, IGN, conf, hist, counters)
+    assert counters.tolist() == [11, 11, 11] and int(hist.sum()) == pixels
+    t[::7] = IGN
+    t[3::50] = c + 2
+    buf[5, 1] = float("inf")                                                    # pixel 5 keeps a target inside the classes
+    live, void, invalid, nonfinite = R.pixel_classes(t.numpy(), c, IGN, buf[:, :c].numpy())
+    assert void.sum() > 0 and invalid.sum() > 0 and nonfinite.sum() == 1
+    K.ohem_conf(buf.cuda(), t.cuda(), pixels, c, ldc, IGN, conf, hist, counters)
+    assert counters.tolist() == [11 + int(void.sum()), 11 + int(invalid.sum()), 12]
+    assert int(hist.sum()) == pixels + int(live.sum())

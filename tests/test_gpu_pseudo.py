@@ -379,3 +379,27 @@ def test_label_large(P, r18):
     assert torch.equal(torch.bincount(labels[kept].long(), minlength=23), tail) and int(lab.hist.nonfinite) == 0
     assert torch.equal(h.table, lab.hist.table)                      # fit_large saw the same probabilities
     assert lab.report()["kept"] == [int(v) for v in tail]
+
+
+def test_counters_accumulate_and_no_nonfinite_pixel_adds_nothing(P):
+    """The void / non-finite pair of pseudo_labels and conf_hist's non-finite count at 1030 pixels (more than one block, a ragged last
+    wave), into buffers that hold 13 already.  No pixel is non-finite, so those words keep their 13 (no atomic is issued); the kept
+    and void counts are the bincount of the labels ``test_void_label_and_unaligned_label_buffer`` holds against the module."""
+    from uda_aerial_semantic_segmentation_research_amd import kernels as K
+    from uda_aerial_semantic_segmentation_research_amd._args import padded_nhwc
+    classes, pixels, bins = 5, 1030, 256
+    x = _nchw(_logits("scaled", classes, pixels, seed=5))
+    thr = P.ConfidenceHistogram(classes, bins).update(x).thresholds(0.5, cap=1.0)
+    ref = P.pseudo_labels(x, thr, void=5, bins=bins).reshape(-1)
+    want = torch.bincount(ref.long(), minlength=classes + 1).tolist() + [0]      # kept per class, void, non-finite
+    assert want[classes] > 0
+    buf, ldc = padded_nhwc(x)
+    labels = torch.empty(pixels, dtype=torch.uint8, device="cuda")
+    counts = torch.full((classes + 2,), 13, dtype=torch.int64, device="cuda")
+    for calls in (1, 2):
+        K.pseudo_labels(buf, pixels, classes, ldc, 0, bins, thr, 5, labels, None, counts)
+        assert torch.equal(labels, ref) and counts.tolist() == [13 + calls * v for v in want]
+    table = torch.zeros(classes, bins, dtype=torch.int64, device="cuda")
+    nonfinite = torch.full((1,), 13, dtype=torch.int64, device="cuda")
+    K.conf_hist(buf, pixels, classes, ldc, 0, bins, table, nonfinite)
+    assert int(nonfinite) == 13 and int(table.sum()) == pixels

@@ -25,11 +25,12 @@
 // The counters run the truth map and then the prediction through steps 1-4 in the same block, keep the truth's band (and label)
 // of the tile in LDS between the two, count into an LDS table and flush it with one 64-bit atomic per non-zero counter: integer
 // adds, the same maps give the same bits in any order.
-#include "common.h"
+#include "label_maps.h"
 
 namespace udaseg {
 
 constexpr int BD_THREADS = 256;
+static_assert(BD_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int BD_TW = 64;                      // tile width: 16 groups of four pixels
 constexpr int BD_MAX_R = 32;
 constexpr int BD_DEAD = 0x100;                 // a void pixel or a position outside the image
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_kernel(BdArgs A) {
   uint8_t* gcol = bd_lds + G.off_g;
   uint8_t* flg = bd_lds + G.off_flg;
   float* tab = reinterpret_cast<float*>(bd_lds + G.off_extra);              // lookup: R^2 + 3 floats
-  unsigned int* ecnt = reinterpret_cast<unsigned int*>(bd_lds + G.off_extra);  // erode: 2 counters
+  BlockCounts<2>::Slots& ecnt = *reinterpret_cast<BlockCounts<2>::Slots*>(bd_lds + G.off_extra);   // erode: voided, void
   const int tid = threadIdx.x, n = blockIdx.y;
   const int R = G.R, h = G.h, w = G.w;
   const int ty0 = ((int)blockIdx.x / A.tiles_x) * G.th, tx0 = ((int)blockIdx.x % A.tiles_x) * BD_TW;
@@ -184,14 +185,13 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_kernel(BdArgs A) {
   const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)n * HW * (I64 ? 8 : 1);
   if (PRODUCT == BD_LOOKUP)
     for (int i = tid; i < R * R + 3; i += BD_THREADS) tab[i] = A.table[i];
-  if (PRODUCT == BD_ERODE && tid < 2) ecnt[tid] = 0;
-  bd_tile<I64>(G, img, nullptr, ty0, tx0, lab, flg, gcol);                  // its barriers cover the two fills above
+  bd_tile<I64>(G, img, nullptr, ty0, tx0, lab, flg, gcol);                  // its barriers cover the fill above
 
   constexpr int ELT = PRODUCT == BD_ERODE ? 1 : 4;
   uint8_t* out_img = reinterpret_cast<uint8_t*>(A.out) + (size_t)n * HW * ELT;
   // four outputs of a group go out as one access when every group of the image is whole and aligned (uniform over the block)
   const bool vec = (w & 3) == 0 && (reinterpret_cast<uintptr_t>(out_img) & (4 * ELT - 1)) == 0;
-  unsigned int n_voided = 0, n_void = 0;
+  unsigned int ev[2] = {0, 0};                                               // voided, void
   bd_rows(G, gcol, [&](int y, int x0, const int (&d2)[4]) {
     const int gy = ty0 + y, gx = tx0 + x0;
     if (gy >= h || gx >= w) return;
@@ -226,10 +226,10 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_kernel(BdArgs A) {
         const int l = lc[e];
         if (l == BD_DEAD) {                                                  // void: its label is ignore_index
           o[e] = (unsigned int)G.ignore_index;
-          if (e < cnt) ++n_void;
+          if (e < cnt) ++ev[1];
         } else if (d2[e] <= R * R) {
           o[e] = (unsigned int)A.void_label;
-          if (e < cnt) ++n_voided;
+          if (e < cnt) ++ev[0];
         } else {
           o[e] = (unsigned int)l;
         }
@@ -244,16 +244,7 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_kernel(BdArgs A) {
       }
     }
   });
-  if (PRODUCT == BD_ERODE && A.counts) {
-    n_voided = wave_sum_u32(n_voided);
-    n_void = wave_sum_u32(n_void);
-    if ((tid & 63) == 0) {
-      if (n_voided) atomicAdd(&ecnt[0], n_voided);
-      if (n_void) atomicAdd(&ecnt[1], n_void);
-    }
-    __syncthreads();
-    if (tid < 2 && ecnt[tid]) atomicAdd(&A.counts[(size_t)n * 2 + tid], (unsigned long long)ecnt[tid]);
-  }
+  if (PRODUCT == BD_ERODE && A.counts) BlockCounts<2>::add(ecnt, ev, A.counts + (size_t)n * 2);   // uniform over the block
 }
 
 template <bool I64>
@@ -311,13 +302,10 @@ __global__ __launch_bounds__(BD_THREADS) void boundary_stats_kernel(BdArgs A) {
 
 // the argument rules every entry point shares; 0 or UDASEG_E_BADARG with the message set
 static int bd_check(const char* who, int labels_i64, int n, int h, int w, int radius, int has_ignore, int ignore_index) {
-  UDASEG_CHECK_ARG(labels_i64 == 0 || labels_i64 == 1, "%s: labels_i64 must be 0 (uint8) or 1 (int64), got %d", who, labels_i64);
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "%s: need 0 < n <= 65535 (n=%d)", who, n);
-  UDASEG_CHECK_ARG(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), "%s: need h, w >= 1 and h * w < 2^31 (h=%d w=%d)", who, h, w);
+  if (int rc = map_storage_ok(who, "labels_i64", labels_i64)) return rc;
+  if (int rc = map_extent_ok(who, n, h, w)) return rc;
   UDASEG_CHECK_ARG(radius >= 0 && radius <= BD_MAX_R, "%s: need 0 <= radius <= %d (radius=%d)", who, BD_MAX_R, radius);
-  UDASEG_CHECK_ARG(has_ignore == 0 || has_ignore == 1, "%s: has_ignore must be 0 or 1, got %d", who, has_ignore);
-  UDASEG_CHECK_ARG(ignore_index >= 0 && ignore_index <= 255, "%s: ignore_index must lie in [0, 255] (ignore_index=%d)", who, ignore_index);
-  return UDASEG_OK;
+  return map_ignore_ok(who, has_ignore, ignore_index);
 }
 
 template <typename K>
@@ -339,13 +327,17 @@ static int bd_launch(const char* who, K kern, std::atomic<bool>* attr_done, BdAr
 template <int PRODUCT>
 static int bd_product(const char* who, const void* labels, int labels_i64, int n, int h, int w, int radius, int has_ignore,
                       int ignore_index, BdArgs& A, size_t extra, void* stream) {
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "%s: int64 labels must be 8-byte aligned", who);
+  if (int rc = map_aligned_ok(who, "labels", labels_i64, labels)) return rc;
   A.labels = labels;
   A.truth = nullptr;
   A.G = bd_geom(h, w, radius, bd_tile_h(radius, false), has_ignore, ignore_index);
   static std::atomic<bool> attr_done[2] = {{false}, {false}};
-  if (labels_i64) return bd_launch(who, boundary_kernel<true, PRODUCT>, &attr_done[1], A, n, extra, as_stream(stream));
-  return bd_launch(who, boundary_kernel<false, PRODUCT>, &attr_done[0], A, n, extra, as_stream(stream));
+  return dispatch_flags(
+      [&](auto i64) {
+        return bd_launch(who, boundary_kernel<decltype(i64)::value, PRODUCT>, &attr_done[decltype(i64)::value], A, n, extra,
+                         as_stream(stream));
+      },
+      labels_i64 != 0);
 }
 
 }  // namespace udaseg
@@ -391,7 +383,7 @@ extern "C" int udaseg_boundary_erode(const void* labels, int labels_i64, int n, 
   A.counts = reinterpret_cast<unsigned long long*>(counts);
   A.void_label = void_label;
   return bd_product<BD_ERODE>("boundary_erode launch", labels, labels_i64, n, h, w, radius, has_ignore, ignore_index, A,
-                              2 * sizeof(unsigned int), stream);
+                              sizeof(BlockCounts<2>::Slots), stream);
 }
 
 extern "C" int udaseg_boundary_stats(const void* pred, const void* truth, int labels_i64, int n, int h, int w, int radius,
@@ -401,9 +393,7 @@ extern "C" int udaseg_boundary_stats(const void* pred, const void* truth, int la
   UDASEG_CHECK_ARG(pred && truth && stats && trimap, "boundary_stats: NULL pointer (pred, truth, stats and trimap are required)");
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(trimap)) & 7) == 0,
                    "boundary_stats: stats and trimap must be 8-byte aligned");
-  if (labels_i64)
-    UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(truth)) & 7) == 0,
-                     "boundary_stats: int64 pred / truth must be 8-byte aligned");
+  if (int rc = map_aligned_ok("boundary_stats", "pred / truth", labels_i64, pred, truth)) return rc;
   BdArgs A = {};
   A.labels = pred;
   A.truth = truth;
@@ -413,6 +403,10 @@ extern "C" int udaseg_boundary_stats(const void* pred, const void* truth, int la
   A.G = bd_geom(h, w, radius, bd_tile_h(radius, true), has_ignore, ignore_index);
   const size_t extra = sizeof(unsigned int) * (size_t)(3 * classes + 2) + sizeof(unsigned short) * (size_t)(A.G.th * BD_TW);
   static std::atomic<bool> attr_done[2] = {{false}, {false}};
-  if (labels_i64) return bd_launch("boundary_stats launch", boundary_stats_kernel<true>, &attr_done[1], A, n, extra, as_stream(stream));
-  return bd_launch("boundary_stats launch", boundary_stats_kernel<false>, &attr_done[0], A, n, extra, as_stream(stream));
+  return dispatch_flags(
+      [&](auto i64) {
+        return bd_launch("boundary_stats launch", boundary_stats_kernel<decltype(i64)::value>, &attr_done[decltype(i64)::value], A, n,
+                         extra, as_stream(stream));
+      },
+      labels_i64 != 0);
 }

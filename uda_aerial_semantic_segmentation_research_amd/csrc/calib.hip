@@ -48,28 +48,12 @@ __device__ __forceinline__ PixelConf pixel_conf_at(const float* __restrict__ row
   return r;
 }
 
-// this block's void / non-finite pixel counts into counters[1], counters[2]: one integer atomic per non-zero counter.
-// red: 8 words of LDS.  One barrier, reached by every thread of the 256.
-__device__ __forceinline__ void flush_pixel_counters(unsigned int nvoid, unsigned int nbad, unsigned int (&red)[2][4],
-                                                     unsigned long long* __restrict__ counters) {
-  nvoid = wave_sum_u32(nvoid);
-  nbad = wave_sum_u32(nbad);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = nvoid;
-    red[1][threadIdx.x >> 6] = nbad;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const unsigned int n = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    if (n) atomicAdd(counters + 1 + threadIdx.x, (unsigned long long)n);
-  }
-}
-
 // The block's cells live in LDS, [classes][bins] <= 32 x 64 = 2048 of them: 32-bit count and correct, 64-bit conf_q (32 KiB).  One
 // cell per pixel (score_hist_kernel has one per class), so no class groups.  Few, long blocks: a block flushes three 64-bit global
 // atomics per NON-EMPTY cell, so its pixel count has to be large against its cell count.
 constexpr int CH_CELLS = 2048;
 constexpr int CH_THREADS = 256;
+static_assert(CH_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int CH_BLOCKS = 512;
 
 template <int NV>
@@ -80,7 +64,7 @@ __global__ __launch_bounds__(CH_THREADS) void calib_hist_kernel(const float* __r
                                                                 unsigned long long* __restrict__ counters) {
   __shared__ unsigned int cnt[CH_CELLS], cor[CH_CELLS];
   __shared__ unsigned long long cq[CH_CELLS];
-  __shared__ unsigned int cred[2][4];
+  __shared__ BlockCounts<3>::Slots cred;
   const int cells = classes * bins;                        // <= CH_CELLS (checked by the entry point)
   for (int i = threadIdx.x; i < cells; i += CH_THREADS) {
     cnt[i] = 0;
@@ -111,7 +95,8 @@ __global__ __launch_bounds__(CH_THREADS) void calib_hist_kernel(const float* __r
     atomicAdd(&cq[cell], (unsigned long long)__float2uint_rn(r.p * 16777216.f));
     ++nval;
   }
-  flush_pixel_counters(nvoid, nbad, cred, counters);       // its barrier also closes the LDS tables
+  const unsigned int ev[3] = {nval, nvoid, nbad};         // counters[0]: the pixels in the tables
+  BlockCounts<3>::add(cred, ev, counters);                 // its barrier also closes the LDS tables
   const size_t plane = (size_t)cells;
   for (int i = threadIdx.x; i < cells; i += CH_THREADS) {
     const unsigned int n = cnt[i];
@@ -121,9 +106,6 @@ __global__ __launch_bounds__(CH_THREADS) void calib_hist_kernel(const float* __r
       atomicAdd(&tables[2 * plane + i], cq[i]);
     }
   }
-  // counters[0]: the pixels in the tables
-  nval = wave_sum_u32(nval);
-  if ((threadIdx.x & 63) == 0 && nval) atomicAdd(counters, (unsigned long long)nval);
 }
 
 // One block of 64 threads.  Thread b < bins sums bin b over the classes in class order, thread c < classes walks class c's bins in
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(256) void calib_nll_kernel(const float* __restrict_
                                                         int64_t pixels, int classes, int ldc, const float* __restrict__ inv_temp,
                                                         double* __restrict__ partials, unsigned long long* __restrict__ counters) {
   __shared__ double red[4][4];
-  __shared__ unsigned int cred[2][4];
+  __shared__ BlockCounts<2>::Slots cred;
   const float beta = load_beta(inv_temp);
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   unsigned int nvoid = 0, nbad = 0;
@@ -248,8 +230,10 @@ __global__ __launch_bounds__(256) void calib_nll_kernel(const float* __restrict_
       ++nbad;
     }
   }
-  block_partial_rows<4>(acc, red, partials);
-  flush_pixel_counters(nvoid, nbad, cred, counters);
+  const unsigned int ev[2] = {nvoid, nbad};
+  BlockCounts<2>::put(cred, ev);
+  block_partial_rows<4>(acc, red, partials);               // its barrier is the counters' too
+  BlockCounts<2>::flush(cred, counters + 1);               // counters[1], counters[2]
 }
 
 // single wave over partials[4][n]: lane l sums partials[k][l], partials[k][l + 64], ..., then wave_sum_d; sums[k] += that

@@ -82,16 +82,6 @@ __device__ __forceinline__ int fast_div(int n, int d, float rcp) {
   return q;
 }
 
-// Pixel p of a label map, uint8 or int64: an int64 value outside [0, 255] reads as 255 (boundary.hip, window.hip).
-template <bool I64>
-__device__ __forceinline__ int label_at(const void* __restrict__ img, int64_t p) {
-  if (I64) {
-    const long long v = reinterpret_cast<const long long*>(img)[p];
-    return (v < 0 || v > 255) ? 255 : (int)v;
-  }
-  return reinterpret_cast<const uint8_t*>(img)[p];
-}
-
 __device__ __forceinline__ float act_apply(float x, int act, float slope) {
   return (act == UDASEG_ACT_LEAKY && x < 0.f) ? x * slope : x;
 }
@@ -116,6 +106,46 @@ __device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v) {
   for (int o = 32; o > 0; o >>= 1) v += (unsigned int)__shfl_xor((int)v, o, 64);
   return v;
 }
+
+// The block event counter: K per-thread counts of events (void pixels, non-finite pixels, changed labels ...) become one 64-bit
+// atomicAdd per block and NON-ZERO counter.  THE one definition: thread -> wave is wave_sum_u32, wave -> block is one LDS slot per
+// counter and wave, summed by one thread in wave order -- no zeroing pass, no LDS atomic; integers, so any order gives the same bits.
+// The kernel declares the slots, so that its LDS reads off its own source, and checks WAVES against its own thread count:
+//   static_assert(XX_THREADS == 64 * 4);   __shared__ typename BlockCounts<K>::Slots slots;
+// put and flush are apart so that a kernel with a barrier of its own between them (the one that closes its LDS tables) shares it;
+// total is for a destination that is not dst[k].  Every barrier is reached by all threads of the block or by none (loss_reduce.h's
+// rule): a caller keeps its own conditions around put, the barrier, flush and add uniform over the block.
+template <int K, int WAVES = 4>
+struct BlockCounts {
+  typedef unsigned int Slots[K][WAVES];
+  // every thread of the block: its wave's sums into the wave's slots.  No barrier.
+  static __device__ __forceinline__ void put(Slots& slots, const unsigned int (&v)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const unsigned int s = wave_sum_u32(v[k]);
+      if ((threadIdx.x & 63) == 0) slots[k][threadIdx.x >> 6] = s;
+    }
+  }
+  // after a barrier: the block's count k
+  static __device__ __forceinline__ unsigned int total(const Slots& slots, int k) {
+    unsigned int n = 0;
+#pragma unroll
+    for (int wv = 0; wv < WAVES; ++wv) n += slots[k][wv];
+    return n;
+  }
+  // after a barrier: thread k < K adds count k to dst[k] (per-image counters pass dst + image * K)
+  static __device__ __forceinline__ void flush(const Slots& slots, unsigned long long* __restrict__ dst) {
+    if (threadIdx.x < K) {
+      const unsigned int n = total(slots, threadIdx.x);
+      if (n) atomicAdd(dst + threadIdx.x, (unsigned long long)n);
+    }
+  }
+  static __device__ __forceinline__ void add(Slots& slots, const unsigned int (&v)[K], unsigned long long* __restrict__ dst) {
+    put(slots, v);
+    __syncthreads();
+    flush(slots, dst);
+  }
+};
 
 // Fold per-thread V-channel partials over the rows of a block, then one atomic per channel per block with CONSECUTIVE LANES ON
 // CONSECUTIVE CHANNELS: one atomic instruction then covers 64 adjacent words (4-8 cache lines).  (The first form had the owner

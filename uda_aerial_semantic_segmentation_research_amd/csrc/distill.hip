@@ -199,8 +199,8 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const f32x4* __restrict__ 
   if (stats) {
 #pragma unroll
     for (int k = 0; k < DS_STATS; ++k) {
-      const unsigned int n = wave_sum_u32(cnt[k]);
-      if ((tid & 63) == 0 && n) atomicAdd(&stats[k], (unsigned long long)n);
+      const unsigned int n = wave_sum_u32(cnt[k]);       // per wave, not BlockCounts: the kernel sits at a register cliff
+      if ((tid & 63) == 0 && n) atomicAdd(&stats[k], (unsigned long long)n);   // (profiles/loss_reduce_refactor.txt)
     }
   }
   if (colpart && tid < LDC) {
@@ -238,23 +238,18 @@ template <int NV>
 __global__ __launch_bounds__(256) void conf_share_kernel(const float* __restrict__ scores, int64_t ppi, int classes, int ldc, int probs,
                                                          float tau, unsigned long long* __restrict__ above,
                                                          unsigned long long* __restrict__ nonfinite) {
-  __shared__ unsigned int red[2][4];
+  __shared__ BlockCounts<2>::Slots red;                    // 256 threads: four waves
   const float* img = scores + (int64_t)blockIdx.y * ppi * ldc;
-  unsigned int na = 0, nb = 0;
+  unsigned int ev[2] = {0, 0};                             // above tau, non-finite
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < ppi; p += (int64_t)gridDim.x * 256) {
     const PixelConf r = pixel_conf<NV>(img + p * ldc, classes, probs);
-    na += r.finite && r.p >= tau;
-    nb += !r.finite;
+    ev[0] += r.finite && r.p >= tau;
+    ev[1] += !r.finite;
   }
-  na = wave_sum_u32(na);
-  nb = wave_sum_u32(nb);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = na;
-    red[1][threadIdx.x >> 6] = nb;
-  }
+  BlockCounts<2>::put(red, ev);
   __syncthreads();
-  if (threadIdx.x < 2) {
-    const unsigned int n = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  if (threadIdx.x < 2) {                                   // two arrays, so total and not flush
+    const unsigned int n = BlockCounts<2>::total(red, threadIdx.x);
     if (n) atomicAdd((threadIdx.x ? nonfinite : above) + blockIdx.y, (unsigned long long)n);
   }
 }

@@ -42,6 +42,7 @@ constexpr int FS_KB = 8;                            // kv per reduction batch
 constexpr int FC_THREADS = 128;                     // delta, amplitude
 constexpr int FT_THREADS = 256, FT_TILE = 16, FT_Y = 64;   // column stage: a 16 x 16 tile of (ku, kv) per block, y per staged chunk
 constexpr int FA_THREADS = 256;                     // streaming pass
+static_assert(FA_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int FA_ROWS = 32, FA_COLS = 64, FA_RPL = 8;   // tile; rows per lane (FA_ROWS = 4 waves * FA_RPL)
 constexpr int FA_UC = 32;                           // u per staged twiddle chunk
 constexpr int FA_PITCH = FA_COLS * 3;               // 192 bytes: a multiple of 16
@@ -278,9 +279,8 @@ __global__ __launch_bounds__(FA_THREADS) void fda_apply_kernel(const uint8_t* __
                                                                float* __restrict__ field, unsigned long long* __restrict__ counts) {
   __shared__ float tw[FA_UC][FA_ROWS][2];
   __shared__ __attribute__((aligned(16))) uint8_t tile[FA_ROWS * FA_PITCH];
-  __shared__ unsigned int cnt[2];
+  __shared__ BlockCounts<2>::Slots cnt;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 2) cnt[tid] = 0;
   const int tx = blockIdx.x % tiles_x;
   const int rest = blockIdx.x / tiles_x;
   const int ty = rest % tiles_y, i = rest / tiles_y;
@@ -338,8 +338,8 @@ __global__ __launch_bounds__(FA_THREADS) void fda_apply_kernel(const uint8_t* __
       }
     }
   }
-  __syncthreads();                                                          // the tile is staged (and cnt zeroed)
-  unsigned int below = 0, above = 0;
+  __syncthreads();                                                          // the tile is staged
+  unsigned int ev[2] = {0, 0};                                              // below 0, above 255
 #pragma unroll
   for (int r = 0; r < FA_RPL; ++r) {
     const int row = wave * FA_RPL + r;
@@ -347,23 +347,16 @@ __global__ __launch_bounds__(FA_THREADS) void fda_apply_kernel(const uint8_t* __
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float v = (float)tile[row * FA_PITCH + lane * 3 + c] + acc[r][c];
-        below += v < 0.f ? 1u : 0u;
-        above += v > 255.f ? 1u : 0u;
+        ev[0] += v < 0.f ? 1u : 0u;
+        ev[1] += v > 255.f ? 1u : 0u;
         if (field) field[base + ((size_t)row * w + lane) * 3 + c] = v;
         tile[row * FA_PITCH + lane * 3 + c] = (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f);   // round half to even, then clamp
       }
     }
   }
-  if (counts) {
-    below = wave_sum_u32(below);
-    above = wave_sum_u32(above);
-    if (lane == 0) {
-      if (below) atomicAdd(&cnt[0], below);
-      if (above) atomicAdd(&cnt[1], above);
-    }
-  }
-  __syncthreads();
-  if (counts && tid < 2 && cnt[tid]) atomicAdd(&counts[(size_t)i * 2 + tid], (unsigned long long)cnt[tid]);
+  if (counts) BlockCounts<2>::put(cnt, ev);
+  __syncthreads();                                                          // the tile holds the output bytes; closes the slots
+  if (counts) BlockCounts<2>::flush(cnt, counts + (size_t)i * 2);
   if (!out) return;
   if (WIDE) {
     const int cpr = rb >> 4;

@@ -78,6 +78,7 @@ static inline bool lovasz_bins_ok(int bins) { return bins >= 64 && bins <= 4096 
 constexpr int LH_CELLS = 16384;
 constexpr int LH_THREADS = 512;
 constexpr int LH_TOTAL_BLOCKS = 512;
+typedef BlockCounts<4, LH_THREADS / 64> LhKinds;          // the four pixel kinds, eight waves a block
 
 template <int LDC4>
 __global__ __launch_bounds__(LH_THREADS) void lovasz_hist_kernel(const f32x4* __restrict__ logits, const int64_t* __restrict__ target,
@@ -86,13 +87,12 @@ __global__ __launch_bounds__(LH_THREADS) void lovasz_hist_kernel(const f32x4* __
                                                                  unsigned long long* __restrict__ counters) {
   constexpr int LDC = LDC4 * 4;
   __shared__ unsigned int hist[LH_CELLS];
-  __shared__ unsigned int cnt[4];
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ LhKinds::Slots cnt;
+  const int tid = threadIdx.x;
   const int c0 = blockIdx.y * cg;
   const int nc = min(cg, classes - c0);
   const int cells = nc * 2 * bins;                       // <= LH_CELLS
   for (int i = tid; i < cells; i += LH_THREADS) hist[i] = 0;
-  if (tid < 4) cnt[tid] = 0;
   __syncthreads();
   const int64_t base = (int64_t)blockIdx.z * ppi;
   unsigned int kinds[4] = {0, 0, 0, 0};
@@ -120,20 +120,14 @@ __global__ __launch_bounds__(LH_THREADS) void lovasz_hist_kernel(const f32x4* __
       }
     }
   }
-  if (blockIdx.y == 0) {                                  // every class group sees the same pixels: the first one counts them
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned int s = wave_sum_u32(kinds[k]);
-      if (lane == 0 && s) atomicAdd(&cnt[k], s);
-    }
-  }
-  __syncthreads();
+  if (blockIdx.y == 0) LhKinds::put(cnt, kinds);          // every class group sees the same pixels: the first one counts them
+  __syncthreads();                                        // closes the histogram and the slots
   unsigned int* dst = tables + ((size_t)blockIdx.z * classes + c0) * 2 * bins;    // the group's cells are contiguous there
   for (int i = tid; i < cells; i += LH_THREADS) {
     const unsigned int n = hist[i];
     if (n) atomicAdd(&dst[i], n);
   }
-  if (blockIdx.y == 0 && tid < 4 && cnt[tid]) atomicAdd(&counters[tid], (unsigned long long)cnt[tid]);
+  if (blockIdx.y == 0) LhKinds::flush(cnt, counters);
 }
 
 // ---- the coefficient tables ------------------------------------------------------------------------------------------------

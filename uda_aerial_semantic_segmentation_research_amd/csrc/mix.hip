@@ -19,6 +19,7 @@ namespace udaseg {
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MIX_THREADS = 256;
+static_assert(MIX_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int MIX_MAX_BLOCKS = 2048;
 constexpr int SEL_THREADS = 64;
 
@@ -72,29 +73,13 @@ __device__ __forceinline__ bool mix_pasted(const MixBlock& k, uint32_t s, int y,
   return cls || (y >= k.box.y0 && y < k.box.y1 && x >= k.box.x0 && x < k.box.x1);
 }
 
-__device__ __forceinline__ void mix_flush(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int* cnt,
-                                          unsigned long long* __restrict__ counts, int i) {
-  c0 = wave_sum_u32(c0);
-  c1 = wave_sum_u32(c1);
-  c2 = wave_sum_u32(c2);
-  if ((threadIdx.x & 63) == 0) {
-    if (c0) atomicAdd(&cnt[0], c0);
-    if (c1) atomicAdd(&cnt[1], c1);
-    if (c2) atomicAdd(&cnt[2], c2);
-  }
-  __syncthreads();
-  if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[(size_t)i * 3 + threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
-}
-
 __global__ __launch_bounds__(MIX_THREADS) void classmix_wide_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ src_masks,
                                                                     const uint8_t* __restrict__ tgt, const uint8_t* __restrict__ tgt_masks,
                                                                     const int32_t* __restrict__ sel, const int32_t* __restrict__ boxes,
                                                                     int hw, int w, int bx, int classes, int void_label,
                                                                     uint8_t* __restrict__ out, uint8_t* __restrict__ out_masks,
                                                                     unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int cnt[3];
-  if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
-  __syncthreads();
+  __shared__ BlockCounts<3>::Slots cnt;
   const MixBlock k = mix_block(sel, boxes, bx, classes);
   const size_t base = (size_t)k.i * hw;                                   // hw % 16 == 0: every chunk below is 16-byte aligned
   const u32x4* ps = reinterpret_cast<const u32x4*>(src + base * 3);
@@ -156,7 +141,8 @@ __global__ __launch_bounds__(MIX_THREADS) void classmix_wide_kernel(const uint8_
     c1 += __popc(~pasted & valid);
     done += 16;
   }
-  if (counts) mix_flush(c0, c1, (unsigned int)done - c0 - c1, cnt, counts, k.i);
+  const unsigned int ev[3] = {c0, c1, (unsigned int)done - c0 - c1};
+  if (counts) BlockCounts<3>::add(cnt, ev, counts + (size_t)k.i * 3);     // uniform over the block
 }
 
 __global__ __launch_bounds__(MIX_THREADS) void classmix_scalar_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ src_masks,
@@ -165,9 +151,7 @@ __global__ __launch_bounds__(MIX_THREADS) void classmix_scalar_kernel(const uint
                                                                       int hw, int w, int bx, int classes, int void_label,
                                                                       uint8_t* __restrict__ out, uint8_t* __restrict__ out_masks,
                                                                       unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int cnt[3];
-  if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
-  __syncthreads();
+  __shared__ BlockCounts<3>::Slots cnt;
   const MixBlock k = mix_block(sel, boxes, bx, classes);
   const size_t base = (size_t)k.i * hw;
   unsigned int c0 = 0, c1 = 0, c2 = 0;
@@ -186,7 +170,8 @@ __global__ __launch_bounds__(MIX_THREADS) void classmix_scalar_kernel(const uint
     else if ((int)t < classes) ++c1;
     else ++c2;
   }
-  if (counts) mix_flush(c0, c1, c2, cnt, counts, k.i);
+  const unsigned int ev[3] = {c0, c1, c2};
+  if (counts) BlockCounts<3>::add(cnt, ev, counts + (size_t)k.i * 3);     // uniform over the block
 }
 
 static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {

@@ -83,12 +83,11 @@ __global__ __launch_bounds__(256) void ohem_conf_kernel(const float* __restrict_
                                                         float* __restrict__ conf, unsigned long long* __restrict__ hist0,
                                                         unsigned long long* __restrict__ counters) {
   __shared__ unsigned int cells[KTH_BINS];
-  __shared__ unsigned int cnt[3];
+  __shared__ BlockCounts<3>::Slots cnt;                    // 256 threads: four waves
   const int tid = threadIdx.x;
   for (int i = tid; i < KTH_BINS; i += 256) cells[i] = 0;
-  if (tid < 3) cnt[tid] = 0;
   __syncthreads();
-  unsigned int nvoid = 0, ninvalid = 0, nbad = 0;
+  unsigned int ev[3] = {0, 0, 0};                          // void, invalid, non-finite
   const int64_t nchunks = (pixels + 255) / 256;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int64_t p = chunk * 256 + tid;
@@ -97,9 +96,9 @@ __global__ __launch_bounds__(256) void ohem_conf_kernel(const float* __restrict_
     if (p < pixels) {
       const int64_t t64 = target[p];
       if (has_ignore && t64 == ignore_index) {
-        ++nvoid;
+        ++ev[0];
       } else if ((uint64_t)t64 >= (uint64_t)classes) {
-        ++ninvalid;
+        ++ev[1];
       } else {
         const int t = (int)t64;
         f32x4 v[NV];
@@ -120,24 +119,17 @@ __global__ __launch_bounds__(256) void ohem_conf_kernel(const float* __restrict_
           c = expf(zt - m) / exp_sum<NV>(v, classes, m);
           ok = true;
         } else {
-          ++nbad;
+          ++ev[2];
         }
       }
       conf[p] = c;
     }
     wave_hist_add(cells, ok, (int)(__builtin_bit_cast(unsigned, c) >> 20) & (KTH_BINS - 1));
   }
-  nvoid = wave_sum_u32(nvoid);
-  ninvalid = wave_sum_u32(ninvalid);
-  nbad = wave_sum_u32(nbad);
-  if ((tid & 63) == 0) {
-    if (nvoid) atomicAdd(&cnt[0], nvoid);
-    if (ninvalid) atomicAdd(&cnt[1], ninvalid);
-    if (nbad) atomicAdd(&cnt[2], nbad);
-  }
-  __syncthreads();
+  BlockCounts<3>::put(cnt, ev);
+  __syncthreads();                                         // closes the cells and the slots
   flush_cells(cells, hist0);
-  if (tid < 3 && cnt[tid]) atomicAdd(&counters[tid], (unsigned long long)cnt[tid]);
+  BlockCounts<3>::flush(cnt, counters);
 }
 
 // Thread i of a trip holds the four consecutive values 4 i .. 4 i + 3 (VEC: one 16-byte load; values 16-byte aligned).

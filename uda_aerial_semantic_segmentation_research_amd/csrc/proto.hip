@@ -139,6 +139,8 @@ __global__ __launch_bounds__(PaShape<DV>::threads) void proto_accumulate_kernel(
       atomicAdd(&cnt[key], 1u);
     }
   }
+  // Written out, not BlockCounts (common.h): the two counts are wave sums already (ballots, in scalar registers), and carried through
+  // BlockCounts::put the register allocation of DV = 7 and 9 moved from three waves a SIMD to two (profiles/block_counts_refactor.txt).
   if (lane == 0) {
     if (nvoid) atomicAdd(&cnt[32], nvoid);
     if (nbad) atomicAdd(&cnt[33], nbad);

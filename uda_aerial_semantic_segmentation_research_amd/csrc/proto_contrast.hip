@@ -224,8 +224,8 @@ __global__ __launch_bounds__(PC_THREADS) void proto_contrast_kernel(const float*
   if (stats) {
 #pragma unroll
     for (int s = 0; s < PC_STATS; ++s) {
-      const unsigned int n = wave_sum_u32(cnt[s]);
-      if ((tid & 63) == 0 && n) atomicAdd(&stats[s], (unsigned long long)n);
+      const unsigned int n = wave_sum_u32(cnt[s]);       // per wave, not BlockCounts: that cost +33 instructions a variant
+      if ((tid & 63) == 0 && n) atomicAdd(&stats[s], (unsigned long long)n);   // (profiles/loss_reduce_refactor.txt)
     }
   }
 }

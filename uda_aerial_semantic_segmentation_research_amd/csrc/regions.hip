@@ -25,11 +25,12 @@
 // No block reads a word that another block of the same launch writes; the hand-off between blocks is the launch boundary.  Within
 // a block unions are atomicMin and every find reads ids with a relaxed agent-scope atomic load (L2-served, never a stale L1 line).
 // There are no flags, spin-waits or inter-block counters.  The ids are unique, so two runs give the same bits in any order.
-#include "common.h"
+#include "label_maps.h"
 
 namespace udaseg {
 
 constexpr int RG_THREADS = 256;
+static_assert(RG_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int RG_TH = 64, RG_TW = 64;          // tile: 4096 pixels, 16 per thread; a wave owns one tile row per trip
 constexpr int RG_TILE = RG_TH * RG_TW;
 constexpr int RG_DEAD = 0x100;                 // a void pixel or a position outside the image
@@ -54,17 +55,11 @@ constexpr size_t rg_bytes() { return KIND == RG_I64 ? 8 : KIND == RG_I32 ? 4 : 1
 
 template <int KIND>
 __device__ __forceinline__ int rg_load(const void* __restrict__ img, int64_t p, int has_ignore, int ignore_index) {
-  int v;
   if (KIND == RG_I32) {
-    v = reinterpret_cast<const int*>(img)[p];
+    const int v = reinterpret_cast<const int*>(img)[p];
     return v < 0 ? -1 : v;
   }
-  if (KIND == RG_I64) {
-    const long long q = reinterpret_cast<const long long*>(img)[p];
-    v = (q < 0 || q > 255) ? 255 : (int)q;
-  } else {
-    v = reinterpret_cast<const uint8_t*>(img)[p];
-  }
+  const int v = label_at<KIND == RG_I64>(img, p);
   return (has_ignore && v == ignore_index) ? RG_DEAD : v;
 }
 
@@ -292,7 +287,7 @@ struct RgScanArgs {
 template <bool I64>
 __global__ __launch_bounds__(RG_THREADS) void regions_sieve_kernel(RgScanArgs A) {
   __shared__ int min_area[256];
-  __shared__ unsigned int cnt[3];
+  __shared__ BlockCounts<3>::Slots cnt;
   const int tid = threadIdx.x;
   const int64_t HW = (int64_t)A.h * A.w;
   const uint8_t* img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)blockIdx.y * HW * (I64 ? 8 : 1);
@@ -300,9 +295,8 @@ __global__ __launch_bounds__(RG_THREADS) void regions_sieve_kernel(RgScanArgs A)
   const int* area = A.area + (size_t)blockIdx.y * HW;
   uint8_t* out = A.out + (size_t)blockIdx.y * HW;
   min_area[tid] = A.min_area[tid];             // RG_THREADS == 256 entries
-  if (tid < 3) cnt[tid] = 0;
   __syncthreads();
-  unsigned int voided = 0, removed = 0, kept = 0;
+  unsigned int ev[3] = {0, 0, 0};              // voided pixels, removed components, kept components
   for (int64_t p = (int64_t)blockIdx.x * RG_THREADS + tid; p < HW; p += (int64_t)gridDim.x * RG_THREADS) {
     const int l = rg_load<I64>(img, p, 0, 0);
     int o = l;
@@ -311,25 +305,15 @@ __global__ __launch_bounds__(RG_THREADS) void regions_sieve_kernel(RgScanArgs A)
       const bool root = ids[p] == (int)p;
       if (small) {
         o = A.void_label;
-        ++voided;
+        ++ev[0];
       }
-      removed += root && small;
-      kept += root && !small;
+      ev[1] += root && small;
+      ev[2] += root && !small;
     }
     out[p] = (uint8_t)o;
   }
-  if (A.counts) {                              // a block sees fewer than 2^32 pixels: gridDim.x covers HW < 2^31 of them
-    voided = wave_sum_u32(voided);
-    removed = wave_sum_u32(removed);
-    kept = wave_sum_u32(kept);
-    if ((tid & 63) == 0) {
-      if (voided) atomicAdd(&cnt[0], voided);
-      if (removed) atomicAdd(&cnt[1], removed);
-      if (kept) atomicAdd(&cnt[2], kept);
-    }
-    __syncthreads();
-    if (tid < 3 && cnt[tid]) atomicAdd(&A.counts[(size_t)blockIdx.y * 3 + tid], (unsigned long long)cnt[tid]);
-  }
+  // a block sees fewer than 2^32 pixels: gridDim.x covers HW < 2^31 of them
+  if (A.counts) BlockCounts<3>::add(cnt, ev, A.counts + (size_t)blockIdx.y * 3);
 }
 
 template <bool I64>
@@ -364,12 +348,9 @@ __global__ __launch_bounds__(RG_THREADS) void regions_stats_kernel(RgScanArgs A)
 
 // the argument rules every entry point shares; 0 or UDASEG_E_BADARG with the message set
 static int rg_check(const char* who, int labels_i64, int n, int h, int w, int has_ignore, int ignore_index) {
-  UDASEG_CHECK_ARG(labels_i64 == 0 || labels_i64 == 1, "%s: labels_i64 must be 0 (uint8) or 1 (int64), got %d", who, labels_i64);
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "%s: need 0 < n <= 65535 (n=%d)", who, n);
-  UDASEG_CHECK_ARG(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), "%s: need h, w >= 1 and h * w < 2^31 (h=%d w=%d)", who, h, w);
-  UDASEG_CHECK_ARG(has_ignore == 0 || has_ignore == 1, "%s: has_ignore must be 0 or 1, got %d", who, has_ignore);
-  UDASEG_CHECK_ARG(ignore_index >= 0 && ignore_index <= 255, "%s: ignore_index must lie in [0, 255] (ignore_index=%d)", who, ignore_index);
-  return UDASEG_OK;
+  if (int rc = map_storage_ok(who, "labels_i64", labels_i64)) return rc;
+  if (int rc = map_extent_ok(who, n, h, w)) return rc;
+  return map_ignore_ok(who, has_ignore, ignore_index);
 }
 
 // blocks of a flat per-pixel pass over one image: 8 pixels per thread, at most 1024 blocks (the kernels walk the rest)
@@ -435,7 +416,7 @@ extern "C" int udaseg_regions_label(const void* labels, int labels_i64, int n, i
   UDASEG_CHECK_ARG(labels && ids, "regions_label: NULL pointer (labels and ids are required)");
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(area)) & 3) == 0,
                    "regions_label: ids and area must be 4-byte aligned");
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "regions_label: int64 labels must be 8-byte aligned");
+  if (int rc = map_aligned_ok("regions_label", "labels", labels_i64, labels)) return rc;
   hipStream_t st = as_stream(stream);
   RgArgs A = {};
   A.labels = labels;
@@ -492,7 +473,7 @@ extern "C" int udaseg_regions_sieve(const void* labels, int labels_i64, const in
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(area) | reinterpret_cast<uintptr_t>(min_area)) & 3) == 0,
                    "regions_sieve: ids, area and min_area must be 4-byte aligned");
   UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(counts) & 7) == 0, "regions_sieve: counts must be 8-byte aligned");
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "regions_sieve: int64 labels must be 8-byte aligned");
+  if (int rc = map_aligned_ok("regions_sieve", "labels", labels_i64, labels)) return rc;
   RgScanArgs A = {};
   A.labels = labels;
   A.ids = ids;
@@ -506,8 +487,9 @@ extern "C" int udaseg_regions_sieve(const void* labels, int labels_i64, const in
   A.out = out;
   A.counts = reinterpret_cast<unsigned long long*>(counts);
   const dim3 grid(rg_flat_grid((int64_t)h * w), (unsigned int)n);
-  if (labels_i64) hipLaunchKernelGGL(regions_sieve_kernel<true>, grid, dim3(RG_THREADS), 0, as_stream(stream), A);
-  else hipLaunchKernelGGL(regions_sieve_kernel<false>, grid, dim3(RG_THREADS), 0, as_stream(stream), A);
+  dispatch_flags(
+      [&](auto i64) { hipLaunchKernelGGL(regions_sieve_kernel<decltype(i64)::value>, grid, dim3(RG_THREADS), 0, as_stream(stream), A); },
+      labels_i64 != 0);
   RG_LAUNCHED("regions_sieve launch");
   return UDASEG_OK;
 }
@@ -520,7 +502,7 @@ extern "C" int udaseg_regions_stats(const void* labels, int labels_i64, const in
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(area)) & 3) == 0,
                    "regions_stats: ids and area must be 4-byte aligned");
   UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(stats) & 7) == 0, "regions_stats: stats must be 8-byte aligned");
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "regions_stats: int64 labels must be 8-byte aligned");
+  if (int rc = map_aligned_ok("regions_stats", "labels", labels_i64, labels)) return rc;
   RgScanArgs A = {};
   A.labels = labels;
   A.ids = ids;
@@ -533,8 +515,9 @@ extern "C" int udaseg_regions_stats(const void* labels, int labels_i64, const in
   A.classes = classes;
   const size_t lds = (size_t)classes * (sizeof(unsigned long long) + 33 * sizeof(unsigned int));   // <= 35700 bytes
   const dim3 grid(rg_flat_grid((int64_t)h * w), (unsigned int)n);
-  if (labels_i64) hipLaunchKernelGGL(regions_stats_kernel<true>, grid, dim3(RG_THREADS), lds, as_stream(stream), A);
-  else hipLaunchKernelGGL(regions_stats_kernel<false>, grid, dim3(RG_THREADS), lds, as_stream(stream), A);
+  dispatch_flags(
+      [&](auto i64) { hipLaunchKernelGGL(regions_stats_kernel<decltype(i64)::value>, grid, dim3(RG_THREADS), lds, as_stream(stream), A); },
+      labels_i64 != 0);
   RG_LAUNCHED("regions_stats launch");
   return UDASEG_OK;
 }

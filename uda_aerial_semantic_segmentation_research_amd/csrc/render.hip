@@ -23,11 +23,12 @@
 // (one word each for uint8 labels when the width is a multiple of four, label by label otherwise).
 // The kernel is templated over (int64 labels, base kind, outline, counts, truth): the colour-mask instantiation carries no
 // blend, no neighbour loads and no atomics.
-#include "common.h"
+#include "label_maps.h"
 
 namespace udaseg {
 
 constexpr int RD_THREADS = 256;
+static_assert(RD_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int RD_MAX_BLOCKS = 2048;
 constexpr int RD_GROUPS_PER_THREAD = 2;
 
@@ -44,15 +45,6 @@ struct RenderArgs {
   float sc0, sc1, sc2, sh0, sh1, sh2;
   unsigned int outline;          // r | g << 8 | b << 16
 };
-
-template <bool I64>
-__device__ __forceinline__ int load_label(const void* __restrict__ img, int64_t p) {
-  if (I64) {
-    const long long v = reinterpret_cast<const long long*>(img)[p];
-    return (v < 0 || v > 255) ? 255 : (int)v;
-  }
-  return reinterpret_cast<const uint8_t*>(img)[p];
-}
 
 // clip(rint(x * scale + shift), 0, 255): two separately rounded fp32 operations (no fused multiply-add: numpy has none), NaN -> 0
 __device__ __forceinline__ unsigned int denorm_level(float x, float scale, float shift) {
@@ -75,14 +67,13 @@ template <bool I64, int BASE, bool OUTLINE, bool COUNTS, bool TRUTH>
 __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
   __shared__ unsigned int tab[256];
   __shared__ unsigned int hist[COUNTS ? 256 : 1];
-  __shared__ unsigned int agr[3];
+  __shared__ BlockCounts<3>::Slots agr;
   const int tid = threadIdx.x;
   const int n = blockIdx.y;
   const int w = A.w, h = A.h, classes = A.classes;
   const int64_t HW = (int64_t)h * w;
   tab[tid] = (unsigned int)A.table[3 * tid] | ((unsigned int)A.table[3 * tid + 1] << 8) | ((unsigned int)A.table[3 * tid + 2] << 16);
   if (COUNTS) hist[tid] = 0;
-  if (TRUTH && tid < 3) agr[tid] = 0;
   __syncthreads();
 
   const uint8_t* lab_img = reinterpret_cast<const uint8_t*>(A.labels) + (size_t)n * HW * (I64 ? 8 : 1);
@@ -95,7 +86,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
   const bool base_vec = BASE == UDASEG_RENDER_BASE_U8 && (reinterpret_cast<uintptr_t>(base_img) & 3) == 0;
   const bool out_vec = (reinterpret_cast<uintptr_t>(out_img) & 3) == 0;
 
-  unsigned int n_agree = 0, n_differ = 0, n_tvoid = 0;
+  unsigned int ev[3] = {0, 0, 0};                              // agree, differ, truth void
   const int64_t groups = (HW + 3) >> 2;
   for (int64_t g = (int64_t)blockIdx.x * RD_THREADS + tid; g < groups; g += (int64_t)gridDim.x * RD_THREADS) {
     const int64_t p0 = 4 * g;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
       for (int e = 0; e < 4; ++e) L[e] = (int)((v >> (8 * e)) & 255u);
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) L[e] = e < cnt ? load_label<I64>(lab_img, p0 + e) : 0;
+      for (int e = 0; e < 4; ++e) L[e] = e < cnt ? label_at<I64>(lab_img, p0 + e) : 0;
     }
 
     int k[4];
@@ -142,12 +133,12 @@ __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
         if (e < cnt) {
           if (tv[e]) {
             k[e] = 3;
-            ++n_tvoid;
+            ++ev[2];
           } else if (T[e] == L[e]) {
             k[e] = 2;
-            ++n_agree;
+            ++ev[0];
           } else {
-            ++n_differ;
+            ++ev[1];
           }
         }
       }
@@ -191,10 +182,10 @@ __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
             const int64_t p = p0 + e;
             const int l = L[e];
             bool d = false;
-            if (x > 0) d |= (e > 0 ? L[e > 0 ? e - 1 : 0] : load_label<I64>(lab_img, p - 1)) != l;      // p - 1 is in this row
-            if (x + 1 < w) d |= (e < 3 ? L[e < 3 ? e + 1 : 3] : load_label<I64>(lab_img, p + 1)) != l;  // p + 1 < HW, so e + 1 < cnt
-            if (y > 0) d |= load_label<I64>(lab_img, p - w) != l;
-            if (y + 1 < h) d |= load_label<I64>(lab_img, p + w) != l;
+            if (x > 0) d |= (e > 0 ? L[e > 0 ? e - 1 : 0] : label_at<I64>(lab_img, p - 1)) != l;      // p - 1 is in this row
+            if (x + 1 < w) d |= (e < 3 ? L[e < 3 ? e + 1 : 3] : label_at<I64>(lab_img, p + 1)) != l;  // p + 1 < HW, so e + 1 < cnt
+            if (y > 0) d |= label_at<I64>(lab_img, p - w) != l;
+            if (y + 1 < h) d |= label_at<I64>(lab_img, p + w) != l;
             edge[e] = d;
             if (++x == w) {
               x = 0;
@@ -268,51 +259,13 @@ __global__ __launch_bounds__(RD_THREADS) void render_kernel(RenderArgs A) {
     }
   }
 
-  if (TRUTH && A.agreement) {
-    n_agree = wave_sum_u32(n_agree);
-    n_differ = wave_sum_u32(n_differ);
-    n_tvoid = wave_sum_u32(n_tvoid);
-    if ((tid & 63) == 0) {
-      if (n_agree) atomicAdd(&agr[0], n_agree);
-      if (n_differ) atomicAdd(&agr[1], n_differ);
-      if (n_tvoid) atomicAdd(&agr[2], n_tvoid);
-    }
-  }
-  if (COUNTS || TRUTH) __syncthreads();
+  if (TRUTH && A.agreement) BlockCounts<3>::put(agr, ev);
+  if (COUNTS || TRUTH) __syncthreads();                        // closes the histogram and the agreement slots
   if (COUNTS) {
     const unsigned int v = hist[tid];
     if (v) atomicAdd(&A.counts[(size_t)n * 256 + tid], (unsigned long long)v);
   }
-  if (TRUTH && A.agreement && tid < 3 && agr[tid]) atomicAdd(&A.agreement[(size_t)n * 3 + tid], (unsigned long long)agr[tid]);
-}
-
-template <bool I64, int BASE, bool OUTLINE, bool COUNTS>
-static void render_launch4(bool truth, dim3 grid, hipStream_t st, const RenderArgs& A) {
-  if (truth)
-    hipLaunchKernelGGL((render_kernel<I64, BASE, OUTLINE, COUNTS, true>), grid, dim3(RD_THREADS), 0, st, A);
-  else
-    hipLaunchKernelGGL((render_kernel<I64, BASE, OUTLINE, COUNTS, false>), grid, dim3(RD_THREADS), 0, st, A);
-}
-
-template <bool I64, int BASE>
-static void render_launch2(bool outline, bool counts, bool truth, dim3 grid, hipStream_t st, const RenderArgs& A) {
-  if (outline) {
-    if (counts) render_launch4<I64, BASE, true, true>(truth, grid, st, A);
-    else render_launch4<I64, BASE, true, false>(truth, grid, st, A);
-  } else {
-    if (counts) render_launch4<I64, BASE, false, true>(truth, grid, st, A);
-    else render_launch4<I64, BASE, false, false>(truth, grid, st, A);
-  }
-}
-
-template <bool I64>
-static void render_launch1(int base_kind, bool outline, bool counts, bool truth, dim3 grid, hipStream_t st, const RenderArgs& A) {
-  switch (base_kind) {
-    case UDASEG_RENDER_BASE_NONE: render_launch2<I64, UDASEG_RENDER_BASE_NONE>(outline, counts, truth, grid, st, A); break;
-    case UDASEG_RENDER_BASE_U8: render_launch2<I64, UDASEG_RENDER_BASE_U8>(outline, counts, truth, grid, st, A); break;
-    case UDASEG_RENDER_BASE_F32: render_launch2<I64, UDASEG_RENDER_BASE_F32>(outline, counts, truth, grid, st, A); break;
-    default: render_launch2<I64, UDASEG_RENDER_BASE_BF16>(outline, counts, truth, grid, st, A); break;
-  }
+  if (TRUTH && A.agreement) BlockCounts<3>::flush(agr, A.agreement + (size_t)n * 3);
 }
 
 }  // namespace udaseg
@@ -324,7 +277,7 @@ extern "C" int udaseg_render_u8(const void* labels, const void* truth, int label
                                 const int32_t* alpha, const float* denorm, int outline, uint8_t* out, int64_t* counts,
                                 int64_t* agreement, void* stream) {
   UDASEG_CHECK_ARG(labels && table && out && alpha, "render_u8: NULL pointer (labels, table, out and alpha are required)");
-  UDASEG_CHECK_ARG(labels_i64 == 0 || labels_i64 == 1, "render_u8: labels_i64 must be 0 (uint8) or 1 (int64), got %d", labels_i64);
+  if (int rc = map_storage_ok("render_u8", "labels_i64", labels_i64)) return rc;
   UDASEG_CHECK_ARG(n > 0 && n <= 65535 && h > 0 && w > 0 && (int64_t)h * w < ((int64_t)1 << 31) - 4,
                    "render_u8: need 0 < n <= 65535, h, w > 0, h * w < 2^31 - 4 (n=%d h=%d w=%d)", n, h, w);
   UDASEG_CHECK_ARG(classes >= 1 && classes <= 256, "render_u8: need 1 <= classes <= 256 (classes=%d)", classes);
@@ -336,9 +289,7 @@ extern "C" int udaseg_render_u8(const void* labels, const void* truth, int label
     UDASEG_CHECK_ARG(alpha[i] >= 0 && alpha[i] <= 256, "render_u8: alpha[%d] = %d is outside [0, 256]", i, alpha[i]);
   UDASEG_CHECK_ARG(outline >= -1 && outline <= 0xffffff, "render_u8: outline must be -1 (none) or r | g << 8 | b << 16, got %d", outline);
   UDASEG_CHECK_ARG(!agreement || truth, "render_u8: agreement needs truth");
-  if (labels_i64)
-    UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(truth)) & 7) == 0,
-                     "render_u8: int64 labels / truth must be 8-byte aligned");
+  if (int rc = map_aligned_ok("render_u8", "labels / truth", labels_i64, labels, truth)) return rc;
   const bool model_input = base_kind == UDASEG_RENDER_BASE_F32 || base_kind == UDASEG_RENDER_BASE_BF16;
   if (model_input) {
     UDASEG_CHECK_ARG(denorm, "render_u8: a model-input base needs the de-normalisation constants");
@@ -374,10 +325,21 @@ extern "C" int udaseg_render_u8(const void* labels, const void* truth, int label
   if (gx > cap) gx = cap;
   const dim3 grid((unsigned int)gx, (unsigned int)n);
   hipStream_t st = as_stream(stream);
-  if (labels_i64)
-    render_launch1<true>(base_kind, outline >= 0, counts != nullptr, truth != nullptr, grid, st, A);
-  else
-    render_launch1<false>(base_kind, outline >= 0, counts != nullptr, truth != nullptr, grid, st, A);
+  const auto launch = [&](auto base) {
+    dispatch_flags(
+        [&](auto i64, auto ol, auto cn, auto tr) {
+          hipLaunchKernelGGL((render_kernel<decltype(i64)::value, decltype(base)::value, decltype(ol)::value, decltype(cn)::value,
+                                            decltype(tr)::value>),
+                             grid, dim3(RD_THREADS), 0, st, A);
+        },
+        labels_i64 != 0, outline >= 0, counts != nullptr, truth != nullptr);
+  };
+  switch (base_kind) {
+    case UDASEG_RENDER_BASE_NONE: launch(std::integral_constant<int, UDASEG_RENDER_BASE_NONE>{}); break;
+    case UDASEG_RENDER_BASE_U8: launch(std::integral_constant<int, UDASEG_RENDER_BASE_U8>{}); break;
+    case UDASEG_RENDER_BASE_F32: launch(std::integral_constant<int, UDASEG_RENDER_BASE_F32>{}); break;
+    default: launch(std::integral_constant<int, UDASEG_RENDER_BASE_BF16>{}); break;
+  }
   UDASEG_LAUNCH_CHECK("render_u8 launch");
   return UDASEG_OK;
 }

@@ -33,11 +33,12 @@
 //   gather   mask[p] |= table[ids[p]].
 // Every per-pixel launch is ONE thread per pixel (no capped grid: h * w < 2^31 gives at most 2^23 blocks).  A cluster index read from
 // an ids / labels map is checked against K before it indexes a table: a caller's map cannot send a kernel out of bounds.
-#include "common.h"
+#include "label_maps.h"
 
 namespace udaseg {
 
 constexpr int SP_THREADS = 256;
+static_assert(SP_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int SP_MAX_TC = 16;                                  // cells per tile side at S = 2
 constexpr int SP_SLOTS = (SP_MAX_TC + 2) * (SP_MAX_TC + 2);    // the cells a tile's pixels can choose from
 constexpr int SP_ROUNDS = 2;                                   // wave-level sums per trip before the lanes fall back to their own atomics
@@ -199,23 +200,6 @@ __global__ __launch_bounds__(SP_THREADS) void sp_finish_kernel(SpArgs A) {
   for (int j = 0; j < 6; ++j) a[j] = 0;
 }
 
-// ---- counters: every thread of the block calls; v[j] is added to dst[idx[j]] with one atomic per block and counter
-template <int NC>
-__device__ __forceinline__ void sp_count(unsigned int (&v)[NC], const int (&idx)[NC], unsigned int* lds, unsigned long long* dst) {
-  if (dst == nullptr) return;                  // block-uniform
-  if (threadIdx.x < NC) lds[threadIdx.x] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const unsigned int s = wave_sum_u32(v[j]);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&lds[j], s);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NC; ++j)
-    if ((int)threadIdx.x == j && lds[j]) atomicAdd(&dst[idx[j]], (unsigned long long)lds[j]);
-}
-
 // ---- connect
 struct SpConnArgs {
   const int* labels;                           // the clusters before the step
@@ -233,7 +217,7 @@ __device__ __forceinline__ unsigned long long sp_key(int p, int area) {
 }
 
 __global__ __launch_bounds__(SP_THREADS) void sp_main_kernel(SpConnArgs A) {
-  __shared__ unsigned int cnt[1];
+  __shared__ BlockCounts<1>::Slots cnt;
   const size_t HW = (size_t)A.h * A.w, off = (size_t)blockIdx.y * HW;
   const size_t p = (size_t)blockIdx.x * SP_THREADS + threadIdx.x;
   unsigned int v[1] = {0};
@@ -242,12 +226,11 @@ __global__ __launch_bounds__(SP_THREADS) void sp_main_kernel(SpConnArgs A) {
     v[0] = 1;
     if (k < A.K) atomicMax(A.mainkey + (size_t)blockIdx.y * A.K + k, sp_key((int)p, A.area[off + p]));
   }
-  const int idx[1] = {0};
-  sp_count<1>(v, idx, cnt, A.counts ? A.counts + (size_t)blockIdx.y * 4 : nullptr);
+  if (A.counts) BlockCounts<1>::add(cnt, v, A.counts + (size_t)blockIdx.y * 4);          // counts[0]; block-uniform
 }
 
 __global__ __launch_bounds__(SP_THREADS) void sp_decide_kernel(SpConnArgs A) {
-  __shared__ unsigned int cnt[2];
+  __shared__ BlockCounts<2>::Slots cnt;
   const size_t HW = (size_t)A.h * A.w, off = (size_t)blockIdx.y * HW;
   const size_t p = (size_t)blockIdx.x * SP_THREADS + threadIdx.x;
   unsigned int v[2] = {0, 0};
@@ -262,8 +245,12 @@ __global__ __launch_bounds__(SP_THREADS) void sp_decide_kernel(SpConnArgs A) {
     const int x = (int)(p % (size_t)A.w);
     A.link[off + p] = kept ? k : ~(int)(x > 0 ? p - 1 : p - (size_t)A.w);
   }
-  const int idx[2] = {1, 3};
-  sp_count<2>(v, idx, cnt, A.counts ? A.counts + (size_t)blockIdx.y * 4 : nullptr);
+  if (A.counts) {                              // block-uniform; v[0] goes to counts[1], v[1] to counts[3]
+    BlockCounts<2>::put(cnt, v);
+    __syncthreads();
+    const unsigned int s = threadIdx.x < 2 ? BlockCounts<2>::total(cnt, threadIdx.x) : 0;
+    if (s) atomicAdd(A.counts + (size_t)blockIdx.y * 4 + 1 + 2 * threadIdx.x, (unsigned long long)s);
+  }
 }
 
 __global__ __launch_bounds__(SP_THREADS) void sp_walk_kernel(SpConnArgs A) {
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_walk_kernel(SpConnArgs A) {
 }
 
 __global__ __launch_bounds__(SP_THREADS) void sp_relabel_kernel(SpConnArgs A) {
-  __shared__ unsigned int cnt[1];
+  __shared__ BlockCounts<1>::Slots cnt;
   const size_t HW = (size_t)A.h * A.w, off = (size_t)blockIdx.y * HW;
   const size_t p = (size_t)blockIdx.x * SP_THREADS + threadIdx.x;
   unsigned int v[1] = {0};
@@ -294,8 +281,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_relabel_kernel(SpConnArgs A) {
     v[0] = now != old;
     A.ids[off + p] = now;                      // ids may be labels itself: this thread alone reads and writes the word
   }
-  const int idx[1] = {2};
-  sp_count<1>(v, idx, cnt, A.counts ? A.counts + (size_t)blockIdx.y * 4 : nullptr);
+  if (A.counts) BlockCounts<1>::add(cnt, v, A.counts + (size_t)blockIdx.y * 4 + 2);      // counts[2]; block-uniform
 }
 
 // ---- vote
@@ -362,7 +348,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_vote_decide_kernel(SpVoteArgs A
 
 template <bool I64>
 __global__ __launch_bounds__(SP_THREADS) void sp_vote_apply_kernel(SpVoteArgs A) {
-  __shared__ unsigned int cnt[3];
+  __shared__ BlockCounts<3>::Slots cnt;
   const size_t HW = (size_t)A.h * A.w, off = (size_t)blockIdx.y * HW;
   const size_t p = (size_t)blockIdx.x * SP_THREADS + threadIdx.x;
   unsigned int v[3] = {0, 0, 0};
@@ -376,8 +362,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_vote_apply_kernel(SpVoteArgs A)
     v[1] = !labelled && d >= 0;
     v[2] = labelled && d < 0;
   }
-  const int idx[3] = {0, 1, 2};
-  sp_count<3>(v, idx, cnt, A.counts ? A.counts + (size_t)blockIdx.y * 3 : nullptr);
+  if (A.counts) BlockCounts<3>::add(cnt, v, A.counts + (size_t)blockIdx.y * 3);          // block-uniform
 }
 
 // ---- mean, gather
@@ -430,7 +415,7 @@ __global__ __launch_bounds__(SP_THREADS) void sp_gather_kernel(SpMeanArgs A) {
 static inline bool sp_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static int sp_check_shape(const char* who, int n, int h, int w) {
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "%s: need 0 < n <= 65535 (n=%d)", who, n);
+  if (int rc = map_batch_ok(who, n)) return rc;
   UDASEG_CHECK_ARG(h >= 1 && w >= 1 && h <= SP_MAX_SIDE && w <= SP_MAX_SIDE && (int64_t)h * w < ((int64_t)1 << 31),
                    "%s: need 1 <= h, w <= 32768 and h * w < 2^31 (h=%d w=%d)", who, h, w);
   return UDASEG_OK;
@@ -609,17 +594,16 @@ extern "C" int udaseg_superpixel_vote(const int32_t* ids, const void* masks, int
                                       int void_label, uint8_t* out, int64_t* counts, void* stream) {
   if (int rc = sp_check_shape("superpixel_vote", n, h, w)) return rc;
   if (int rc = sp_check_clusters("superpixel_vote", clusters)) return rc;
-  UDASEG_CHECK_ARG(masks_i64 == 0 || masks_i64 == 1, "superpixel_vote: masks_i64 must be 0 (uint8) or 1 (int64), got %d", masks_i64);
+  if (int rc = map_storage_ok("superpixel_vote", "masks_i64", masks_i64)) return rc;
   UDASEG_CHECK_ARG(classes >= 1 && classes <= 255, "superpixel_vote: need 1 <= classes <= 255 (classes=%d)", classes);
-  UDASEG_CHECK_ARG(has_ignore == 0 || has_ignore == 1, "superpixel_vote: has_ignore must be 0 or 1, got %d", has_ignore);
-  UDASEG_CHECK_ARG(ignore_index >= 0 && ignore_index <= 255, "superpixel_vote: ignore_index must lie in [0, 255] (ignore_index=%d)", ignore_index);
+  if (int rc = map_ignore_ok("superpixel_vote", has_ignore, ignore_index)) return rc;
   UDASEG_CHECK_ARG(min_share >= 0.f && min_share <= 1.f, "superpixel_vote: min_share must lie in [0, 1] (min_share=%g)", (double)min_share);
   UDASEG_CHECK_ARG(min_cover >= 0.f && min_cover <= 1.f, "superpixel_vote: min_cover must lie in [0, 1] (min_cover=%g)", (double)min_cover);
   UDASEG_CHECK_ARG(void_label >= 0 && void_label <= 255, "superpixel_vote: void_label must lie in [0, 255] (void_label=%d)", void_label);
   UDASEG_CHECK_ARG(ids && masks && out, "superpixel_vote: NULL pointer (ids, masks and out are required)");
   UDASEG_CHECK_ARG(sp_aligned(ids, 4), "superpixel_vote: ids must be 4-byte aligned");
   UDASEG_CHECK_ARG(sp_aligned(counts, 8), "superpixel_vote: counts must be 8-byte aligned");
-  if (masks_i64) UDASEG_CHECK_ARG(sp_aligned(masks, 8), "superpixel_vote: int64 masks must be 8-byte aligned");
+  if (int rc = map_aligned_ok("superpixel_vote", "masks", masks_i64, masks)) return rc;
   hipStream_t st = as_stream(stream);
   SpVoteArgs A = {};
   A.ids = ids;
@@ -645,11 +629,13 @@ extern "C" int udaseg_superpixel_vote(const int32_t* ids, const void* masks, int
   if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync(superpixel_vote)");
   const dim3 grid = sp_pixel_grid(h, w, n);
   if (rc == UDASEG_OK) {
-    if (masks_i64) hipLaunchKernelGGL(sp_vote_count_kernel<true>, grid, dim3(SP_THREADS), 0, st, A);
-    else hipLaunchKernelGGL(sp_vote_count_kernel<false>, grid, dim3(SP_THREADS), 0, st, A);
-    hipLaunchKernelGGL(sp_vote_decide_kernel, sp_cluster_grid(clusters, n), dim3(SP_THREADS), 0, st, A);
-    if (masks_i64) hipLaunchKernelGGL(sp_vote_apply_kernel<true>, grid, dim3(SP_THREADS), 0, st, A);
-    else hipLaunchKernelGGL(sp_vote_apply_kernel<false>, grid, dim3(SP_THREADS), 0, st, A);
+    dispatch_flags(
+        [&](auto i64) {
+          hipLaunchKernelGGL(sp_vote_count_kernel<decltype(i64)::value>, grid, dim3(SP_THREADS), 0, st, A);
+          hipLaunchKernelGGL(sp_vote_decide_kernel, sp_cluster_grid(clusters, n), dim3(SP_THREADS), 0, st, A);
+          hipLaunchKernelGGL(sp_vote_apply_kernel<decltype(i64)::value>, grid, dim3(SP_THREADS), 0, st, A);
+        },
+        masks_i64 != 0);
     e = hipGetLastError();
     if (e != hipSuccess) rc = hip_fail(e, "superpixel vote launch");
   }

@@ -23,12 +23,14 @@
 // The score product first stages the entropy tile (0 at a dead position) and sums it DIRECTLY: a row pass of 2R + 1 terms left to
 // right into LDS, then a column pass of 2R + 1 row sums top to bottom in the owner thread -- no running add / subtract, which would
 // carry its cancellation error along the tile.
-// No atomics on the maps; the counters take one LDS add per wave and one 64-bit atomic per block and non-zero counter.
+// No atomics on the maps; the counters take one LDS slot per wave and one 64-bit atomic per block and non-zero counter (BlockCounts).
+#include "label_maps.h"
 #include "scores_common.h"
 
 namespace udaseg {
 
 constexpr int WN_THREADS = 256;
+static_assert(WN_THREADS == 64 * 4, "BlockCounts<K>: four waves a block");
 constexpr int WN_TW = 64;
 constexpr int WN_MAX_R = 16;
 constexpr int WN_DEAD = 0xff;
@@ -68,7 +70,7 @@ static inline WnGeom wn_geom(int h, int w, int R, int classes, int has_ignore, i
   G.off_tab = G.off_col + col_bytes;
   G.off_ent = G.off_tab + (product == WN_MODE ? 0 : 4 * ((2 * R + 1) * (2 * R + 1) + 1));
   G.off_cnt = G.off_ent + (product == WN_SCORE ? 4 * G.lh * G.lw : 0);
-  G.lds = G.off_cnt + 4 * (int)sizeof(unsigned int);
+  G.lds = G.off_cnt + (int)sizeof(BlockCounts<3>::Slots);
   G.tiles_x = cdiv(w, WN_TW);
   return G;
 }
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_kernel(WnArgs A) {
   float* erow = reinterpret_cast<float*>(wn_lds + G.off_col);      // score: the entropy row sums, before the first group
   float* tab = reinterpret_cast<float*>(wn_lds + G.off_tab);
   float* ent = reinterpret_cast<float*>(wn_lds + G.off_ent);
-  unsigned int* bcnt = reinterpret_cast<unsigned int*>(wn_lds + G.off_cnt);
+  BlockCounts<3>::Slots& bcnt = *reinterpret_cast<BlockCounts<3>::Slots*>(wn_lds + G.off_cnt);
   const int tid = threadIdx.x, img_i = blockIdx.y;
   const int R = G.R, h = G.h, w = G.w, lw = G.lw, lws = G.lws, lh = G.lh;
   const int ty0 = ((int)blockIdx.x / G.tiles_x) * TH, tx0 = ((int)blockIdx.x % G.tiles_x) * WN_TW;
@@ -156,7 +158,6 @@ __global__ __launch_bounds__(WN_THREADS) void window_kernel(WnArgs A) {
   }
   if (PRODUCT != WN_MODE)
     for (int i = tid; i < (2 * R + 1) * (2 * R + 1) + 1; i += WN_THREADS) tab[i] = A.table[i];
-  if (tid < 4) bcnt[tid] = 0;
   __syncthreads();
 
   const int oy = tid % TH, ox0 = (tid / TH) * SEG;                   // the owner of pixels (oy, ox0 .. ox0 + SEG - 1) of the tile
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_kernel(WnArgs A) {
 
   // 3. the products
   const int gy = ty0 + oy, gx = tx0 + ox0;
-  unsigned int n_changed = 0, n_filled = 0, n_left = 0;
+  unsigned int ev[3] = {0, 0, 0};                                    // changed, filled, left
   if (gy < h && gx < w) {
     const int cnt = w - gx >= SEG ? SEG : w - gx;                    // pixels gx .. gx + cnt - 1 exist
     const int64_t p = (int64_t)gy * w + gx;
@@ -245,13 +246,13 @@ __global__ __launch_bounds__(WN_THREADS) void window_kernel(WnArgs A) {
         ag[e] = P.n > 0 ? (float)P.best_cnt / (float)P.n : 0.f;
         if (l != WN_DEAD) {
           o[e] = (unsigned int)mode;
-          if (e < cnt && mode != l) ++n_changed;
+          if (e < cnt && mode != l) ++ev[0];
         } else if (A.fill_void && P.n > 0) {
           o[e] = (unsigned int)mode;
-          if (e < cnt) ++n_filled;
+          if (e < cnt) ++ev[1];
         } else {
           o[e] = (unsigned int)A.void_label;
-          if (e < cnt) ++n_left;
+          if (e < cnt) ++ev[2];
         }
       }
       wn_store<SEG>(out_img + p, o, cnt, (w & 3) == 0 && (reinterpret_cast<uintptr_t>(out_img) & 3) == 0);
@@ -295,18 +296,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_kernel(WnArgs A) {
       }
     }
   }
-  if (PRODUCT == WN_MODE && A.counts) {                              // uniform over the block
-    n_changed = wave_sum_u32(n_changed);
-    n_filled = wave_sum_u32(n_filled);
-    n_left = wave_sum_u32(n_left);
-    if ((tid & 63) == 0) {
-      if (n_changed) atomicAdd(&bcnt[0], n_changed);
-      if (n_filled) atomicAdd(&bcnt[1], n_filled);
-      if (n_left) atomicAdd(&bcnt[2], n_left);
-    }
-    __syncthreads();
-    if (tid < 3 && bcnt[tid]) atomicAdd(&A.counts[(size_t)img_i * 3 + tid], (unsigned long long)bcnt[tid]);
-  }
+  if (PRODUCT == WN_MODE && A.counts) BlockCounts<3>::add(bcnt, ev, A.counts + (size_t)img_i * 3);   // uniform over the block
 }
 
 // ------------------------------------------------------------------------------------------------ scores -> labels and entropy
@@ -318,10 +308,8 @@ __global__ __launch_bounds__(256) void acquire_prepare_kernel(const float* __res
                                                               int64_t pixels, float s, uint8_t* __restrict__ labels,
                                                               float* __restrict__ entropy, unsigned long long* __restrict__ counters) {
 #pragma clang fp contract(off)
-  __shared__ unsigned int cnt[2];
-  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-  __syncthreads();
-  unsigned int n_fin = 0, n_bad = 0;
+  __shared__ BlockCounts<2>::Slots cnt;
+  unsigned int ev[2] = {0, 0};                                       // finite, not finite
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * 256) {
     f32x4 v[NV];
     load_row<NV>(scores + p * ldc, v);
@@ -352,16 +340,10 @@ __global__ __launch_bounds__(256) void acquire_prepare_kernel(const float* __res
     fin = fin && __builtin_isfinite(hsum);
     labels[p] = fin ? (uint8_t)am : (uint8_t)255;
     entropy[p] = fin ? hsum : 0.f;
-    if (fin) ++n_fin; else ++n_bad;
+    ev[0] += fin;
+    ev[1] += !fin;
   }
-  n_fin = wave_sum_u32(n_fin);
-  n_bad = wave_sum_u32(n_bad);
-  if ((threadIdx.x & 63) == 0) {
-    if (n_fin) atomicAdd(&cnt[0], n_fin);
-    if (n_bad) atomicAdd(&cnt[1], n_bad);
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+  BlockCounts<2>::add(cnt, ev, counters);
 }
 
 // ------------------------------------------------------------------------------------------------------ cells, select, expand
@@ -396,34 +378,23 @@ __global__ __launch_bounds__(256) void acquire_cells_kernel(const float* __restr
 __global__ __launch_bounds__(256) void acquire_select_kernel(const float* __restrict__ key, const float* __restrict__ thresholds,
                                                              int64_t items, uint8_t* __restrict__ mask,
                                                              unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int cnt[2];
-  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-  __syncthreads();
+  __shared__ BlockCounts<2>::Slots cnt;
   const int i = blockIdx.y;
   const float thr = thresholds[i];
   const float* k = key + (size_t)i * items;
   uint8_t* m = mask + (size_t)i * items;
-  unsigned int n_new = 0, n_cand = 0;
+  unsigned int ev[2] = {0, 0};                                       // new, candidates
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < items; j += (int64_t)gridDim.x * 256) {
     const float v = k[j];
     if (v >= 0.f) {
-      ++n_cand;
+      ++ev[1];
       if (v <= thr) {
-        if (m[j] == 0) ++n_new;
+        if (m[j] == 0) ++ev[0];
         m[j] |= 1;
       }
     }
   }
-  if (counts) {
-    n_new = wave_sum_u32(n_new);
-    n_cand = wave_sum_u32(n_cand);
-    if ((threadIdx.x & 63) == 0) {
-      if (n_new) atomicAdd(&cnt[0], n_new);
-      if (n_cand) atomicAdd(&cnt[1], n_cand);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[(size_t)i * 2 + threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
-  }
+  if (counts) BlockCounts<2>::add(cnt, ev, counts + (size_t)i * 2);
 }
 
 __global__ __launch_bounds__(256) void acquire_expand_kernel(const uint8_t* __restrict__ cell_mask, int h, int w, int cell_h, int cell_w,
@@ -440,20 +411,11 @@ __global__ __launch_bounds__(256) void acquire_expand_kernel(const uint8_t* __re
 
 // the argument rules the window entry points share; 0 or UDASEG_E_BADARG with the message set
 static int wn_check(const char* who, int labels_i64, int n, int h, int w, int radius, int classes, int has_ignore, int ignore_index) {
-  UDASEG_CHECK_ARG(labels_i64 == 0 || labels_i64 == 1, "%s: labels_i64 must be 0 (uint8) or 1 (int64), got %d", who, labels_i64);
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "%s: need 0 < n <= 65535 (n=%d)", who, n);
-  UDASEG_CHECK_ARG(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), "%s: need h, w >= 1 and h * w < 2^31 (h=%d w=%d)", who, h, w);
+  if (int rc = map_storage_ok(who, "labels_i64", labels_i64)) return rc;
+  if (int rc = map_extent_ok(who, n, h, w)) return rc;
   UDASEG_CHECK_ARG(radius >= 0 && radius <= WN_MAX_R, "%s: need 0 <= radius <= %d (radius=%d)", who, WN_MAX_R, radius);
   UDASEG_CHECK_ARG(classes >= 2 && classes <= 32, "%s: need 2 <= classes <= 32 (classes=%d)", who, classes);
-  UDASEG_CHECK_ARG(has_ignore == 0 || has_ignore == 1, "%s: has_ignore must be 0 or 1, got %d", who, has_ignore);
-  UDASEG_CHECK_ARG(ignore_index >= 0 && ignore_index <= 255, "%s: ignore_index must lie in [0, 255] (ignore_index=%d)", who, ignore_index);
-  return UDASEG_OK;
-}
-
-static int grid_check(const char* who, int n, int h, int w) {
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "%s: need 0 < n <= 65535 (n=%d)", who, n);
-  UDASEG_CHECK_ARG(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), "%s: need h, w >= 1 and h * w < 2^31 (h=%d w=%d)", who, h, w);
-  return UDASEG_OK;
+  return map_ignore_ok(who, has_ignore, ignore_index);
 }
 
 template <int PRODUCT>
@@ -466,13 +428,11 @@ static int wn_launch(const char* who, WnArgs& A, int labels_i64, int n, hipStrea
     set_error("%s: internal: %d bytes of LDS", who, G.lds);
     return UDASEG_E_UNSUPPORTED;
   }
-  if (G.th == 32) {
-    if (labels_i64) hipLaunchKernelGGL((window_kernel<true, 32, PRODUCT>), grid, block, G.lds, st, A);
-    else hipLaunchKernelGGL((window_kernel<false, 32, PRODUCT>), grid, block, G.lds, st, A);
-  } else {
-    if (labels_i64) hipLaunchKernelGGL((window_kernel<true, 16, PRODUCT>), grid, block, G.lds, st, A);
-    else hipLaunchKernelGGL((window_kernel<false, 16, PRODUCT>), grid, block, G.lds, st, A);
-  }
+  dispatch_flags(
+      [&](auto i64, auto tall) {
+        hipLaunchKernelGGL((window_kernel<decltype(i64)::value, decltype(tall)::value ? 32 : 16, PRODUCT>), grid, block, G.lds, st, A);
+      },
+      labels_i64 != 0, G.th == 32);
   UDASEG_LAUNCH_CHECK(who);
   return UDASEG_OK;
 }
@@ -493,7 +453,7 @@ extern "C" int udaseg_window_mode(const void* labels, int labels_i64, int n, int
   UDASEG_CHECK_ARG(fill_void == 0 || fill_void == 1, "window_mode: fill_void must be 0 or 1, got %d", fill_void);
   UDASEG_CHECK_ARG(void_label >= 0 && void_label <= 255, "window_mode: void_label must lie in [0, 255] (void_label=%d)", void_label);
   UDASEG_CHECK_ARG(labels && out, "window_mode: NULL pointer (labels and out are required)");
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "window_mode: int64 labels must be 8-byte aligned");
+  if (int rc = map_aligned_ok("window_mode", "labels", labels_i64, labels)) return rc;
   UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(agreement) & 3) == 0 && (reinterpret_cast<uintptr_t>(counts) & 7) == 0,
                    "window_mode: agreement must be 4-byte and counts 8-byte aligned");
   WnArgs A = {};
@@ -511,7 +471,7 @@ extern "C" int udaseg_window_impurity(const void* labels, int labels_i64, int n,
                                       int ignore_index, const float* table, float* out, void* stream) {
   if (int rc = wn_check("window_impurity", labels_i64, n, h, w, radius, classes, has_ignore, ignore_index)) return rc;
   UDASEG_CHECK_ARG(labels && table && out, "window_impurity: NULL pointer (labels, table and out are required)");
-  if (labels_i64) UDASEG_CHECK_ARG((reinterpret_cast<uintptr_t>(labels) & 7) == 0, "window_impurity: int64 labels must be 8-byte aligned");
+  if (int rc = map_aligned_ok("window_impurity", "labels", labels_i64, labels)) return rc;
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(table)) & 3) == 0,
                    "window_impurity: table and out must be 4-byte aligned");
   WnArgs A = {};
@@ -566,7 +526,7 @@ extern "C" int udaseg_acquire_score(const uint8_t* labels, const float* entropy,
 }
 
 extern "C" int udaseg_acquire_cells(const float* key, int n, int h, int w, int cell_h, int cell_w, float* cell_key, void* stream) {
-  if (int rc = grid_check("acquire_cells", n, h, w)) return rc;
+  if (int rc = map_extent_ok("acquire_cells", n, h, w)) return rc;
   UDASEG_CHECK_ARG(cell_h >= 1 && cell_w >= 1, "acquire_cells: need cell_h, cell_w >= 1 (cell_h=%d cell_w=%d)", cell_h, cell_w);
   UDASEG_CHECK_ARG(key && cell_key, "acquire_cells: NULL pointer");
   UDASEG_CHECK_ARG(((reinterpret_cast<uintptr_t>(key) | reinterpret_cast<uintptr_t>(cell_key)) & 3) == 0,
@@ -580,7 +540,7 @@ extern "C" int udaseg_acquire_cells(const float* key, int n, int h, int w, int c
 
 extern "C" int udaseg_acquire_select(const float* key, const float* thresholds, int n, int64_t items_per_image, uint8_t* mask,
                                      int64_t* counts, void* stream) {
-  UDASEG_CHECK_ARG(n > 0 && n <= 65535, "acquire_select: need 0 < n <= 65535 (n=%d)", n);
+  if (int rc = map_batch_ok("acquire_select", n)) return rc;
   UDASEG_CHECK_ARG(items_per_image > 0 && items_per_image < ((int64_t)1 << 31),
                    "acquire_select: need 0 < items_per_image < 2^31 (items_per_image=%lld)", (long long)items_per_image);
   UDASEG_CHECK_ARG(key && thresholds && mask, "acquire_select: NULL pointer (key, thresholds and mask are required)");
@@ -596,7 +556,7 @@ extern "C" int udaseg_acquire_select(const float* key, const float* thresholds, 
 
 extern "C" int udaseg_acquire_expand(const uint8_t* cell_mask, int n, int h, int w, int cell_h, int cell_w, uint8_t* mask,
                                      void* stream) {
-  if (int rc = grid_check("acquire_expand", n, h, w)) return rc;
+  if (int rc = map_extent_ok("acquire_expand", n, h, w)) return rc;
   UDASEG_CHECK_ARG(cell_h >= 1 && cell_w >= 1, "acquire_expand: need cell_h, cell_w >= 1 (cell_h=%d cell_w=%d)", cell_h, cell_w);
   UDASEG_CHECK_ARG(cell_mask && mask, "acquire_expand: NULL pointer");
   const int gh = cdiv(h, cell_h), gw = cdiv(w, cell_w);
