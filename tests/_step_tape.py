@@ -23,6 +23,13 @@ that difference, sum_i half_ulp_bf16(v_i) |coefficient_i| -- the precision of th
 The activation band: where the backward re-evaluates the activation's argument in fp32 instead of reading a written z (the z-less
 fp32 forms and the LazyAct form), an element may take either branch only where the float64 argument lies within
 max(4 x max|arg32 - arg64| over the layer, 2 ulp of fp32 at the layer's scale) of zero; at most BAND_CAP of a layer's elements may.
+
+The discriminators (tests/test_gpu_disc_tape.py, tests/test_disc_tape_host.py) run on the same Plan and add what the segmenter's step
+never does.  Their checks: a convolution's fused activation (Layer.fused_act), check_act_bwd, check_tail (both pooled tails, judged
+as tests/test_gpu_loss_grade.py judges the kernels), the pad lanes of an input gradient, check_eval_layer (the folded eval plan,
+bn_fold judged as tests/test_gpu_conv_f32_grade.py judges it), check_grad_sum (k delivered arenas) and check_running (judged as
+tests/test_gpu_norm_grade.py judges the two outputs).  Recorder.watch wraps a discriminator's ``_forward_plan``; every recorded call
+carries the Plan it ran under, so two forwards followed by one backward come apart again (image_tape / feature_tape / eval_tape).
 """
 import time
 
@@ -30,8 +37,9 @@ import numpy as np
 import torch
 
 import _conv_ref as R
+import _loss_ref as LR
 import _norm_ref as N
-from _grade import log as _log
+from _grade import Grader as _NormGrader, log as _log
 
 F32, F64 = np.float32, np.float64
 BAND_CAP = 1e-3
@@ -120,6 +128,32 @@ class Report:
         _log(f"{PREFIX} {self.tag} | {layer}:{kind} | {'exact' if same else 'DIFFERS'}")
         self._note(layer, kind, 0.0 if same else float("inf"), same, f"{layer}:{kind}: not bit for bit")
 
+    def tail(self, layer, kind, got, r64, r32, mag, bf16_out=False):
+        """tests/_loss_ref.py's Grader as tests/test_gpu_loss_grade.py uses it: its margin, its floor."""
+        g = LR.Grader(self.tag, lambda line: _log(f"{PREFIX} {line}"))
+        g.grade(f"{layer}:{kind}", got, r64, r32, mag, bf16_out)
+        self._note(layer, kind, g.worst, not g.bad, "; ".join(g.bad))
+
+    def fold(self, layer, what, got, r64, leg, mag):
+        """tests/test_gpu_conv_f32_grade.py::test_bn_fold's verdict: the norm bar of the fp32 restatement of the same formula."""
+        A, dleg = N.bar(leg, r64, mag)
+        got = np.asarray(got, dtype=F64)
+        e = float(N.normalised(got - r64, mag).max(initial=0.0)) if got.shape == np.shape(r64) and np.isfinite(got).all() else float("inf")
+        _log(f"{PREFIX} {self.tag} | {layer}:fold:{what} | fp32 | e {e:.3e} d_rne {dleg:.3e} bar {A:.3e} e/bar {e / A:.3f}")
+        self._note(layer, "fold", e / A, e <= A, f"{layer}:fold:{what}: e {e:.3e} > bar {A:.3e}")
+
+    def ulp2(self, layer, kind, got, r64, operand, slack=None):
+        """tests/_grade.py's Grader.ulp2 as tests/test_gpu_norm_grade.py applies it to running_mean / running_var; ``slack`` as in _less."""
+        if slack is not None:
+            dev = np.asarray(got, dtype=F64) - r64
+            got = r64 + np.sign(dev) * np.maximum(np.abs(dev) - slack, 0.0)
+        g = _NormGrader(self.tag)
+        g.PREFIX = PREFIX
+        g.ulp2(f"{layer}:{kind}", got, r64, operand)
+        ulp = np.spacing(np.maximum(np.abs(r64), operand).astype(F32)).astype(F64)
+        err = np.abs(np.asarray(got, dtype=F64) - r64) / ulp
+        self._note(layer, kind, float(err.max(initial=0.0)) / 2.0 if np.isfinite(err).all() else float("inf"), not g.bad, "; ".join(g.bad))
+
     def share(self, layer, count, size):
         s = count / max(size, 1)
         self.band[layer] = s
@@ -144,10 +178,12 @@ class Inp:
 
 class Layer:
     """One convolution (+ BatchNorm + activation) of the forward.  Arrays are NHWC fp32 numpy with the PHYSICAL (padded) channel
-    counts; w is the LOGICAL OHWI weight.  z None with ``lazy`` = (scale, shift): the activation was never written."""
+    counts; w is the LOGICAL OHWI weight.  z None with ``lazy`` = (scale, shift): the activation was never written.  ``fused_act`` /
+    ``fused_slope``: a convolution without BatchNorm whose stored y is act(conv + bias), the pre-activation never written."""
 
     def __init__(self, **kw):
-        self.bias = self.gamma = self.beta = self.z = self.lazy = self.mean = self.rstd = self.residual = None
+        self.bias = self.gamma = self.beta = self.z = self.lazy = self.mean = self.rstd = self.residual = self.fused_act = None
+        self.fused_slope = 0.0
         self.act, self.slope, self.eps, self.storage = N.NONE, 0.0, 1e-5, "fp32"
         self.__dict__.update(kw)
 
@@ -197,20 +233,27 @@ def seq_sums(y2d):
     return R.stats_ref(R.Ref(y2d, np.abs(y2d), y2d, y2d))
 
 
-def check_stats(rep, L):
-    """mean / rstd against the float64 statistics of the engine's own y.  The bound is that of the two sums (their Refs' bars, the
-    legs sequential fp32 sums) carried through var = s2 / P - mean^2 and rstd = (var + eps)^-1/2, plus 2 ulp of the fp32 store."""
-    c = L.y.shape[-1]
-    y = L.y.reshape(-1, c).astype(F64)
+def stats_bound(y, eps, bf16):
+    """(mean, var, rstd, a1, dv) of y [pixels, channels]: the float64 statistics and how far the kernels' mean / variance may lie from
+    them -- the bars of the two sums' Refs (the legs sequential fp32 sums) over P, carried through var = s2 / P - mean^2; bf16 storage:
+    plus what the values lost in their bf16 store, since the epilogue summed them before it."""
+    y = np.asarray(y, dtype=F64)
     p = y.shape[0]
-    mean, var, rstd = N.stats(y, L.eps)
+    mean, var, rstd = N.stats(y, eps)
     s1, s2 = seq_sums(y)
     a1, a2 = R.bar(s1)[0] * s1.mag / p, R.bar(s2)[0] * s2.mag / p
-    if L.bf16:       # the epilogue summed the values before their bf16 store
+    if bf16:
         h = N.bf16_half_ulp(y)
         a1 = a1 + h.sum(0) / p
         a2 = a2 + ((2.0 * np.abs(y) + h) * h).sum(0) / p
-    dv = a2 + (2.0 * np.abs(mean) + a1) * a1
+    return mean, var, rstd, a1, a2 + (2.0 * np.abs(mean) + a1) * a1
+
+
+def check_stats(rep, L):
+    """mean / rstd against the float64 statistics of the engine's own y.  The bound is that of the two sums (stats_bound) carried through
+    rstd = (var + eps)^-1/2, plus 2 ulp of the fp32 store."""
+    c = L.y.shape[-1]
+    mean, var, rstd, a1, dv = stats_bound(L.y.reshape(-1, c), L.eps, L.bf16)
     rep.bound(L.name, "mean", L.mean.astype(F64) - mean, a1 + 2.0 * np.spacing(np.abs(mean).astype(F32)).astype(F64))
     lo = 1.0 / np.sqrt(np.maximum(var - dv, 0.0) + L.eps)
     rep.bound(L.name, "rstd", L.rstd.astype(F64) - rstd, (lo - rstd) + 2.0 * np.spacing(rstd.astype(F32)).astype(F64))
@@ -227,8 +270,11 @@ def check_forward(rep, L):
     w = phys_weight(L, cin_p, cout_p)
     ar = arith(L.storage, "fwd", L.route, cin_p, cout_p)
     ref = _ref("fwd", ar, x64, x32, w, L.stride, L.pad)
-    if L.bias is not None:
-        ref = R.epilogue(ref, bias=np.pad(L.bias, (0, cout_p - L.bias.shape[0])))
+    bias = None if L.bias is None else np.pad(L.bias, (0, cout_p - L.bias.shape[0]))
+    if L.fused_act == N.LEAKY:           # the stored output is act(conv + bias); LeakyReLU is 1-Lipschitz: the same bar, no band
+        ref = R.epilogue(ref, bias=bias, slope=float(F32(L.fused_slope)))
+    elif bias is not None:
+        ref = R.epilogue(ref, bias=bias)
     rep.grade(ar, L.name, "y", L.route, L.y, ref, L.bf16 and not getattr(L, "y_fp32", False))
     if cout_p > L.w.shape[0]:
         rep.exact(L.name, "y-pad", L.y[..., L.w.shape[0]:], np.zeros_like(L.y[..., L.w.shape[0]:]))
@@ -367,6 +413,8 @@ def check_conv_bwd(rep, L, call):
         if call["dx_old"] is not None:
             ref = R.epilogue(ref, old=call["dx_old"])
         rep.grade(ar, L.name, "dx", route, call["dx"], ref, L.bf16)
+        if ci < cin_p:                  # the input's pad lanes meet zero weights: no gradient may appear in them
+            rep.exact(L.name, "dx-pad", call["dx"][..., ci:], np.zeros_like(call["dx"][..., ci:]))
         return
     ca = L.x.a.y.shape[-1] if L.x.a.kind == "lazy" else L.x.a.t.shape[-1]
     if call["dx_kind"] == "pair":
@@ -380,26 +428,128 @@ def check_conv_bwd(rep, L, call):
         rep.grade(ar, L.name, "d_skip", route, call["d_skip"], _cut(ref, ca, cin_p), L.bf16)
 
 
+def check_act_bwd(rep, L, call):
+    """The in-place act_bwd through a convolution's fused activation: dz * act'(stored output), one fp32 product per element, bit for
+    bit (rounded once to bf16 under bf16 storage)."""
+    want = N.act_bwd(call["dz"], L.y, L.fused_act, L.fused_slope, F32)[0]
+    rep.exact(L.name, "act-bwd", call["dy"], N.bf16_round(want) if L.bf16 else want)
+
+
+def check_tail(rep, t):
+    """A pooled tail (global average pool -> dot product (-> sigmoid)) as the plan wired it, judged as tests/test_gpu_loss_grade.py
+    judges the same kernels.  t: layer, sigmoid, bf16, z [n, h, w, c], w [c], b, pooled [n, c], out [n]; with a backward also dp [n],
+    dz [n, h, w, c], gw [c], gb, gw_old, gb_old; the feature-level tail also block / block_old: the [rows][c] gradient block of the 1x1
+    convolution whose row 0 is gw."""
+    name, sig = t["layer"], t["sigmoid"]
+    n, c = t["pooled"].shape
+    z = t["z"].reshape(n, -1, c)
+    hw = z.shape[1]
+    f64, f32 = (LR.tail_forward(z, t["w"], t["b"], sig, e) for e in (F64, F32))
+    for key, got in (("pooled", t["pooled"]), ("out", np.reshape(t["out"], -1))):
+        rep.tail(name, key, got, f64[key][0], f32[key][0], f64[key][1])
+    if t.get("dp") is None:
+        return
+    b64, b32 = (LR.tail_backward(t["dp"], np.reshape(t["out"], -1), t["pooled"], t["w"], hw, sig, e) for e in (F64, F32))
+    spread = lambda a: np.repeat(np.asarray(a)[:, None, :], hw, axis=1)  # noqa: E731
+    rep.tail(name, "dz", t["dz"].reshape(n, hw, c), spread(b64["dz"][0]), spread(b32["dz"][0]), spread(b64["dz"][1]), t["bf16"])
+    rep.exact(name, "dw-old", t["gw_old"], np.zeros_like(t["gw_old"]))
+    rep.exact(name, "db-old", t["gb_old"], np.zeros_like(t["gb_old"]))
+    rep.tail(name, "dw", t["gw"], b64["dw"][0], b32["dw"][0], b64["dw"][1])
+    rep.tail(name, "db", t["gb"], b64["db"][0], b32["db"][0], b64["db"][1])
+    if t.get("block") is not None:
+        block = t["block"].reshape(t["block"].shape[0], -1)
+        rep.exact(name, "block-old", t["block_old"], np.zeros_like(t["block_old"]))
+        rep.exact(name, "dw-rows", block[1:], np.zeros_like(block[1:]))
+        rep.exact(name, "dw-row0", block[0], t["gw"])
+
+
+def check_eval_layer(rep, ev):
+    """One Plan._conv_bn_act_eval call from the operands the engine itself used.  ev: layer, storage, x (Inp), k, stride, pad, w32 (the
+    physical fp32 weights), bias, gamma, beta, rm, rv, eps, wf / bf (the folded slices the call wrote), wf16 (their cast, bf16 storage),
+    z, act, slope, residual."""
+    name, bf16 = ev["layer"], ev["storage"] == "bf16"
+    c = ev["gamma"].shape[0]
+    bias = None if ev["bias"] is None else ev["bias"][:c]
+    args = (ev["w32"][:c], bias, ev["gamma"], ev["beta"], ev["rm"], ev["rv"], ev["eps"])
+    (w64, b64, bmag), (w32, b32, _) = R.bn_fold_ref(*args, F64), R.bn_fold_ref(*args, F32)
+    rep.fold(name, "weights", ev["wf"][:c], w64, w32, np.abs(w64))
+    rep.fold(name, "bias", ev["bf"][:c], b64, b32, bmag)
+    stored = ev["wf"]
+    if bf16:
+        rep.exact(name, "fold-bf16", ev["wf16"], N.bf16_round(ev["wf"]))
+        stored = ev["wf16"]
+    x64, x32 = materialise(ev["x"], bf16)
+    cin_p, cout_p = x64.shape[-1], ev["z"].shape[-1]
+    ar = arith(ev["storage"], "fwd", "igemm", cin_p, cout_p)
+    ref = _ref("fwd", ar, x64, x32, stored, ev["stride"], ev["pad"])
+    ref = R.epilogue(ref, bias=np.pad(ev["bf"][:c], (0, cout_p - c)), residual=ev["residual"],
+                     slope=float(F32(ev["slope"])) if ev["act"] == N.LEAKY else None)
+    rep.grade(ar, name, "z-eval", "igemm", ev["z"], ref, bf16)
+
+
+def check_grad_sum(rep, name, delivered, arena):
+    """After a backward that delivered k arenas the module's gradient arena is their fp32 sum in delivery order, bit for bit."""
+    want = np.asarray(delivered[0], dtype=F32)
+    for d in delivered[1:]:
+        want = (want + np.asarray(d, dtype=F32)).astype(F32)
+    rep.exact(name, "grad-sum", arena, want)
+
+
+def check_running(rep, r):
+    """running_mean / running_var of one BatchNorm after its training forwards: ``_norm_ref.running`` applied in forward order to the
+    float64 statistics of each forward's recorded y, judged as tests/test_gpu_norm_grade.py judges the two (2 ulp of fp32 at the larger
+    operand); num_batches_tracked counts the forwards.  r: layer, ys, eps, momentum, bf16, rm0 / rv0 / nbt0 (before), rm / rv / nbt.
+    That grade feeds the kernel float64 sums of the stored values.  The plan's statistics are made in the convolution's epilogue: what
+    check_stats allows the saved mean and the variance for it (stats_bound: the sums' own bars, under bf16 storage also the values'
+    bf16 store), carried through the same recurrence, is taken off the deviation first, as _less does."""
+    name, mom = r["layer"], float(F32(r["momentum"]))
+    rm, rv = r["rm0"].astype(F64), r["rv0"].astype(F64)
+    sm = sv = op_m = op_v = np.zeros_like(rm)
+    for y in r["ys"]:
+        y2 = y.reshape(-1, y.shape[-1])[:, :rm.shape[0]]
+        p = y2.shape[0]
+        mean, var, _, a1, dv = stats_bound(y2, r["eps"], r["bf16"])
+        rm, rv, op_m, op_v = N.running(mean, var, p, mom, rm, rv)
+        sm, sv = (1.0 - mom) * sm + mom * a1, (1.0 - mom) * sv + mom * dv * (p / (p - 1.0) if p > 1 else 1.0)
+    rep.ulp2(name, "running_mean", r["rm"], rm, op_m, sm)
+    rep.ulp2(name, "running_var", r["rv"], rv, op_v, sv)
+    want = int(r["nbt0"]) + len(r["ys"])
+    rep._note(name, "batches", 0.0, int(r["nbt"]) == want, f"{name}: num_batches_tracked {int(r['nbt'])}, expected {want}")
+
+
 def check_step(rep, tape, only=None):
-    """Every forward and backward check of a recorded step {"layers": {name: Layer}, "pool": (f1, pooled, pidx) or None, "calls": [...]}
-    (``only``: a predicate on layer names, the section of a parametrised case)."""
+    """Every forward and backward check of a recorded step {"layers": {name: Layer}, "pool": (f1, pooled, pidx) or None, "calls": [...],
+    "tail": a pooled tail or None} (``only``: a predicate on layer names, the section of a parametrised case)."""
     keep = only or (lambda name: True)
     for L in tape["layers"].values():
         if keep(L.name):
             check_forward(rep, L)
     if tape.get("pool") is not None and keep("maxpool"):
         check_pool(rep, *tape["pool"])
+    if tape.get("tail") is not None and keep(tape["tail"]["layer"]):
+        check_tail(rep, tape["tail"])
     seen = {}
+    checks = {"bn": check_bn_bwd, "conv": check_conv_bwd, "act": check_act_bwd}
     for call in tape["calls"]:
         if keep(call["layer"]):
             L = tape["layers"][call["layer"]]
             seen[(call["layer"], call["kind"])] = seen.get((call["layer"], call["kind"]), 0) + 1
-            (check_bn_bwd if call["kind"] == "bn" else check_conv_bwd)(rep, L, call)
-    for L in tape["layers"].values():            # every conv is visited once, every BatchNorm once
+            checks[call["kind"]](rep, L, call)
+    for L in tape["layers"].values():            # every conv is visited once, every BatchNorm once, every fused activation once
         if keep(L.name):
-            want = {"conv": 1, "bn": 0 if L.gamma is None else 1}
+            want = {"conv": 1, "bn": 0 if L.gamma is None else 1, "act": 0 if L.fused_act is None else 1}
             got = {k: seen.get((L.name, k), 0) for k in want}
             rep._note(L.name, "visits", 0.0, got == want, f"{L.name}: backward calls {got}, expected {want}")
+
+
+def check_eval(rep, tape, only=None):
+    """Every check of a recorded eval forward {"evals": [...], "tail": a pooled tail without a backward}."""
+    keep = only or (lambda name: True)
+    for ev in tape["evals"]:
+        if keep(ev["layer"]):
+            check_eval_layer(rep, ev)
+    if tape.get("tail") is not None and keep(tape["tail"]["layer"]):
+        check_tail(rep, tape["tail"])
 
 
 def census(tape):
@@ -424,13 +574,18 @@ def to_host(t):
 
 class Recorder:
     """Wraps Plan.bn_bwd / Plan.conv_bwd (and, to learn the data-gradient route ACTUALLY taken and whether the BatchNorm backward read
-    a z, the engine's kernel entry points of those two families) through ``monkeypatch`` for one backward pass."""
+    a z, the engine's kernel entry points of those two families) through ``monkeypatch`` for one backward pass.  With values it also
+    wraps what the discriminators run around them (_wrap_tails); ``watch`` a discriminator to get its forwards."""
     DGRAD = {"conv2d_dgrad_up": "phase", "conv2d_dgrad_n16": "n16", "conv2d_dgrad_frag": "frag", "conv2d_dgrad_bnreduce": "bnreduce",
              "conv2d_dgrad_split": "split", "conv2d_dgrad": "igemm"}
 
     def __init__(self, engine, monkeypatch, values=True):
         """values False: routes only, nothing is copied and nothing synchronised (the census of a full-size step)."""
         self.E, self.calls, self._dg, self._mask = engine, [], [], None
+        # the discriminators' records: forwards (watch), delivered gradient arenas, the plan whose backward is running, what the forward
+        # in progress noted (eval layers, tail forwards), the last bf16 cast, the feature-level tail's gradient block (a function of the plan)
+        self.forwards, self.delivered, self._plan, self._now, self._cast, self.tail_block = [], [], None, [], None, None
+        self._mp = monkeypatch
         E, rec = engine, self
         sync = torch.cuda.synchronize if values else (lambda: None)
         host = self._h = to_host if values else (lambda t: None)
@@ -438,7 +593,7 @@ class Recorder:
 
         def bn_bwd(P, bn, y, z, ms, dz, act, slope, dres=None, dres_acc=False, has_res=True):
             sync()
-            call = {"kind": "bn", "key": y, "dz": host(dz), "dres_old": host(dres) if dres is not None and dres_acc else None,
+            call = {"kind": "bn", "plan": P, "key": y, "dz": host(dz), "dres_old": host(dres) if dres is not None and dres_acc else None,
                     "fused": id(y) in P._bnb}
             rec._mask = None
             out = bn_orig(P, bn, y, z, ms, dz, act, slope, dres, dres_acc, has_res)
@@ -450,7 +605,7 @@ class Recorder:
         def conv_bwd(P, conv, d, x, dy, dx=None, dx_acc=False, dbias=None, prev=None):
             sync()
             up = isinstance(dx, E.UpGrad)
-            call = {"kind": "conv", "key": conv, "dy": host(dy), "gw_old": host(P.gw(conv)),
+            call = {"kind": "conv", "plan": P, "key": conv, "dy": host(dy), "gw_old": host(P.gw(conv)),
                     "gb_old": host(P.gvec(conv, "bias")) if conv.bias is not None else None,
                     "dx_kind": None if dx is None else "upgrad" if up else "pair" if isinstance(dx, tuple) else "plain",
                     "dx_old": host(dx) if dx_acc and torch.is_tensor(dx) else None, "da_old": host(dx.da) if up and dx.acc else None}
@@ -485,6 +640,200 @@ class Recorder:
 
         monkeypatch.setattr(E.K, "bn_bwd_apply", bn_bwd_apply)
         monkeypatch.setattr(E.K, "bn_bwd_apply_recompute", bn_bwd_apply_recompute)
+        if values:
+            self._wrap_tails(monkeypatch, sync, host)
+
+    def _wrap_tails(self, monkeypatch, sync, host):
+        """What the discriminators run around Plan.conv_bwd / Plan.bn_bwd: the in-place act_bwd, the two pooled tails, the eval layers,
+        the delivery of a gradient arena.  A kernel entry point does not know its plan: Plan.begin_backward names the one whose
+        backward is running, the forward in progress (watch) collects what its own calls note."""
+        E, rec = self.E, self
+        begin_orig, act_orig, eval_orig, deliver_orig = E.Plan.begin_backward, E.K.act_bwd, E.Plan._conv_bn_act_eval, E.ArenaModule.deliver_grads
+        cast_orig = E.K.cast_to_bf16
+
+        def begin_backward(P):
+            rec._plan = P
+            return begin_orig(P)
+
+        def act_bwd(dz, z, dy, act, slope, st=None):
+            sync()
+            call = {"kind": "act", "plan": rec._plan, "key": z, "dz": host(dz), "act": act, "slope": slope}
+            act_orig(dz, z, dy, act, slope, st)
+            sync()
+            call["dy"] = host(dy)
+            rec.calls.append(call)
+
+        def tail_bwd(orig, sigmoid):
+            def wrapped(dp, *a):
+                p, (pooled, w, dz, dw, db) = (a[0], a[1:6]) if sigmoid else (None, a[0:5])
+                sync()
+                P = rec._plan
+                block = rec.tail_block(P) if rec.tail_block is not None else None
+                call = {"kind": "tail", "plan": P, "key": pooled, "sigmoid": sigmoid, "dp": host(dp).reshape(-1), "gw_old": host(dw), "gb_old": host(db)[:1],
+                        "block_old": host(block)}
+                orig(dp, *a)
+                sync()
+                call.update(dz=host(dz), gw=host(dw), gb=host(db)[0], block=host(block))
+                rec.calls.append(call)
+            return wrapped
+
+        def tail_fwd(orig, sigmoid):
+            def wrapped(z, w, b, st=None):
+                out, pooled = orig(z, w, b, st)
+                sync()
+                rec._now.append({"kind": "tail_fwd", "key": pooled, "sigmoid": sigmoid, "bf16": z.dtype == torch.bfloat16, "z": host(z),
+                                 "w": host(w), "b": host(b)[:1], "pooled": host(pooled), "out": host(out).reshape(-1)})
+                return out, pooled
+            return wrapped
+
+        def cast_to_bf16(x, out=None, st=None):
+            rec._cast = cast_orig(x, out, st)
+            return rec._cast
+
+        def conv_bn_act_eval(P, conv, bn, d, x, bias, act, slope, residual):
+            sync()
+            off, c = P._fold_off, bn.c
+            o, nel, shp = P.idx[(id(conv), "weight")]
+            ev = {"kind": "eval", "plan": P, "key": conv, "bn": bn, "x": rec._inp(x), "k": conv.k, "stride": conv.stride, "pad": conv.pad,
+                  "w32": host(P.net._arena[o:o + nel].view(shp)), "bias": host(bias), "gamma": host(P.pvec(bn, "weight"))[:c],
+                  "beta": host(P.pvec(bn, "bias"))[:c], "rm": host(bn.running_mean), "rv": host(bn.running_var), "eps": bn.eps, "act": act,
+                  "slope": slope, "residual": host(residual), "storage": "bf16" if P.bf16 else "fp32"}
+            rec._cast = None
+            z = eval_orig(P, conv, bn, d, x, bias, act, slope, residual)
+            sync()
+            ev.update(wf=host(P.fold_w[o:o + nel].view(shp)), bf=host(P.fold_b[off:off + E.ceil4(c)]), z=host(z),
+                      wf16=host(rec._cast.view(shp)) if P.bf16 and rec._cast is not None else None)
+            rec._now.append(ev)
+            return z
+
+        def deliver_grads(net, garena):
+            sync()
+            rec.delivered.append((net, host(garena)))          # before the original adds it onto an earlier one
+            return deliver_orig(net, garena)
+
+        monkeypatch.setattr(E.Plan, "begin_backward", begin_backward)
+        monkeypatch.setattr(E.K, "act_bwd", act_bwd)
+        monkeypatch.setattr(E.K, "gap_linear_sigmoid_bwd", tail_bwd(E.K.gap_linear_sigmoid_bwd, True))
+        monkeypatch.setattr(E.K, "gap_linear_bwd", tail_bwd(E.K.gap_linear_bwd, False))
+        monkeypatch.setattr(E.K, "gap_linear_sigmoid_fwd", tail_fwd(E.K.gap_linear_sigmoid_fwd, True))
+        monkeypatch.setattr(E.K, "gap_linear_fwd", tail_fwd(E.K.gap_linear_fwd, False))
+        monkeypatch.setattr(E.K, "cast_to_bf16", cast_to_bf16)
+        monkeypatch.setattr(E.Plan, "_conv_bn_act_eval", conv_bn_act_eval)
+        monkeypatch.setattr(E.ArenaModule, "deliver_grads", deliver_grads)
+
+    def _inp(self, x):
+        E, host = self.E, self._h
+        if isinstance(x, E.UpCat):
+            return Inp("upcat", a=self._inp(x.a), skip=host(x.skip))
+        if isinstance(x, E.LazyAct):
+            return Inp("lazy", y=host(x.y), scale=host(x.scale), shift=host(x.shift), act=x.act, slope=x.slope)
+        return Inp("plain", t=host(x))
+
+    def watch(self, net):
+        """Wrap ``_forward_plan`` on this discriminator (through monkeypatch): every forward leaves {"net", "tape", "out", "events" (its
+        eval layers and its tail's forward), "bn": the BatchNorm buffers before and after} in ``self.forwards``; debug_keep_tape makes
+        Plan.keep_grads hold."""
+        rec, host, orig = self, self._h, net._forward_plan
+        self._mp.setattr(net, "debug_keep_tape", True, raising=False)
+        names = {n: m for n, m in net.named_modules() if isinstance(m, self.E.BNP)}
+        state = lambda: {n: (host(m.running_mean), host(m.running_var), int(m.num_batches_tracked)) for n, m in names.items()}  # noqa: E731
+
+        def forward_plan(x, save):
+            torch.cuda.synchronize()
+            before, rec._now = state(), []
+            out, tape = orig(x, save)
+            torch.cuda.synchronize()
+            rec.forwards.append({"net": net, "tape": tape, "out": host(out), "events": rec._now, "training": net.training,
+                                 "bn": (before, state())})
+            rec._now = []
+            return out, tape
+
+        self._mp.setattr(net, "_forward_plan", forward_plan, raising=False)
+        return net
+
+    # -- the discriminators' tapes, in the form of ``tape`` below
+    def _of(self, f, records, tail_layer, first=None):
+        """Layers, calls, tail of one training forward ``f`` of a watched discriminator.  records: [(ConvRecord, name)]; first: (Layer of
+        the BatchNorm-less first convolution, its module, its stored output)."""
+        host, net, P = self._h, f["net"], f["tape"][0]
+        sd = {k: host(v) for k, v in net.state_dict().items()}
+        names = {id(m): n for n, m in net.named_modules()}
+        storage = "bf16" if P.bf16 else "fp32"
+
+        def conv_fields(conv):
+            nm = names[id(conv)]
+            return dict(name=nm, k=conv.k, stride=conv.stride, pad=conv.pad, w=np.ascontiguousarray(sd[nm + ".weight"].transpose(0, 2, 3, 1)),
+                        bias=sd[nm + ".bias"] if conv.bias is not None else None, storage=storage)
+
+        layers, by = {}, {}
+        if first is not None:
+            conv0, d0, x4, a0 = first
+            route, _ = P.fwd_route(conv0, d0, x4, (self.E.FRAG_BNIN, self.E.FRAG, self.E.IGEMM))
+            L = Layer(x=self._inp(x4), y=host(a0), route=route, fused_act=N.LEAKY, fused_slope=float(self.act_slope), **conv_fields(conv0))
+            layers[L.name] = L
+            by[id(conv0)], by[id(a0)] = L.name, L.name
+        for r in records:
+            bn = names[id(r.bn)]
+            L = Layer(x=self._inp(r.x), y=host(r.y), z=host(r.z), mean=host(r.mean), rstd=host(r.rstd), gamma=sd[bn + ".weight"],
+                      beta=sd[bn + ".bias"], eps=r.bn.eps, act=r.act, slope=r.slope, route=r.route, bn_name=bn, **conv_fields(r.conv))
+            layers[L.name] = L
+            by[id(r.y)], by[id(r.conv)] = L.name, L.name
+        calls, tail = [], next(dict(e) for e in f["events"] if e["kind"] == "tail_fwd")
+        pooled = tail.pop("key")
+        tail.update(layer=tail_layer, dp=None)
+        for call in self.calls:
+            if call.get("plan") is not P:
+                continue
+            call = dict(call)
+            key = call.pop("key")
+            call.pop("plan")
+            if call["kind"] == "tail":
+                assert key is pooled, "a tail backward on another forward's pooled vector"
+                tail.update({k: v for k, v in call.items() if k not in ("kind", "sigmoid")})
+                continue
+            call["layer"] = by[id(key)]
+            calls.append(call)
+        return {"layers": layers, "pool": None, "calls": calls, "tail": tail, "out": f["out"], "bf16": P.bf16}
+
+    act_slope = 0.2          # discriminator.SLOPE, the slope of the image-level network's LeakyReLUs
+
+    def image_tape(self, f):
+        """The step of one training forward of the image-level discriminator: tape (P, (conv0, d0, x4, a0), recs, (lin, h, pooled, p))."""
+        P, first, recs, (lin, h, pooled, p) = f["tape"]
+        return self._of(f, recs, {id(m): n for n, m in f["net"].named_modules()}[id(lin)], first)
+
+    def feature_tape(self, f):
+        """The step of one training forward of the feature-level discriminator: tape (P, recs, (last, h, pooled))."""
+        P, recs, (last, h, pooled) = f["tape"]
+        return self._of(f, recs, {id(m): n for n, m in f["net"].named_modules()}[id(last)])
+
+    def eval_tape(self, f):
+        """An eval forward of a watched discriminator: its folded layers and its tail's forward."""
+        names = {id(m): n for n, m in f["net"].named_modules()}
+        evals = []
+        for e in f["events"]:
+            if e["kind"] == "eval":
+                e = dict(e)
+                e["layer"] = names[id(e.pop("key"))]
+                e.pop("plan"), e.pop("bn")
+                evals.append(e)
+        tail = next(dict(e) for e in f["events"] if e["kind"] == "tail_fwd")
+        tail.pop("key")
+        tail.update(layer=names[id(f["net"]._layers()[-1])], dp=None)
+        return {"evals": evals, "tail": tail, "out": f["out"]}
+
+    def running(self, net, forwards):
+        """check_running's records of a watched network after its training ``forwards`` (in forward order), one per BatchNorm."""
+        names = {id(m): n for n, m in net.named_modules()}
+        out = []
+        for i, r in enumerate(forwards[0]["tape"][2] if len(forwards[0]["tape"]) == 4 else forwards[0]["tape"][1]):
+            bn = names[id(r.bn)]
+            ys = [self._h((f["tape"][2] if len(f["tape"]) == 4 else f["tape"][1])[i].y) for f in forwards]
+            rm0, rv0, nbt0 = forwards[0]["bn"][0][bn]
+            rm, rv, nbt = forwards[-1]["bn"][1][bn]
+            out.append({"layer": bn, "ys": ys, "eps": r.bn.eps, "momentum": r.bn.momentum, "bf16": forwards[0]["tape"][0].bf16,
+                        "rm0": rm0, "rv0": rv0, "nbt0": nbt0, "rm": rm, "rv": rv, "nbt": nbt})
+        return out
 
     def _noting(self, fn, route):
         def wrapped(*a, **kw):
@@ -529,8 +878,11 @@ class Recorder:
             by_y[id(r.y)], by_conv[id(r.conv)] = L.name, L.name
         calls = []
         for call in self.calls:
+            if call["kind"] not in ("bn", "conv"):
+                continue
             call = dict(call)
             key = call.pop("key")
+            call.pop("plan")
             if call["kind"] == "conv" and key is head:
                 hx = inp(h_last)
                 d = d_head
